@@ -9,7 +9,12 @@ across the ranks (configs[3]: strong scaling) with ONE all-reduce of the per-gen
 per train pass on the device (one-shot peer-to-peer over xGMI, else RCCL).  A run whose data path
 would fall back to the host exits non-zero unless --allow-host-fallback is given.
 
+A plain run sets up, warms up, times --steps iterations in one region and prints the headline line (--dump-outputs DIR also writes
+what the timed call computed); --full adds everything else this file measures (roofline and per-kernel figures, the steady-state
+region, the default fit's wall-clock, the other configurations, the CPU baselines and the parity check, the multi-rank extras).
+
   python bench.py --gpus 1 --steps 50 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -84,6 +89,41 @@ def run_agreed_calls(call, budget_ms, dist=None):
     for _ in range(n - 1):
         call()
     return n
+
+
+DUMP_MAX_BYTES = 64 << 20
+CELL_PARAMS = ("clone_probs", "s", "psi")   # the per-cell arrays of get_params(); the others are per gene or per clone
+
+
+def dump_outputs(outdir, eng, last_elbo, seed, rank=0, world=1, dist=None):
+    """--dump-outputs: what the timed ca_iterate call leaves its caller -- the last ELBO it returned and the fitted parameters (get_params,
+    R/inference-tflow.R:424-434) -- as DIR/<name>.npy in float64.  Every rank calls this: at world > 1 the per-cell arrays of the shards
+    are gathered on rank 0 in rank order (cell_range: contiguous shards).  When the files would pass 64 MB in all, the per-cell arrays keep
+    a fixed, seeded sample of the cells, in cell order, whose indices are written as cell_index.npy."""
+    params = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in eng.get_params().items()}
+    cells = [k for k in CELL_PARAMS if k in params]
+    if world > 1:
+        box = [None] * world
+        dist.all_gather_object(box, {k: params[k] for k in cells})
+        if rank != 0:
+            return
+        for k in cells:
+            params[k] = np.concatenate([b[k] for b in box], axis=0)
+    out = {"elbo": np.array([last_elbo], dtype=np.float64), **params}
+    total = sum(v.nbytes for v in out.values())
+    room = DUMP_MAX_BYTES - 1024 * (len(out) + 1)                    # (each file's .npy header, cell_index's included)
+    if total > room:
+        n = params[cells[0]].shape[0]
+        row = sum(params[k][:1].nbytes for k in cells) + 8            # (+ the row's entry in cell_index)
+        keep = (room - (total - n * (row - 8))) // row
+        if keep < 1:
+            raise SystemExit(f"bench.py --dump-outputs: the per-gene outputs alone pass {DUMP_MAX_BYTES >> 20} MB")
+        idx = np.sort(np.random.default_rng(seed).choice(n, int(keep), replace=False))
+        out.update({k: np.ascontiguousarray(params[k][idx]) for k in cells})
+        out["cell_index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(outdir, f"{k}.npy"), v)
 
 
 def pmc_traffic(build_id, kernel_class):
@@ -388,15 +428,23 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)   # the reference's default max_iter
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="the --steps long timed region is run this many times; value = median region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline and per-kernel figures, the steady-state region, the default fit's "
+                         "wall-clock, the other configurations, the CPU baselines and the parity check, the multi-rank extras; without it a run "
+                         "sets up, warms up, times --steps steps and prints the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed call left a caller (its last ELBO and the fitted parameters) as DIR/<name>.npy, "
+                         "float64; at most 64 MB (a fixed, seeded sample of the cells above that)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the --steps long timed region is run this many times; value = median region (default 1, with --full 5)")
     ap.add_argument("--cells", type=int, default=100_000)
     ap.add_argument("--genes", type=int, default=5_000)
     ap.add_argument("--clones", type=int, default=8)
     ap.add_argument("--latent", type=int, default=1)
     ap.add_argument("--y-storage", default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the parity check")
     ap.add_argument("--cpu-sample-cells", type=int, default=0,
-                    help="cells handed to the CPU baseline; 0 = all of them when the host has 10x the matrix free, else 65536")
+                    help="--full: cells handed to the CPU baseline; 0 = all of them when the host has 10x the matrix free, else 65536")
     ap.add_argument("--seed", type=int, default=20243)
     ap.add_argument("--collective", default="auto", choices=["auto", "p2p", "rccl", "host"],
                     help="data-path all-reduce at --gpus > 1: auto = one-shot peer-to-peer, else RCCL")
@@ -404,11 +452,16 @@ def main():
                     help="at --gpus > 1, let the run continue on the gloo host all-reduce when no device transport comes up "
                          "(the result is then NOT a measurement of the device data path)")
     ap.add_argument("--selftest-fail", default="", help="test hook: treat the known-answer all-reduce test of this transport (p2p | rccl) as failed on rank 0")
-    ap.add_argument("--preheat-ms", type=float, default=60.0,
-                    help="untimed iterations run for this long right before the timed regions (after the --warmup steps): the GPU's clocks need "
-                         "~30 ms of load to ramp; 0 = none")
+    ap.add_argument("--preheat-iters", type=int, default=-1,
+                    help="untimed iterations right before the timed regions (after the --warmup steps): the GPU's clocks need ~30 ms of load to ramp "
+                         "(400 iterations are ~70 ms at the headline shape).  A count, not a time, so that the state the timed steps start from -- "
+                         "and what --dump-outputs writes -- is the same from run to run.  -1 = one --steps call's worth, at least 400 and at most "
+                         "20000 iterations; 0 = none")
+    ap.add_argument("--preheat-ms", type=float, default=0.0,
+                    help="instead of --preheat-iters: untimed --steps long calls for this long (the count agreed over the ranks; the state the "
+                         "timed steps start from then depends on the clock)")
     ap.add_argument("--busy-seconds", type=float, default=4.0,
-                    help="untimed iterations run for this long after the measurements (single GPU), so that a coarse GPU-utilisation sampler sees the device at work")
+                    help="--full: untimed iterations run for this long after the measurements (single GPU), so that a coarse GPU-utilisation sampler sees the device at work")
     ap.add_argument("--allow-foreign-lib", action="store_true",
                     help="run a library whose ca_build_id() is not the tree's (CLONEALIGN_HIP_LIB timing builds; labelled in the output)")
     ap.add_argument("--no-live-events", action="store_true",
@@ -417,21 +470,25 @@ def main():
     ap.add_argument("--variant-on", default="", help="comma-separated opt-in engine variants (engine.VARIANTS_ON), for A/B runs")
     ap.add_argument("--tune", default="", help="comma-separated name=value decomposition overrides (engine.TUNE), for A/B runs")
     ap.add_argument("--steady-steps", type=int, default=-1,
-                    help="length of the extra one-region steady-state measurement after the headline regions; -1 = 200 unless --steps is 200 "
+                    help="--full: length of the extra one-region steady-state measurement after the headline regions; -1 = 200 unless --steps is 200 "
                          "or a profiler is attached (its launches would mix into the per-launch statistics), 0 = none")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the 200-step regions of the other single-GPU BASELINE configurations (cfg-2, one cfg-5 restart, the 12.5k-cell shard) "
+                    help="--full: skip the 200-step regions of the other single-GPU BASELINE configurations (cfg-2, one cfg-5 restart, the 12.5k-cell shard) "
                          "and of the VALU fallback shapes that follow the headline measurement (single GPU only)")
     ap.add_argument("--through-api", action="store_true",
                     help="run the workload as ONE fit cell-sharded over --gpus devices INSIDE THIS PROCESS (the device group behind "
                          "inference_tflow(devices=) / C_clonealign_fit(devices)) instead of one process per GPU; no launcher is used or needed")
     ap.add_argument("--no-through-api-leg", action="store_true",
-                    help="at --gpus > 1 (one process per GPU): skip the extra measurement in which rank 0, after the headline, runs the same workload "
+                    help="--full at --gpus > 1 (one process per GPU): skip the extra measurement in which rank 0, after the headline, runs the same workload "
                          "through the in-process device group over all the devices")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.repeats is None:
+        args.repeats = 5 if (args.full or args.through_api) else 1
     if args.through_api:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is not supported with --through-api")
         if int(os.environ.get("WORLD_SIZE", "1")) != 1:
             raise SystemExit("bench.py --through-api is ONE process driving --gpus devices: run it bare, not under a launcher")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -609,7 +666,7 @@ def main():
     # The CPU baseline's copy of the counts is taken AFTER the GPU measurements (the generated matrix stays on the device until
     # then): fetching and converting 2 GB here left the GPU idle for seconds in front of the timed region, and W = 5 warm-up
     # iterations (1.7 ms) do not bring its clocks back -- the driver-style run read 3 % low whenever the baseline was on.
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = rank == 0 and world == 1 and args.full and not args.no_cpu_baseline
     # The generated int32 matrix (2 GB at cfg-3) is dropped before anything is timed, ALSO when the CPU baseline will want its counts: kept alive beside the
     # engine it made the 20-step regions read 2 % low (188.4 against 184.3 us per iteration on one box, with and without --no-cpu-baseline; round 6).  The
     # baseline's leg generates it again from the same seed after the measurements (its parity check against the engine would show any difference).
@@ -619,21 +676,22 @@ def main():
     rng = np.random.default_rng(args.seed + 2 + 0)   # same eps on every rank
     eps0 = rng.normal(size=(1, G)).astype(np.float32)
     eng.gamma_init(eps0)
-    # --- warmup (+ find the dominant kernel class with all classes timed)
-    eng.set_profile(0x1F)
+    # --- warmup (--full: + find the dominant kernel class with all classes timed)
+    eng.set_profile(0x1F if args.full else 0)
     eps_w = rng.normal(size=(2 * max(args.warmup, 1), 1, G)).astype(np.float32)
     eng.iterate(max(args.warmup, 1), eps_w)
-    kt = eng.kernel_times(reset=True)
-    dominant = max(("fwd", "bwd", "ypass"), key=lambda k: kt[k][0])
-    if info.get("fwd_series") and kt["ypass"][0] > 0:
-        # the series form: the count-matrix stream is the one launch whose work is proportional to the matrix (HBM-bound); the "fwd" class there is a handful of
-        # small launches and the cell kernel, with no flop count of the reference's formulation to price them against -- at 2+ ranks (half the matrix per rank)
-        # their summed warm-up time can edge past the stream's, and the sweeps' flop roofline would be quoted for kernels that do not execute those flops
-        dominant = "ypass"
-    kid = {"fwd": 0, "bwd": 1, "ypass": 2}[dominant]
-    # live HIP events around every 8th launch of the dominant class (an event pair costs the stream 5-6 us: 1.6 % at cfg-3, 9 % at
-    # cfg-2 when every launch is timed -- measured with --no-live-events; sampled, the timed region is left alone)
-    eng.set_profile(0 if args.no_live_events else (1 << kid) | ((EVENT_STRIDE - 1) << 8))
+    if args.full:
+        kt = eng.kernel_times(reset=True)
+        dominant = max(("fwd", "bwd", "ypass"), key=lambda k: kt[k][0])
+        if info.get("fwd_series") and kt["ypass"][0] > 0:
+            # the series form: the count-matrix stream is the one launch whose work is proportional to the matrix (HBM-bound); the "fwd" class there is a handful of
+            # small launches and the cell kernel, with no flop count of the reference's formulation to price them against -- at 2+ ranks (half the matrix per rank)
+            # their summed warm-up time can edge past the stream's, and the sweeps' flop roofline would be quoted for kernels that do not execute those flops
+            dominant = "ypass"
+        kid = {"fwd": 0, "bwd": 1, "ypass": 2}[dominant]
+        # live HIP events around every 8th launch of the dominant class (an event pair costs the stream 5-6 us: 1.6 % at cfg-3, 9 % at
+        # cfg-2 when every launch is timed -- measured with --no-live-events; sampled, the timed region is left alone)
+        eng.set_profile(0 if args.no_live_events else (1 << kid) | ((EVENT_STRIDE - 1) << 8))
     eps_t = draws_for_calls(rng, args.steps, 1, G)   # (2 K + 1 draws: every timed call carries the next call's forward half, K sweeps per K iterations)
 
     def barrier():
@@ -646,8 +704,8 @@ def main():
     #     clocks -- kernel trace of a default run (profiles/r03_v1_timeline.txt): the iteration period falls from
     #     322 us right after an idle gap to 289 us 30 ms later, the merged forward launch from 151 to 135 us.  W = 5 warm-up steps are
     #     1.6 ms of work, and a 20-step timed region is 6 ms: without this the whole region sits on the ramp and measures the power
-    #     management, not the kernels.  The same iterations, the same arguments as the timed call; `preheat_ms` is in the output.
-    #     At world > 1 every ca_iterate call is collective (one all-reduce per pass), so the NUMBER of pre-heat calls must be the same
+    #     management, not the kernels.  The output's `preheat` says how many iterations ran, in how many calls and ms.
+    #     --preheat-ms (calls of --steps iterations for that long): at world > 1 every ca_iterate call is collective (one all-reduce per pass), so the NUMBER of pre-heat calls must be the same
     #     on every rank: one call is timed, the slowest rank's time is agreed on (gloo MAX) and the call count follows from it --
     #     a loop that lets each rank's own clock decide ran one call more on one rank than on its peer (r03: CA_ERR_COMM after 10 s).
     pre_it, pre_calls, t_pre = 0, 0, time.perf_counter()
@@ -656,6 +714,21 @@ def main():
         t_pre = time.perf_counter()
         pre_calls = run_agreed_calls(lambda: eng.iterate(args.steps, eps_t), args.preheat_ms, dist if world > 1 else None)
         pre_it = pre_calls * args.steps
+    elif args.preheat_iters != 0:
+        # --preheat-iters: a fixed number of calls of at most --steps iterations, on draws whose first and last are the timed draws' first -- every
+        # call's carried forward half is picked up by the next one, the first timed region's included (it starts from a carried half like the others).
+        # The time an iteration takes drifts by about 1 % along the fit, so the default is one --steps call (400 to 20000 iterations): the timed region
+        # then starts as far into the fit as behind a time-based pre-heat, which always made at least one such call
+        pre_total = args.preheat_iters if args.preheat_iters > 0 else max(400, min(args.steps, 20000))
+        pre_len = min(args.steps, pre_total)
+        eps_p = draws_for_calls(np.random.default_rng(args.seed + 3), pre_len, 1, G)
+        eps_p[0] = eps_p[-1] = eps_t[0]
+        pre_calls = -(-pre_total // pre_len)
+        barrier()
+        t_pre = time.perf_counter()
+        for _ in range(pre_calls):
+            eng.iterate(pre_len, eps_p)
+        pre_it = pre_calls * pre_len
     else:
         eng.iterate(args.steps, eps_t)   # (one untimed call all the same: the first timed region must start from a carried half like the others)
     pre_ms = (time.perf_counter() - t_pre) * 1e3
@@ -677,13 +750,17 @@ def main():
             dt = float(t[0])
         regions.append(dt)
     dt = float(np.median(regions))
-    kt_timed = eng.kernel_times(reset=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, last, args.seed, rank, world, dist)
+    kt_timed = eng.kernel_times(reset=True) if args.full else None
     info = {**info, **{k: v for k, v in eng.info().items() if k in ("series_passes", "series_fallbacks")}}   # (how the passes so far were carried out)
-    # the same call at the reference's default max_iter = 200 (one region): a ca_iterate call of k steps makes k + 1 forward sweeps
+    # --full: the same call at the reference's default max_iter = 200 (one region): a ca_iterate call of k steps makes k + 1 forward sweeps
     # (first and last carry one draw), so a 20-step region pays 21/20 of the steady-state sweep cost -- this shows the difference
     steady = None
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith("ROCPROF") for k in os.environ)
     steady_steps = args.steady_steps if args.steady_steps >= 0 else (0 if (args.steps == 200 or profiled) else 200)
+    if not args.full:
+        steady_steps = 0
     if steady_steps > 0:
         # (under a profiler this region's 2 x steady_steps iterations -- steady_steps + 1 sweeps per call, another call shape -- would mix into the
         #  per-launch statistics of the --steps regions: off by default there)
@@ -707,7 +784,7 @@ def main():
     # the replicas after everything the timed regions did to them: every rank applied the same all-reduced sums in the same order, so the
     # replicated variables must be bit-identical across ranks (a transport that tears or reorders rarely would show here first)
     replicas_equal = None
-    if world > 1:
+    if world > 1 and args.full:
         import hashlib
         hsh = hashlib.sha1()
         for nm in ("loc", "ls", "W", "alpha_unconstr", "v"):
@@ -717,7 +794,7 @@ def main():
         replicas_equal = len(set(box)) == 1
     # a monitor pass on its own (plain forward + its (3 + C)-double all-reduce + read-back): the latency floor of one collective
     mon_us = None
-    if world > 1:
+    if world > 1 and args.full:
         eng.set_profile(0)
         barrier()
         t1 = time.perf_counter()
@@ -728,7 +805,7 @@ def main():
     # the collective on its own: 200 back-to-back all-reduces of the train pass's payload (15 011 doubles at cfg-4) on the
     # transport in use and -- when it also comes up on every rank -- on RCCL, between two HIP events on the engine's stream
     ar_us = None
-    if world > 1 and collective in ("p2p", "rccl"):
+    if world > 1 and args.full and collective in ("p2p", "rccl"):
         ar_us = {"payload_doubles": int(info["red_n"]), "calls": 200}
         try:
             ar_us[collective] = eng.comm_benchmark(collective, 200)
@@ -759,20 +836,22 @@ def main():
     # second half of the metric ("wall-clock to convergence"): the reference's default fit FROM ITS INITIAL VALUES (ca_reinit:
     # variables, Adam slots and beta powers reset), max_iter = 200, rel_tol = 1e-6, through ca_run (host reads the ELBO every
     # iteration for the window-10 stop rule), then the 20 final ELBOs
-    eng.set_profile(0)
-    eng.reinit(psi0, loc0)
-    barrier()
-    t1 = time.perf_counter()
-    trace = eng.run(None, 200, 1e-6)
-    finals = eng.final_elbo(None, 20)
-    eng.synchronize()
-    fit_s = time.perf_counter() - t1
+    fit_s, trace, finals = None, None, None
+    if args.full:
+        eng.set_profile(0)
+        eng.reinit(psi0, loc0)
+        barrier()
+        t1 = time.perf_counter()
+        trace = eng.run(None, 200, 1e-6)
+        finals = eng.final_elbo(None, 20)
+        eng.synchronize()
+        fit_s = time.perf_counter() - t1
     # every other single-GPU BASELINE configuration on the same clock, after the headline and outside its regions: cfg-2, one
     # restart of cfg-5, the shards of cfg-4 at 8 and 4 GPUs as one-device problems; and the argument space outside the fused loop
     # (mc_samples > 2, more than 16 clones, D = K + P >= 3: vector sweeps up to round 5, matrix-core sweeps since round 6), so that their cost is a number.  Skipped under a profiler (their
     # launches would mix into the per-kernel statistics of the headline shape).
     other, fallbacks = None, None
-    if world == 1 and rank == 0 and not args.no_other_configs and not profiled:
+    if world == 1 and rank == 0 and args.full and not args.no_other_configs and not profiled:
         other, fallbacks = {}, {}
         for nm, kw in (("cfg2", dict(N=10_000, G=2_000, C=4, what="BASELINE.json configs[1]")),
                        ("cfg5_one_restart", dict(N=50_000, G=3_000, C=6, what="one restart of BASELINE.json configs[4]")),
@@ -794,7 +873,7 @@ def main():
     # keep the device demonstrably busy for a few seconds after the measurements (untimed): the timed regions of a 20-step run are
     # 35 ms inside a minute of CPU baseline, which a once-per-few-seconds utilisation sampler around the run never lands on
     busy_s, busy_it = 0.0, 0
-    if world == 1 and args.busy_seconds > 0:
+    if world == 1 and args.full and args.busy_seconds > 0:
         tb = time.perf_counter()
         while time.perf_counter() - tb < args.busy_seconds:
             eng.iterate(args.steps, eps_t)
@@ -808,7 +887,7 @@ def main():
     # path inference_tflow(devices=) / C_clonealign_fit(devices) take, next to the one-process-per-GPU number.  Never part of `value`; an error
     # in it is reported inside the line, it cannot fail the headline.
     api_leg = None
-    if world > 1 and not args.no_through_api_leg:
+    if world > 1 and args.full and not args.no_through_api_leg:
         keep_info = info
         eng.close()
         dist.barrier()
@@ -833,43 +912,7 @@ def main():
 
     if rank == 0:
         build = eng_mod.build_id()
-        ms, launches = kt_timed[dominant] if not args.no_live_events else kt[dominant]
-        per_launch_s = ms / max(launches, 1) * 1e-3
-        ride = bool(info.get("y_ride")) and dominant == "fwd"
-        bound, work = algorithmic_work(dominant, n_loc, G, C, K, bool(info.get("fused_sweep")), args.steps, ride)
-        canonical_work = work
-        if dominant == "ypass":
-            # the count-matrix stream is the dominant launch (series form of the contraction): its roof is HBM, and what it MOVES is the matrix at its
-            # stored width -- the canonical 4 B per count of SURVEY.md section 8d would read as 2.6x the HBM peak (a fraction above one by
-            # construction is not printed); the canonical figure is kept beside it, labelled
-            work = n_loc * G * float(info["y_bytes_per_elem"]) + (n_loc + G) * K * 4.0 * 2
-        if bound == "hbm":
-            achieved, peak, unit = work / per_launch_s / 1e9, PEAK_HBM_GBS, "GB/s"
-        else:
-            achieved, peak, unit = work / per_launch_s / 1e12, PEAK_F32_TFLOPS, "TFLOP/s"
-        same_workload = (N, G, C, K, world) == (100_000, 5_000, 8, 1, 1)
-        traffic, traffic_src = pmc_traffic(build, dominant) if same_workload else (None, None)
-        # the HBM-bound kernel of the iteration (SURVEY.md section 8d asks for both roofs): the Y stream, timed by HIP events on
-        # its own stream during the warmup iterations, where every kernel class is timed
-        ystream = None
-        if K > 0 and (kt["ypass"][1] > 0 or ride):
-            # riding: the stream has no launch of its own -- its bytes are spread over the merged launch's whole duration
-            y_s = per_launch_s if ride else kt["ypass"][0] / kt["ypass"][1] * 1e-3
-            canon = n_loc * G * 4.0 + (n_loc + G) * K * 4.0 * 2
-            ytraffic, ysrc = pmc_traffic(build, "fwd" if ride else "ypass") if same_workload else (None, None)
-            stored = n_loc * G * float(info["y_bytes_per_elem"])
-            ystream = {"bound": "hbm", "kernel": "ypass (blocks inside the forward sweep's launch)" if ride else "ypass",
-                       "achieved": stored / y_s / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": stored / y_s / 1e9 / PEAK_HBM_GBS,
-                       "traffic": ytraffic, "traffic_source": ysrc, "launch_ms": y_s * 1e3, "canonical_bytes": canon, "stored_bytes": stored,
-                       "note": f"physical rate: the {info['y_bytes_per_elem']} B per count the matrix is stored at, over the launch the stream rides in.  (The "
-                               "canonical 4 B per count of SURVEY.md section 8d would read as more than the HBM peak here -- bytes this build does not move; "
-                               "that figure is no longer printed.)  HBM is not what binds this launch: see roofline.binding"}
         step_s = dt / args.steps
-        it_flops = N * G * (8.0 * C + 12.0 * K + 3.0)                       # SURVEY.md section 8d, whole iteration, all ranks
-        it_bytes = N * G * 4.0 + N * (8.0 * C + 6.0 * K + 2.0) * 4.0
-        it_bytes_stored = N * G * float(info["y_bytes_per_elem"]) + N * (8.0 * C + 6.0 * K + 2.0) * 4.0   # the same formula at the stored width
-        meas = [pmc_traffic(build, k)[0] for k in (("ypass", "fwd", "bwd") if dominant == "ypass" else ("fwd", "bwd"))] if same_workload else [None]
-        it_bytes_measured = float(sum(meas)) if all(m is not None for m in meas) else None               # PMC: forward (+ riding Y stream) + backward launch
         out = {
             "metric": "ELBO iterations/sec", "value": args.steps / dt, "unit": "iterations/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": step_s * 1e3,
@@ -890,101 +933,140 @@ def main():
                         "ms_per_step_max": max(regions) / args.steps * 1e3,
                         "what": "the --steps long region timed this many times (barrier + synchronize on both sides each time); "
                                 "value / ms_per_step are the median region"},
-            "roofline": {"bound": bound, "kernel": dominant, "achieved": achieved, "peak": peak, "unit": unit,
-                         "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
-                         **({"bytes_per_launch_stored": work, "bytes_per_launch_canonical_f32": canonical_work,
-                             "series_form": {"passes": int(info.get("series_passes", 0)), "handed_to_the_sweeps": int(info.get("series_fallbacks", 0))}}
-                            if dominant == "ypass" else {}),
-                         "launch_ms": per_launch_s * 1e3, "launches": int(launches),
-                         **({k: v for k, v in (sq_fractions(build, dominant) or {}).items() if k != "file"} if same_workload else {}),
-                         "sq_source": (sq_fractions(build, dominant) or {}).get("file") if same_workload else None,
-                         "event_stride": 1 if args.no_live_events else EVENT_STRIDE,
-                         "binding": ("HBM latency / occupancy of the stream kernel (5.3-5.7 TB/s of the 8 TB/s peak with every CU streaming)" if dominant == "ypass" else
-                                     "vector issue (VALU + MFMA share the SIMD's issue port; valu_active_frac / mfma_busy_frac from the SQ counter pass of this "
-                                     "build; HBM: traffic per launch against launch_ms is ~0.5 of peak)"),
-                         "note": ("the count-matrix stream (Y.W and Y^T.psi on the int8 matrix cores, one pass over the 1-byte matrix) is the iteration's longest launch: "
-                                  "the cells x genes x clones contraction runs in its series form (ca_poly.hip: moments over gene bins, O(N + G) work), so the "
-                                  "O(N G) work left is this stream; achieved = stored bytes / launch time"
-                                  if dominant == "ypass" else
-                                  "algorithmic fp32 flops of the fused two-eps sweep against the fp32 peak; the contraction "
-                                  "itself runs as bf16 hi/lo MFMAs (fp32-accurate), the kernel is bound by VALU issue "
-                                  "(v_exp_f32 + bf16 split)"
-                                  + ("; the Y stream's blocks ride inside this launch (its 4K flop per count are counted, its "
-                                     "512 MB of HBM reads are roofline_ystream's), so launch_ms is sweep + stream"
-                                     if ride else " and shares the GPU with the Y-stream kernel on a side stream")
-                                  + " (DESIGN.md sections 5 and 8); traffic is filled only from a PMC file of THIS build")
-                         if dominant == "fwd" else "traffic is filled only from a PMC file of THIS build"},
-            "roofline_iteration": (
-                {"reference_flops": it_flops, "reference_bytes_canonical": it_bytes,
-                 "reference_roofs_ms": {"fp32": it_flops / (PEAK_F32_TFLOPS * 1e12 * world) * 1e3, "hbm_canonical": it_bytes / (PEAK_HBM_GBS * 1e9 * world) * 1e3},
-                 "measured_ms": step_s * 1e3,
-                 "bytes_stored": it_bytes_stored, "frac_of_hbm_peak_stored": it_bytes_stored / step_s / 1e9 / (PEAK_HBM_GBS * world),
-                 "bytes_measured_pmc": it_bytes_measured,
-                 "frac_of_hbm_peak_measured": None if it_bytes_measured is None else it_bytes_measured / step_s / 1e9 / (PEAK_HBM_GBS * world),
-                 "what": "whole iteration (train + monitor pass).  reference_flops / reference_bytes_canonical are what the REFERENCE's formulation costs (SURVEY.md section 8d: "
-                         "N G (8C + 12K + 3) flop, float32 counts) and reference_roofs_ms the time either roof allows for it; the measured iteration is shorter than both "
-                         "because the series form of the contraction (ca_poly.hip) executes O(N + G) work instead of the N G C flops and the matrix is held at one byte "
-                         "per count -- so no fraction of those roofs is quoted (it would exceed one by construction).  What the iteration is bound by: one pass over the stored "
-                         "matrix (frac_of_hbm_peak_stored) plus a chain of small launches (DESIGN.md section 5e)"}
-                if (info.get("fwd_series") and info.get("series_passes", 0) > 0) else
-                {"flops": it_flops, "bytes_canonical": it_bytes,
-                 "achieved_TFLOPs": it_flops / step_s / 1e12,
-                 "frac_of_fp32_peak": it_flops / step_s / 1e12 / (PEAK_F32_TFLOPS * world),
-                 "achieved_GBps_canonical": it_bytes / step_s / 1e9,
-                 "frac_of_hbm_peak_canonical": it_bytes / step_s / 1e9 / (PEAK_HBM_GBS * world),
-                 "bytes_stored": it_bytes_stored,
-                 "frac_of_hbm_peak_stored": it_bytes_stored / step_s / 1e9 / (PEAK_HBM_GBS * world),
-                 "bytes_measured_pmc": it_bytes_measured,
-                 "frac_of_hbm_peak_measured": None if it_bytes_measured is None else it_bytes_measured / step_s / 1e9 / (PEAK_HBM_GBS * world),
-                 "what": "whole iteration (train + monitor pass) against both roofs: N G (8C + 12K + 3) flop and "
-                         "N G 4 + N (8C + 6K + 2) 4 canonical bytes (SURVEY.md section 8d) over ms_per_step.  The canonical bytes are an "
-                         "accounting convention (float32 counts): bytes_stored is the same formula at the width the matrix is held at, "
-                         "bytes_measured_pmc the two sweeps' HBM traffic from the PMC pass of this build -- what the memory system actually moves"}),
-            "kernel_ms_per_iter_warmup": {k: v[0] / max(args.warmup, 1) for k, v in kt.items()},
-            "roofline_ystream": ystream,
             "final_elbo": last,
-            "fit_wallclock": {"seconds": fit_s, "iterations": int(len(trace) - 1), "max_iter": 200, "rel_tol": 1e-6,
-                              "final_elbo_mean": float(np.mean(finals)), "from_initial_values": True,
-                              "what": "ca_reinit (initial values, fresh Adam state), ca_run + 20 final ELBOs, eps generated by the "
-                                      "built-in Philox stream (inside the time)"},
         }
         out["preheat"] = {"ms": pre_ms, "iterations": pre_it, "calls": pre_calls,
-                          "what": "untimed iterations between the --warmup steps and the timed regions (clock ramp; see --preheat-ms)"}
-        if steady is not None:
-            out["steady_state_200"] = steady
-        if other is not None:
-            out["other_configs"] = other
-            out["fallbacks"] = fallbacks
-        if busy_it:
-            out["untimed_busy_tail"] = {"seconds": busy_s, "iterations": busy_it, "it_per_s": busy_it / busy_s,
-                                        "what": "untimed ca_iterate calls after the measurements (see --busy-seconds); not part of value"}
-        if replicas_equal is not None:
-            out["replicas_bit_identical_after_timed_regions"] = replicas_equal
-        if mon_us is not None:
-            out["monitor_pass_us_with_collective"] = mon_us
-        if ar_us is not None:
-            out["allreduce_us"] = ar_us
-        if api_leg is not None:
-            out["through_api"] = api_leg
-        if want_cpu:
-            n_cpu = args.cpu_sample_cells
-            if n_cpu <= 0:
-                import psutil
-                n_cpu = n_loc if psutil.virtual_memory().available > 10 * 8 * n_loc * G else 65536
-            Yd, _aux2 = synth.make_problem_torch(N, G, C, seed=args.seed, rows=(lo, hi), device=f"cuda:{local_rank}")   # (the same counts as above: same seed)
-            Ysample = Yd[:min(n_cpu, n_loc)].cpu().numpy().astype(np.float64)
-            del Yd, _aux2
-            torch.cuda.empty_cache()
-            try:
-                out["parity_check"] = parity_check(eng, Ysample, aux["L"], psi0[:Ysample.shape[0]], loc0, K) if Ysample.shape[0] == n_loc else {
-                    "skipped": "the host has no room for the full matrix in float64; tests/test_gpu_scale.py holds the at-size check"}
-            except Exception as ex:  # noqa: BLE001
-                out["parity_check"] = {"error": str(ex)[:300]}
-            out["cpu_baseline"] = cpu_baseline(Ysample, aux["L"], psi0, loc0, K, N)
-            try:
-                out["cpu_ref_dataflow"] = cpu_ref_dataflow()
-            except Exception as ex:  # noqa: BLE001
-                out["cpu_ref_dataflow"] = {"error": str(ex)}
+                          "what": "untimed iterations between the --warmup steps and the timed regions (clock ramp; see --preheat-iters, --preheat-ms)"}
+        if args.full:
+            ms, launches = kt_timed[dominant] if not args.no_live_events else kt[dominant]
+            per_launch_s = ms / max(launches, 1) * 1e-3
+            ride = bool(info.get("y_ride")) and dominant == "fwd"
+            bound, work = algorithmic_work(dominant, n_loc, G, C, K, bool(info.get("fused_sweep")), args.steps, ride)
+            canonical_work = work
+            if dominant == "ypass":
+                # the count-matrix stream is the dominant launch (series form of the contraction): its roof is HBM, and what it MOVES is the matrix at its
+                # stored width -- the canonical 4 B per count of SURVEY.md section 8d would read as 2.6x the HBM peak (a fraction above one by
+                # construction is not printed); the canonical figure is kept beside it, labelled
+                work = n_loc * G * float(info["y_bytes_per_elem"]) + (n_loc + G) * K * 4.0 * 2
+            if bound == "hbm":
+                achieved, peak, unit = work / per_launch_s / 1e9, PEAK_HBM_GBS, "GB/s"
+            else:
+                achieved, peak, unit = work / per_launch_s / 1e12, PEAK_F32_TFLOPS, "TFLOP/s"
+            same_workload = (N, G, C, K, world) == (100_000, 5_000, 8, 1, 1)
+            traffic, traffic_src = pmc_traffic(build, dominant) if same_workload else (None, None)
+            # the HBM-bound kernel of the iteration (SURVEY.md section 8d asks for both roofs): the Y stream, timed by HIP events on
+            # its own stream during the warmup iterations, where every kernel class is timed
+            ystream = None
+            if K > 0 and (kt["ypass"][1] > 0 or ride):
+                # riding: the stream has no launch of its own -- its bytes are spread over the merged launch's whole duration
+                y_s = per_launch_s if ride else kt["ypass"][0] / kt["ypass"][1] * 1e-3
+                canon = n_loc * G * 4.0 + (n_loc + G) * K * 4.0 * 2
+                ytraffic, ysrc = pmc_traffic(build, "fwd" if ride else "ypass") if same_workload else (None, None)
+                stored = n_loc * G * float(info["y_bytes_per_elem"])
+                ystream = {"bound": "hbm", "kernel": "ypass (blocks inside the forward sweep's launch)" if ride else "ypass",
+                           "achieved": stored / y_s / 1e9, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": stored / y_s / 1e9 / PEAK_HBM_GBS,
+                           "traffic": ytraffic, "traffic_source": ysrc, "launch_ms": y_s * 1e3, "canonical_bytes": canon, "stored_bytes": stored,
+                           "note": f"physical rate: the {info['y_bytes_per_elem']} B per count the matrix is stored at, over the launch the stream rides in.  (The "
+                                   "canonical 4 B per count of SURVEY.md section 8d would read as more than the HBM peak here -- bytes this build does not move; "
+                                   "that figure is no longer printed.)  HBM is not what binds this launch: see roofline.binding"}
+            it_flops = N * G * (8.0 * C + 12.0 * K + 3.0)                       # SURVEY.md section 8d, whole iteration, all ranks
+            it_bytes = N * G * 4.0 + N * (8.0 * C + 6.0 * K + 2.0) * 4.0
+            it_bytes_stored = N * G * float(info["y_bytes_per_elem"]) + N * (8.0 * C + 6.0 * K + 2.0) * 4.0   # the same formula at the stored width
+            meas = [pmc_traffic(build, k)[0] for k in (("ypass", "fwd", "bwd") if dominant == "ypass" else ("fwd", "bwd"))] if same_workload else [None]
+            it_bytes_measured = float(sum(meas)) if all(m is not None for m in meas) else None               # PMC: forward (+ riding Y stream) + backward launch
+            out.update({
+                "roofline": {"bound": bound, "kernel": dominant, "achieved": achieved, "peak": peak, "unit": unit,
+                             "frac": achieved / peak, "traffic": traffic, "traffic_source": traffic_src,
+                             **({"bytes_per_launch_stored": work, "bytes_per_launch_canonical_f32": canonical_work,
+                                 "series_form": {"passes": int(info.get("series_passes", 0)), "handed_to_the_sweeps": int(info.get("series_fallbacks", 0))}}
+                                if dominant == "ypass" else {}),
+                             "launch_ms": per_launch_s * 1e3, "launches": int(launches),
+                             **({k: v for k, v in (sq_fractions(build, dominant) or {}).items() if k != "file"} if same_workload else {}),
+                             "sq_source": (sq_fractions(build, dominant) or {}).get("file") if same_workload else None,
+                             "event_stride": 1 if args.no_live_events else EVENT_STRIDE,
+                             "binding": ("HBM latency / occupancy of the stream kernel (5.3-5.7 TB/s of the 8 TB/s peak with every CU streaming)" if dominant == "ypass" else
+                                         "vector issue (VALU + MFMA share the SIMD's issue port; valu_active_frac / mfma_busy_frac from the SQ counter pass of this "
+                                         "build; HBM: traffic per launch against launch_ms is ~0.5 of peak)"),
+                             "note": ("the count-matrix stream (Y.W and Y^T.psi on the int8 matrix cores, one pass over the 1-byte matrix) is the iteration's longest launch: "
+                                      "the cells x genes x clones contraction runs in its series form (ca_poly.hip: moments over gene bins, O(N + G) work), so the "
+                                      "O(N G) work left is this stream; achieved = stored bytes / launch time"
+                                      if dominant == "ypass" else
+                                      "algorithmic fp32 flops of the fused two-eps sweep against the fp32 peak; the contraction "
+                                      "itself runs as bf16 hi/lo MFMAs (fp32-accurate), the kernel is bound by VALU issue "
+                                      "(v_exp_f32 + bf16 split)"
+                                      + ("; the Y stream's blocks ride inside this launch (its 4K flop per count are counted, its "
+                                         "512 MB of HBM reads are roofline_ystream's), so launch_ms is sweep + stream"
+                                         if ride else " and shares the GPU with the Y-stream kernel on a side stream")
+                                      + " (DESIGN.md sections 5 and 8); traffic is filled only from a PMC file of THIS build")
+                             if dominant == "fwd" else "traffic is filled only from a PMC file of THIS build"},
+                "roofline_iteration": (
+                    {"reference_flops": it_flops, "reference_bytes_canonical": it_bytes,
+                     "reference_roofs_ms": {"fp32": it_flops / (PEAK_F32_TFLOPS * 1e12 * world) * 1e3, "hbm_canonical": it_bytes / (PEAK_HBM_GBS * 1e9 * world) * 1e3},
+                     "measured_ms": step_s * 1e3,
+                     "bytes_stored": it_bytes_stored, "frac_of_hbm_peak_stored": it_bytes_stored / step_s / 1e9 / (PEAK_HBM_GBS * world),
+                     "bytes_measured_pmc": it_bytes_measured,
+                     "frac_of_hbm_peak_measured": None if it_bytes_measured is None else it_bytes_measured / step_s / 1e9 / (PEAK_HBM_GBS * world),
+                     "what": "whole iteration (train + monitor pass).  reference_flops / reference_bytes_canonical are what the REFERENCE's formulation costs (SURVEY.md section 8d: "
+                             "N G (8C + 12K + 3) flop, float32 counts) and reference_roofs_ms the time either roof allows for it; the measured iteration is shorter than both "
+                             "because the series form of the contraction (ca_poly.hip) executes O(N + G) work instead of the N G C flops and the matrix is held at one byte "
+                             "per count -- so no fraction of those roofs is quoted (it would exceed one by construction).  What the iteration is bound by: one pass over the stored "
+                             "matrix (frac_of_hbm_peak_stored) plus a chain of small launches (DESIGN.md section 5e)"}
+                    if (info.get("fwd_series") and info.get("series_passes", 0) > 0) else
+                    {"flops": it_flops, "bytes_canonical": it_bytes,
+                     "achieved_TFLOPs": it_flops / step_s / 1e12,
+                     "frac_of_fp32_peak": it_flops / step_s / 1e12 / (PEAK_F32_TFLOPS * world),
+                     "achieved_GBps_canonical": it_bytes / step_s / 1e9,
+                     "frac_of_hbm_peak_canonical": it_bytes / step_s / 1e9 / (PEAK_HBM_GBS * world),
+                     "bytes_stored": it_bytes_stored,
+                     "frac_of_hbm_peak_stored": it_bytes_stored / step_s / 1e9 / (PEAK_HBM_GBS * world),
+                     "bytes_measured_pmc": it_bytes_measured,
+                     "frac_of_hbm_peak_measured": None if it_bytes_measured is None else it_bytes_measured / step_s / 1e9 / (PEAK_HBM_GBS * world),
+                     "what": "whole iteration (train + monitor pass) against both roofs: N G (8C + 12K + 3) flop and "
+                             "N G 4 + N (8C + 6K + 2) 4 canonical bytes (SURVEY.md section 8d) over ms_per_step.  The canonical bytes are an "
+                             "accounting convention (float32 counts): bytes_stored is the same formula at the width the matrix is held at, "
+                             "bytes_measured_pmc the two sweeps' HBM traffic from the PMC pass of this build -- what the memory system actually moves"}),
+                "kernel_ms_per_iter_warmup": {k: v[0] / max(args.warmup, 1) for k, v in kt.items()},
+                "roofline_ystream": ystream,
+                "fit_wallclock": {"seconds": fit_s, "iterations": int(len(trace) - 1), "max_iter": 200, "rel_tol": 1e-6,
+                                  "final_elbo_mean": float(np.mean(finals)), "from_initial_values": True,
+                                  "what": "ca_reinit (initial values, fresh Adam state), ca_run + 20 final ELBOs, eps generated by the "
+                                          "built-in Philox stream (inside the time)"},
+            })
+            if steady is not None:
+                out["steady_state_200"] = steady
+            if other is not None:
+                out["other_configs"] = other
+                out["fallbacks"] = fallbacks
+            if busy_it:
+                out["untimed_busy_tail"] = {"seconds": busy_s, "iterations": busy_it, "it_per_s": busy_it / busy_s,
+                                            "what": "untimed ca_iterate calls after the measurements (see --busy-seconds); not part of value"}
+            if replicas_equal is not None:
+                out["replicas_bit_identical_after_timed_regions"] = replicas_equal
+            if mon_us is not None:
+                out["monitor_pass_us_with_collective"] = mon_us
+            if ar_us is not None:
+                out["allreduce_us"] = ar_us
+            if api_leg is not None:
+                out["through_api"] = api_leg
+            if want_cpu:
+                n_cpu = args.cpu_sample_cells
+                if n_cpu <= 0:
+                    import psutil
+                    n_cpu = n_loc if psutil.virtual_memory().available > 10 * 8 * n_loc * G else 65536
+                Yd, _aux2 = synth.make_problem_torch(N, G, C, seed=args.seed, rows=(lo, hi), device=f"cuda:{local_rank}")   # (the same counts as above: same seed)
+                Ysample = Yd[:min(n_cpu, n_loc)].cpu().numpy().astype(np.float64)
+                del Yd, _aux2
+                torch.cuda.empty_cache()
+                try:
+                    out["parity_check"] = parity_check(eng, Ysample, aux["L"], psi0[:Ysample.shape[0]], loc0, K) if Ysample.shape[0] == n_loc else {
+                        "skipped": "the host has no room for the full matrix in float64; tests/test_gpu_scale.py holds the at-size check"}
+                except Exception as ex:  # noqa: BLE001
+                    out["parity_check"] = {"error": str(ex)[:300]}
+                out["cpu_baseline"] = cpu_baseline(Ysample, aux["L"], psi0, loc0, K, N)
+                try:
+                    out["cpu_ref_dataflow"] = cpu_ref_dataflow()
+                except Exception as ex:  # noqa: BLE001
+                    out["cpu_ref_dataflow"] = {"error": str(ex)}
         print(json.dumps(out), flush=True)
     eng.close()
     if world > 1:

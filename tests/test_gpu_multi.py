@@ -191,7 +191,12 @@ def _bench(world, extra, same_device=True, shape=("--cells", "20000", "--genes",
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "6", "--warmup", "2",
            "--repeats", "2", *shape, "--no-cpu-baseline", "--busy-seconds", "0", *([] if api_leg else ["--no-through-api-leg"]), *extra]
-    return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)   # (a run takes 15-60 s)
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)   # (a run takes 15-60 s)
+    if r.returncode != 0 and "EADDRINUSE" in r.stderr:
+        # another process took the free port before the launcher's rendezvous bound it: the launcher stopped before any rank started -- a new port
+        cmd[cmd.index("--master-port") + 1] = str(_free_port())
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)
+    return r
 
 
 def _bench_bare(world, extra=(), same_device=True, shape=("--cells", "20000", "--genes", "1000", "--clones", "4"), timeout=600):
@@ -218,7 +223,7 @@ def test_bench_through_the_api_runs_one_sharded_fit_inside_one_process():
     t = line["through_api"]
     assert line["n_gpus"] == 2 and line["config"]["collective"] == "host" and t["transport"] == "host" and "more than one rank" in t["note"]
     assert t["cells_per_rank"] == [10000, 10000] and t["finite"] and line["value"] == t["value"] > 0 and t["fit_wallclock"]["iterations"] >= 10
-    r = _bench_bare(2, ["--api-leg", "--preheat-ms", "20"])
+    r = _bench_bare(2, ["--api-leg", "--full", "--preheat-ms", "20"])
     assert r.returncode == 0, child_report(r)
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["config"]["collective"] == "p2p" and "error" not in line["through_api"], line.get("through_api")
@@ -229,7 +234,7 @@ def test_bench_through_the_api_runs_one_sharded_fit_inside_one_process():
 def test_bare_bench_command_starts_its_own_ranks(world):
     """`python bench.py --gpus N` without torch.distributed.run around it used to run ONE rank and print n_gpus 1.  Now the
     process becomes the launcher (before anything touches a GPU): N fresh ranks, rank 0's line relayed, the worst rank's exit code."""
-    r = _bench_bare(world, ["--preheat-ms", "30"], shape=("--cells", "24000", "--genes", "600", "--clones", "8") if world == 8 else ("--cells", "20000", "--genes", "1000", "--clones", "4"))
+    r = _bench_bare(world, ["--full", "--preheat-ms", "30"], shape=("--cells", "24000", "--genes", "600", "--clones", "8") if world == 8 else ("--cells", "20000", "--genes", "1000", "--clones", "4"))
     assert r.returncode == 0, child_report(r)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]                      # exactly ONE JSON line: rank 0's
@@ -276,6 +281,35 @@ def test_bench_two_ranks_use_a_device_transport_and_fail_loudly_without_one():
         assert line["config"]["collective"] == "gloo-host-fallback" and line["config"]["collectives_tried"] == ["rccl", "host"]
 
 
+def test_plain_bench_times_its_steps_once_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` is the lean run: one timed region of exactly K steps, the headline line alone (what --full
+    adds is absent), and --dump-outputs writes what the timed call computed -- in float64, the same bits from run to run (seeded inputs and a
+    pre-heat of a fixed number of iterations)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "CLONEALIGN_BENCH_DEVICE")}
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+               "--cells", "20000", "--genes", "1000", "--clones", "4", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=420, cwd=ROOT)
+        assert r.returncode == 0, child_report(r)
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    line = lines[0]
+    assert line["steps"] == 7 and line["warmup"] == 3 and line["repeats"]["n"] == 1 and line["n_gpus"] == 1
+    assert line["metric"] == "ELBO iterations/sec" and line["unit"] == "iterations/s" and line["higher_is_better"] is True and line["dtype"]
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    for k in ("roofline", "kernel_ms_per_iter_warmup", "fit_wallclock", "steady_state_200", "other_configs", "cpu_baseline", "untimed_busy_tail"):
+        assert k not in line, k
+    a, b = dumps
+    assert set(a) == {"elbo", "mu", "clone_probs", "s", "alpha", "psi", "W", "chi"} and a["clone_probs"].shape == (20000, 4)
+    assert all(v.dtype == np.float64 for v in a.values()) and a["elbo"][0] == line["final_elbo"]
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_preheat_makes_the_same_number_of_collective_calls_on_every_rank():
     """the clock pre-heat is a loop of collective calls; its length must be agreed on, not decided by each
     rank's own clock.  A long pre-heat of short calls (about 150 calls here) gives a per-rank clock every chance to disagree;
@@ -295,7 +329,7 @@ def test_bench_eight_ranks_on_one_device_run_the_driver_command_shape():
     """The driver's scaling command at W = 8 -- `bench.py --gpus 8 --steps K --warmup W` under torch.distributed.run -- with every rank on
     device 0 and a small matrix: transport bring-up over eight processes, agreed pre-heat, timed regions, the all-reduce benchmark, the fit
     with its stop rule on eight replicas.  (The numbers mean nothing: eight processes time-slice one GPU.)"""
-    r = _bench(8, ["--preheat-ms", "30"], shape=("--cells", "24000", "--genes", "600", "--clones", "8"))
+    r = _bench(8, ["--full", "--preheat-ms", "30"], shape=("--cells", "24000", "--genes", "600", "--clones", "8"))
     assert r.returncode == 0, child_report(r)
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 8 and line["config"]["collective"] == "p2p" and line["scaling"] == "strong"
@@ -311,7 +345,7 @@ def test_bench_on_eight_gpus_uses_a_device_collective_and_replicas_agree(tmp_pat
     # the BARE command (no launcher, no WORLD_SIZE): bench.py starts its eight ranks itself, one per device
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "CLONEALIGN_BENCH_DEVICE")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert r.returncode == 0, child_report(r)
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -328,11 +362,11 @@ def test_bench_two_ranks_take_the_series_form_sharded():
     genes per rank; sharded, the pick asks for G >= 2000 + 7.5e7 / N of the rank): every pass on the series form on both ranks, replicas bit-identical after the timed regions, and the payload of the collective is the
     series prefix of sharding.reduce_plan (cell sums, Y^T psi, backward moments, a max |psi| slot per rank) -- not the per-gene sums."""
     from clonealign_amd import sharding
-    r = _bench(2, [], shape=("--cells", "70000", "--genes", "5000", "--clones", "8"))
+    r = _bench(2, ["--full"], shape=("--cells", "70000", "--genes", "5000", "--clones", "8"))
     if r.returncode != 0 and ("time limit" in r.stderr or "CA_ERR_COMM" in r.stderr or "error 5" in r.stderr):
         # two PROCESSES on one device: a rank's all-reduce kernel spins for its peer's data while the peer's kernels wait for the same GPU -- the one-device rig's
         # own hazard (bounded by comm_timeout_ms, reported as CA_ERR_COMM; seen once in a dozen runs of this test).  Distinct devices have no such wait.  Once more.
-        r = _bench(2, [], shape=("--cells", "70000", "--genes", "5000", "--clones", "8"))
+        r = _bench(2, ["--full"], shape=("--cells", "70000", "--genes", "5000", "--clones", "8"))
     assert r.returncode == 0, child_report(r)
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["collective"] == "p2p" and line["config"]["series_form"] is True, line["config"]
@@ -352,9 +386,9 @@ def test_bench_four_ranks_on_one_device_keep_their_collectives_in_step_when_a_ga
     cfg-3 over four ranks (25 000 cells each: the series form), the driver's command shape, twice."""
     shape = ("--cells", "100000", "--genes", "5000", "--clones", "8")
     for _ in range(2):
-        r = _bench(4, [], shape=shape)
+        r = _bench(4, ["--full"], shape=shape)
         if r.returncode != 0 and "time limit" in r.stderr and "cannot cover" not in r.stderr:
-            r = _bench(4, [], shape=shape)   # (the one-device rig's own hazard: a rank's all-reduce spinning for a peer whose kernels wait for the same GPU)
+            r = _bench(4, ["--full"], shape=shape)   # (the one-device rig's own hazard: a rank's all-reduce spinning for a peer whose kernels wait for the same GPU)
         assert r.returncode == 0, child_report(r)
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         assert line["n_gpus"] == 4 and line["config"]["series_form"] is True and line["replicas_bit_identical_after_timed_regions"] is True, line["config"]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # one timing build (extra -D flags), many dispatch patterns:  tools/lab_patterns.sh "<-D flags>" "<bench args>" pat1 pat2 ...
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-FLAGS="$1"; ARGS="$2"; shift; shift
+FLAGS="$1"; ARGS="--full $2"; shift; shift   # (--full: the line carries kernel_ms_per_iter_warmup)
 /opt/rocm/bin/hipcc -O3 -fno-slp-vectorize -std=c++17 --offload-arch=gfx950 -fPIC -shared -I$ROOT/include -mllvm -amdgpu-mfma-vgpr-form \
   -DCA_BUILD_ID=\"lab_pat\" $FLAGS -o /tmp/lab_pat.so $ROOT/clonealign_amd/csrc/clonealign_hip.hip -ldl -pthread 2>/dev/null || { echo "build failed"; exit 1; }
 for pat in "$@"; do
