@@ -101,8 +101,16 @@ def correlations_from_sums(T, Syy, L, clone_counts):
     return out
 
 
+def _is_sparse(a):
+    import scipy.sparse as sps
+    return sps.issparse(a)
+
+
 def _counts_array(a):
-    """The count matrix in its own dtype when the engine can upload it as it is (no float64 copy of N x G), else float64."""
+    """The count matrix in its own dtype when the engine can upload it as it is (no float64 copy of N x G), else float64.  A
+    scipy.sparse matrix stays sparse (the engine takes its compressed arrays: engine.sparse_counts)."""
+    if _is_sparse(a):
+        return a
     a = np.asarray(a)
     if a.dtype in (np.float64, np.float32, np.int32, np.uint16, np.uint8):
         return a
@@ -125,10 +133,12 @@ def _parse_expression(gene_expression_data):
             names = [str(i) for i in counts.index]
         elif isinstance(g, dict) and "rownames" in g:
             names = list(g["rownames"])
-        return _counts_array(counts).T, names
+        return _counts_array(counts).T, names                           # (sparse: the CSC of genes x cells is the CSR of Y, no copy)
     if hasattr(g, "columns") and hasattr(g, "values"):               # pandas DataFrame cells x genes
         return _counts_array(g.values), [str(c) for c in g.columns]
     if isinstance(g, np.ndarray) and g.ndim == 2:
+        return _counts_array(g), None
+    if _is_sparse(g) and g.ndim == 2:                                # the dgCMatrix branch of :207-222, kept sparse
         return _counts_array(g), None
     raise TypeError("Input gene_expression_data must be SingleCellExperiment, SummarizedExperiment, or matrix")
 
@@ -221,8 +231,11 @@ def clonealign(gene_expression_data, copy_number_data, max_iter=200, rel_tol=1e-
     if post is not None:
         res["correlations"] = correlations_from_sums(post["T"], post["Syy"], L[keep, :], post["counts"])   # :292-294
     else:
-        Ysel = Y if (sel_c is None and sel_g is None) else Y[np.ix_(np.arange(Y.shape[0]) if sel_c is None else sel_c,
-                                                                    np.arange(Y.shape[1]) if sel_g is None else sel_g)]
+        if _is_sparse(Y):                                            # (engines without device sums fit small matrices only)
+            Ysel = Y.tocsr()[np.arange(Y.shape[0]) if sel_c is None else sel_c][:, np.arange(Y.shape[1]) if sel_g is None else sel_g].toarray()
+        else:
+            Ysel = Y if (sel_c is None and sel_g is None) else Y[np.ix_(np.arange(Y.shape[0]) if sel_c is None else sel_c,
+                                                                        np.arange(Y.shape[1]) if sel_g is None else sel_g)]
         res["correlations"] = compute_correlations(Ysel[:, keep], L[keep, :], res["clone"], clone_names)   # :292-294
     cor = res["correlations"]
     if np.any(~np.isnan(cor)):

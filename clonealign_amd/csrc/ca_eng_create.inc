@@ -40,7 +40,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   h->gate_ticks = (unsigned long long)(h->ticks_per_us * (double)(h->opt.gate_timeout_us > 0 ? h->opt.gate_timeout_us : 1000));
   h->run_fwd = h->run_gate && variantx_on(h, CA_VARX_RUN_FWD, "CA_RUN_FWD");   // opt-in: see the header (no runtime call may block between a gated launch and its answer)
   h->pair_elbo = variant_on(h, CA_VAR_PAIR_ELBO, "CA_PAIR_ELBO");
-  CACK(upload_y(h, p));
+  CACK(h->sp_in ? upload_y_sparse(h, p, h->sp_in) : upload_y(h, p));
   const int G = h->G, C = h->C, K = h->K, P = h->P, S = h->S, D = h->D;
   const int64_t Nn = h->N;
   h->nchunk = cdiv(C, CA_CW);

@@ -1,25 +1,9 @@
 // ca_eng_ingest.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): ingestion: storage scan and conversion, selection gather, host -> device pipeline (float64 narrowed on the host), fit constants.
 
-template <typename ST>
-int scan_and_convert(ca_engine* h, const ST* src_dev, int64_t sn, int64_t sg) {
-  double* maxv = nullptr;
-  int* flags = nullptr;
-  HIPCK(h, hipMalloc((void**)&maxv, 32));
-  flags = (int*)(maxv + 1);
-  unsigned long long* cnt = (unsigned long long*)(maxv + 2);
-  HIPCK(h, hipMemsetAsync(maxv, 0, 32, h->stream));
-  const int64_t total = h->N * (int64_t)h->G;
-  hipLaunchKernelGGL((k_scan_y<ST>), dim3(std::min<int64_t>(4096, cdiv(total, CA_TB))), dim3(CA_TB), 0, h->stream, src_dev, total, maxv, flags, cnt);
-  HIPCK(h, hipGetLastError());
-  double hm[4];
-  HIPCK(h, hipMemcpyAsync(hm, maxv, 32, hipMemcpyDeviceToHost, h->stream));
-  SYNC(h);
-  const double mx = hm[0];
-  int fl;
-  memcpy(&fl, &hm[1], sizeof(int));
-  unsigned long long n255;
-  memcpy(&n255, &hm[2], sizeof(n255));
-  if (fl & 2) { hipFree(maxv); h->err = "count matrix has negative or NaN entries"; return CA_ERR_INVALID; }
+// storage pick from the scan of the (selected) counts -- the one rule of both ingest paths (upload_y / upload_y_sparse): sets ystore,
+// ybytes, VEC, nseg, Gp, y_dev_bytes.  total = N * G of the selection (implicit zeros of a sparse matrix are counts too).
+int pick_ystore(ca_engine* h, double mx, int fl, unsigned long long n255, int64_t total) {
+  if (fl & 2) { h->err = "count matrix has negative or NaN entries"; return CA_ERR_INVALID; }
   int store = h->opt.y_storage;
   const bool integral = !(fl & 1);
   // u8 also serves matrices with a few entries above 255 (at most 1 in 64, each < 2^24): those keep 255 in
@@ -32,7 +16,6 @@ int scan_and_convert(ca_engine* h, const ST* src_dev, int64_t sn, int64_t sg) {
     else store = CA_YSTORE_F32;
   }
   if ((store == CA_YSTORE_U8 && !(integral && mx < 16777216.0)) || (store == CA_YSTORE_U16 && (!integral || mx > 65535.0))) {
-    hipFree(maxv);
     h->err = "requested y_storage cannot hold the counts (max " + std::to_string(mx) + ")";
     return CA_ERR_INVALID;
   }
@@ -49,28 +32,14 @@ int scan_and_convert(ca_engine* h, const ST* src_dev, int64_t sn, int64_t sg) {
     h->err = "count matrix too large for this build (cells x padded genes >= 2^36 bytes, or 2^31 cells)";
     return CA_ERR_INVALID;
   }
-  uint8_t* yb = nullptr;
-  CACK(dalloc(h, &yb, h->y_dev_bytes));
-  h->Y = yb;
-  HIPCK(h, hipMemsetAsync(maxv, 0, 32, h->stream));
-  const int64_t tot = h->N * (int64_t)h->Gp;
-  const dim3 grid = ca_grid_flat(tot, CA_TB);
-  if (store == CA_YSTORE_U8 && n255 > 0) {
-    h->n_ovf = (int64_t)n255;
-    int *orow = nullptr, *ocol = nullptr; float* oval = nullptr;
-    HIPCK(h, hipMalloc((void**)&orow, n255 * sizeof(int)));
-    HIPCK(h, hipMalloc((void**)&ocol, n255 * sizeof(int)));
-    HIPCK(h, hipMalloc((void**)&oval, n255 * sizeof(float)));
-    hipLaunchKernelGGL((k_convert_y_u8ovf<ST>), grid, dim3(CA_TB), 0, h->stream, src_dev, (uint8_t*)h->Y, h->N, h->G, h->Gp, sn, sg, cnt, orow, ocol, oval);
-    HIPCK(h, hipGetLastError());
-    h->h_orow.resize(n255); h->h_ocol.resize(n255); h->h_oval.resize(n255);
-    HIPCK(h, hipMemcpyAsync(h->h_orow.data(), orow, n255 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipMemcpyAsync(h->h_ocol.data(), ocol, n255 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipMemcpyAsync(h->h_oval.data(), oval, n255 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    SYNC(h);
-    hipFree(orow); hipFree(ocol); hipFree(oval); hipFree(maxv);
-    // fixed order: sort by (cell, gene) for the CSR copy and by (gene, cell) for the CSC copy
-    const int64_t nz = (int64_t)n255;
+  return CA_OK;
+}
+
+// the u8 overflow list (h_orow / h_ocol / h_oval, n_ovf entries in the order the conversion appended them) into its fixed form:
+// sorted by (cell, gene) for the CSR copy and by (gene, cell) for the CSC copy, 256-entry chunks per gene, all uploaded
+int finish_ovf(ca_engine* h) {
+  {
+    const int64_t nz = h->n_ovf;
     std::vector<int64_t> idx(nz);
     for (int64_t i = 0; i < nz; ++i) idx[i] = i;
     std::sort(idx.begin(), idx.end(), [&](int64_t a, int64_t b) {
@@ -110,7 +79,55 @@ int scan_and_convert(ca_engine* h, const ST* src_dev, int64_t sn, int64_t sg) {
     HIPCK(h, hipMemcpyAsync(h->ovf_val, v1.data(), nz * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIPCK(h, hipMemcpyAsync(h->ovf_val2, v2.data(), nz * sizeof(float), hipMemcpyHostToDevice, h->stream));
     SYNC(h);   // (the sources are this function's vectors; and every copy above is ordered on the engine's stream, behind the buffers' zeroing)
-    return CA_OK;
+  }
+  return CA_OK;
+}
+
+template <typename ST>
+int scan_and_convert(ca_engine* h, const ST* src_dev, int64_t sn, int64_t sg) {
+  double* maxv = nullptr;
+  int* flags = nullptr;
+  HIPCK(h, hipMalloc((void**)&maxv, 32));
+  flags = (int*)(maxv + 1);
+  unsigned long long* cnt = (unsigned long long*)(maxv + 2);
+  HIPCK(h, hipMemsetAsync(maxv, 0, 32, h->stream));
+  const int64_t total = h->N * (int64_t)h->G;
+  hipLaunchKernelGGL((k_scan_y<ST>), dim3(std::min<int64_t>(4096, cdiv(total, CA_TB))), dim3(CA_TB), 0, h->stream, src_dev, total, maxv, flags, cnt);
+  HIPCK(h, hipGetLastError());
+  double hm[4];
+  HIPCK(h, hipMemcpyAsync(hm, maxv, 32, hipMemcpyDeviceToHost, h->stream));
+  SYNC(h);
+  const double mx = hm[0];
+  int fl;
+  memcpy(&fl, &hm[1], sizeof(int));
+  unsigned long long n255;
+  memcpy(&n255, &hm[2], sizeof(n255));
+  {
+    const int rcp = pick_ystore(h, mx, fl, n255, total);
+    if (rcp != CA_OK) { hipFree(maxv); return rcp; }
+  }
+  const int store = h->ystore;
+  uint8_t* yb = nullptr;
+  CACK(dalloc(h, &yb, h->y_dev_bytes));
+  h->Y = yb;
+  HIPCK(h, hipMemsetAsync(maxv, 0, 32, h->stream));
+  const int64_t tot = h->N * (int64_t)h->Gp;
+  const dim3 grid = ca_grid_flat(tot, CA_TB);
+  if (store == CA_YSTORE_U8 && n255 > 0) {
+    h->n_ovf = (int64_t)n255;
+    int *orow = nullptr, *ocol = nullptr; float* oval = nullptr;
+    HIPCK(h, hipMalloc((void**)&orow, n255 * sizeof(int)));
+    HIPCK(h, hipMalloc((void**)&ocol, n255 * sizeof(int)));
+    HIPCK(h, hipMalloc((void**)&oval, n255 * sizeof(float)));
+    hipLaunchKernelGGL((k_convert_y_u8ovf<ST>), grid, dim3(CA_TB), 0, h->stream, src_dev, (uint8_t*)h->Y, h->N, h->G, h->Gp, sn, sg, cnt, orow, ocol, oval);
+    HIPCK(h, hipGetLastError());
+    h->h_orow.resize(n255); h->h_ocol.resize(n255); h->h_oval.resize(n255);
+    HIPCK(h, hipMemcpyAsync(h->h_orow.data(), orow, n255 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(h->h_ocol.data(), ocol, n255 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(h->h_oval.data(), oval, n255 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    SYNC(h);
+    hipFree(orow); hipFree(ocol); hipFree(oval); hipFree(maxv);
+    return finish_ovf(h);
   }
   if (store == CA_YSTORE_U8) hipLaunchKernelGGL((k_convert_y<ST, uint8_t>), grid, dim3(CA_TB), 0, h->stream, src_dev, (uint8_t*)h->Y, h->N, h->G, h->Gp, sn, sg, flags);
   else if (store == CA_YSTORE_U16) hipLaunchKernelGGL((k_convert_y<ST, uint16_t>), grid, dim3(CA_TB), 0, h->stream, src_dev, (uint16_t*)h->Y, h->N, h->G, h->Gp, sn, sg, flags);
@@ -355,6 +372,203 @@ int upload_y(ca_engine* h, const ca_problem* p) {
   }
   cleanup();
   return rc;
+}
+
+// ---- compressed count matrix (ca_create_sparse) ----------------------------------------------------------------------------------
+// The caller's CSR / CSC arrays go up as they are (float64 values narrowed through ingest_host_matrix, as a dense float64 Y is); the
+// device checks their canonical form, scans the SELECTED stored entries for the storage pick (pick_ystore, as the dense path), turns
+// CSC into CSR over the selection, and expands each selected cell's run into its resident row (k_sp_densify).  No N x G buffer exists at
+// any point: peak memory is the resident matrix plus the compressed arrays (plus the CSR transpose of a CSC matrix).
+struct sp_bufs {   // device buffers owned by one upload_y_sparse call
+  std::vector<void*> p;
+  template <typename T> hipError_t alloc(T** out, int64_t n) {
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, (size_t)std::max<int64_t>(n, 1) * sizeof(T));
+    if (e == hipSuccess) p.push_back(q);
+    *out = (T*)q;
+    return e;
+  }
+  void release(void* q) { for (auto& x : p) if (x == q) { hipFree(x); x = nullptr; } }
+  ~sp_bufs() { for (void* x : p) if (x) hipFree(x); }
+};
+#define SPCK(h, x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) { (h)->err = std::string("sparse count matrix: ") + hipGetErrorString(e_); return e_ == hipErrorOutOfMemory ? CA_ERR_NOMEM : CA_ERR_HIP; } } while (0)
+
+// scan, storage pick and densify of a CSR view over the selection (rows / ginv as in ca_k_sparse.hip.h); scratch = 32 zeroed bytes
+template <typename PT, typename IT, typename VT>
+int sparse_densify(ca_engine* h, sp_bufs& b, const PT* ptr, const IT* idx, const VT* val, const int64_t* rows, const int32_t* ginv, double* scratch) {
+  int* flags = (int*)(scratch + 1);
+  unsigned long long* cnt = (unsigned long long*)(scratch + 2);
+  const int64_t total = h->N * (int64_t)h->G;
+  hipLaunchKernelGGL((k_sp_scan<PT, IT, VT>), dim3((unsigned)std::min<int64_t>(4096, cdiv(h->N, CA_TB / 64))), dim3(CA_TB), 0, h->stream, ptr, idx, val,
+                     rows, ginv, h->N, scratch, flags, cnt);
+  HIPCK(h, hipGetLastError());
+  double hm[4];
+  HIPCK(h, hipMemcpyAsync(hm, scratch, 32, hipMemcpyDeviceToHost, h->stream));
+  SYNC(h);
+  int fl;
+  memcpy(&fl, &hm[1], sizeof(int));
+  unsigned long long n255;
+  memcpy(&n255, &hm[2], sizeof(n255));
+  CACK(pick_ystore(h, hm[0], fl, n255, total));
+  uint8_t* yb = nullptr;
+  CACK(dalloc(h, &yb, h->y_dev_bytes));
+  h->Y = yb;
+  HIPCK(h, hipMemsetAsync(scratch, 0, 32, h->stream));
+  const bool ovf = h->ystore == CA_YSTORE_U8 && n255 > 0;
+  int *orow = nullptr, *ocol = nullptr; float* oval = nullptr;
+  if (ovf) {
+    h->n_ovf = (int64_t)n255;
+    SPCK(h, b.alloc(&orow, (int64_t)n255)); SPCK(h, b.alloc(&ocol, (int64_t)n255)); SPCK(h, b.alloc(&oval, (int64_t)n255));
+  }
+  const int seg = std::min(h->Gp, 32768 / h->ybytes);   // LDS budget of a row segment: 32 KiB (Gp * ybytes is a multiple of 1 KiB)
+  hipLaunchKernelGGL((k_sp_densify<PT, IT, VT>), dim3((unsigned)h->N), dim3(CA_TB), (size_t)seg * h->ybytes, h->stream, ptr, idx, val, rows, ginv,
+                     h->Gp, h->ybytes, seg, (uint8_t*)h->Y, flags, ovf ? cnt : nullptr, orow, ocol, oval);
+  HIPCK(h, hipGetLastError());
+  HIPCK(h, hipMemcpyAsync(hm, scratch, 32, hipMemcpyDeviceToHost, h->stream));
+  SYNC(h);
+  memcpy(&fl, &hm[1], sizeof(int));
+  if (ovf) {
+    h->h_orow.resize(n255); h->h_ocol.resize(n255); h->h_oval.resize(n255);
+    HIPCK(h, hipMemcpyAsync(h->h_orow.data(), orow, n255 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(h->h_ocol.data(), ocol, n255 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(h->h_oval.data(), oval, n255 * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    SYNC(h);
+    return finish_ovf(h);
+  }
+  if (fl & 1) { h->err = "counts are not exactly representable in the on-device storage type"; return CA_ERR_INVALID; }
+  return CA_OK;
+}
+
+template <typename IT, typename VT>
+int sparse_ingest(ca_engine* h, sp_bufs& b, const ca_sparse* sp, const IT* ptr, const IT* idx, const VT* val, int64_t Ns, int64_t Gs,
+                  const int64_t* ci_dev, const int32_t* gi_dev, double* scratch) {
+  const bool csc = sp->kind == CA_SPARSE_CSC;
+  const int64_t nrun = csc ? Gs : Ns, ndim = csc ? Ns : Gs, nnz = sp->nnz;
+  int* flags = (int*)(scratch + 1);
+  hipLaunchKernelGGL((k_sp_check<IT>), dim3((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, cdiv(nrun, CA_TB / 64)))), dim3(CA_TB), 0, h->stream,
+                     ptr, idx, nrun, ndim, nnz, flags);
+  HIPCK(h, hipGetLastError());
+  int fl = 0;
+  HIPCK(h, hipMemcpyAsync(&fl, flags, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  SYNC(h);
+  if (fl & 4) { h->err = "sparse count matrix: ptr must start at 0, never decrease and end at nnz"; return CA_ERR_INVALID; }
+  if (fl & 8) { h->err = std::string("sparse count matrix: an index is out of range (") + (csc ? "cell" : "gene") + " indices must lie in [0, " +
+                         std::to_string(ndim) + "))"; return CA_ERR_INVALID; }
+  if (fl & 16) { h->err = "sparse count matrix: indices must be strictly increasing within each run (unsorted or duplicate entries)"; return CA_ERR_INVALID; }
+  HIPCK(h, hipMemsetAsync(scratch, 0, 32, h->stream));
+  // inverse maps of the selection: source gene -> selected gene or -1 (and for CSC, source cell -> selected cell or -1)
+  int32_t *ginv = nullptr, *cinv = nullptr;
+  if (gi_dev) {
+    SPCK(h, b.alloc(&ginv, Gs));
+    HIPCK(h, hipMemsetAsync(ginv, 0xFF, (size_t)Gs * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL((k_sp_inverse<int32_t>), dim3((unsigned)cdiv(h->G, CA_TB)), dim3(CA_TB), 0, h->stream, gi_dev, (int64_t)h->G, ginv);
+    HIPCK(h, hipGetLastError());
+  }
+  if (!csc) return sparse_densify<IT, IT, VT>(h, b, ptr, idx, val, ci_dev, ginv, scratch);
+  if (ci_dev) {
+    SPCK(h, b.alloc(&cinv, Ns));
+    HIPCK(h, hipMemsetAsync(cinv, 0xFF, (size_t)Ns * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL((k_sp_inverse<int64_t>), dim3((unsigned)cdiv(h->N, CA_TB)), dim3(CA_TB), 0, h->stream, ci_dev, h->N, cinv);
+    HIPCK(h, hipGetLastError());
+  }
+  // CSC -> CSR of the selection: per-cell counts, exclusive scan, scatter (genes already in the selection's numbering)
+  int64_t* rowptr = nullptr; unsigned long long* fill = nullptr;
+  SPCK(h, b.alloc(&rowptr, h->N + 1));
+  SPCK(h, b.alloc(&fill, h->N));
+  HIPCK(h, hipMemsetAsync(rowptr, 0, (size_t)(h->N + 1) * sizeof(int64_t), h->stream));
+  const dim3 gw((unsigned)std::min<int64_t>(4096, std::max<int64_t>(1, cdiv(nrun, CA_TB / 64))));
+  hipLaunchKernelGGL((k_sp_csc_count<IT>), gw, dim3(CA_TB), 0, h->stream, ptr, idx, nrun, ginv, cinv, (unsigned long long*)rowptr);
+  HIPCK(h, hipGetLastError());
+  hipLaunchKernelGGL(k_sp_exscan, dim3(1), dim3(1024), 0, h->stream, rowptr, h->N);
+  HIPCK(h, hipGetLastError());
+  int64_t nsel = 0;
+  HIPCK(h, hipMemcpyAsync(&nsel, rowptr + h->N, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCK(h, hipMemcpyAsync(fill, rowptr, (size_t)h->N * sizeof(int64_t), hipMemcpyDeviceToDevice, h->stream));
+  SYNC(h);
+  int32_t* col = nullptr; VT* v2 = nullptr;
+  SPCK(h, b.alloc(&col, nsel));
+  SPCK(h, b.alloc(&v2, nsel));
+  hipLaunchKernelGGL((k_sp_csc_scatter<IT, VT>), gw, dim3(CA_TB), 0, h->stream, ptr, idx, val, nrun, ginv, cinv, fill, col, v2);
+  HIPCK(h, hipGetLastError());
+  SYNC(h);
+  b.release(fill); b.release(cinv); b.release(ginv);
+  b.release((void*)ptr); b.release((void*)idx); b.release((void*)val);   // (the uploaded copies, if these are ours; the caller's device arrays are not in b)
+  return sparse_densify<int64_t, int32_t, VT>(h, b, rowptr, col, v2, nullptr, nullptr, scratch);
+}
+
+int upload_y_sparse(ca_engine* h, const ca_problem* p, const ca_sparse* sp) {
+  // the caller's matrix: N_src x G_src when a selection is given, else N x G (descriptor fields checked by ca_create_sparse)
+  const bool sel = p->cell_index || p->gene_index;
+  const int64_t Ns = sel ? p->N_src : h->N;
+  const int64_t Gs = sel ? (int64_t)p->G_src : (int64_t)h->G;
+  const bool csc = sp->kind == CA_SPARSE_CSC;
+  const int64_t nrun = csc ? Gs : Ns, nnz = sp->nnz;
+  const size_t ib = (size_t)sp->index_bytes;
+  const size_t vsz = sp->val_dtype == CA_F64 ? 8 : (sp->val_dtype == CA_F32 || sp->val_dtype == CA_I32) ? 4 : sp->val_dtype == CA_U16 ? 2 : 1;
+  sp_bufs b;
+  auto bad = [&](const char* m) { h->err = m; return CA_ERR_INVALID; };
+  // selection lists: validated on the host as on the dense path
+  int64_t* ci_dev = nullptr; int32_t* gi_dev = nullptr;
+  if (p->cell_index) {
+    for (int64_t n = 0; n < h->N; ++n)
+      if (p->cell_index[n] < 0 || p->cell_index[n] >= Ns || (n > 0 && p->cell_index[n] <= p->cell_index[n - 1]))
+        return bad("cell_index must be strictly increasing and within [0, N_src)");
+    SPCK(h, b.alloc(&ci_dev, h->N));
+    SPCK(h, hipMemcpy(ci_dev, p->cell_index, (size_t)h->N * sizeof(int64_t), hipMemcpyHostToDevice));
+  } else if (h->N != Ns) return bad("N must equal N_src when cell_index is NULL");
+  if (p->gene_index) {
+    for (int g = 0; g < h->G; ++g)
+      if (p->gene_index[g] < 0 || p->gene_index[g] >= Gs || (g > 0 && p->gene_index[g] <= p->gene_index[g - 1]))
+        return bad("gene_index must be strictly increasing and within [0, G_src)");
+    SPCK(h, b.alloc(&gi_dev, h->G));
+    SPCK(h, hipMemcpy(gi_dev, p->gene_index, (size_t)h->G * sizeof(int32_t), hipMemcpyHostToDevice));
+  } else if (h->G != Gs) return bad("G must equal G_src when gene_index is NULL");
+  // the compressed arrays on the device, each in its own dtype (float64 values narrowed to float32 when every value is a float)
+  const void *dptr = sp->ptr, *didx = sp->idx, *dval = sp->val;
+  int vdt = sp->val_dtype;
+  if (!sp->on_device) {
+    char *q = nullptr, *x = nullptr;
+    SPCK(h, b.alloc(&q, (int64_t)((nrun + 1) * ib)));
+    SPCK(h, hipMemcpy(q, sp->ptr, (size_t)(nrun + 1) * ib, hipMemcpyHostToDevice));
+    SPCK(h, b.alloc(&x, (int64_t)(nnz * ib)));
+    if (nnz > 0) SPCK(h, hipMemcpy(x, sp->idx, (size_t)nnz * ib, hipMemcpyHostToDevice));
+    dptr = q; didx = x;
+    char* v = nullptr;
+    if (vdt == CA_F64 && nnz > 0) {
+      SPCK(h, b.alloc(&v, nnz * 4));
+      ingest_result ir;
+      int rci;
+      try { rci = ingest_host_matrix(h->stream, h->err, sp->val, nnz, CA_F64, v, &ir); }
+      catch (const std::exception& ex) { h->err = std::string("upload of the count matrix: ") + ex.what(); rci = CA_ERR_NOMEM; }   // (nothing unwinds through the C ABI)
+      if (rci != CA_OK) return rci;
+      if (ir.inexact) {
+        // some value is not a float (non-integral, NaN, huge, or outside the selection): up again as float64, the scan below judges it
+        b.release(v);
+        SPCK(h, b.alloc(&v, nnz * 8));
+        SPCK(h, hipMemcpy(v, sp->val, (size_t)nnz * 8, hipMemcpyHostToDevice));
+      } else {
+        vdt = CA_F32;
+      }
+    } else {
+      SPCK(h, b.alloc(&v, (int64_t)(nnz * vsz)));
+      if (nnz > 0) SPCK(h, hipMemcpy(v, sp->val, (size_t)nnz * vsz, hipMemcpyHostToDevice));
+    }
+    dval = v;
+  }
+  double* scratch = nullptr;   // max, flags, count above 255
+  SPCK(h, b.alloc(&scratch, 4));
+  HIPCK(h, hipMemsetAsync(scratch, 0, 32, h->stream));
+#define CA_SP_VT(IT)                                                                                                                       \
+  switch (vdt) {                                                                                                                           \
+    case CA_F64: return sparse_ingest<IT, double>(h, b, sp, (const IT*)dptr, (const IT*)didx, (const double*)dval, Ns, Gs, ci_dev, gi_dev, scratch);   \
+    case CA_F32: return sparse_ingest<IT, float>(h, b, sp, (const IT*)dptr, (const IT*)didx, (const float*)dval, Ns, Gs, ci_dev, gi_dev, scratch);     \
+    case CA_I32: return sparse_ingest<IT, int32_t>(h, b, sp, (const IT*)dptr, (const IT*)didx, (const int32_t*)dval, Ns, Gs, ci_dev, gi_dev, scratch); \
+    case CA_U16: return sparse_ingest<IT, uint16_t>(h, b, sp, (const IT*)dptr, (const IT*)didx, (const uint16_t*)dval, Ns, Gs, ci_dev, gi_dev, scratch); \
+    default: return sparse_ingest<IT, uint8_t>(h, b, sp, (const IT*)dptr, (const IT*)didx, (const uint8_t*)dval, Ns, Gs, ci_dev, gi_dev, scratch);   \
+  }
+  if (ib == 4) { CA_SP_VT(int32_t) }
+  CA_SP_VT(int64_t)
+#undef CA_SP_VT
 }
 
 template <typename YT>

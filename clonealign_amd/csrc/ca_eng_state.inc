@@ -87,6 +87,7 @@ struct ca_engine {
   int *ovf_col = nullptr, *ovf_row2 = nullptr;
   float *ovf_val = nullptr, *ovf_val2 = nullptr;
   std::vector<int> h_orow, h_ocol; std::vector<float> h_oval;
+  const ca_sparse* sp_in = nullptr;   // ca_create_sparse: the compressed count matrix (read during create_impl only)
   // ---- constants
   float* Lb = nullptr;       // [nchunk][G][8]
   double *A = nullptr, *cn = nullptr, *s64 = nullptr, *colsum = nullptr, *YtX = nullptr;

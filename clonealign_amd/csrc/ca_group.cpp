@@ -69,6 +69,11 @@ struct Shard {
   ca_problem p;
   std::vector<double> psi0, X, extra;
   std::vector<int64_t> ci;
+  // ca_group_create_sparse: the rank's view of the compressed matrix (kept for create_handles, which runs again after a transport rebuild)
+  bool sparse = false;
+  ca_sparse sp;
+  std::vector<int32_t> ptr32;   // a host CSR matrix's ptr rebased to the rank's rows (the width of the caller's)
+  std::vector<int64_t> ptr64;
 };
 
 }  // namespace
@@ -205,12 +210,51 @@ void scatter_rows(const double* src, int layout, int64_t N, int64_t cols, int64_
 
 size_t dtype_bytes(int dt) { return dt == CA_F64 ? 8 : (dt == CA_F32 || dt == CA_I32) ? 4 : dt == CA_U16 ? 2 : 1; }
 
+// a sparse shard: its cells as a cell_index subset over the caller's compressed arrays; a host CSR matrix is rebased to the rank's rows
+// [r0, r1] (a copy of that part of ptr, idx / val offset in place), so that only those runs cross PCIe
+void make_sparse_shard(const ca_problem& p, const ca_sparse& sp, Shard& s) {
+  const int64_t n = s.hi - s.lo;
+  const bool sel = p.cell_index || p.gene_index;
+  const int64_t Ns = sel ? p.N_src : p.N;
+  s.sparse = true;
+  s.sp = sp;
+  s.p.Y = nullptr;
+  const int64_t r0 = p.cell_index ? p.cell_index[s.lo] : s.lo, r1 = p.cell_index ? p.cell_index[s.hi - 1] : s.hi - 1;
+  if (sp.kind == CA_SPARSE_CSR && !sp.on_device) {
+    const bool w4 = sp.index_bytes == 4;
+    auto at = [&](int64_t i) { return w4 ? (int64_t)static_cast<const int32_t*>(sp.ptr)[i] : static_cast<const int64_t*>(sp.ptr)[i]; };
+    const int64_t a = at(r0), z = at(r1 + 1);
+    if (0 <= a && a <= z && z <= sp.nnz) {   // (else the rank reads the whole matrix and its device check reports what is wrong)
+      const int64_t m = r1 - r0 + 1;
+      if (w4) { s.ptr32.resize((size_t)m + 1); for (int64_t i = 0; i <= m; ++i) s.ptr32[(size_t)i] = (int32_t)(at(r0 + i) - a); s.sp.ptr = s.ptr32.data(); }
+      else { s.ptr64.resize((size_t)m + 1); for (int64_t i = 0; i <= m; ++i) s.ptr64[(size_t)i] = at(r0 + i) - a; s.sp.ptr = s.ptr64.data(); }
+      s.sp.idx = static_cast<const char*>(sp.idx) + (size_t)a * (size_t)sp.index_bytes;
+      s.sp.val = static_cast<const char*>(sp.val) + (size_t)a * dtype_bytes(sp.val_dtype);
+      s.sp.nnz = z - a;
+      if (sel) s.p.N_src = m;
+      if (p.cell_index) {
+        s.ci.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) s.ci[(size_t)i] = p.cell_index[s.lo + i] - r0;
+        s.p.cell_index = s.ci.data();
+      }
+      return;
+    }
+  }
+  s.p.N_src = Ns;
+  if (!sel) s.p.G_src = p.G;
+  s.ci.resize((size_t)n);
+  for (int64_t i = 0; i < n; ++i) s.ci[(size_t)i] = p.cell_index ? p.cell_index[s.lo + i] : s.lo + i;
+  s.p.cell_index = s.ci.data();
+}
+
 // the shard's view of the caller's problem: its rows of Y in place (y_ld), compact copies of the small per-cell inputs
-void make_shard(const ca_problem& p, int rank, int W, Shard& s) {
+void make_shard(const ca_problem& p, const ca_sparse* sp, int rank, int W, Shard& s) {
   s.lo = (p.N * rank) / W; s.hi = (p.N * (rank + 1)) / W;
   const int64_t n = s.hi - s.lo;
   s.p = p;
   s.p.N = n;
+  if (sp) make_sparse_shard(p, *sp, s);
+  else {
   const bool sel = p.cell_index || p.gene_index;
   const int64_t Ns = sel ? p.N_src : p.N, Gs = sel ? (int64_t)p.G_src : (int64_t)p.G;
   const int64_t run = p.layout == CA_COL_MAJOR ? Ns : Gs, ld = p.y_ld > 0 ? p.y_ld : run;
@@ -226,6 +270,7 @@ void make_shard(const ca_problem& p, int rank, int W, Shard& s) {
       for (int64_t i = 0; i < n; ++i) s.ci[(size_t)i] = p.cell_index[s.lo + i] - r0;
       s.p.cell_index = s.ci.data();
     }
+  }
   }
   if (p.K > 0 && p.psi0) { slice_rows(p.psi0, p.layout, p.N, p.K, s.lo, s.hi, s.psi0); s.p.psi0 = s.psi0.data(); }
   if (p.P > 0 && p.X) { slice_rows(p.X, p.layout, p.N, p.P, s.lo, s.hi, s.X); s.p.X = s.X.data(); }
@@ -251,7 +296,8 @@ int create_handles(ca_group* g) {
   std::vector<int> rc = dispatch(g, [g, &errs](int r) {
     ca_options o = g->opt;
     o.device = g->devices[(size_t)r]; o.rank = r; o.world = g->W;
-    const int c = ca_create(&g->shard[(size_t)r].p, &o, &g->h[(size_t)r]);
+    const Shard& sh = g->shard[(size_t)r];
+    const int c = sh.sparse ? ca_create_sparse(&sh.p, &sh.sp, &o, &g->h[(size_t)r]) : ca_create(&sh.p, &o, &g->h[(size_t)r]);
     if (c != CA_OK) errs[(size_t)r] = ca_last_error(nullptr);
     return c;
   });
@@ -360,7 +406,8 @@ int ca_group_destroy(ca_group_handle g) {
   return CA_OK;
 }
 
-int ca_group_create(const ca_problem* p, const ca_options* o, const int32_t* devices, int32_t n_devices, int32_t transport, ca_group_handle* out) {
+static int group_create(const ca_problem* p, const ca_sparse* sp, const ca_options* o, const int32_t* devices, int32_t n_devices, int32_t transport,
+                        ca_group_handle* out) {
   g_group_error.clear();
   auto bad = [&](const std::string& m, int code = CA_ERR_INVALID) { g_group_error = m; return code; };
   if (!p || !out || !devices) return bad("null argument");
@@ -368,11 +415,30 @@ int ca_group_create(const ca_problem* p, const ca_options* o, const int32_t* dev
   if (n_devices < 1 || n_devices > 64) return bad("1 to 64 devices");
   if (p->N < n_devices) return bad("fewer cells than devices");
   if (transport != 0 && transport != CA_TRANSPORT_RCCL && transport != CA_TRANSPORT_HOST && transport != CA_TRANSPORT_P2P) return bad("transport must be 0 (automatic) or a ca_transport");
-  if (!p->Y || !p->L) return bad("Y and L are required");
+  if (sp) {
+    if (p->Y) return bad("ca_group_create_sparse: problem->Y must be NULL (the counts are the ca_sparse argument)");
+    if (!p->L) return bad("L is required");
+    if (sp->kind != CA_SPARSE_CSR && sp->kind != CA_SPARSE_CSC) return bad("ca_sparse.kind must be CA_SPARSE_CSR or CA_SPARSE_CSC");
+    if (sp->val_dtype < CA_F64 || sp->val_dtype > CA_U8) return bad("ca_sparse.val_dtype must be a ca_dtype");
+    if (sp->index_bytes != 4 && sp->index_bytes != 8) return bad("ca_sparse.index_bytes must be 4 or 8");
+    if (sp->nnz < 0) return bad("ca_sparse.nnz must not be negative");
+    if (!sp->ptr || (sp->nnz > 0 && (!sp->idx || !sp->val))) return bad("ca_sparse: ptr, idx and val are required");
+    // (the shards index the caller's arrays by cell_index before any rank has looked at them: the range first)
+    if (p->cell_index && (p->N_src < p->N || p->cell_index[0] < 0 || p->cell_index[p->N - 1] >= p->N_src))
+      return bad("cell_index must be strictly increasing and within [0, N_src)");
+    if ((p->cell_index || p->gene_index) && (p->N_src < p->N || p->G_src < p->G)) return bad("N_src / G_src must be at least N / G when a selection is given");
+    if (sp->kind == CA_SPARSE_CSR && !sp->on_device) {   // ranks read only their rows' runs: the ends of ptr are checked here
+      const int64_t Ns = (p->cell_index || p->gene_index) ? p->N_src : p->N;
+      const int64_t first = sp->index_bytes == 4 ? static_cast<const int32_t*>(sp->ptr)[0] : static_cast<const int64_t*>(sp->ptr)[0];
+      const int64_t last = sp->index_bytes == 4 ? static_cast<const int32_t*>(sp->ptr)[Ns] : static_cast<const int64_t*>(sp->ptr)[Ns];
+      if (first != 0 || last != sp->nnz) return bad("sparse count matrix: ptr must start at 0, never decrease and end at nnz");
+    }
+  } else if (!p->Y || !p->L) return bad("Y and L are required");
   if (p->K > 0 && !p->psi0) return bad("psi0 is required when K > 0");
   if (p->P > 0 && !p->X) return bad("X is required when P > 0");
   if (p->cell_index) for (int64_t n = 1; n < p->N; ++n) if (p->cell_index[n] <= p->cell_index[n - 1]) return bad("cell_index must be strictly increasing and within [0, N_src)");
-  if (p->y_on_device) for (int d = 1; d < n_devices; ++d) if (devices[d] != devices[0]) return bad("a device-resident count matrix can only be sharded over ranks of its own device; hand the matrix over from host memory");
+  if (sp && sp->on_device) for (int d = 1; d < n_devices; ++d) if (devices[d] != devices[0]) return bad("device-resident sparse arrays can only be sharded over ranks of their own device; hand them over from host memory");
+  if (!sp && p->y_on_device) for (int d = 1; d < n_devices; ++d) if (devices[d] != devices[0]) return bad("a device-resident count matrix can only be sharded over ranks of its own device; hand the matrix over from host memory");
   ca_group* g = nullptr;
   try {
     g = new ca_group();
@@ -393,7 +459,7 @@ int ca_group_create(const ca_problem* p, const ca_options* o, const int32_t* dev
       g->workers[(size_t)r] = new Worker();
       g->workers[(size_t)r]->th = std::thread(worker_main, g->workers[(size_t)r], r);
     }
-    for (int r = 0; r < g->W; ++r) make_shard(*p, r, g->W, g->shard[(size_t)r]);
+    for (int r = 0; r < g->W; ++r) make_shard(*p, sp, r, g->W, g->shard[(size_t)r]);
   } catch (const std::exception& ex) {
     const std::string m = std::string("ca_group_create: ") + ex.what();
     if (g) ca_group_destroy(g);
@@ -427,6 +493,16 @@ int ca_group_create(const ca_problem* p, const ca_options* o, const int32_t* dev
   g->info.selftest_rounds = SELFTEST_ROUNDS;
   *out = g;
   return CA_OK;
+}
+
+int ca_group_create(const ca_problem* p, const ca_options* o, const int32_t* devices, int32_t n_devices, int32_t transport, ca_group_handle* out) {
+  return group_create(p, nullptr, o, devices, n_devices, transport, out);
+}
+
+int ca_group_create_sparse(const ca_problem* p, const ca_sparse* y, const ca_options* o, const int32_t* devices, int32_t n_devices, int32_t transport,
+                           ca_group_handle* out) {
+  if (!y) { g_group_error = "null argument"; return CA_ERR_INVALID; }
+  return group_create(p, y, o, devices, n_devices, transport, out);
 }
 
 int ca_group_get_info(ca_group_handle g, ca_group_info* info) {

@@ -118,6 +118,7 @@ __device__ __forceinline__ double ca_sigmoid_d(double x) { return 1.0 / (1.0 + e
 #endif
 
 #include "ca_k_stream.hip.h"   // ingest / fit-constant kernels, the vector count-matrix stream (k_ypass), per-gene prologues, the VALU and first matrix-core forward sweeps
+#include "ca_k_sparse.hip.h"   // device ingest of a compressed (CSR / CSC) count matrix: canonical-form check, selected scan, CSC -> CSR, densify
 #include "ca_k_bwd.hip.h"   // backward sweeps (k_bwd, k_bwd_mfma), TF1 Adam, the O(K + C) ELBO assembly body, preprocessing and allele kernels
 #include "ca_k_cell.hip.h"   // per-cell epilogues (plain and fused), the count-matrix finishers, the fused forward sweep with its cell epilogue (k_fwd_cell*) and the riding vector stream
 // fixed-order reduction of block partials: out[j] = sum_b part[b][j]; one block per column j

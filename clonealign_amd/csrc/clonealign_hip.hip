@@ -228,6 +228,16 @@ int gate_close(ca_engine* h) {
   } while (0)
 
 
+// the fields of a ca_sparse that can be judged without reading its arrays (shared with ca_group.cpp's copy of the rule: same messages)
+static const char* sparse_descriptor_error(const ca_sparse* sp) {
+  if (sp->kind != CA_SPARSE_CSR && sp->kind != CA_SPARSE_CSC) return "ca_sparse.kind must be CA_SPARSE_CSR or CA_SPARSE_CSC";
+  if (sp->val_dtype < CA_F64 || sp->val_dtype > CA_U8) return "ca_sparse.val_dtype must be a ca_dtype";
+  if (sp->index_bytes != 4 && sp->index_bytes != 8) return "ca_sparse.index_bytes must be 4 or 8";
+  if (sp->nnz < 0) return "ca_sparse.nnz must not be negative";
+  if (!sp->ptr || (sp->nnz > 0 && (!sp->idx || !sp->val))) return "ca_sparse: ptr, idx and val are required";
+  return nullptr;
+}
+
 extern "C" {
 
 int ca_abi_version(void) { return CA_ABI_VERSION; }
@@ -256,7 +266,7 @@ int ca_default_options(ca_options* o) {
 
 const char* ca_last_error(ca_handle h) { return h ? h->err.c_str() : g_last_error.c_str(); }
 
-int ca_create(const ca_problem* p, const ca_options* o, ca_handle* out) {
+static int create_common(const ca_problem* p, const ca_sparse* sp, const ca_options* o, ca_handle* out) {
   g_last_error.clear();
   if (!p || !out) { g_last_error = "null argument"; return CA_ERR_INVALID; }
   *out = nullptr;
@@ -268,7 +278,12 @@ int ca_create(const ca_problem* p, const ca_options* o, ca_handle* out) {
   if (p->K < 0 || p->P < 0 || p->S < 1) return bad("K >= 0, P >= 0, S >= 1 required");
   const int D = p->K > 0 ? p->K + p->P : 0;
   if (D > 8) return bad("K + P > 8 not supported");
-  if (!p->Y || !p->L) return bad("Y and L are required");
+  if (sp) {
+    if (p->Y) return bad("ca_create_sparse: problem->Y must be NULL (the counts are the ca_sparse argument)");
+    if (!p->L) return bad("L is required");
+    const char* m = sparse_descriptor_error(sp);
+    if (m) return bad(m);
+  } else if (!p->Y || !p->L) return bad("Y and L are required");
   if (p->K > 0 && !p->psi0) return bad("psi0 is required when K > 0");
   if (p->P > 0 && !p->X) return bad("X is required when P > 0");
   if (opt.world < 1 || opt.rank < 0 || opt.rank >= opt.world) return bad("bad rank/world");
@@ -281,6 +296,7 @@ int ca_create(const ca_problem* p, const ca_options* o, ca_handle* out) {
   ca_engine* h = new ca_engine();
   h->N = p->N; h->G = p->G; h->C = p->C; h->K = p->K; h->P = p->P; h->S = p->S; h->D = D;
   h->layout = p->layout; h->opt = opt; h->device = opt.device;
+  h->sp_in = sp;
   int rc;
   try { rc = create_impl(h, p); }
   catch (const std::exception& ex) { h->err = std::string("ca_create: ") + ex.what(); rc = CA_ERR_NOMEM; }   // (bad_alloc / system_error never cross the C ABI)
@@ -289,8 +305,16 @@ int ca_create(const ca_problem* p, const ca_options* o, ca_handle* out) {
     ca_destroy(h);
     return rc;
   }
+  h->sp_in = nullptr;
   *out = h;
   return CA_OK;
+}
+
+int ca_create(const ca_problem* p, const ca_options* o, ca_handle* out) { return create_common(p, nullptr, o, out); }
+
+int ca_create_sparse(const ca_problem* p, const ca_sparse* y, const ca_options* o, ca_handle* out) {
+  if (!y) { g_last_error = "null argument"; return CA_ERR_INVALID; }
+  return create_common(p, y, o, out);
 }
 
 int ca_destroy(ca_handle h) {

@@ -39,7 +39,10 @@ EXPORTS = (
     "ca_group_create", "ca_group_destroy", "ca_group_last_error", "ca_group_get_info", "ca_group_rank_handle", "ca_group_init_psi_pca", "ca_group_gamma_init",
     "ca_group_elbo", "ca_group_step", "ca_group_run_ex", "ca_group_iterate", "ca_group_final_elbo", "ca_group_get_param", "ca_group_reinit",
     "ca_group_clone_gene_sums",
+    # sparse (CSR / CSC) count matrices, additions to ABI 6
+    "ca_create_sparse", "ca_group_create_sparse",
 )
+CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
 
 class CaProblem(C.Structure):
@@ -49,6 +52,11 @@ class CaProblem(C.Structure):
                 ("X", C.c_void_p), ("extra_loglik", C.c_void_p),
                 ("N_src", C.c_int64), ("G_src", C.c_int32), ("cell_index", C.c_void_p), ("gene_index", C.c_void_p),
                 ("y_ld", C.c_int64)]
+
+
+class CaSparse(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("val_dtype", C.c_int32), ("index_bytes", C.c_int32), ("on_device", C.c_int32),
+                ("nnz", C.c_int64), ("ptr", C.c_void_p), ("idx", C.c_void_p), ("val", C.c_void_p)]
 
 
 class CaOptions(C.Structure):
@@ -110,6 +118,7 @@ def load_library(path=None):
             getattr(lib, name).restype = C.c_int
     lib.ca_device_count.argtypes = [C.POINTER(C.c_int32)]
     lib.ca_create.argtypes = [C.POINTER(CaProblem), C.POINTER(CaOptions), C.POINTER(C.c_void_p)]
+    lib.ca_create_sparse.argtypes = [C.POINTER(CaProblem), C.POINTER(CaSparse), C.POINTER(CaOptions), C.POINTER(C.c_void_p)]
     lib.ca_destroy.argtypes = [C.c_void_p]
     lib.ca_get_info.argtypes = [C.c_void_p, C.POINTER(CaInfo)]
     lib.ca_synchronize.argtypes = [C.c_void_p]
@@ -149,6 +158,8 @@ def load_library(path=None):
     lib.ca_allele_loglik.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_void_p, C.c_char_p]
     lib.ca_group_create.argtypes = [C.POINTER(CaProblem), C.POINTER(CaOptions), C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    lib.ca_group_create_sparse.argtypes = [C.POINTER(CaProblem), C.POINTER(CaSparse), C.POINTER(CaOptions), C.c_void_p, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_void_p)]
     lib.ca_group_destroy.argtypes = [C.c_void_p]
     lib.ca_group_get_info.argtypes = [C.c_void_p, C.POINTER(CaGroupInfo)]
     lib.ca_group_rank_handle.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
@@ -208,6 +219,61 @@ _Y_DTYPES = {np.dtype(np.float64): CA_F64, np.dtype(np.float32): CA_F32, np.dtyp
              np.dtype(np.uint16): CA_U16, np.dtype(np.uint8): CA_U8}
 
 
+def is_sparse(a):
+    """A scipy.sparse matrix / array (without importing scipy when it was never loaded: nothing else can be one)."""
+    import sys
+    sps = sys.modules.get("scipy.sparse")
+    return sps is not None and sps.issparse(a)
+
+
+def sparse_counts(Y):
+    """(ca_sparse fields, arrays to keep alive) of a scipy.sparse count matrix of cells x genes: CSR and CSC go as they are (no dense
+    copy); another format, or a matrix with duplicate / unsorted entries, is converted on a copy (``sum_duplicates`` also sorts).  Values
+    keep their dtype when the engine takes it, else the narrowest exact one of u8 / u16 / i32, else float64."""
+    if Y.format not in ("csr", "csc"):
+        Y = Y.tocsr()
+    if not Y.has_canonical_format:
+        Y = Y.copy()
+        Y.sum_duplicates()
+    data = Y.data
+    if data.dtype not in _Y_DTYPES:
+        if data.dtype.kind in "iub" and data.size and data.min() >= 0:
+            mx = int(data.max())
+            dt = np.uint8 if mx <= 255 else np.uint16 if mx <= 65535 else np.int32 if mx <= np.iinfo(np.int32).max else np.float64
+            data = data.astype(dt)
+        else:
+            data = data.astype(np.uint8 if not data.size else np.float64)
+    ptr, idx = Y.indptr, Y.indices
+    if ptr.dtype != idx.dtype or ptr.dtype not in (np.int32, np.int64):
+        ptr, idx = ptr.astype(np.int64), idx.astype(np.int64)
+    ptr, idx, data = np.ascontiguousarray(ptr), np.ascontiguousarray(idx), np.ascontiguousarray(data)
+    sp = CaSparse(kind=CA_SPARSE_CSR if Y.format == "csr" else CA_SPARSE_CSC, val_dtype=_Y_DTYPES[data.dtype], index_bytes=ptr.dtype.itemsize,
+                  on_device=0, nnz=int(idx.shape[0]), ptr=ptr.ctypes.data_as(C.c_void_p), idx=idx.ctypes.data_as(C.c_void_p),
+                  val=data.ctypes.data_as(C.c_void_p))
+    return sp, [ptr, idx, data]
+
+
+def _torch_sparse_counts(Y):
+    """(ca_sparse fields, tensors to keep alive) of a torch sparse CSR / CSC tensor of cells x genes on the GPU: its device arrays as
+    they are (on_device = 1; index and value dtypes must be ones the engine takes)."""
+    import torch
+    if Y.layout == torch.sparse_csr:
+        kind, ptr, idx = CA_SPARSE_CSR, Y.crow_indices(), Y.col_indices()
+    elif Y.layout == torch.sparse_csc:
+        kind, ptr, idx = CA_SPARSE_CSC, Y.ccol_indices(), Y.row_indices()
+    else:
+        raise ValueError("a torch count matrix must be dense (y_device_ptr=) or sparse CSR / CSC")
+    val = Y.values()
+    vdt = {torch.float64: CA_F64, torch.float32: CA_F32, torch.int32: CA_I32, torch.uint8: CA_U8}.get(val.dtype)
+    if vdt is None or ptr.dtype != idx.dtype or ptr.dtype not in (torch.int32, torch.int64):
+        raise ValueError("torch sparse counts: values float64 / float32 / int32 / uint8, crow / col indices both int32 or both int64")
+    ptr, idx, val = ptr.contiguous(), idx.contiguous(), val.contiguous()
+    torch.cuda.synchronize(Y.device)          # (the engine's runtime and stream are not torch's)
+    sp = CaSparse(kind=kind, val_dtype=vdt, index_bytes=ptr.element_size(), on_device=1, nnz=int(idx.numel()),
+                  ptr=C.c_void_p(ptr.data_ptr()), idx=C.c_void_p(idx.data_ptr()), val=C.c_void_p(val.data_ptr()))
+    return sp, [ptr, idx, val]
+
+
 def comm_unique_id():
     lib = load_library()
     buf = C.create_string_buffer(128)
@@ -237,12 +303,17 @@ class HipEngine:
         ``comm_timeout_ms``: bound of the peer-to-peer all-reduce's device-side wait for its peers (0 = 10 s; ca_options).
         ``gate_timeout_us``: how long ``run``'s queued-ahead update waits on the device for the host's decision before it gives up and is
         queued again afterwards (0 = 1000 us; ca_options).
+        ``Y`` may be a scipy.sparse matrix of cells x genes: CSR / CSC go to the device as their three arrays (ca_create_sparse), no dense
+        copy is made, and the fit is the dense fit bit for bit.  So may a torch sparse CSR / CSC tensor on the GPU (its device arrays).
         ``variant_off``: names from VARIANTS (or a bitmask) to switch off; ``variant_on``: names from VARIANTS_ON to switch on;
         ``tune``: {name from TUNE: value}."""
         prob, opt = self._prepare(Y, L, psi0, loc0, K, S, X, extra_loglik, learning_rate, device, y_storage, seed, rank, world, profile,
                                   y_device_ptr, y_device_dtype, shape, layout, cell_index, gene_index, variant_off, variant_on, tune, verbose,
                                   comm_timeout_ms, gate_timeout_us)
-        rc = self.lib.ca_create(C.byref(prob), C.byref(opt), C.byref(self.h))
+        if self._sparse is not None:
+            rc = self.lib.ca_create_sparse(C.byref(prob), C.byref(self._sparse), C.byref(opt), C.byref(self.h))
+        else:
+            rc = self.lib.ca_create(C.byref(prob), C.byref(opt), C.byref(self.h))
         if rc != CA_OK:
             msg = (self.lib.ca_last_error(None) or b"").decode()
             self.h = C.c_void_p()
@@ -292,7 +363,13 @@ class HipEngine:
         mat = lambda a, shape=None: np.require(  # noqa: E731  (a contiguous float64 matrix in the problem's layout)
             np.asarray(a, dtype=np.float64) if shape is None else np.asarray(a, dtype=np.float64).reshape(shape),
             requirements=[self._order, "A"])
-        if y_device_ptr is not None:
+        self._sparse = None
+        if y_device_ptr is None and (is_sparse(Y) or "sparse_cs" in str(getattr(Y, "layout", ""))):
+            # CSR / CSC arrays as they are (ca_create_sparse); Y = NULL in the problem
+            Ns, Gs = (int(d) for d in Y.shape)
+            self._sparse, self._keep = sparse_counts(Y) if is_sparse(Y) else _torch_sparse_counts(Y)
+            y_dt, y_ptr = CA_F64, None
+        elif y_device_ptr is not None:
             Ns, Gs = shape
             y_dt = _Y_DTYPES[np.dtype(y_device_dtype)]
             y_ptr = C.c_void_p(int(y_device_ptr))
@@ -613,7 +690,11 @@ class HipGroupEngine(HipEngine):
                                   comm_timeout_ms, gate_timeout_us)
         self.devices = [int(d) for d in devices]
         dev = (C.c_int32 * len(self.devices))(*self.devices)
-        rc = self.lib.ca_group_create(C.byref(prob), C.byref(opt), dev, len(self.devices), self._TRANSPORT[transport], C.byref(self.h))
+        if self._sparse is not None:
+            rc = self.lib.ca_group_create_sparse(C.byref(prob), C.byref(self._sparse), C.byref(opt), dev, len(self.devices),
+                                                 self._TRANSPORT[transport], C.byref(self.h))
+        else:
+            rc = self.lib.ca_group_create(C.byref(prob), C.byref(opt), dev, len(self.devices), self._TRANSPORT[transport], C.byref(self.h))
         if rc != CA_OK:
             msg = (self.lib.ca_group_last_error(None) or b"").decode()
             self.h = C.c_void_p()

@@ -43,13 +43,51 @@ def gene_filter(Y, L, gene_filter_threshold=0):
     return np.ascontiguousarray(Y[:, keep]), L[keep, :], keep
 
 
+def is_sparse(Y):
+    """A scipy.sparse count matrix (kept sparse on every path that has a device-side form)."""
+    import scipy.sparse as sps
+    return sps.issparse(Y)
+
+
+def _sparse_selected_sums(Y, rows, cols, axis):
+    """selected_sums of a scipy.sparse matrix in O(nnz): products with the 0 / 1 indicator of the other axis's selection (float64 --
+    exact for integer counts, every partial sum is an integer below 2^53).  Taken over slices of about 1M stored entries along the
+    format's major axis: scipy upcasts the values of a matrix it multiplies by a float64 vector, and a float64 copy of ALL the values
+    would be 8 bytes per stored count."""
+    N, G = Y.shape
+    if Y.format not in ("csr", "csc"):
+        Y = Y.tocsr()
+    wr = np.ones(N) if rows is None else np.bincount(np.asarray(rows), minlength=N).astype(np.float64)
+    wc = np.ones(G) if cols is None else np.bincount(np.asarray(cols), minlength=G).astype(np.float64)
+    major = N if Y.format == "csr" else G
+    step = max(1, int(major * (1 << 20) // max(Y.nnz, 1)))
+    out = np.zeros(G if axis == 0 else N)
+    for a in range(0, major, step):
+        b = min(major, a + step)
+        if Y.format == "csr":
+            part = Y[a:b]
+            if axis == 0:
+                out += part.T @ wr[a:b]
+            else:
+                out[a:b] = part @ wc
+        else:
+            part = Y[:, a:b]
+            if axis == 0:
+                out[a:b] = part.T @ wr
+            else:
+                out += part @ wc[a:b]
+    return out[np.asarray(cols)] if axis == 0 and cols is not None else out[np.asarray(rows)] if axis == 1 and rows is not None else out
+
+
 def selected_sums(Y, rows, cols, axis):
     """colSums (axis=0) / rowSums (axis=1) of Y[rows][:, cols] in float64 WITHOUT materialising the sub-matrix.
     Integer counts: the full sums minus the sums over the dropped rows / columns when less is dropped than kept (masks
     from preprocessing keep almost everything) -- exact, every partial sum is an integer below 2^53.  Floating-point
     counts are always summed directly over the selection: the subtraction would leave rounding residue (a true 0 coming
     out as 1e-12) exactly where the gene filter compares against its threshold (R/inference-tflow.R:117-124).
-    rows / cols: sorted index arrays or None (= all)."""
+    rows / cols: sorted index arrays or None (= all).  A scipy.sparse Y: _sparse_selected_sums."""
+    if is_sparse(Y):
+        return _sparse_selected_sums(Y, rows, cols, axis)
     N, G = Y.shape
     rows = None if rows is None or len(rows) == N else np.asarray(rows)
     cols = None if cols is None or len(cols) == G else np.asarray(cols)

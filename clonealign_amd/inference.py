@@ -73,6 +73,21 @@ def run_vi_loop(eng, eps, max_iter, rel_tol, verbose=False):
     return elbos
 
 
+def _sparse_input(Y, cell_index, gene_index, engine, engine_opts, psi_init, K):
+    """A scipy.sparse Y_dat: kept sparse (CSR / CSC) where the HIP engine cuts the matrix on the device -- above 4e6 selected counts,
+    the size at which a dense matrix takes that path -- else densified (a small matrix, or an engine without a device-side ingest)."""
+    sel = lambda m, n: n if m is None else int(np.count_nonzero(m)) if np.asarray(m).dtype == bool else len(m)  # noqa: E731
+    if not (engine is None and sel(cell_index, Y.shape[0]) * sel(gene_index, Y.shape[1]) > 4_000_000):
+        return Y.toarray()
+    if int((engine_opts or {}).get("world", 1)) != 1:
+        raise ValueError("a sparse count matrix is not densified on the host, and one process per GPU (engine_opts rank/world) needs the "
+                         "host matrix; shard the fit inside this process with devices=[...] instead")
+    if psi_init == "host" and int(K) > 0:
+        raise ValueError("psi_init='host' needs the dense count matrix on the host, which a sparse input above 4e6 counts does not get; "
+                         "use psi_init='auto' / 'device' (the device PCA), or shard with devices=[...]")
+    return Y if Y.format in ("csr", "csc") else Y.tocsr()
+
+
 def inference_tflow(Y_dat, L_dat, max_iter=100, rel_tol=1e-5, learning_rate=0.1,
                     gene_filter_threshold=0, x=None, clone_allele=None, cov=None, ref=None,
                     fix_alpha=False, dtype="float32", saturate=True, saturation_threshold=6,
@@ -102,6 +117,10 @@ def inference_tflow(Y_dat, L_dat, max_iter=100, rel_tol=1e-5, learning_rate=0.1,
     joined by the first transport that passes its known-answer test (peer-to-peer by address -> RCCL -> host reduction;
     ``engine_opts={"transport": ...}`` insists on one).  The return value is the one-device fit's for all cells (trace to the
     grouping of the fp64 cell sums).  One ordinal, or None, is the plain single-device fit on that device.
+    ``Y_dat`` may be a scipy.sparse matrix: above 4e6 selected counts (HIP engine) it stays sparse -- gene filter and cell sums from
+    O(nnz) scipy sums, the engine's device PCA and mu initialisation, the CSR / CSC arrays handed to ca_create_sparse -- and no N x G
+    array is made on the host; ``psi_init="host"`` and engine_opts rank / world then raise (they need the host matrix).  Otherwise it is
+    densified and takes the dense path.
     ``_reuse``: a dict owned by run_clonealign()'s restart loop (multirun.py).  The first fit leaves its prepared inputs and
     its engine in it; later fits on the SAME data and settings skip the host passes and the upload and restart the resident
     engine (``ca_reinit``).  The owner closes the engine.
@@ -132,10 +151,13 @@ def inference_tflow(Y_dat, L_dat, max_iter=100, rel_tol=1e-5, learning_rate=0.1,
             engine_opts["devices"] = devices
     cached = None if _reuse is None else _reuse.get("prep")
     if cached is None:
-        Y_dat = np.asarray(Y_dat)
-        if Y_dat.dtype not in (np.float64, np.float32, np.int32, np.uint16, np.uint8):   # dtypes the engine uploads as they are
-            fits = Y_dat.dtype.kind in "iu" and Y_dat.size and 0 <= Y_dat.min() and Y_dat.max() <= np.iinfo(np.int32).max
-            Y_dat = Y_dat.astype(np.int32 if fits else np.float64)
+        if hostprep.is_sparse(Y_dat):
+            Y_dat = _sparse_input(Y_dat, cell_index, gene_index, engine, engine_opts, psi_init, K)
+        if not hostprep.is_sparse(Y_dat):
+            Y_dat = np.asarray(Y_dat)
+            if Y_dat.dtype not in (np.float64, np.float32, np.int32, np.uint16, np.uint8):   # dtypes the engine uploads as they are
+                fits = Y_dat.dtype.kind in "iu" and Y_dat.size and 0 <= Y_dat.min() and Y_dat.max() <= np.iinfo(np.int32).max
+                Y_dat = Y_dat.astype(np.int32 if fits else np.float64)
         L_dat = np.asarray(L_dat, dtype=np.float64)
         # optional selection of rows / columns of the raw matrix (masks of preprocess_for_clonealign)
         as_index = lambda m, n: None if m is None else (np.flatnonzero(np.asarray(m)) if np.asarray(m).dtype == bool  # noqa: E731

@@ -8,7 +8,8 @@ of the device form.
 """
 import numpy as np
 
-from .api import _parse_cnv, _parse_expression
+from . import hostprep
+from .api import _is_sparse, _parse_cnv, _parse_expression
 
 
 def _mad(x, constant=1.4826):
@@ -19,7 +20,10 @@ def _mad(x, constant=1.4826):
 
 def get_outlying_genes(Y, nmads):
     """R/preprocess.R:59-63."""
-    gene_means = np.asarray(Y, dtype=np.float64).mean(0)
+    return _outlying(np.asarray(Y, dtype=np.float64).mean(0), nmads)
+
+
+def _outlying(gene_means, nmads):
     md = _mad(gene_means)
     return gene_means > gene_means.mean() + nmads * md
 
@@ -34,7 +38,9 @@ def preprocess_for_clonealign(gene_expression_data, copy_number_data, min_counts
     ``return_masks=True`` (device statistics): no filtered copy of the count matrix is made -- the result carries
     ``keep_cells`` / ``keep_genes`` (boolean masks over the input) next to the filtered copy-number matrix and names, for
     ``clonealign(raw, result["copy_number_data"], cell_index=result["keep_cells"], gene_index=result["keep_genes"])``: the
-    engine cuts the raw matrix at upload (ca_problem.cell_index / gene_index; the reference returns copies, :141-147)."""
+    engine cuts the raw matrix at upload (ca_problem.cell_index / gene_index; the reference returns copies, :141-147).
+    A scipy.sparse count matrix (the reference's dgCMatrix) is filtered from O(nnz) host sums; the filtered matrix is returned as CSR,
+    ``return_masks=True`` works, ``on="device"`` raises (ca_preprocess takes a dense matrix)."""
     Y, gn = _parse_expression(gene_expression_data)
     L, _ = _parse_cnv(copy_number_data)
     G = Y.shape[1]
@@ -44,6 +50,12 @@ def preprocess_for_clonealign(gene_expression_data, copy_number_data, min_counts
     cells = np.array(cell_names if cell_names is not None else np.arange(Y.shape[0]))
     if on not in ("auto", "host", "device"):
         raise ValueError("on must be 'auto', 'host' or 'device'")
+    if _is_sparse(Y):
+        if on == "device":
+            raise ValueError("on='device' takes a dense count matrix (ca_preprocess); a sparse one is filtered with O(nnz) host sums "
+                             "(on='auto' / 'host')")
+        return _preprocess_sparse(Y, L, genes, cells, min_counts_per_gene, min_counts_per_cell, remove_outlying_genes, nmads,
+                                  max_copy_number, remove_genes_same_copy_number, return_masks)
     if on == "device" or (on == "auto" and Y.size > 20_000_000):
         from .engine import preprocess_masks
         kg, kc, _gs, _cs = preprocess_masks(Y, L, min_counts_per_gene, min_counts_per_cell, remove_outlying_genes, nmads,
@@ -79,4 +91,29 @@ def preprocess_for_clonealign(gene_expression_data, copy_number_data, min_counts
         "copy_number_data": L,
         "retained_cells": cells,
         "retained_genes": genes,
+    }
+
+
+def _preprocess_sparse(Y, L, genes, cells, min_counts_per_gene, min_counts_per_cell, remove_outlying_genes, nmads, max_copy_number,
+                       remove_genes_same_copy_number, return_masks):
+    """The filters of R/preprocess.R:114-139 on a scipy.sparse count matrix, in the same order, from O(nnz) sums (float64: exact for
+    integer counts, so every decision is the dense one).  A gene's statistics do not depend on the other genes, so one colSums serves
+    all gene filters; the mean / MAD of the outlier rule are taken over the genes kept so far, as on the dense path."""
+    N = Y.shape[0]
+    colsum = hostprep.selected_sums(Y, None, None, 0)
+    kg = ~(L.max(1) > max_copy_number)                              # :114-116
+    kg &= colsum > min_counts_per_gene                              # :118-120
+    if remove_outlying_genes:                                       # :123-128
+        kg[kg] = ~_outlying(colsum[kg] / N, nmads)
+    if remove_genes_same_copy_number:                               # :131-135
+        kg[kg] = ~(L[kg].var(1, ddof=1) == 0)
+    kc = hostprep.selected_sums(Y, None, np.flatnonzero(kg), 1) > min_counts_per_cell   # :138-139
+    if return_masks:
+        return {"keep_cells": kc, "keep_genes": kg, "copy_number_data": L[kg, :], "retained_cells": cells[kc],
+                "retained_genes": genes[kg]}
+    return {
+        "gene_expression_data": Y.tocsr()[np.flatnonzero(kc)][:, np.flatnonzero(kg)],
+        "copy_number_data": L[kg, :],
+        "retained_cells": cells[kc],
+        "retained_genes": genes[kg],
     }

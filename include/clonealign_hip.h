@@ -240,6 +240,31 @@ int ca_default_options(ca_options* opts);
  * A = Y.log L, column sums), zero-initialise the variables as :240-272 does.
  * Replaces graph construction + `sess$run(init)` (:240-353). */
 int ca_create(const ca_problem* problem, const ca_options* opts, ca_handle* out);
+
+/* Sparse count matrices (additions to ABI 6): the compressed form of Y -- scipy's csr / csc matrices, R's dgCMatrix -- goes to the
+ * device as it is (no N x G copy on the host or in a staging buffer), is validated and scanned there, and is expanded into the same
+ * resident [N][Gp] matrix (and u8 overflow list) ca_create builds from the dense form: every fit on it is the dense fit, bit for bit.
+ * Implicit zeros are zeros; the storage pick (ca_options.y_storage, AUTO) is taken over the SELECTED counts exactly as for a dense Y. */
+enum ca_sparse_kind { CA_SPARSE_CSR = 0,   /* one run per cell: ptr has N_src + 1 entries, idx are gene indices
+                                              (scipy csr of cells x genes; the CSC dgCMatrix of a genes x cells assay) */
+                      CA_SPARSE_CSC = 1 }; /* one run per gene: ptr has G_src + 1 entries, idx are cell indices (dgCMatrix / scipy csc of cells x genes) */
+typedef struct ca_sparse {
+  int32_t kind;         /* ca_sparse_kind */
+  int32_t val_dtype;    /* ca_dtype of val: CA_F64 (R's @x), CA_F32, CA_I32, CA_U16, CA_U8 */
+  int32_t index_bytes;  /* 4 or 8: width of ptr AND idx (R: 4; scipy: 4 or 8; torch: 8) */
+  int32_t on_device;    /* ptr / idx / val are device pointers on ca_options.device */
+  int64_t nnz;
+  const void* ptr;
+  const void* idx;      /* canonical: strictly increasing within each run; explicit zeros allowed */
+  const void* val;
+} ca_sparse;
+/* ca_create with the count matrix in compressed form.  problem->Y must be NULL; y_dtype, y_on_device and y_ld are ignored; layout
+ * still applies to L, psi0, X, extra_loglik and the outputs.  The matrix is N_src x G_src with a selection (cell_index / gene_index,
+ * as for ca_create), else N x G.  Canonical form, checked on the device (CA_ERR_INVALID with a message otherwise): ptr[0] = 0,
+ * ptr never decreases, ptr[last] = nnz, every idx in range and strictly increasing within its run.  Host arrays go up in their own
+ * dtype (float64 values narrowed to float32 on the way, as a dense float64 Y is); peak device memory while ingesting is the resident
+ * matrix plus the compressed arrays (plus their CSR transpose for CSC).  The arrays are read during the call only. */
+int ca_create_sparse(const ca_problem* problem, const ca_sparse* y, const ca_options* opts, ca_handle* out);
 int ca_destroy(ca_handle h);
 const char* ca_last_error(ca_handle h); /* h may be NULL: error of the last failed ca_create on this thread */
 int ca_get_info(ca_handle h, ca_info* info);
@@ -436,6 +461,11 @@ typedef struct ca_group_info {
 } ca_group_info;
 int ca_group_create(const ca_problem* problem, const ca_options* opts, const int32_t* devices, int32_t n_devices, int32_t transport,
                     ca_group_handle* out);
+/* ca_group_create with the count matrix in compressed form (ca_create_sparse's contract; problem->Y must be NULL): rank r takes its
+ * cells as a cell_index subset over the same compressed arrays (host CSR: its rows' runs only).  Device arrays only when every rank
+ * is on that device.  The arrays are read during the call only. */
+int ca_group_create_sparse(const ca_problem* problem, const ca_sparse* y, const ca_options* opts, const int32_t* devices,
+                           int32_t n_devices, int32_t transport, ca_group_handle* out);
 int ca_group_destroy(ca_group_handle g);
 const char* ca_group_last_error(ca_group_handle g);   /* g may be NULL: the last failed ca_group_create on this thread */
 int ca_group_get_info(ca_group_handle g, ca_group_info* info);

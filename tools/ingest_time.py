@@ -6,7 +6,13 @@
 For float64 column-major (R), int32 column-major and int32 row-major host matrices of the same counts:
   ca_create (HipEngine(...)) wall time, against the same engine built from a DEVICE pointer (no host bytes to move) -- the
   difference is the ingestion; then ca_run(200) + 20 final ELBOs.  Beside it the box's own copy rates for the same bytes:
-  pinned hipMemcpy (the roof of any upload) and pageable hipMemcpy (what a single full-size copy gets)."""
+  pinned hipMemcpy (the roof of any upload) and pageable hipMemcpy (what a single full-size copy gets).
+
+  python tools/ingest_time.py --sparse [cells genes clones]
+
+The sparse leg (profiles/r07_sparse_ingest.txt): ca_create_sparse of the synth_data.make_problem matrix as CSR (int32 indices; values
+in the narrowest exact dtype -- uint8, or uint16 when some count exceeds 255 -- and in float64) and as CSC with int32 indices and float64 values (R's dgCMatrix), against ca_create of the same matrix as float64
+column-major (R's dense matrix) and int32 row-major.  Every form must give the same storage and the same 20-iteration trace."""
 import argparse
 import ctypes
 import sys
@@ -24,8 +30,53 @@ ap = argparse.ArgumentParser()
 ap.add_argument("shape", nargs="*", type=int, default=[100_000, 5_000, 8])
 ap.add_argument("--tag", default="")
 ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--sparse", action="store_true")
 args = ap.parse_args()
 N, G, C = args.shape
+
+
+def sparse_leg():
+    import scipy.sparse as sps
+    print(f"== ingest_time --sparse {args.tag}: {N} x {G} x {C}, build {build_id()}")
+    prob = synth.make_problem(N, G, C, seed=20240)
+    Yh, L = prob["Y"], prob["L"]
+    psi0 = np.random.default_rng(1).normal(size=(N, 1))
+    csr = sps.csr_matrix(Yh)
+    nnz = csr.nnz
+    # the narrowest exact value dtype (uint8 when every count is below 256, else uint16: what engine.sparse_counts would pick)
+    csr_small = sps.csr_matrix((csr.data.astype(np.uint8 if csr.data.max() <= 255 else np.uint16), csr.indices, csr.indptr), shape=csr.shape)
+    csr_f64 = sps.csr_matrix((csr.data.astype(np.float64), csr.indices, csr.indptr), shape=csr.shape)
+    csc_f64 = csr_f64.tocsc()
+    print(f"nnz {nnz} ({nnz / (N * G) * 100:.1f} % of the counts); max count {int(csr.data.max())}")
+    forms = [("dense float64 col-major (R)", np.asfortranarray(Yh.astype(np.float64)), "col"), ("dense int32 row-major", Yh, "row"),
+             (f"CSR int32 idx, {csr_small.data.dtype} val", csr_small, "row"), ("CSR int32 idx, float64 val", csr_f64, "row"),
+             ("CSC int32 idx, float64 val (dgCMatrix)", csc_f64, "row")]
+    ref = None
+    for name, Y, lay in forms:
+        Lx = np.asfortranarray(L) if lay == "col" else L
+        ts, eng = [], None
+        for _ in range(args.reps):
+            if eng is not None:
+                eng.close()
+            t0 = time.perf_counter()
+            eng = HipEngine(Y, Lx, psi0, None, 1, layout=lay)
+            eng.synchronize()
+            ts.append(time.perf_counter() - t0)
+        if sps.issparse(Y):
+            hb = Y.data.nbytes + Y.indices.nbytes + Y.indptr.nbytes
+        else:
+            hb = Y.nbytes
+        tr = eng.run(None, 20, 1e-12)
+        st = (eng.info()["y_storage_name"], tr.tolist())
+        ref = st if ref is None else ref
+        print(f"{name:40s} {hb / 1e9:5.2f} GB host: ca_create{'_sparse' if sps.issparse(Y) else ''} {min(ts) * 1e3:7.1f} ms "
+              f"(median {float(np.median(ts)) * 1e3:.1f}); storage {st[0]}; same 20-iteration trace as the first form: {st == ref}")
+        eng.close()
+
+
+if args.sparse:
+    sparse_leg()
+    sys.exit(0)
 print(f"== ingest_time {args.tag}: {N} x {G} x {C}, build {build_id()}")
 Yd, aux = synth.make_problem_torch(N, G, C, seed=20243, device="cuda:0")
 rm = Yd.sum(1, keepdim=True).to(torch.float64) / G
