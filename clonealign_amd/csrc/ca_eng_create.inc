@@ -409,7 +409,37 @@ int create_impl(ca_engine* h, const ca_problem* p) {
     h->ys_RS = 64;
     while (h->ys_RS < 512 && cdiv(Nn, 4 * h->ys_RS) * h->ys_nseg > 4 * h->n_cu) h->ys_RS *= 2;
     h->ys_nrg = cdiv(Nn, 4 * h->ys_RS);
-    CACK(dalloc(h, &h->Ys, h->ys_N64 * h->Gp));
+    // the loop image at 4 bits per count (CA_VAR_Y4): by default for the series form only (its stream is a launch of its own; the sweeps' riding
+    // forms keep the 1-byte body) and where the escape list (stored counts >= 15) is at most 1 in 256 counts -- the shapes measured, at about
+    // 1 in 370 (profiles/r07_*); CA_VARX_Y4 forces it at any shape and fraction.  A deterministic function of the shape and the matrix (int
+    // offsets: below 2^31 counts)
+    const bool y4_force = variantx_on(h, CA_VARX_Y4, "CA_Y4_ON");
+    if (variant_on(h, CA_VAR_Y4, "CA_Y4") && (h->poly || y4_force) && (double)Nn * (double)h->Gp < 2.0e9) {
+      const int64_t nkeys = (int64_t)h->ys_nrg * h->ys_nseg * 4 * h->ys_RS;
+      CACK(dalloc(h, &h->esc_off, nkeys + 1));
+      const int64_t nw = Nn * h->ys_nseg;
+      hipLaunchKernelGGL(k_esc_count, dim3(cdiv(nw * 64, CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, Nn, h->Gp, h->ys_nseg, h->ys_RS,
+                         h->esc_off);
+      hipLaunchKernelGGL(k_esc_scan, dim3(1), dim3(1024), 0, h->stream, h->esc_off, nkeys);
+      HIPCK(h, hipGetLastError());
+      int total = 0;
+      HIPCK(h, hipMemcpyAsync(&total, h->esc_off + nkeys, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+      SYNC(h);
+      h->n_esc = total;
+      h->ys4 = h->n_esc * 256 <= Nn * (int64_t)h->G || y4_force;
+      if (!h->ys4) {   // the offsets were the last allocation: returned, nothing of the 4-bit image stays resident
+        HIPCK(h, hipFree(h->esc_off));
+        h->allocs.pop_back();
+        h->dev_bytes -= 4 * (nkeys + 1);
+        h->esc_off = nullptr;
+      } else {
+        CACK(dalloc(h, &h->esc, h->n_esc));
+        hipLaunchKernelGGL(k_esc_fill, dim3(cdiv(nw * 64, CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, Nn, h->Gp, h->ys_nseg, h->ys_RS,
+                           h->esc_off, h->esc);
+        HIPCK(h, hipGetLastError());
+      }
+    }
+    CACK(dalloc(h, &h->Ys, h->ys_N64 * h->Gp / (h->ys4 ? 2 : 1)));
     uint8_t *wr = nullptr, *pr = nullptr;
     CACK(dalloc(h, &wr, (int64_t)(h->Gp / 64) * 1024));
     CACK(dalloc(h, &pr, (h->ys_N64 / 64) * 1024));
@@ -423,8 +453,12 @@ int create_impl(ca_engine* h, const ca_problem* p) {
     h->ys_nq = cdiv((int64_t)(h->Gp / 64) + h->ys_N64 / 64, CA_YM_TB / 64);
     h->ys_ncap = std::max(h->ys_nq, h->ngblk + cdiv(Nn, CA_TB)) + 2;
     CACK(dalloc(h, &h->ys_amaxp, (int64_t)3 * h->ys_ncap * 2));
-    hipLaunchKernelGGL(k_bias_y, dim3(cdiv(h->ys_N64 * (h->Gp / 16), CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, (uint4*)h->Ys, Nn,
-                       h->ys_N64, h->Gp);
+    if (h->ys4)
+      hipLaunchKernelGGL(k_pack_y4, dim3(cdiv(h->ys_N64 * (h->Gp / 32), CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, (uint4*)h->Ys, Nn,
+                         h->ys_N64, h->Gp);
+    else
+      hipLaunchKernelGGL(k_bias_y, dim3(cdiv(h->ys_N64 * (h->Gp / 16), CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, (uint4*)h->Ys, Nn,
+                         h->ys_N64, h->Gp);
     HIPCK(h, hipGetLastError());
     {
       // what ONE TF1-Adam step can add to a magnitude: lr_t |m| / sqrt(v) <= lr_t (1 - b1) / sqrt((1 - b2)(1 - b1^2 / b2)) (Cauchy-
@@ -437,7 +471,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
       }
     }
     h->y_ys = true;
-    h->y_dev_bytes += h->ys_N64 * h->Gp;
+    h->y_dev_bytes += h->ys4 ? h->ys_N64 * h->Gp / 2 + 4 * h->n_esc + 4 * ((int64_t)h->ys_nrg * h->ys_nseg * 4 * h->ys_RS + 1) : h->ys_N64 * h->Gp;
   }
   // the Y stream rides on the forward sweep's launch: 1-byte storage, K = 1, the fused sweep with its default block shapes
   h->ride_ok = h->ystore == CA_YSTORE_U8 && K == 1 && D <= 2 && h->fused_ok && !h->c16 && h->fwd_cell && (h->fc_tl == 6 || h->fc_tl == 8 || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
@@ -445,7 +479,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   constexpr bool kRideSeqDefault = false;
   h->ride_seq = h->ride_ok && variant_on(h, CA_VAR_RIDE_SEQ, "CA_RIDE_SEQ") && (kRideSeqDefault || lab_variantx_on(h, CA_VARX_RIDE_SEQ, "CA_RIDE_SEQ_ON"));
   const bool tl1_ok = h->fc_tl == 1 && h->fc_nbig == 0 && !h->c16;
-  h->ride_ys = h->y_ys && D <= 2 && h->fused_ok && h->fwd_cell && (h->fc_tl == 6 || tl1_ok || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
+  h->ride_ys = h->y_ys && (!h->ys4 || (h->poly && D == 1 && !h->c16 && !h->s2)) && D <= 2 && h->fused_ok && h->fwd_cell && (h->fc_tl == 6 || tl1_ok || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
                variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE");
   h->yfin_split = h->ride_ys && h->bwd_mfma && h->tail_fuse && variant_on(h, CA_VAR_YFIN_RIDE, "CA_YFIN_RIDE");
   // The int8 one-copy stream either rides or runs in line: as a launch of its own on the SIDE stream (variant y_ride off at 4e7 counts and more) its parameter

@@ -155,10 +155,12 @@ int ys_quant(ca_engine* h) {
   LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_ys_quant, dim3(a.nblk), dim3(CA_YM_TB), 0, h->stream, a));
   return CA_OK;
 }
+// (with the 4-bit image the body reads neither Wsum nor Psum -- no bias to undo; the quantiser still writes them, a few KB per pass)
 ca_ys_io ys_io(ca_engine* h) {
   ca_ys_io io;
   io.Wr = h->Wr; io.Pr = h->Pr; io.Wsum = h->Wsum; io.Psum = h->Psum; io.exps = h->ys_exps + 2 * h->ys_slot;
   io.YWpart = h->YWpart; io.YTpart = h->YTpart;
+  io.esc_off = h->ys4 ? h->esc_off : nullptr; io.esc = h->ys4 ? h->esc : nullptr;
   return io;
 }
 ca_ovf_args ys_ovf(ca_engine* h) {
@@ -209,11 +211,16 @@ int ycache_ys(ca_engine* h) {
   const int nb_main = h->ys_nrg * h->ys_nseg;
   if (h->n_ovf > 0) {
     const ca_ovf_args ovf = ys_ovf(h);
-    LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf, dim3(nb_main + ovf.nb_rows + ovf.nb_chunks), dim3(CA_YM_TB), CA_YS_LDS_BYTES,
-                                                  h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D));
+    const dim3 grid(nb_main + ovf.nb_rows + ovf.nb_chunks);
+    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf<true>, grid, dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
+                                                              h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D));
+    else LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf<false>, grid, dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
+                                                       h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D));
   } else {
-    LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma, dim3(nb_main), dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
-                                                  h->Gp, h->ys_RS));
+    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma<true>, dim3(nb_main), dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h),
+                                                              h->N, h->Gp, h->ys_RS));
+    else LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma<false>, dim3(nb_main), dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h),
+                                                       h->N, h->Gp, h->ys_RS));
   }
   const bool defer = h->ys_defer_next;
   h->ys_defer_next = false;
@@ -1223,9 +1230,13 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     if (h->opt.ride_pattern < 0) ya.pers = std::min(-h->opt.ride_pattern, ya.nb_main);
     else if (h->opt.ride_pattern == 0 && ya.nb_main >= 2 * h->n_cu) ya.pers = h->n_cu;
     const dim3 grid(ya.pers > 0 ? (unsigned)(ya.pers + h->ncblk_f + (ya.nb_y - ya.nb_main)) : (unsigned)(h->ncblk_f + ya.nb_y));
-#define CA_FCYS(DV, TLBV, DPV, C16V, S2FV)                                                                                            \
-  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_ys<DV, TLBV, 2, DPV, C16V, S2FV>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, \
+#define CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, Y4V)                                                                                                   \
+  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_ys<DV, TLBV, 2, DPV, C16V, S2FV, Y4V>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, \
                                               h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya))
+// (the 4-bit image rides only with the series form's shapes: D = 1, no c16 / s2 -- ride_ys, ca_eng_create.inc)
+#define CA_FCYS(DV, TLBV, DPV, C16V, S2FV) do {                                                                          \
+    if constexpr (DV == 1 && !C16V && !S2FV) { if (h->ys4) CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, true); else CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, false); } \
+    else CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, false); } while (0)
 #define CA_FCYS_D(TLBV, DPV) do { if (h->c16) { if (h->D == 1) CA_FCYS(1, TLBV, DPV, true, false); else CA_FCYS(2, TLBV, DPV, true, false); }  \
                                   else if (s2f) { if (h->D == 1) CA_FCYS(1, TLBV, DPV, false, true); else CA_FCYS(2, TLBV, DPV, false, true); } \
                                   else { if (h->D == 1) CA_FCYS(1, TLBV, DPV, false, false); else CA_FCYS(2, TLBV, DPV, false, false); } } while (0)
@@ -1249,7 +1260,8 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
       //  ride_pattern = 2 asks for two)
       ba.stream_units = h->opt.ride_pattern == 2 ? 2 : 1;
       const dim3 gridb((unsigned)(h->n_cu + ba.extra + (ba.stream_units == 2 ? (ya.nb_main + 1) / 2 : ya.nb_main) + (ya.nb_y - ya.nb_main)));   // sweep blocks, left-over tiles' blocks, stream blocks, the overflow list's
-#define CA_FBAL(TLV) LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_bal_ys<1, TLV, CA_YS_RIDE_DEPTH>), gridb, dim3(CA_BAL_TB), 0, h->stream, h->F, h->etamax2, \
+#define CA_FBAL(TLV) if (h->ys4) CA_FBAL_L(TLV, true); else CA_FBAL_L(TLV, false)
+#define CA_FBAL_L(TLV, Y4V) LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_bal_ys<1, TLV, CA_YS_RIDE_DEPTH, Y4V>), gridb, dim3(CA_BAL_TB), 0, h->stream, h->F, h->etamax2, \
                                                                  h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, ba, ya))
       switch (h->bal_q) {
         case 1: CA_FBAL(1); break;
@@ -1260,12 +1272,14 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
         default: CA_FBAL(6); break;
       }
 #undef CA_FBAL
+#undef CA_FBAL_L
     } else
     if (h->fc_tl == 6) CA_FCYS_D(6, CA_YS_RIDE_DEPTH);
     else if (h->fc_tl == 1 && !h->c16) { if (h->D == 1) CA_FCYS(1, 1, CA_YS_RIDE_DEPTH, false, false); else CA_FCYS(2, 1, CA_YS_RIDE_DEPTH, false, false); }
     else CA_FCYS_D(2, CA_YS_RIDE_DEPTH);
 #undef CA_FCYS_D
 #undef CA_FCYS
+#undef CA_FCYS_L
     CACK(ys_finish(h, h->yfin_split && (!is_sharded(h) || p2p_ride_ok(h, h->red_n))));
   } else if (h->fwd_cell && ride) {   // ... and the Y stream's blocks interleaved with the sweep's in the same grid
     cell_blocks = h->ncblk_f;

@@ -200,7 +200,8 @@ struct ca_engine {
   uint4 *Yf = nullptr, *Yb = nullptr, *Wq = nullptr, *Pq = nullptr; unsigned* ym_amax = nullptr; int* ym_out = nullptr;
   hipEvent_t ev_ywdone = nullptr; bool yw_pending = false, on_side = false;
   // ... and from ONE tiled copy through the transposing LDS read (k_ys_mfma; K = 1)
-  bool y_ys = false; uint8_t* Ys = nullptr; uint4 *Wr = nullptr, *Pr = nullptr; int *Wsum = nullptr, *Psum = nullptr;
+  bool y_ys = false, ys4 = false; int* esc_off = nullptr; unsigned* esc = nullptr; int64_t n_esc = 0;
+  uint8_t* Ys = nullptr; uint4 *Wr = nullptr, *Pr = nullptr; int *Wsum = nullptr, *Psum = nullptr;
   int* ys_exps = nullptr;        // [3][2]: rotating slots, see ca_ys_quant_body
   unsigned* ys_amax = nullptr;   // [2]: exact maxima of a fresh state (k_ym_absmax), float bit patterns
   float* ys_amaxp = nullptr; int ys_nq = 0;   // [3][ys_ncap][2]: per-block maxima each quantiser run leaves for the next one

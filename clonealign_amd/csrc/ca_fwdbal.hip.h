@@ -156,7 +156,7 @@ __device__ __forceinline__ double ca_bal_block_sum(double v, double* sm /* >= CA
   return r;
 }
 
-template <int D, int TL, int DEPTH>
+template <int D, int TL, int DEPTH, bool Y4 = false>
 __global__ void __launch_bounds__(CA_BAL_TB, 2) k_fwd_bal_ys(const float* __restrict__ F, const float* __restrict__ etamax2,
                                                              const float* __restrict__ Vs, const unsigned short* __restrict__ Mq, ca_cell_ptrs p,
                                                              const float* __restrict__ alpha_u, double* __restrict__ cell_part, int64_t N, int C,
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(CA_BAL_TB, 2) k_fwd_bal_ys(const float* __rest
     const int idx = ba.stream_units == 2 ? 2 * sb + half : sb;
     if (idx >= y.nb_main) return;
     CA_PRIO_STREAM();
-    ca_ys_mfma_body<DEPTH>(idx, y.Ys, y.io, N, y.Gp, y.RS, smem + (size_t)half * CA_YS_LDS_BYTES);
+    ca_ys_mfma_body<DEPTH, Y4>(idx, y.Ys, y.io, N, y.Gp, y.RS, smem + (size_t)half * CA_YS_LDS_BYTES);
     return;
   }
   // ---- a sweep block

@@ -856,6 +856,7 @@ __global__ void __launch_bounds__(CA_TB) k_p2p_allreduce(double* __restrict__ bu
 }
 
 // the one-copy stream with the overflow list's per-entry work (cell side, then gene side) as extra blocks, like k_ypass
+template <bool Y4>
 __global__ void __launch_bounds__(CA_YM_TB, CA_YS_WAVES) k_ys_mfma_ovf(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS,
                                                                        int nb_main, ca_ovf_args ovf, const float* __restrict__ F,
                                                                        const float* __restrict__ V, int Dstride) {
@@ -866,7 +867,7 @@ __global__ void __launch_bounds__(CA_YM_TB, CA_YS_WAVES) k_ys_mfma_ovf(const uin
     return;
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];
-  ca_ys_mfma_body<CA_YS_DEPTH>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 
 // The one-copy int8 matrix-core stream RIDING on the forward sweep's launch (round 3).  The vector stream of k_fwd_cell_mix_y
@@ -887,7 +888,7 @@ struct ca_ysride_args {
 #ifndef CA_YS_RIDE_WAVES
 #define CA_YS_RIDE_WAVES 4   // waves per SIMD the merged launch's register budget is set for (lab: 3 = 168 VGPRs, three blocks per CU)
 #endif
-template <int D, int TLB, int TLS, int DEPTH, bool C16 = false, bool S2F = false>
+template <int D, int TLB, int TLS, int DEPTH, bool C16 = false, bool S2F = false, bool Y4 = false>
 __global__ void __launch_bounds__(CA_TB, (DEPTH == 1 && !C16 && !S2F) ? CA_YS_RIDE_WAVES : 3) k_fwd_cell_mix_ys(const float* __restrict__ F, const float* __restrict__ etamax2,
                                                            const float* __restrict__ Vs, const unsigned short* __restrict__ Mq,
                                                            ca_cell_ptrs p, const float* __restrict__ alpha_u,
@@ -923,10 +924,10 @@ __global__ void __launch_bounds__(CA_TB, (DEPTH == 1 && !C16 && !S2F) ? CA_YS_RI
     if (y.pers > 0) {
       for (int u = idx; u < y.nb_main; u += y.pers) {
         if (u != idx) __syncthreads();   // the previous unit's combine has been read by every wave before the LDS regions are reused
-        ca_ys_mfma_body<DEPTH>(u, y.Ys, y.io, N, y.Gp, y.RS, smem);
+        ca_ys_mfma_body<DEPTH, Y4>(u, y.Ys, y.io, N, y.Gp, y.RS, smem);
       }
     } else {
-      ca_ys_mfma_body<DEPTH>(idx, y.Ys, y.io, N, y.Gp, y.RS, smem);
+      ca_ys_mfma_body<DEPTH, Y4>(idx, y.Ys, y.io, N, y.Gp, y.RS, smem);
     }
     CA_YS_LEAVE();
   }

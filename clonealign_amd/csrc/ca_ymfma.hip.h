@@ -151,6 +151,98 @@ __global__ void __launch_bounds__(CA_YM_TB) k_bias_y(const uint8_t* __restrict__
   Ys[i] = v;
 }
 
+// ---------------------------------------------------------------- the 4-bit loop image and its escape list (CA_VAR_Y4)
+// Y4 [N64/64][Gp/64][2 loads][64 lanes][16 B], 2-KiB pieces in the walk of Ys: nibbles of min(y, 15), no bias (0..15 is a valid signed
+// byte).  Lane l = (j = l & 15, q = l >> 4) of load i, dword d, byte b: low nibble = cell 64 cs + 32 i + j, high nibble = cell 64 cs + 32 i
+// + 16 + j, gene 64 gb + 16 q + 4 d + b -- so v & 0x0F0F0F0F and (v >> 4) & 0x0F0F0F0F are the A operands of the row products for cell
+// tiles 2i and 2i + 1 straight from the load.  One thread per 16 bytes of the image.
+__device__ __forceinline__ unsigned ca_nib4(unsigned lo, unsigned hi) {
+  unsigned r = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const unsigned x = (lo >> (8 * b)) & 0xFFu, y = (hi >> (8 * b)) & 0xFFu;
+    r |= ((x < 15u ? x : 15u) | ((y < 15u ? y : 15u) << 4)) << (8 * b);
+  }
+  return r;
+}
+__global__ void __launch_bounds__(CA_YM_TB) k_pack_y4(const uint8_t* __restrict__ Y, uint4* __restrict__ Y4, int64_t N, int64_t N64, int Gp) {
+  const int64_t i = (int64_t)blockIdx.x * CA_YM_TB + threadIdx.x;
+  const int64_t nb = Gp / 64;
+  if (i >= (N64 / 64) * nb * 128) return;
+  const int l = (int)(i & 63), ld = (int)((i >> 6) & 1);
+  const int64_t piece = i >> 7, cs = piece / nb, gb = piece - cs * nb;
+  const int64_t n0 = cs * 64 + 32 * ld + (l & 15), n1 = n0 + 16;
+  const uint8_t* base = Y + gb * 64 + 16 * (l >> 4);
+  uint4 a = {0u, 0u, 0u, 0u}, b = {0u, 0u, 0u, 0u};
+  if (n0 < N) a = *reinterpret_cast<const uint4*>(base + n0 * (int64_t)Gp);
+  if (n1 < N) b = *reinterpret_cast<const uint4*>(base + n1 * (int64_t)Gp);
+  Y4[i] = (uint4){ca_nib4(a.x, b.x), ca_nib4(a.y, b.y), ca_nib4(a.z, b.z), ca_nib4(a.w, b.w)};
+}
+// Escape list: every stored count y >= 15 as ONE word, cell-in-strip (9 bits) | gene-in-segment (9 bits) << 9 | (y - 15) << 18 (y <= 255:
+// counts above keep 255 here and their excess in the overflow list).  Ordered by the stream's units -- row group rg, segment seg, wave
+// strip wv of RS cells -- then by cell, then by gene: key(n, seg) = ((rg nseg + seg) 4 + wv) RS + (n - strip start), esc_off[key] = first
+// entry of cell n in segment seg, esc_off[nkeys] = the total.  Built on the device: count, scan, fill (one wave per cell and segment).
+__device__ __forceinline__ int64_t ca_esc_key(int64_t n, int seg, int nseg, int RS) {
+  const int64_t s = n / RS;
+  return (((s >> 2) * nseg + seg) * 4 + (s & 3)) * RS + (n - s * RS);
+}
+__device__ __forceinline__ int ca_esc_count8(uint2 v) {
+  int c = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) c += (((v.x >> (8 * b)) & 0xFFu) >= 15u) + (((v.y >> (8 * b)) & 0xFFu) >= 15u);
+  return c;
+}
+__global__ void __launch_bounds__(CA_YM_TB) k_esc_count(const uint8_t* __restrict__ Y, int64_t N, int Gp, int nseg, int RS, int* __restrict__ off) {
+  const int64_t w = ((int64_t)blockIdx.x * CA_YM_TB + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (w >= N * nseg) return;
+  const int64_t n = w / nseg;
+  const int seg = (int)(w - n * nseg);
+  int c = ca_esc_count8(*reinterpret_cast<const uint2*>(Y + n * (int64_t)Gp + seg * 512 + 8 * lane));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if (lane == 0) off[ca_esc_key(n, seg, nseg, RS)] = c;
+}
+// exclusive scan of off[0 .. n) in place, off[n] = the total (create time: one block)
+__global__ void __launch_bounds__(1024) k_esc_scan(int* __restrict__ off, int64_t n) {
+  __shared__ int64_t sm[1024];
+  const int t = threadIdx.x;
+  const int64_t chunk = (n + 1023) / 1024, a = t * chunk, b = (a + chunk < n) ? a + chunk : n;
+  int64_t s = 0;
+  for (int64_t i = a; i < b; ++i) s += off[i];
+  sm[t] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {
+    const int64_t v = t >= o ? sm[t - o] : 0;
+    __syncthreads();
+    sm[t] += v;
+    __syncthreads();
+  }
+  int64_t run = sm[t] - s;
+  for (int64_t i = a; i < b; ++i) { const int c = off[i]; off[i] = (int)run; run += c; }
+  if (t == 1023) off[n] = (int)sm[1023];
+}
+__global__ void __launch_bounds__(CA_YM_TB) k_esc_fill(const uint8_t* __restrict__ Y, int64_t N, int Gp, int nseg, int RS, const int* __restrict__ off,
+                                                       unsigned* __restrict__ esc) {
+  const int64_t w = ((int64_t)blockIdx.x * CA_YM_TB + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (w >= N * nseg) return;
+  const int64_t n = w / nseg;
+  const int seg = (int)(w - n * nseg);
+  const uint2 v = *reinterpret_cast<const uint2*>(Y + n * (int64_t)Gp + seg * 512 + 8 * lane);
+  const int c = ca_esc_count8(v);
+  int x = c;   // inclusive prefix over the lanes
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(x, o, 64); if (lane >= o) x += u; }
+  int e = off[ca_esc_key(n, seg, nseg, RS)] + x - c;
+  const unsigned cl = (unsigned)(n % RS);
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const unsigned y = ((b < 4 ? v.x : v.y) >> (8 * (b & 3))) & 0xFFu;
+    if (y >= 15u) esc[e++] = cl | ((unsigned)(8 * lane + b) << 9) | ((y - 15u) << 18);
+  }
+}
+
 // ---------------------------------------------------------------- the two streams
 // streamed once: non-temporal, so the tiles do not push the sweeps' shared operands out of the XCD's L2
 __device__ __forceinline__ uint4 ca_ld_stream(const uint4* p) {
@@ -365,8 +457,14 @@ __device__ __forceinline__ uint4 ca_and4(uint4 a, unsigned m) { return (uint4){a
 struct ca_ys_io {
   const uint4* Wr; const uint4* Pr; const int* Wsum; const int* Psum; const int* exps;   // exps[0] for W, exps[1] for psi
   float* YWpart; float* YTpart;
+  const int* esc_off; const unsigned* esc;   // the 4-bit image's escape list (k_esc_fill); null: the image is the 1-byte one (Ys)
 };
-template <int DEPTH = CA_YS_DEPTH>
+#ifndef CA_YS4_DEPTH
+#define CA_YS4_DEPTH 4   // pieces in flight per wave of the 4-bit image's own launch (2 KiB each)
+#endif
+// Y4: the loop image is the 4-bit one (k_pack_y4) and its escape list is added exactly -- row side into the cell's 64-bit sum before it
+// becomes a float, column side into the block's integer combine -- so YWpart / YTpart are the 1-byte image's to the last bit.
+template <int DEPTH = CA_YS_DEPTH, bool Y4 = false>
 __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restrict__ Ys, const ca_ys_io& io, int64_t N, int Gp,
                                                 int RS /* cells per strip, multiple of 64 */,
                                                 unsigned char* ca_ys_lds /* 16-byte aligned, CA_YS_LDS_BYTES: [4 waves][64][CA_YS_PITCH], reused for the combine */) {
@@ -399,10 +497,11 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   unsigned char* wr_dst = my + lrow * CA_YS_PITCH + 16 * lch;
   const unsigned char* rd_row = my + j * CA_YS_PITCH + 16 * q;
   const unsigned rd_tr = (unsigned)(size_t)my + (unsigned)((16 * q + (j >> 1)) * CA_YS_PITCH + 8 * (j & 1));
-  const uint8_t* src = Ys + ((c0 >> 6) * (int64_t)(Gp / 64) + (g0 >> 6)) * 4096;   // (scalar) piece (cell step, gene block), 1 KiB per load
+  constexpr int PB = Y4 ? 2048 : 4096, NL = PB / 1024;                              // bytes of a piece, 1-KiB loads per piece
+  const uint8_t* src = Ys + ((c0 >> 6) * (int64_t)(Gp / 64) + (g0 >> 6)) * PB;     // (scalar) piece (cell step, gene block), 1 KiB per load
   const uint4* wsrc = Wr + (int64_t)(g0 >> 6) * 64;                                 // (scalar)
   const unsigned voff = 16u * (unsigned)lane;                                       // the lane's 16 bytes of a 1-KiB load
-  uint4 R[DEPTH][4], W[DEPTH];
+  uint4 R[DEPTH][NL], W[DEPTH];
   // pieces of the strip: cell step st (64 cells), gene block a (0 .. NP-1); DEPTH pieces in flight
   const int nsteps = c0 < c1 ? (int)((c1 - c0 + 63) / 64) : 0;
   // Buffer loads: a scalar base (the strip's first piece; the segment's W image; psi's image) in a resource descriptor, the piece's byte offset in a
@@ -413,9 +512,9 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wsrc), 0, NP * 1024, 0x00020000);
   const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(Pr + (c0 >> 6) * 64), 0, 0x7FFFFFFF, 0x00020000);
   auto issue = [&](int slot, int st, int a) {
-    const int so = (st * (Gp / 64) + a) * 4096;   // (scalar)
+    const int so = (st * (Gp / 64) + a) * PB;   // (scalar)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < NL; ++i) {
       const ca_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(voff + 1024u * (unsigned)i), so, 2 /* nt: streamed once */);
       R[slot][i] = (uint4){v.x, v.y, v.z, v.w};
     }
@@ -438,7 +537,7 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   // bias of the row products: 128 x (digit sums of the segment's W image) per digit -- wave-uniform addresses, so the sums live
   // in scalar registers for the whole strip and cost the piece loop no vector register; a lane picks digit p = j & 3 at the flush
   int wtot[4] = {0, 0, 0, 0};
-  {
+  if (!Y4) {
     const int* ws = io.Wsum + (g0 >> 6) * 4;
 #pragma unroll
     for (int a = 0; a < NP; ++a)
@@ -446,6 +545,11 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
       for (int p_ = 0; p_ < 4; ++p_) wtot[p_] += ws[a * 4 + p_];
   }
   const int e_w = io.exps[0];
+  // Y4: the bucket of this wave (its strip of the block's segment) in the escape list, and 64 int64 slots of LDS past the four staging
+  // regions where a cell step's row-side escapes are summed (slot = cell in the step)
+  const int64_t kb = ((int64_t)blk * 4 + wv) * RS;
+  unsigned long long* rowesc = reinterpret_cast<unsigned long long*>(ca_ys_lds + 4 * 64 * CA_YS_PITCH) + wv * 64;
+  if (Y4) rowesc[lane] = 0ull;
   for (int st = 0; st < nsteps; ++st) {
     const int64_t cs = c0 + (int64_t)st * 64;
     const bool more = st + 1 < nsteps;   // (wave-uniform)
@@ -461,16 +565,32 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
       const int slot = a % DEPTH;
       __builtin_amdgcn_sched_barrier(0);   // (pieces one after the other: hoisting the next piece's LDS reads over this one's costs registers the sweep's budget has not)
       // the piece is in R[slot]: park it in LDS, start the loads of the piece DEPTH further on, then feed the matrix core
-#pragma unroll
-      for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(wr_dst + 16 * i * CA_YS_PITCH) = R[slot][i];
       const uint4 wr = W[slot];
-      if (a + DEPTH < NP) issue(slot, st, a + DEPTH);
-      else if (more) issue(slot, st + 1, a + DEPTH - NP);
-      // row products: the four cell tiles against this 64-gene block
+      if (Y4) {
+        // the four cell tiles' A operands are the nibbles of the two loads: row products from registers, the bytes parked in LDS (row
+        // 16 t + j, bytes 16 q ..) only for the transposed reads of the column products
+        // (one tile at a time: four registers of unpacked bytes live, not sixteen -- the riding form's budget is 128)
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const uint4 av = *reinterpret_cast<const uint4*>(rd_row + 16 * t * CA_YS_PITCH);
-        acc_yw[t] = ca_mfma_i8(av, wr, acc_yw[t]);
+        for (int t = 0; t < 4; ++t) {
+          const uint4 v = R[slot][t >> 1];
+          const int sh = 4 * (t & 1);
+          const uint4 av = ca_and4((uint4){v.x >> sh, v.y >> sh, v.z >> sh, v.w >> sh}, 0x0F0F0F0Fu);
+          *reinterpret_cast<uint4*>(const_cast<unsigned char*>(rd_row) + 16 * t * CA_YS_PITCH) = av;
+          acc_yw[t] = ca_mfma_i8(av, wr, acc_yw[t]);
+        }
+        if (a + DEPTH < NP) issue(slot, st, a + DEPTH);
+        else if (more) issue(slot, st + 1, a + DEPTH - NP);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(wr_dst + 16 * i * CA_YS_PITCH) = R[slot][i];
+        if (a + DEPTH < NP) issue(slot, st, a + DEPTH);
+        else if (more) issue(slot, st + 1, a + DEPTH - NP);
+        // row products: the four cell tiles against this 64-gene block
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const uint4 av = *reinterpret_cast<const uint4*>(rd_row + 16 * t * CA_YS_PITCH);
+          acc_yw[t] = ca_mfma_i8(av, wr, acc_yw[t]);
+        }
       }
       // column products: the four gene tiles of the block against the 64 cells, one accumulator (tile t -> rows 4t .. 4t+3)
 #pragma unroll
@@ -481,6 +601,18 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
         for (int t = 0; t < 2; ++t) acc_yt[a] = ca_mfma_i8(prm[2 * h2 + t], (uint4){lo[t].x, lo[t].y, hi[t].x, hi[t].y}, acc_yt[a]);
       }
     }
+    if (Y4) {   // the step's escapes, one per lane: excess x fix(W_g), the full fixed-point value reassembled from the digits the MFMAs took
+      const int64_t sc = (int64_t)st * 64;
+      const int e1 = io.esc_off[kb + ((sc + 64 < RS) ? sc + 64 : RS)];
+      const signed char* wd = reinterpret_cast<const signed char*>(Wr);
+      for (int e = io.esc_off[kb + sc] + lane; e < e1; e += 64) {
+        const unsigned en = io.esc[e];
+        const int g = g0 + (int)((en >> 9) & 511u);
+        const signed char* d = wd + ((int64_t)(g >> 6) * 64 + 16 * ((g >> 4) & 3)) * 16 + (g & 15);
+        const long long x = (long long)d[0] + (long long)d[16] * 256ll + (long long)d[32] * 65536ll + (long long)d[48] * 16777216ll;
+        atomicAdd(rowesc + ((en & 511u) & 63u), (unsigned long long)((long long)(en >> 18) * x));
+      }
+    }
     {   // the cell step is complete: lane (column 4t + p, q) holds cells 16 t + 4 q + r, digit p
       const int t = j >> 2, p = j & 3;
 #pragma unroll
@@ -489,10 +621,12 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
         const int wb = p == 0 ? wtot[0] : p == 1 ? wtot[1] : p == 2 ? wtot[2] : wtot[3];
         const int ar = t == 0 ? acc_yw[0][r] : t == 1 ? acc_yw[1][r] : t == 2 ? acc_yw[2][r] : acc_yw[3][r];
         long long v = ((long long)ar + 128ll * (long long)wb) << (8 * p);   // digit p of the quad's four (lanes j & 3): exact in 64 bits
+        if (Y4 && p == 0) v += (long long)rowesc[16 * t + 4 * q + r];
         v += __shfl_xor(v, 1, 64);
         v += __shfl_xor(v, 2, 64);
         if (p == 0 && n < N) io.YWpart[(int64_t)seg * N + n] = (float)ldexp((double)v, -e_w);
       }
+      if (Y4) rowesc[lane] = 0ull;   // (after every lane's reads: a wave's LDS operations complete in order)
     }
   }
   // column products of the strip: lane (gene n = j, q), accumulator a: gene tile 4 a + q, digits r = 0..3; combine the four
@@ -504,9 +638,22 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
 #pragma unroll
     for (int r = 0; r < 4; ++r) comb[((wv * NP + a) * 64 + lane) * 4 + r] = acc_yt[a][r];
   __syncthreads();
+  if (Y4) {   // the strip's escapes, four lanes per entry (lane & 3 = digit r of fix(psi_n)): excess x digit into the combine
+    const signed char* pd = reinterpret_cast<const signed char*>(Pr);
+    const int r = lane & 3;
+    const int e1 = io.esc_off[kb + RS];
+    for (int e = io.esc_off[kb] + (lane >> 2); e < e1; e += 16) {
+      const unsigned en = io.esc[e];
+      const int64_t n = c0 + (int64_t)(en & 511u);
+      const int gi = (int)((en >> 9) & 511u);
+      const int d = pd[((n >> 6) * 64 + 16 * ((n >> 4) & 3) + r) * 16 + (n & 15)];
+      atomicAdd(comb + ((wv * NP + (gi >> 6)) * 64 + (gi & 63)) * 4 + r, (int)(en >> 18) * d);
+    }
+    __syncthreads();
+  }
   // bias of the column products: 128 x (digit sums of psi's image over the block's cell steps); scale 2^-e_psi
   long long pb[4] = {0, 0, 0, 0};
-  {
+  if (!Y4) {
     const int64_t s0_ = ((int64_t)rg * 4 * RS) >> 6;
     const int64_t s1_ = (((int64_t)rg * 4 + 4) * RS < ((N + 63) / 64) * 64 ? ((int64_t)rg * 4 + 4) * RS : ((N + 63) / 64) * 64) >> 6;
     for (int64_t st = s0_; st < s1_; ++st) {
@@ -528,11 +675,15 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
     io.YTpart[(int64_t)rg * Gp + gene] = (float)(v * inv_p);
   }
 }
+template <bool Y4>
 __global__ void __launch_bounds__(CA_YM_TB, CA_YS_WAVES) k_ys_mfma(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];
-  ca_ys_mfma_body<CA_YS_DEPTH>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
-constexpr int CA_YS_LDS_BYTES = 4 * (CA_YS_GW / 64) * 64 * 4 * 4;   // the combine buffer (32 KB) >= 4 x 64 x CA_YS_PITCH
+// (the riding forms -- k_fwd_cell_mix_ys, k_fwd_bal_ys -- are instantiated per format: the 1-byte ones are round 6's code; the 4-bit ones exist
+//  only for the series form's rank-one shapes (D = 1, no c16 / s2), whose sweeps run only in the passes the series form hands over)
+constexpr int CA_YS_LDS_BYTES = 4 * (CA_YS_GW / 64) * 64 * 4 * 4;   // the combine buffer (32 KB) >= 4 x 64 x CA_YS_PITCH (+ 4 x 64 x 8 B of the 4-bit image's row escapes)
+static_assert(4 * 64 * CA_YS_PITCH + 4 * 64 * 8 <= CA_YS_LDS_BYTES, "staging + row escapes fit the combine buffer");
 
 // per-step digit sums of a replicated image (for the bias): sums[step][p] = sum over the step's 64 entries of digit p
 __global__ void __launch_bounds__(CA_YM_TB) k_ym_digit_sums(const uint4* __restrict__ img, int64_t steps, int* __restrict__ sums) {

@@ -120,6 +120,9 @@ enum ca_variant {
   CA_VAR_YFIN_RIDE = 1 << 15, /* the riding int8 stream's finishing sums (Y^T psi column sums, YW and the psi.(YW) partials) as extra blocks of the
                                  backward sweep's launch; the pending monitor pass's ELBO is then assembled one kernel later (per-gene kernel).
                                  Off: a finisher launch (k_yfinish) between the two sweeps */
+  CA_VAR_Y4 = 1 << 22,        /* the one-copy stream's loop image at 4 bits per count (min(y, 15) in a nibble, the counts from 15 up as their exact excess in
+                                 an escape list bucketed by the stream's own units): half the bytes per pass, the same integer sums; picked where the escapes
+                                 are at most 1 in 64 counts (CA_VARX_Y4 forces it).  Off: the 1-byte loop image */
   CA_VAR_RIDE_SEQ = 1 << 13   /* off: the riding stream as blocks of its own interleaved in the sweep's grid (k_fwd_cell_mix_y), never fused in
                                  sequence into the sweep's blocks (k_fwd_cell_seq_y; see CA_VARX_RIDE_SEQ) */
 };
@@ -148,6 +151,7 @@ enum ca_variant_on {
                                  clones: Z_nc = sum_g M_gc exp(x_n v_g) is one function of x per clone; genes binned by v, a 20-term expansion per bin (argument <= 2,
                                  float64): moments over genes, evaluation over cells, the same form on the way back.  No cells x genes sweep: O(N nb R C + G R C)
                                  instead of O(N G C) per pass; the cell epilogue is the sweep's.  Other shapes keep the matrix-core sweeps */
+  CA_VARX_Y4 = 1 << 9,        /* the 4-bit loop image (CA_VAR_Y4) at any escape fraction */
   CA_VARX_ASYNC_SMALL = 1 << 1 /* side stream also below 4e7 counts (small shards run the Y stream in line: the two cross-stream
                                  events cost more than the overlap returns there) */
 };
@@ -211,7 +215,7 @@ typedef struct ca_info {
   int32_t update_merge;      /* 1: the loop's update half is one launch (CA_VAR_UPDATE_MERGE) */
   int32_t fwd_balanced;      /* > 0: the fused forward sweep is the balanced small-problem form (CA_VAR_FWD_BAL), that many tiles per block */
   int32_t fwd_series;        /* ABI 6: 1: the loop's contraction takes its series form (CA_VAR_SERIES / CA_VARX_SERIES, ca_poly.hip) wherever the exponent range allows */
-  int32_t reserved_;
+  int32_t y_stream_bits;     /* bits per count of the one-copy stream's loop image: 8, or 4 (CA_VAR_Y4); 0 where there is no loop image */
   int64_t series_passes;     /* fused passes of this engine that ran in the series form ... */
   int64_t series_fallbacks;  /* ... and those the look ahead at the exponent range (max|psi| (max W - min W), plus what the Adam steps since can add) gave to the sweeps */
 } ca_info;
