@@ -212,12 +212,12 @@ int ycache_ys(ca_engine* h) {
   if (h->n_ovf > 0) {
     const ca_ovf_args ovf = ys_ovf(h);
     const dim3 grid(nb_main + ovf.nb_rows + ovf.nb_chunks);
-    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf<true>, grid, dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
+    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf<true>, grid, dim3(CA_YM_TB), CA_YS4_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
                                                               h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D));
     else LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf<false>, grid, dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
                                                        h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D));
   } else {
-    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma<true>, dim3(nb_main), dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h),
+    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma<true>, dim3(nb_main), dim3(CA_YM_TB), CA_YS4_LDS_BYTES, h->stream, h->Ys, ys_io(h),
                                                               h->N, h->Gp, h->ys_RS));
     else LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma<false>, dim3(nb_main), dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h),
                                                        h->N, h->Gp, h->ys_RS));

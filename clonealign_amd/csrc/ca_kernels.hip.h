@@ -857,7 +857,7 @@ __global__ void __launch_bounds__(CA_TB) k_p2p_allreduce(double* __restrict__ bu
 
 // the one-copy stream with the overflow list's per-entry work (cell side, then gene side) as extra blocks, like k_ypass
 template <bool Y4>
-__global__ void __launch_bounds__(CA_YM_TB, CA_YS_WAVES) k_ys_mfma_ovf(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS,
+__global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_ovf(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS,
                                                                        int nb_main, ca_ovf_args ovf, const float* __restrict__ F,
                                                                        const float* __restrict__ V, int Dstride) {
   if ((int)blockIdx.x >= nb_main) {
@@ -866,8 +866,8 @@ __global__ void __launch_bounds__(CA_YM_TB, CA_YS_WAVES) k_ys_mfma_ovf(const uin
     else ca_ovf_chunks_body(b - ovf.nb_rows, ovf.chunk_start, ovf.row2, ovf.val2, F, Dstride, ovf.csum, ovf.nchunk, 1, 0);
     return;
   }
-  extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];
-  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
+  extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];   // Y4: CA_YS4_LDS_BYTES, else CA_YS_LDS_BYTES
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 
 // The one-copy int8 matrix-core stream RIDING on the forward sweep's launch (round 3).  The vector stream of k_fwd_cell_mix_y

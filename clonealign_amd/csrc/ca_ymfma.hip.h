@@ -462,14 +462,33 @@ struct ca_ys_io {
 #ifndef CA_YS4_DEPTH
 #define CA_YS4_DEPTH 4   // pieces in flight per wave of the 4-bit image's own launch (2 KiB each)
 #endif
+#ifndef CA_YS4_WAVES
+#define CA_YS4_WAVES 4   // waves per SIMD of the 4-bit image's own launch: 128 VGPRs, four blocks per CU -- the whole grid of cfg-3 in one round
+#endif
+// LDS of the 4-bit image's own launch (OWN): the staging regions, then the segment's W image (read by the row products and the escapes
+// instead of a buffer load per piece), the row-escape sums, each wave's copy of psi's digits for the step, and -- past the 32-KB combine
+// buffer, since it is read in the combine -- the block's column-escape sums [512 genes] int64.  36 KB: four blocks per CU (160 KB).
+constexpr int CA_YS4_OFF_W = 4 * 64 * CA_YS_PITCH;
+constexpr int CA_YS4_OFF_ROW = CA_YS4_OFF_W + (CA_YS_GW / 64) * 1024;
+constexpr int CA_YS4_OFF_PSI = CA_YS4_OFF_ROW + 4 * 64 * 8;
+constexpr int CA_YS4_OFF_COL = 4 * (CA_YS_GW / 64) * 64 * 4 * 4;
+constexpr int CA_YS4_LDS_BYTES = CA_YS4_OFF_COL + CA_YS_GW * 8;
+static_assert(CA_YS4_OFF_PSI + 4 * 256 <= CA_YS4_OFF_COL, "the 4-bit launch's tables fit below its column-escape sums");
+static_assert(4 * CA_YS4_LDS_BYTES <= 160 * 1024, "four blocks of the 4-bit launch per CU");
 // Y4: the loop image is the 4-bit one (k_pack_y4) and its escape list is added exactly -- row side into the cell's 64-bit sum before it
 // becomes a float, column side into the block's integer combine -- so YWpart / YTpart are the 1-byte image's to the last bit.
-template <int DEPTH = CA_YS_DEPTH, bool Y4 = false>
+// OWN (with Y4: the series form's own launch, k_ys_mfma / k_ys_mfma_ovf; CA_YS4_LDS_BYTES of LDS): the escapes come off the critical
+// path -- the strip's step offsets are read once, a step's first 128 entries are loaded when the step starts (their wait is a piece's),
+// both sides of an entry are LDS operations (fix(W_g) from the block's W image, fix(psi_n) from the step's digits, row and column sums
+// in LDS int64) -- and the register budget is the one of four waves per SIMD: W from LDS, psi masked per MFMA.  The riding forms keep OWN
+// = false: the same sums, the layout of CA_YS_LDS_BYTES.
+template <int DEPTH = CA_YS_DEPTH, bool Y4 = false, bool OWN = false>
 __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restrict__ Ys, const ca_ys_io& io, int64_t N, int Gp,
                                                 int RS /* cells per strip, multiple of 64 */,
                                                 unsigned char* ca_ys_lds /* 16-byte aligned, CA_YS_LDS_BYTES: [4 waves][64][CA_YS_PITCH], reused for the combine */) {
   const uint4* __restrict__ Wr = io.Wr;
   const uint4* __restrict__ Pr = io.Pr;
+  constexpr bool Y4L = Y4 && OWN;
   constexpr int NP = CA_YS_GW / 64;
   static_assert(NP % DEPTH == 0, "pieces per cell step must be a multiple of the pipeline depth");
   const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
@@ -518,12 +537,33 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
       const ca_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(voff + 1024u * (unsigned)i), so, 2 /* nt: streamed once */);
       R[slot][i] = (uint4){v.x, v.y, v.z, v.w};
     }
-    const ca_v4u w = __builtin_amdgcn_raw_buffer_load_b128(rw, (int)voff, a * 1024, 0);
-    W[slot] = (uint4){w.x, w.y, w.z, w.w};
+    if (!Y4L) {
+      const ca_v4u w = __builtin_amdgcn_raw_buffer_load_b128(rw, (int)voff, a * 1024, 0);
+      W[slot] = (uint4){w.x, w.y, w.z, w.w};
+    }
   };
+  // Y4L: the block's tables (the segment's W image, loaded before the first pieces so that its wait is not theirs; the column-escape
+  // sums zeroed), and the strip's escape offsets at its cell steps, lane st = the first entry of step st (lane nsteps: the end)
+  uint4* wl = reinterpret_cast<uint4*>(ca_ys_lds + CA_YS4_OFF_W);
+  unsigned long long* colesc = reinterpret_cast<unsigned long long*>(ca_ys_lds + CA_YS4_OFF_COL);
+  uint4 wimg[2];
+  int eoff = 0;
+  if (Y4L) {
+    wimg[0] = wsrc[threadIdx.x];
+    wimg[1] = wsrc[threadIdx.x + CA_YM_TB];
+    if (lane <= nsteps) eoff = io.esc_off[((int64_t)blk * 4 + wv) * RS + (64 * lane < RS ? 64 * lane : RS)];
+  }
   if (nsteps > 0) {
 #pragma unroll
     for (int d_ = 0; d_ < DEPTH; ++d_) issue(d_, 0, d_);
+  }
+  if (Y4L) {
+    static_assert(2 * CA_YM_TB == CA_YS_GW, "the block's threads hold the segment's W image and column sums in two halves");
+    wl[threadIdx.x] = wimg[0];
+    wl[threadIdx.x + CA_YM_TB] = wimg[1];
+    colesc[threadIdx.x] = 0ull;
+    colesc[threadIdx.x + CA_YM_TB] = 0ull;
+    __syncthreads();
   }
   // Round 5: the gene blocks of a cell step are UNROLLED, so that every accumulator is a fixed register (the loop over pieces with a switch on the
   // block index moved the 32 accumulator registers through chains of copies: ~40 v_mov per piece), the column products chain straight onto their
@@ -548,24 +588,38 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   // Y4: the bucket of this wave (its strip of the block's segment) in the escape list, and 64 int64 slots of LDS past the four staging
   // regions where a cell step's row-side escapes are summed (slot = cell in the step)
   const int64_t kb = ((int64_t)blk * 4 + wv) * RS;
-  unsigned long long* rowesc = reinterpret_cast<unsigned long long*>(ca_ys_lds + 4 * 64 * CA_YS_PITCH) + wv * 64;
+  unsigned long long* rowesc = reinterpret_cast<unsigned long long*>(ca_ys_lds + (Y4L ? CA_YS4_OFF_ROW : 4 * 64 * CA_YS_PITCH)) + wv * 64;
+  unsigned char* psl = ca_ys_lds + CA_YS4_OFF_PSI + wv * 256;   // (Y4L) psi's digits of the step: [cell quarter][digit][16 cells]
   if (Y4) rowesc[lane] = 0ull;
   for (int st = 0; st < nsteps; ++st) {
     const int64_t cs = c0 + (int64_t)st * 64;
     const bool more = st + 1 < nsteps;   // (wave-uniform)
+    uint4 pr;
     {
       // (the wait for this load is also the wait for the step's first piece, which is needed next anyway; a stream wave has ~2000 cycles per piece)
       const ca_v4u pv = __builtin_amdgcn_raw_buffer_load_b128(rp, (int)voff, st * 1024, 0);
-      const uint4 pr = {pv.x, pv.y, pv.z, pv.w};
+      pr = (uint4){pv.x, pv.y, pv.z, pv.w};
 #pragma unroll
-      for (int t = 0; t < 4; ++t) { acc_yw[t] = (ca_i32x4){0, 0, 0, 0}; prm[t] = ca_and4(pr, msk[t]); }
+      for (int t = 0; t < 4; ++t) { acc_yw[t] = (ca_i32x4){0, 0, 0, 0}; if (!Y4L) prm[t] = ca_and4(pr, msk[t]); }
+    }
+    // Y4L: the step's first 128 escape entries (two per lane), issued after the step's own pieces and before the next step's: waited for
+    // at the end of the step, when only the younger pieces are still in flight
+    int e_lo = 0, e_hi = 0;
+    unsigned en0 = 0u, en1 = 0u;
+    if (Y4L) {
+      e_lo = __builtin_amdgcn_readlane(eoff, st);
+      e_hi = __builtin_amdgcn_readlane(eoff, st + 1);
+      if (e_hi > e_lo) {   // (uniform; past the last entry: the last one again, never used)
+        en0 = io.esc[e_lo + lane < e_hi ? e_lo + lane : e_hi - 1];
+        en1 = io.esc[e_lo + 64 + lane < e_hi ? e_lo + 64 + lane : e_hi - 1];
+      }
     }
 #pragma unroll
     for (int a = 0; a < NP; ++a) {
       const int slot = a % DEPTH;
       __builtin_amdgcn_sched_barrier(0);   // (pieces one after the other: hoisting the next piece's LDS reads over this one's costs registers the sweep's budget has not)
       // the piece is in R[slot]: park it in LDS, start the loads of the piece DEPTH further on, then feed the matrix core
-      const uint4 wr = W[slot];
+      const uint4 wr = Y4L ? wl[a * 64 + lane] : W[slot];
       if (Y4) {
         // the four cell tiles' A operands are the nibbles of the two loads: row products from registers, the bytes parked in LDS (row
         // 16 t + j, bytes 16 q ..) only for the transposed reads of the column products
@@ -598,10 +652,42 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
         uint2 lo[2], hi[2];
         ca_ds_read_tr_b8_x4(rd_tr + 32u * (unsigned)h2, lo, hi);
 #pragma unroll
-        for (int t = 0; t < 2; ++t) acc_yt[a] = ca_mfma_i8(prm[2 * h2 + t], (uint4){lo[t].x, lo[t].y, hi[t].x, hi[t].y}, acc_yt[a]);
+        for (int t = 0; t < 2; ++t) {
+          uint4 pa;
+          if (Y4L) {   // psi masked to row group 2 h2 + t here, not held four times over the step (the opaque copy keeps it from being shared)
+            unsigned g_ = grp;
+            asm volatile("" : "+v"(g_));
+            pa = ca_and4(pr, g_ == (unsigned)(2 * h2 + t) ? 0xFFFFFFFFu : 0u);
+          } else {
+            pa = prm[2 * h2 + t];
+          }
+          acc_yt[a] = ca_mfma_i8(pa, (uint4){lo[t].x, lo[t].y, hi[t].x, hi[t].y}, acc_yt[a]);
+        }
       }
     }
-    if (Y4) {   // the step's escapes, one per lane: excess x fix(W_g), the full fixed-point value reassembled from the digits the MFMAs took
+    if (Y4L) {   // the step's escapes, one per lane, both sides from LDS: excess x fix(W_g) into the cell's row sum, excess x fix(psi_n) into the gene's
+      if (j < 4) *reinterpret_cast<uint4*>(psl + (4 * q + j) * 16) = pr;   // lane (q, digit j) of column group 0: cells 16 q + b
+      const unsigned char* wlb = reinterpret_cast<const unsigned char*>(wl);
+      auto esc1 = [&](unsigned en) {
+        const int c = (int)(en & 63u), gi = (int)((en >> 9) & 511u);
+        const unsigned char* dw = wlb + ((gi >> 6) * 64 + 16 * ((gi >> 4) & 3)) * 16 + (gi & 15);
+        const unsigned char* dp = psl + 64 * (c >> 4) + (c & 15);
+        // x = sum_p d_p 256^p modulo 2^32 (|x| < 2^31: exact)
+        unsigned fw = 0u, fp = 0u;
+#pragma unroll
+        for (int p_ = 0; p_ < 4; ++p_) {
+          fw += (unsigned)(int)(signed char)dw[16 * p_] << (8 * p_);
+          fp += (unsigned)(int)(signed char)dp[16 * p_] << (8 * p_);
+        }
+        const long long x = (long long)(en >> 18);
+        atomicAdd(rowesc + c, (unsigned long long)(x * (long long)(int)fw));
+        atomicAdd(colesc + gi, (unsigned long long)(x * (long long)(int)fp));
+      };
+      const int ne = e_hi - e_lo;
+      if (lane < ne) esc1(en0);
+      if (64 + lane < ne) esc1(en1);
+      for (int e = e_lo + 128 + lane; e < e_hi; e += 64) esc1(io.esc[e]);
+    } else if (Y4) {   // the step's escapes, one per lane: excess x fix(W_g), the full fixed-point value reassembled from the digits the MFMAs took
       const int64_t sc = (int64_t)st * 64;
       const int e1 = io.esc_off[kb + ((sc + 64 < RS) ? sc + 64 : RS)];
       const signed char* wd = reinterpret_cast<const signed char*>(Wr);
@@ -638,7 +724,7 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
 #pragma unroll
     for (int r = 0; r < 4; ++r) comb[((wv * NP + a) * 64 + lane) * 4 + r] = acc_yt[a][r];
   __syncthreads();
-  if (Y4) {   // the strip's escapes, four lanes per entry (lane & 3 = digit r of fix(psi_n)): excess x digit into the combine
+  if (Y4 && !OWN) {   // the strip's escapes, four lanes per entry (lane & 3 = digit r of fix(psi_n)): excess x digit into the combine
     const signed char* pd = reinterpret_cast<const signed char*>(Pr);
     const int r = lane & 3;
     const int e1 = io.esc_off[kb + RS];
@@ -671,14 +757,15 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
       const int sr = (comb[o] + comb[o + NP * 256]) + (comb[o + 2 * NP * 256] + comb[o + 3 * NP * 256]);
       v = v * 256.0 + (double)((long long)sr + 128 * pb[r]);
     }
-    const int gene = g0 + 16 * (4 * a + (l >> 4)) + (l & 15);
+    const int gl = 16 * (4 * a + (l >> 4)) + (l & 15), gene = g0 + gl;
+    if (Y4L) v += (double)(long long)colesc[gl];   // (integers below 2^53 throughout: the same total as the escapes added digit by digit)
     io.YTpart[(int64_t)rg * Gp + gene] = (float)(v * inv_p);
   }
 }
 template <bool Y4>
-__global__ void __launch_bounds__(CA_YM_TB, CA_YS_WAVES) k_ys_mfma(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];
-  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
+__global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];   // Y4: CA_YS4_LDS_BYTES, else CA_YS_LDS_BYTES
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 // (the riding forms -- k_fwd_cell_mix_ys, k_fwd_bal_ys -- are instantiated per format: the 1-byte ones are round 6's code; the 4-bit ones exist
 //  only for the series form's rank-one shapes (D = 1, no c16 / s2), whose sweeps run only in the passes the series form hands over)
