@@ -259,7 +259,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
       // fewer 32-cell blocks than CUs: 16-cell blocks, where the int8 stream rides (round 3, with this round's kernels: 6250 cells
       // 17.2k -> 18.8k it/s; at 12.5k cells and at 10k x 2k they still lose, 13.7k vs 14.2k and 21.7k vs 22.1k)
       if (h->fwd_cell && h->fc_tl == 2 && cdiv(Nn, 32) < h->n_cu && h->ystore == CA_YSTORE_U8 && K == 1 && D <= 2 && !h->c16 && h->fused_ok &&
-          variant_on(h, CA_VAR_Y_MFMA1, "CA_Y_MFMA1") && variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE") && !lab_variantx_on(h, CA_VARX_Y_MFMA2, "CA_Y_MFMA2"))
+          variant_on(h, CA_VAR_Y_MFMA1, "CA_Y_MFMA1") && variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE"))
         h->fc_tl = 1;   // (only where the int8 stream will ride: the other streams' merged kernels exist for 32- and 96-cell blocks)
       if (const int t = tune_val(h, CA_TUNE_FC_TL, "CA_FC_TL")) { if (t == 1 || t == 2 || t == 4 || t == 5 || t == 6 || t == 8) h->fc_tl = t; }
       if ((h->c16 || h->s2 || D >= 3) && h->fc_tl != 2) h->fc_tl = 6;   // (the two-operand-set kernels -- sixteen clones, four draws of mc_samples = 2 -- exist for the two default block shapes)
@@ -322,7 +322,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   CACK(dalloc(h, &h->Zpart, (int64_t)S * h->gsplit * h->nchunk * Nn * CA_CW));
   CACK(dalloc(h, &h->coef, (int64_t)S * h->nchunk * Nn * CA_CW));
   CACK(dalloc(h, &h->scratch, Nn * C));
-  const int64_t n_cpart = std::max(std::max(h->ncblk, h->ncblk_f), 2 * h->n_cu);   // (balanced sweep: n_cu blocks + up to n_cu - 1 left-over tiles' blocks)
+  const int64_t n_cpart = std::max(std::max(h->ncblk, h->ncblk_f), h->n_cu);   // (balanced sweep: one block per CU)
   CACK(dalloc(h, &h->cell_part, n_cpart * (3 + C)));
   // The series form of the contraction (ca_poly.hip) where it is measured faster than the sweeps: the count-matrix stream then runs as a launch of its own
   // (in line) and the rest is O(N + G) work in five small launches.  What the sweeps cost grows with N G, the series form with N and with a fixed chain of
@@ -368,41 +368,9 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   h->n_yw = cdiv(Nn, CA_TB);
   CACK(dalloc(h, &h->yw_part, h->n_yw));
   CACK(dalloc(h, &h->ytpsi, (int64_t)h->Gp * std::max(K, 1)));
-  // ---- count-matrix products on the int8 matrix cores: two tiled copies of the 1-byte matrix (cell-tiled for Y.W,
-  //      gene-tiled for Y^T.psi), each in the operand layout of v_mfma_i32_16x16x64_i8 (ca_ymfma.hip.h)
-#ifdef CA_LAB
-  if (h->ystore == CA_YSTORE_U8 && K >= 1 && K <= 4 && variantx_on(h, CA_VARX_Y_MFMA2, "CA_Y_MFMA2")) {
-    h->ym_NT = cdiv(Nn, 16); h->ym_NS = cdiv(Nn, 64); h->ym_GS = cdiv(G, 64); h->ym_GT = cdiv(G, 16);
-    uint8_t *yf = nullptr, *yb = nullptr;
-    CACK(dalloc(h, &yf, h->ym_NT * h->ym_GS * 1024));
-    CACK(dalloc(h, &yb, (int64_t)h->ym_GT * h->ym_NS * 1024));
-    h->Yf = (uint4*)yf; h->Yb = (uint4*)yb;
-    uint8_t *wq = nullptr, *pq = nullptr;
-    CACK(dalloc(h, &wq, (int64_t)h->ym_GS * 1024));
-    CACK(dalloc(h, &pq, h->ym_NS * 1024));
-    h->Wq = (uint4*)wq; h->Pq = (uint4*)pq;
-    CACK(dalloc(h, &h->ym_amax, 2));
-    // waves: rows 64 TL cells per block, at least ~4 waves per CU; columns 8 gene tiles per block x cell slices
-    h->ym_tl = (h->ym_NT / 4 >= 4 * h->n_cu) ? 4 : (h->ym_NT / 2 >= 4 * h->n_cu) ? 2 : 1;
-    h->n_yw = cdiv(h->ym_NT, 4 * h->ym_tl);   // blocks of k_yw_mfma = partials of sum_n psi_n.(YW)_n
-    CACK(dalloc(h, &h->yw_part, h->n_yw));
-    const int gblocks = cdiv(h->ym_GT, 8);
-    h->ym_csplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(16, cdiv(8 * (int64_t)h->n_cu, 4 * gblocks)), h->ym_NS / 4));
-    h->ym_schunk = cdiv(h->ym_NS, h->ym_csplit);
-    h->ym_csplit = cdiv(h->ym_NS, h->ym_schunk);
-    CACK(dalloc(h, &h->ym_out, (int64_t)h->ym_csplit * h->ym_GT * 256));
-    hipLaunchKernelGGL(k_tile_yf, dim3(cdiv(h->ym_NT * h->ym_GS * 64, CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, h->Yf, Nn, h->Gp,
-                       h->ym_NT, h->ym_GS);
-    hipLaunchKernelGGL(k_tile_yb, dim3((unsigned)h->ym_NS, cdiv(h->ym_GT, 4)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, h->Yb, Nn, h->Gp,
-                       h->ym_GT, h->ym_NS);
-    HIPCK(h, hipGetLastError());
-    h->y_mfma = true;
-    h->y_dev_bytes += (h->ym_NT * h->ym_GS + (int64_t)h->ym_GT * h->ym_NS) * 1024;
-  }
-#endif   // CA_LAB
-  // ---- both products from ONE tiled copy (k_ys_mfma): K = 1, 1-byte storage
+  // ---- count-matrix products on the int8 matrix cores, both from ONE tiled copy (k_ys_mfma, ca_ymfma.hip.h): K = 1, 1-byte storage
   // (the stream's buffer loads carry 32-bit byte offsets inside a strip: RS <= 512 cells x Gp bytes, and 16 N bytes of psi's image -- far inside 2^31 below these bounds)
-  if (h->ystore == CA_YSTORE_U8 && K == 1 && !h->y_mfma && h->Gp < (1 << 21) && Nn < ((int64_t)1 << 26) && variant_on(h, CA_VAR_Y_MFMA1, "CA_Y_MFMA1")) {
+  if (h->ystore == CA_YSTORE_U8 && K == 1 && h->Gp < (1 << 21) && Nn < ((int64_t)1 << 26) && variant_on(h, CA_VAR_Y_MFMA1, "CA_Y_MFMA1")) {
     h->ys_N64 = (Nn + 63) / 64 * 64;
     h->ys_nseg = h->Gp / CA_YS_GW;                  // Gp is a multiple of 1024
     // strips of RS cells per wave: about one resident round of blocks (3 per CU), at least 64 cells
@@ -475,9 +443,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   }
   // the Y stream rides on the forward sweep's launch: 1-byte storage, K = 1, the fused sweep with its default block shapes
   h->ride_ok = h->ystore == CA_YSTORE_U8 && K == 1 && D <= 2 && h->fused_ok && !h->c16 && h->fwd_cell && (h->fc_tl == 6 || h->fc_tl == 8 || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
-               !h->y_mfma && !h->y_ys && variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE");
-  constexpr bool kRideSeqDefault = false;
-  h->ride_seq = h->ride_ok && variant_on(h, CA_VAR_RIDE_SEQ, "CA_RIDE_SEQ") && (kRideSeqDefault || lab_variantx_on(h, CA_VARX_RIDE_SEQ, "CA_RIDE_SEQ_ON"));
+               !h->y_ys && variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE");
   const bool tl1_ok = h->fc_tl == 1 && h->fc_nbig == 0 && !h->c16;
   h->ride_ys = h->y_ys && (!h->ys4 || (h->poly && D == 1 && !h->c16 && !h->s2)) && D <= 2 && h->fused_ok && h->fwd_cell && (h->fc_tl == 6 || tl1_ok || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
                variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE");
@@ -492,12 +458,10 @@ int create_impl(ca_engine* h, const ca_problem* p) {
     // pipeline fills of a block that also sweeps a chunk cost more than the balance returns (10k x 2k x 4: 42.7 against 39.3 us per iteration)
     h->fwd_bal = h->ride_ys && !h->c16 && !h->s2 && D == 1 && C <= 8 && qb >= 1 && qb <= 6 && h->nk32 >= 96 && h->host_dev && variant_on(h, CA_VAR_FWD_BAL, "CA_FWD_BAL");
     if (h->fwd_bal) {
-      // left-over tiles: gene chunks swept by the sweep blocks beside their own tiles (the default), or -- opt-in CA_VARX_BAL_TILES, bal_nchunk = 0 -- single-tile
-      // blocks of their own with no exchange (measured, us per iteration at 12 500 / 25 000 / 10 240 / 14 336 cells, i.e. 14 / 27 / 128 / 128 left-over tiles:
-      // chunks 63.6 / 95.1 / 57.3 / 68.0, tile blocks 63.2 / 96.7 / 60.6 / 72.0, four-wave sweep 65.0 / 98.7 / 58.5 / 69.3: level at few left-over tiles --
-      // the stream's blocks go to the CUs without a tile block -- and slower at many; profiles/r05_small_shapes.txt)
+      // left-over tiles: gene chunks swept by the sweep blocks beside their own tiles (us per iteration at 12 500 / 25 000 / 10 240 / 14 336 cells, i.e. 14 / 27 /
+      // 128 / 128 left-over tiles: chunks 63.6 / 95.1 / 57.3 / 68.0, four-wave sweep 65.0 / 98.7 / 58.5 / 69.3; profiles/r05_small_shapes.txt)
       h->bal_q = qb; h->bal_r = rb;
-      h->bal_nchunk = (rb > 0 && !lab_variantx_on(h, CA_VARX_BAL_TILES, "CA_BAL_TILES")) ? std::min(CA_BAL_MAXCHUNK, h->n_cu / rb) : 0;
+      h->bal_nchunk = rb > 0 ? std::min(CA_BAL_MAXCHUNK, h->n_cu / rb) : 0;
       CACK(dalloc(h, &h->bal_xw, std::max<int64_t>(1, (int64_t)rb * h->bal_nchunk * 512)));
     }
   }

@@ -74,51 +74,39 @@ int refresh_derived(ca_engine* h) {
   return CA_OK;
 }
 
-// The same two products on the int8 matrix cores (ca_ymfma.hip.h): fixed-point images of W and psi, then one stream
-// over each tiled copy of the count matrix.  Runs on h->stream (the side stream when deferred).
-#ifdef CA_LAB   // (the two-copy form, CA_VARX_Y_MFMA2: lab library only)
-template <int TL, int DEPTH>
-void launch_yw(ca_engine* h) {
-  hipLaunchKernelGGL((k_yw_mfma<TL, DEPTH>), dim3(cdiv(h->ym_NT, 4 * TL)), dim3(CA_YM_TB), 0, h->stream, h->Yf, h->Wq, h->ym_NT, h->ym_GS, h->N,
-                     h->K, h->F, h->D, h->V, h->D, h->ym_amax, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, h->ovf_col, h->ovf_val, h->YW, h->yw_part);
-}
-int ycache_mfma(ca_engine* h) {
-  HIPCK(h, hipMemsetAsync(h->ym_amax, 0, 2 * sizeof(unsigned), h->stream));
-  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_ym_absmax, dim3(cdiv(std::max<int64_t>(h->N, h->G), CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream,
-                                                h->V, h->D, (int64_t)h->G, h->F, h->D, h->N, h->K, h->ym_amax));
-  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_ym_quant, dim3(cdiv((h->ym_GS + h->ym_NS) * 64, CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream,
-                                                h->V, h->D, (int64_t)h->G, h->ym_GS, h->F, h->D, h->N, h->ym_NS, h->K, h->ym_amax, h->Wq, h->Pq));
-  // row products: YW and the psi.(YW) partials, one block per 64 * TL cells (n_yw blocks when TL = 4)
-  CACK(prof_begin(h, CA_KERNEL_YPASS));
-  if (h->ym_tl == 4) launch_yw<4, 2>(h);
-  else if (h->ym_tl == 2) launch_yw<2, 4>(h);
-  else launch_yw<1, 8>(h);
-  HIPCK(h, hipGetLastError());
-  CACK(prof_end(h));
-  if (h->on_side) { HIPCK(h, hipEventRecord(h->ev_ywdone, h->stream)); h->yw_pending = true; }
-  // column products: digit sums per cell slice, then Y^T psi into red_y
+// The overflow list's share of a stream launch (counts above 255): its per-entry work rides as extra blocks -- the cell side into one extra strip of YWpart
+// (YWextra, behind the stream's own strips), the gene side into the chunk sums the finisher adds per gene.  All zero without a list.
+ca_ovf_args ovf_args(ca_engine* h, float* YWextra) {
   ca_ovf_args ovf;
   memset(&ovf, 0, sizeof(ovf));
-  int nb_ovf = 0;
   if (h->n_ovf > 0) {
-    nb_ovf = cdiv(h->n_ovf_chunk, CA_TB / 64);
+    ovf.nb_rows = cdiv(h->N, CA_TB); ovf.nb_chunks = cdiv(h->n_ovf_chunk, CA_TB / 64);
+    ovf.rowptr = h->ovf_rowptr; ovf.col = h->ovf_col; ovf.val = h->ovf_val; ovf.YWextra = YWextra;
     ovf.chunk_start = h->ovf_chunk_start; ovf.row2 = h->ovf_row2; ovf.val2 = h->ovf_val2; ovf.csum = h->ovf_csum; ovf.nchunk = h->n_ovf_chunk;
   }
-  const int nb_main = cdiv(h->ym_GT, 4 * 2);
-  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_yt_mfma<2, 2>), dim3(nb_main + nb_ovf, h->ym_csplit), dim3(CA_YM_TB), 0, h->stream, h->Yb, h->Pq,
-                                                h->ym_GT, h->ym_NS, h->ym_schunk, h->ym_out, nb_main, ovf, h->F, h->D, h->K));
-  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_yt_finish, dim3(cdiv((int64_t)h->G * h->K, CA_TB)), dim3(CA_TB), 0, h->stream, h->ym_out,
-                                                h->ym_csplit, h->ym_GT, h->G, h->K, h->ym_amax, h->n_ovf > 0 ? h->ovf_col_chunk_ptr : nullptr,
-                                                h->n_ovf > 0 ? h->ovf_csum : nullptr, h->red + h->off_y));
-  h->ycache_valid = true;
+  return ovf;
+}
+// The finishing sums over a stream's float partial slabs: column sums of YTpart's `rows` row groups (+ the overflow list's chunk sums per gene) into red_y, laid out
+// [Gp][K] (first G rows used); YW = sum of YWpart's `nseg` strips (+ the overflow list's) and the psi.(YW) partials of the ELBO.  As a struct they ride as extra blocks
+// of the backward sweep (k_bwd_mfma) or of the series form's cell launch; launch_yfinish is the same sums as a launch of their own (k_yfinish = k_colsum's blocks +
+// k_yw_dot's).
+ca_yfin_args yfin_args(ca_engine* h, int rows, int nseg) {
+  ca_yfin_args a;
+  memset(&a, 0, sizeof(a));
+  a.ncol = cdiv((int64_t)h->Gp * h->K, 64); a.nrow = h->n_yw;
+  a.part = h->YTpart; a.out = h->red + h->off_y; a.rows = rows; a.ld = (int64_t)h->Gp * h->K; a.cols = h->Gp * h->K; a.G = h->G;
+  if (h->n_ovf > 0) { a.col_chunk_ptr = h->ovf_col_chunk_ptr; a.csum = h->ovf_csum; }
+  a.YWpart = h->YWpart; a.nseg = nseg + (h->n_ovf > 0 ? 1 : 0); a.F = h->F; a.D = h->D; a.N = h->N; a.YW = h->YW; a.yw_part = h->yw_part;
+  return a;
+}
+int launch_yfinish(ca_engine* h, int rows, int nseg) {
+  const ca_yfin_args a = yfin_args(h, rows, nseg);
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_yfinish, dim3(a.ncol + a.nrow), dim3(1024), 0, h->stream, a.part, a.out, a.rows, a.ld, a.cols, a.col_chunk_ptr,
+                                                a.csum, h->K, a.G, a.ncol, a.YWpart, a.nseg, a.F, a.D, a.N, a.YW, a.yw_part));
   return CA_OK;
 }
 
-#else
-int ycache_mfma(ca_engine* h) { h->err = "internal: the two-copy matrix-core stream is not in this build"; return CA_ERR_STATE; }
-#endif   // CA_LAB
-
-// Both products from ONE tiled copy through the transposing LDS read (k_ys_mfma): a quantiser launch (fixed-point images of W and
+// The same two products on the int8 matrix cores (ca_ymfma.hip.h), both from ONE tiled copy through the transposing LDS read (k_ys_mfma; K = 1): a quantiser launch (fixed-point images of W and
 // psi; exact maxima by a separate pass only for the first state after a reset, afterwards bounded from the previous state's),
 // the stream, the finisher.  Three launches, like the VALU stream's.
 // Arguments of the quantiser for the current parameters (slot ys_slot).  lagged = true: the exponents are bounded from the previous
@@ -163,37 +151,12 @@ ca_ys_io ys_io(ca_engine* h) {
   io.esc_off = h->ys4 ? h->esc_off : nullptr; io.esc = h->ys4 ? h->esc : nullptr;
   return io;
 }
-ca_ovf_args ys_ovf(ca_engine* h) {
-  ca_ovf_args ovf;
-  memset(&ovf, 0, sizeof(ovf));
-  if (h->n_ovf > 0) {
-    ovf.nb_rows = cdiv(h->N, CA_TB); ovf.nb_chunks = cdiv(h->n_ovf_chunk, CA_TB / 64);
-    ovf.rowptr = h->ovf_rowptr; ovf.col = h->ovf_col; ovf.val = h->ovf_val; ovf.YWextra = h->YWpart + (int64_t)h->ys_nseg * h->N;
-    ovf.chunk_start = h->ovf_chunk_start; ovf.row2 = h->ovf_row2; ovf.val2 = h->ovf_val2; ovf.csum = h->ovf_csum; ovf.nchunk = h->n_ovf_chunk;
-  }
-  return ovf;
-}
-// finisher of the one-copy stream: the vector stream's own (k_yfinish) over the float partial slabs the stream left; advances
-// the quantiser's slot ring
+ca_ovf_args ys_ovf(ca_engine* h) { return ovf_args(h, h->YWpart + (int64_t)h->ys_nseg * h->N); }
+// finisher of the one-copy stream: the vector stream's own (k_yfinish) over the float partial slabs the stream left
 int yfin_flush(ca_engine* h) {
   if (!h->yfin_pending) return CA_OK;
   h->yfin_pending = false;
-  const int nb_col = cdiv((int64_t)h->Gp, 64);
-  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_yfinish, dim3(nb_col + h->n_yw), dim3(1024), 0, h->stream, h->YTpart, h->red + h->off_y, h->ys_nrg,
-                                                (int64_t)h->Gp, h->Gp, h->n_ovf > 0 ? h->ovf_col_chunk_ptr : nullptr,
-                                                h->n_ovf > 0 ? h->ovf_csum : nullptr, 1, h->G, nb_col, h->YWpart,
-                                                h->ys_nseg + (h->n_ovf > 0 ? 1 : 0), h->F, h->D, h->N, h->YW, h->yw_part));
-  return CA_OK;
-}
-// the same sums as extra blocks of the backward sweep (k_bwd_mfma)
-ca_yfin_args yfin_args(ca_engine* h) {
-  ca_yfin_args a;
-  memset(&a, 0, sizeof(a));
-  a.ncol = cdiv((int64_t)h->Gp, 64); a.nrow = h->n_yw;
-  a.part = h->YTpart; a.out = h->red + h->off_y; a.rows = h->ys_nrg; a.ld = h->Gp; a.cols = h->Gp; a.G = h->G;
-  if (h->n_ovf > 0) { a.col_chunk_ptr = h->ovf_col_chunk_ptr; a.csum = h->ovf_csum; }
-  a.YWpart = h->YWpart; a.nseg = h->ys_nseg + (h->n_ovf > 0 ? 1 : 0); a.F = h->F; a.D = h->D; a.N = h->N; a.YW = h->YW; a.yw_part = h->yw_part;
-  return a;
+  return launch_yfinish(h, h->ys_nrg, h->ys_nseg);
 }
 // the stream's slabs are complete (launch issued): finisher now, or left pending for the backward sweep that follows in the loop;
 // advances the quantiser's slot ring
@@ -206,22 +169,22 @@ int ys_finish(ca_engine* h, bool defer = false) {
   h->ycache_valid = true;
   return CA_OK;
 }
+template <bool Y4>
+void launch_ys(ca_engine* h) {
+  constexpr int lds = Y4 ? CA_YS4_LDS_BYTES : CA_YS_LDS_BYTES;
+  const int nb_main = h->ys_nrg * h->ys_nseg;
+  if (h->n_ovf > 0) {   // (the overflow list's blocks behind the stream's)
+    const ca_ovf_args ovf = ys_ovf(h);
+    hipLaunchKernelGGL(k_ys_mfma_ovf<Y4>, dim3(nb_main + ovf.nb_rows + ovf.nb_chunks), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS,
+                       nb_main, ovf, h->F, h->V, h->D);
+  } else {
+    hipLaunchKernelGGL(k_ys_mfma<Y4>, dim3(nb_main), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS);
+  }
+}
 int ycache_ys(ca_engine* h) {
   CACK(ys_quant(h));
-  const int nb_main = h->ys_nrg * h->ys_nseg;
-  if (h->n_ovf > 0) {
-    const ca_ovf_args ovf = ys_ovf(h);
-    const dim3 grid(nb_main + ovf.nb_rows + ovf.nb_chunks);
-    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf<true>, grid, dim3(CA_YM_TB), CA_YS4_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
-                                                              h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D));
-    else LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma_ovf<false>, grid, dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h), h->N,
-                                                       h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D));
-  } else {
-    if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma<true>, dim3(nb_main), dim3(CA_YM_TB), CA_YS4_LDS_BYTES, h->stream, h->Ys, ys_io(h),
-                                                              h->N, h->Gp, h->ys_RS));
-    else LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL(k_ys_mfma<false>, dim3(nb_main), dim3(CA_YM_TB), CA_YS_LDS_BYTES, h->stream, h->Ys, ys_io(h),
-                                                       h->N, h->Gp, h->ys_RS));
-  }
+  if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, launch_ys<true>(h));
+  else LAUNCH(h, CA_KERNEL_YPASS, launch_ys<false>(h));
   const bool defer = h->ys_defer_next;
   h->ys_defer_next = false;
   return ys_finish(h, defer);
@@ -240,26 +203,17 @@ int ensure_ycache(ca_engine* h) {
     CACK(rc);
     HIPCK(h, hipEventRecord(h->ev_ydone, h->stream2));
     h->y_pending = true;
-    if (!h->yw_pending) {   // (the VALU stream has no earlier point: its row products are finished by its last launch)
-      HIPCK(h, hipEventRecord(h->ev_ywdone, h->stream2));
-      h->yw_pending = true;
-    }
+    HIPCK(h, hipEventRecord(h->ev_ywdone, h->stream2));   // (no earlier point: the row products are finished by the stream's last launch)
+    h->yw_pending = true;
     return CA_OK;
   }
   if (h->ycache_valid || h->K == 0) { h->ycache_valid = true; return yfin_flush(h); }
   h->yfin_pending = false;
   if (h->y_ys) return ycache_ys(h);
-  if (h->y_mfma) return ycache_mfma(h);
   dim3 grid((unsigned)((int64_t)h->nrg * h->nseg));
   // entries above 255: one extra "segment" of YW and one extra term of Y^T psi; their per-entry work rides on the
   // first stream launch, the per-gene sums on the column-sum launch
-  ca_ovf_args ovf;
-  memset(&ovf, 0, sizeof(ovf));
-  if (h->n_ovf > 0) {
-    ovf.nb_rows = cdiv(h->N, CA_TB); ovf.nb_chunks = cdiv(h->n_ovf_chunk, CA_TB / 64);
-    ovf.rowptr = h->ovf_rowptr; ovf.col = h->ovf_col; ovf.val = h->ovf_val; ovf.YWextra = h->YWpart + (int64_t)h->nseg * h->N * h->K;
-    ovf.chunk_start = h->ovf_chunk_start; ovf.row2 = h->ovf_row2; ovf.val2 = h->ovf_val2; ovf.csum = h->ovf_csum; ovf.nchunk = h->n_ovf_chunk;
-  }
+  const ca_ovf_args ovf = ovf_args(h, h->YWpart + (int64_t)h->nseg * h->N * h->K);
   ca_ovf_args none;
   memset(&none, 0, sizeof(none));
   for (int koff = 0; koff < h->K; koff += 4) {
@@ -274,13 +228,9 @@ int ensure_ycache(ca_engine* h) {
   }
   // YTpart is [nrb][Gp*K]: column sums over the row blocks (+ the overflow list's chunk sums per gene); ytpsi is laid
   // out [Gp][K] (first G rows used).  Row side: YW = sum of the strips, and the psi.(YW) partials of the ELBO (the fused
-  // loop's cell epilogue leaves both to this).  One launch for both (k_yfinish = k_colsum's blocks + k_yw_dot's).
+  // loop's cell epilogue leaves both to this).  One launch for both (launch_yfinish).
   if (!h->on_side) {
-    const int nb_col = cdiv((int64_t)h->Gp * h->K, 64);
-    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_yfinish, dim3(nb_col + h->n_yw), dim3(1024), 0, h->stream, h->YTpart, h->red + h->off_y, h->nrg,
-                                                  (int64_t)h->Gp * h->K, h->Gp * h->K, h->n_ovf > 0 ? h->ovf_col_chunk_ptr : nullptr,
-                                                  h->n_ovf > 0 ? h->ovf_csum : nullptr, h->K, h->G, nb_col, h->YWpart,
-                                                  h->nseg + (h->n_ovf > 0 ? 1 : 0), h->F, h->D, h->N, h->YW, h->yw_part));
+    CACK(launch_yfinish(h, h->nrg, h->nseg));
   } else {
     // on the side stream, beside the forward sweep, the two finishers stay two small launches: the merged one's 1024-thread
     // blocks need sixteen free wave slots at once and took 64 us to get through a GPU the sweep has filled (profiles/r02_v1_timeline.txt)
@@ -621,7 +571,7 @@ int train_bwd(ca_engine* h, const float* mu32, bool cell_sums_global) {
     // slabs -- fwd, bwd, all-reduce, update: four launches where there were six.  Other transports keep the launches.
     ride_ar = is_sharded(h) && p2p_ride_ok(h, h->red_n);
     if (is_sharded(h) && !ride_ar) CACK(yfin_flush(h));   // (the tail's local sums go into this pass's all-reduce, so they stay here)
-    if (h->yfin_pending) { yfin = yfin_args(h); h->yfin_pending = false; }
+    if (h->yfin_pending) { yfin = yfin_args(h, h->ys_nrg, h->ys_nseg); h->yfin_pending = false; }
     ca_small_args bwd_tail = no_small_args();
     bool split_tail = false;
     if (h->mon_tail.enabled && h->mon_tail.cell_part) {
@@ -971,7 +921,7 @@ int run_pass(ca_engine* h, int64_t eps_slot, int mode, int apply, double* elbo_d
     }
   CACK(wait_y(h, true));   // the cell epilogue is the first consumer of YW / Y^T psi
   // (matrix-core products arrive as finished row sums: one "strip", already in YW)
-  const bool yw_done = h->y_mfma || h->y_ys;
+  const bool yw_done = h->y_ys;
   const float* ywp = yw_done ? h->YW : h->YWpart;
   const int ywseg = yw_done ? 1 : h->nseg + (h->n_ovf > 0 ? 1 : 0);
   if (h->C <= 64) {
@@ -1088,6 +1038,25 @@ int poly_guard(ca_engine* h, bool* use_series, double** mirror, double* seq, boo
   return CA_OK;
 }
 
+// Block order of a launch the count-matrix stream rides on (ca_yride_args / ca_ysride_args: nb_main stream units, nb_y with the overflow list's blocks; nf
+// sweep blocks); returns the grid's block count.
+// Interleave of the two kinds in dispatch order.  Blocks go round-robin over the 8 XCDs, so a period that divides 8 (the
+// obvious even / odd split) puts ALL sweep blocks on four XCDs and all stream blocks on the other four; two sweep blocks per
+// stream block mixes them on every CU: cfg-3 2795 -> 3008 it/s, 12.5k cells 10.9k -> 12.1k, cfg-2 16.3k -> 17.9k
+// (profiles/r02_ab_ystream.txt section 8).
+// Long-lived stream blocks lead the grid (ca_yride_args::pers) when there are at least two units of the matrix per CU: one
+// such block per CU measured best (cfg-3, with the non-temporal stream: 2:1 interleave 3090, 256 blocks 3147, 341 / 512
+// blocks 3008 / 2979, 192 / 128 blocks 2790 / 2320 it/s).  ca_options.ride_pattern < 0 sets the number, > 0 asks for the interleave (a << 8 | b).
+template <typename RideArgs>
+unsigned ride_pattern(const ca_engine* h, RideArgs& ya, int nf) {
+  const int rp = h->opt.ride_pattern;
+  ya.pat_a = 2; ya.pat_b = 1;
+  if (rp > 0 && (rp >> 8) > 0 && (rp & 255) > 0) { ya.pat_a = rp >> 8; ya.pat_b = rp & 255; }
+  if (rp < 0) ya.pers = std::min(-rp, ya.nb_main);
+  else if (rp == 0 && ya.nb_main >= 2 * h->n_cu) ya.pers = h->n_cu;
+  return ya.pers > 0 ? (unsigned)(ya.pers + nf + (ya.nb_y - ya.nb_main)) : (unsigned)(nf + ya.nb_y);
+}
+
 // Monitor pass for eps slot A fused with the forward half of the NEXT train pass (eps slot B): one sweep,
 // one exp per (cell, gene) for both (same parameters, R/inference-tflow.R:401,403 of consecutive iterations).
 int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, double* elbo_dstB = nullptr, int64_t trainA = -1) {
@@ -1191,7 +1160,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     h->ys_defer_next = false;
     ca_yfin_args yfin_ride;
     const bool yfin_rides = h->yfin_pending;
-    if (yfin_rides) { yfin_ride = yfin_args(h); h->yfin_pending = false; }
+    if (yfin_rides) { yfin_ride = yfin_args(h, h->ys_nrg, h->ys_nseg); h->yfin_pending = false; }
     if (moments_aside) HIPCK(h, hipStreamWaitEvent(h->stream, h->ev_poly1, 0));
     CACK(prof_begin(h, CA_KERNEL_FWD));
     // cell-sharded: what the iteration's collective needs from this rank besides the moments -- the monitor pass's local block sums (red[0 .. 3 + C)) and the
@@ -1223,13 +1192,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     ya.Gp = h->Gp; ya.RS = h->ys_RS; ya.nb_main = h->ys_nrg * h->ys_nseg; ya.nb_y = ya.nb_main;
     ya.ovf = ys_ovf(h);
     ya.nb_y += ya.ovf.nb_rows + ya.ovf.nb_chunks;
-    ya.pat_a = 2; ya.pat_b = 1;
-    if (h->opt.ride_pattern > 0 && (h->opt.ride_pattern >> 8) > 0 && (h->opt.ride_pattern & 255) > 0) {
-      ya.pat_a = h->opt.ride_pattern >> 8; ya.pat_b = h->opt.ride_pattern & 255;
-    }
-    if (h->opt.ride_pattern < 0) ya.pers = std::min(-h->opt.ride_pattern, ya.nb_main);
-    else if (h->opt.ride_pattern == 0 && ya.nb_main >= 2 * h->n_cu) ya.pers = h->n_cu;
-    const dim3 grid(ya.pers > 0 ? (unsigned)(ya.pers + h->ncblk_f + (ya.nb_y - ya.nb_main)) : (unsigned)(h->ncblk_f + ya.nb_y));
+    const dim3 grid(ride_pattern(h, ya, h->ncblk_f));
 #define CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, Y4V)                                                                                                   \
   LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_ys<DV, TLBV, 2, DPV, C16V, S2FV, Y4V>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, \
                                               h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya))
@@ -1249,8 +1212,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
       ca_bal_args ba;
       memset(&ba, 0, sizeof(ba));
       ba.nb = h->n_cu; ba.r = h->bal_r; ba.nchunk = h->bal_nchunk; ba.xw = h->bal_xw;
-      ba.extra = h->bal_nchunk == 0 ? h->bal_r : 0;   // left-over tiles exchanged in gene chunks (default), or as single-tile blocks of their own
-      cell_blocks = h->n_cu + ba.extra;               // (a row of block partials per block that runs an epilogue)
+      cell_blocks = h->n_cu;   // (a row of block partials per block that runs an epilogue)
       if (++h->bal_tag == 0u) h->bal_tag = 1u;
       ba.tag = h->bal_tag;
       ba.timeout_ticks = 50000000ull;   // 0.5 s: every chunk a block waits for was dispatched before it and is made first
@@ -1259,7 +1221,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
       // (measured, 8192 ... 25 000 cells x 5000 genes: one unit per block is 2-4 us per iteration faster at every size, gpurun_out/r5/stair_units.txt;
       //  ride_pattern = 2 asks for two)
       ba.stream_units = h->opt.ride_pattern == 2 ? 2 : 1;
-      const dim3 gridb((unsigned)(h->n_cu + ba.extra + (ba.stream_units == 2 ? (ya.nb_main + 1) / 2 : ya.nb_main) + (ya.nb_y - ya.nb_main)));   // sweep blocks, left-over tiles' blocks, stream blocks, the overflow list's
+      const dim3 gridb((unsigned)(h->n_cu + (ba.stream_units == 2 ? (ya.nb_main + 1) / 2 : ya.nb_main) + (ya.nb_y - ya.nb_main)));   // sweep blocks, stream blocks, the overflow list's
 #define CA_FBAL(TLV) if (h->ys4) CA_FBAL_L(TLV, true); else CA_FBAL_L(TLV, false)
 #define CA_FBAL_L(TLV, Y4V) LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_bal_ys<1, TLV, CA_YS_RIDE_DEPTH, Y4V>), gridb, dim3(CA_BAL_TB), 0, h->stream, h->F, h->etamax2, \
                                                                  h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, ba, ya))
@@ -1288,57 +1250,17 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     ya.Y = (const uint8_t*)h->Y; ya.F = h->F; ya.Dstride = h->D; ya.V = h->V; ya.YWpart = h->YWpart; ya.YTpart = h->YTpart;
     ya.G = h->G; ya.Gp = h->Gp; ya.nseg = h->nseg; ya.nrb = h->nrb; ya.TR = h->TR;
     ya.nb_main = h->nrg * h->nseg; ya.nb_y = ya.nb_main;
-    if (h->n_ovf > 0) {
-      ya.ovf.nb_rows = cdiv(h->N, CA_TB); ya.ovf.nb_chunks = cdiv(h->n_ovf_chunk, CA_TB / 64);
-      ya.ovf.rowptr = h->ovf_rowptr; ya.ovf.col = h->ovf_col; ya.ovf.val = h->ovf_val; ya.ovf.YWextra = h->YWpart + (int64_t)h->nseg * h->N * h->K;
-      ya.ovf.chunk_start = h->ovf_chunk_start; ya.ovf.row2 = h->ovf_row2; ya.ovf.val2 = h->ovf_val2; ya.ovf.csum = h->ovf_csum; ya.ovf.nchunk = h->n_ovf_chunk;
-      ya.nb_y += ya.ovf.nb_rows + ya.ovf.nb_chunks;
-    }
-    // Interleave of the two kinds in dispatch order.  Blocks go round-robin over the 8 XCDs, so a period that divides 8 (the
-    // obvious even / odd split) puts ALL sweep blocks on four XCDs and all stream blocks on the other four; two sweep blocks per
-    // stream block mixes them on every CU: cfg-3 2795 -> 3008 it/s, 12.5k cells 10.9k -> 12.1k, cfg-2 16.3k -> 17.9k
-    // (profiles/r02_ab_ystream.txt section 8).
-    ya.pat_a = 2; ya.pat_b = 1;
-    if (h->opt.ride_pattern > 0 && (h->opt.ride_pattern >> 8) > 0 && (h->opt.ride_pattern & 255) > 0) {
-      ya.pat_a = h->opt.ride_pattern >> 8; ya.pat_b = h->opt.ride_pattern & 255;
-    }
-    // ride_seq: no separate stream blocks -- sweep block b also streams unit b (k_fwd_cell_seq_y); units past the sweep's block
-    // count and the overflow list's blocks follow as stream-only blocks
-    const bool seq = h->ride_seq;
-    // Long-lived stream blocks lead the grid (ca_yride_args::pers) when there are at least two units of the matrix per CU: one
-    // such block per CU measured best (cfg-3, with the non-temporal stream: 2:1 interleave 3090, 256 blocks 3147, 341 / 512
-    // blocks 3008 / 2979, 192 / 128 blocks 2790 / 2320 it/s).  ride_pattern < 0 sets the number, > 0 asks for the interleave.
-    if (!seq && h->opt.ride_pattern < 0) ya.pers = std::min(-h->opt.ride_pattern, ya.nb_main);
-    else if (!seq && h->opt.ride_pattern == 0 && ya.nb_main >= 2 * h->n_cu) ya.pers = h->n_cu;
-    const dim3 grid(seq ? (unsigned)(h->ncblk_f + std::max(0, ya.nb_main - h->ncblk_f) + (ya.nb_y - ya.nb_main))
-                        : ya.pers > 0 ? (unsigned)(ya.pers + h->ncblk_f + (ya.nb_y - ya.nb_main)) : (unsigned)(h->ncblk_f + ya.nb_y));
-#ifdef CA_LAB   // (the stream fused in sequence into the sweep's blocks, CA_VARX_RIDE_SEQ: measured slower, lab library only)
-#define CA_FCY_SEQ(DV, TLBV)                                                                                                          \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_seq_y<DV, TLBV, 2>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, \
-                                                  cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya))
-#else
-#define CA_FCY_SEQ(DV, TLBV) do { h->err = "internal: the sequence-fused riding stream is not in this build"; return CA_ERR_STATE; } while (0)
-#endif
+    ya.ovf = ovf_args(h, h->YWpart + (int64_t)h->nseg * h->N * h->K);
+    ya.nb_y += ya.ovf.nb_rows + ya.ovf.nb_chunks;
+    const dim3 grid(ride_pattern(h, ya, h->ncblk_f));
 #define CA_FCY(DV, TLBV)                                                                                                              \
-  do {                                                                                                                                \
-    if (seq)                                                                                                                          \
-      CA_FCY_SEQ(DV, TLBV);                                                                                                           \
-    else                                                                                                                              \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_y<DV, TLBV, 2>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, \
-                                                  cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya)); \
-  } while (0)
+  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_y<DV, TLBV, 2>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, \
+                                              cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya))
     if (h->fc_tl == 8) { if (h->D == 1) CA_FCY(1, 8); else CA_FCY(2, 8); }
     else if (h->fc_tl == 6) { if (h->D == 1) CA_FCY(1, 6); else CA_FCY(2, 6); }
     else { if (h->D == 1) CA_FCY(1, 2); else CA_FCY(2, 2); }
 #undef CA_FCY
-#undef CA_FCY_SEQ
-    {   // the stream's finishers, in line behind the launch they rode on (one launch: column sums + row sums / psi.(YW) partials)
-      const int nb_col = cdiv((int64_t)h->Gp * h->K, 64);
-      LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_yfinish, dim3(nb_col + h->n_yw), dim3(1024), 0, h->stream, h->YTpart, h->red + h->off_y, h->nrg,
-                                                    (int64_t)h->Gp * h->K, h->Gp * h->K, h->n_ovf > 0 ? h->ovf_col_chunk_ptr : nullptr,
-                                                    h->n_ovf > 0 ? h->ovf_csum : nullptr, h->K, h->G, nb_col, h->YWpart,
-                                                    h->nseg + (h->n_ovf > 0 ? 1 : 0), h->F, h->D, h->N, h->YW, h->yw_part));
-    }
+    CACK(launch_yfinish(h, h->nrg, h->nseg));   // the stream's finishers, in line behind the launch they rode on
     h->ycache_valid = true;
   } else if (h->fwd_cell) {   // sweep + cell epilogue in one kernel: no Z partials, one launch
     cell_blocks = h->ncblk_f;

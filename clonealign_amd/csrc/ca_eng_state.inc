@@ -161,7 +161,6 @@ struct ca_engine {
   bool y_defer = false;
   bool ride_ok = false;   // the Y stream's blocks ride on the forward sweep's launch (k_fwd_cell_mix_y) instead of a side stream
   bool ride_ys = false;   // ... as the one-copy int8 matrix-core stream (k_fwd_cell_mix_ys)
-  bool ride_seq = false;  // ... fused in sequence into the sweep's own blocks (k_fwd_cell_seq_y)
   bool fold_gsum = false, fold_now = false;   // small problems: the backward sweep's partials are summed inside k_final_gene
   // per-gene prologue of the next fused pass, computed ahead by the train pass before it (ca_pre_args): the loops announce
   // the next (monitor, train) eps slots in hint_*, train_update fills the alternate partial buffers, fused_pass swaps them in
@@ -194,12 +193,8 @@ struct ca_engine {
   unsigned short* coefq = nullptr; int64_t N16 = 0, cchunk_m = 0; int csplit_m = 1, nwt = 0;
   int bwd_tl = CA_BWD_TL;   // gene tiles of 16 per wave in the matrix-core backward sweep: 4, or 3 for small problems (more, shorter wave jobs)
   uint64_t draw = 0;  // built-in stream position
-  // count-matrix products on the int8 matrix cores (ca_ymfma.hip.h): tiled copies, fixed-point parameter images
-  bool y_mfma = false;
-  int64_t ym_NT = 0, ym_NS = 0, ym_schunk = 0; int ym_GS = 0, ym_GT = 0, ym_csplit = 1, ym_tl = 4;
-  uint4 *Yf = nullptr, *Yb = nullptr, *Wq = nullptr, *Pq = nullptr; unsigned* ym_amax = nullptr; int* ym_out = nullptr;
   hipEvent_t ev_ywdone = nullptr; bool yw_pending = false, on_side = false;
-  // ... and from ONE tiled copy through the transposing LDS read (k_ys_mfma; K = 1)
+  // count-matrix products on the int8 matrix cores (ca_ymfma.hip.h): ONE tiled copy through the transposing LDS read (k_ys_mfma; K = 1), fixed-point parameter images
   bool y_ys = false, ys4 = false; int* esc_off = nullptr; unsigned* esc = nullptr; int64_t n_esc = 0;
   uint8_t* Ys = nullptr; uint4 *Wr = nullptr, *Pr = nullptr; int *Wsum = nullptr, *Psum = nullptr;
   int* ys_exps = nullptr;        // [3][2]: rotating slots, see ca_ys_quant_body
@@ -363,17 +358,9 @@ inline bool variantx_on(const ca_engine* h, unsigned bit, const char* env) {   /
   if (debug_env()) if (const char* e = getenv(env)) return atoi(e) != 0;
   return false;
 }
-// Opt-in variants that were measured slower than what ships and are kept as evidence (round 6, VERDICT r5 #7): the LAB library only (`make lab`, -DCA_LAB).  The
-// product library has neither their kernels nor their host paths, and ca_create refuses the bits instead of ignoring them.
-#define CA_LAB_VARX (CA_VARX_Y_MFMA2 | CA_VARX_RIDE_SEQ | CA_VARX_BAL_TILES)
-inline bool lab_variantx_on(const ca_engine* h, unsigned bit, const char* env) {
-#ifdef CA_LAB
-  return variantx_on(h, bit, env);
-#else
-  (void)h; (void)bit; (void)env;
-  return false;
-#endif
-}
+// Opt-in variants that were measured slower than what ships (rounds 2-5; DESIGN_HISTORY.md, profiles/) and whose code has been deleted: ca_create refuses the
+// bits, in every build, instead of ignoring them.
+#define CA_RETIRED_VARX (CA_VARX_Y_MFMA2 | CA_VARX_RIDE_SEQ | CA_VARX_BAL_TILES)
 inline int tune_val(const ca_engine* h, int id, const char* env) {
   int v = h->opt.tune[id];
   if (v == 0 && debug_env()) if (const char* e = getenv(env)) { v = atoi(e); if (id == CA_TUNE_FC_NBIG && v == 0) v = -1; }

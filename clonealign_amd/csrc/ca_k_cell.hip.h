@@ -897,60 +897,3 @@ __global__ void __launch_bounds__(CA_TB, CA_RIDE_WAVES) k_fwd_cell_mix_y(const f
   }
   CA_LAB_BLOCK_END(sweep ? (nbig > 0 && idx >= nbig ? 2 : 1) : 0, idx);
 }
-
-// The Y stream FUSED IN SEQUENCE with the sweep (round 3): every sweep block also streams one unit of the count matrix (one gene
-// segment x four row blocks, what a k_ypass block does), either before or after its sweep.  Block timelines of the interleaved
-// form (tools/stamps.py, profiles/r03_ab_ystream.txt) show why: everything resident on a CU -- sweep and stream blocks alike --
-// ends when that CU's vector work is done, CUs that drew two, three or four sweep blocks at the start end at 42, 62 and 83 us,
-// a stream block needs 83 us instead of the 40 it takes alone, and the launch ends when the last stragglers have gone through.
-// Here every block carries the same work, so every CU carries the same work, and at any time about half the blocks of a CU are
-// in their (latency-bound) stream phase while the other half has the vector pipes: which half goes first alternates along the
-// XCD's own block sequence, whichever way the dispatcher deals that sequence over the CUs (i = b / 8: i ^ (i >> 5)).
-// Blocks past the sweep's own: leftover stream units (small shards have more units than sweep blocks), then the overflow list's.
-template <int D, int TLB, int TLS>
-__global__ void __launch_bounds__(CA_TB, CA_RIDE_WAVES) k_fwd_cell_seq_y(const float* __restrict__ F, const float* __restrict__ etamax2,
-                                                                         const float* __restrict__ Vs, const unsigned short* __restrict__ Mq,
-                                                                         ca_cell_ptrs p, const float* __restrict__ alpha_u,
-                                                                         double* __restrict__ cell_part, int64_t N, int C, int K, int nk, int nbig,
-                                                                         int nf, ca_yride_args y) {
-  constexpr size_t FW = sizeof(ca_f32x4) * 4 * TLB * 64 + sizeof(double) * (CA_TB + 64);
-  constexpr size_t YW_ = sizeof(float) * (CA_TB / 64) * 64 * 17;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[FW > YW_ ? FW : YW_];
-  const int b = (int)blockIdx.x;
-  CA_LAB_BLOCK_T0();
-  const bool sweep_blk = b < nf;
-  int unit;
-  bool first = false;
-  if (!sweep_blk) {                                // stream-only blocks
-    const int e = b - nf, rest = y.nb_main > nf ? y.nb_main - nf : 0;
-    unit = e < rest ? nf + e : y.nb_main + (e - rest);
-  } else {
-    const int i = b >> 3;
-    unit = b < y.nb_main ? b : -1;
-    first = ((i ^ (i >> 5)) & 1) != 0;
-  }
-  if (unit >= 0 && (!sweep_blk || first)) {
-    CA_PRIO_STREAM();
-    ca_ypass_body<uint8_t, 1, 0>(unit, y.Y, y.F, y.Dstride, y.V, 0, y.YWpart, y.YTpart, N, y.G, y.Gp, y.nseg, y.nrb, y.TR, 1, y.ovf, y.nb_main,
-                                 reinterpret_cast<float (*)[64][17]>(smem));
-    if (sweep_blk) __syncthreads();
-  }
-  if (sweep_blk) {
-    ca_f32x4* comb = reinterpret_cast<ca_f32x4*>(smem);
-    double* sm = reinterpret_cast<double*>(smem + sizeof(ca_f32x4) * 4 * TLB * 64);
-    double* la = sm + CA_TB;
-    ca_log_softmax_alpha(alpha_u, C, la);
-    if (nbig > 0 && b >= nbig)
-      ca_fwd_cell_body<D, TLS>(F, etamax2, Vs, Mq, p, cell_part, N, C, K, nk, (int64_t)nbig * (TLB * 16) + (int64_t)(b - nbig) * (TLS * 16), b, comb, sm, la);
-    else
-      ca_fwd_cell_body<D, TLB>(F, etamax2, Vs, Mq, p, cell_part, N, C, K, nk, (int64_t)b * (TLB * 16), b, comb, sm, la);
-    if (unit >= 0 && !first) {
-      __syncthreads();
-      CA_PRIO_STREAM();
-      ca_ypass_body<uint8_t, 1, 0>(unit, y.Y, y.F, y.Dstride, y.V, 0, y.YWpart, y.YTpart, N, y.G, y.Gp, y.nseg, y.nrb, y.TR, 1, y.ovf, y.nb_main,
-                                   reinterpret_cast<float (*)[64][17]>(smem));
-    }
-  }
-  CA_LAB_BLOCK_END(b >= nf ? 0 : (nbig > 0 && b >= nbig ? 2 : 1), b);
-}
-

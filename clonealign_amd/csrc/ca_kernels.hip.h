@@ -714,41 +714,6 @@ __global__ void __launch_bounds__(CA_UM_TB) k_update_merged(const double* __rest
   if (b == 0) CA_LAB_CP(43, 1);
 }
 
-// Column products, engine form: the sweep of ca_yt_block plus, as extra blocks of the launch, the gene side of the overflow
-// list (per-chunk sums of the counts above 255; they depend on psi only).
-template <int TL, int DEPTH>
-__global__ void __launch_bounds__(CA_YM_TB) k_yt_mfma(const uint4* __restrict__ Yb, const uint4* __restrict__ Pq, int GT, int64_t NS,
-                                                      int64_t schunk, int* __restrict__ out, int nb_main, ca_ovf_args ovf,
-                                                      const float* __restrict__ F, int Df, int K) {
-  if ((int)blockIdx.x >= nb_main) {
-    if (blockIdx.y == 0) ca_ovf_chunks_body(blockIdx.x - nb_main, ovf.chunk_start, ovf.row2, ovf.val2, F, Df, ovf.csum, ovf.nchunk, K, 0);
-    return;
-  }
-  ca_yt_block<TL, DEPTH>(Yb, Pq, GT, NS, schunk, out);
-}
-#ifdef CA_LAB   // (CA_VARX_Y_MFMA2's finisher)
-// Y^T psi from the slices' digit sums: integer sum over the slices (exact), digits combined in fp64, the fixed-point scale
-// taken out, the overflow list's chunk sums of the gene added.  One thread per (gene, k); red_y is [G][K].
-__global__ void __launch_bounds__(CA_TB) k_yt_finish(const int* __restrict__ out /*[csplit][GT * 16][16]*/, int csplit, int GT, int G, int K,
-                                                     const unsigned* __restrict__ amax, const int* __restrict__ col_chunk_ptr,
-                                                     const float* __restrict__ csum, double* __restrict__ red_y) {
-  const int i = blockIdx.x * CA_TB + threadIdx.x;
-  if (i >= G * K) return;
-  const int g = i / K, k = i - g * K;
-  double v = 0.0;
-#pragma unroll
-  for (int p = 3; p >= 0; --p) {
-    long long a = 0;
-    for (int sp = 0; sp < csplit; ++sp) a += out[(((int64_t)sp * GT * 16) + g) * 16 + 4 * k + p];
-    v = v * 256.0 + (double)a;
-  }
-  v *= ldexp(1.0, -ca_fix_exp(__uint_as_float(amax[1])));
-  if (csum)
-    for (int ch = col_chunk_ptr[g]; ch < col_chunk_ptr[g + 1]; ++ch) v += (double)csum[(int64_t)ch * K + k];
-  red_y[i] = v;
-}
-
-#endif   // CA_LAB
 // ------------------------------------------------------------------ one-shot peer-to-peer all-reduce
 // Round 4: the flag travels IN the data.  Slab of a rank (fine-grained device memory, IPC-mapped by every peer):
 //   inbox[parity 2][source rank W][cap entries], one entry = 16 bytes = {low half of the double, tag} {high half, tag}, each 8-byte half

@@ -287,11 +287,9 @@ static int create_common(const ca_problem* p, const ca_sparse* sp, const ca_opti
   if (p->K > 0 && !p->psi0) return bad("psi0 is required when K > 0");
   if (p->P > 0 && !p->X) return bad("X is required when P > 0");
   if (opt.world < 1 || opt.rank < 0 || opt.rank >= opt.world) return bad("bad rank/world");
-#ifndef CA_LAB
-  if (opt.variant_on & CA_LAB_VARX)
-    return bad("ca_options.variant_on asks for a variant that is built into the lab library only (CA_VARX_Y_MFMA2, CA_VARX_RIDE_SEQ, CA_VARX_BAL_TILES: measured slower than "
-               "what ships; `make -C clonealign_amd/csrc lab`)");
-#endif
+  if (opt.variant_on & CA_RETIRED_VARX)
+    return bad("ca_options.variant_on asks for a variant that was removed (CA_VARX_Y_MFMA2, CA_VARX_RIDE_SEQ, CA_VARX_BAL_TILES: measured slower than what ships; "
+               "the measurements are in DESIGN_HISTORY.md and profiles/, the code in the history)");
   if ((p->cell_index || p->gene_index) && (p->N_src < p->N || p->G_src < p->G)) return bad("N_src / G_src must be at least N / G when a selection is given");
   ca_engine* h = new ca_engine();
   h->N = p->N; h->G = p->G; h->C = p->C; h->K = p->K; h->P = p->P; h->S = p->S; h->D = D;
@@ -359,7 +357,7 @@ int ca_get_info(ca_handle h, ca_info* i) {
   i->y_storage = h->ystore; i->y_bytes_per_elem = h->ybytes; i->y_device_bytes = h->y_dev_bytes; i->device_bytes = h->dev_bytes;
   i->gsplit = h->gsplit; i->csplit = h->csplit; i->n_cu = h->n_cu; i->fused_sweep = h->fused_ok ? 1 : 0;
   i->fwd_mfma = ((h->fused_ok && h->fwd_mfma) || h->pfwd) ? 1 : 0; i->bwd_mfma = h->bwd_mfma ? 1 : 0; i->fsplit = h->fsplit; i->fwd_cell = (h->fused_ok && h->fwd_cell) ? 1 : 0;
-  i->y_mfma = h->y_ys ? 2 : h->y_mfma ? 1 : 0;
+  i->y_mfma = h->y_ys ? 2 : 0;
   i->y_stream_bits = h->y_ys ? (h->ys4 ? 4 : 8) : 0;
   i->y_ride = (h->ride_ok || h->ride_ys) ? 1 : 0;
   i->transport = (h->p2p && h->p2p->connected) ? CA_TRANSPORT_P2P : h->comm ? CA_TRANSPORT_RCCL : h->host_ar ? CA_TRANSPORT_HOST : CA_TRANSPORT_NONE;

@@ -123,19 +123,17 @@ enum ca_variant {
   CA_VAR_Y4 = 1 << 22,        /* the one-copy stream's loop image at 4 bits per count (min(y, 15) in a nibble, the counts from 15 up as their exact excess in
                                  an escape list bucketed by the stream's own units): half the bytes per pass, the same integer sums; picked where the escapes
                                  are at most 1 in 64 counts (CA_VARX_Y4 forces it).  Off: the 1-byte loop image */
-  CA_VAR_RIDE_SEQ = 1 << 13   /* off: the riding stream as blocks of its own interleaved in the sweep's grid (k_fwd_cell_mix_y), never fused in
-                                 sequence into the sweep's blocks (k_fwd_cell_seq_y; see CA_VARX_RIDE_SEQ) */
+  CA_VAR_RIDE_SEQ = 1 << 13   /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
-/* Opt-in variants (bits of ca_options.variant_on).  Those marked LAB were measured slower than what ships and are kept as the evidence for the choice (DESIGN_HISTORY.md):
- * since round 6 they are compiled into the lab library only (`make -C clonealign_amd/csrc lab`, -DCA_LAB); ca_create of the product library returns CA_ERR_INVALID for them. */
+/* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
+ * code has been deleted; the constants keep their values and ca_create returns CA_ERR_INVALID for them, in every build. */
 enum ca_variant_on {
-  CA_VARX_Y_MFMA2 = 1 << 0,   /* LAB.  count-matrix products on the int8 matrix cores from TWO tiled copies (cell-tiled for Y.W,
-                                 gene-tiled for Y^T.psi; ca_ymfma.hip.h): 6.0 TB/s per stream against 4.7 for k_ypass, but twice
-                                 the bytes per iteration */
+  CA_VARX_Y_MFMA2 = 1 << 0,   /* RETIRED.  count-matrix products on the int8 matrix cores from TWO tiled copies (cell-tiled for Y.W,
+                                 gene-tiled for Y^T.psi): 6.0 TB/s per stream against 4.7 for k_ypass, but twice the bytes per iteration */
   CA_VARX_Y_MFMA1 = 1 << 2,   /* (round 2's opt-in for what is now the default, CA_VAR_Y_MFMA1; accepted and ignored) */
   CA_VARX_FOLD_ALWAYS = 1 << 3, /* backward-sweep partials summed inside the per-gene kernel at every size (default: up to 32k cells) */
-  CA_VARX_RIDE_SEQ = 1 << 4,  /* LAB.  riding Y stream fused in sequence: every forward-sweep block also streams one unit of the count matrix,
-                                 before or after its sweep (k_fwd_cell_seq_y), instead of separate stream blocks in the same grid */
+  CA_VARX_RIDE_SEQ = 1 << 4,  /* RETIRED.  riding Y stream fused in sequence: every forward-sweep block also streamed one unit of the count matrix,
+                                 before or after its sweep, instead of separate stream blocks in the same grid */
   CA_VARX_P2P_SAME_DEVICE = 1 << 5, /* test rigs only: let ca_p2p_connect map a peer handle of the SAME process on the SAME device (refused
                                  otherwise: device-wide synchronising runtime calls of one handle would wait on the other's all-reduce) */
   CA_VARX_RUN_FWD = 1 << 6,   /* ca_run with the gated update: the forward sweep behind it is queued before the host's decision as well (its blocks return at
@@ -143,10 +141,9 @@ enum ca_variant_on {
                                  the sweep is queued while the gated update may already be waiting for the host, and a runtime call made in that window can block
                                  behind another thread that holds a runtime lock while IT waits for the GPU (two engines of one process on one device did exactly
                                  that: the update then gives up after its 10 s and ca_run returns CA_ERR_STATE).  Worth about 1 us per iteration. */
-  CA_VARX_BAL_TILES = 1 << 7, /* LAB.  balanced forward sweep of small problems (CA_VAR_FWD_BAL): a single-tile block of its own per left-over tile behind the sweep
-                                 blocks, no exchange (the stream's blocks then go to the CUs without one); default: the left-over tiles cut gene-wise into chunks
-                                 that the sweep blocks sweep beside their own tiles, partial Z exchanged through tagged words.  Level at few left-over tiles,
-                                 slower at many */
+  CA_VARX_BAL_TILES = 1 << 7, /* RETIRED.  balanced forward sweep of small problems (CA_VAR_FWD_BAL): a single-tile block of its own per left-over tile behind the
+                                 sweep blocks, no exchange, instead of the left-over tiles cut gene-wise into chunks that the sweep blocks sweep beside their own
+                                 tiles.  Level at few left-over tiles, slower at many */
   CA_VARX_SERIES = 1 << 8,    /* ABI 6: force the series form (CA_VAR_SERIES) at ANY size.  The form: where the exponent is rank one -- K + P = 1, one MC sample, 3..8
                                  clones: Z_nc = sum_g M_gc exp(x_n v_g) is one function of x per clone; genes binned by v, a 20-term expansion per bin (argument <= 2,
                                  float64): moments over genes, evaluation over cells, the same form on the way back.  No cells x genes sweep: O(N nb R C + G R C)
@@ -203,7 +200,7 @@ typedef struct ca_info {
   int32_t bwd_mfma;          /* 1: the backward sweep's t = coef.L contraction runs on the matrix cores (k_bwd_mfma) */
   int32_t fsplit;            /* gene slices of the matrix-core forward sweep */
   int32_t fwd_cell;          /* 1: forward sweep and cell epilogue of the fused pass are ONE kernel (k_fwd_cell) */
-  int32_t y_mfma;            /* the loop's count-matrix products on the int8 matrix cores: 0 no (k_ypass), 1 two tiled copies, 2 one */
+  int32_t y_mfma;            /* the loop's count-matrix products on the int8 matrix cores: 0 no (k_ypass), 2 from one tiled copy (1, two tiled copies, is no longer reported: CA_VARX_Y_MFMA2 is retired) */
   int32_t transport;         /* 0 none, 1 RCCL all-reduce, 2 host callback, 3 one-shot peer-to-peer (ca_transport) */
   int32_t y_ride;            /* 1: the Y stream's blocks ride on the fused forward sweep's launch (k_fwd_cell_mix_y): no launch of its own */
   int64_t red_n;             /* doubles all-reduced per train pass (= sharding.reduce_plan(...)["total"]) */

@@ -451,14 +451,14 @@ def test_final_elbos_from_pair_sweeps_equal_single_passes(shape):
 
 def test_variants_measured_slower_are_refused_by_the_product_library():
     """Round 6: the two-copy int8 stream (y_mfma2), the riding stream fused in sequence into the sweep's blocks (ride_seq) and the balanced sweep's
-    single-tile blocks (bal_tiles) were measured slower than what ships and live in the LAB library only (`make -C clonealign_amd/csrc lab`).  The product library
-    says so at ca_create instead of ignoring the request."""
+    single-tile blocks (bal_tiles) were measured slower than what ships; their code has been removed (the measurements are in DESIGN_HISTORY.md and profiles/).
+    The library says so at ca_create instead of ignoring the request."""
     from clonealign_amd.engine import EngineError, HipEngine
     case = make_case(seed=41, N=300, G=130, C=3, K=1)
     for v in ("y_mfma2", "ride_seq", "bal_tiles"):
         with pytest.raises(EngineError) as ei:
             HipEngine(**case, variant_on=(v,))
-        assert ei.value.code == 1 and "lab library only" in str(ei.value), (v, str(ei.value))
+        assert ei.value.code == 1 and "was removed" in str(ei.value), (v, str(ei.value))
 
 
 @pytest.mark.parametrize("variant", ["y_mfma1"])
@@ -467,7 +467,7 @@ def test_count_matrix_products_on_the_int8_matrix_cores(shape, variant):
     """Y.W and Y^T.psi of the loop on the int8 matrix cores: fixed-point parameters in four base-256 digits, exact integer accumulation, both products from
     ONE tiled copy whose column form comes out of the transposing LDS read (k_ys_mfma, "y_mfma1", K = 1; its fixed-point exponents are bounded from the previous
     state's maxima inside the loop), against the VALU stream (k_ypass) and the oracle: ragged N and G (padding tiles), counts above 255 (overflow list next to
-    the 1-byte copy), call by call and through the fused loop.  (The two-copy form of round 2, "y_mfma2", K up to 4, is in the lab library only since round 6.)"""
+    the 1-byte copy), call by call and through the fused loop.  (The two-copy form of round 2, "y_mfma2", K up to 4, has been removed.)"""
     from clonealign_amd.engine import HipEngine
     from oracle.fused_numpy import FusedModel
     case = make_case(seed=41, **shape)
@@ -547,8 +547,8 @@ def test_riding_dispatch_order_does_not_change_a_single_bit(shape):
     for stream in ("int8", "vector"):          # the default int8 matrix-core stream (y_mfma1) and the vector stream it replaced
       ref = None
       for pat in (None, "1:1", "3:2", "16:8", "1:200", "255:1", -3, -64, "mixed", "fin"):
-        # (negative: that many long-lived stream blocks lead the grid.  "mixed", vector stream only: the sequence-fused form switched off outright -- it is
-        #  in the lab library only since round 6 --, the stream as blocks of its own in the same grid, k_fwd_cell_mix_y.  "fin", int8 stream only:
+        # (negative: that many long-lived stream blocks lead the grid.  "mixed", vector stream only: the off-switch of the sequence-fused form -- a no-op since
+        #  that form was removed --, the stream as blocks of its own in the same grid, k_fwd_cell_mix_y.  "fin", int8 stream only:
         #  the stream's finishing sums as a launch of their own between the sweeps, k_yfinish, instead of extra blocks of the backward
         #  sweep -- the same additions in the same order, and the monitor pass's ELBO assembled in one stage instead of two)
         if (stream == "int8" and pat == "mixed") or (stream == "vector" and pat == "fin"):

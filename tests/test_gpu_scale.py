@@ -676,7 +676,7 @@ def test_balanced_forward_sweep_of_small_problems_matches_c_oracle_and_the_four_
     update), the pair sweeps of the final ELBOs and ca_iterate, against the float64 C oracle (trace 1e-5, parameters 1e-4, clone labels)
     and against the four-wave sweep of the same engine (variant fwd_bal off: same sums grouped differently, 2e-6).  The left-over tiles go
     through the gene-chunk exchange; the other treatment of round 5 (a single-tile block of its own per tile behind the sweep blocks, variant_on
-    bal_tiles: measured level at few left-over tiles and slower at many) is in the lab library only since round 6."""
+    bal_tiles: measured level at few left-over tiles and slower at many) has been removed."""
     from clonealign_amd.engine import HipEngine
     from clonealign_amd.inference import run_vi_loop
     from clonealign_amd.rng import EpsStream
