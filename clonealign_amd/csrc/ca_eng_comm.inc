@@ -1,4 +1,61 @@
-// ca_eng_comm.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, transports: RCCL communicator, one-shot peer-to-peer set-up (two-phase), benchmark, known-answer test, host callback.
+// ca_eng_comm.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, transports: setup sums over all ranks, RCCL communicator, one-shot peer-to-peer set-up (two-phase), benchmark, known-answer test, host callback.
+namespace {
+// the per-gene count totals are sums over ALL cells (SURVEY.md §8e): reduced once, when the transport is set
+int setup_global_sums(ca_engine* h) {
+  if (h->sums_global) return CA_OK;
+  // a transport that died between the two reductions leaves colsum reduced and YtX not: no second transport may reduce colsum again
+  if (h->sums_started) { h->err = "an earlier transport failed inside the setup reductions; this engine cannot take another one -- destroy it"; return CA_ERR_STATE; }
+  h->sums_started = true;
+  CACK(allreduce(h, h->colsum, h->G));
+  if (h->P > 0 && h->K > 0) CACK(allreduce(h, h->YtX, (int64_t)h->G * h->P));
+  SYNC(h);
+  if (!h->mu_part.empty()) {
+    // loc0 = NULL on a shard (ABI 6): mu_guess_g = mean over ALL cells of y_ng / rowMeans(Y)_n (R/inference-tflow.R:220-235) -- the ranks' partial sums and
+    // cell counts are added here, then loc0 = safe_inverse_softplus(mu_guess) (:262, :6-11) exactly as create_impl does it for one handle
+    const int G = h->G;
+    std::vector<double> pack(h->mu_part);
+    pack.push_back((double)h->N);
+    HIPCK(h, hipMemcpyAsync(h->red, pack.data(), pack.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CACK(allreduce(h, h->red, (int64_t)pack.size()));
+    HIPCK(h, hipMemcpyAsync(pack.data(), h->red, pack.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    SYNC(h);
+    std::vector<float> l0((size_t)G);
+    for (int g = 0; g < G; ++g) {
+      const double mu = pack[(size_t)g] / pack[(size_t)G];
+      l0[g] = (float)(std::log(1.0 - std::exp(-std::fabs(mu))) + std::max(mu, 0.0));
+    }
+    CACK(upload_f(h, h->loc, l0));
+    HIPCK(h, hipMemcpyAsync(h->loc_init, h->loc, (size_t)G * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    HIPCK(h, hipMemsetAsync(h->red, 0, pack.size() * sizeof(double), h->stream));
+    CACK(refresh_derived(h));
+    SYNC(h);
+    h->mu_part.clear();
+  }
+  if (h->layout_series) {   // (this function runs when a transport has come up)
+    // the ranks agree on the series form (its pick looks at the rank's own cell count): used where EVERY rank picked it; otherwise nobody uses it and everybody
+    // goes back to the classic layout of the reduction buffer -- the collectives' lengths are then the same on all ranks either way
+    double f[2] = {h->poly ? 1.0 : 0.0, 1.0};
+    HIPCK(h, hipMemcpyAsync(h->red, f, sizeof(f), hipMemcpyHostToDevice, h->stream));
+    SYNC(h);
+    CACK(allreduce(h, h->red, 2));
+    HIPCK(h, hipMemcpyAsync(f, h->red, sizeof(f), hipMemcpyDeviceToHost, h->stream));
+    SYNC(h);
+    HIPCK(h, hipMemsetAsync(h->red, 0, sizeof(f), h->stream));
+    if (f[0] != f[1]) h->poly = false;
+    if (!h->poly) {
+      h->layout_series = false;
+      h->off_g = 3 + h->C;
+      h->off_y = h->off_g + (int64_t)h->G * (h->S + h->D);
+      h->red_n = h->off_y + (int64_t)h->G * h->K;   // (the buffer is longer than this layout needs: the Gp - G padding rows of Y^T psi fit behind it)
+      h->off_q = h->off_x = 0;
+    }
+    SYNC(h);
+  }
+  h->sums_global = true;
+  return CA_OK;
+}
+}  // namespace
+
 int ca_comm_unique_id(char id[128]) {
   if (!g_rccl.load()) { g_last_error = g_rccl.err; return CA_ERR_COMM; }
   ca_nccl_uid u;

@@ -519,12 +519,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
       dim3 grid((unsigned)((int64_t)h->nrg * h->nseg));
       ca_ovf_args no_ovf;
       memset(&no_ovf, 0, sizeof(no_ovf));
-      if (h->ystore == CA_YSTORE_U8)
-        hipLaunchKernelGGL((k_ypass<uint8_t, 1>), grid, dim3(CA_TB), 0, h->stream, (const uint8_t*)h->Y, Ft, 1, Vt, 0, YWp, YTp, Nn, G, h->Gp, h->nseg, h->nrb, h->TR, 1, no_ovf, (int)grid.x);
-      else if (h->ystore == CA_YSTORE_U16)
-        hipLaunchKernelGGL((k_ypass<uint16_t, 1>), grid, dim3(CA_TB), 0, h->stream, (const uint16_t*)h->Y, Ft, 1, Vt, 0, YWp, YTp, Nn, G, h->Gp, h->nseg, h->nrb, h->TR, 1, no_ovf, (int)grid.x);
-      else
-        hipLaunchKernelGGL((k_ypass<float, 1>), grid, dim3(CA_TB), 0, h->stream, (const float*)h->Y, Ft, 1, Vt, 0, YWp, YTp, Nn, G, h->Gp, h->nseg, h->nrb, h->TR, 1, no_ovf, (int)grid.x);
+      ypass<0>(h, ca_ypass_ops{Ft, 1, Vt, YWp, YTp, 1}, 0, 1, grid, no_ovf);
       HIPCK(h, hipGetLastError());
       hipLaunchKernelGGL(k_colsum, dim3(cdiv(h->Gp, 64)), dim3(1024), 0, h->stream, YTp, yt, h->nrg, (int64_t)h->Gp, h->Gp);
       std::vector<double> tmp((size_t)G);

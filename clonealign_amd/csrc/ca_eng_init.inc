@@ -1,4 +1,89 @@
-// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (blocked subspace iteration), per-clone gene sums.
+// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums.
+extern "C++" {   // (templates: this part sits inside the C ABI's extern "C" block)
+namespace {
+// Transformed pass over Y with explicit factor buffers (PCA init): row products Y'.Vp -> YWp, column products Y'^T.Fp -> YTp
+template <int TF>
+int ypass_tf(ca_engine* h, const float* Fp, const float* Vp, int q, float* YWp, float* YTp, float* csum) {
+  dim3 grid((unsigned)((int64_t)h->nrg * h->nseg));
+  const ca_ypass_ops ops = {Fp, q, Vp, YWp, YTp, q};
+  ca_ovf_args no_ovf;   // (the overflow list: the three launches below)
+  memset(&no_ovf, 0, sizeof(no_ovf));
+  for (int koff = 0; koff < q; koff += 4) {
+    const int kk = std::min(4, q - koff);
+    ypass<TF>(h, ops, koff, kk, grid, no_ovf);
+    HIPCK(h, hipGetLastError());
+  }
+  if (h->n_ovf > 0) {
+    hipLaunchKernelGGL(k_ovf_rows, dim3(cdiv(h->N, CA_TB)), dim3(CA_TB), 0, h->stream, h->ovf_rowptr, h->ovf_col, h->ovf_val, Vp, q,
+                       YWp + (int64_t)h->nseg * h->N * q, h->N, q, TF);
+    hipLaunchKernelGGL(k_ovf_chunks, dim3(cdiv(h->n_ovf_chunk, CA_TB / 64)), dim3(CA_TB), 0, h->stream, h->ovf_chunk_start, h->ovf_row2,
+                       h->ovf_val2, Fp, q, csum, h->n_ovf_chunk, q, TF);
+    hipLaunchKernelGGL(k_ovf_cols, dim3(cdiv(h->Gp, CA_TB)), dim3(CA_TB), 0, h->stream, h->ovf_col_chunk_ptr, csum,
+                       YTp + (int64_t)h->nrg * h->Gp * q, h->Gp, h->G, q);
+    HIPCK(h, hipGetLastError());
+  }
+  return CA_OK;
+}
+
+// modified Gram-Schmidt (twice) on the columns of Q [G][q] (row-major), double precision
+void orthonormalize(std::vector<double>& Q, int G, int q) {
+  for (int rep = 0; rep < 2; ++rep)
+    for (int k = 0; k < q; ++k) {
+      for (int j = 0; j < k; ++j) {
+        double d = 0.0;
+        for (int g = 0; g < G; ++g) d += Q[(size_t)g * q + k] * Q[(size_t)g * q + j];
+        for (int g = 0; g < G; ++g) Q[(size_t)g * q + k] -= d * Q[(size_t)g * q + j];
+      }
+      double nn = 0.0;
+      for (int g = 0; g < G; ++g) nn += Q[(size_t)g * q + k] * Q[(size_t)g * q + k];
+      nn = std::sqrt(nn);
+      if (nn < 1e-300) nn = 1.0;
+      for (int g = 0; g < G; ++g) Q[(size_t)g * q + k] /= nn;
+    }
+}
+// cyclic Jacobi eigen-decomposition of a symmetric q x q matrix; eigenvalues descending, eigenvectors in columns of W
+void sym_eig(std::vector<double> T, int q, std::vector<double>& lam, std::vector<double>& W) {
+  W.assign((size_t)q * q, 0.0);
+  for (int i = 0; i < q; ++i) W[(size_t)i * q + i] = 1.0;
+  for (int sweep = 0; sweep < 60; ++sweep) {
+    double off = 0.0;
+    for (int i = 0; i < q; ++i) for (int j = i + 1; j < q; ++j) off += T[(size_t)i * q + j] * T[(size_t)i * q + j];
+    if (off < 1e-30) break;
+    for (int p_ = 0; p_ < q; ++p_)
+      for (int r = p_ + 1; r < q; ++r) {
+        const double apr = T[(size_t)p_ * q + r];
+        if (std::fabs(apr) < 1e-300) continue;
+        const double th = (T[(size_t)r * q + r] - T[(size_t)p_ * q + p_]) / (2.0 * apr);
+        const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < q; ++k) {
+          const double a = T[(size_t)k * q + p_], b = T[(size_t)k * q + r];
+          T[(size_t)k * q + p_] = c * a - sn * b; T[(size_t)k * q + r] = sn * a + c * b;
+        }
+        for (int k = 0; k < q; ++k) {
+          const double a = T[(size_t)p_ * q + k], b = T[(size_t)r * q + k];
+          T[(size_t)p_ * q + k] = c * a - sn * b; T[(size_t)r * q + k] = sn * a + c * b;
+        }
+        for (int k = 0; k < q; ++k) {
+          const double a = W[(size_t)k * q + p_], b = W[(size_t)k * q + r];
+          W[(size_t)k * q + p_] = c * a - sn * b; W[(size_t)k * q + r] = sn * a + c * b;
+        }
+      }
+  }
+  std::vector<int> idx(q);
+  for (int i = 0; i < q; ++i) idx[i] = i;
+  std::sort(idx.begin(), idx.end(), [&](int a, int b) { return T[(size_t)a * q + a] > T[(size_t)b * q + b]; });
+  lam.resize(q);
+  std::vector<double> W2((size_t)q * q);
+  for (int j = 0; j < q; ++j) {
+    lam[j] = T[(size_t)idx[j] * q + idx[j]];
+    for (int k = 0; k < q; ++k) W2[(size_t)k * q + j] = W[(size_t)k * q + idx[j]];
+  }
+  W = W2;
+}
+}  // namespace
+}  // extern "C++"
+
 // host-side all-reduce of a small double vector through the engine's transport (device scratch round trip)
 static int allreduce_host_vec(ca_engine* h, std::vector<double>& v, double* dev_scratch) {
   if (!is_sharded(h)) return CA_OK;

@@ -1,0 +1,252 @@
+// ca_eng_launch.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): one launch site per templated kernel family of the loop (matrix-core sweeps, fused forward sweeps and their riding streams, cell epilogues): the argument list once, the instantiation picked from the engine's picks.
+//
+// Each family: `..._t<...>` holds the family's one hipLaunchKernelGGL; `launch_...` maps the engine's picks to an instantiation.  The dispatch names exactly the
+// combinations that exist (a cross product would add kernels, minutes of compile time and megabytes of code object); a pick that ca_eng_create.inc never makes
+// falls to the last branch of its level.
+inline ca_small_args no_small_args() { ca_small_args a; memset(&a, 0, sizeof(a)); return a; }
+
+// calls f with the exponent dimension as a constant: 1 .. DMAX, any other D as DMAX
+template <int DMAX, typename Fn>
+int with_d(int D, Fn&& f) {
+  static_assert(DMAX == 2 || DMAX == 4, "");
+  if (D == 1) return f(std::integral_constant<int, 1>());
+  if constexpr (DMAX == 2) return f(std::integral_constant<int, 2>());
+  else {
+    if (D == 2) return f(std::integral_constant<int, 2>());
+    if (D == 3) return f(std::integral_constant<int, 3>());
+    return f(std::integral_constant<int, 4>());
+  }
+}
+
+// ---- k_bwd_mfma<TL, D, FRAC, C16, S2>: the matrix-core backward sweep ------------------------
+// what rides on a sweep's first launch as extra block rows behind the sweep's own: a pending monitor pass's tail, the count-matrix stream's finishing sums
+struct ca_bwdm_extra { ca_small_args tail; ca_yfin_args yfin; int rows; };
+// one launch of the sweep: a sample (or both, S2), or a sample and a pair of clone chunks
+struct ca_bwdm_ops {
+  const unsigned short* coefq; const float* Lb; const float* mu; int sidx, first_s;
+  const ca_bwdm_extra* extra;      // non-null: this launch is the sweep's first and carries the extra block rows
+  const unsigned short* coefq1;    // C16 / S2: the third-part image of coef
+  const float* mu1;                // S2: the second sample's mu
+  bool frac, c16, s2, tl3;         // the form: two-part copy numbers, sixteen clones, both samples in one sweep, three gene tiles per wave
+};
+template <int TL, int DD, bool FRAC, bool C16, bool S2>
+int bwd_mfma_t(ca_engine* h, const ca_bwdm_ops& o) {
+  ca_yfin_args no_yfin;
+  memset(&no_yfin, 0, sizeof(no_yfin));
+  LAUNCH(h, CA_KERNEL_BWD,
+         hipLaunchKernelGGL((k_bwd_mfma<TL, DD, FRAC, C16, S2>), dim3(cdiv(h->nwt, CA_TB / 64), h->csplit_m + (o.extra ? o.extra->rows : 0)), dim3(CA_TB),
+                            (size_t)h->cchunk_m * 4 * DD * sizeof(float) * (S2 ? 2 : 1), h->stream, o.coefq, h->F, h->etamax2, o.Lb, o.mu, h->Vs, h->V, h->gpart,
+                            h->dFpart, h->N, h->G, h->cchunk_m, h->S, o.sidx, o.first_s, o.extra ? 1 : 0, o.extra ? o.extra->tail : no_small_args(), h->csplit_m,
+                            o.extra ? o.extra->yfin : no_yfin, o.coefq1, o.mu1));
+  return CA_OK;
+}
+// D = 1, 2: CA_BWD_TL tiles per wave in every form, three in the plain form of small problems; D = 3, 4: the three-tile wave (CA_BWD_TL_D34), plain or two-part
+int launch_bwd_mfma(ca_engine* h, int D, const ca_bwdm_ops& o) {
+  return with_d<4>(D, [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    if constexpr (DD <= 2) {
+      if (o.c16) return bwd_mfma_t<CA_BWD_TL, DD, false, true, false>(h, o);
+      if (o.s2) return o.frac ? bwd_mfma_t<CA_BWD_TL, DD, true, false, true>(h, o) : bwd_mfma_t<CA_BWD_TL, DD, false, false, true>(h, o);
+      if (o.frac) return bwd_mfma_t<CA_BWD_TL, DD, true, false, false>(h, o);
+      if (o.tl3) return bwd_mfma_t<3, DD, false, false, false>(h, o);
+      return bwd_mfma_t<CA_BWD_TL, DD, false, false, false>(h, o);
+    } else {
+      return o.frac ? bwd_mfma_t<CA_BWD_TL_D34, DD, true, false, false>(h, o) : bwd_mfma_t<CA_BWD_TL_D34, DD, false, false, false>(h, o);
+    }
+  });
+}
+
+// ---- k_fwd_mfma<D>: the matrix-core forward sweep into Z partials (D = 1, 2) -----------------
+int launch_fwd_mfma(ca_engine* h, const unsigned short* Mq, float* Zp, int split, int kchunk) {
+  const dim3 grid(cdiv(h->N, (CA_TB / 64) * CA_FM_TL * 16), split);
+  return with_d<2>(h->D, [&](auto d) -> int {
+    LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_mfma<decltype(d)::value>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, Mq, Zp, h->N, h->G, kchunk, h->nk32));
+    return CA_OK;
+  });
+}
+
+// ---- k_fwd_cell<D, TL, C16, S2F> / k_fwd_cell_mix<D, TL, 2, C16, S2F>: sweep + cell epilogue in one kernel: no Z partials, one launch ------
+template <int D, int TL, bool C16, bool S2F>
+int fwd_cell_t(ca_engine* h, const ca_cell_ptrs& cp) {
+  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell<D, TL, C16, S2F>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, cp,
+                                              h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32));
+  return CA_OK;
+}
+template <int D, int TL, bool C16, bool S2F>
+int fwd_cell_mix_t(ca_engine* h, const ca_cell_ptrs& cp) {
+  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix<D, TL, 2, C16, S2F>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, cp,
+                                              h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig));
+  return CA_OK;
+}
+// one block shape (fc_nbig = 0) or two (k_fwd_cell_mix); TL 2 and 6 exist for D = 1 .. 4, every other TL for D = 1, 2
+template <int TL, int DMAX, bool MIX>
+int fwd_cell_tl(ca_engine* h, const ca_cell_ptrs& cp) {
+  return with_d<DMAX>(h->D, [&](auto d) {
+    if constexpr (MIX) return fwd_cell_mix_t<decltype(d)::value, TL, false, false>(h, cp);
+    else return fwd_cell_t<decltype(d)::value, TL, false, false>(h, cp);
+  });
+}
+// 9..16 clones (C16) and mc_samples = 2 with four draws (S2F): the two default block shapes, D = 1, 2
+template <bool C16, bool S2F>
+int fwd_cell_wide(ca_engine* h, const ca_cell_ptrs& cp) {
+  return with_d<2>(h->D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (h->fc_nbig > 0) return fwd_cell_mix_t<D, 6, C16, S2F>(h, cp);
+    return h->fc_tl == 6 ? fwd_cell_t<D, 6, C16, S2F>(h, cp) : fwd_cell_t<D, 2, C16, S2F>(h, cp);
+  });
+}
+int launch_fwd_cell(ca_engine* h, const ca_cell_ptrs& cp, bool s2f) {
+  if (h->c16) return fwd_cell_wide<true, false>(h, cp);
+  if (s2f) return fwd_cell_wide<false, true>(h, cp);
+  if (h->fc_nbig > 0)
+    switch (h->fc_tl) {
+      case 4: return fwd_cell_tl<4, 2, true>(h, cp);
+      case 5: return fwd_cell_tl<5, 2, true>(h, cp);
+      case 8: return fwd_cell_tl<8, 2, true>(h, cp);
+      default: return fwd_cell_tl<6, 4, true>(h, cp);   // (D = 3, 4: this shape and the 32-cell one only)
+    }
+  switch (h->fc_tl) {
+    case 1: return fwd_cell_tl<1, 2, false>(h, cp);
+    case 2: return fwd_cell_tl<2, 4, false>(h, cp);
+    case 4: return fwd_cell_tl<4, 2, false>(h, cp);
+    case 5: return fwd_cell_tl<5, 2, false>(h, cp);
+    case 6: return fwd_cell_tl<6, 4, false>(h, cp);
+    default: return fwd_cell_tl<8, 2, false>(h, cp);
+  }
+}
+
+// ---- the count-matrix stream riding on the fused forward sweep's launch ----------------------
+// Block order of a launch the count-matrix stream rides on (ca_yride_args / ca_ysride_args: nb_main stream units, nb_y with the overflow list's blocks; nf
+// sweep blocks); returns the grid's block count.
+// Interleave of the two kinds in dispatch order.  Blocks go round-robin over the 8 XCDs, so a period that divides 8 (the
+// obvious even / odd split) puts ALL sweep blocks on four XCDs and all stream blocks on the other four; two sweep blocks per
+// stream block mixes them on every CU: cfg-3 2795 -> 3008 it/s, 12.5k cells 10.9k -> 12.1k, cfg-2 16.3k -> 17.9k
+// (profiles/r02_ab_ystream.txt section 8).
+// Long-lived stream blocks lead the grid (ca_yride_args::pers) when there are at least two units of the matrix per CU: one
+// such block per CU measured best (cfg-3, with the non-temporal stream: 2:1 interleave 3090, 256 blocks 3147, 341 / 512
+// blocks 3008 / 2979, 192 / 128 blocks 2790 / 2320 it/s).  ca_options.ride_pattern < 0 sets the number, > 0 asks for the interleave (a << 8 | b).
+template <typename RideArgs>
+unsigned ride_pattern(const ca_engine* h, RideArgs& ya, int nf) {
+  const int rp = h->opt.ride_pattern;
+  ya.pat_a = 2; ya.pat_b = 1;
+  if (rp > 0 && (rp >> 8) > 0 && (rp & 255) > 0) { ya.pat_a = rp >> 8; ya.pat_b = rp & 255; }
+  if (rp < 0) ya.pers = std::min(-rp, ya.nb_main);
+  else if (rp == 0 && ya.nb_main >= 2 * h->n_cu) ya.pers = h->n_cu;
+  return ya.pers > 0 ? (unsigned)(ya.pers + nf + (ya.nb_y - ya.nb_main)) : (unsigned)(nf + ya.nb_y);
+}
+
+// k_fwd_cell_mix_y<D, TLB, 2>: the vector stream's blocks interleaved with the sweep's (D = 1, 2; 128-, 96- or 32-cell big blocks)
+template <int D, int TLB>
+int fwd_cell_mix_y_t(ca_engine* h, const ca_cell_ptrs& cp, ca_yride_args& ya) {
+  const dim3 grid(ride_pattern(h, ya, h->ncblk_f));
+  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_y<D, TLB, 2>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, cp, h->alpha_u,
+                                              h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya));
+  return CA_OK;
+}
+int launch_fwd_cell_mix_y(ca_engine* h, const ca_cell_ptrs& cp, ca_yride_args& ya) {
+  return with_d<2>(h->D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if (h->fc_tl == 8) return fwd_cell_mix_y_t<D, 8>(h, cp, ya);
+    if (h->fc_tl == 6) return fwd_cell_mix_y_t<D, 6>(h, cp, ya);
+    return fwd_cell_mix_y_t<D, 2>(h, cp, ya);
+  });
+}
+
+// (one piece in flight per wave: 128 VGPRs = four waves per SIMD like the vector stream's launch; two pieces, 162 VGPRs and
+//  three waves, measured 2824 against 2869 it/s at cfg-3 -- profiles/r03_ab_ystream.txt)
+#ifndef CA_YS_RIDE_DEPTH
+#define CA_YS_RIDE_DEPTH 1   // (lab: pieces in flight per stream wave)
+#endif
+// k_fwd_cell_mix_ys<D, TLB, 2, DEPTH, C16, S2F, Y4>: the one-copy int8 matrix-core stream's blocks interleaved with the sweep's
+template <int D, int TLB, bool C16, bool S2F, bool Y4>
+int fwd_cell_mix_ys_t(ca_engine* h, const ca_cell_ptrs& cp, ca_ysride_args& ya) {
+  const dim3 grid(ride_pattern(h, ya, h->ncblk_f));
+  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_ys<D, TLB, 2, CA_YS_RIDE_DEPTH, C16, S2F, Y4>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs,
+                                              h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya));
+  return CA_OK;
+}
+// (the 4-bit image rides only with the series form's shapes: D = 1, no c16 / s2 -- ride_ys, ca_eng_create.inc)
+template <int D, int TLB, bool C16, bool S2F>
+int fwd_cell_mix_ys_y4(ca_engine* h, const ca_cell_ptrs& cp, ca_ysride_args& ya) {
+  if constexpr (D == 1 && !C16 && !S2F) { if (h->ys4) return fwd_cell_mix_ys_t<D, TLB, C16, S2F, true>(h, cp, ya); }
+  return fwd_cell_mix_ys_t<D, TLB, C16, S2F, false>(h, cp, ya);
+}
+// 96- and 32-cell big blocks: D = 1, 2 in the plain, the sixteen-clone and the four-draw form; 16-cell ones: the plain form only
+template <int TLB>
+int fwd_cell_mix_ys_tl(ca_engine* h, const ca_cell_ptrs& cp, ca_ysride_args& ya, bool c16, bool s2f) {
+  return with_d<2>(h->D, [&](auto d) {
+    constexpr int D = decltype(d)::value;
+    if constexpr (TLB != 1) {
+      if (c16) return fwd_cell_mix_ys_y4<D, TLB, true, false>(h, cp, ya);
+      if (s2f) return fwd_cell_mix_ys_y4<D, TLB, false, true>(h, cp, ya);
+    }
+    return fwd_cell_mix_ys_y4<D, TLB, false, false>(h, cp, ya);
+  });
+}
+int launch_fwd_cell_mix_ys(ca_engine* h, const ca_cell_ptrs& cp, ca_ysride_args& ya, bool s2f) {
+  if (h->fc_tl == 6) return fwd_cell_mix_ys_tl<6>(h, cp, ya, h->c16, s2f);
+  if (h->fc_tl == 1 && !h->c16) return fwd_cell_mix_ys_tl<1>(h, cp, ya, false, false);
+  return fwd_cell_mix_ys_tl<2>(h, cp, ya, h->c16, s2f);
+}
+
+// k_fwd_bal_ys<1, TL, DEPTH, Y4>: small problems, one eight-wave sweep block per CU with bal_q = TL tiles each, left-over tiles spread gene-wise (ca_fwdbal.hip.h);
+// the grid: sweep blocks, stream blocks (ba.stream_units units each), the overflow list's (its own block order: ya's interleave fields stay unset)
+template <int TL, bool Y4>
+int fwd_bal_ys_t(ca_engine* h, const ca_cell_ptrs& cp, const ca_bal_args& ba, const ca_ysride_args& ya) {
+  const dim3 grid((unsigned)(h->n_cu + (ba.stream_units == 2 ? (ya.nb_main + 1) / 2 : ya.nb_main) + (ya.nb_y - ya.nb_main)));
+  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_bal_ys<1, TL, CA_YS_RIDE_DEPTH, Y4>), grid, dim3(CA_BAL_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, cp,
+                                              h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, ba, ya));
+  return CA_OK;
+}
+template <int TL>
+int fwd_bal_ys_y4(ca_engine* h, const ca_cell_ptrs& cp, const ca_bal_args& ba, const ca_ysride_args& ya) {
+  return h->ys4 ? fwd_bal_ys_t<TL, true>(h, cp, ba, ya) : fwd_bal_ys_t<TL, false>(h, cp, ba, ya);
+}
+int launch_fwd_bal_ys(ca_engine* h, const ca_cell_ptrs& cp, const ca_bal_args& ba, const ca_ysride_args& ya) {
+  switch (h->bal_q) {
+    case 1: return fwd_bal_ys_y4<1>(h, cp, ba, ya);
+    case 2: return fwd_bal_ys_y4<2>(h, cp, ba, ya);
+    case 3: return fwd_bal_ys_y4<3>(h, cp, ba, ya);
+    case 4: return fwd_bal_ys_y4<4>(h, cp, ba, ya);
+    case 5: return fwd_bal_ys_y4<5>(h, cp, ba, ya);
+    default: return fwd_bal_ys_y4<6>(h, cp, ba, ya);
+  }
+}
+
+// ---- cell epilogues over Z partials: CP = the clone count rounded up to a power of two lanes per cell ------
+// k_cell_par<CP> (plain pass, up to 64 clones): Z partials of the vector sweeps, or of the paired matrix-core sweeps (pfwd)
+template <int CP>
+int cell_par_t(ca_engine* h, const float* ywp, int ywseg, int mode) {
+  LAUNCH(h, CA_KERNEL_CELL,
+         hipLaunchKernelGGL((k_cell_par<CP>), dim3(h->ncblk), dim3(CA_TB), 0, h->stream, h->pfwd ? h->pf_Z : h->Zpart, h->A, h->cn, h->s64, h->etamax2, h->glogit,
+                            h->alpha_u, h->F, ywp, h->YW, h->coef, h->dgl, h->cell_part, h->N, h->C, h->S, h->D, h->K, h->pfwd ? h->pf_fsplit : h->gsplit,
+                            h->nchunk, ywseg, mode, h->bwd_mfma ? h->coefq : nullptr, h->N16, h->pfwd ? 1 : 0, (int64_t)h->S * cdiv(h->nchunk, 2) * h->N16 * 32));
+  return CA_OK;
+}
+inline int clone_lanes(const ca_engine* h) { int CP = 1; while (CP < h->C) CP <<= 1; return CP; }
+int launch_cell_par(ca_engine* h, const float* ywp, int ywseg, int mode) {
+  switch (clone_lanes(h)) {
+    case 1: return cell_par_t<1>(h, ywp, ywseg, mode);
+    case 2: return cell_par_t<2>(h, ywp, ywseg, mode);
+    case 4: return cell_par_t<4>(h, ywp, ywseg, mode);
+    case 8: return cell_par_t<8>(h, ywp, ywseg, mode);
+    case 16: return cell_par_t<16>(h, ywp, ywseg, mode);
+    case 32: return cell_par_t<32>(h, ywp, ywseg, mode);
+    default: return cell_par_t<64>(h, ywp, ywseg, mode);
+  }
+}
+// k_cell_fused<CP> (fused two-draw pass over Zpart2, up to 8 clones)
+template <int CP>
+int cell_fused_t(ca_engine* h, const ca_cell_ptrs& cp) {
+  LAUNCH(h, CA_KERNEL_CELL, hipLaunchKernelGGL((k_cell_fused<CP>), dim3(h->ncblk), dim3(CA_TB), 0, h->stream, h->Zpart2, h->frow, cp, h->alpha_u, h->cell_part, h->N,
+                                               h->C, h->D, h->K, h->fwd_mfma ? h->fsplit : h->gsplit));
+  return CA_OK;
+}
+int launch_cell_fused(ca_engine* h, const ca_cell_ptrs& cp) {
+  switch (clone_lanes(h)) {
+    case 1: return cell_fused_t<1>(h, cp);
+    case 2: return cell_fused_t<2>(h, cp);
+    case 4: return cell_fused_t<4>(h, cp);
+    default: return cell_fused_t<8>(h, cp);
+  }
+}

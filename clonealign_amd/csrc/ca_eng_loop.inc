@@ -1,30 +1,4 @@
-// ca_eng_loop.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): the loop: host matrix helpers, count-matrix products per parameter state, transports' all-reduce, backward / update halves, plain and fused passes (sweeps or series form), eps staging.
-// ---- host matrix helpers ------------------------------------------------------------------
-// element (r, c) of an R x Cn host matrix in the problem's layout
-inline int64_t hidx(int layout, int64_t r, int64_t c, int64_t R, int64_t Cn) {
-  return layout == CA_COL_MAJOR ? c * R + r : r * Cn + c;
-}
-
-int upload_f(ca_engine* h, float* dst, const std::vector<float>& v) {
-  if (v.empty()) return CA_OK;
-  HIPCK(h, hipMemcpyAsync(dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  SYNC(h);
-  return CA_OK;
-}
-int upload_d(ca_engine* h, double* dst, const std::vector<double>& v) {
-  if (v.empty()) return CA_OK;
-  HIPCK(h, hipMemcpyAsync(dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  SYNC(h);
-  return CA_OK;
-}
-int download_f(ca_engine* h, std::vector<float>& v, const float* src, int64_t n) {
-  v.resize((size_t)n);
-  if (n == 0) return CA_OK;
-  HIPCK(h, hipMemcpyAsync(v.data(), src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-  SYNC(h);
-  return CA_OK;
-}
-
+// ca_eng_loop.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): the loop: count-matrix products per parameter state, backward / update halves, plain and fused passes (sweeps or series form), the host's waits, eps staging.
 // The side stream's products: the row products (YW, psi.(YW) partials) are done at ev_ywdone, everything (also Y^T psi)
 // at ev_ydone.  all = false waits for the row products only (the backward sweep's ELBO tail needs nothing else).
 int wait_y(ca_engine* h, bool all) {
@@ -40,14 +14,17 @@ int wait_y(ca_engine* h, bool all) {
 
 // After a merged update (k_update_merged) the per-cell exponent bound of the stepped state has not been made: the fused forward sweep's
 // blocks make it themselves (ca_cell_ptrs::vmm_part); every OTHER consumer of etamax2 calls this first (the two small kernels of setup).
-int ensure_etamax(ca_engine* h) {
-  if (!h->em_stale) return CA_OK;
+int make_etamax(ca_engine* h) {   // (from the block ranges of V' in vmm_part)
   if (h->D > 0) {
     LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_vmm_final, dim3(1), dim3(64), 0, h->stream, h->vmm_part, h->vmm, h->ngblk, h->D));
     LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_etamax, dim3(cdiv(h->N, CA_TB)), dim3(CA_TB), 0, h->stream, h->F, h->vmm, h->etamax2, h->N, h->D));
   }
   h->em_stale = false;
   return CA_OK;
+}
+int ensure_etamax(ca_engine* h) {
+  if (!h->em_stale) return CA_OK;
+  return make_etamax(h);
 }
 
 // ---- derived state that depends on the parameters only (not on eps) -------------------------
@@ -57,12 +34,8 @@ int refresh_derived(ca_engine* h) {
   h->pre_valid = false;
   h->ys_steps = -1;     // arbitrary parameter change: the fixed-point exponents are taken from exact maxima again
   h->ys_quant_ready = false;
-  if (h->D > 0) {
-    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_vprep, dim3(h->ngblk), dim3(CA_TB), 0, h->stream, h->V, h->Vs, h->vmm_part, h->G, h->D));
-    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_vmm_final, dim3(1), dim3(64), 0, h->stream, h->vmm_part, h->vmm, h->ngblk, h->D));
-    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_etamax, dim3(cdiv(h->N, CA_TB)), dim3(CA_TB), 0, h->stream, h->F, h->vmm, h->etamax2, h->N, h->D));
-  }
-  h->em_stale = false;
+  if (h->D > 0) LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_vprep, dim3(h->ngblk), dim3(CA_TB), 0, h->stream, h->V, h->Vs, h->vmm_part, h->G, h->D));
+  CACK(make_etamax(h));
   h->gaux_slot = -1;
   h->ycache_valid = false;
   h->yfin_pending = false;
@@ -216,13 +189,12 @@ int ensure_ycache(ca_engine* h) {
   const ca_ovf_args ovf = ovf_args(h, h->YWpart + (int64_t)h->nseg * h->N * h->K);
   ca_ovf_args none;
   memset(&none, 0, sizeof(none));
+  const ca_ypass_ops fit = {h->F, h->D, h->V, h->YWpart, h->YTpart, h->K};
   for (int koff = 0; koff < h->K; koff += 4) {
     const int kk = std::min(4, h->K - koff);
     CACK(prof_begin(h, CA_KERNEL_YPASS));
     const ca_ovf_args& o = koff == 0 ? ovf : none;
-    if (h->ystore == CA_YSTORE_U8) ypass_t<uint8_t>(h, koff, kk, grid, o);
-    else if (h->ystore == CA_YSTORE_U16) ypass_t<uint16_t>(h, koff, kk, grid, o);
-    else ypass_t<float>(h, koff, kk, grid, o);
+    ypass<0>(h, fit, koff, kk, grid, o);
     HIPCK(h, hipGetLastError());
     CACK(prof_end(h));
   }
@@ -241,204 +213,6 @@ int ensure_ycache(ca_engine* h) {
                                                   h->nseg + (h->n_ovf > 0 ? 1 : 0), h->F, h->D, h->K, h->N, h->YW, h->yw_part));
   }
   h->ycache_valid = true;
-  return CA_OK;
-}
-
-// Transformed pass over Y with explicit factor buffers (PCA init): row products Y'.Vp -> YWp, column products Y'^T.Fp -> YTp
-template <typename YT, int TF>
-void ypass_tf_t(ca_engine* h, const float* Fp, const float* Vp, int q, int koff, int kk, float* YWp, float* YTp, dim3 grid) {
-  const YT* Y = (const YT*)h->Y;
-  ca_ovf_args no_ovf;
-  memset(&no_ovf, 0, sizeof(no_ovf));
-#define CA_YPT(KK)                                                                                                    \
-  hipLaunchKernelGGL((k_ypass<YT, KK, TF>), grid, dim3(CA_TB), 0, h->stream, Y, Fp, q, Vp, koff, YWp, YTp, h->N, h->G, \
-                     h->Gp, h->nseg, h->nrb, h->TR, q, no_ovf, (int)grid.x)
-  switch (kk) {
-    case 1: CA_YPT(1); break;
-    case 2: CA_YPT(2); break;
-    case 3: CA_YPT(3); break;
-    default: CA_YPT(4); break;
-  }
-#undef CA_YPT
-}
-template <int TF>
-int ypass_tf(ca_engine* h, const float* Fp, const float* Vp, int q, float* YWp, float* YTp, float* csum) {
-  dim3 grid((unsigned)((int64_t)h->nrg * h->nseg));
-  for (int koff = 0; koff < q; koff += 4) {
-    const int kk = std::min(4, q - koff);
-    if (h->ystore == CA_YSTORE_U8) ypass_tf_t<uint8_t, TF>(h, Fp, Vp, q, koff, kk, YWp, YTp, grid);
-    else if (h->ystore == CA_YSTORE_U16) ypass_tf_t<uint16_t, TF>(h, Fp, Vp, q, koff, kk, YWp, YTp, grid);
-    else ypass_tf_t<float, TF>(h, Fp, Vp, q, koff, kk, YWp, YTp, grid);
-    HIPCK(h, hipGetLastError());
-  }
-  if (h->n_ovf > 0) {
-    hipLaunchKernelGGL(k_ovf_rows, dim3(cdiv(h->N, CA_TB)), dim3(CA_TB), 0, h->stream, h->ovf_rowptr, h->ovf_col, h->ovf_val, Vp, q,
-                       YWp + (int64_t)h->nseg * h->N * q, h->N, q, TF);
-    hipLaunchKernelGGL(k_ovf_chunks, dim3(cdiv(h->n_ovf_chunk, CA_TB / 64)), dim3(CA_TB), 0, h->stream, h->ovf_chunk_start, h->ovf_row2,
-                       h->ovf_val2, Fp, q, csum, h->n_ovf_chunk, q, TF);
-    hipLaunchKernelGGL(k_ovf_cols, dim3(cdiv(h->Gp, CA_TB)), dim3(CA_TB), 0, h->stream, h->ovf_col_chunk_ptr, csum,
-                       YTp + (int64_t)h->nrg * h->Gp * q, h->Gp, h->G, q);
-    HIPCK(h, hipGetLastError());
-  }
-  return CA_OK;
-}
-
-// modified Gram-Schmidt (twice) on the columns of Q [G][q] (row-major), double precision
-void orthonormalize(std::vector<double>& Q, int G, int q) {
-  for (int rep = 0; rep < 2; ++rep)
-    for (int k = 0; k < q; ++k) {
-      for (int j = 0; j < k; ++j) {
-        double d = 0.0;
-        for (int g = 0; g < G; ++g) d += Q[(size_t)g * q + k] * Q[(size_t)g * q + j];
-        for (int g = 0; g < G; ++g) Q[(size_t)g * q + k] -= d * Q[(size_t)g * q + j];
-      }
-      double nn = 0.0;
-      for (int g = 0; g < G; ++g) nn += Q[(size_t)g * q + k] * Q[(size_t)g * q + k];
-      nn = std::sqrt(nn);
-      if (nn < 1e-300) nn = 1.0;
-      for (int g = 0; g < G; ++g) Q[(size_t)g * q + k] /= nn;
-    }
-}
-// cyclic Jacobi eigen-decomposition of a symmetric q x q matrix; eigenvalues descending, eigenvectors in columns of W
-void sym_eig(std::vector<double> T, int q, std::vector<double>& lam, std::vector<double>& W) {
-  W.assign((size_t)q * q, 0.0);
-  for (int i = 0; i < q; ++i) W[(size_t)i * q + i] = 1.0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0.0;
-    for (int i = 0; i < q; ++i) for (int j = i + 1; j < q; ++j) off += T[(size_t)i * q + j] * T[(size_t)i * q + j];
-    if (off < 1e-30) break;
-    for (int p_ = 0; p_ < q; ++p_)
-      for (int r = p_ + 1; r < q; ++r) {
-        const double apr = T[(size_t)p_ * q + r];
-        if (std::fabs(apr) < 1e-300) continue;
-        const double th = (T[(size_t)r * q + r] - T[(size_t)p_ * q + p_]) / (2.0 * apr);
-        const double t = (th >= 0 ? 1.0 : -1.0) / (std::fabs(th) + std::sqrt(th * th + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-        for (int k = 0; k < q; ++k) {
-          const double a = T[(size_t)k * q + p_], b = T[(size_t)k * q + r];
-          T[(size_t)k * q + p_] = c * a - sn * b; T[(size_t)k * q + r] = sn * a + c * b;
-        }
-        for (int k = 0; k < q; ++k) {
-          const double a = T[(size_t)p_ * q + k], b = T[(size_t)r * q + k];
-          T[(size_t)p_ * q + k] = c * a - sn * b; T[(size_t)r * q + k] = sn * a + c * b;
-        }
-        for (int k = 0; k < q; ++k) {
-          const double a = W[(size_t)k * q + p_], b = W[(size_t)k * q + r];
-          W[(size_t)k * q + p_] = c * a - sn * b; W[(size_t)k * q + r] = sn * a + c * b;
-        }
-      }
-  }
-  std::vector<int> idx(q);
-  for (int i = 0; i < q; ++i) idx[i] = i;
-  std::sort(idx.begin(), idx.end(), [&](int a, int b) { return T[(size_t)a * q + a] > T[(size_t)b * q + b]; });
-  lam.resize(q);
-  std::vector<double> W2((size_t)q * q);
-  for (int j = 0; j < q; ++j) {
-    lam[j] = T[(size_t)idx[j] * q + idx[j]];
-    for (int k = 0; k < q; ++k) W2[(size_t)k * q + j] = W[(size_t)k * q + idx[j]];
-  }
-  W = W2;
-}
-
-// work that rides in the peer-to-peer all-reduce's launch instead of getting launches of its own in front of it (ca_p2p_args)
-struct ca_ar_ride {
-  const float* gpart = nullptr; int nslice = 0; int64_t fold_lo = 0, fold_n = 0;
-  const double* yw_part = nullptr; int n_yw = 0; int64_t yw_index = -1;
-};
-inline bool p2p_ride_ok(const ca_engine* h, int64_t n) { return h->p2p && h->p2p->connected && h->p2p_ride && n <= h->p2p->cap; }
-int allreduce(ca_engine* h, double* buf, int64_t n, const ca_ar_ride* ride = nullptr) {
-  if (h->opt.world <= 1 && !h->comm && !h->host_ar && !(h->p2p && h->p2p->connected)) return CA_OK;   // a 1-rank communicator still reduces (tests)
-  if (h->p2p && h->p2p->connected) {
-    ca_p2p* pp = h->p2p;
-    for (int64_t o = 0; o < n; o += pp->cap) {   // (one launch for everything the loop reduces; longer vectors go in pieces)
-      const int64_t m = std::min<int64_t>(pp->cap, n - o);
-      const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(m, CA_TB), 64));
-      ca_p2p_args a;
-      memset(&a, 0, sizeof(a));
-      a.peers = pp->peers_dev; a.rank = h->opt.rank; a.world = h->opt.world; a.cap = pp->cap;
-      a.seq = ++pp->seq; a.err = pp->err_dev; a.err_local = pp->err_local; a.timeout_ticks = pp->timeout_ticks;
-      a.yw_index = -1;
-      if (ride) {   // (only ever with n <= cap: one piece, p2p_ride_ok)
-        a.gpart = ride->gpart; a.nslice = ride->nslice; a.fold_lo = ride->fold_lo; a.fold_n = ride->fold_n;
-        a.yw_part = ride->yw_part; a.n_yw = ride->n_yw; a.yw_index = ride->yw_index;
-      }
-      LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_p2p_allreduce, dim3(nblk), dim3(CA_TB), 0, h->stream, buf + o, m, a));
-    }
-    return CA_OK;
-  }
-  if (h->host_ar) {
-    if (n > h->host_ar_cap) {
-      if (h->host_ar_buf) HIPCK(h, hipHostFree(h->host_ar_buf));
-      HIPCK(h, hipHostMalloc((void**)&h->host_ar_buf, (size_t)n * sizeof(double)));
-      h->host_ar_cap = n;
-    }
-    HIPCK(h, hipMemcpyAsync(h->host_ar_buf, buf, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    SYNC(h);
-    if (h->host_ar(h->host_ar_user, h->host_ar_buf, n) != 0) { h->err = "host all-reduce callback failed"; return CA_ERR_COMM; }
-    HIPCK(h, hipMemcpyAsync(buf, h->host_ar_buf, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    return CA_OK;
-  }
-  if (!h->comm) { h->err = "world > 1 but neither ca_comm_init() nor ca_set_host_allreduce() was called"; return CA_ERR_STATE; }
-  int rc = g_rccl.AllReduce(buf, buf, (size_t)n, kNcclFloat64, kNcclSum, h->comm, h->stream);
-  if (rc != 0) {
-    h->err = std::string("ncclAllReduce: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error");
-    return CA_ERR_COMM;
-  }
-  return CA_OK;
-}
-
-// the per-gene count totals are sums over ALL cells (SURVEY.md §8e): reduced once, when the transport is set
-int setup_global_sums(ca_engine* h) {
-  if (h->sums_global) return CA_OK;
-  // a transport that died between the two reductions leaves colsum reduced and YtX not: no second transport may reduce colsum again
-  if (h->sums_started) { h->err = "an earlier transport failed inside the setup reductions; this engine cannot take another one -- destroy it"; return CA_ERR_STATE; }
-  h->sums_started = true;
-  CACK(allreduce(h, h->colsum, h->G));
-  if (h->P > 0 && h->K > 0) CACK(allreduce(h, h->YtX, (int64_t)h->G * h->P));
-  SYNC(h);
-  if (!h->mu_part.empty()) {
-    // loc0 = NULL on a shard (ABI 6): mu_guess_g = mean over ALL cells of y_ng / rowMeans(Y)_n (R/inference-tflow.R:220-235) -- the ranks' partial sums and
-    // cell counts are added here, then loc0 = safe_inverse_softplus(mu_guess) (:262, :6-11) exactly as create_impl does it for one handle
-    const int G = h->G;
-    std::vector<double> pack(h->mu_part);
-    pack.push_back((double)h->N);
-    HIPCK(h, hipMemcpyAsync(h->red, pack.data(), pack.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    CACK(allreduce(h, h->red, (int64_t)pack.size()));
-    HIPCK(h, hipMemcpyAsync(pack.data(), h->red, pack.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    SYNC(h);
-    std::vector<float> l0((size_t)G);
-    for (int g = 0; g < G; ++g) {
-      const double mu = pack[(size_t)g] / pack[(size_t)G];
-      l0[g] = (float)(std::log(1.0 - std::exp(-std::fabs(mu))) + std::max(mu, 0.0));
-    }
-    CACK(upload_f(h, h->loc, l0));
-    HIPCK(h, hipMemcpyAsync(h->loc_init, h->loc, (size_t)G * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
-    HIPCK(h, hipMemsetAsync(h->red, 0, pack.size() * sizeof(double), h->stream));
-    CACK(refresh_derived(h));
-    SYNC(h);
-    h->mu_part.clear();
-  }
-  if (h->layout_series) {   // (this function runs when a transport has come up)
-    // the ranks agree on the series form (its pick looks at the rank's own cell count): used where EVERY rank picked it; otherwise nobody uses it and everybody
-    // goes back to the classic layout of the reduction buffer -- the collectives' lengths are then the same on all ranks either way
-    double f[2] = {h->poly ? 1.0 : 0.0, 1.0};
-    HIPCK(h, hipMemcpyAsync(h->red, f, sizeof(f), hipMemcpyHostToDevice, h->stream));
-    SYNC(h);
-    CACK(allreduce(h, h->red, 2));
-    HIPCK(h, hipMemcpyAsync(f, h->red, sizeof(f), hipMemcpyDeviceToHost, h->stream));
-    SYNC(h);
-    HIPCK(h, hipMemsetAsync(h->red, 0, sizeof(f), h->stream));
-    if (f[0] != f[1]) h->poly = false;
-    if (!h->poly) {
-      h->layout_series = false;
-      h->off_g = 3 + h->C;
-      h->off_y = h->off_g + (int64_t)h->G * (h->S + h->D);
-      h->red_n = h->off_y + (int64_t)h->G * h->K;   // (the buffer is longer than this layout needs: the Gp - G padding rows of Y^T psi fit behind it)
-      h->off_q = h->off_x = 0;
-    }
-    SYNC(h);
-  }
-  h->sums_global = true;
   return CA_OK;
 }
 
@@ -469,8 +243,6 @@ ca_small_args small_args(ca_engine* h, const double* gene_part, int apply, float
   }
   return a;
 }
-// a fused monitor pass leaves its ELBO assembly for the next backward sweep; if none is coming, run it now
-inline bool is_sharded(const ca_engine* h) { return h->opt.world > 1 || h->comm || h->host_ar || (h->p2p && h->p2p->connected); }
 // Reduce a pending monitor tail's cell partials (and psi.(YW) partials) for a sharded run: red[0 .. 3 + C) local sums,
 // ready for the all-reduce.  The Y stream (side stream) must have delivered the psi.(YW) partials first.
 int mon_tail_local_sums(ca_engine* h) {
@@ -496,7 +268,6 @@ int flush_mon_tail(ca_engine* h) {
   h->mon_tail.enabled = 0;
   return CA_OK;
 }
-inline ca_small_args no_small_args() { ca_small_args a; memset(&a, 0, sizeof(a)); return a; }
 
 #ifndef CA_BWD_TL3_MAXN
 #define CA_BWD_TL3_MAXN 18432   // cells up to which the backward sweep takes three gene tiles per wave (see create_impl)
@@ -589,60 +360,33 @@ int train_bwd(ca_engine* h, const float* mu32, bool cell_sums_global) {
       if (split_tail) { bwd_tail.reduce_only = 1; bwd_tail.host_out = nullptr; bwd_tail.yw_part = nullptr; }
     }
     const int nextra = (bwd_tail.enabled || yfin.nrow) ? 1 + cdiv(yfin.ncol, CA_TB / 64) + yfin.nrow : 0;
-    const int yextra = cdiv(nextra, xb);   // extra block rows behind the sweep's
-    ca_yfin_args no_yfin;
-    memset(&no_yfin, 0, sizeof(no_yfin));
+    const ca_bwdm_extra extra = {bwd_tail, yfin, cdiv(nextra, xb)};   // (rows: extra block rows behind the sweep's)
     // mc_samples = 2 (round 4): both samples in ONE sweep (k_bwd_mfma<.., S2>: one exp per (cell, gene) for the two of them)
     const bool s2b = h->s2f && h->S == 2 && !h->c16;
-#define CA_BWDM(DDV) do { if (h->c16) CA_BWDM_(CA_BWD_TL, DDV, false, true, false); else if (s2b) { if (h->bwd_frac) CA_BWDM_(CA_BWD_TL, DDV, true, false, true); else CA_BWDM_(CA_BWD_TL, DDV, false, false, true); } \
-                          else if (h->bwd_frac) CA_BWDM_(CA_BWD_TL, DDV, true, false, false); else if (h->bwd_tl == 3) CA_BWDM_(3, DDV, false, false, false); else CA_BWDM_(CA_BWD_TL, DDV, false, false, false); } while (0)
-#define CA_BWDM_(TL, DDV, FRV, C16V, S2V)                                                                                   \
-  LAUNCH(h, CA_KERNEL_BWD,                                                                                                 \
-         hipLaunchKernelGGL((k_bwd_mfma<TL, DDV, FRV, C16V, S2V>), dim3(xb, h->csplit_m + (s == 0 ? yextra : 0)), dim3(CA_TB), \
-                            (size_t)h->cchunk_m * 4 * DDV * sizeof(float) * (S2V ? 2 : 1), h->stream,                       \
-                            h->coefq + (int64_t)s * h->N16 * 32, h->F, h->etamax2, h->Lb, mu32 + (int64_t)s * h->G, h->Vs,  \
-                            h->V, h->gpart, h->dFpart, h->N, h->G, h->cchunk_m, h->S, s, 1, s == 0 ? 1 : 0,                 \
-                            s == 0 ? bwd_tail : no_small_args(), h->csplit_m, s == 0 ? yfin : no_yfin,                      \
-                            (S2V || C16V) ? h->coefq + h->N16 * 32 : nullptr, S2V ? mu32 + h->G : nullptr))   /* (C16: the third-part image, S = 1) */
+    ca_bwdm_ops o;
+    memset(&o, 0, sizeof(o));
     if (h->bwd_pairs) {
       // 17..32 clones, or 9..16 with mc_samples >= 2: the sixteen-clone form once per sample and pair of clone chunks, accumulating into the same partials
       // (the copy numbers of the pair: Lb + 2 pair G 8, a chunk of zeros behind an odd last one; coef: one image per sample and pair, k_cell_par)
-#define CA_BWDP(DDV)                                                                                                          \
-  LAUNCH(h, CA_KERNEL_BWD,                                                                                                   \
-         hipLaunchKernelGGL((k_bwd_mfma<CA_BWD_TL, DDV, false, true, false>), dim3(xb, h->csplit_m + (first ? yextra : 0)), dim3(CA_TB), \
-                            (size_t)h->cchunk_m * 4 * DDV * sizeof(float), h->stream,                                         \
-                            h->coefq + ((int64_t)s * h->bwd_pairs + pr) * h->N16 * 32, h->F, h->etamax2,                      \
-                            h->Lb + (int64_t)pr * 2 * h->G * CA_CW, mu32 + (int64_t)s * h->G, h->Vs,                          \
-                            h->V, h->gpart, h->dFpart, h->N, h->G, h->cchunk_m, h->S, s, pr == 0 ? 1 : 0, first ? 1 : 0,     \
-                            first ? bwd_tail : no_small_args(), h->csplit_m, first ? yfin : no_yfin,                          \
-                            h->coefq + ((int64_t)(h->S + s) * h->bwd_pairs + pr) * h->N16 * 32, nullptr))   /* (the third-part image of this sample and pair) */
       // an odd last chunk stands alone: the eight-clone form on its own image (k_cell_par wrote it in that layout)
-#define CA_BWDL(DDV)                                                                                                          \
-  LAUNCH(h, CA_KERNEL_BWD,                                                                                                   \
-         hipLaunchKernelGGL((k_bwd_mfma<CA_BWD_TL, DDV, false, false, false>), dim3(xb, h->csplit_m + (first ? yextra : 0)), dim3(CA_TB), \
-                            (size_t)h->cchunk_m * 4 * DDV * sizeof(float), h->stream,                                         \
-                            h->coefq + ((int64_t)s * h->bwd_pairs + pr) * h->N16 * 32, h->F, h->etamax2,                      \
-                            h->Lb + (int64_t)pr * 2 * h->G * CA_CW, mu32 + (int64_t)s * h->G, h->Vs,                          \
-                            h->V, h->gpart, h->dFpart, h->N, h->G, h->cchunk_m, h->S, s, pr == 0 ? 1 : 0, first ? 1 : 0,     \
-                            first ? bwd_tail : no_small_args(), h->csplit_m, first ? yfin : no_yfin, nullptr, nullptr))
       for (int s = 0; s < h->S; ++s)
         for (int pr = 0; pr < h->bwd_pairs; ++pr) {
-          const bool first = s == 0 && pr == 0;
           const bool lone = (h->nchunk & 1) && pr == h->bwd_pairs - 1;
-          if (lone) { if (h->D == 1) CA_BWDL(1); else CA_BWDL(2); }
-          else { if (h->D == 1) CA_BWDP(1); else CA_BWDP(2); }
+          o.coefq = h->coefq + ((int64_t)s * h->bwd_pairs + pr) * h->N16 * 32; o.Lb = h->Lb + (int64_t)pr * 2 * h->G * CA_CW; o.mu = mu32 + (int64_t)s * h->G;
+          o.sidx = s; o.first_s = pr == 0 ? 1 : 0; o.extra = (s == 0 && pr == 0) ? &extra : nullptr;
+          o.c16 = !lone;
+          o.coefq1 = lone ? nullptr : h->coefq + ((int64_t)(h->S + s) * h->bwd_pairs + pr) * h->N16 * 32;   // (the third-part image of this sample and pair)
+          CACK(launch_bwd_mfma(h, h->D == 1 ? 1 : 2, o));
         }
-#undef CA_BWDL
-#undef CA_BWDP
-    } else
-    for (int s = 0; s < (s2b ? 1 : h->S); ++s) {
-      if (h->D == 1) CA_BWDM(1);
-      else if (h->D == 2) CA_BWDM(2);
-      else if (h->D == 3) { if (h->bwd_frac) CA_BWDM_(CA_BWD_TL_D34, 3, true, false, false); else CA_BWDM_(CA_BWD_TL_D34, 3, false, false, false); }   // (D = 3, 4: the three-tile wave)
-      else { if (h->bwd_frac) CA_BWDM_(CA_BWD_TL_D34, 4, true, false, false); else CA_BWDM_(CA_BWD_TL_D34, 4, false, false, false); }
+    } else {
+      o.Lb = h->Lb; o.first_s = 1; o.frac = h->bwd_frac; o.c16 = h->c16; o.s2 = s2b; o.tl3 = h->bwd_tl == 3;
+      if ((h->D == 1 || h->D == 2) && (s2b || h->c16)) o.coefq1 = h->coefq + h->N16 * 32;   // (C16: the third-part image, S = 1)
+      if ((h->D == 1 || h->D == 2) && s2b) o.mu1 = mu32 + h->G;
+      for (int s = 0; s < (s2b ? 1 : h->S); ++s) {
+        o.coefq = h->coefq + (int64_t)s * h->N16 * 32; o.mu = mu32 + (int64_t)s * h->G; o.sidx = s; o.extra = s == 0 ? &extra : nullptr;
+        CACK(launch_bwd_mfma(h, h->D, o));   // (D = 3, 4: the three-tile wave)
+      }
     }
-#undef CA_BWDM
-#undef CA_BWDM_
     if (bwd_tail.enabled) {
       if (merged) { h->mon_tail.cell_part = nullptr; h->mon_tail.yw_part = nullptr; }   // local sums done; assembly still pending
       else if (split_tail) h->mon_tail.cell_part = nullptr;
@@ -703,6 +447,54 @@ inline bool update_merges(const ca_engine* h, int apply, const double* elbo_dst)
   const int64_t mB = h->s2 ? 2 * h->hint_A + 1 : h->hint_B;
   return apply && h->upd_merge && !elbo_dst && h->pre_ok && h->hint_A >= 0 && mB >= 0 && h->fused_ok && h->gene_part_alt && h->fwd_cell && h->K > 0;
 }
+// the next fused pass's per-gene prologue for eps draws A and B, riding on the update (ca_pre_args): into the alternate partial buffers, fused_pass swaps them in
+ca_pre_args pre_args(const ca_engine* h, int64_t A, int64_t B) {
+  ca_pre_args pre;
+  memset(&pre, 0, sizeof(pre));
+  pre.nblk = h->ngblk;
+  pre.loc = h->loc; pre.ls = h->ls; pre.epsA = h->eps_dev + A * (int64_t)h->G; pre.epsB = h->eps_dev + B * (int64_t)h->G;
+  pre.colsum = h->colsum; pre.Lb = h->Lb; pre.V = h->V; pre.YtX = h->YtX; pre.muA = h->mu32; pre.muB = h->s2 ? h->mu32 + h->G : h->mu32B; pre.Mb = h->Mb2;
+  pre.s2 = h->s2 ? 1 : 0;
+  pre.gene_partA = h->gene_part_alt; pre.gene_partB = h->gene_partB_alt; pre.Mq = h->fwd_mfma ? h->Mq : nullptr;
+  pre.G = h->G; pre.D = h->D; pre.K = h->K; pre.mrow = h->frow; pre.C = h->C;
+  return pre;
+}
+// The int8 count-matrix stream's quantiser for the state an Adam step is about to produce, as extra blocks of the update's launch (W and psi are final there):
+// possible when the exponents can be bounded from the maxima of the state before (`ys_steps` steps ago, + this one).  nblk = 0: it does not ride (ys_quant runs it).
+ca_ysq_args ys_quant_ride(ca_engine* h) {
+  ca_ysq_args a;
+  memset(&a, 0, sizeof(a));
+  if (!h->y_ys || h->K == 0 || h->ys_quant_ready) return a;
+  bool lagged = false;
+  const ca_ysq_args q = ys_quant_args(h, h->ys_steps >= 0 ? h->ys_steps + 1 : -1, &lagged);
+  if (!lagged) return a;
+  h->ys_quant_ready = true;
+  return q;
+}
+// psi is final: the Y pass for the new parameters goes to the side stream from HERE (its launches are issued by the
+// next pass, so the main stream is not left waiting for the host to get through them), and what the update still has to run
+// (k_adam_cell -- q(z) logits, exponent bound, the O(K + C) update and the next pass's per-gene prologue: 12-16 us) is its head
+// start over the next forward sweep.  The Y stream needs one: letting the sweep and the Y kernel start together
+// cost 18 % (2219 -> 1825 it/s; the sweep's blocks take the CUs first).  Not when the stream rides on the sweep's launch.
+int defer_y_to_side(ca_engine* h) {
+  if (!h->async_y || h->K == 0 || h->ride_ok || h->ride_ys) return CA_OK;
+  HIPCK(h, hipEventRecord(h->ev_params, h->stream));
+  h->y_defer = true;
+  return CA_OK;
+}
+// bookkeeping after an applied Adam step (both forms of the update).  xmax_ready: the launch left max |psi| of the stepped state per 256-cell piece (ca_merge_args::xpart)
+void adam_stepped(ca_engine* h, bool xmax_ready) {
+  if (h->ys_steps >= 0) h->ys_steps += 1;
+  h->b1p *= (float)h->opt.beta1;
+  h->b2p *= (float)h->opt.beta2;
+  h->adam_steps += 1;
+  h->poly_xmax_ready = xmax_ready;
+  if (h->poly_xglob_steps >= 0) h->poly_xglob_steps += 1;
+  h->ycache_valid = false;
+  h->yfin_pending = false;
+  h->look_valid = false;
+  if (h->poly && h->y_ys && h->K > 0) h->poly_y_defer = true;   // series form: the next series pass sends the count-matrix products of the stepped state to the side stream
+}
 int train_update(ca_engine* h, const float* eps, int apply, double* elbo_dst) {
   const int N256 = cdiv(h->N, CA_TB);
   float lr_t = 0.f;
@@ -746,21 +538,11 @@ int train_update(ca_engine* h, const float* eps, int apply, double* elbo_dst) {
         h->gate_t0 = std::chrono::steady_clock::now();   // (before the launch below: the relay's clock starts no earlier)
       }
       h->gate_req = false;
-      ca_pre_args& pre = mg.pre;
-      pre.nblk = h->ngblk;
-      pre.loc = h->loc; pre.ls = h->ls; pre.epsA = h->eps_dev + mA * (int64_t)h->G; pre.epsB = h->eps_dev + mB * (int64_t)h->G;
-      pre.colsum = h->colsum; pre.Lb = h->Lb; pre.V = h->V; pre.YtX = h->YtX; pre.muA = h->mu32; pre.muB = h->s2 ? h->mu32 + h->G : h->mu32B; pre.Mb = h->Mb2;
-      pre.s2 = h->s2 ? 1 : 0;
-      pre.gene_partA = h->gene_part_alt; pre.gene_partB = h->gene_partB_alt; pre.Mq = h->fwd_mfma ? h->Mq : nullptr;
-      pre.G = h->G; pre.D = h->D; pre.K = h->K; pre.mrow = h->frow; pre.C = h->C;
-      if (h->y_ys && !h->ys_quant_ready) {   // the int8 stream's images of the stepped W and psi (exponents from the lagged maxima, as on k_adam_cell)
-        bool lagged = false;
-        const ca_ysq_args a = ys_quant_args(h, h->ys_steps >= 0 ? h->ys_steps + 1 : -1, &lagged);
-        if (lagged) {
-          mg.ysq = a; mg.ysq.nblk = h->ngblk + N256;
-          h->ys_namax[(h->ys_slot + 1) % 3] = h->ngblk + N256;   // one pair per gene block, then one per psi block
-          h->ys_quant_ready = true;
-        }
+      mg.pre = pre_args(h, mA, mB);
+      mg.ysq = ys_quant_ride(h);   // the int8 stream's images of the stepped W and psi (exponents from the lagged maxima, as on k_adam_cell)
+      if (mg.ysq.nblk) {
+        mg.ysq.nblk = h->ngblk + N256;
+        h->ys_namax[(h->ys_slot + 1) % 3] = h->ngblk + N256;   // one pair per gene block, then one per psi block
       }
       mg.tail = small_args(h, h->gene_part, 1, lr_t, nullptr, false);
       mg.tail.terms_out = nullptr;                 // (the pending monitor pass's block of this launch owns the ELBO terms)
@@ -789,10 +571,7 @@ int train_update(ca_engine* h, const float* eps, int apply, double* elbo_dst) {
                                 (float)h->opt.beta1, (float)h->opt.beta2, (float)h->opt.adam_eps, mon, h->ngblk, psi,
                                 h->fold_now ? h->gpart : nullptr, h->csplit_m, mg));
       h->fold_now = false;
-      if (h->async_y && !h->ride_ok && !h->ride_ys) {   // side-stream Y pass (2- / 4-byte storage, K != 1): psi is final from here, as below
-        HIPCK(h, hipEventRecord(h->ev_params, h->stream));
-        h->y_defer = true;
-      }
+      CACK(defer_y_to_side(h));   // (2- / 4-byte storage, K != 1)
       std::swap(h->vchi, h->vchi_alt);
       std::swap(h->alpha_u, h->alpha_u_alt);
       h->em_stale = true;
@@ -800,16 +579,7 @@ int train_update(ca_engine* h, const float* eps, int apply, double* elbo_dst) {
       h->gaux_idx = 1 - h->gaux_idx; h->gaux_slot = h->S == 1 ? mB : -1;
       h->pre_valid = true; h->pre_A = mA; h->pre_B = mB;
       h->hint_A = h->hint_B = -1;
-      if (h->ys_steps >= 0) h->ys_steps += 1;
-      h->b1p *= (float)h->opt.beta1;
-      h->b2p *= (float)h->opt.beta2;
-      h->adam_steps += 1;
-      h->poly_xmax_ready = mg.xpart != nullptr;   // (the series form's next moment launches need no k_poly_xmax in front)
-      if (h->poly_xglob_steps >= 0) h->poly_xglob_steps += 1;
-      h->ycache_valid = false;
-      h->yfin_pending = false;
-      h->look_valid = false;
-      if (h->poly && h->y_ys) h->poly_y_defer = true;   // series form: the next series pass sends the count-matrix products of the stepped state to the side stream
+      adam_stepped(h, mg.xpart != nullptr);   // (max |psi| came with the update: the series form's next moment launches need no k_poly_xmax in front)
       return CA_OK;
     }
   }
@@ -821,38 +591,19 @@ int train_update(ca_engine* h, const float* eps, int apply, double* elbo_dst) {
                             lr_t, (float)h->opt.beta1, (float)h->opt.beta2, (float)h->opt.adam_eps, mon, h->ngblk, psi,
                             h->fold_now ? h->gpart : nullptr, h->csplit_m));
   h->fold_now = false;
-  if (apply && h->async_y && h->K > 0 && !h->ride_ok && !h->ride_ys) {
-    // psi is final: the Y pass for the new parameters goes to the side stream from HERE (its launches are issued by the
-    // next pass, so the main stream is not left waiting for the host to get through them), and the per-cell kernel below
-    // (q(z) logits, exponent bound, the O(K + C) update and the next pass's per-gene prologue: 12-16 us) is its head
-    // start over the next forward sweep.  The Y stream needs one: letting the sweep and the Y kernel start together
-    // cost 18 % (2219 -> 1825 it/s; the sweep's blocks take the CUs first).
-    HIPCK(h, hipEventRecord(h->ev_params, h->stream));
-    h->y_defer = true;
-  }
+  if (apply) CACK(defer_y_to_side(h));   // (the per-cell kernel below is the Y pass's head start over the next forward sweep)
   // the next fused pass's per-gene prologue, when the loop has announced its eps slots: extra blocks of the per-cell kernel
   ca_pre_args pre;
   memset(&pre, 0, sizeof(pre));
   // (the hints are PASS slots; two samples per pass for mc_samples = 2)
   int64_t hA = h->hint_A, hB = h->hint_B;
   if (h->s2) { hA = 2 * h->hint_A; hB = hA + 1; }
-  if (apply && h->pre_ok && h->hint_A >= 0 && hB >= 0 && h->fused_ok && h->gene_part_alt) {
-    pre.nblk = h->ngblk;
-    pre.loc = h->loc; pre.ls = h->ls; pre.epsA = h->eps_dev + hA * (int64_t)h->G; pre.epsB = h->eps_dev + hB * (int64_t)h->G;
-    pre.colsum = h->colsum; pre.Lb = h->Lb; pre.V = h->V; pre.YtX = h->YtX; pre.muA = h->mu32; pre.muB = h->s2 ? h->mu32 + h->G : h->mu32B; pre.Mb = h->Mb2;
-    pre.s2 = h->s2 ? 1 : 0;
-    pre.gene_partA = h->gene_part_alt; pre.gene_partB = h->gene_partB_alt; pre.Mq = h->fwd_mfma ? h->Mq : nullptr;
-    pre.G = h->G; pre.D = h->D; pre.K = h->K; pre.mrow = h->frow; pre.C = h->C;
-  }
+  if (apply && h->pre_ok && h->hint_A >= 0 && hB >= 0 && h->fused_ok && h->gene_part_alt) pre = pre_args(h, hA, hB);
   // the int8 count-matrix stream's quantiser for the state this step produces: extra blocks of the same launch (W and psi are
   // final since k_final_gene), exponents bounded from the maxima of the state before (`ys_steps` steps ago, + this one)
   ca_ysq_args ysq;
   memset(&ysq, 0, sizeof(ysq));
-  if (apply && h->y_ys && h->K > 0 && !h->ys_quant_ready) {
-    bool lagged = false;
-    const ca_ysq_args a = ys_quant_args(h, h->ys_steps >= 0 ? h->ys_steps + 1 : -1, &lagged);
-    if (lagged) { ysq = a; h->ys_quant_ready = true; }
-  }
+  if (apply) ysq = ys_quant_ride(h);
   LAUNCH(h, CA_KERNEL_OTHER,
          hipLaunchKernelGGL(k_adam_cell, dim3(N256 + 1 + pre.nblk + ysq.nblk), dim3(CA_TB), 0, h->stream, h->F, h->glogit, h->dgl, h->m_gl, h->v_gl,
                             h->N, h->C, h->D, apply, lr_t, (float)h->opt.beta1, (float)h->opt.beta2, (float)h->opt.adam_eps,
@@ -860,18 +611,7 @@ int train_update(ca_engine* h, const float* eps, int apply, double* elbo_dst) {
                             N256, pre, ysq));
   if (pre.nblk) { h->pre_valid = true; h->pre_A = hA; h->pre_B = hB; }
   h->hint_A = h->hint_B = -1;
-  if (apply) {
-    if (h->ys_steps >= 0) h->ys_steps += 1;
-    h->b1p *= (float)h->opt.beta1;
-    h->b2p *= (float)h->opt.beta2;
-    h->adam_steps += 1;
-    h->poly_xmax_ready = false;
-    if (h->poly_xglob_steps >= 0) h->poly_xglob_steps += 1;
-    h->ycache_valid = false;   // V', its range and etamax2 were refreshed inside the step's own kernels
-    h->yfin_pending = false;
-    h->look_valid = false;
-    if (h->poly && h->y_ys && h->K > 0) h->poly_y_defer = true;   // (as in the one-launch form above)
-  }
+  if (apply) adam_stepped(h, false);   // (V', its range and etamax2 were refreshed inside the step's own kernels)
   return CA_OK;
 }
 
@@ -900,14 +640,10 @@ int run_pass(ca_engine* h, int64_t eps_slot, int mode, int apply, double* elbo_d
     // the pass's S x nchunk slices of M two to a sixteen-column matrix-core sweep (round 6; mc_samples = 3: two sweeps where there were three vector sweeps
     // of 1.4x the time each; 20 clones: two where there were three)
     LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_mq_pairs, dim3(h->ngblk, h->S * h->nchunk), dim3(CA_TB), 0, h->stream, h->Mb, h->pf_Mq, h->G, h->nk32));
-    const dim3 grid(cdiv(h->N, (CA_TB / 64) * CA_FM_TL * 16), h->pf_fsplit);
     for (int pr = 0; pr < h->pf_npair; ++pr) {
       const unsigned short* mq = h->pf_Mq + (int64_t)pr * h->nk32 * 1024;
       float* zp = h->pf_Z + (int64_t)pr * h->pf_fsplit * h->N * 16;
-      if (h->D == 1)
-        LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_mfma<1>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, mq, zp, h->N, h->G, h->pf_kchunk, h->nk32));
-      else
-        LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_mfma<2>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, mq, zp, h->N, h->G, h->pf_kchunk, h->nk32));
+      CACK(launch_fwd_mfma(h, mq, zp, h->pf_fsplit, h->pf_kchunk));
     }
   } else
   for (int s = 0; s < h->S; ++s)
@@ -925,25 +661,7 @@ int run_pass(ca_engine* h, int64_t eps_slot, int mode, int apply, double* elbo_d
   const float* ywp = yw_done ? h->YW : h->YWpart;
   const int ywseg = yw_done ? 1 : h->nseg + (h->n_ovf > 0 ? 1 : 0);
   if (h->C <= 64) {
-    int CP = 1;
-    while (CP < h->C) CP <<= 1;
-    dim3 grid(h->ncblk);
-#define CA_CELL(CPV)                                                                                                          \
-  LAUNCH(h, CA_KERNEL_CELL,                                                                                                   \
-         hipLaunchKernelGGL((k_cell_par<CPV>), grid, dim3(CA_TB), 0, h->stream, h->pfwd ? h->pf_Z : h->Zpart, h->A, h->cn, h->s64, h->etamax2, \
-                            h->glogit, h->alpha_u, h->F, ywp, h->YW, h->coef, h->dgl, h->cell_part, h->N, h->C, h->S,       \
-                            h->D, h->K, h->pfwd ? h->pf_fsplit : h->gsplit, h->nchunk, ywseg, mode, h->bwd_mfma ? h->coefq : nullptr, h->N16, h->pfwd ? 1 : 0, \
-                            (int64_t)h->S * cdiv(h->nchunk, 2) * h->N16 * 32))
-    switch (CP) {
-      case 1: CA_CELL(1); break;
-      case 2: CA_CELL(2); break;
-      case 4: CA_CELL(4); break;
-      case 8: CA_CELL(8); break;
-      case 16: CA_CELL(16); break;
-      case 32: CA_CELL(32); break;
-      default: CA_CELL(64); break;
-    }
-#undef CA_CELL
+    CACK(launch_cell_par(h, ywp, ywseg, mode));
   } else {
     LAUNCH(h, CA_KERNEL_CELL,
            hipLaunchKernelGGL(k_cell, dim3(h->ncblk), dim3(CA_TB), 0, h->stream, h->Zpart, h->A, h->cn, h->s64, h->etamax2, h->glogit,
@@ -1038,25 +756,6 @@ int poly_guard(ca_engine* h, bool* use_series, double** mirror, double* seq, boo
   return CA_OK;
 }
 
-// Block order of a launch the count-matrix stream rides on (ca_yride_args / ca_ysride_args: nb_main stream units, nb_y with the overflow list's blocks; nf
-// sweep blocks); returns the grid's block count.
-// Interleave of the two kinds in dispatch order.  Blocks go round-robin over the 8 XCDs, so a period that divides 8 (the
-// obvious even / odd split) puts ALL sweep blocks on four XCDs and all stream blocks on the other four; two sweep blocks per
-// stream block mixes them on every CU: cfg-3 2795 -> 3008 it/s, 12.5k cells 10.9k -> 12.1k, cfg-2 16.3k -> 17.9k
-// (profiles/r02_ab_ystream.txt section 8).
-// Long-lived stream blocks lead the grid (ca_yride_args::pers) when there are at least two units of the matrix per CU: one
-// such block per CU measured best (cfg-3, with the non-temporal stream: 2:1 interleave 3090, 256 blocks 3147, 341 / 512
-// blocks 3008 / 2979, 192 / 128 blocks 2790 / 2320 it/s).  ca_options.ride_pattern < 0 sets the number, > 0 asks for the interleave (a << 8 | b).
-template <typename RideArgs>
-unsigned ride_pattern(const ca_engine* h, RideArgs& ya, int nf) {
-  const int rp = h->opt.ride_pattern;
-  ya.pat_a = 2; ya.pat_b = 1;
-  if (rp > 0 && (rp >> 8) > 0 && (rp & 255) > 0) { ya.pat_a = rp >> 8; ya.pat_b = rp & 255; }
-  if (rp < 0) ya.pers = std::min(-rp, ya.nb_main);
-  else if (rp == 0 && ya.nb_main >= 2 * h->n_cu) ya.pers = h->n_cu;
-  return ya.pers > 0 ? (unsigned)(ya.pers + nf + (ya.nb_y - ya.nb_main)) : (unsigned)(nf + ya.nb_y);
-}
-
 // Monitor pass for eps slot A fused with the forward half of the NEXT train pass (eps slot B): one sweep,
 // one exp per (cell, gene) for both (same parameters, R/inference-tflow.R:401,403 of consecutive iterations).
 int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, double* elbo_dstB = nullptr, int64_t trainA = -1) {
@@ -1114,8 +813,6 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
   else CACK(ensure_etamax(h));
   cp.ee_partB = (elbo_dstB && h->fwd_cell) ? h->ee_partB : nullptr;
   cp.s2 = h->s2 ? 1 : 0; cp.N16 = h->N16;
-  int CP = 1;
-  while (CP < h->C) CP <<= 1;
   int cell_blocks = h->ncblk;
   if (series) {
     // Z of both draws from the moments of M over gene bins (ca_poly.hip), the same cell epilogue, d/dF and the backward moments in one pass over
@@ -1192,22 +889,6 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     ya.Gp = h->Gp; ya.RS = h->ys_RS; ya.nb_main = h->ys_nrg * h->ys_nseg; ya.nb_y = ya.nb_main;
     ya.ovf = ys_ovf(h);
     ya.nb_y += ya.ovf.nb_rows + ya.ovf.nb_chunks;
-    const dim3 grid(ride_pattern(h, ya, h->ncblk_f));
-#define CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, Y4V)                                                                                                   \
-  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_ys<DV, TLBV, 2, DPV, C16V, S2FV, Y4V>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, \
-                                              h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya))
-// (the 4-bit image rides only with the series form's shapes: D = 1, no c16 / s2 -- ride_ys, ca_eng_create.inc)
-#define CA_FCYS(DV, TLBV, DPV, C16V, S2FV) do {                                                                          \
-    if constexpr (DV == 1 && !C16V && !S2FV) { if (h->ys4) CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, true); else CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, false); } \
-    else CA_FCYS_L(DV, TLBV, DPV, C16V, S2FV, false); } while (0)
-#define CA_FCYS_D(TLBV, DPV) do { if (h->c16) { if (h->D == 1) CA_FCYS(1, TLBV, DPV, true, false); else CA_FCYS(2, TLBV, DPV, true, false); }  \
-                                  else if (s2f) { if (h->D == 1) CA_FCYS(1, TLBV, DPV, false, true); else CA_FCYS(2, TLBV, DPV, false, true); } \
-                                  else { if (h->D == 1) CA_FCYS(1, TLBV, DPV, false, false); else CA_FCYS(2, TLBV, DPV, false, false); } } while (0)
-    // (one piece in flight per wave: 128 VGPRs = four waves per SIMD like the vector stream's launch; two pieces, 162 VGPRs and
-    //  three waves, measured 2824 against 2869 it/s at cfg-3 -- profiles/r03_ab_ystream.txt)
-#ifndef CA_YS_RIDE_DEPTH
-#define CA_YS_RIDE_DEPTH 1   // (lab: pieces in flight per stream wave)
-#endif
     if (h->fwd_bal && !s2f) {   // small problems: one eight-wave sweep block per CU, left-over tiles spread gene-wise (ca_fwdbal.hip.h)
       ca_bal_args ba;
       memset(&ba, 0, sizeof(ba));
@@ -1221,27 +902,8 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
       // (measured, 8192 ... 25 000 cells x 5000 genes: one unit per block is 2-4 us per iteration faster at every size, gpurun_out/r5/stair_units.txt;
       //  ride_pattern = 2 asks for two)
       ba.stream_units = h->opt.ride_pattern == 2 ? 2 : 1;
-      const dim3 gridb((unsigned)(h->n_cu + (ba.stream_units == 2 ? (ya.nb_main + 1) / 2 : ya.nb_main) + (ya.nb_y - ya.nb_main)));   // sweep blocks, stream blocks, the overflow list's
-#define CA_FBAL(TLV) if (h->ys4) CA_FBAL_L(TLV, true); else CA_FBAL_L(TLV, false)
-#define CA_FBAL_L(TLV, Y4V) LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_bal_ys<1, TLV, CA_YS_RIDE_DEPTH, Y4V>), gridb, dim3(CA_BAL_TB), 0, h->stream, h->F, h->etamax2, \
-                                                                 h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, ba, ya))
-      switch (h->bal_q) {
-        case 1: CA_FBAL(1); break;
-        case 2: CA_FBAL(2); break;
-        case 3: CA_FBAL(3); break;
-        case 4: CA_FBAL(4); break;
-        case 5: CA_FBAL(5); break;
-        default: CA_FBAL(6); break;
-      }
-#undef CA_FBAL
-#undef CA_FBAL_L
-    } else
-    if (h->fc_tl == 6) CA_FCYS_D(6, CA_YS_RIDE_DEPTH);
-    else if (h->fc_tl == 1 && !h->c16) { if (h->D == 1) CA_FCYS(1, 1, CA_YS_RIDE_DEPTH, false, false); else CA_FCYS(2, 1, CA_YS_RIDE_DEPTH, false, false); }
-    else CA_FCYS_D(2, CA_YS_RIDE_DEPTH);
-#undef CA_FCYS_D
-#undef CA_FCYS
-#undef CA_FCYS_L
+      CACK(launch_fwd_bal_ys(h, cp, ba, ya));
+    } else CACK(launch_fwd_cell_mix_ys(h, cp, ya, s2f));
     CACK(ys_finish(h, h->yfin_split && (!is_sharded(h) || p2p_ride_ok(h, h->red_n))));
   } else if (h->fwd_cell && ride) {   // ... and the Y stream's blocks interleaved with the sweep's in the same grid
     cell_blocks = h->ncblk_f;
@@ -1252,101 +914,22 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     ya.nb_main = h->nrg * h->nseg; ya.nb_y = ya.nb_main;
     ya.ovf = ovf_args(h, h->YWpart + (int64_t)h->nseg * h->N * h->K);
     ya.nb_y += ya.ovf.nb_rows + ya.ovf.nb_chunks;
-    const dim3 grid(ride_pattern(h, ya, h->ncblk_f));
-#define CA_FCY(DV, TLBV)                                                                                                              \
-  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix_y<DV, TLBV, 2>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq, \
-                                              cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig, h->ncblk_f, ya))
-    if (h->fc_tl == 8) { if (h->D == 1) CA_FCY(1, 8); else CA_FCY(2, 8); }
-    else if (h->fc_tl == 6) { if (h->D == 1) CA_FCY(1, 6); else CA_FCY(2, 6); }
-    else { if (h->D == 1) CA_FCY(1, 2); else CA_FCY(2, 2); }
-#undef CA_FCY
+    CACK(launch_fwd_cell_mix_y(h, cp, ya));
     CACK(launch_yfinish(h, h->nrg, h->nseg));   // the stream's finishers, in line behind the launch they rode on
     h->ycache_valid = true;
   } else if (h->fwd_cell) {   // sweep + cell epilogue in one kernel: no Z partials, one launch
     cell_blocks = h->ncblk_f;
-#define CA_FC(DV, TLV)                                                                                                       \
-  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell<DV, TLV>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, h->etamax2, \
-                                              h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32))
-#define CA_FCD(TLV) do { if (h->D == 1) CA_FC(1, TLV); else CA_FC(2, TLV); } while (0)
-#define CA_FCD4(TLV) do { if (h->D == 1) CA_FC(1, TLV); else if (h->D == 2) CA_FC(2, TLV); else if (h->D == 3) CA_FC(3, TLV); else CA_FC(4, TLV); } while (0)
-#define CA_FCM(DV, TLV)                                                                                                      \
-  LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix<DV, TLV, 2>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, \
-                                              h->etamax2, h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig))
-#define CA_FCMD(TLV) do { if (h->D == 1) CA_FCM(1, TLV); else CA_FCM(2, TLV); } while (0)
-#define CA_FCMD4(TLV) do { if (h->D == 1) CA_FCM(1, TLV); else if (h->D == 2) CA_FCM(2, TLV); else if (h->D == 3) CA_FCM(3, TLV); else CA_FCM(4, TLV); } while (0)
-    if (h->c16) {   // 9..16 clones: the two default block shapes
-#define CA_FC16(DV) do { if (h->fc_nbig > 0) \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix<DV, 6, 2, true>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, \
-                                                  h->etamax2, h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig)); \
-    else if (h->fc_tl == 6) \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell<DV, 6, true>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, h->etamax2, \
-                                                  h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32)); \
-    else \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell<DV, 2, true>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, h->etamax2, \
-                                                  h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32)); } while (0)
-      if (h->D == 1) CA_FC16(1); else CA_FC16(2);
-#undef CA_FC16
-    } else if (s2f) {   // mc_samples = 2, four draws: the same two block shapes
-#define CA_FCS2(DV) do { if (h->fc_nbig > 0) \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell_mix<DV, 6, 2, false, true>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, \
-                                                  h->etamax2, h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32, h->fc_nbig)); \
-    else if (h->fc_tl == 6) \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell<DV, 6, false, true>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, h->etamax2, \
-                                                  h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32)); \
-    else \
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_cell<DV, 2, false, true>), dim3(h->ncblk_f), dim3(CA_TB), 0, h->stream, h->F, h->etamax2, \
-                                                  h->Vs, h->Mq, cp, h->alpha_u, h->cell_part, h->N, h->C, h->K, h->nk32)); } while (0)
-      if (h->D == 1) CA_FCS2(1); else CA_FCS2(2);
-#undef CA_FCS2
-    } else if (h->fc_nbig > 0) {
-      switch (h->fc_tl) {
-        case 4: CA_FCMD(4); break;
-        case 5: CA_FCMD(5); break;
-        case 8: CA_FCMD(8); break;
-        default: CA_FCMD4(6); break;   // (D = 3, 4: this shape and the 32-cell one only)
-      }
-    } else
-    switch (h->fc_tl) {
-      case 1: CA_FCD(1); break;
-      case 2: CA_FCD4(2); break;
-      case 4: CA_FCD(4); break;
-      case 5: CA_FCD(5); break;
-      case 6: CA_FCD4(6); break;
-      default: CA_FCD(8); break;
-    }
-#undef CA_FCMD4
-#undef CA_FCMD
-#undef CA_FCM
-#undef CA_FCD4
-#undef CA_FCD
-#undef CA_FC
+    CACK(launch_fwd_cell(h, cp, s2f));
   } else {
   if (h->fwd_mfma) {
-    const dim3 grid(cdiv(h->N, (CA_TB / 64) * CA_FM_TL * 16), h->fsplit);
-    if (h->D == 1)
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_mfma<1>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq,
-                                                  h->Zpart2, h->N, h->G, h->fkchunk, h->nk32));
-    else
-      LAUNCH(h, CA_KERNEL_FWD, hipLaunchKernelGGL((k_fwd_mfma<2>), grid, dim3(CA_TB), 0, h->stream, h->F, h->etamax2, h->Vs, h->Mq,
-                                                  h->Zpart2, h->N, h->G, h->fkchunk, h->nk32));
+    CACK(launch_fwd_mfma(h, h->Mq, h->Zpart2, h->fsplit, h->fkchunk));
   } else {
     LAUNCH(h, CA_KERNEL_FWD, launch_fwd_fused(h->C, h->D, dim3(cdiv(h->N, CA_TB * kFwdR), h->gsplit), h->stream, h->F, h->etamax2,
                                               h->Vs, h->Mb2, h->Zpart2, h->N, h->G, h->gchunk));
   }
   {
     // (no wait for the side stream here: this epilogue does not touch the Y stream's products -- k_yw_dot does)
-    dim3 grid(h->ncblk);
-#define CA_CELLF(CPV)                                                                                                   \
-  LAUNCH(h, CA_KERNEL_CELL,                                                                                             \
-         hipLaunchKernelGGL((k_cell_fused<CPV>), grid, dim3(CA_TB), 0, h->stream, h->Zpart2, h->frow, cp, h->alpha_u,    \
-                            h->cell_part, h->N, h->C, h->D, h->K, h->fwd_mfma ? h->fsplit : h->gsplit))
-    switch (CP) {
-      case 1: CA_CELLF(1); break;
-      case 2: CA_CELLF(2); break;
-      case 4: CA_CELLF(4); break;
-      default: CA_CELLF(8); break;
-    }
-#undef CA_CELLF
+    CACK(launch_cell_fused(h, cp));
   }
   }
   // The ELBO assembly (reduction of the cell partials and of k_yw_dot's psi.(YW) partials, then the O(K + C) body) is
@@ -1398,7 +981,6 @@ int train_bwd_speculative(ca_engine* h) {
   h->bwd_slot = h->look_slot;
   return CA_OK;
 }
-int read_doubles(ca_engine* h, const double* dev, double* out, int n);
 // ca_run: the monitor pass's O(K + C) body mirrors its ELBO into pinned host memory and raises a sequence flag
 // (ca_small_args::host_*); the host spins on the flag instead of draining a stream, so whatever was queued behind
 // the monitor pass (the speculative backward sweep) keeps the GPU busy.  Falls back to a plain read-back when the
@@ -1483,12 +1065,25 @@ int ensure_elbo_cap(ca_engine* h, int64_t n) {
   return CA_OK;
 }
 
+// The pinned staging buffer of the eps stream, at least `bytes` long and free to be refilled: the copy that last read it has completed BEFORE it is freed,
+// regrown or written.
+int stage_reserve(ca_engine* h, size_t bytes) {
+  if (h->ev_stage) HIPCK(h, hipEventSynchronize(h->ev_stage));
+  if (bytes > h->eps_stage_bytes) {
+    if (h->eps_stage) HIPCK(h, hipHostFree(h->eps_stage));
+    h->eps_stage = nullptr; h->eps_stage_bytes = 0;
+    HIPCK(h, hipHostMalloc((void**)&h->eps_stage, bytes));
+    h->eps_stage_bytes = bytes;
+  }
+  return CA_OK;
+}
 // put `n_draws` draws on the device: from the caller's stream, or generated (built-in Philox stream)
 int stage_eps(ca_engine* h, const float* eps_stream, int64_t have, int64_t need) {
   const int64_t per = (int64_t)h->S * h->G;
   h->look_valid = false;   // the staged eps slots are about to change
   h->gaux_slot = -1;
   CACK(ensure_eps_cap(h, std::max<int64_t>(need, 1)));
+  const size_t bytes = (size_t)need * per * sizeof(float);
   if (eps_stream) {
     if (have < need) {
       h->err = "eps stream too short: need " + std::to_string(need) + " draws, got " + std::to_string(have);
@@ -1496,32 +1091,14 @@ int stage_eps(ca_engine* h, const float* eps_stream, int64_t have, int64_t need)
     }
     // Through the engine's pinned staging buffer, stream-ordered, WITHOUT draining the stream: a copy from the caller's pageable
     // memory followed by a synchronisation left the GPU idle for ~250 us at the start of every call (kernel trace of the
-    // driver's 20-step command: 4 % of its time).  The buffer is reused only after the copy that last read it has completed.
-    const size_t bytes = (size_t)need * per * sizeof(float);
-    if (bytes > h->eps_stage_bytes) {
-      if (h->ev_stage) HIPCK(h, hipEventSynchronize(h->ev_stage));
-      if (h->eps_stage) HIPCK(h, hipHostFree(h->eps_stage));
-      h->eps_stage = nullptr; h->eps_stage_bytes = 0;
-      HIPCK(h, hipHostMalloc((void**)&h->eps_stage, bytes));
-      h->eps_stage_bytes = bytes;
-    }
-    if (!h->ev_stage) HIPCK(h, hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
-    else HIPCK(h, hipEventSynchronize(h->ev_stage));
+    // driver's 20-step command: 4 % of its time).
+    CACK(stage_reserve(h, bytes));
     memcpy(h->eps_stage, eps_stream, bytes);
-    HIPCK(h, hipMemcpyAsync(h->eps_dev, h->eps_stage, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCK(h, hipEventRecord(h->ev_stage, h->stream));
   } else {
     // counter-based stream: draws are independent, so a long run's worth (2 + 2 max_iter draws) is generated by several
     // host threads -- same values whatever the thread count -- straight into a pinned staging buffer the engine keeps
     // (pageable memory cost 1.5 ms of copy for 8 MB; with 16 threads the 402 draws of a default fit took 3.3 ms in all)
-    const size_t bytes = (size_t)need * per * sizeof(float);
-    if (h->ev_stage) HIPCK(h, hipEventSynchronize(h->ev_stage));   // the copy that last read the buffer is done BEFORE it is freed or refilled
-    if (bytes > h->eps_stage_bytes) {
-      if (h->eps_stage) HIPCK(h, hipHostFree(h->eps_stage));
-      h->eps_stage = nullptr; h->eps_stage_bytes = 0;
-      HIPCK(h, hipHostMalloc((void**)&h->eps_stage, bytes));
-      h->eps_stage_bytes = bytes;
-    }
+    CACK(stage_reserve(h, bytes));
     float* out = h->eps_stage;
     const int64_t nt = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(need / 4, 48), (int64_t)std::thread::hardware_concurrency() / 2));
     if (nt > 1 && need * per >= (1 << 16)) {
@@ -1534,16 +1111,10 @@ int stage_eps(ca_engine* h, const float* eps_stream, int64_t have, int64_t need)
       for (int64_t d = 0; d < need; ++d) ca_philox::normal_draw(h->opt.seed, h->draw + d, per, out + d * per);
     }
     h->draw += need;
-    HIPCK(h, hipMemcpyAsync(h->eps_dev, out, bytes, hipMemcpyHostToDevice, h->stream));
-    if (!h->ev_stage) HIPCK(h, hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
-    HIPCK(h, hipEventRecord(h->ev_stage, h->stream));
   }
-  return CA_OK;
-}
-
-int read_doubles(ca_engine* h, const double* dev, double* out, int n) {
-  HIPCK(h, hipMemcpyAsync(h->host_pinned, dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  SYNC(h);
-  for (int i = 0; i < n; ++i) out[i] = h->host_pinned[i];
+  // the copy, and behind it the event the next call waits for before it touches the buffer
+  HIPCK(h, hipMemcpyAsync(h->eps_dev, h->eps_stage, bytes, hipMemcpyHostToDevice, h->stream));
+  if (!h->ev_stage) HIPCK(h, hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+  HIPCK(h, hipEventRecord(h->ev_stage, h->stream));
   return CA_OK;
 }

@@ -1,4 +1,4 @@
-// ca_eng_state.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): engine state (struct ca_engine), error / launch macros, profiling wrappers, variant switches, template dispatch of the VALU sweeps.
+// ca_eng_state.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): engine state (struct ca_engine), error / launch macros, profiling wrappers, variant switches, template dispatch of the VALU sweeps and of the vector count-matrix stream, host matrix helpers.
 namespace {
 
 thread_local std::string g_last_error;
@@ -73,7 +73,7 @@ struct ca_engine {
   hipStream_t stream3 = nullptr;   // (highest priority)
   hipEvent_t ev_poly0 = nullptr, ev_poly1 = nullptr;
   bool poly_xmax_ready = false; float* poly_xpart = nullptr;   // series form: the merged update that made the current state left max |psi| per 256-cell piece (ca_merge_args::xpart)
-  bool ys_defer_next = false;   // series form: the next one-copy stream launch leaves its finisher pending (it rides on the cell launch)   // series form: the moment launches on the side stream beside the count-matrix stream's launch
+  bool ys_defer_next = false;   // series form: the next one-copy stream launch leaves its finisher pending (it rides on the cell launch)
   std::string err;
   std::vector<void*> allocs;
   int64_t dev_bytes = 0;
@@ -470,20 +470,61 @@ void launch_bwd(int RG, int nc, dim3 grid, hipStream_t st, const BwdArgs& a) {
   else bwd_rg<4>(nc, grid, st, a);
 }
 
-template <typename YT>
-void ypass_t(ca_engine* h, int koff, int kk, dim3 grid, const ca_ovf_args& ovf) {
-  const YT* Y = (const YT*)h->Y;
+// ---- the vector count-matrix stream (k_ypass<YT, KK, TF>) ---------------------------------
+// kk (1 .. 4) columns from `koff` on of the row products Y'.V -> YWp and of the column products Y'^T.F -> YTp, Y' = the stored counts under value transform TF
+// (0 in the fit; the PCA initialisation's, ca_k_stream.hip.h); the overflow list's per-entry work as extra blocks behind the stream's `grid`
+struct ca_ypass_ops { const float* F; int Dstride; const float* V; float *YWp, *YTp; int K; };
+template <typename YT, int TF>
+void ypass_t(ca_engine* h, const ca_ypass_ops& p, int koff, int kk, dim3 grid, const ca_ovf_args& ovf) {
   const int nb_main = grid.x;
   grid.x += ovf.nb_rows + ovf.nb_chunks;
-#define CA_YP(KK)                                                                                                        \
-  hipLaunchKernelGGL((k_ypass<YT, KK>), grid, dim3(CA_TB), 0, h->stream, Y, h->F, h->D, h->V, koff, h->YWpart, h->YTpart, \
-                     h->N, h->G, h->Gp, h->nseg, h->nrb, h->TR, h->K, ovf, nb_main)
+  auto go = [&](auto kc) {
+    hipLaunchKernelGGL((k_ypass<YT, decltype(kc)::value, TF>), grid, dim3(CA_TB), 0, h->stream, (const YT*)h->Y, p.F, p.Dstride, p.V, koff, p.YWp, p.YTp, h->N, h->G,
+                       h->Gp, h->nseg, h->nrb, h->TR, p.K, ovf, nb_main);
+  };
   switch (kk) {
-    case 1: CA_YP(1); break;
-    case 2: CA_YP(2); break;
-    case 3: CA_YP(3); break;
-    default: CA_YP(4); break;
+    case 1: go(std::integral_constant<int, 1>()); break;
+    case 2: go(std::integral_constant<int, 2>()); break;
+    case 3: go(std::integral_constant<int, 3>()); break;
+    default: go(std::integral_constant<int, 4>()); break;
   }
-#undef CA_YP
+}
+template <int TF>
+void ypass(ca_engine* h, const ca_ypass_ops& p, int koff, int kk, dim3 grid, const ca_ovf_args& ovf) {
+  if (h->ystore == CA_YSTORE_U8) ypass_t<uint8_t, TF>(h, p, koff, kk, grid, ovf);
+  else if (h->ystore == CA_YSTORE_U16) ypass_t<uint16_t, TF>(h, p, koff, kk, grid, ovf);
+  else ypass_t<float, TF>(h, p, koff, kk, grid, ovf);
+}
+
+// ---- host matrix helpers ------------------------------------------------------------------
+// element (r, c) of an R x Cn host matrix in the problem's layout
+inline int64_t hidx(int layout, int64_t r, int64_t c, int64_t R, int64_t Cn) {
+  return layout == CA_COL_MAJOR ? c * R + r : r * Cn + c;
+}
+
+int upload_f(ca_engine* h, float* dst, const std::vector<float>& v) {
+  if (v.empty()) return CA_OK;
+  HIPCK(h, hipMemcpyAsync(dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  SYNC(h);
+  return CA_OK;
+}
+int upload_d(ca_engine* h, double* dst, const std::vector<double>& v) {
+  if (v.empty()) return CA_OK;
+  HIPCK(h, hipMemcpyAsync(dst, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  SYNC(h);
+  return CA_OK;
+}
+int download_f(ca_engine* h, std::vector<float>& v, const float* src, int64_t n) {
+  v.resize((size_t)n);
+  if (n == 0) return CA_OK;
+  HIPCK(h, hipMemcpyAsync(v.data(), src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  SYNC(h);
+  return CA_OK;
+}
+int read_doubles(ca_engine* h, const double* dev, double* out, int n) {
+  HIPCK(h, hipMemcpyAsync(h->host_pinned, dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  SYNC(h);
+  for (int i = 0; i < n; ++i) out[i] = h->host_pinned[i];
+  return CA_OK;
 }
 

@@ -24,8 +24,10 @@
 #include "ca_poly.h"
 #include "philox_host.h"
 
-#include "ca_eng_state.inc"   // engine state (struct ca_engine), error / launch macros, profiling wrappers, variant switches, template dispatch of the VALU sweeps
-#include "ca_eng_loop.inc"   // the loop: host matrix helpers, count-matrix products per parameter state, transports' all-reduce, backward / update halves, plain and fused passes (sweeps or series form), eps staging
+#include "ca_eng_state.inc"   // engine state (struct ca_engine), error / launch macros, profiling wrappers, variant switches, template dispatch of the VALU sweeps and of the vector count-matrix stream, host matrix helpers
+#include "ca_eng_launch.inc"   // one launch site per templated kernel family of the loop (matrix-core sweeps, fused forward sweeps and their riding streams, cell epilogues): the argument list once, the instantiation picked from the engine's picks
+#include "ca_eng_reduce.inc"   // the transports' all-reduce of a device vector (peer-to-peer launch with its riders, host callback, RCCL)
+#include "ca_eng_loop.inc"   // the loop: count-matrix products per parameter state, backward / update halves, plain and fused passes (sweeps or series form), the host's waits, eps staging
 #include "ca_eng_ingest.inc"   // ingestion: storage scan and conversion, selection gather, host -> device pipeline (float64 narrowed on the host), fit constants
 #include "ca_eng_create.inc"   // create_impl: buffers, decomposition picks (every threshold measured: DESIGN.md section 5), setup sums; find_param
 }  // namespace
@@ -387,7 +389,7 @@ int ca_synchronize(ca_handle h) {
   return CA_OK;
 }
 
-#include "ca_eng_comm.inc"   // C ABI, transports: RCCL communicator, one-shot peer-to-peer set-up (two-phase), benchmark, known-answer test, host callback
+#include "ca_eng_comm.inc"   // C ABI, transports: setup sums over all ranks, RCCL communicator, one-shot peer-to-peer set-up (two-phase), benchmark, known-answer test, host callback
 static int stage_one(ca_handle h, const float* eps) { return stage_eps(h, eps, 1, 1); }
 
 int ca_gamma_init(ca_handle h, const float* eps) {
@@ -643,7 +645,7 @@ int ca_final_elbo(ca_handle h, int32_t n_rep, const float* eps_stream, int64_t n
   return CA_OK;
 }
 
-#include "ca_eng_init.inc"   // C ABI, once per fit on the resident matrix: PCA initialisation of psi (blocked subspace iteration), per-clone gene sums
+#include "ca_eng_init.inc"   // C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums
 static int get_generic(ca_handle h, const char* name, double* out, bool grad) {
   if (!h || !name || !out) return CA_ERR_INVALID;
   HIPCK(h, hipSetDevice(h->device));
