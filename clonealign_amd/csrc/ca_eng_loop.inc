@@ -142,16 +142,22 @@ int ys_finish(ca_engine* h, bool defer = false) {
   h->ycache_valid = true;
   return CA_OK;
 }
+// (h->mom_args set: the series form's forward moments ride as the launch's first blocks, ca_polymom.hip.h -- taken here, so that the caller can tell)
 template <bool Y4>
 void launch_ys(ca_engine* h) {
   constexpr int lds = Y4 ? CA_YS4_LDS_BYTES : CA_YS_LDS_BYTES;
   const int nb_main = h->ys_nrg * h->ys_nseg;
+  const ca_pm_args* pm = h->mom_args;
+  h->mom_args = nullptr;
+  const int nmom = pm ? pm->nmb + pm->nred : 0;
   if (h->n_ovf > 0) {   // (the overflow list's blocks behind the stream's)
     const ca_ovf_args ovf = ys_ovf(h);
-    hipLaunchKernelGGL(k_ys_mfma_ovf<Y4>, dim3(nb_main + ovf.nb_rows + ovf.nb_chunks), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS,
-                       nb_main, ovf, h->F, h->V, h->D);
+    const dim3 grid(nmom + nb_main + ovf.nb_rows + ovf.nb_chunks);
+    if (pm) hipLaunchKernelGGL(k_ys_mfma_ovf_mom<Y4>, grid, dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D, *pm);
+    else hipLaunchKernelGGL(k_ys_mfma_ovf<Y4>, grid, dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D);
   } else {
-    hipLaunchKernelGGL(k_ys_mfma<Y4>, dim3(nb_main), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS);
+    if (pm) hipLaunchKernelGGL(k_ys_mfma_mom<Y4>, dim3(nmom + nb_main), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, *pm);
+    else hipLaunchKernelGGL(k_ys_mfma<Y4>, dim3(nb_main), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS);
   }
 }
 int ycache_ys(ca_engine* h) {
@@ -817,9 +823,8 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
   if (series) {
     // Z of both draws from the moments of M over gene bins (ca_poly.hip), the same cell epilogue, d/dF and the backward moments in one pass over
     // the CELLS: no cells x genes sweep.  The count-matrix products of this state run as their own launch (in line).
-    // Order: the three small moment launches FIRST, on an empty device (they are chains of memory latencies: beside the stream's blocks they took twice
-    // as long, and the cell launch waits for them); THEN the count-matrix stream goes to the side stream (deferred since the update: poly_y_defer) and runs
-    // beside the cell launch, which is arithmetic.
+    // Order: the forward moments ride as the first blocks of the count-matrix stream's launch (CA_VAR_MOM_RIDE, below); where they cannot, their launches come
+    // FIRST, on an empty device, and the stream's launch behind them (lab, poly_side: on the side stream beside the cell launch, deferred since the update).
     cp.etamax2 = h->poly_zero; cp.coefq = nullptr; cp.vmm_at = nullptr; cp.etamax_w = nullptr;
     ca_xsrc xs_m;
     CACK(poly_xsrc(h, &xs_m));
@@ -833,17 +838,39 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
       HIPCK(h, hipStreamWaitEvent(h->stream3, h->ev_poly0, 0));
       std::swap(h->stream, h->stream3);
     }
-    CACK(prof_begin(h, CA_KERNEL_FWD));
-    hipError_t e = ca_poly_moments(h->stream, &h->pws, h->V, h->F, h->mu32, h->mu32B, h->Lb, h->G, h->N, h->C,
-                                   h->host_dev ? reinterpret_cast<unsigned int*>(h->host_dev + 42) : nullptr, pl_mirror, pl_seq,
-                                   xs_m.xpart, xs_m.nx, xs_m.xglob, xs_m.nglob, xs_m.xadd);
-    int pe = (e == hipSuccess) ? prof_end(h) : CA_OK;   // (both events of the pair on the stream the chain ran on)
-    if (moments_aside) {
-      if (e == hipSuccess) e = hipEventRecord(h->ev_poly1, h->stream);
-      std::swap(h->stream, h->stream3);
+    // CA_VAR_MOM_RIDE: the moments as the moment role of the count-matrix stream's launch (ca_polymom.hip.h) -- the stream reads the count matrix and the W / psi
+    // images, the moments V, mu, L and max |psi|: neither reads what the other writes, and as blocks of one launch they need no event between them.  Wherever this
+    // pass launches no stream in line (its products are cached, or go to a side stream), or max |psi| would need a launch of its own, the moments keep theirs.
+    hipError_t e = hipSuccess;
+    ca_pm_args pm;
+    const bool mom_rides = h->mom_ride && h->y_ys && !h->ycache_valid && !h->poly_side && !moments_aside && !h->y_defer && !h->y_pending && h->host_dev &&
+                           ((xs_m.xpart && xs_m.nx > 0) || (xs_m.xglob && xs_m.nglob > 0));
+    if (mom_rides) {
+      memset(&pm, 0, sizeof(pm));
+      const int nglob = xs_m.xglob ? xs_m.nglob : 0;
+      pm.V = h->V; pm.xbits = h->pws.xbits; pm.muA = h->mu32; pm.muB = h->mu32B; pm.Lb = h->Lb; pm.G = h->G; pm.C = h->C;
+      pm.hdr = h->pws.hdr; pm.part = h->pws.partB; pm.bad_word = reinterpret_cast<unsigned int*>(h->host_dev + 42); pm.mirror = pl_mirror; pm.seq = pl_seq;
+      pm.xpart = xs_m.xpart; pm.nx = (nglob || !xs_m.xpart) ? 0 : xs_m.nx; pm.xglob = xs_m.xglob; pm.nglob = nglob; pm.xadd = xs_m.xadd;
+      pm.tabB = h->pws.tabB; pm.flags = h->pws.mflags;
+      if (++h->mom_tag == 0u) h->mom_tag = 1u;
+      pm.tag = h->mom_tag;
+      pm.ngrp = h->pws.n_gene_blocks; pm.per = CA_MOM_PER; pm.nmb = (int)cdiv(pm.ngrp, pm.per); pm.nred = CA_MOM_NRED;
+      pm.timeout_ticks = 50000000ull;   // 0.5 s: every block a reducer waits for was dispatched before it and depends on nobody
+      pm.err = reinterpret_cast<unsigned int*>(h->host_dev + 43);
+      h->mom_args = &pm;
+    } else {
+      CACK(prof_begin(h, CA_KERNEL_FWD));
+      e = ca_poly_moments(h->stream, &h->pws, h->V, h->F, h->mu32, h->mu32B, h->Lb, h->G, h->N, h->C,
+                          h->host_dev ? reinterpret_cast<unsigned int*>(h->host_dev + 42) : nullptr, pl_mirror, pl_seq,
+                          xs_m.xpart, xs_m.nx, xs_m.xglob, xs_m.nglob, xs_m.xadd);
+      int pe = (e == hipSuccess) ? prof_end(h) : CA_OK;   // (both events of the pair on the stream the chain ran on)
+      if (moments_aside) {
+        if (e == hipSuccess) e = hipEventRecord(h->ev_poly1, h->stream);
+        std::swap(h->stream, h->stream3);
+      }
+      HIPCK(h, e);
+      CACK(pe);
     }
-    HIPCK(h, e);
-    CACK(pe);
     if (h->poly_side && h->poly_y_defer && !h->ycache_valid) {
       h->poly_y_defer = false;
       HIPCK(h, hipEventRecord(h->ev_params, h->stream));
@@ -853,7 +880,11 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     //  per iteration at cfg-3, 110 against 102 at 50k x 3k x 6)
     // ... nor as its own launch in line (5.4 us and a gap): its jobs ride as extra blocks of the cell launch, as they do on the backward sweep's
     h->ys_defer_next = h->y_ys && !h->ycache_valid && h->opt.reserved[1] != 3;   // (reserved[1] = 3: the finisher as a launch of its own, lab)
-    CACK(ensure_ycache(h));
+    const int yrc = ensure_ycache(h);
+    const bool mom_left = h->mom_args != nullptr;
+    h->mom_args = nullptr;   // (pm leaves scope with this pass)
+    CACK(yrc);
+    if (mom_left) { h->err = "internal: the series form's moments were to ride on a count-matrix stream launch that was not made"; return CA_ERR_STATE; }
     h->ys_defer_next = false;
     ca_yfin_args yfin_ride;
     const bool yfin_rides = h->yfin_pending;

@@ -156,6 +156,9 @@ struct ca_engine {
   // that deep) and the bound of an Adam step -- a deterministic decision, the same on every run, and never a truncated series
   int64_t n_series = 0, n_series_fallback = 0;
   double *poly_ring = nullptr, *poly_ring_dev = nullptr; uint64_t poly_seq = 0, poly_seq_base = 1, adam_steps = 0, poly_steps_at[16] = {};
+  // the series form's forward moments as the moment role of its count-matrix stream's launch (CA_VAR_MOM_RIDE, ca_polymom.hip.h): the pick, the launch tag, and the
+  // arguments of the pass being queued (run_fused sets them, the stream's launch site takes them)
+  bool mom_ride = false; unsigned mom_tag = 0; const ca_pm_args* mom_args = nullptr;
   bool poly = false, poly_side = false, poly_y_defer = false, poly_fresh = false, poly_df = false /* the last backward half was the series form's: d/dF is ONE slab */; ca_poly_ws pws; float* poly_zero = nullptr; unsigned char* poly_mem = nullptr;
   float *Mb2 = nullptr, *mu32B = nullptr, *Zpart2 = nullptr; double* gene_partB = nullptr;
   bool y_defer = false;
@@ -237,6 +240,10 @@ namespace {
 int comm_check(ca_engine* h) {
   if (h->host_pinned && *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 41) != 0u) {
     h->err = "a forward-sweep block gave up waiting for a chunk of a left-over tile (k_fwd_bal_ys); the engine's state is undefined";
+    return CA_ERR_STATE;
+  }
+  if (h->host_pinned && *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 43) != 0u) {
+    h->err = "a reducer block of the series form's moment role gave up waiting for the moment blocks of its launch (k_ys_mfma_mom); the engine's state is undefined";
     return CA_ERR_STATE;
   }
   if (h->host_pinned && *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 42) != 0u) {

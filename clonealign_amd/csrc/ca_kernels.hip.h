@@ -835,6 +835,36 @@ __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_y
   ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 
+// The series form's forward moments RIDING on its count-matrix stream's launch (CA_VAR_MOM_RIDE): blocks 0 .. nmb + nred - 1 are the moment role
+// (ca_polymom.hip.h: moment blocks, then their reducers), dispatched first, so that they hold slots before the stream's blocks fill the chip; the stream's
+// blocks follow with their index moved down by that many -- nothing else of the stream changes (same body, same register budget, same dynamic LDS, out of
+// which the moment role carves its tables).  Neither role reads what the other writes.
+#include "ca_polymom.hip.h"
+static_assert(sizeof(ca_pm_lds) <= (size_t)CA_YS_LDS_BYTES && sizeof(ca_pm_lds) <= (size_t)CA_YS4_LDS_BYTES, "the moment role's tables fit the stream's dynamic LDS");
+template <bool Y4>
+__global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_mom(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS, ca_pm_args pm) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];   // Y4: CA_YS4_LDS_BYTES, else CA_YS_LDS_BYTES
+  const int nmom = pm.nmb + pm.nred;
+  if ((int)blockIdx.x < nmom) { ca_pm_ride_block<CA_YM_TB>(pm, (int)blockIdx.x, ca_ys_dyn); return; }
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x - nmom, Ys, io, N, Gp, RS, ca_ys_dyn);
+}
+template <bool Y4>
+__global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_ovf_mom(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS,
+                                                                           int nb_main, ca_ovf_args ovf, const float* __restrict__ F,
+                                                                           const float* __restrict__ V, int Dstride, ca_pm_args pm) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];
+  const int nmom = pm.nmb + pm.nred;
+  if ((int)blockIdx.x < nmom) { ca_pm_ride_block<CA_YM_TB>(pm, (int)blockIdx.x, ca_ys_dyn); return; }
+  const int blk = (int)blockIdx.x - nmom;
+  if (blk >= nb_main) {
+    const int b = blk - nb_main;
+    if (b < ovf.nb_rows) ca_ovf_rows_body(b, ovf.rowptr, ovf.col, ovf.val, V, Dstride, ovf.YWextra, N, 1, 0);
+    else ca_ovf_chunks_body(b - ovf.nb_rows, ovf.chunk_start, ovf.row2, ovf.val2, F, Dstride, ovf.csum, ovf.nchunk, 1, 0);
+    return;
+  }
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>(blk, Ys, io, N, Gp, RS, ca_ys_dyn);
+}
+
 // The one-copy int8 matrix-core stream RIDING on the forward sweep's launch (round 3).  The vector stream of k_fwd_cell_mix_y
 // spends 3.5 vector instructions per count in a launch whose vector pipes are full (profiles/r02_v2_sq_counters.json: 44 % of
 // the merged launch's VALU instructions are the stream's), and a matrix-core instruction occupies the same issue pipe as the

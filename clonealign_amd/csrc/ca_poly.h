@@ -14,7 +14,7 @@
 
 struct ca_poly_hdr { double vlo, delta, xmax; int nb, bad; };
 struct ca_poly_ws {
-  ca_poly_hdr* hdr; unsigned int* xbits; double *tabB, *partB, *tabQ, *Qpart;
+  ca_poly_hdr* hdr; unsigned int* xbits; unsigned int* mflags /* [n_gene_blocks] */; double *tabB, *partB, *tabQ, *Qpart;
   int n_cell_blocks, n_gene_blocks;
 };
 

@@ -28,8 +28,9 @@ namespace ca_series {   // (a namespace of its own: the header's kernels get nam
 #include "ca_kernels.hip.h"   // the cell epilogue and its helpers (this unit instantiates only what it launches)
 
 constexpr int R = CA_PL_R, NB = CA_PL_NB;
+#include "ca_polymom.hip.h"     // the moments' bodies: one copy of the arithmetic for these kernels and for the stream launch's moment role
 constexpr int TB_B = 384;       // k_poly_B block: one thread per (k, column) output (21 x 16 = 336)
-constexpr int GPB = 32;         // genes per k_poly_B block
+constexpr int GPB = CA_PM_GPB;  // genes per k_poly_B block
 
 __device__ __forceinline__ float warp_max(float v) {
 #pragma unroll
@@ -40,15 +41,6 @@ __device__ __forceinline__ float warp_min(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
   return v;
-}
-
-// the ranges of one parameter state, for the host's look ahead (ca_poly_guard in the engine): values first, the sequence number last
-__device__ __forceinline__ void ca_poly_mirror_store(double* m, double seq, double xmax, double vlo, double vhi) {
-  __hip_atomic_store(m + 1, xmax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(m + 2, vlo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __hip_atomic_store(m + 3, vhi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __threadfence_system();
-  __hip_atomic_store(m, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ---- K0: max |x| over the cells (an order-preserving unsigned maximum: exact whatever the order); k_poly_red resets the word behind its reader ------------
@@ -105,115 +97,12 @@ __global__ void __launch_bounds__(CA_TB) k_poly_ranges(const float* __restrict__
   }
 }
 
-// ---- K1: bin geometry (every block makes the same one: min / max are exact in any order) and the forward moments ----------------------------------
+// ---- K1: bin geometry and the forward moments: the body is ca_pm_B_body (ca_polymom.hip.h), shared with the moment role of the count-matrix stream's launch ----
 // part[blk][b][k][col] block partials (the 1 / k! inside the powers), summed in block order by k_poly_red into tabB[b][k][col].
-// col: draw A clones 0..7 | draw B clones 0..7.  (The blocks of one launch share nothing: the XCDs' L2s are not coherent with each other, and a
-// device-scope fence per block costs more than the kernel boundary the reduction gets for free.)
-__global__ void __launch_bounds__(TB_B) k_poly_B(const float* __restrict__ V, const unsigned int* __restrict__ xbits, const float* __restrict__ muA,
-                                                 const float* __restrict__ muB, const float* __restrict__ Lb /*[G][8]*/, int G, int C,
-                                                 ca_poly_hdr* __restrict__ hdr, double* __restrict__ part, unsigned int* __restrict__ bad_word,
-                                                 double* __restrict__ mirror /* mapped host ring slot {seq, xmax, vlo, vhi} or null */, double seq,
-                                                 const float* __restrict__ xpart /* nx > 0: max |x| per piece of cells (the merged update's), instead of *xbits */, int nx,
-                                                 const double* __restrict__ xglob, int nglob, double xadd) {
-  __shared__ float smn[TB_B / 64], smx[TB_B / 64], sxm[TB_B / 64];
-  __shared__ double pw[GPB][R + 1];
-  __shared__ double Mg[GPB][16];
-  __shared__ int binof[GPB];
-  __shared__ unsigned int present[(NB + 31) / 32];
-  const int t = threadIdx.x;
-  float mn = INFINITY, mx = -INFINITY;
-  {   // (eight loads in flight: a load per iteration waited for the one before -- 0.5 us each)
-    constexpr int U = 8;
-    for (int g0_ = 0; g0_ < G; g0_ += TB_B * U) {
-      float v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) { const int g = g0_ + u * TB_B + t; v[u] = V[g < G ? g : G - 1]; }
-#pragma unroll
-      for (int u = 0; u < U; ++u) { mn = fminf(mn, v[u]); mx = fmaxf(mx, v[u]); }
-    }
-  }
-  float xm = 0.f;
-  {
-    constexpr int U = 4;
-    for (int i0 = 0; i0 < nx; i0 += TB_B * U) {
-      float v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) { const int i = i0 + u * TB_B + t; v[u] = xpart[i < nx ? i : nx - 1]; }
-#pragma unroll
-      for (int u = 0; u < U; ++u) xm = fmaxf(xm, v[u]);
-    }
-  }
-  mn = warp_min(mn); mx = warp_max(mx); xm = warp_max(xm);
-  if ((t & 63) == 0) { smn[t >> 6] = mn; smx[t >> 6] = mx; sxm[t >> 6] = xm; }
-  if (t < (NB + 31) / 32) present[t] = 0u;
-  __syncthreads();
-  mn = smn[0]; mx = smx[0]; xm = sxm[0];
-#pragma unroll
-  for (int w_ = 1; w_ < TB_B / 64; ++w_) { mn = fminf(mn, smn[w_]); mx = fmaxf(mx, smx[w_]); xm = fmaxf(xm, sxm[w_]); }
-  double xmax = nx > 0 ? (double)xm : (double)__uint_as_float(*xbits);
-  if (nglob > 0) { xmax = 0.0; for (int r = 0; r < nglob; ++r) xmax = fmax(xmax, xglob[r]); xmax += xadd; }   // (uniform; a handful of ranks)
-  const double vlo = (double)mn, width = (double)mx - (double)mn;
-  int nb = (int)ceil(xmax * width / (2.0 * CA_PL_A));
-  nb = nb < 1 ? 1 : (nb > NB ? NB : nb);
-  const double delta = width > 0.0 ? width / nb : 1.0;
-  // (all loadings equal -- W = 0 at the start of every fit -- is one bin of width zero: any |x| is covered)
-  const int bad = !(xmax * (width > 0.0 ? delta : 0.0) * 0.5 <= CA_PL_A * 1.25) || !isfinite(xmax) || !isfinite(width);
-  if (blockIdx.x == 0 && t == 0) {
-    hdr->vlo = vlo; hdr->delta = delta; hdr->xmax = xmax; hdr->nb = nb;
-    if (bad) { hdr->bad = 1; if (bad_word) __hip_atomic_store(bad_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }   // (the host looks at its next synchronisation)
-    if (mirror) ca_poly_mirror_store(mirror, seq, xmax, vlo, (double)mx);
-  }
-  // this block's genes: bin, powers of (v - v_b) over k!, the sixteen M columns
-  const int g0 = blockIdx.x * GPB;
-  if (t < GPB) {
-    const int g = g0 + t;
-    if (g < G) {
-      const double v = (double)V[g];
-      int b = (int)floor((v - vlo) / delta);
-      b = b < 0 ? 0 : (b >= nb ? nb - 1 : b);
-      binof[t] = b;
-      atomicOr(&present[b >> 5], 1u << (b & 31));
-      const double dv = v - (vlo + ((double)b + 0.5) * delta);
-      double p = 1.0;
-#pragma unroll
-      for (int k = 0; k <= R; ++k) { pw[t][k] = p; p = p * dv * (1.0 / (double)(k + 1)); }   // (the reciprocals are compile-time constants)
-      const double ma = (double)muA[g], mb = (double)muB[g];
-      for (int c = 0; c < 8; ++c) {
-        const double l = c < C ? (double)Lb[(int64_t)g * CA_CW + c] : 0.0;
-        Mg[t][c] = ma * l; Mg[t][8 + c] = mb * l;
-      }
-    } else binof[t] = -1;
-  }
-  __syncthreads();
-  const int ng = min(GPB, G - g0);
-  constexpr int NO = (R + 1) * 16;
-  double* mine = part + (int64_t)blockIdx.x * NB * NO;
-  if (t < NO) {
-    const int k = t >> 4, col = t & 15;
-    // ONE pass over the block's genes for the first four bins (the usual case is one to three): four accumulators, genes in order
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    if (nb == 1) {   // (uniform: one bin, no selects)
-#pragma unroll 8
-      for (int i = 0; i < ng; ++i) a0 += pw[i][k] * Mg[i][col];
-    } else {
-#pragma unroll 4
-      for (int i = 0; i < ng; ++i) {
-        const double pr = pw[i][k] * Mg[i][col];
-        const int bi = binof[i];
-        a0 += bi == 0 ? pr : 0.0; a1 += bi == 1 ? pr : 0.0; a2 += bi == 2 ? pr : 0.0; a3 += bi == 3 ? pr : 0.0;
-      }
-    }
-    mine[0 * NO + t] = a0;
-    if (nb > 1) mine[1 * NO + t] = a1;
-    if (nb > 2) mine[2 * NO + t] = a2;
-    if (nb > 3) mine[3 * NO + t] = a3;
-    for (int b = 4; b < nb; ++b) {          // (a wide exponent range)
-      double acc = 0.0;
-      if ((present[b >> 5] >> (b & 31)) & 1u)
-        for (int i = 0; i < ng; ++i) acc += binof[i] == b ? pw[i][k] * Mg[i][col] : 0.0;
-      mine[(int64_t)b * NO + t] = acc;
-    }
-  }
+// col: draw A clones 0..7 | draw B clones 0..7.  (As launches of their own the blocks share nothing: the kernel boundary hands the partials to the reduction.)
+__global__ void __launch_bounds__(TB_B) k_poly_B(ca_pm_args a) {
+  __shared__ ca_pm_lds s;
+  ca_pm_B_body<TB_B, false>(a, (int)blockIdx.x, 1, blockIdx.x == 0, s);
 }
 
 // ---- K2: per cell: Z for both draws and dZ/dx for the train draw by Horner over the bins, the cell epilogue, d/dF, the backward moments --------------
@@ -362,29 +251,7 @@ __global__ void __launch_bounds__(CA_TB) k_poly_red(const double* __restrict__ p
     return;
   }
   if (xbits && blockIdx.x == 0 && threadIdx.x == 0) *xbits = 0u;   // (its reader, k_poly_B, is complete: ready for the next state's maximum)
-  const int lane = threadIdx.x & 63, nwave = nred * (CA_TB / 64);
-  const int nout = hdr->nb * per_bin;
-  for (int j = blockIdx.x * (CA_TB / 64) + (threadIdx.x >> 6); j < nout; j += nwave) {
-    // (up to eight loads in flight per lane: a miss to another XCD's data costs a microsecond, a chain of them is the kernel)
-    double v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { const int blk = lane + 64 * u; v[u] = blk < nblk ? part[(int64_t)blk * stride + j] : 0.0; }
-    double a = 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) a += v[u];
-    for (int blk = lane + 512; blk < nblk; blk += 64) a += part[(int64_t)blk * stride + j];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-    if (lane == 0) {
-      if (mode == 1) {
-        const int k = (j / C) % (R + 2);
-        double f = 1.0;
-        for (int i = 2; i <= k; ++i) f *= (double)i;
-        a /= f;
-      }
-      out[j] = a;
-    }
-  }
+  ca_pm_red_body<false>(part, nblk, stride, hdr->nb * per_bin, mode, C, out, blockIdx.x * (CA_TB / 64) + (threadIdx.x >> 6), nred * (CA_TB / 64));
 }
 
 // ---- K3: per gene: the two gradient sums from its bin's polynomial ---------------------------------------------------------------------------------
@@ -447,7 +314,7 @@ using namespace ca_series;
 
 size_t ca_poly_workspace_bytes(int G, int n_cell_blocks) {
   const size_t nbg = (size_t)cdiv_i(G, GPB);
-  return sizeof(ca_poly_hdr) + 64 + sizeof(double) * ((size_t)NB * (R + 1) * 16 * (nbg + 1) + (size_t)NB * (R + 2) * 8 * ((size_t)n_cell_blocks + 1));
+  return sizeof(ca_poly_hdr) + 64 + ((nbg * sizeof(unsigned int) + 63) / 64) * 64 + sizeof(double) * ((size_t)NB * (R + 1) * 16 * (nbg + 1) + (size_t)NB * (R + 2) * 8 * ((size_t)n_cell_blocks + 1));
 }
 
 void ca_poly_bind(ca_poly_ws* w, void* base, int G, int n_cell_blocks) {
@@ -455,6 +322,7 @@ void ca_poly_bind(ca_poly_ws* w, void* base, int G, int n_cell_blocks) {
   w->hdr = reinterpret_cast<ca_poly_hdr*>(q); q += sizeof(ca_poly_hdr);
   w->xbits = reinterpret_cast<unsigned int*>(q); q += 64;
   const size_t nbg = (size_t)cdiv_i(G, GPB);
+  w->mflags = reinterpret_cast<unsigned int*>(q); q += ((nbg * sizeof(unsigned int) + 63) / 64) * 64;   // (the moment role's tags, ca_polymom.hip.h: zeroed with the workspace)
   w->tabB = reinterpret_cast<double*>(q); q += sizeof(double) * (size_t)NB * (R + 1) * 16;
   w->partB = reinterpret_cast<double*>(q); q += sizeof(double) * (size_t)NB * (R + 1) * 16 * nbg;
   w->tabQ = reinterpret_cast<double*>(q); q += sizeof(double) * (size_t)NB * (R + 2) * 8;
@@ -488,8 +356,11 @@ hipError_t ca_poly_moments(hipStream_t st, const ca_poly_ws* w, const float* V, 
   if (!xpart) nx = 0;
   if (!xglob) nglob = 0;
   if (nx == 0 && nglob == 0) hipLaunchKernelGGL(k_poly_xmax, dim3((unsigned)std::min<int64_t>(128, (N + 4 * CA_TB - 1) / (4 * CA_TB))), dim3(CA_TB), 0, st, F, N, w->xbits);
-  hipLaunchKernelGGL(k_poly_B, dim3(w->n_gene_blocks), dim3(TB_B), 0, st, V, w->xbits, muA, muB, Lb, G, C, w->hdr, w->partB, bad_word, mirror, seq, xpart, nglob ? 0 : nx,
-                     xglob, nglob, xadd);
+  ca_pm_args a;
+  memset(&a, 0, sizeof(a));
+  a.V = V; a.xbits = w->xbits; a.muA = muA; a.muB = muB; a.Lb = Lb; a.G = G; a.C = C; a.hdr = w->hdr; a.part = w->partB; a.bad_word = bad_word; a.mirror = mirror; a.seq = seq;
+  a.xpart = xpart; a.nx = nglob ? 0 : nx; a.xglob = xglob; a.nglob = nglob; a.xadd = xadd;
+  hipLaunchKernelGGL(k_poly_B, dim3(w->n_gene_blocks), dim3(TB_B), 0, st, a);
   {
     ca_small_args no_tail; memset(&no_tail, 0, sizeof(no_tail));
     ca_xslot_args no_xs; memset(&no_xs, 0, sizeof(no_xs));

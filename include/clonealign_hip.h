@@ -123,6 +123,9 @@ enum ca_variant {
   CA_VAR_Y4 = 1 << 22,        /* the one-copy stream's loop image at 4 bits per count (min(y, 15) in a nibble, the counts from 15 up as their exact excess in
                                  an escape list bucketed by the stream's own units): half the bytes per pass, the same integer sums; picked where the escapes
                                  are at most 1 in 64 counts (CA_VARX_Y4 forces it).  Off: the 1-byte loop image */
+  CA_VAR_MOM_RIDE = 1 << 23,  /* the series form's forward moments (bin geometry, per-group partials, their fixed-order sums) as the first blocks of its count-matrix
+                                 stream's launch instead of two launches in front of it: two launches and their boundaries less per iteration, the same additions
+                                 in the same order; on wherever the series form runs its stream in line.  Off: k_poly_B + k_poly_red, then the stream */
   CA_VAR_RIDE_SEQ = 1 << 13   /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
 /* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
@@ -215,6 +218,7 @@ typedef struct ca_info {
   int32_t y_stream_bits;     /* bits per count of the one-copy stream's loop image: 8, or 4 (CA_VAR_Y4); 0 where there is no loop image */
   int64_t series_passes;     /* fused passes of this engine that ran in the series form ... */
   int64_t series_fallbacks;  /* ... and those the look ahead at the exponent range (max|psi| (max W - min W), plus what the Adam steps since can add) gave to the sweeps */
+  int32_t mom_ride;          /* 1: the series form's forward moments ride on its count-matrix stream's launch (CA_VAR_MOM_RIDE) */
 } ca_info;
 enum ca_transport { CA_TRANSPORT_NONE = 0, CA_TRANSPORT_RCCL = 1, CA_TRANSPORT_HOST = 2, CA_TRANSPORT_P2P = 3 };
 
