@@ -106,6 +106,95 @@ def _is_sparse(a):
     return sps.issparse(a)
 
 
+def _fit_mse_host(Y, E, clone_idx, per_gene=False, chunk=4096):
+    """Float64 host form of ``HipEngine.fit_mse`` (R/clonealign.R:429-432), for engines without it: Y [N, G] dense or scipy.sparse (densified
+    ``chunk`` cells at a time), E [G, C] the predicted-expression table, ``clone_idx`` in [-1, C) with -1 = skip the cell.  Same return value."""
+    E = np.asarray(E, dtype=np.float64)
+    idx = np.asarray(clone_idx, dtype=np.int64).reshape(-1)
+    N, G = Y.shape
+    if E.shape[0] != G or idx.shape[0] != N:
+        raise ValueError(f"fit_mse: Y is {N} x {G}, E has {E.shape[0]} rows, clone_idx {idx.shape[0]} entries")
+    if idx.size and (idx.min() < -1 or idx.max() >= E.shape[1]):
+        raise ValueError(f"fit_mse: clone index outside [-1, {E.shape[1]})")
+    esum = E.sum(0)
+    used = np.flatnonzero(idx >= 0)
+    sse_gene = np.zeros(G)
+    for lo in range(0, used.size, int(chunk)):
+        rows = used[lo:lo + int(chunk)]
+        Yc = Y[rows]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+        a = Yc.sum(1) / esum[idx[rows]]                                  # normalizer, :429
+        r = E[:, idx[rows]].T * a[:, None] - Yc                          # :430-432
+        sse_gene += (r * r).sum(0)
+    sse = float(sse_gene.sum())
+    out = {"sse": sse, "n_cells": int(used.size), "mse": sse / (used.size * G) if used.size and G else float("nan")}
+    if per_gene:
+        out["sse_gene"] = sse_gene
+    return out
+
+
+def compute_ca_fit_mse(fit, Y, L, model_mu=False, random_clones=False, *, seed=None, drop_unassigned=False, per_gene=False,
+                       engine=None, engine_opts=None):
+    """Mean squared error of a clonealign fit on expression data under given clones, R/clonealign.R:415-434 (first five arguments as there):
+    ``mean((t(L[, clones]) * rowSums(Y) / colSums(L[, clones]) - Y)^2)``, with ``mu * L`` in place of ``L`` when ``model_mu``.
+
+    ``Y`` [cells, genes]: a dense array in any dtype the engine uploads, or a scipy.sparse matrix; it is evaluated on the device in one sweep
+    (``HipEngine.fit_mse``) and never densified or copied as float64 on the host.  ``engine``: a live engine whose resident matrix is ``Y`` (used as
+    it is); without it a throwaway engine is built for the upload and the fit constants only (``K=0``; ``engine_opts`` go to its constructor) and
+    closed afterwards.  An engine without ``fit_mse`` gets the float64 host form.
+    ``random_clones`` draws one label per cell, with replacement, from the distinct labels present, through ``numpy.random.default_rng(seed)``: the
+    reference uses R's ``sample()``, whose stream cannot be reproduced here, so the labels (not their distribution) differ from R's under any seed.
+    Cells labelled "unassigned": the reference fails on ``L[, "unassigned"]`` and so does this (ValueError) unless ``drop_unassigned=True``, which
+    skips them and takes the mean over the cells that are left.
+    Returns the MSE; with ``per_gene=True`` ``(mse, mse_gene[G])``, the same mean per gene."""
+    L, cn = _parse_cnv(L)
+    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else
+                                                                   [f"clone_{string.ascii_lowercase[i]}" for i in range(L.shape[1])])
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if L.shape[0] != G:
+        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    if len(names) != L.shape[1]:
+        raise ValueError(f"fit has {len(names)} clone names but L has {L.shape[1]} columns (clones)")
+    clones = np.asarray(fit["clone"], dtype=object).reshape(-1)
+    if random_clones:
+        distinct = list(dict.fromkeys(clones.tolist()))              # unique(), in order of first appearance (:420)
+        clones = np.asarray(distinct, dtype=object)[np.random.default_rng(seed).integers(0, len(distinct), size=N)]   # :421
+    if clones.shape[0] != N:
+        raise ValueError(f"fit has {clones.shape[0]} clone labels but Y has {N} rows (cells)")
+    lut = {c: i for i, c in enumerate(names)}
+    unknown = sorted({str(c) for c in clones if c not in lut and c != "unassigned"})
+    if unknown:
+        raise ValueError("clone labels that are no column of L: " + ", ".join(unknown))          # subscript out of bounds, :423
+    idx = np.array([lut.get(c, -1) for c in clones], dtype=np.int32)
+    if np.any(idx < 0) and not drop_unassigned:
+        raise ValueError(f"{int((idx < 0).sum())} cells are \"unassigned\", which is no column of L (the reference fails at L[, clones]); "
+                         "pass drop_unassigned=True to take the mean over the assigned cells")
+    E = L
+    if model_mu:
+        mu = np.asarray(fit["ml_params"]["mu"], dtype=np.float64).reshape(-1)                  # :426-427
+        if mu.shape[0] != G:
+            raise ValueError(f"fit$ml_params$mu has length {mu.shape[0]} but L has {G} rows: evaluate on the retained genes")
+        E = mu[:, None] * L
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    try:
+        if hasattr(engine, "fit_mse"):
+            if (engine.N, engine.G) != (N, G):
+                raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+            out = engine.fit_mse(idx, E, per_gene=per_gene)
+        else:
+            out = _fit_mse_host(Y, E, idx, per_gene=per_gene)
+    finally:
+        if own:
+            engine.close()
+    if per_gene:
+        return out["mse"], (out["sse_gene"] / out["n_cells"] if out["n_cells"] else np.full(G, np.nan))
+    return out["mse"]
+
+
 def _counts_array(a):
     """The count matrix in its own dtype when the engine can upload it as it is (no float64 copy of N x G), else float64.  A
     scipy.sparse matrix stays sparse (the engine takes its compressed arrays: engine.sparse_counts)."""
@@ -117,6 +206,13 @@ def _counts_array(a):
     if a.dtype.kind in "iu" and a.size and 0 <= a.min() and a.max() <= np.iinfo(np.int32).max:
         return a.astype(np.int32)            # e.g. numpy's default int64 counts: half the bytes of a float64 copy
     return a.astype(np.float64)
+
+
+def _fit_mse_result(plain, with_mu):
+    """``res["fit_mse"]`` of clonealign(fit_mse=True) from the two evaluations (E = L with its per-gene sums, E = mu * L)."""
+    n = plain["n_cells"]
+    return {"mse": plain["mse"], "mse_model_mu": with_mu["mse"],
+            "mse_gene": plain["sse_gene"] / n if n else np.full(plain["sse_gene"].shape, np.nan), "n_cells": n}
 
 
 def _parse_expression(gene_expression_data):
@@ -165,7 +261,8 @@ def clonealign(gene_expression_data, copy_number_data, max_iter=200, rel_tol=1e-
                cov=None, ref=None, fix_alpha=False, dtype="float32", saturate=True,
                saturation_threshold=6, K=None, mc_samples=1, verbose=True, initial_shrink=5,
                clone_call_probability=0.95, data_init_mu=True, *, seed=None, engine=None,
-               engine_opts=None, clone_names=None, allele_ref="cov", cell_index=None, gene_index=None, devices=None, _reuse=None):
+               engine_opts=None, clone_names=None, allele_ref="cov", cell_index=None, gene_index=None, devices=None, fit_mse=False,
+               _reuse=None):
     """Assign scRNA-seq cells to clones.  Arguments as R/clonealign.R:184-203.
 
     Keyword-only extras: ``allele_ref`` -- "cov" (default) reproduces the reference, which forwards ``ref = cov`` to
@@ -174,7 +271,9 @@ def clonealign(gene_expression_data, copy_number_data, max_iter=200, rel_tol=1e-
     index arrays from ``preprocess_for_clonealign(..., return_masks=True)``; the raw matrix is then fitted on that selection
     without a filtered copy (``copy_number_data`` etc. are given for the selected genes / cells).  ``devices``: HIP ordinals -- this ONE fit
     cell-sharded over those devices of this process (forwarded untouched to ``inference_tflow``; ``run_clonealign(devices=)`` is the
-    other thing: independent restarts dealt over devices)."""
+    other thing: independent restarts dealt over devices).  ``fit_mse=True``: the result gains ``res["fit_mse"] = {"mse", "mse_model_mu",
+    "mse_gene", "n_cells"}``, compute_ca_fit_mse() of the called clones on the retained genes (unassigned cells dropped; with ``L`` and with
+    ``mu * L``; the per-gene means are those of ``L``), taken on the still-resident matrix before the engine is closed (``HipEngine.fit_mse``)."""
     if allele_ref not in ("cov", "ref"):
         raise ValueError("allele_ref must be 'cov' (reference behaviour) or 'ref'")
     Y, gene_names = _parse_expression(gene_expression_data)
@@ -202,7 +301,7 @@ def clonealign(gene_expression_data, copy_number_data, max_iter=200, rel_tol=1e-
     if gene_names is None:
         gene_names = _default_gene_names(G)
     # NB the reference forwards ``ref = cov`` (R/clonealign.R:271); kept for drop-in behaviour
-    def _post(eng, rlist):
+    def _post(eng, rlist, keep):
         # device-side sums for compute_correlations: no second pass over Y on the host
         if not hasattr(eng, "clone_gene_sums"):
             return None
@@ -210,7 +309,13 @@ def clonealign(gene_expression_data, copy_number_data, max_iter=200, rel_tol=1e-
         lut = {c: i for i, c in enumerate(clone_names)}
         idx = np.array([lut.get(c, -1) for c in labels], dtype=np.int32)
         T, Syy = eng.clone_gene_sums(idx)
-        return dict(T=T, Syy=Syy, counts=np.bincount(idx[idx >= 0], minlength=C))
+        out = dict(T=T, Syy=Syy, counts=np.bincount(idx[idx >= 0], minlength=C))
+        if fit_mse and hasattr(eng, "fit_mse"):                      # compute_ca_fit_mse on the resident matrix, R/clonealign.R:415-434
+            Lk = L[np.asarray(keep, dtype=bool), :]
+            a = eng.fit_mse(idx, Lk, per_gene=True)
+            b = eng.fit_mse(idx, np.asarray(rlist["mu"], dtype=np.float64).reshape(-1, 1) * Lk)
+            out["fit_mse"] = _fit_mse_result(a, b)
+        return out
 
     res = inference_tflow(Y, L, max_iter=max_iter, rel_tol=rel_tol, learning_rate=learning_rate,
                           gene_filter_threshold=gene_filter_threshold, x=x,
@@ -228,15 +333,25 @@ def clonealign(gene_expression_data, copy_number_data, max_iter=200, rel_tol=1e-
     # its symbol with a retained one as kept, and L[keep] would then have more rows than the fitted matrix)
     keep = np.asarray(res.pop("retained_mask"), dtype=bool)
     post = res.pop("post", None)
+
+    def _host_selection():                                           # (engines without device sums fit small matrices only)
+        if _is_sparse(Y):
+            return Y.tocsr()[np.arange(Y.shape[0]) if sel_c is None else sel_c][:, np.arange(Y.shape[1]) if sel_g is None else sel_g].toarray()
+        return Y if (sel_c is None and sel_g is None) else Y[np.ix_(np.arange(Y.shape[0]) if sel_c is None else sel_c,
+                                                                    np.arange(Y.shape[1]) if sel_g is None else sel_g)]
     if post is not None:
         res["correlations"] = correlations_from_sums(post["T"], post["Syy"], L[keep, :], post["counts"])   # :292-294
     else:
-        if _is_sparse(Y):                                            # (engines without device sums fit small matrices only)
-            Ysel = Y.tocsr()[np.arange(Y.shape[0]) if sel_c is None else sel_c][:, np.arange(Y.shape[1]) if sel_g is None else sel_g].toarray()
-        else:
-            Ysel = Y if (sel_c is None and sel_g is None) else Y[np.ix_(np.arange(Y.shape[0]) if sel_c is None else sel_c,
-                                                                        np.arange(Y.shape[1]) if sel_g is None else sel_g)]
-        res["correlations"] = compute_correlations(Ysel[:, keep], L[keep, :], res["clone"], clone_names)   # :292-294
+        res["correlations"] = compute_correlations(_host_selection()[:, keep], L[keep, :], res["clone"], clone_names)   # :292-294
+    if fit_mse:
+        if post is not None and "fit_mse" in post:
+            res["fit_mse"] = post["fit_mse"]
+        else:                                                        # an engine without fit_mse: the float64 host form
+            lut = {c: i for i, c in enumerate(clone_names)}
+            idx = np.array([lut.get(c, -1) for c in res["clone"]], dtype=np.int32)
+            Yk, Lk = _host_selection()[:, keep], L[keep, :]
+            res["fit_mse"] = _fit_mse_result(_fit_mse_host(Yk, Lk, idx, per_gene=True),
+                                             _fit_mse_host(Yk, np.asarray(res["ml_params"]["mu"], dtype=np.float64).reshape(-1, 1) * Lk, idx))
     cor = res["correlations"]
     if np.any(~np.isnan(cor)):
         if np.nanquantile(cor, 0.25) < 0:                            # :296-300

@@ -1,4 +1,4 @@
-// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums.
+// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit (ca_fit_mse).
 extern "C++" {   // (templates: this part sits inside the C ABI's extern "C" block)
 namespace {
 // Transformed pass over Y with explicit factor buffers (PCA init): row products Y'.Vp -> YWp, column products Y'^T.Fp -> YTp
@@ -310,3 +310,104 @@ int ca_clone_gene_sums(ca_handle h, const int32_t* clone_of_cell, double* Tout, 
 #undef PCK
 }
 
+
+// sum of v[lo, hi) by halves: a fixed order whose error grows with log2 of the length
+static double pairwise_sum(const double* v, int64_t lo, int64_t hi) {
+  if (hi - lo <= 8) { double s = 0.0; for (int64_t i = lo; i < hi; ++i) s += v[i]; return s; }
+  const int64_t mid = lo + (hi - lo) / 2;
+  return pairwise_sum(v, lo, mid) + pairwise_sum(v, mid, hi);
+}
+
+// compute_ca_fit_mse (R/clonealign.R:415-434) on the resident matrix.  Reads the matrix, the row sums and the overflow list only: no wait for the loop's side
+// stream, no variable, Adam slot or draw index changes.  A sharded handle takes part in the collective even when ITS input is invalid (the flag travels
+// with the sums), so that every rank returns the same code instead of one of them leaving the others waiting.
+int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, double* sse_total, int64_t* n_cells_used, double* sse_gene, double* sse_cell) {
+  if (!h || !clone_of_cell || !E || !sse_total || !n_cells_used) return CA_ERR_INVALID;
+  CA_NOT_IN_RUN(h);
+  HIPCK(h, hipSetDevice(h->device));
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg;
+  std::string bad;
+  // the table: finite, clone-major and zero padded for the device, its column sums in gene order
+  std::vector<double> Et((size_t)C * Gp, 0.0), esum((size_t)C, 0.0);
+  for (int c = 0; c < C && bad.empty(); ++c)
+    for (int g = 0; g < G; ++g) {
+      const double v = E[hidx(h->layout, g, c, G, C)];
+      if (!std::isfinite(v)) { bad = "predicted expression has a non-finite entry (gene " + std::to_string(g) + ", clone " + std::to_string(c) + ")"; break; }
+      Et[(size_t)c * Gp + g] = v;
+      esum[(size_t)c] += v;
+    }
+  // the used cells, sorted by clone (stable: cells ascending within a clone)
+  std::vector<int64_t> start((size_t)C + 1, 0);
+  for (int64_t n = 0; n < N && bad.empty(); ++n) {
+    const int c = clone_of_cell[n];
+    if (c < -1 || c >= C) bad = "clone index " + std::to_string(c) + " of cell " + std::to_string(n) + " is outside [-1, " + std::to_string(C) + ")";
+    else if (c >= 0) start[(size_t)c + 1]++;
+  }
+  for (int c = 0; c < C && bad.empty(); ++c)
+    if (start[(size_t)c + 1] > 0 && (!std::isfinite(esum[(size_t)c]) || esum[(size_t)c] == 0.0))
+      bad = "predicted expression of clone " + std::to_string(c) + ", which is in use, sums to " + std::to_string(esum[(size_t)c]) + " over the genes";
+  if (!bad.empty() && !is_sharded(h)) { h->err = "ca_fit_mse: " + bad; return CA_ERR_INVALID; }
+  for (int c = 0; c < C; ++c) start[(size_t)c + 1] += start[(size_t)c];
+  const int64_t M = bad.empty() ? start[(size_t)C] : 0;
+  std::vector<double> gene((size_t)Gp, 0.0), cell;
+  int2* list_d = nullptr; ca_mse_row* meta = nullptr; double *Et_d = nullptr, *esum_d = nullptr, *cellpart = nullptr, *genepart = nullptr, *gene_d = nullptr, *cell_d = nullptr;
+  auto cleanup = [&]() { hipFree(list_d); hipFree(meta); hipFree(Et_d); hipFree(esum_d); hipFree(cellpart); hipFree(genepart); hipFree(gene_d); hipFree(cell_d); };
+#define PCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return CA_ERR_HIP; } } while (0)
+  if (M > 0) {
+    std::vector<int2> list((size_t)M);
+    {
+      std::vector<int64_t> fill(start.begin(), start.end() - 1);
+      for (int64_t n = 0; n < N; ++n) { const int c = clone_of_cell[n]; if (c >= 0) list[(size_t)fill[(size_t)c]++] = make_int2((int)n, c); }
+    }
+    // strips of TR list entries per wave: as long as the grid still holds four blocks per CU (short strips mean more rows of genepart to add up)
+    int TR = 256;
+    while (TR > 32 && (int64_t)nseg * cdiv(cdiv(M, TR), CA_TB / 64) < 4 * (int64_t)h->n_cu) TR /= 2;
+    ca_mse_ops o;
+    o.M = M; o.TR = TR; o.nrb = cdiv(M, TR); o.nrg = cdiv(o.nrb, CA_TB / 64);
+    PCK(hipMalloc((void**)&list_d, (size_t)M * sizeof(int2)));
+    PCK(hipMalloc((void**)&meta, (size_t)M * sizeof(ca_mse_row)));
+    PCK(hipMalloc((void**)&Et_d, Et.size() * sizeof(double)));
+    PCK(hipMalloc((void**)&esum_d, (size_t)C * sizeof(double)));
+    PCK(hipMalloc((void**)&cellpart, (size_t)nseg * M * sizeof(double)));
+    PCK(hipMalloc((void**)&genepart, (size_t)o.nrg * Gp * sizeof(double)));
+    PCK(hipMalloc((void**)&gene_d, (size_t)Gp * sizeof(double)));
+    PCK(hipMalloc((void**)&cell_d, (size_t)N * sizeof(double)));
+    PCK(hipMemcpyAsync(list_d, list.data(), (size_t)M * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    PCK(hipMemcpyAsync(Et_d, Et.data(), Et.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PCK(hipMemcpyAsync(esum_d, esum.data(), (size_t)C * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PCK(hipMemsetAsync(cell_d, 0, (size_t)N * sizeof(double), h->stream));
+    hipLaunchKernelGGL(k_mse_prep, dim3(cdiv(M, CA_TB)), dim3(CA_TB), 0, h->stream, list_d, h->s64, esum_d, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, meta, M);
+    PCK(hipGetLastError());
+    o.meta = meta; o.Et = Et_d; o.cellpart = cellpart; o.genepart = genepart;
+    { const int rc = launch_fit_mse(h, o); if (rc != CA_OK) { cleanup(); return rc; } }
+    const int nb_gene = cdiv(Gp, 64);
+    hipLaunchKernelGGL(k_mse_finish, dim3(nb_gene + cdiv(M, 1024)), dim3(1024), 0, h->stream, genepart, o.nrg, Gp, gene_d, cellpart, meta, M, (int)nseg, cell_d, nb_gene);
+    PCK(hipGetLastError());
+    PCK(hipMemcpyAsync(gene.data(), gene_d, (size_t)Gp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (sse_cell) {
+      cell.resize((size_t)N);
+      PCK(hipMemcpyAsync(cell.data(), cell_d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    PCK(hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
+    cleanup();
+  }
+#undef PCK
+  double n_used = (double)M;
+  if (is_sharded(h)) {   // totals over all ranks: [sse_gene G | cells used | ranks whose input was refused]
+    std::vector<double> pack(gene.begin(), gene.begin() + G);
+    pack.push_back(n_used); pack.push_back(bad.empty() ? 0.0 : 1.0);
+    double* scratch = nullptr;
+    HIPCK(h, hipMalloc((void**)&scratch, pack.size() * sizeof(double)));
+    const int rc = allreduce_host_vec(h, pack, scratch);
+    hipFree(scratch);
+    if (rc != CA_OK) return rc;
+    if (pack[(size_t)G + 1] != 0.0) { h->err = "ca_fit_mse: " + (bad.empty() ? std::string("another rank refused its input") : bad); return CA_ERR_INVALID; }
+    std::copy(pack.begin(), pack.begin() + G, gene.begin());
+    n_used = pack[(size_t)G];
+  }
+  *sse_total = pairwise_sum(gene.data(), 0, G);
+  *n_cells_used = (int64_t)n_used;
+  if (sse_gene) std::copy(gene.begin(), gene.begin() + G, sse_gene);
+  if (sse_cell) { if (M > 0) std::copy(cell.begin(), cell.end(), sse_cell); else std::fill(sse_cell, sse_cell + N, 0.0); }
+  return CA_OK;
+}

@@ -250,3 +250,18 @@ int launch_cell_fused(ca_engine* h, const ca_cell_ptrs& cp) {
     default: return cell_fused_t<8>(h, cp);
   }
 }
+
+// ---- k_fit_mse<YT>: the squared-error sweep over the resident matrix in its storage (ca_fit_mse; never the 4-bit loop image) ----
+// the list of used cells (sorted by clone, M entries), the clone-major table and the partial slabs of one call; TR list entries per wave
+struct ca_mse_ops { const ca_mse_row* meta; const double* Et; double *cellpart, *genepart; int64_t M; int TR, nrb, nrg; };
+template <typename YT>
+int fit_mse_t(ca_engine* h, const ca_mse_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_fit_mse<YT>), dim3((unsigned)((int64_t)o.nrg * h->nseg)), dim3(CA_TB), 0, h->stream, (const YT*)h->Y, o.meta, o.Et,
+                                                h->ovf_col, h->ovf_val, o.cellpart, o.genepart, o.M, h->G, h->Gp, h->nseg, o.nrb, o.TR));
+  return CA_OK;
+}
+int launch_fit_mse(ca_engine* h, const ca_mse_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) return fit_mse_t<uint8_t>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return fit_mse_t<uint16_t>(h, o);
+  return fit_mse_t<float>(h, o);
+}

@@ -663,4 +663,27 @@ int ca_group_clone_gene_sums(ca_group_handle g, const int32_t* clone_of_cell, do
   }), "ca_clone_gene_sums");
 }
 
+int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell, const double* E, double* sse_total, int64_t* n_cells_used, double* sse_gene, double* sse_cell) {
+  GROUP_ALIVE(g);
+  if (!clone_of_cell || !E || !sse_total || !n_cells_used) return CA_ERR_INVALID;
+  // every rank returns the totals over ALL cells (ca_fit_mse all-reduces them, and the verdict on the input with them); rank 0's copy is the caller's
+  std::vector<double> tot((size_t)g->W, 0.0);
+  std::vector<int64_t> used((size_t)g->W, 0);
+  std::vector<std::vector<double>> gene((size_t)g->W), cell((size_t)g->W);
+  for (int r = 0; r < g->W; ++r) {
+    if (r > 0 && sse_gene) gene[(size_t)r].resize((size_t)g->G);
+    if (sse_cell) cell[(size_t)r].resize((size_t)(g->shard[(size_t)r].hi - g->shard[(size_t)r].lo));
+  }
+  const int s = settle(g, dispatch(g, [&](int r) {
+    return ca_fit_mse(g->h[(size_t)r], clone_of_cell + g->shard[(size_t)r].lo, E, &tot[(size_t)r], &used[(size_t)r],
+                      sse_gene ? (r == 0 ? sse_gene : gene[(size_t)r].data()) : nullptr, sse_cell ? cell[(size_t)r].data() : nullptr);
+  }), "ca_fit_mse");
+  if (s != CA_OK) return s;
+  *sse_total = tot[0];
+  *n_cells_used = used[0];
+  if (sse_cell)
+    for (int r = 0; r < g->W; ++r) std::copy(cell[(size_t)r].begin(), cell[(size_t)r].end(), sse_cell + g->shard[(size_t)r].lo);
+  return CA_OK;
+}
+
 }  // extern "C"

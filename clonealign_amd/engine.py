@@ -41,6 +41,8 @@ EXPORTS = (
     "ca_group_clone_gene_sums",
     # sparse (CSR / CSC) count matrices, additions to ABI 6
     "ca_create_sparse", "ca_group_create_sparse",
+    # squared error of a fit on the resident matrix (compute_ca_fit_mse), additions to ABI 6
+    "ca_fit_mse", "ca_group_fit_mse",
 )
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
@@ -145,6 +147,7 @@ def load_library(path=None):
                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.ca_init_psi_pca.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p]
     lib.ca_clone_gene_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ca_fit_mse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -173,6 +176,7 @@ def load_library(path=None):
     lib.ca_group_get_param.argtypes = lib.ca_get_param.argtypes
     lib.ca_group_reinit.argtypes = lib.ca_reinit.argtypes
     lib.ca_group_clone_gene_sums.argtypes = lib.ca_clone_gene_sums.argtypes
+    lib.ca_group_fit_mse.argtypes = lib.ca_fit_mse.argtypes
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -594,6 +598,25 @@ class HipEngine:
         self._ck(self._fn("clone_gene_sums")(self.h, ci.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p),
                                              Syy.ctypes.data_as(C.c_void_p)))
         return T, Syy
+
+    def fit_mse(self, clone_idx, E, per_gene=False, per_cell=False):
+        """Squared error of the clones ``clone_idx`` (-1 = skip the cell) under the predicted-expression table ``E`` [G, C] (L, or mu * L), in one
+        float64 sweep over the resident matrix (ca_fit_mse; R/clonealign.R:415-434).  Returns {"sse": total, "n_cells": cells used, "mse": sse /
+        (n_cells * G)} plus "sse_gene" [G] / "sse_cell" [N] when asked for.  Changes nothing in the engine; two calls agree bit for bit."""
+        ci = np.ascontiguousarray(np.asarray(clone_idx, dtype=np.int32).reshape(self.N))
+        Em = np.require(np.asarray(E, dtype=np.float64).reshape(self.G, self.C), requirements=[self._order, "A"])
+        tot, used = C.c_double(), C.c_int64()
+        sg = np.zeros(self.G, dtype=np.float64) if per_gene else None
+        sc = np.zeros(self.N, dtype=np.float64) if per_cell else None
+        self._ck(self._fn("fit_mse")(self.h, ci.ctypes.data_as(C.c_void_p), Em.ctypes.data_as(C.c_void_p), C.byref(tot), C.byref(used),
+                                     None if sg is None else sg.ctypes.data_as(C.c_void_p), None if sc is None else sc.ctypes.data_as(C.c_void_p)))
+        out = {"sse": tot.value, "n_cells": int(used.value),
+               "mse": tot.value / (used.value * self.G) if used.value > 0 and self.G > 0 else float("nan")}
+        if per_gene:
+            out["sse_gene"] = sg
+        if per_cell:
+            out["sse_cell"] = sc
+        return out
 
     def synchronize(self):
         self._ck(self.lib.ca_synchronize(self.h))

@@ -105,7 +105,7 @@ def inference_tflow(Y_dat, L_dat, max_iter=100, rel_tol=1e-5, learning_rate=0.1,
     subspace iteration over the resident count matrix, once N*G exceeds 4e6; exact SVD on the host below that);
     ``allele_on`` in {"auto", "host", "device"}: where the parameter-free allele term of :166-187 is evaluated ("auto": on
     the device, ca_allele_loglik, once cells x variants exceeds 2e5);
-    ``post(engine, ml_params)`` runs before the engine is closed (clonealign() uses it for the device-side
+    ``post(engine, ml_params, retained_mask)`` runs before the engine is closed (clonealign() uses it for the device-side
     correlation sums) and its result is returned under ``"post"``.
     ``cell_index`` / ``gene_index`` (sorted integer arrays or boolean masks): fit only these rows / columns of ``Y_dat`` --
     the masks of ``preprocess_for_clonealign(..., return_masks=True)``.  ``L_dat`` (and ``x``, ``cov``, ``ref``) are then given
@@ -304,7 +304,7 @@ def inference_tflow(Y_dat, L_dat, max_iter=100, rel_tol=1e-5, learning_rate=0.1,
             elbos = run_vi_loop(eng, eps_stream, max_iter, rel_tol, verbose)
         log("\nELBO converged or reached max iterations")
         rlist = eng.get_params()                                        # :424-434
-        post_out = post(eng, rlist) if post is not None else None
+        post_out = post(eng, rlist, np.asarray(keep, dtype=bool)) if post is not None else None
         log("Computing final ELBO")
         if hasattr(eng, "final_elbo"):
             final = eng.final_elbo(eps_stream, N_FINAL_ELBO)

@@ -382,6 +382,20 @@ int ca_init_psi_pca(ca_handle h, const double* noise, int32_t n_iter, uint64_t s
  * Pearson's r of (copy number of the assigned clone, counts) follows from T, Syy and the clone sizes on the host. */
 int ca_clone_gene_sums(ca_handle h, const int32_t* clone_of_cell, double* T, double* Syy);
 
+/* Squared error of a fit, compute_ca_fit_mse() (R/clonealign.R:415-434), in ONE sweep over the resident counts (any storage; the
+ * matrix is not shipped back and no N x G array is made): clone_of_cell[n] in [0, C), or -1 for a cell that is skipped; E is the
+ * predicted-expression table, G x C in the problem's layout (L, or mu * L for model_mu = TRUE, :423-428).  All in float64:
+ *   a_n = rowSums(Y)_n / sum_g E[g][c_n]  (:429)      r_ng = a_n E[g][c_n] - y_ng  (:430-432)
+ *   sse_total = sum of r_ng^2 over the used cells and all genes; the reference's value is sse_total / (n_cells_used * G)
+ *   sse_gene[g] (G values) and sse_cell[n] (N values, 0 for a skipped cell): the same sum per gene / per cell; either may be NULL.
+ * The residual is formed and squared per count, sums run in a fixed order (no atomics): two calls agree bit for bit.
+ * CA_ERR_INVALID (with a message): a clone index outside [-1, C), a non-finite entry of E, a clone in use whose column of E sums
+ * to zero or to a non-finite value.  Sharded handle: collective; sse_total, n_cells_used and sse_gene are totals over all ranks
+ * (through the engine's transport), sse_cell covers the local cells, and input refused on one rank is refused on every rank.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, double* sse_total, int64_t* n_cells_used,
+               double* sse_gene, double* sse_cell);
+
 /* Fetch (:424-434).  name in {"mu","clone_probs","s","alpha","beta","psi","W","chi"} (the
  * reference's ml_params) or a raw variable {"loc","ls","gamma_logits","alpha_unconstr","v"}.
  * Output is float64 in the problem's layout; sizes: mu/loc/ls G, clone_probs/gamma_logits
@@ -488,6 +502,9 @@ int ca_group_final_elbo(ca_group_handle g, int32_t n_rep, const float* eps_strea
 int ca_group_get_param(ca_group_handle g, const char* name, double* out);
 int ca_group_reinit(ca_group_handle g, const double* psi0 /* N x K, all cells */, const double* loc0);
 int ca_group_clone_gene_sums(ca_group_handle g, const int32_t* clone_of_cell /* N, all cells */, double* T, double* Syy);
+/* ca_fit_mse (R/clonealign.R:415-434) over the group: clone_of_cell and sse_cell hold ALL cells; the totals are rank 0's (every rank has the same) */
+int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell /* N, all cells */, const double* E, double* sse_total,
+                     int64_t* n_cells_used, double* sse_gene, double* sse_cell /* N, all cells, or NULL */);
 
 #ifdef __cplusplus
 }
