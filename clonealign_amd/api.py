@@ -1,4 +1,4 @@
-"""User-facing API: ``clonealign()``, ``run_clonealign()`` and the ``clonealign_fit`` object.
+"""User-facing API: ``clonealign()``, ``run_clonealign()``, ``plot_clonealign()`` and the ``clonealign_fit`` object.
 
 Mirrors ``R/clonealign.R`` (exports in NAMESPACE:3-7) argument for argument; the only
 compute-heavy callee, ``inference_tflow``, runs on the MI355X engine.
@@ -193,6 +193,230 @@ def compute_ca_fit_mse(fit, Y, L, model_mu=False, random_clones=False, *, seed=N
     if per_gene:
         return out["mse"], (out["sse_gene"] / out["n_cells"] if out["n_cells"] else np.full(G, np.nan))
     return out["mse"]
+
+
+def _logexpr_sums_host(Y, group_idx, n_groups, size_factors=None, chunk=4096):
+    """Float64 host form of ``HipEngine.logexpr_sums`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time),
+    ``group_idx`` in [-1, n_groups) with -1 = leave the cell out.  Same return value, same refusals (ValueError)."""
+    idx = np.asarray(group_idx, dtype=np.int64).reshape(-1)
+    N, G = Y.shape
+    Q = int(n_groups)
+    if not 1 <= Q <= 64:
+        raise ValueError(f"logexpr_sums: n_groups = {Q} is outside [1, 64]")
+    if idx.shape[0] != N:
+        raise ValueError(f"logexpr_sums: Y has {N} rows (cells) but group_idx {idx.shape[0]} entries")
+    if idx.size and (idx.min() < -1 or idx.max() >= Q):
+        n = int(np.flatnonzero((idx < -1) | (idx >= Q))[0])
+        raise ValueError(f"logexpr_sums: group index {idx[n]} of cell {n} is outside [-1, {Q})")
+    used = np.flatnonzero(idx >= 0)
+    if size_factors is None:                                         # library-size factors centred at 1 over the used cells
+        lib = np.asarray(Y.sum(1), dtype=np.float64).reshape(-1) if _is_sparse(Y) else np.asarray(Y).sum(1, dtype=np.float64)
+        mean = lib[used].mean() if used.size else 1.0
+        sf = lib / mean if mean > 0 else np.zeros(N)
+    else:
+        sf = np.asarray(size_factors, dtype=np.float64).reshape(-1)
+        if sf.shape[0] != N:
+            raise ValueError(f"logexpr_sums: Y has {N} rows (cells) but size_factors {sf.shape[0]} entries")
+    wrong = used[~((sf[used] > 0) & np.isfinite(sf[used]))]
+    if wrong.size:
+        raise ValueError(f"logexpr_sums: cell {wrong[0]} (group {idx[wrong[0]]}) has size factor {sf[wrong[0]]}: it must be positive and finite")
+    S1, S2 = np.zeros((G, Q)), np.zeros(G)
+    for lo in range(0, used.size, int(chunk)):
+        rows = used[lo:lo + int(chunk)]
+        Yc = Y[rows]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+        lc = np.log2(Yc / sf[rows, None] + 1.0)                      # logcounts, R/plotting.R:177
+        S2 += (lc * lc).sum(0)
+        for q in np.unique(idx[rows]):
+            S1[:, q] += lc[idx[rows] == q].sum(0)
+    return {"S1": S1, "S2": S2, "n_group": np.bincount(idx[used], minlength=Q).astype(np.int64)}
+
+
+def clone_expression_profile(Y, clones, *, size_factors=None, engine=None, engine_opts=None):
+    """Per-clone expression profile: the data side of plot_clonealign (R/plotting.R:177-201) from ONE sweep over the count matrix.
+
+    ``Y`` [cells, genes]: a dense array in any dtype the engine uploads, or a scipy.sparse matrix; never densified or copied as float64 on the host.
+    ``clones``: one label per cell, used as given (:181): "unassigned" is a label like any other.  The log-expression is formed from the counts,
+    ``lc = log2(y / sf + 1)``, with library-size factors centred at 1 (scater's ``normalize()`` default) unless ``size_factors`` [cells] are given.
+    ``engine``: a live engine whose resident matrix is ``Y``; without it a throwaway engine is built for the upload only (``K=0``; ``engine_opts`` go
+    to its constructor) and closed afterwards.  An engine without ``logexpr_sums`` gets the chunked float64 host form.
+
+    Returns a dict: ``labels`` (distinct labels in order of first appearance), ``n_cells`` per label, ``mean`` [G] and ``sd`` [G] of lc over all cells
+    (sample sd, n - 1; an sd of 0 is replaced by 1, :193; a variance not above ``1e-12 * S2 / N`` counts as 0) and ``mean_z`` [G, Q], the mean z-score
+    of gene g over the cells of label q, ``(S1[g][q] / n_q - mean_g) / sd_g`` (:195-200)."""
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    clones = np.asarray(clones, dtype=object).reshape(-1)
+    if clones.shape[0] != N:
+        raise ValueError(f"clones has {clones.shape[0]} labels but Y has {N} rows (cells)")
+    labels = list(dict.fromkeys(clones.tolist()))
+    Q = len(labels)
+    if not 1 <= Q <= 64:
+        raise ValueError(f"clones holds {Q} distinct labels; between 1 and 64 are supported")
+    lut = {c: i for i, c in enumerate(labels)}
+    idx = np.array([lut[c] for c in clones], dtype=np.int32)
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, np.ones((G, 2)), np.zeros((N, 0)), np.zeros(G), 0, **(engine_opts or {}))
+    try:
+        if hasattr(engine, "logexpr_sums"):
+            if (engine.N, engine.G) != (N, G):
+                raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+            out = engine.logexpr_sums(idx, Q, size_factors)
+        else:
+            out = _logexpr_sums_host(Y, idx, Q, size_factors)
+    finally:
+        if own:
+            engine.close()
+    return _profile_from_sums(out["S1"], out["S2"], out["n_group"], labels)
+
+
+def _profile_from_sums(S1, S2, n_group, labels):
+    """mean, sd and per-label mean z-scores (R/plotting.R:188-200) from the sums of ``logexpr_sums``."""
+    S1 = np.asarray(S1, dtype=np.float64)
+    S2 = np.asarray(S2, dtype=np.float64)
+    nq = np.asarray(n_group, dtype=np.float64)
+    n = nq.sum()
+    mean = S1.sum(1) / n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = (S2 - n * mean ** 2) / (n - 1) if n > 1 else np.full(S2.shape, np.nan)           # sd(), :189
+        var = np.where(var > 1e-12 * S2 / n, var, 0.0) if n > 1 else var                     # round-off must not make a constant gene vary
+        sd = np.sqrt(var)
+        sd[sd == 0] = 1.0                                                                     # :193
+        mean_z = (S1 / nq[None, :] - mean[:, None]) / sd[:, None]                             # :195-200
+    return {"labels": list(labels), "n_cells": np.asarray(n_group, dtype=np.int64), "mean": mean, "sd": sd, "mean_z": mean_z}
+
+
+class ClonealignTracks(dict):
+    """What plot_clonealign (R/plotting.R:70-226) draws, as numpy arrays: a dict with attribute access (``genes``, ``cnv_segments``, ``expression``,
+    ``expression_segments``, each a dict of equally long columns).  ``draw()`` renders the two stacked panels."""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError as e:
+            raise AttributeError(k) from e
+
+    def draw(self, ax=None):
+        """The two stacked panels (:168-224): per-gene mean z-scores with the per-state segments on top, copy-number segments below.  Needs
+        matplotlib; returns the figure."""
+        try:
+            import matplotlib.pyplot as plt
+        except ImportError as e:
+            raise ImportError("ClonealignTracks.draw() needs matplotlib, which is not installed; the tracks themselves (genes, cnv_segments, "
+                              "expression, expression_segments) are the result") from e
+        fig, (top, bottom) = plt.subplots(2, 1, sharex=True) if ax is None else (ax[0].figure, ax)
+        names = list(dict.fromkeys(list(self["expression"]["clone"]) + list(self["cnv_segments"]["clone"])))
+        cmap = plt.get_cmap(self["ggplot_palette"])
+        colour = {c: cmap(i % max(getattr(cmap, "N", 9), 1)) for i, c in enumerate(names)}
+        ex, es, cs = self["expression"], self["expression_segments"], self["cnv_segments"]
+        for c in names:
+            m = ex["clone"] == c
+            top.scatter(ex["rank_position"][m], ex["mean_z_score"][m], color=colour[c], alpha=0.5, s=8, label=str(c))
+            for i in np.flatnonzero(es["clone"] == c):
+                top.plot([es["start"][i] - 1, es["end"][i] + 1], [es["per_clone_state_z_score"][i]] * 2, color=colour[c], linewidth=1.2)
+            for i in np.flatnonzero(cs["clone"] == c):
+                bottom.plot([cs["start"][i] - 1, cs["end"][i] + 1], [cs["copy_number"][i]] * 2, color=colour[c], linewidth=1.8)
+        top.set_ylim(*self["expression_ylim"])
+        top.set_ylabel("Gene expression")
+        top.set_title("scRNA-seq", loc="left")
+        top.legend(title="Inferred\nclone")
+        bottom.set_xlabel("Genomic position")
+        bottom.set_ylabel("Copy number")
+        bottom.set_title("scDNA-seq", loc="left")
+        return fig
+
+
+def _average_rank(x):
+    """R's rank() with ties.method = "average"."""
+    x = np.asarray(x, dtype=np.float64)
+    order = np.argsort(x, kind="stable")
+    xs = x[order]
+    first = np.r_[True, xs[1:] != xs[:-1]]
+    run = np.cumsum(first) - 1
+    lo = np.flatnonzero(first)
+    hi = np.r_[lo[1:], x.size]
+    out = np.empty(x.size)
+    out[order] = ((lo + 1 + hi) / 2.0)[run]
+    return out
+
+
+def plot_clonealign(sce, clones, cnv_data, chromosome="1", chr_str="chr", start_str="start_position", end_str="end_position", jitter_cnv=True,
+                    ggplot_palette="Set1", expression_ylim=(-.15, .15), cnv_dodge_sd=0.1, *, seed=None, size_factors=None, profile=None,
+                    engine=None, engine_opts=None):
+    """Gene expression and copy number along one chromosome, per clone: R/plotting.R:70-226, first eleven arguments as at :70-77.
+
+    ``sce``: whatever ``clonealign()`` accepts as expression data, with the gene annotation under ``sce["rowData"]`` (a dict of columns holding
+    ``chr_str``, ``start_str``, ``end_str`` and optionally ``ensembl_gene_id``); ``clones``: one label per cell; ``cnv_data``: the gene-by-clone
+    copy-number DataFrame or array given to the fit.  Returns a :class:`ClonealignTracks` with the plot's data (``.draw()`` renders it):
+    ``genes`` (rank_position :121, state :139-151), ``cnv_segments`` per (state, clone, copy_number) (:156-159), ``expression`` -- the mean z-score
+    per (clone, gene) (:199-201) -- and ``expression_segments`` per (clone, state), joined with the segments (:203-212).
+
+    The expression side is one device sweep over the count matrix (``clone_expression_profile``; its ``engine`` / ``engine_opts`` /
+    ``size_factors`` are passed on), never a dense N x G matrix on the host; ``profile=`` takes a ``clone_expression_profile`` result so that
+    several chromosomes cost one sweep.
+    Differences from the reference, both stated: (1) the reference reads ``logcounts(sce)`` as the user normalised it; this forms them from the
+    counts with library-size factors centred at 1, scater's ``normalize()`` default -- pass ``size_factors`` for anything else.  (2) ``jitter_cnv``
+    adds ``N(0, cnv_dodge_sd)`` noise through ``numpy.random.default_rng(seed)``: the reference uses R's ``rnorm()``, whose stream cannot be
+    reproduced here, so the jitter (not its distribution) differs from R's under any seed."""
+    row_data = sce["rowData"] if isinstance(sce, dict) and "rowData" in sce else getattr(sce, "rowData", None)
+    row_data = {} if row_data is None else row_data
+    for arg, col, what in (("chr_str", chr_str, "chromosome"), ("start_str", start_str, "start position"), ("end_str", end_str, "end position")):
+        if col not in row_data:                                      # :93-103
+            raise ValueError(f"The column '{arg}' (currently set to '{col}') must be in rowData(sce) and refer to the {what} of each gene")
+    on_chr = np.asarray([str(c) for c in np.asarray(row_data[chr_str]).reshape(-1)], dtype=object) == str(chromosome)   # :105
+    if not on_chr.any():
+        raise ValueError(f"No genes on chromosome {chromosome} in CNV regions")                 # :107-109
+    L, cn = _parse_cnv(cnv_data)                                     # :83-85
+    clone_names = cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(L.shape[1])]
+    if L.shape[0] != on_chr.shape[0]:
+        raise ValueError(f"cnv_data has {L.shape[0]} rows (genes) but rowData(sce) has {on_chr.shape[0]}")
+    gi = np.flatnonzero(on_chr)                                      # :111-113
+    Lc = L[gi]
+    ids = (np.asarray([str(v) for v in np.asarray(row_data["ensembl_gene_id"]).reshape(-1)], dtype=object)[gi] if "ensembl_gene_id" in row_data
+           else np.asarray([str(i + 1) for i in range(gi.size)], dtype=object))                 # :115-117
+    pos = (np.asarray(row_data[start_str], dtype=np.float64).reshape(-1)[gi] + np.asarray(row_data[end_str], dtype=np.float64).reshape(-1)[gi]) / 2
+    rank = _average_rank(pos)                                        # :121
+    order = np.argsort(rank, kind="stable")                          # arrange(rank_position), :135
+    changed = np.r_[False, np.any(Lc[order][1:] != Lc[order][:-1], axis=1)]
+    state = np.empty(gi.size, dtype=np.int64)
+    state[order] = 1 + np.cumsum(changed)                            # :139-151
+    n_state = int(state.max())
+    # segments per (state, clone, copy_number): within a state every clone has ONE copy number, so the groups are the (state, clone) pairs (:156-159)
+    seg = {k: [] for k in ("state", "clone", "copy_number", "start", "end")}
+    for st in range(1, n_state + 1):
+        m = state == st
+        for c in sorted(range(len(clone_names)), key=lambda i: str(clone_names[i])):             # group_by() sorts its keys
+            seg["state"].append(st); seg["clone"].append(clone_names[c]); seg["copy_number"].append(Lc[m, c][0])
+            seg["start"].append(rank[m].min()); seg["end"].append(rank[m].max())
+    seg = {"state": np.asarray(seg["state"], dtype=np.int64), "clone": np.asarray(seg["clone"], dtype=object),
+           "copy_number": np.asarray(seg["copy_number"], dtype=np.float64), "start": np.asarray(seg["start"]), "end": np.asarray(seg["end"])}
+    seg["length"] = seg["end"] - seg["start"]
+    if jitter_cnv:                                                   # :162-164
+        seg["copy_number"] = seg["copy_number"] + np.random.default_rng(seed).normal(0.0, cnv_dodge_sd, size=seg["copy_number"].shape)
+    # RNA side (:177-201): the profile covers every gene of the matrix; a gene's z-scores do not depend on the other genes
+    if profile is None:
+        Y, _ = _parse_expression(sce)
+        profile = clone_expression_profile(Y, clones, size_factors=size_factors, engine=engine, engine_opts=engine_opts)
+    mz = np.asarray(profile["mean_z"])
+    if mz.shape[0] != on_chr.shape[0]:
+        raise ValueError(f"the expression profile covers {mz.shape[0]} genes but rowData(sce) has {on_chr.shape[0]}")
+    labels = list(profile["labels"])
+    Q = len(labels)
+    expr = {"clone": np.repeat(np.asarray(labels, dtype=object), gi.size), "ensembl_gene_id": np.tile(ids, Q), "gene_index": np.tile(gi, Q),
+            "rank_position": np.tile(rank, Q), "state": np.tile(state, Q), "mean_z_score": mz[gi].T.reshape(-1).copy()}
+    per_state = np.full((Q, n_state), np.nan)                        # :203-205
+    for st in range(1, n_state + 1):
+        per_state[:, st - 1] = mz[gi][state == st].mean(0)
+    expr["per_clone_state_z_score"] = per_state[np.repeat(np.arange(Q), gi.size), np.tile(state, Q) - 1]   # :209
+    lab_of = {c: i for i, c in enumerate(labels)}
+    keep = np.array([c in lab_of for c in seg["clone"]], dtype=bool)                            # inner_join(cnv_df_2, gex_per_clone_state), :212
+    eseg = {k: v[keep] for k, v in seg.items()}
+    eseg["per_clone_state_z_score"] = np.array([per_state[lab_of[c], st - 1] for c, st in zip(eseg["clone"], eseg["state"])], dtype=np.float64)
+    return ClonealignTracks(genes={"ensembl_gene_id": ids, "gene_index": gi, "rank_position": rank, "state": state}, cnv_segments=seg, expression=expr,
+                            expression_segments=eseg, clone_names=list(clone_names), labels=labels, chromosome=chromosome,
+                            ggplot_palette=ggplot_palette, expression_ylim=tuple(expression_ylim), profile=profile)
 
 
 def _counts_array(a):

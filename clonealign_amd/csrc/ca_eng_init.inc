@@ -1,4 +1,4 @@
-// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit (ca_fit_mse).
+// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit (ca_fit_mse), log-expression sums per gene and cell group (ca_logexpr_sums).
 extern "C++" {   // (templates: this part sits inside the C ABI's extern "C" block)
 namespace {
 // Transformed pass over Y with explicit factor buffers (PCA init): row products Y'.Vp -> YWp, column products Y'^T.Fp -> YTp
@@ -409,5 +409,138 @@ int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, doubl
   *n_cells_used = (int64_t)n_used;
   if (sse_gene) std::copy(gene.begin(), gene.begin() + G, sse_gene);
   if (sse_cell) { if (M > 0) std::copy(cell.begin(), cell.end(), sse_cell); else std::fill(sse_cell, sse_cell + N, 0.0); }
+  return CA_OK;
+}
+
+// The data side of plot_clonealign (R/plotting.R:177-205) on the resident matrix: S1[g][q] = sum over the cells of group q of lc_ng, S2[g] = sum over all used
+// cells of lc_ng^2, lc_ng = log2(y_ng / sf_n + 1).  Like ca_fit_mse it reads the matrix, the row sums and the overflow list only: no wait for the loop's side
+// stream, no variable, Adam slot or draw index changes.  A sharded handle takes part in both collectives (the used cells' library sizes for the default size
+// factors, then the sums) even when ITS input is refused: the verdict travels with the numbers, so that every rank returns the same code.
+int ca_logexpr_sums(ca_handle h, const int32_t* group_of_cell, int32_t n_groups, const double* size_factor, double* S1, double* S2, int64_t* n_group) {
+  if (!h || !group_of_cell || !S1 || !S2 || !n_group) return CA_ERR_INVALID;
+  CA_NOT_IN_RUN(h);
+  if (n_groups < 1 || n_groups > 64) { h->err = "ca_logexpr_sums: n_groups = " + std::to_string(n_groups) + " is outside [1, 64]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
+  HIPCK(h, hipSetDevice(h->device));
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, Q = n_groups, nseg = h->nseg;
+  std::string bad;
+  // the used cells, sorted by group (stable: cells ascending within a group)
+  std::vector<int64_t> start((size_t)Q + 1, 0);
+  for (int64_t n = 0; n < N && bad.empty(); ++n) {
+    const int q = group_of_cell[n];
+    if (q < -1 || q >= Q) bad = "group index " + std::to_string(q) + " of cell " + std::to_string(n) + " is outside [-1, " + std::to_string(Q) + ")";
+    else if (q >= 0) start[(size_t)q + 1]++;
+  }
+  if (!bad.empty()) std::fill(start.begin(), start.end(), 0);
+  for (int q = 0; q < Q; ++q) start[(size_t)q + 1] += start[(size_t)q];
+  int64_t M = start[(size_t)Q];
+  std::vector<int2> list((size_t)M);
+  {
+    std::vector<int64_t> fill(start.begin(), start.end() - 1);
+    for (int64_t n = 0; n < N && M > 0; ++n) { const int q = group_of_cell[n]; if (q >= 0) list[(size_t)fill[(size_t)q]++] = make_int2((int)n, q); }
+  }
+  // size factors in list order: the caller's, or library sizes over their mean over the used cells of ALL ranks (scater's library-size factors, centred at 1)
+  std::vector<double> sf((size_t)M);
+  double lib_sum = 0.0;
+  if (size_factor) {
+    for (int64_t i = 0; i < M; ++i) sf[(size_t)i] = size_factor[list[(size_t)i].x];
+  } else {
+    std::vector<double> rs((size_t)N), lib;
+    HIPCK(h, hipMemcpyAsync(rs.data(), h->s64, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    SYNC(h);
+    for (int64_t i = 0; i < M; ++i) sf[(size_t)i] = rs[(size_t)list[(size_t)i].x];
+    lib.reserve((size_t)M);   // in cell order, so that the sum does not depend on the grouping
+    for (int64_t n = 0; n < N && M > 0; ++n) if (group_of_cell[n] >= 0) lib.push_back(rs[(size_t)n]);
+    lib_sum = pairwise_sum(lib.data(), 0, (int64_t)lib.size());
+  }
+  {
+    std::vector<double> pack{lib_sum, (double)M, bad.empty() ? 0.0 : 1.0};   // [the used cells' library sizes | used cells | ranks whose input was refused]
+    if (is_sharded(h)) {
+      double* scratch = nullptr;
+      HIPCK(h, hipMalloc((void**)&scratch, pack.size() * sizeof(double)));
+      const int rc = allreduce_host_vec(h, pack, scratch);
+      hipFree(scratch);
+      if (rc != CA_OK) return rc;
+    }
+    if (pack[2] != 0.0) { h->err = "ca_logexpr_sums: " + (bad.empty() ? std::string("another rank refused its input") : bad); return CA_ERR_INVALID; }
+    if (!size_factor && pack[1] > 0.0) {
+      const double mean = pack[0] / pack[1];
+      for (int64_t i = 0; i < M; ++i) sf[(size_t)i] = mean > 0.0 ? sf[(size_t)i] / mean : 0.0;
+    }
+  }
+  for (int64_t i = 0; i < M; ++i)
+    if (!(sf[(size_t)i] > 0.0) || !std::isfinite(sf[(size_t)i])) {
+      bad = "cell " + std::to_string(list[(size_t)i].x) + " (group " + std::to_string(list[(size_t)i].y) + ") has size factor " + std::to_string(sf[(size_t)i]) +
+            (size_factor ? "" : " (library size over the mean library size)") + ": it must be positive and finite";
+      break;
+    }
+  if (!bad.empty() && !is_sharded(h)) { h->err = "ca_logexpr_sums: " + bad; return CA_ERR_INVALID; }
+  if (!bad.empty()) M = 0;
+  std::vector<double> sums((size_t)(Q + 1) * Gp, 0.0);   // [S1 of group 0 .. Q-1 | S2], each Gp values
+  int2* list_d = nullptr; ca_mse_row* meta = nullptr; ca_lx_blk* blk_d = nullptr; int* first_d = nullptr; double *inv_d = nullptr, *part1 = nullptr, *part2 = nullptr, *sums_d = nullptr;
+  auto cleanup = [&]() { hipFree(list_d); hipFree(meta); hipFree(blk_d); hipFree(first_d); hipFree(inv_d); hipFree(part1); hipFree(part2); hipFree(sums_d); };
+#define PCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return CA_ERR_HIP; } } while (0)
+  if (M > 0) {
+    for (int64_t i = 0; i < M; ++i) sf[(size_t)i] = 1.0 / sf[(size_t)i];
+    // block pieces of at most 4 TR list entries, cut at the group boundaries; TR as long as the grid still holds four blocks per CU
+    auto pieces = [&](int tr) { int64_t p = 0; for (int q = 0; q < Q; ++q) p += cdiv(start[(size_t)q + 1] - start[(size_t)q], (int64_t)(CA_TB / 64) * tr); return p; };
+    int TR = 256;
+    while (TR > 32 && (int64_t)nseg * pieces(TR) < 4 * (int64_t)h->n_cu) TR /= 2;
+    const int64_t BR = (int64_t)(CA_TB / 64) * TR;
+    std::vector<ca_lx_blk> blk;
+    std::vector<int> first((size_t)Q + 1, 0);
+    for (int q = 0; q < Q; ++q) {
+      for (int64_t r = start[(size_t)q]; r < start[(size_t)q + 1]; r += BR) {
+        ca_lx_blk b; b.r0 = r; b.nrows = (int)std::min<int64_t>(BR, start[(size_t)q + 1] - r); b.pad = 0;
+        blk.push_back(b);
+      }
+      first[(size_t)q + 1] = (int)blk.size();
+    }
+    ca_lx_ops o;
+    o.nrg = (int)blk.size();
+    PCK(hipMalloc((void**)&list_d, (size_t)M * sizeof(int2)));
+    PCK(hipMalloc((void**)&meta, (size_t)M * sizeof(ca_mse_row)));
+    PCK(hipMalloc((void**)&blk_d, blk.size() * sizeof(ca_lx_blk)));
+    PCK(hipMalloc((void**)&first_d, first.size() * sizeof(int)));
+    PCK(hipMalloc((void**)&inv_d, (size_t)M * sizeof(double)));
+    PCK(hipMalloc((void**)&part1, (size_t)o.nrg * Gp * sizeof(double)));
+    PCK(hipMalloc((void**)&part2, (size_t)o.nrg * Gp * sizeof(double)));
+    PCK(hipMalloc((void**)&sums_d, sums.size() * sizeof(double)));
+    PCK(hipMemcpyAsync(list_d, list.data(), (size_t)M * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+    PCK(hipMemcpyAsync(inv_d, sf.data(), (size_t)M * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PCK(hipMemcpyAsync(blk_d, blk.data(), blk.size() * sizeof(ca_lx_blk), hipMemcpyHostToDevice, h->stream));
+    PCK(hipMemcpyAsync(first_d, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_lx_prep, dim3(cdiv(M, CA_TB)), dim3(CA_TB), 0, h->stream, list_d, inv_d, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, meta, M);
+    PCK(hipGetLastError());
+    o.meta = meta; o.blk = blk_d; o.part1 = part1; o.part2 = part2;
+    { const int rc = launch_logexpr(h, o); if (rc != CA_OK) { cleanup(); return rc; } }
+    hipLaunchKernelGGL(k_lx_finish, dim3(cdiv(Gp, 64), Q + 1), dim3(1024), 0, h->stream, part1, part2, first_d, Q, Gp, sums_d);
+    PCK(hipGetLastError());
+    PCK(hipMemcpyAsync(sums.data(), sums_d, sums.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
+    cleanup();
+  }
+#undef PCK
+  std::vector<double> cnt((size_t)Q, 0.0);
+  if (bad.empty()) for (int q = 0; q < Q; ++q) cnt[(size_t)q] = (double)(start[(size_t)q + 1] - start[(size_t)q]);
+  if (is_sharded(h)) {   // totals over all ranks: [S1 Q x G | S2 G | cells per group Q | ranks whose input was refused]
+    std::vector<double> pack;
+    pack.reserve((size_t)(Q + 1) * G + Q + 1);
+    for (int q = 0; q <= Q; ++q) pack.insert(pack.end(), sums.begin() + (size_t)q * Gp, sums.begin() + (size_t)q * Gp + G);
+    pack.insert(pack.end(), cnt.begin(), cnt.end());
+    pack.push_back(bad.empty() ? 0.0 : 1.0);
+    double* scratch = nullptr;
+    HIPCK(h, hipMalloc((void**)&scratch, pack.size() * sizeof(double)));
+    const int rc = allreduce_host_vec(h, pack, scratch);
+    hipFree(scratch);
+    if (rc != CA_OK) return rc;
+    if (pack.back() != 0.0) { h->err = "ca_logexpr_sums: " + (bad.empty() ? std::string("another rank refused its input") : bad); return CA_ERR_INVALID; }
+    for (int q = 0; q <= Q; ++q) std::copy(pack.begin() + (size_t)q * G, pack.begin() + (size_t)(q + 1) * G, sums.begin() + (size_t)q * Gp);
+    std::copy(pack.begin() + (size_t)(Q + 1) * G, pack.begin() + (size_t)(Q + 1) * G + Q, cnt.begin());
+  }
+  for (int g = 0; g < G; ++g) {
+    for (int q = 0; q < Q; ++q) S1[hidx(h->layout, g, q, G, Q)] = sums[(size_t)q * Gp + g];
+    S2[g] = sums[(size_t)Q * Gp + g];
+  }
+  for (int q = 0; q < Q; ++q) n_group[q] = (int64_t)cnt[(size_t)q];
   return CA_OK;
 }

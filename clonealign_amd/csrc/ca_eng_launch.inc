@@ -265,3 +265,18 @@ int launch_fit_mse(ca_engine* h, const ca_mse_ops& o) {
   if (h->ystore == CA_YSTORE_U16) return fit_mse_t<uint16_t>(h, o);
   return fit_mse_t<float>(h, o);
 }
+
+// ---- k_logexpr<YT>: the log-expression sweep over the resident matrix in its storage (ca_logexpr_sums; never the 4-bit loop image) ----
+// the list of used cells (sorted by group), its nrg block pieces (none crosses a group boundary) and the two partial slabs of one call
+struct ca_lx_ops { const ca_mse_row* meta; const ca_lx_blk* blk; double *part1, *part2; int nrg; };
+template <typename YT>
+int logexpr_t(ca_engine* h, const ca_lx_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_logexpr<YT>), dim3((unsigned)((int64_t)o.nrg * h->nseg)), dim3(CA_TB), 0, h->stream, (const YT*)h->Y, o.meta, o.blk,
+                                                h->ovf_col, h->ovf_val, o.part1, o.part2, h->G, h->Gp, h->nseg));
+  return CA_OK;
+}
+int launch_logexpr(ca_engine* h, const ca_lx_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) return logexpr_t<uint8_t>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return logexpr_t<uint16_t>(h, o);
+  return logexpr_t<float>(h, o);
+}

@@ -686,4 +686,27 @@ int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell, const doub
   return CA_OK;
 }
 
+int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell, int32_t n_groups, const double* size_factor, double* S1, double* S2, int64_t* n_group) {
+  GROUP_ALIVE(g);
+  if (!group_of_cell || !S1 || !S2 || !n_group) return CA_ERR_INVALID;
+  if (n_groups < 1 || n_groups > 64) { g->err = "ca_logexpr_sums: n_groups = " + std::to_string(n_groups) + " is outside [1, 64]"; return CA_ERR_INVALID; }
+  // every rank returns the totals over ALL cells (ca_logexpr_sums all-reduces them, and the verdict on the input with them); rank 0's copy is the caller's
+  std::vector<std::vector<double>> s1((size_t)g->W), s2((size_t)g->W);
+  std::vector<std::vector<int64_t>> ng((size_t)g->W);
+  for (int r = 1; r < g->W; ++r) { s1[(size_t)r].resize((size_t)g->G * n_groups); s2[(size_t)r].resize((size_t)g->G); ng[(size_t)r].resize((size_t)n_groups); }
+  const int s = settle(g, dispatch(g, [&](int r) {
+    const int64_t lo = g->shard[(size_t)r].lo;
+    return ca_logexpr_sums(g->h[(size_t)r], group_of_cell + lo, n_groups, size_factor ? size_factor + lo : nullptr, r == 0 ? S1 : s1[(size_t)r].data(),
+                           r == 0 ? S2 : s2[(size_t)r].data(), r == 0 ? n_group : ng[(size_t)r].data());
+  }), "ca_logexpr_sums");
+  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  return s;
+}
+
 }  // extern "C"

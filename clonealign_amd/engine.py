@@ -43,6 +43,8 @@ EXPORTS = (
     "ca_create_sparse", "ca_group_create_sparse",
     # squared error of a fit on the resident matrix (compute_ca_fit_mse), additions to ABI 6
     "ca_fit_mse", "ca_group_fit_mse",
+    # log-expression sums per gene and cell group on the resident matrix (plot_clonealign), additions to ABI 6
+    "ca_logexpr_sums", "ca_group_logexpr_sums",
 )
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
@@ -148,6 +150,7 @@ def load_library(path=None):
     lib.ca_init_psi_pca.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p]
     lib.ca_clone_gene_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_fit_mse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+    lib.ca_logexpr_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -177,6 +180,7 @@ def load_library(path=None):
     lib.ca_group_reinit.argtypes = lib.ca_reinit.argtypes
     lib.ca_group_clone_gene_sums.argtypes = lib.ca_clone_gene_sums.argtypes
     lib.ca_group_fit_mse.argtypes = lib.ca_fit_mse.argtypes
+    lib.ca_group_logexpr_sums.argtypes = lib.ca_logexpr_sums.argtypes
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -617,6 +621,21 @@ class HipEngine:
         if per_cell:
             out["sse_cell"] = sc
         return out
+
+    def logexpr_sums(self, group_idx, n_groups, size_factors=None):
+        """Sums of the log-expression ``lc = log2(y / sf + 1)`` per gene and cell group, in one float64 sweep over the resident matrix (ca_logexpr_sums;
+        the data side of plot_clonealign, R/plotting.R:177-205).  ``group_idx`` [N] in [0, n_groups), -1 = leave the cell out; ``size_factors`` [N] or
+        None for library-size factors centred at 1 over the used cells.  Returns {"S1" [G, n_groups]: sums of lc per group, "S2" [G]: sums of lc^2 over
+        the used cells, "n_group" [n_groups]: cells per group}.  Changes nothing in the engine; two calls agree bit for bit."""
+        gi = np.ascontiguousarray(np.asarray(group_idx, dtype=np.int32).reshape(self.N))
+        Q = int(n_groups)
+        sf = None if size_factors is None else np.ascontiguousarray(np.asarray(size_factors, dtype=np.float64).reshape(self.N))
+        S1 = np.zeros((self.G, max(Q, 0)), dtype=np.float64, order=self._order)
+        S2 = np.zeros(self.G, dtype=np.float64)
+        ng = np.zeros(max(Q, 0), dtype=np.int64)
+        self._ck(self._fn("logexpr_sums")(self.h, gi.ctypes.data_as(C.c_void_p), Q, None if sf is None else sf.ctypes.data_as(C.c_void_p),
+                                          S1.ctypes.data_as(C.c_void_p), S2.ctypes.data_as(C.c_void_p), ng.ctypes.data_as(C.c_void_p)))
+        return {"S1": S1, "S2": S2, "n_group": ng}
 
     def synchronize(self):
         self._ck(self.lib.ca_synchronize(self.h))

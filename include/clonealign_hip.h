@@ -396,6 +396,26 @@ int ca_clone_gene_sums(ca_handle h, const int32_t* clone_of_cell, double* T, dou
 int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, double* sse_total, int64_t* n_cells_used,
                double* sse_gene, double* sse_cell);
 
+/* The data side of plot_clonealign() (R/plotting.R:177-205: the dense t(logcounts), its N*G-row long table, the per-gene mean and
+ * sd and the per (clone, gene) means of the z-scores) as sums from ONE sweep over the resident counts (any storage; nothing N x G
+ * is made on the host).  group_of_cell[n] in [0, n_groups), or -1 for a cell left out of every sum and count; n_groups in [1, 64].
+ * size_factor: N values, or NULL for library-size factors centred at 1 over the used cells, sf_n = rowSums(Y)_n / mean(rowSums(Y))
+ * (the engine's float64 row sums; scater's normalize() default).  All in float64:
+ *   lc_ng = log2(y_ng / sf_n + 1)                                     (logcounts, :177)
+ *   S1[g][q] = sum over the cells of group q of lc_ng                 (G x n_groups, the problem's layout)
+ *   S2[g]    = sum over all used cells of lc_ng^2                     (G values)
+ *   n_group[q] = cells of group q                                     (n_groups values)
+ * from which mean_g = sum_q S1[g][q] / n, var_g = (S2[g] - n mean_g^2) / (n - 1) (:188-189) and the mean z-score of a group,
+ * (S1[g][q] / n_group[q] - mean_g) / sd_g (:195-200), follow on the host.  Sums run in a fixed order (no atomics): two calls agree
+ * bit for bit.  CA_ERR_INVALID (with a message naming the cell or group): a group index outside [-1, n_groups), n_groups outside
+ * [1, 64], a used cell whose size factor is <= 0 or not finite (a zero library size among them, as in scater).
+ * Sharded handle: collective, with the same n_groups and the same NULL-ness of size_factor on every rank; S1, S2 and n_group are
+ * totals over all ranks and the default size factors use the mean over all ranks' used cells (through the engine's transport);
+ * input refused on one rank is refused on every rank.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_logexpr_sums(ca_handle h, const int32_t* group_of_cell, int32_t n_groups, const double* size_factor, double* S1, double* S2,
+                    int64_t* n_group);
+
 /* Fetch (:424-434).  name in {"mu","clone_probs","s","alpha","beta","psi","W","chi"} (the
  * reference's ml_params) or a raw variable {"loc","ls","gamma_logits","alpha_unconstr","v"}.
  * Output is float64 in the problem's layout; sizes: mu/loc/ls G, clone_probs/gamma_logits
@@ -505,6 +525,9 @@ int ca_group_clone_gene_sums(ca_group_handle g, const int32_t* clone_of_cell /* 
 /* ca_fit_mse (R/clonealign.R:415-434) over the group: clone_of_cell and sse_cell hold ALL cells; the totals are rank 0's (every rank has the same) */
 int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell /* N, all cells */, const double* E, double* sse_total,
                      int64_t* n_cells_used, double* sse_gene, double* sse_cell /* N, all cells, or NULL */);
+/* ca_logexpr_sums (R/plotting.R:177-205) over the group: group_of_cell and size_factor (or NULL) hold ALL cells; the totals are rank 0's (every rank has the same) */
+int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell /* N, all cells */, int32_t n_groups,
+                          const double* size_factor /* N, all cells, or NULL */, double* S1, double* S2, int64_t* n_group);
 
 #ifdef __cplusplus
 }
