@@ -24,6 +24,10 @@ class ClonealignFit(dict):
 
     def __repr__(self):                                             # print.clonealign_fit, :348-357
         N = len(self["clone"])
+        if "mu" not in self["ml_params"]:                            # assign_cells(): cells scored under another fit, no gene parameters
+            return (f"A clonealign assignment of {N} cells to {self['ml_params']['clone_probs'].shape[1]} clones under a fitted model\n"
+                    "To access clone assignments, call x$clone\n"
+                    "To access the per-clone log-likelihoods, call x$clone_loglik\n")
         G = len(self["ml_params"]["mu"])
         C = self["ml_params"]["clone_probs"].shape[1]
         return (f"A clonealign_fit for {N} cells, {G} genes, and {C} clones\n"
@@ -40,7 +44,7 @@ def clone_assignment(gamma, clone_names, clone_assignment_probability=0.95):
     mx = gamma.max(1)
     names = np.asarray(list(clone_names), dtype=object)
     out = names[best]
-    out[mx < clone_assignment_probability] = "unassigned"
+    out[~(mx >= clone_assignment_probability)] = "unassigned"        # (a row of NaN, no clone possible, is unassigned too)
     return out
 
 
@@ -193,6 +197,162 @@ def compute_ca_fit_mse(fit, Y, L, model_mu=False, random_clones=False, *, seed=N
     if per_gene:
         return out["mse"], (out["sse_gene"] / out["n_cells"] if out["n_cells"] else np.full(G, np.nan))
     return out["mse"]
+
+
+def _clone_loglik_host(Y, E, U=None, V=None, const=True, chunk=2048):
+    """Float64 host form of ``HipEngine.clone_loglik`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time), E
+    [G, C], U [N, D] and V [G, D] or both None.  Same return value, same rules (xlogy, the shift by the largest exponent), same refusals (ValueError)."""
+    from scipy.special import gammaln
+    E = np.asarray(E, dtype=np.float64)
+    N, G = Y.shape
+    if E.ndim != 2 or E.shape[0] != G:
+        raise ValueError(f"clone_loglik: Y is {N} x {G} but E is {E.shape}")
+    C = E.shape[1]
+    D = 0
+    if (U is None) != (V is None):
+        raise ValueError("clone_loglik: U and V go together (both, or neither)")
+    if U is not None:
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"clone_loglik: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = U.shape[1]
+    if D > 8:
+        raise ValueError(f"clone_loglik: D = {D} is outside [0, 8]")
+    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
+    if wrong.size:
+        raise ValueError(f"clone_loglik: expected expression has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
+    esum = E.sum(0)
+    wrong = np.flatnonzero(~np.isfinite(esum) | (esum == 0))
+    if wrong.size:
+        raise ValueError(f"clone_loglik: expected expression of clone {wrong[0]} sums to {esum[wrong[0]]} over the genes")
+    for name, M, row in (("V", V, "gene"), ("U", U, "cell")):
+        if D > 0 and not np.isfinite(M).all():
+            r, d = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"clone_loglik: {name} has a non-finite entry ({row} {r}, factor {d})")
+    zero = E == 0
+    logE = np.log(np.where(zero, 1.0, E))                            # xlogy: 0 where E = 0, put right below
+    ll = np.empty((N, C))
+    for lo in range(0, N, int(chunk)):
+        Yc = Y[lo:lo + int(chunk)]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+        s = Yc.sum(1)
+        a = Yc @ logE
+        if zero.any():
+            a[((Yc > 0).astype(np.float64) @ zero.astype(np.float64)) > 0] = -np.inf
+        if D > 0:
+            eta = U[lo:lo + int(chunk)] @ V.T
+            m = eta.max(1)
+            logz = m[:, None] + np.log(np.exp(eta - m[:, None]) @ E)
+            a += (Yc * eta).sum(1)[:, None]
+        else:
+            logz = np.log(esum)[None, :]
+        a -= np.where(s[:, None] > 0, s[:, None] * logz, 0.0)
+        if const:
+            a += (gammaln(s + 1.0) - gammaln(Yc + 1.0).sum(1))[:, None]
+        ll[lo:lo + int(chunk)] = a
+    return ll
+
+
+def clone_loglik(fit, Y, L, *, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
+    """Log-likelihood ``ll`` [cells, clones] of the cells of ``Y`` under every clone of a fitted model, taken at the fit's point estimates: the
+    reference's ``p_y_on_c`` (R/inference-tflow.R:288-296) with the draw of ``mu`` replaced by ``fit["ml_params"]["mu"]``, i.e.
+    ``Multinomial(total = s_n, probs ~ mu * L[:, c] * exp(psi_n W^T + x_n beta^T)).log_prob(y_n)``.  The cells need not be the ones the fit saw.
+
+    ``Y`` [cells, genes]: a dense array in any dtype the engine uploads, or a scipy.sparse matrix; it is evaluated on the device in one float64 sweep
+    (``HipEngine.clone_loglik``) and never densified or copied as float64 on the host.  ``L`` [genes, clones] is given for the fit's retained genes and
+    saturated as ``inference_tflow`` does by default (:142-144); ``saturate=False`` is for fits made that way.
+    ``psi``, for fits with ``K > 0`` (the default ``clonealign()`` fit has ``K = 1``): ``None`` means the cells are NEW -- their ``psi`` is taken at its
+    prior mean 0 (:318), so the ``W`` term drops out; ``"fit"`` takes ``fit["ml_params"]["psi"]`` (the cells are the fit's own, in its order); an array
+    [cells, K] is used as given.  ``x`` [cells, P]: the covariates, required exactly when the fit has ``beta``.
+    ``const=False`` leaves out the clone-independent ``lgamma(s + 1) - sum(lgamma(y + 1))``.
+    ``engine``: a live engine whose resident matrix is ``Y`` (used as it is); without it a throwaway engine is built for the upload only (``K=0``;
+    ``engine_opts`` go to its constructor) and closed afterwards.  An engine without ``clone_loglik`` gets the chunked float64 host form.
+    A positive count on a gene where a clone has copy number 0 makes that entry exactly ``-inf``; a zero count there adds nothing."""
+    L, _cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if L.shape[0] != G:
+        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    ml = fit["ml_params"]
+    mu = np.asarray(ml["mu"], dtype=np.float64).reshape(-1)
+    if mu.shape[0] != G:
+        raise ValueError(f"fit$ml_params$mu has length {mu.shape[0]} but L has {G} rows: evaluate on the retained genes")
+    if "clone_names" in fit and len(fit["clone_names"]) != L.shape[1]:
+        raise ValueError(f"fit has {len(fit['clone_names'])} clone names but L has {L.shape[1]} columns (clones)")
+    if saturate:
+        L = hostprep.saturate(L, saturation_threshold)               # :142-144
+    E = mu[:, None] * L
+    W = np.asarray(ml["W"], dtype=np.float64).reshape(G, -1) if ml.get("W") is not None else np.zeros((G, 0))
+    beta = np.asarray(ml["beta"], dtype=np.float64).reshape(G, -1) if ml.get("beta") is not None else np.zeros((G, 0))
+    K, P = W.shape[1], beta.shape[1]
+    if (P > 0) != (x is not None):
+        raise ValueError(f"x is required exactly when the fit has beta: the fit has {P} covariates and x is {'missing' if x is None else 'given'}")
+    Ucols, Vcols = [], []
+    if K > 0 and psi is not None:
+        if isinstance(psi, str):
+            if psi != "fit":
+                raise ValueError("psi must be None (new cells: the prior mean 0), \"fit\" (the fit's own cells) or an array [cells, K]")
+            psi = ml["psi"]
+        psi = np.asarray(psi, dtype=np.float64)
+        if psi.size != N * K or psi.reshape(-1, K).shape[0] != N:
+            raise ValueError(f"psi has {psi.reshape(-1, K).shape[0] if psi.size % K == 0 else psi.size} rows (cells) but Y has {N}")
+        Ucols.append(psi.reshape(N, K))
+        Vcols.append(W)
+    if P > 0:
+        x = np.asarray(x, dtype=np.float64)
+        x = x.reshape(-1, 1) if x.ndim == 1 else x
+        if x.shape != (N, P):
+            raise ValueError(f"x is {x.shape} but Y has {N} rows (cells) and the fit {P} covariates")
+        Ucols.append(x)
+        Vcols.append(beta)
+    U = np.concatenate(Ucols, axis=1) if Ucols else None
+    V = np.concatenate(Vcols, axis=1) if Vcols else None
+    if U is not None and U.shape[1] > 8:
+        raise ValueError(f"the fit has {U.shape[1]} exponent factors (K + P); at most 8 are supported")
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    try:
+        if hasattr(engine, "clone_loglik"):
+            if (engine.N, engine.G) != (N, G):
+                raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+            return engine.clone_loglik(E, U, V, const=const)
+        return _clone_loglik_host(Y, E, U, V, const=const)
+    finally:
+        if own:
+            engine.close()
+
+
+def assign_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=None, x=None, psi=None, saturate=True, saturation_threshold=6,
+                 const=True, engine=None, engine_opts=None):
+    """Assign the cells of ``Y`` to the clones of a fitted model without refitting: ``clone_probs = softmax_c(ll + log alpha + extra_loglik)`` with
+    ``ll = clone_loglik(fit, Y, L, ...)`` (same keywords), the exact optimum of ``q(z)`` given the fit's other parameters
+    (R/inference-tflow.R:308,322,333).  ``extra_loglik`` [cells, clones]: an addend such as the allele-specific term.
+
+    Returns a :class:`ClonealignFit` with ``clone_probs`` [cells, clones], ``clone`` (through ``clone_assignment`` at
+    ``clone_assignment_probability``), ``loglik`` [cells] (the logsumexp of the same sum: the cell's marginal log-likelihood), ``clone_loglik``
+    [cells, clones] and ``clone_names``; ``recompute_clone_assignment`` works on it.  A cell whose ``ll`` is ``-inf`` in every clone gets NaN
+    probabilities and the label "unassigned"; ``-inf`` in some clones gives probability 0 there."""
+    ll = clone_loglik(fit, Y, L, x=x, psi=psi, saturate=saturate, saturation_threshold=saturation_threshold, const=const, engine=engine,
+                      engine_opts=engine_opts)
+    N, C = ll.shape
+    _L, cn = _parse_cnv(L)
+    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(C)])
+    alpha = fit["ml_params"].get("alpha")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = ll + (0.0 if alpha is None else np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C)))   # :308
+        if extra_loglik is not None:
+            ex = np.asarray(extra_loglik, dtype=np.float64)
+            if ex.shape != (N, C):
+                raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
+            t = t + ex
+        m = t.max(1, keepdims=True)
+        lse = m + np.log(np.exp(t - m).sum(1, keepdims=True))        # (a row of -inf: NaN - no clone is possible)
+        probs = np.exp(t - lse)
+    loglik = np.where(np.isneginf(m[:, 0]), -np.inf, lse[:, 0])
+    return ClonealignFit(clone_probs=probs, clone=clone_assignment(probs, names, clone_assignment_probability), loglik=loglik, clone_loglik=ll,
+                         clone_names=names, ml_params={"clone_probs": probs})
 
 
 def _logexpr_sums_host(Y, group_idx, n_groups, size_factors=None, chunk=4096):

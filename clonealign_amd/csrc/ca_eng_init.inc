@@ -1,4 +1,4 @@
-// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit (ca_fit_mse), log-expression sums per gene and cell group (ca_logexpr_sums).
+// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit (ca_fit_mse), the per-cell, per-clone log-likelihood under a fit (ca_clone_loglik), log-expression sums per gene and cell group (ca_logexpr_sums).
 extern "C++" {   // (templates: this part sits inside the C ABI's extern "C" block)
 namespace {
 // Transformed pass over Y with explicit factor buffers (PCA init): row products Y'.Vp -> YWp, column products Y'^T.Fp -> YTp
@@ -409,6 +409,115 @@ int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, doubl
   *n_cells_used = (int64_t)n_used;
   if (sse_gene) std::copy(gene.begin(), gene.begin() + G, sse_gene);
   if (sse_cell) { if (M > 0) std::copy(cell.begin(), cell.end(), sse_cell); else std::fill(sse_cell, sse_cell + N, 0.0); }
+  return CA_OK;
+}
+
+// p_y_on_c (R/inference-tflow.R:288-296) at a fit's point estimates on the resident matrix: ll[n][c] for every cell and clone (include/clonealign_hip.h has the
+// formula and the rules).  Like ca_fit_mse it reads the matrix, the row sums and the overflow list only: no wait for the loop's side stream, no variable, Adam
+// slot or draw index changes.  U and ll cover the local cells, so a sharded handle needs no sums from its peers; it still takes part in ONE small collective,
+// the verdict on the input (a non-finite U is local), so that every rank returns the same code instead of one of them leaving the others waiting.
+int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, double* ll) {
+  if (!h || !E || !ll) return CA_ERR_INVALID;
+  CA_NOT_IN_RUN(h);
+  if (D < 0 || D > CA_LL_DMAX) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
+  if (D > 0 && (!U || !V)) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
+  HIPCK(h, hipSetDevice(h->device));
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg;
+  std::string bad;
+  // the sweep's table: per gene the columns [log E of the clones | V], in groups of NC columns, zero padded; where E = 0 the entry is 0 and the gene's mask has the bit
+  const int ncol = C + D;
+  const int NC = ncol <= 8 ? 8 : ncol <= 16 ? 16 : 32, ngrp = cdiv(ncol, NC), nct = ngrp * NC;
+  std::vector<double> tab((size_t)ngrp * Gp * NC, 0.0), logz0((size_t)C, 0.0), col((size_t)G);
+  std::vector<unsigned> zmask((size_t)ngrp * Gp, 0u);
+  for (int c = 0; c < C && bad.empty(); ++c) {
+    const int grp = c / NC, cc = c % NC;
+    for (int g = 0; g < G; ++g) {
+      const double v = E[hidx(h->layout, g, c, G, C)];
+      if (!std::isfinite(v) || v < 0.0) { bad = "expected expression has a negative or non-finite entry (gene " + std::to_string(g) + ", clone " + std::to_string(c) + ")"; break; }
+      col[(size_t)g] = v;
+      if (v > 0.0) tab[((size_t)grp * Gp + g) * NC + cc] = std::log(v);
+      else zmask[(size_t)grp * Gp + g] |= 1u << cc;
+    }
+    if (!bad.empty()) break;
+    const double sum = pairwise_sum(col.data(), 0, G);
+    if (!std::isfinite(sum) || sum == 0.0) { bad = "expected expression of clone " + std::to_string(c) + " sums to " + std::to_string(sum) + " over the genes"; break; }
+    logz0[(size_t)c] = std::log(sum);
+  }
+  for (int g = 0; g < G && D > 0 && bad.empty(); ++g)
+    for (int d = 0; d < D; ++d) {
+      const double v = V[hidx(h->layout, g, d, G, D)];
+      if (!std::isfinite(v)) { bad = "V has a non-finite entry (gene " + std::to_string(g) + ", factor " + std::to_string(d) + ")"; break; }
+      tab[((size_t)((C + d) / NC) * Gp + g) * NC + (C + d) % NC] = v;
+    }
+  // the contraction's operands (D > 0): U and V padded to CA_LL_DMAX factors, E in groups of NZ clone columns
+  const int NZ = C <= 8 ? 8 : C <= 16 ? 16 : 32, ngz = cdiv(C, NZ), nzt = ngz * NZ, nzc = cdiv(G, CA_LL_ZCHUNK);
+  std::vector<double> Ut, Vt, Ez;
+  if (D > 0 && bad.empty()) {
+    Ut.assign((size_t)N * CA_LL_DMAX, 0.0); Vt.assign((size_t)Gp * CA_LL_DMAX, 0.0); Ez.assign((size_t)ngz * Gp * NZ, 0.0);
+    for (int64_t n = 0; n < N && bad.empty(); ++n)
+      for (int d = 0; d < D; ++d) {
+        const double v = U[hidx(h->layout, n, d, N, D)];
+        if (!std::isfinite(v)) { bad = "U has a non-finite entry (cell " + std::to_string(n) + ", factor " + std::to_string(d) + ")"; break; }
+        Ut[(size_t)n * CA_LL_DMAX + d] = v;
+      }
+    for (int g = 0; g < G; ++g) {
+      for (int d = 0; d < D; ++d) Vt[(size_t)g * CA_LL_DMAX + d] = V[hidx(h->layout, g, d, G, D)];
+      for (int c = 0; c < C; ++c) Ez[((size_t)(c / NZ) * Gp + g) * NZ + c % NZ] = E[hidx(h->layout, g, c, G, C)];
+    }
+  }
+  if (is_sharded(h)) {   // [ranks whose input was refused]
+    std::vector<double> pack{bad.empty() ? 0.0 : 1.0};
+    double* scratch = nullptr;
+    HIPCK(h, hipMalloc((void**)&scratch, sizeof(double)));
+    const int rc = allreduce_host_vec(h, pack, scratch);
+    hipFree(scratch);
+    if (rc != CA_OK) return rc;
+    if (pack[0] != 0.0 && bad.empty()) bad = "another rank refused its input";
+  }
+  if (!bad.empty()) { h->err = "ca_clone_loglik: " + bad; return CA_ERR_INVALID; }
+  if (N == 0) return CA_OK;
+  std::vector<double> lgt;
+  if (with_const) { lgt.resize(CA_LL_LGTAB); for (int k = 0; k < CA_LL_LGTAB; ++k) lgt[(size_t)k] = std::lgamma((double)k + 1.0); }
+  // cells in batches, so that the partial slabs stay below a quarter of a gigabyte (a cell's sums do not depend on its batch)
+  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (D > 0 ? (int64_t)nzc * (nzt + 1) : 0)) * (int64_t)sizeof(double);
+  const int64_t NB = std::min<int64_t>(N, std::max<int64_t>(CA_TB, (((int64_t)1 << 28) / per_cell) / CA_TB * CA_TB));
+  std::vector<double> out((size_t)N * C);
+  double *tab_d = nullptr, *lgt_d = nullptr, *logz_d = nullptr, *Ut_d = nullptr, *Vt_d = nullptr, *Ez_d = nullptr, *part = nullptr, *lgpart = nullptr, *zpart = nullptr, *mpart = nullptr, *ll_d = nullptr;
+  unsigned* zm_d = nullptr;
+  auto cleanup = [&]() { hipFree(tab_d); hipFree(lgt_d); hipFree(logz_d); hipFree(Ut_d); hipFree(Vt_d); hipFree(Ez_d); hipFree(part); hipFree(lgpart); hipFree(zpart); hipFree(mpart); hipFree(ll_d); hipFree(zm_d); };
+#define PCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return CA_ERR_HIP; } } while (0)
+#define UP(dst, vec) do { PCK(hipMalloc((void**)&dst, (vec).size() * sizeof((vec)[0]))); PCK(hipMemcpyAsync(dst, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, h->stream)); } while (0)
+  UP(tab_d, tab); UP(zm_d, zmask); UP(logz_d, logz0);
+  if (with_const) UP(lgt_d, lgt);
+  if (D > 0) { UP(Ut_d, Ut); UP(Vt_d, Vt); UP(Ez_d, Ez); }
+  PCK(hipMalloc((void**)&part, (size_t)nseg * NB * nct * sizeof(double)));
+  if (with_const) PCK(hipMalloc((void**)&lgpart, (size_t)nseg * NB * sizeof(double)));
+  if (D > 0) {
+    PCK(hipMalloc((void**)&zpart, (size_t)nzc * NB * nzt * sizeof(double)));
+    PCK(hipMalloc((void**)&mpart, (size_t)nzc * NB * sizeof(double)));
+  }
+  PCK(hipMalloc((void**)&ll_d, (size_t)N * C * sizeof(double)));
+  for (int64_t n_lo = 0; n_lo < N; n_lo += NB) {
+    const int64_t n_cnt = std::min<int64_t>(NB, N - n_lo);
+    ca_ll_ops o;
+    o.tab = tab_d; o.zmask = zm_d; o.lgtab = lgt_d; o.part = part; o.lgpart = lgpart; o.n_lo = n_lo; o.n_cnt = n_cnt; o.NC = NC; o.ngrp = ngrp;
+    { const int rc = launch_clone_ll(h, o); if (rc != CA_OK) { cleanup(); return rc; } }
+    if (D > 0) {
+      ca_llz_ops z;
+      z.Ut = Ut_d; z.Vt = Vt_d; z.Ez = Ez_d; z.zpart = zpart; z.mpart = mpart; z.n_lo = n_lo; z.n_cnt = n_cnt; z.NC = NZ; z.ngrp = ngz; z.nzc = nzc;
+      { const int rc = launch_clone_ll_z(h, z); if (rc != CA_OK) { cleanup(); return rc; } }
+    }
+    hipLaunchKernelGGL(k_clone_ll_finish, dim3((unsigned)cdiv(n_cnt * C, CA_TB)), dim3(CA_TB), 0, h->stream, part, lgpart, zpart, mpart, logz_d, Ut_d, h->s64, ll_d, n_lo, n_cnt, C,
+                       (int)D, (int)nseg, nct, nzc, nzt);
+    PCK(hipGetLastError());
+  }
+  PCK(hipMemcpyAsync(out.data(), ll_d, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PCK(hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
+  cleanup();
+#undef UP
+#undef PCK
+  if (h->layout == CA_COL_MAJOR) { for (int64_t n = 0; n < N; ++n) for (int c = 0; c < C; ++c) ll[hidx(h->layout, n, c, N, C)] = out[(size_t)n * C + c]; }
+  else std::copy(out.begin(), out.end(), ll);
   return CA_OK;
 }
 

@@ -280,3 +280,38 @@ int launch_logexpr(ca_engine* h, const ca_lx_ops& o) {
   if (h->ystore == CA_YSTORE_U16) return logexpr_t<uint16_t>(h, o);
   return logexpr_t<float>(h, o);
 }
+
+// ---- k_clone_ll<YT, NC> / k_clone_ll_z<NC>: the log-likelihood sweep over the resident matrix in its storage and the contraction beside it (ca_clone_loglik; never the 4-bit loop image) ----
+// one batch of cells [n_lo, n_lo + n_cnt): the table of NC columns per gene and group (log E | V, zero padded) with its E = 0 masks, the partial slabs
+struct ca_ll_ops { const double* tab; const unsigned* zmask; const double* lgtab; double *part, *lgpart; int64_t n_lo, n_cnt; int NC, ngrp; };
+template <typename YT, int NC>
+int clone_ll_t(ca_engine* h, const ca_ll_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_clone_ll<YT, NC>), dim3((unsigned)((int64_t)cdiv(o.n_cnt, CA_TB) * h->nseg), (unsigned)o.ngrp), dim3(CA_TB), 0, h->stream,
+                                                (const YT*)h->Y, o.tab, o.zmask, o.lgtab, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, h->ovf_col, h->ovf_val, o.part, o.lgpart,
+                                                h->N, o.n_lo, o.n_cnt, h->G, h->Gp, h->nseg));
+  return CA_OK;
+}
+template <typename YT>
+int clone_ll_nc(ca_engine* h, const ca_ll_ops& o) {
+  if (o.NC == 8) return clone_ll_t<YT, 8>(h, o);
+  if (o.NC == 16) return clone_ll_t<YT, 16>(h, o);
+  return clone_ll_t<YT, 32>(h, o);
+}
+int launch_clone_ll(ca_engine* h, const ca_ll_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) return clone_ll_nc<uint8_t>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return clone_ll_nc<uint16_t>(h, o);
+  return clone_ll_nc<float>(h, o);
+}
+// the contraction Z of one batch (D > 0): NC clone columns per group of the table E
+struct ca_llz_ops { const double *Ut, *Vt, *Ez; double *zpart, *mpart; int64_t n_lo, n_cnt; int NC, ngrp, nzc; };
+template <int NC>
+int clone_ll_z_t(ca_engine* h, const ca_llz_ops& o) {
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_clone_ll_z<NC>), dim3((unsigned)cdiv(o.n_cnt, CA_TB), (unsigned)o.nzc, (unsigned)o.ngrp), dim3(CA_TB), 0, h->stream, o.Ut, o.Vt,
+                                                o.Ez, o.zpart, o.mpart, o.n_lo, o.n_cnt, h->G, h->Gp));
+  return CA_OK;
+}
+int launch_clone_ll_z(ca_engine* h, const ca_llz_ops& o) {
+  if (o.NC == 8) return clone_ll_z_t<8>(h, o);
+  if (o.NC == 16) return clone_ll_z_t<16>(h, o);
+  return clone_ll_z_t<32>(h, o);
+}

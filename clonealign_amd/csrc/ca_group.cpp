@@ -686,6 +686,33 @@ int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell, const doub
   return CA_OK;
 }
 
+int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, double* ll) {
+  GROUP_ALIVE(g);
+  if (!E || !ll) return CA_ERR_INVALID;
+  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
+    g->err = "ca_clone_loglik: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
+    return CA_ERR_INVALID;
+  }
+  std::vector<std::vector<double>> us((size_t)g->W), part((size_t)g->W);
+  for (int r = 0; r < g->W; ++r) {
+    if (D > 0) slice_rows(U, g->layout, g->N, D, g->shard[(size_t)r].lo, g->shard[(size_t)r].hi, us[(size_t)r]);
+    part[(size_t)r].resize((size_t)((g->shard[(size_t)r].hi - g->shard[(size_t)r].lo) * g->C));
+  }
+  const int s = settle(g, dispatch(g, [&](int r) {
+    return ca_clone_loglik(g->h[(size_t)r], E, D > 0 ? us[(size_t)r].data() : nullptr, V, D, with_const, part[(size_t)r].data());
+  }), "ca_clone_loglik");
+  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  if (s != CA_OK) return s;
+  for (int r = 0; r < g->W; ++r) scatter_rows(part[(size_t)r].data(), g->layout, g->N, g->C, g->shard[(size_t)r].lo, g->shard[(size_t)r].hi, ll);
+  return CA_OK;
+}
+
 int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell, int32_t n_groups, const double* size_factor, double* S1, double* S2, int64_t* n_group) {
   GROUP_ALIVE(g);
   if (!group_of_cell || !S1 || !S2 || !n_group) return CA_ERR_INVALID;

@@ -45,6 +45,8 @@ EXPORTS = (
     "ca_fit_mse", "ca_group_fit_mse",
     # log-expression sums per gene and cell group on the resident matrix (plot_clonealign), additions to ABI 6
     "ca_logexpr_sums", "ca_group_logexpr_sums",
+    # per-cell, per-clone log-likelihood of the resident matrix under a fitted model (clone_loglik / assign_cells), additions to ABI 6
+    "ca_clone_loglik", "ca_group_clone_loglik",
 )
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
@@ -151,6 +153,7 @@ def load_library(path=None):
     lib.ca_clone_gene_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_fit_mse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.ca_logexpr_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ca_clone_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -181,6 +184,7 @@ def load_library(path=None):
     lib.ca_group_clone_gene_sums.argtypes = lib.ca_clone_gene_sums.argtypes
     lib.ca_group_fit_mse.argtypes = lib.ca_fit_mse.argtypes
     lib.ca_group_logexpr_sums.argtypes = lib.ca_logexpr_sums.argtypes
+    lib.ca_group_clone_loglik.argtypes = lib.ca_clone_loglik.argtypes
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -636,6 +640,33 @@ class HipEngine:
         self._ck(self._fn("logexpr_sums")(self.h, gi.ctypes.data_as(C.c_void_p), Q, None if sf is None else sf.ctypes.data_as(C.c_void_p),
                                           S1.ctypes.data_as(C.c_void_p), S2.ctypes.data_as(C.c_void_p), ng.ctypes.data_as(C.c_void_p)))
         return {"S1": S1, "S2": S2, "n_group": ng}
+
+    def clone_loglik(self, E, U=None, V=None, const=True):
+        """Log-likelihood ``ll`` [N, C] of every resident cell under every clone at point estimates, in one float64 sweep over the resident matrix
+        (ca_clone_loglik; p_y_on_c of R/inference-tflow.R:288-296): ``Multinomial(total = s_n, probs ~ E[:, c] * exp(U[n] @ V.T)).log_prob(y_n)``.
+        ``E`` [G, C] non-negative (a fit gives ``mu[:, None] * L``); ``U`` [N, D] and ``V`` [G, D], 0 <= D <= 8, or both None (a fit gives
+        ``[psi | x]`` and ``[W | beta]``); ``const=False`` leaves out ``lgamma(s + 1) - sum(lgamma(y + 1))``.  A positive count against ``E = 0`` gives
+        exactly ``-inf``, a zero count against it adds nothing; no NaN.  Changes nothing in the engine; two calls agree bit for bit."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"clone_loglik: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        if (U is None) != (V is None):
+            raise ValueError("clone_loglik: U and V go together (both, or neither)")
+        D = 0
+        Um = Vm = None
+        if U is not None:
+            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
+                raise ValueError(f"clone_loglik: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
+            D = int(U.shape[1])
+            if D > 0:
+                Um = np.require(U, requirements=[self._order, "A"])
+                Vm = np.require(V, requirements=[self._order, "A"])
+        Em = np.require(E, requirements=[self._order, "A"])
+        ll = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self._fn("clone_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(ll)))
+        return ll
 
     def synchronize(self):
         self._ck(self.lib.ca_synchronize(self.h))

@@ -396,6 +396,27 @@ int ca_clone_gene_sums(ca_handle h, const int32_t* clone_of_cell, double* T, dou
 int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, double* sse_total, int64_t* n_cells_used,
                double* sse_gene, double* sse_cell);
 
+/* Per-cell, per-clone log-likelihood of the resident counts under a fitted model at its point estimates: the reference's p_y_on_c
+ * (R/inference-tflow.R:288-296) with mu_samples replaced by the point estimate, in ONE float64 sweep over the resident counts (any
+ * storage; the matrix is not shipped back and no N x G array is made).  E: expected expression, G x C, non-negative (a fit gives
+ * mu_g L[g][c]); U (N x D) and V (G x D), 0 <= D <= 8: per-cell and per-gene factors of the exponent eta_ng = sum_d U[n][d] V[g][d]
+ * (a fit gives U = [psi | x], V = [W | beta]); both may be NULL when D = 0.  Matrices in the problem's layout.
+ *   ll[n][c] = sum_g xlogy(y_ng, E[g][c]) + sum_g y_ng eta_ng - s_n log sum_g E[g][c] exp(eta_ng) + const_n,      s_n = sum_g y_ng
+ *   const_n  = lgamma(s_n + 1) - sum_g lgamma(y_ng + 1)   when with_const != 0, else 0
+ * i.e. Multinomial(total = s_n, probs ~ E[.][c] exp(eta_n.)).log_prob(y_n).  Rules:
+ *   xlogy: a count of 0 against E = 0 adds 0; a positive count against E = 0 makes that ll[n][c] exactly -inf; no NaN is produced,
+ *     neither in that cell's other clones nor anywhere else.
+ *   log sum_g E exp(eta) is taken under a per-cell shift by max_g eta_ng: it does not overflow while ll itself is representable.
+ *   Everything is float64; sums run in a fixed order (no atomics): two calls agree bit for bit; a cell's row of ll does not depend on
+ *     its place in the launch, so a cell-sharded group returns the single handle's bits.
+ * CA_ERR_INVALID (with a message naming the clone, gene or cell): D outside [0, 8]; D > 0 with U or V NULL; an entry of E negative or
+ * non-finite; a column of E that sums to zero or to a non-finite value; a non-finite entry of U or V.
+ * Sharded handle: U and ll cover the local cells; the only collective is the verdict on the input, so that input refused on one
+ * rank (a non-finite U is local) is refused on every rank.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_clone_loglik(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */,
+                    int32_t D, int32_t with_const, double* ll /* N x C */);
+
 /* The data side of plot_clonealign() (R/plotting.R:177-205: the dense t(logcounts), its N*G-row long table, the per-gene mean and
  * sd and the per (clone, gene) means of the z-scores) as sums from ONE sweep over the resident counts (any storage; nothing N x G
  * is made on the host).  group_of_cell[n] in [0, n_groups), or -1 for a cell left out of every sum and count; n_groups in [1, 64].
@@ -525,6 +546,9 @@ int ca_group_clone_gene_sums(ca_group_handle g, const int32_t* clone_of_cell /* 
 /* ca_fit_mse (R/clonealign.R:415-434) over the group: clone_of_cell and sse_cell hold ALL cells; the totals are rank 0's (every rank has the same) */
 int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell /* N, all cells */, const double* E, double* sse_total,
                      int64_t* n_cells_used, double* sse_gene, double* sse_cell /* N, all cells, or NULL */);
+/* ca_clone_loglik (R/inference-tflow.R:288-296) over the group: U and ll hold ALL cells (sliced by the shards); each cell's row is the single handle's, bit for bit */
+int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D,
+                          int32_t with_const, double* ll /* N x C, all cells */);
 /* ca_logexpr_sums (R/plotting.R:177-205) over the group: group_of_cell and size_factor (or NULL) hold ALL cells; the totals are rank 0's (every rank has the same) */
 int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell /* N, all cells */, int32_t n_groups,
                           const double* size_factor /* N, all cells, or NULL */, double* S1, double* S2, int64_t* n_group);
