@@ -355,6 +355,231 @@ def assign_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=N
                          clone_names=names, ml_params={"clone_probs": probs})
 
 
+def _project_cells_host(Y, E, V, K, P, X, log_prior, psi_start, const=True, max_iter=25, tol=1e-9, max_step=1.0, chunk=2048):
+    """Float64 numpy restatement of ``HipEngine.project_cells`` (ca_project_cells; the algorithm is stated in include/clonealign_hip.h), step for step,
+    ``chunk`` cells at a time: Y [N, G] dense or scipy.sparse, E [G, C], V = [W | beta] [G, K + P] or None, X [N, P] or None, log_prior [N, C] or None,
+    psi_start [N, K] or None.  Any K (the device takes K <= 2).  Same return value, same rules, same refusals (ValueError)."""
+    from scipy.special import gammaln
+    E = np.asarray(E, dtype=np.float64)
+    N, G = Y.shape
+    K, P = int(K), int(P)
+    D = K + P
+    if E.ndim != 2 or E.shape[0] != G:
+        raise ValueError(f"project_cells: Y is {N} x {G} but E is {E.shape}")
+    C = E.shape[1]
+    if K < 0:
+        raise ValueError(f"project_cells: K = {K} is negative")
+    if P < 0 or D > 8:
+        raise ValueError(f"project_cells: K + P = {D} is outside [0, 8]")
+    if D > 0 and V is None:
+        raise ValueError(f"project_cells: K + P = {D} needs V (genes x (K + P))")
+    if P > 0 and X is None:
+        raise ValueError(f"project_cells: P = {P} needs X (cells x P)")
+    if max_iter < 0:
+        raise ValueError(f"project_cells: max_iter = {max_iter} is negative")
+    for name, v in (("tol", tol), ("max_step", max_step)):
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"project_cells: {name} = {v} is not a positive finite number")
+    V = np.zeros((G, 0)) if D == 0 else np.asarray(V, dtype=np.float64)
+    X = np.zeros((N, 0)) if P == 0 else np.asarray(X, dtype=np.float64)
+    psi = np.zeros((N, K)) if psi_start is None or K == 0 else np.array(psi_start, dtype=np.float64)
+    if V.shape != (G, D) or X.shape != (N, P) or psi.shape != (N, K):
+        raise ValueError(f"project_cells: V is {V.shape}, X {X.shape}, psi_start {psi.shape}; expected ({G}, {D}), ({N}, {P}), ({N}, {K})")
+    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
+    if wrong.size:
+        raise ValueError(f"project_cells: expected expression has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
+    esum = E.sum(0)
+    wrong = np.flatnonzero(~np.isfinite(esum) | (esum == 0))
+    if wrong.size:
+        raise ValueError(f"project_cells: expected expression of clone {wrong[0]} sums to {esum[wrong[0]]} over the genes")
+    for name, M, row, colname in (("V", V, "gene", "factor"), ("psi_start", psi, "cell", "factor"), ("X", X, "cell", "covariate")):
+        if M.size and not np.isfinite(M).all():
+            r, d = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"project_cells: {name} has a non-finite entry ({row} {r}, {colname} {d})")
+    lp = None
+    if log_prior is not None:
+        lp = np.asarray(log_prior, dtype=np.float64)
+        if lp.shape != (N, C):
+            raise ValueError(f"project_cells: log_prior is {lp.shape}; expected ({N}, {C})")
+        wrong = np.argwhere(np.isnan(lp) | np.isposinf(lp))
+        if wrong.size:
+            raise ValueError(f"project_cells: log_prior has a NaN or +inf entry (cell {wrong[0][0]}, clone {wrong[0][1]}); -inf excludes a clone")
+    zero = E == 0
+    logE = np.log(np.where(zero, 1.0, E))                            # xlogy: 0 where E = 0, put right below
+    W = V[:, :K]
+    tri = [(k, l) for k in range(K) for l in range(k, K)]
+    out = {"psi": psi, "ll": np.empty((N, C)), "clone_probs": np.empty((N, C)), "objective": np.empty(N), "rounds": np.zeros(N, dtype=np.int32),
+           "converged": np.zeros(N, dtype=bool)}
+    for lo in range(0, N, int(chunk)):
+        Yc = Y[lo:lo + int(chunk)]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+        n = Yc.shape[0]
+        s = Yc.sum(1)
+        A = Yc @ logE                                                # the sweep: A, B, s and the constant
+        if zero.any():
+            A[((Yc > 0).astype(np.float64) @ zero.astype(np.float64)) > 0] = -np.inf
+        if const:
+            A += (gammaln(s + 1.0) - gammaln(Yc + 1.0).sum(1))[:, None]
+        B = Yc @ V
+        U = np.concatenate([psi[lo:lo + n], X[lo:lo + n]], axis=1)
+        lpc = 0.0 if lp is None else lp[lo:lo + n]
+        frozen = np.zeros(n, dtype=bool)
+
+        def evaluate(i, moments):
+            """steps 1-2 (and the moments of step 3) for the cells i of the chunk"""
+            eta = U[i] @ V.T
+            m = eta.max(1) if G else np.zeros(i.size)
+            w = np.exp(eta - m[:, None])
+            Z0 = w @ E
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ll = A[i] + (U[i] * B[i]).sum(1)[:, None] - np.where(s[i, None] > 0, s[i, None] * (m[:, None] + np.log(Z0)), 0.0)
+                t = ll + (lpc if lp is None else lpc[i])
+                M = t.max(1)
+                lse = M + np.log(np.exp(t - M[:, None]).sum(1))       # (a row of -inf: NaN - no clone is possible)
+                gamma = np.exp(t - lse[:, None])
+            if not moments:
+                return ll, gamma, lse, M, None, None
+            mean = np.empty((i.size, C, K))
+            cov = np.empty((i.size, C, K, K))
+            for k in range(K):
+                wk = w * W[:, k]
+                mean[:, :, k] = (wk @ E) / Z0
+                for l in range(k, K):
+                    cov[:, :, k, l] = cov[:, :, l, k] = ((wk * W[:, l]) @ E) / Z0
+            cov -= mean[:, :, :, None] * mean[:, :, None, :]
+            return ll, gamma, lse, M, mean, cov
+
+        def settle(i, ll, gamma, lse, M, ok, used):
+            """freeze the cells i with this evaluation's outputs"""
+            dead = np.isneginf(M)
+            j = lo + i
+            out["ll"][j], out["clone_probs"][j] = ll, gamma
+            out["objective"][j] = np.where(dead, -np.inf, lse - 0.5 * (U[i, :K] ** 2).sum(1))
+            out["rounds"][j] = np.where(dead, 0, used)
+            out["converged"][j] = ok & ~dead
+            frozen[i] = True
+
+        for t in range(int(max_iter) if K > 0 else 0):
+            i = np.flatnonzero(~frozen)
+            if i.size == 0:
+                break
+            ll, gamma, lse, M, mean, cov = evaluate(i, True)
+            dead = np.isneginf(M)
+            g0 = np.where(dead[:, None], 0.0, gamma)                 # (a cell without a possible clone takes no step)
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                g = B[i, :K] - s[i, None] * np.einsum("nc,nck->nk", g0, mean) - U[i, :K]
+                H = np.eye(K)[None] + s[i, None, None] * np.einsum("nc,nckl->nkl", g0, cov)
+                if K == 1:
+                    d = g / H[:, 0]
+                elif K == 2:                                             # the closed form the device uses
+                    det = H[:, 0, 0] * H[:, 1, 1] - H[:, 0, 1] * H[:, 0, 1]
+                    d = np.stack([(H[:, 1, 1] * g[:, 0] - H[:, 0, 1] * g[:, 1]) / det, (H[:, 0, 0] * g[:, 1] - H[:, 0, 1] * g[:, 0]) / det], axis=1)
+                else:
+                    d = np.linalg.solve(H, g[:, :, None])[:, :, 0]
+                dmax = np.abs(d).max(1)
+            nan = ~(dmax < np.inf)                                        # a step that is no number: the cell stops where it is, not converged
+            stop = dead | nan | (dmax <= tol)
+            if stop.any():
+                settle(i[stop], ll[stop], gamma[stop], lse[stop], M[stop], (dmax <= tol)[stop], t + 1)
+            go = ~stop
+            f = np.where(dmax[go] > max_step, max_step / dmax[go], 1.0)
+            U[i[go], :K] += d[go] * f[:, None]
+        i = np.flatnonzero(~frozen)
+        if i.size:                                                   # the cells that never froze: ll and the posterior at the psi they hold
+            ll, gamma, lse, M, _m, _c = evaluate(i, False)
+            settle(i, ll, gamma, lse, M, np.full(i.size, K == 0), int(max_iter) if K > 0 else 0)
+        psi[lo:lo + n] = U[:, :K]
+    return out
+
+
+def project_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=None, x=None, psi_start=None, saturate=True, saturation_threshold=6,
+                  const=True, max_iter=25, tol=1e-9, max_step=1.0, engine=None, engine_opts=None):
+    """Place cells the fit never saw: for every cell of ``Y`` the MAP value of its latent factor ``psi`` under the fit's gene-level parameters (``mu``,
+    ``W``, ``beta``, ``alpha``) and the exact clone posterior at it, without refitting -- ``assign_cells`` with the ``W`` term switched on.  Per cell it
+    maximises ``F(psi) = logsumexp_c(ll_c(psi) + log alpha_c + extra_loglik_c) - |psi|^2 / 2`` (``ll`` is ``clone_loglik``'s; the prior is the
+    reference's ``Normal(0, 1)``, R/inference-tflow.R:318-319) by generalised EM with one safeguarded Newton step per round, from ``psi_start`` (default
+    0); a cell stops when its step falls to ``tol`` or after ``max_iter`` rounds (include/clonealign_hip.h states the algorithm).
+
+    ``Y``, ``L``, ``x``, ``saturate``, ``const``, ``engine`` and ``engine_opts`` as for ``clone_loglik``: one float64 sweep over the matrix on the device,
+    then two launches per round that do not read it (``HipEngine.project_cells``); an engine without the method gets the chunked float64 host form.
+    The device takes fits with ``K <= 2`` (ValueError otherwise).
+    Returns a :class:`ClonealignFit` with ``psi`` [cells, K], ``clone_probs``, ``clone``, ``loglik`` (``F + |psi|^2 / 2``: the cell's marginal over the
+    clones at its psi), ``objective`` (``F``), ``clone_loglik`` [cells, clones], ``rounds``, ``converged`` and ``clone_names``;
+    ``recompute_clone_assignment`` works on it.  A fit with ``K = 0`` returns what ``assign_cells`` returns, plus an empty ``psi``."""
+    ml = fit["ml_params"]
+    Lm, cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if Lm.shape[0] != G:
+        raise ValueError(f"L has {Lm.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    W = np.asarray(ml["W"], dtype=np.float64).reshape(G, -1) if ml.get("W") is not None else np.zeros((G, 0))
+    K = W.shape[1]
+    if K == 0:
+        out = assign_cells(fit, Y, L, clone_assignment_probability, extra_loglik=extra_loglik, x=x, saturate=saturate,
+                           saturation_threshold=saturation_threshold, const=const, engine=engine, engine_opts=engine_opts)
+        out.update(psi=np.zeros((N, 0)), objective=out["loglik"].copy(), rounds=np.zeros(N, dtype=np.int32), converged=np.isfinite(out["loglik"]))
+        out["ml_params"] = {"psi": out["psi"], "clone_probs": out["clone_probs"]}
+        return out
+    mu = np.asarray(ml["mu"], dtype=np.float64).reshape(-1)
+    if mu.shape[0] != G:
+        raise ValueError(f"fit$ml_params$mu has length {mu.shape[0]} but L has {G} rows: evaluate on the retained genes")
+    C = Lm.shape[1]
+    if "clone_names" in fit and len(fit["clone_names"]) != C:
+        raise ValueError(f"fit has {len(fit['clone_names'])} clone names but L has {C} columns (clones)")
+    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(C)])
+    if saturate:
+        Lm = hostprep.saturate(Lm, saturation_threshold)             # :142-144
+    E = mu[:, None] * Lm
+    beta = np.asarray(ml["beta"], dtype=np.float64).reshape(G, -1) if ml.get("beta") is not None else np.zeros((G, 0))
+    P = beta.shape[1]
+    if (P > 0) != (x is not None):
+        raise ValueError(f"x is required exactly when the fit has beta: the fit has {P} covariates and x is {'missing' if x is None else 'given'}")
+    if K + P > 8:
+        raise ValueError(f"the fit has {K + P} exponent factors (K + P); at most 8 are supported")
+    if P > 0:
+        x = np.asarray(x, dtype=np.float64)
+        x = x.reshape(-1, 1) if x.ndim == 1 else x
+        if x.shape != (N, P):
+            raise ValueError(f"x is {x.shape} but Y has {N} rows (cells) and the fit {P} covariates")
+    if psi_start is not None:
+        psi_start = np.asarray(psi_start, dtype=np.float64)
+        if psi_start.size != N * K:
+            raise ValueError(f"psi_start has {psi_start.size} entries but Y has {N} rows (cells) and the fit K = {K}")
+        psi_start = psi_start.reshape(N, K)
+    V = np.concatenate([W, beta], axis=1)
+    alpha = ml.get("alpha")
+    lp = None
+    if alpha is not None or extra_loglik is not None:
+        with np.errstate(divide="ignore"):
+            lp = np.zeros((N, C)) + (0.0 if alpha is None else np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C)))   # :308
+        if extra_loglik is not None:
+            ex = np.asarray(extra_loglik, dtype=np.float64)
+            if ex.shape != (N, C):
+                raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
+            lp = lp + ex
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, Lm, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    try:
+        if hasattr(engine, "project_cells"):
+            if (engine.N, engine.G) != (N, G):
+                raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+            if K > 2:
+                raise ValueError(f"the fit has K = {K} latent factors; the device form of project_cells takes K <= 2")
+            r = engine.project_cells(E, V, K, X=x if P > 0 else None, log_prior=lp, psi_start=psi_start, const=const, max_iter=max_iter, tol=tol,
+                                     max_step=max_step)
+        else:
+            r = _project_cells_host(Y, E, V, K, P, x if P > 0 else None, lp, psi_start, const, max_iter, tol, max_step)
+    finally:
+        if own:
+            engine.close()
+    psi, probs = r["psi"], r["clone_probs"]
+    return ClonealignFit(psi=psi, clone_probs=probs, clone=clone_assignment(probs, names, clone_assignment_probability),
+                         loglik=r["objective"] + 0.5 * (psi ** 2).sum(1), objective=r["objective"], clone_loglik=r["ll"], rounds=r["rounds"],
+                         converged=r["converged"], clone_names=names, ml_params={"psi": psi, "clone_probs": probs})
+
+
 def _logexpr_sums_host(Y, group_idx, n_groups, size_factors=None, chunk=4096):
     """Float64 host form of ``HipEngine.logexpr_sums`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time),
     ``group_idx`` in [-1, n_groups) with -1 = leave the cell out.  Same return value, same refusals (ValueError)."""

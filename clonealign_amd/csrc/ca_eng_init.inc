@@ -1,4 +1,4 @@
-// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit (ca_fit_mse), the per-cell, per-clone log-likelihood under a fit (ca_clone_loglik), log-expression sums per gene and cell group (ca_logexpr_sums).
+// ca_eng_init.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit (ca_fit_mse), the per-cell, per-clone log-likelihood under a fit (ca_clone_loglik), the per-cell MAP psi of cells outside a fit (ca_project_cells), log-expression sums per gene and cell group (ca_logexpr_sums).
 extern "C++" {   // (templates: this part sits inside the C ABI's extern "C" block)
 namespace {
 // Transformed pass over Y with explicit factor buffers (PCA init): row products Y'.Vp -> YWp, column products Y'^T.Fp -> YTp
@@ -412,23 +412,15 @@ int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, doubl
   return CA_OK;
 }
 
-// p_y_on_c (R/inference-tflow.R:288-296) at a fit's point estimates on the resident matrix: ll[n][c] for every cell and clone (include/clonealign_hip.h has the
-// formula and the rules).  Like ca_fit_mse it reads the matrix, the row sums and the overflow list only: no wait for the loop's side stream, no variable, Adam
-// slot or draw index changes.  U and ll cover the local cells, so a sharded handle needs no sums from its peers; it still takes part in ONE small collective,
-// the verdict on the input (a non-finite U is local), so that every rank returns the same code instead of one of them leaving the others waiting.
-int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, double* ll) {
-  if (!h || !E || !ll) return CA_ERR_INVALID;
-  CA_NOT_IN_RUN(h);
-  if (D < 0 || D > CA_LL_DMAX) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
-  if (D > 0 && (!U || !V)) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
-  HIPCK(h, hipSetDevice(h->device));
-  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg;
+// The table of the log-likelihood sweep (k_clone_ll; ca_clone_loglik and ca_project_cells): per gene the columns [log E of the clones | V], in groups of NC
+// columns, zero padded; where E = 0 the entry is 0 and the gene's mask has the bit.  logz0[c] = log sum_g E[g][c].  Returns the refusal, or "".
+extern "C++" {
+namespace {
+std::string ll_sweep_table(ca_engine* h, const double* E, const double* V, int D, int NC, int ngrp, std::vector<double>& tab, std::vector<unsigned>& zmask, std::vector<double>& logz0) {
+  const int G = h->G, Gp = h->Gp, C = h->C;
   std::string bad;
-  // the sweep's table: per gene the columns [log E of the clones | V], in groups of NC columns, zero padded; where E = 0 the entry is 0 and the gene's mask has the bit
-  const int ncol = C + D;
-  const int NC = ncol <= 8 ? 8 : ncol <= 16 ? 16 : 32, ngrp = cdiv(ncol, NC), nct = ngrp * NC;
-  std::vector<double> tab((size_t)ngrp * Gp * NC, 0.0), logz0((size_t)C, 0.0), col((size_t)G);
-  std::vector<unsigned> zmask((size_t)ngrp * Gp, 0u);
+  std::vector<double> col((size_t)G);
+  tab.assign((size_t)ngrp * Gp * NC, 0.0); logz0.assign((size_t)C, 0.0); zmask.assign((size_t)ngrp * Gp, 0u);
   for (int c = 0; c < C && bad.empty(); ++c) {
     const int grp = c / NC, cc = c % NC;
     for (int g = 0; g < G; ++g) {
@@ -449,6 +441,28 @@ int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double*
       if (!std::isfinite(v)) { bad = "V has a non-finite entry (gene " + std::to_string(g) + ", factor " + std::to_string(d) + ")"; break; }
       tab[((size_t)((C + d) / NC) * Gp + g) * NC + (C + d) % NC] = v;
     }
+  return bad;
+}
+}  // namespace
+}  // extern "C++"
+
+// p_y_on_c (R/inference-tflow.R:288-296) at a fit's point estimates on the resident matrix: ll[n][c] for every cell and clone (include/clonealign_hip.h has the
+// formula and the rules).  Like ca_fit_mse it reads the matrix, the row sums and the overflow list only: no wait for the loop's side stream, no variable, Adam
+// slot or draw index changes.  U and ll cover the local cells, so a sharded handle needs no sums from its peers; it still takes part in ONE small collective,
+// the verdict on the input (a non-finite U is local), so that every rank returns the same code instead of one of them leaving the others waiting.
+int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, double* ll) {
+  if (!h || !E || !ll) return CA_ERR_INVALID;
+  CA_NOT_IN_RUN(h);
+  if (D < 0 || D > CA_LL_DMAX) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
+  if (D > 0 && (!U || !V)) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
+  HIPCK(h, hipSetDevice(h->device));
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg;
+  // the sweep's table: per gene the columns [log E of the clones | V], in groups of NC columns, zero padded; where E = 0 the entry is 0 and the gene's mask has the bit
+  const int ncol = C + D;
+  const int NC = ncol <= 8 ? 8 : ncol <= 16 ? 16 : 32, ngrp = cdiv(ncol, NC), nct = ngrp * NC;
+  std::vector<double> tab, logz0;
+  std::vector<unsigned> zmask;
+  std::string bad = ll_sweep_table(h, E, V, D, NC, ngrp, tab, zmask, logz0);
   // the contraction's operands (D > 0): U and V padded to CA_LL_DMAX factors, E in groups of NZ clone columns
   const int NZ = C <= 8 ? 8 : C <= 16 ? 16 : 32, ngz = cdiv(C, NZ), nzt = ngz * NZ, nzc = cdiv(G, CA_LL_ZCHUNK);
   std::vector<double> Ut, Vt, Ez;
@@ -518,6 +532,153 @@ int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double*
 #undef PCK
   if (h->layout == CA_COL_MAJOR) { for (int64_t n = 0; n < N; ++n) for (int c = 0; c < C; ++c) ll[hidx(h->layout, n, c, N, C)] = out[(size_t)n * C + c]; }
   else std::copy(out.begin(), out.end(), ll);
+  return CA_OK;
+}
+
+// Per-cell MAP psi and the clone posterior at it for the resident cells under a fit's gene-level parameters (include/clonealign_hip.h has the algorithm and the
+// rules).  ONE sweep over the matrix (k_clone_ll against [log E | V]: A, B and the constant), then rounds of two launches that never read it, queued back to
+// back; every few rounds the host reads the frozen flags and stops queuing when no cell is left -- freezing is per cell, so WHEN the host looks changes no
+// result.  Read-only like ca_clone_loglik; a sharded handle takes part in ONE small collective, the verdict on the input.
+int ca_project_cells(ca_handle h, const double* E, const double* V, int32_t K, int32_t P, const double* X, const double* log_prior, const double* psi_start,
+                     int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi, double* ll, double* clone_probs, double* objective,
+                     int32_t* rounds, uint8_t* converged) {
+  if (!h || !E || !ll || !clone_probs || !objective || !rounds || !converged || (K > 0 && !psi)) return CA_ERR_INVALID;
+  CA_NOT_IN_RUN(h);
+  const int D = K + P;
+  auto refuse = [&](const std::string& why) { h->err = "ca_project_cells: " + why; return CA_ERR_INVALID; };   // (these are the same on every rank: no collective)
+  if (K < 0 || K > CA_PROJ_KMAX) return refuse("K = " + std::to_string(K) + " is outside [0, " + std::to_string(CA_PROJ_KMAX) + "] (the device limit of the moment kernel)");
+  if (P < 0 || D > CA_LL_DMAX) return refuse("K + P = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]");
+  if (D > 0 && !V) return refuse("K + P = " + std::to_string(D) + " needs V (genes x (K + P))");
+  if (P > 0 && !X) return refuse("P = " + std::to_string(P) + " needs X (cells x P)");
+  if (max_iter < 0) return refuse("max_iter = " + std::to_string(max_iter) + " is negative");
+  if (!(tol > 0.0) || !std::isfinite(tol)) return refuse("tol = " + std::to_string(tol) + " is not a positive finite number");
+  if (!(max_step > 0.0) || !std::isfinite(max_step)) return refuse("max_step = " + std::to_string(max_step) + " is not a positive finite number");
+  const int poll_set = (with_const >> 8) & 0xFF, poll = poll_set ? poll_set : 4;   // rounds between two looks at the frozen flags (255: practically never)
+  const bool lgc = (with_const & 1) != 0;
+  HIPCK(h, hipSetDevice(h->device));
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg;
+  const int ncol = C + D;
+  const int NC = ncol <= 8 ? 8 : ncol <= 16 ? 16 : 32, ngrp = cdiv(ncol, NC), nct = ngrp * NC;
+  std::vector<double> tab, logz0;
+  std::vector<unsigned> zmask;
+  std::string bad = ll_sweep_table(h, E, V, D, NC, ngrp, tab, zmask, logz0);
+  // the moments' operands: U = [psi | x] and V padded to CA_LL_DMAX factors, E in groups of NZ clone columns
+  const int NM = 1 + K + K * (K + 1) / 2;
+  const int NZ = (K <= 1 && C > 8) ? 16 : 8, ngz = cdiv(C, NZ), nmt = ngz * NZ * NM, nzc = cdiv(G, CA_LL_ZCHUNK);
+  std::vector<double> Ut((size_t)N * CA_LL_DMAX, 0.0), Vt((size_t)Gp * CA_LL_DMAX, 0.0), Ez((size_t)ngz * Gp * NZ, 0.0), lp;
+  for (int64_t n = 0; n < N && bad.empty(); ++n) {
+    for (int k = 0; k < K && psi_start; ++k) {
+      const double v = psi_start[hidx(h->layout, n, k, N, K)];
+      if (!std::isfinite(v)) { bad = "psi_start has a non-finite entry (cell " + std::to_string(n) + ", factor " + std::to_string(k) + ")"; break; }
+      Ut[(size_t)n * CA_LL_DMAX + k] = v;
+    }
+    for (int p = 0; p < P && bad.empty(); ++p) {
+      const double v = X[hidx(h->layout, n, p, N, P)];
+      if (!std::isfinite(v)) { bad = "X has a non-finite entry (cell " + std::to_string(n) + ", covariate " + std::to_string(p) + ")"; break; }
+      Ut[(size_t)n * CA_LL_DMAX + K + p] = v;
+    }
+  }
+  if (log_prior && bad.empty()) {
+    lp.resize((size_t)N * C);
+    for (int64_t n = 0; n < N && bad.empty(); ++n)
+      for (int c = 0; c < C; ++c) {
+        const double v = log_prior[hidx(h->layout, n, c, N, C)];
+        if (std::isnan(v) || v == HUGE_VAL) { bad = "log_prior has a NaN or +inf entry (cell " + std::to_string(n) + ", clone " + std::to_string(c) + "); -inf excludes a clone"; break; }
+        lp[(size_t)n * C + c] = v;
+      }
+  }
+  if (bad.empty())
+    for (int g = 0; g < G; ++g) {
+      for (int d = 0; d < D; ++d) Vt[(size_t)g * CA_LL_DMAX + d] = V[hidx(h->layout, g, d, G, D)];
+      for (int c = 0; c < C; ++c) Ez[((size_t)(c / NZ) * Gp + g) * NZ + c % NZ] = E[hidx(h->layout, g, c, G, C)];
+    }
+  if (is_sharded(h)) {   // [ranks whose input was refused]
+    std::vector<double> pack{bad.empty() ? 0.0 : 1.0};
+    double* scratch = nullptr;
+    HIPCK(h, hipMalloc((void**)&scratch, sizeof(double)));
+    const int rc = allreduce_host_vec(h, pack, scratch);
+    hipFree(scratch);
+    if (rc != CA_OK) return rc;
+    if (pack[0] != 0.0 && bad.empty()) bad = "another rank refused its input";
+  }
+  if (!bad.empty()) return refuse(bad);
+  if (N == 0) return CA_OK;
+  std::vector<double> lgt;
+  if (lgc) { lgt.resize(CA_LL_LGTAB); for (int k = 0; k < CA_LL_LGTAB; ++k) lgt[(size_t)k] = std::lgamma((double)k + 1.0); }
+  // cells in batches, so that the partial slabs stay below a quarter of a gigabyte (a cell's results do not depend on its batch)
+  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (int64_t)nzc * (nmt + 1)) * (int64_t)sizeof(double);
+  const int64_t NB = std::min<int64_t>(N, std::max<int64_t>(CA_TB, (((int64_t)1 << 28) / per_cell) / CA_TB * CA_TB));
+  std::vector<double> o_ll((size_t)N * C), o_pr((size_t)N * C), o_u((size_t)N * CA_LL_DMAX);
+  std::vector<unsigned char> fr((size_t)NB);
+  double *tab_d = nullptr, *lgt_d = nullptr, *Ut_d = nullptr, *Vt_d = nullptr, *Ez_d = nullptr, *lp_d = nullptr, *part = nullptr, *lgpart = nullptr, *zpart = nullptr, *mpart = nullptr,
+         *A_d = nullptr, *B_d = nullptr, *ll_d = nullptr, *pr_d = nullptr, *obj_d = nullptr;
+  unsigned* zm_d = nullptr; unsigned char *fr_d = nullptr, *cv_d = nullptr; int* rd_d = nullptr;
+  auto cleanup = [&]() { hipFree(tab_d); hipFree(lgt_d); hipFree(Ut_d); hipFree(Vt_d); hipFree(Ez_d); hipFree(lp_d); hipFree(part); hipFree(lgpart); hipFree(zpart); hipFree(mpart);
+                         hipFree(A_d); hipFree(B_d); hipFree(ll_d); hipFree(pr_d); hipFree(obj_d); hipFree(zm_d); hipFree(fr_d); hipFree(cv_d); hipFree(rd_d); };
+#define PCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return CA_ERR_HIP; } } while (0)
+#define UP(dst, vec) do { PCK(hipMalloc((void**)&dst, (vec).size() * sizeof((vec)[0]))); PCK(hipMemcpyAsync(dst, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, h->stream)); } while (0)
+  UP(tab_d, tab); UP(zm_d, zmask); UP(Ut_d, Ut); UP(Vt_d, Vt); UP(Ez_d, Ez);
+  if (lgc) UP(lgt_d, lgt);
+  if (log_prior) UP(lp_d, lp);
+  PCK(hipMalloc((void**)&part, (size_t)nseg * NB * nct * sizeof(double)));
+  if (lgc) PCK(hipMalloc((void**)&lgpart, (size_t)nseg * NB * sizeof(double)));
+  PCK(hipMalloc((void**)&zpart, (size_t)nzc * NB * nmt * sizeof(double)));
+  PCK(hipMalloc((void**)&mpart, (size_t)nzc * NB * sizeof(double)));
+  PCK(hipMalloc((void**)&A_d, (size_t)N * C * sizeof(double)));
+  PCK(hipMalloc((void**)&B_d, (size_t)N * CA_LL_DMAX * sizeof(double)));
+  PCK(hipMalloc((void**)&ll_d, (size_t)N * C * sizeof(double)));
+  PCK(hipMalloc((void**)&pr_d, (size_t)N * C * sizeof(double)));
+  PCK(hipMalloc((void**)&obj_d, (size_t)N * sizeof(double)));
+  PCK(hipMalloc((void**)&fr_d, (size_t)N));
+  PCK(hipMalloc((void**)&cv_d, (size_t)N));
+  PCK(hipMalloc((void**)&rd_d, (size_t)N * sizeof(int)));
+  PCK(hipMemsetAsync(B_d, 0, (size_t)N * CA_LL_DMAX * sizeof(double), h->stream));   // (the padding factors)
+  PCK(hipMemsetAsync(fr_d, 0, (size_t)N, h->stream));
+  for (int64_t n_lo = 0; n_lo < N; n_lo += NB) {
+    const int64_t n_cnt = std::min<int64_t>(NB, N - n_lo);
+    ca_ll_ops o;
+    o.tab = tab_d; o.zmask = zm_d; o.lgtab = lgt_d; o.part = part; o.lgpart = lgpart; o.n_lo = n_lo; o.n_cnt = n_cnt; o.NC = NC; o.ngrp = ngrp;
+    { const int rc = launch_clone_ll(h, o); if (rc != CA_OK) { cleanup(); return rc; } }
+    hipLaunchKernelGGL(k_proj_sums, dim3((unsigned)cdiv(n_cnt * ncol, CA_TB)), dim3(CA_TB), 0, h->stream, part, lgpart, h->s64, A_d, B_d, n_lo, n_cnt, C, D, (int)nseg, nct);
+    PCK(hipGetLastError());
+    ca_pm_ops m;
+    m.Ut = Ut_d; m.Vt = Vt_d; m.Ez = Ez_d; m.frozen = fr_d; m.zpart = zpart; m.mpart = mpart; m.n_lo = n_lo; m.n_cnt = n_cnt; m.K = K; m.NC = NZ; m.ngrp = ngz; m.nzc = nzc;
+    ca_ps_ops s;
+    s.zpart = zpart; s.mpart = mpart; s.A = A_d; s.B = B_d; s.lp = lp_d; s.Ut = Ut_d; s.frozen = fr_d; s.conv = cv_d; s.rounds = rd_d; s.ll = ll_d; s.probs = pr_d; s.obj = obj_d;
+    s.n_lo = n_lo; s.n_cnt = n_cnt; s.K = K; s.nzc = nzc; s.nmt = nmt; s.final = 0; s.tol = tol; s.max_step = max_step;
+    bool all_frozen = false;
+    for (int t = 0; K > 0 && t < max_iter && !all_frozen; ++t) {
+      s.round = t;
+      { const int rc = launch_proj_mom(h, m); if (rc != CA_OK) { cleanup(); return rc; } }
+      { const int rc = launch_proj_step(h, s); if (rc != CA_OK) { cleanup(); return rc; } }
+      if ((t + 1) % poll == 0 && t + 1 < max_iter) {
+        PCK(hipMemcpyAsync(fr.data(), fr_d + n_lo, (size_t)n_cnt, hipMemcpyDeviceToHost, h->stream));
+        PCK(hipStreamSynchronize(h->stream));
+        all_frozen = std::find(fr.begin(), fr.begin() + n_cnt, (unsigned char)0) == fr.begin() + n_cnt;
+      }
+    }
+    if (!all_frozen) {   // the cells that never froze (all of them when K = 0 or max_iter = 0): ll and the posterior at the psi they hold
+      s.round = K > 0 ? max_iter : 0; s.final = 1;
+      { const int rc = launch_proj_mom(h, m); if (rc != CA_OK) { cleanup(); return rc; } }
+      { const int rc = launch_proj_step(h, s); if (rc != CA_OK) { cleanup(); return rc; } }
+    }
+  }
+  std::vector<int> o_rd((size_t)N);
+  PCK(hipMemcpyAsync(o_ll.data(), ll_d, o_ll.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PCK(hipMemcpyAsync(o_pr.data(), pr_d, o_pr.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PCK(hipMemcpyAsync(o_u.data(), Ut_d, o_u.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PCK(hipMemcpyAsync(objective, obj_d, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  PCK(hipMemcpyAsync(o_rd.data(), rd_d, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  PCK(hipMemcpyAsync(converged, cv_d, (size_t)N, hipMemcpyDeviceToHost, h->stream));
+  PCK(hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
+  cleanup();
+#undef UP
+#undef PCK
+  for (int64_t n = 0; n < N; ++n) {
+    rounds[n] = o_rd[(size_t)n];
+    for (int c = 0; c < C; ++c) { ll[hidx(h->layout, n, c, N, C)] = o_ll[(size_t)n * C + c]; clone_probs[hidx(h->layout, n, c, N, C)] = o_pr[(size_t)n * C + c]; }
+    for (int k = 0; k < K; ++k) psi[hidx(h->layout, n, k, N, K)] = o_u[(size_t)n * CA_LL_DMAX + k];
+  }
   return CA_OK;
 }
 

@@ -315,3 +315,31 @@ int launch_clone_ll_z(ca_engine* h, const ca_llz_ops& o) {
   if (o.NC == 16) return clone_ll_z_t<16>(h, o);
   return clone_ll_z_t<32>(h, o);
 }
+
+// ---- k_proj_mom<NC, K> / k_proj_step<K>: one round of ca_project_cells on one batch of cells (neither reads the count matrix) ----
+// the moments' operands: U = [psi | x] and V = [W | beta] padded to CA_LL_DMAX factors, E in groups of NC clone columns, the frozen flags, the chunk slabs
+struct ca_pm_ops { const double *Ut, *Vt, *Ez; const unsigned char* frozen; double *zpart, *mpart; int64_t n_lo, n_cnt; int K, NC, ngrp, nzc; };
+template <int NC, int K>
+int proj_mom_t(ca_engine* h, const ca_pm_ops& o) {
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_proj_mom<NC, K>), dim3((unsigned)cdiv(o.n_cnt, CA_TB), (unsigned)o.nzc, (unsigned)o.ngrp), dim3(CA_TB), 0, h->stream, o.Ut, o.Vt,
+                                                o.Ez, o.frozen, o.zpart, o.mpart, o.n_lo, o.n_cnt, h->G, h->Gp));
+  return CA_OK;
+}
+int launch_proj_mom(ca_engine* h, const ca_pm_ops& o) {   // (sixteen clones per group only where the accumulators of eight leave room: K <= 1)
+  if (o.K == 0) return o.NC == 8 ? proj_mom_t<8, 0>(h, o) : proj_mom_t<16, 0>(h, o);
+  if (o.K == 1) return o.NC == 8 ? proj_mom_t<8, 1>(h, o) : proj_mom_t<16, 1>(h, o);
+  return proj_mom_t<8, 2>(h, o);
+}
+// the round's finisher (final = 0) or the closing evaluation (final = 1)
+struct ca_ps_ops { const double *zpart, *mpart, *A, *B, *lp; double* Ut; unsigned char *frozen, *conv; int* rounds; double *ll, *probs, *obj; int64_t n_lo, n_cnt; int K, nzc, nmt, round, final; double tol, max_step; };
+template <int K>
+int proj_step_t(ca_engine* h, const ca_ps_ops& o) {
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_proj_step<K>), dim3((unsigned)cdiv(o.n_cnt, CA_TB)), dim3(CA_TB), 0, h->stream, o.zpart, o.mpart, o.A, o.B, o.lp, h->s64, o.Ut, o.frozen,
+                                                o.rounds, o.conv, o.ll, o.probs, o.obj, o.n_lo, o.n_cnt, h->C, o.nzc, o.nmt, o.round, o.final, o.tol, o.max_step));
+  return CA_OK;
+}
+int launch_proj_step(ca_engine* h, const ca_ps_ops& o) {
+  if (o.K == 0) return proj_step_t<0>(h, o);
+  if (o.K == 1) return proj_step_t<1>(h, o);
+  return proj_step_t<2>(h, o);
+}

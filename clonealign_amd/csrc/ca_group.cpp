@@ -713,6 +713,47 @@ int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U, c
   return CA_OK;
 }
 
+int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X, const double* log_prior, const double* psi_start,
+                           int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi, double* ll, double* clone_probs, double* objective,
+                           int32_t* rounds, uint8_t* converged) {
+  GROUP_ALIVE(g);
+  if (!E || !ll || !clone_probs || !objective || !rounds || !converged || (K > 0 && !psi)) return CA_ERR_INVALID;
+  if (K < 0 || P < 0 || K + P > 8 || (P > 0 && !X)) {   // (what decides how the cell arrays are sliced; the ranks refuse everything else in their own words)
+    g->err = K < 0 || P < 0 || K + P > 8 ? "ca_project_cells: K + P = " + std::to_string(K + P) + " is outside [0, 8]" : "ca_project_cells: P = " + std::to_string(P) + " needs X (cells x P)";
+    return CA_ERR_INVALID;
+  }
+  const size_t W = (size_t)g->W;
+  std::vector<std::vector<double>> xs(W), lps(W), pss(W), o_psi(W), o_ll(W), o_pr(W);
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t lo = g->shard[r].lo, hi = g->shard[r].hi;
+    if (P > 0) slice_rows(X, g->layout, g->N, P, lo, hi, xs[r]);
+    if (log_prior) slice_rows(log_prior, g->layout, g->N, g->C, lo, hi, lps[r]);
+    if (K > 0 && psi_start) slice_rows(psi_start, g->layout, g->N, K, lo, hi, pss[r]);
+    o_psi[r].resize((size_t)((hi - lo) * std::max(K, 1))); o_ll[r].resize((size_t)((hi - lo) * g->C)); o_pr[r].resize((size_t)((hi - lo) * g->C));
+  }
+  const int s = settle(g, dispatch(g, [&](int ri) {
+    const size_t r = (size_t)ri;
+    const int64_t lo = g->shard[r].lo;   // (objective, rounds and converged are one value per cell: a rank writes its own stretch in place)
+    return ca_project_cells(g->h[r], E, V, K, P, P > 0 ? xs[r].data() : nullptr, log_prior ? lps[r].data() : nullptr, K > 0 && psi_start ? pss[r].data() : nullptr, with_const,
+                            max_iter, tol, max_step, o_psi[r].data(), o_ll[r].data(), o_pr[r].data(), objective + lo, rounds + lo, converged + lo);
+  }), "ca_project_cells");
+  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  if (s != CA_OK) return s;
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t lo = g->shard[r].lo, hi = g->shard[r].hi;
+    if (K > 0) scatter_rows(o_psi[r].data(), g->layout, g->N, K, lo, hi, psi);
+    scatter_rows(o_ll[r].data(), g->layout, g->N, g->C, lo, hi, ll);
+    scatter_rows(o_pr[r].data(), g->layout, g->N, g->C, lo, hi, clone_probs);
+  }
+  return CA_OK;
+}
+
 int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell, int32_t n_groups, const double* size_factor, double* S1, double* S2, int64_t* n_group) {
   GROUP_ALIVE(g);
   if (!group_of_cell || !S1 || !S2 || !n_group) return CA_ERR_INVALID;

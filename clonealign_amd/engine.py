@@ -47,6 +47,8 @@ EXPORTS = (
     "ca_logexpr_sums", "ca_group_logexpr_sums",
     # per-cell, per-clone log-likelihood of the resident matrix under a fitted model (clone_loglik / assign_cells), additions to ABI 6
     "ca_clone_loglik", "ca_group_clone_loglik",
+    # per-cell MAP psi and clone posterior of cells outside the fit (project_cells), additions to ABI 6
+    "ca_project_cells", "ca_group_project_cells",
 )
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
@@ -154,6 +156,8 @@ def load_library(path=None):
     lib.ca_fit_mse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.ca_logexpr_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_clone_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.ca_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -185,6 +189,7 @@ def load_library(path=None):
     lib.ca_group_fit_mse.argtypes = lib.ca_fit_mse.argtypes
     lib.ca_group_logexpr_sums.argtypes = lib.ca_logexpr_sums.argtypes
     lib.ca_group_clone_loglik.argtypes = lib.ca_clone_loglik.argtypes
+    lib.ca_group_project_cells.argtypes = lib.ca_project_cells.argtypes
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -667,6 +672,60 @@ class HipEngine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         self._ck(self._fn("clone_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(ll)))
         return ll
+
+    def project_cells(self, E, V=None, K=0, X=None, log_prior=None, psi_start=None, const=True, max_iter=25, tol=1e-9, max_step=1.0, poll_every=None):
+        """Per-cell MAP ``psi`` of the resident cells under a fit's gene-level parameters and the exact clone posterior at it (ca_project_cells;
+        include/clonealign_hip.h has the algorithm): maximises ``logsumexp_c(ll_nc(psi) + log_prior_nc) - |psi|^2 / 2`` per cell by generalised EM with one
+        safeguarded Newton step per round.  ``E`` [G, C]; ``V`` = ``[W | beta]`` [G, K + P] with ``K`` <= 2 free factors (the device limit); ``X`` [N, P];
+        ``log_prior`` [N, C] (``log alpha + extra``; ``-inf`` excludes a clone) or None; ``psi_start`` [N, K] or None = 0.  One sweep over the resident
+        matrix, then two launches per round that do not read it.  Returns a dict: ``psi`` [N, K], ``ll`` and ``clone_probs`` [N, C], ``objective`` [N],
+        ``rounds`` [N] int32, ``converged`` [N] bool.  ``poll_every``: rounds between two host reads of the frozen flags (None = 4); no result depends
+        on it.  Changes nothing in the engine; two calls agree bit for bit."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"project_cells: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        K = int(K)
+        Vm = Xm = lpm = psm = None
+        D = 0
+        if V is not None:
+            V = np.asarray(V, dtype=np.float64)
+            if V.ndim != 2 or V.shape[0] != self.G:
+                raise ValueError(f"project_cells: V is {V.shape}; expected ({self.G}, K + P)")
+            D = int(V.shape[1])
+        P = D - K
+        if P < 0:
+            raise ValueError(f"project_cells: V has {D} columns but K = {K}")
+        if D > 0:
+            Vm = np.require(V, requirements=[self._order, "A"])
+        if X is not None or P > 0:
+            X = np.zeros((self.N, 0)) if X is None else np.asarray(X, dtype=np.float64)
+            if X.shape != (self.N, P):
+                raise ValueError(f"project_cells: X is {X.shape}; V has K + P = {D} columns with K = {K}, so X must be ({self.N}, {P})")
+            Xm = np.require(X, requirements=[self._order, "A"]) if P > 0 else None
+        if log_prior is not None:
+            log_prior = np.asarray(log_prior, dtype=np.float64)
+            if log_prior.shape != (self.N, self.C):
+                raise ValueError(f"project_cells: log_prior is {log_prior.shape}; expected ({self.N}, {self.C})")
+            lpm = np.require(log_prior, requirements=[self._order, "A"])
+        if psi_start is not None and K > 0:
+            psi_start = np.asarray(psi_start, dtype=np.float64)
+            if psi_start.shape != (self.N, K):
+                raise ValueError(f"project_cells: psi_start is {psi_start.shape}; expected ({self.N}, {K})")
+            psm = np.require(psi_start, requirements=[self._order, "A"])
+        if poll_every is not None and not 1 <= int(poll_every) <= 255:
+            raise ValueError("project_cells: poll_every must be in [1, 255]")
+        Em = np.require(E, requirements=[self._order, "A"])
+        psi = np.zeros((self.N, max(K, 0)), dtype=np.float64, order=self._order)
+        ll = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
+        pr = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
+        obj = np.zeros(self.N, dtype=np.float64)
+        rounds = np.zeros(self.N, dtype=np.int32)
+        conv = np.zeros(self.N, dtype=np.uint8)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        flags = int(bool(const)) | ((int(poll_every) if poll_every is not None else 0) << 8)
+        self._ck(self._fn("project_cells")(self.h, ptr(Em), ptr(Vm), K, P, ptr(Xm), ptr(lpm), ptr(psm), flags, int(max_iter), float(tol), float(max_step),
+                                           ptr(psi) if K > 0 else None, ptr(ll), ptr(pr), ptr(obj), ptr(rounds), ptr(conv)))
+        return {"psi": psi, "ll": ll, "clone_probs": pr, "objective": obj, "rounds": rounds, "converged": conv.astype(bool)}
 
     def synchronize(self):
         self._ck(self.lib.ca_synchronize(self.h))

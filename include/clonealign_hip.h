@@ -417,6 +417,41 @@ int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, doubl
 int ca_clone_loglik(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */,
                     int32_t D, int32_t with_const, double* ll /* N x C */);
 
+/* Project cells onto a fitted model: for every resident cell the MAP value of its latent factor psi_n under the fit's GENE-LEVEL parameters, and the
+ * exact clone posterior at it -- the per-cell part of the model for cells the fit never saw (no refit; every cell is independent).  Notation of
+ * ca_clone_loglik: E (G x C) = mu L, V = [W | beta] (G x D, D = K + P), U_n = [psi_n | x_n] (the first K columns free, the last P given by X),
+ * s_n = sum_g y_ng.  Per cell it maximises
+ *   F_n(psi) = logsumexp_c( ll_nc(psi) + log_prior_nc ) - |psi|^2 / 2
+ * with ll exactly ca_clone_loglik's and the reference's Normal(0, 1) prior on psi (R/inference-tflow.R:318-319); log_prior is the N x C addend
+ * log alpha_c + extra_nc (NULL = 0).  Method: generalised EM, one safeguarded Newton step per round.
+ *   once, one sweep over the resident counts:  A_nc = sum_g xlogy(y, E_gc) (+ const_n),  B_nd = sum_g y_ng V_gd,  s_n
+ *   round t = 0 .. max_iter - 1, for every cell not yet frozen:
+ *     1. eta_g = U_n . V_g, m = max_g eta_g; per clone Z0_c = sum_g E_gc e^(eta_g - m), Z1_c[k] = sum_g E_gc e^(eta_g - m) W_gk,
+ *        Z2_c[k][l] = sum_g E_gc e^(eta_g - m) W_gk W_gl (k <= l)
+ *     2. ll_c = A_c + U_n . B_n - s_n (m + log Z0_c);  gamma = softmax_c(ll + log_prior); clones at -inf get 0
+ *     3. mean_c = Z1_c / Z0_c, cov_c = Z2_c / Z0_c - mean_c mean_c^T;  g = B_n[:K] - s_n sum_c gamma_c mean_c - psi;
+ *        H = I + s_n sum_c gamma_c cov_c (symmetric positive definite);  d = H^-1 g, scaled to max-norm max_step when max|d| exceeds it;  psi += d
+ *     4. the cell is FROZEN when max|d| (before scaling) <= tol -- before the update is applied; its outputs are those of step 2 of that round
+ *   cells that reach max_iter without freezing get one more evaluation of steps 1-2 (ll / clone_probs belong to the returned psi), converged = 0.
+ * Outputs: psi (N x K), ll (N x C, at psi), clone_probs (N x C), objective (N: F_n), rounds (N: rounds evaluated -- t + 1 for a cell frozen in round t,
+ * max_iter otherwise), converged (N).  psi_start (N x K) or NULL = 0.  A cell whose ll + log_prior is -inf in every clone keeps its starting psi and gets
+ * NaN probabilities, objective -inf, rounds = 0 and converged = 0; no NaN reaches any other cell.  K = 0: ca_clone_loglik followed by the softmax, zero
+ * rounds, converged = 1.  with_const: bit 0 as in ca_clone_loglik; bits 8..15: rounds between two host reads of the frozen flags, after which no further
+ * round is queued once every cell is frozen (0 = every 4th round) -- a cell's result depends on its own row alone, so this changes no result.
+ * Matrices in the problem's layout; everything float64, sums in a fixed order, no atomics: two calls agree bit for bit, and a cell-sharded group returns
+ * the single handle's bits.
+ * K <= 2 IS THE DEVICE LIMIT: the moment kernel keeps C_group x (1 + K + K (K + 1) / 2) float64 accumulators per lane -- 24 for eight clones at K = 1, 48 at
+ * K = 2, 120 at K = 4, which does not fit (open: the two-pass form, per-clone first moments and then ONE gamma-weighted second moment).
+ * CA_ERR_INVALID (with a message naming the offender): K outside [0, 2]; K + P outside [0, 8]; V NULL with K + P > 0; X NULL with P > 0; max_iter < 0;
+ * tol or max_step non-positive or non-finite; ca_clone_loglik's refusals on E and V; a non-finite entry of X or psi_start; a +inf or NaN in log_prior
+ * (-inf is allowed: the clone is excluded for that cell).
+ * Sharded handle: the cell-indexed arrays cover the local cells; the only collective is the verdict on the input.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_project_cells(ca_handle h, const double* E /* G x C */, const double* V /* G x (K + P), or NULL */, int32_t K, int32_t P,
+                     const double* X /* N x P, or NULL */, const double* log_prior /* N x C, or NULL */, const double* psi_start /* N x K, or NULL = 0 */,
+                     int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi /* N x K */, double* ll /* N x C */,
+                     double* clone_probs /* N x C */, double* objective /* N */, int32_t* rounds /* N */, uint8_t* converged /* N */);
+
 /* The data side of plot_clonealign() (R/plotting.R:177-205: the dense t(logcounts), its N*G-row long table, the per-gene mean and
  * sd and the per (clone, gene) means of the z-scores) as sums from ONE sweep over the resident counts (any storage; nothing N x G
  * is made on the host).  group_of_cell[n] in [0, n_groups), or -1 for a cell left out of every sum and count; n_groups in [1, 64].
@@ -549,6 +584,11 @@ int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell /* N, all c
 /* ca_clone_loglik (R/inference-tflow.R:288-296) over the group: U and ll hold ALL cells (sliced by the shards); each cell's row is the single handle's, bit for bit */
 int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D,
                           int32_t with_const, double* ll /* N x C, all cells */);
+/* ca_project_cells over the group: X, log_prior, psi_start and every output hold ALL cells (sliced by the shards); each cell's results are the single handle's, bit for bit */
+int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X /* N x P, all cells, or NULL */,
+                           const double* log_prior /* N x C, all cells, or NULL */, const double* psi_start /* N x K, all cells, or NULL */,
+                           int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi, double* ll, double* clone_probs,
+                           double* objective, int32_t* rounds, uint8_t* converged);
 /* ca_logexpr_sums (R/plotting.R:177-205) over the group: group_of_cell and size_factor (or NULL) hold ALL cells; the totals are rank 0's (every rank has the same) */
 int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell /* N, all cells */, int32_t n_groups,
                           const double* size_factor /* N, all cells, or NULL */, double* S1, double* S2, int64_t* n_group);
