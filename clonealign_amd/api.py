@@ -253,26 +253,11 @@ def _clone_loglik_host(Y, E, U=None, V=None, const=True, chunk=2048):
     return ll
 
 
-def clone_loglik(fit, Y, L, *, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
-    """Log-likelihood ``ll`` [cells, clones] of the cells of ``Y`` under every clone of a fitted model, taken at the fit's point estimates: the
-    reference's ``p_y_on_c`` (R/inference-tflow.R:288-296) with the draw of ``mu`` replaced by ``fit["ml_params"]["mu"]``, i.e.
-    ``Multinomial(total = s_n, probs ~ mu * L[:, c] * exp(psi_n W^T + x_n beta^T)).log_prob(y_n)``.  The cells need not be the ones the fit saw.
-
-    ``Y`` [cells, genes]: a dense array in any dtype the engine uploads, or a scipy.sparse matrix; it is evaluated on the device in one float64 sweep
-    (``HipEngine.clone_loglik``) and never densified or copied as float64 on the host.  ``L`` [genes, clones] is given for the fit's retained genes and
-    saturated as ``inference_tflow`` does by default (:142-144); ``saturate=False`` is for fits made that way.
-    ``psi``, for fits with ``K > 0`` (the default ``clonealign()`` fit has ``K = 1``): ``None`` means the cells are NEW -- their ``psi`` is taken at its
-    prior mean 0 (:318), so the ``W`` term drops out; ``"fit"`` takes ``fit["ml_params"]["psi"]`` (the cells are the fit's own, in its order); an array
-    [cells, K] is used as given.  ``x`` [cells, P]: the covariates, required exactly when the fit has ``beta``.
-    ``const=False`` leaves out the clone-independent ``lgamma(s + 1) - sum(lgamma(y + 1))``.
-    ``engine``: a live engine whose resident matrix is ``Y`` (used as it is); without it a throwaway engine is built for the upload only (``K=0``;
-    ``engine_opts`` go to its constructor) and closed afterwards.  An engine without ``clone_loglik`` gets the chunked float64 host form.
-    A positive count on a gene where a clone has copy number 0 makes that entry exactly ``-inf``; a zero count there adds nothing."""
-    L, _cn = _parse_cnv(L)
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if L.shape[0] != G:
-        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+def _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold, what="Y"):
+    """The model tables of a fit for ``N`` cells, shared by ``clone_loglik`` and ``simulate_counts``: ``L`` [G, C] (parsed) saturated as asked,
+    ``E = mu * L`` [G, C], ``U = [psi | x]`` [N, D] and ``V = [W | beta]`` [G, D] (both None when no exponent term is in play).  ``psi``: None (the
+    ``W`` term drops out), ``"fit"`` or an array [N, K]; ``x`` exactly when the fit has ``beta``.  ``what`` names the cells' owner in the refusals."""
+    G = L.shape[0]
     ml = fit["ml_params"]
     mu = np.asarray(ml["mu"], dtype=np.float64).reshape(-1)
     if mu.shape[0] != G:
@@ -295,20 +280,44 @@ def clone_loglik(fit, Y, L, *, x=None, psi=None, saturate=True, saturation_thres
             psi = ml["psi"]
         psi = np.asarray(psi, dtype=np.float64)
         if psi.size != N * K or psi.reshape(-1, K).shape[0] != N:
-            raise ValueError(f"psi has {psi.reshape(-1, K).shape[0] if psi.size % K == 0 else psi.size} rows (cells) but Y has {N}")
+            raise ValueError(f"psi has {psi.reshape(-1, K).shape[0] if psi.size % K == 0 else psi.size} rows (cells) but {what} has {N}")
         Ucols.append(psi.reshape(N, K))
         Vcols.append(W)
     if P > 0:
         x = np.asarray(x, dtype=np.float64)
         x = x.reshape(-1, 1) if x.ndim == 1 else x
         if x.shape != (N, P):
-            raise ValueError(f"x is {x.shape} but Y has {N} rows (cells) and the fit {P} covariates")
+            raise ValueError(f"x is {x.shape} but {what} has {N} rows (cells) and the fit {P} covariates")
         Ucols.append(x)
         Vcols.append(beta)
     U = np.concatenate(Ucols, axis=1) if Ucols else None
     V = np.concatenate(Vcols, axis=1) if Vcols else None
     if U is not None and U.shape[1] > 8:
         raise ValueError(f"the fit has {U.shape[1]} exponent factors (K + P); at most 8 are supported")
+    return L, E, U, V
+
+
+def clone_loglik(fit, Y, L, *, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
+    """Log-likelihood ``ll`` [cells, clones] of the cells of ``Y`` under every clone of a fitted model, taken at the fit's point estimates: the
+    reference's ``p_y_on_c`` (R/inference-tflow.R:288-296) with the draw of ``mu`` replaced by ``fit["ml_params"]["mu"]``, i.e.
+    ``Multinomial(total = s_n, probs ~ mu * L[:, c] * exp(psi_n W^T + x_n beta^T)).log_prob(y_n)``.  The cells need not be the ones the fit saw.
+
+    ``Y`` [cells, genes]: a dense array in any dtype the engine uploads, or a scipy.sparse matrix; it is evaluated on the device in one float64 sweep
+    (``HipEngine.clone_loglik``) and never densified or copied as float64 on the host.  ``L`` [genes, clones] is given for the fit's retained genes and
+    saturated as ``inference_tflow`` does by default (:142-144); ``saturate=False`` is for fits made that way.
+    ``psi``, for fits with ``K > 0`` (the default ``clonealign()`` fit has ``K = 1``): ``None`` means the cells are NEW -- their ``psi`` is taken at its
+    prior mean 0 (:318), so the ``W`` term drops out; ``"fit"`` takes ``fit["ml_params"]["psi"]`` (the cells are the fit's own, in its order); an array
+    [cells, K] is used as given.  ``x`` [cells, P]: the covariates, required exactly when the fit has ``beta``.
+    ``const=False`` leaves out the clone-independent ``lgamma(s + 1) - sum(lgamma(y + 1))``.
+    ``engine``: a live engine whose resident matrix is ``Y`` (used as it is); without it a throwaway engine is built for the upload only (``K=0``;
+    ``engine_opts`` go to its constructor) and closed afterwards.  An engine without ``clone_loglik`` gets the chunked float64 host form.
+    A positive count on a gene where a clone has copy number 0 makes that entry exactly ``-inf``; a zero count there adds nothing."""
+    L, _cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if L.shape[0] != G:
+        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    L, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
     own = engine is None
     if own:
         from .engine import HipEngine
@@ -578,6 +587,213 @@ def project_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=
     return ClonealignFit(psi=psi, clone_probs=probs, clone=clone_assignment(probs, names, clone_assignment_probability),
                          loglik=r["objective"] + 0.5 * (psi ** 2).sum(1), objective=r["objective"], clone_loglik=r["ll"], rounds=r["rounds"],
                          converged=r["converged"], clone_names=names, ml_params={"psi": psi, "clone_probs": probs})
+
+
+def _simulate_counts_host(E, V, U, clone, total, seed, draw=0, cell_offset=0, chunk=1 << 20, _cumsum=None):
+    """Numpy float64 restatement of ``ca_simulate_counts`` (include/clonealign_hip.h states the sampler): rows ``y_n ~ Multinomial(total[n], p_n)`` with
+    ``p_ng ~ E[g, clone[n]] exp(U[n] . V[g])``.  Per cell: ``eta`` summed factor by factor, the shift by its maximum over the genes with ``E > 0``,
+    ``w = E exp(eta - m)``, the SEQUENTIAL ``np.cumsum``; per draw ``j`` the Philox4x32-10 block ``j >> 1`` of ``rng.philox4x32`` (key = the seed's halves,
+    counter = ``(j >> 1, q lo, draw lo, draw bits 32..47 | (q >> 32) << 16)`` with ``q = cell_offset + n``; words (0, 1) for even ``j``, (2, 3) for odd),
+    ``u = ((hi << 21 | lo >> 11) + 0.5) 2^-53``, ``t = min(u cum[-1], nextafter(cum[-1], 0))`` and ``np.searchsorted(cum, t, side="right")``.
+    Returns ``(Y int32 [N, G], flagged int64 [N])``: ``flagged[n]`` counts the cell's draws whose ``t`` lies within ``1e-12 cum[-1]`` of a cumulative
+    boundary next to it -- the only draws where another grouping of the float64 sums, or the last bit of ``exp``, may pick the neighbouring gene.
+    ``chunk``: Philox blocks generated at a time.  Refusals are ``ca_simulate_counts``'s, as ValueError.  ``_cumsum``: another cumulative sum (tests)."""
+    from .rng import philox4x32
+    E = np.asarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"simulate_counts: E is {E.shape}; expected (genes, clones)")
+    G, C = E.shape
+    clone = np.asarray(clone, dtype=np.int64).reshape(-1)
+    N = clone.shape[0]
+    total = np.array(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
+    if (U is None) != (V is None):
+        raise ValueError("simulate_counts: U and V go together (both, or neither)")
+    D = 0
+    if U is not None:
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"simulate_counts: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = U.shape[1]
+    if D > 8:
+        raise ValueError(f"simulate_counts: D = {D} is outside [0, 8]")
+    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
+    if wrong.size:
+        raise ValueError(f"simulate_counts: E has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
+    for name, M, row in (("V", V, "gene"), ("U", U, "cell")):
+        if D > 0 and not np.isfinite(M).all():
+            r, d = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"simulate_counts: {name} has a non-finite entry ({row} {r}, factor {d})")
+    wrong = np.flatnonzero((clone < 0) | (clone >= C))
+    if wrong.size:
+        raise ValueError(f"simulate_counts: clone[{wrong[0]}] = {clone[wrong[0]]} is outside [0, {C})")
+    wrong = np.flatnonzero((total < 0) | (total > 2 ** 31 - 1))
+    if wrong.size:
+        raise ValueError(f"simulate_counts: total[{wrong[0]}] = {total[wrong[0]]} is outside [0, 2^31 - 1]")
+    wrong = np.flatnonzero((total > 0) & ~(E > 0).any(0)[clone])
+    if wrong.size:
+        raise ValueError(f"simulate_counts: total[{wrong[0]}] = {total[wrong[0]]} but E is zero in every gene of the cell's clone {clone[wrong[0]]}")
+    seed, draw, cell_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw), int(cell_offset)
+    if cell_offset < 0 or cell_offset + N > 2 ** 48 or not 0 <= draw < 2 ** 48:
+        raise ValueError("simulate_counts: cell_offset + N must lie in [0, 2^48] and draw in [0, 2^48)")
+    cumsum = np.cumsum if _cumsum is None else _cumsum
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    Y = np.zeros((N, G), dtype=np.int32)
+    flagged = np.zeros(N, dtype=np.int64)
+    nblk = (total + 1) // 2
+    lo = 0
+    while lo < N:                                                    # cells [lo, hi): about `chunk` Philox blocks, at least one cell
+        hi = lo + max(1, int(np.searchsorted(np.cumsum(nblk[lo:]), int(chunk), side="right")))
+        hi = min(hi, N)
+        nb = nblk[lo:hi]
+        first = np.concatenate([[0], np.cumsum(nb)])
+        ctr = np.zeros((int(first[-1]), 4), dtype=np.uint32)
+        q = np.repeat(np.arange(lo, hi, dtype=np.int64) + cell_offset, nb)
+        ctr[:, 0] = np.arange(first[-1], dtype=np.int64) - np.repeat(first[:-1], nb)     # j >> 1
+        ctr[:, 1] = q & 0xFFFFFFFF
+        ctr[:, 2] = draw & 0xFFFFFFFF
+        ctr[:, 3] = ((draw >> 32) & 0xFFFF) | ((q >> 32) << 16)
+        r = philox4x32(ctr, key).astype(np.uint64)
+        x = np.stack([(r[:, 1] << np.uint64(21)) | (r[:, 0] >> np.uint64(11)), (r[:, 3] << np.uint64(21)) | (r[:, 2] >> np.uint64(11))], axis=1)
+        u_all = ((x.astype(np.float64) + 0.5) * 2.0 ** -53).reshape(-1)                  # draws 2b, 2b + 1 of every block, cell after cell
+        for n in range(lo, hi):
+            if total[n] == 0:
+                continue
+            e = E[:, clone[n]]
+            if D > 0:
+                eta = U[n, 0] * V[:, 0]
+                for d in range(1, D):
+                    eta = eta + U[n, d] * V[:, d]
+                m = eta[e > 0].max()
+                with np.errstate(over="ignore"):
+                    w = np.where(e > 0, e * np.exp(np.where(e > 0, eta - m, 0.0)), 0.0)
+            else:
+                w = e
+            cum = cumsum(w)
+            u = u_all[2 * first[n - lo]:2 * first[n - lo] + total[n]]
+            t = np.minimum(u * cum[-1], np.nextafter(cum[-1], 0.0))
+            g = np.searchsorted(cum, t, side="right")
+            Y[n] = np.bincount(g, minlength=G)
+            tol = 1e-12 * cum[-1]
+            near = (cum[g] - t <= tol) | ((g > 0) & (t - cum[np.maximum(g - 1, 0)] <= tol))
+            flagged[n] = int(near.sum())
+        lo = hi
+    return Y, flagged
+
+
+def simulate_counts(fit, L, *, n_cells=None, clones=None, total_counts=None, psi=None, x=None, seed=0, draw=0, saturate=True, saturation_threshold=6,
+                    device=0, host=False):
+    """Simulate a count matrix from a fitted model on the device: the model's generative direction, ``y_n ~ Multinomial(total_counts[n], p_n)`` with
+    ``p_ng ~ mu_g L[g, z_n] exp(psi_n W_g^T + x_n beta_g^T)`` at the fit's point estimates (``engine.simulate_counts`` / ``ca_simulate_counts``;
+    include/clonealign_hip.h states the sampler).  ``L`` [genes, clones] for the fit's retained genes, saturated as ``clone_loglik`` does.
+
+    ``total_counts`` (required): a scalar or an array [cells] of library sizes; passing the OBSERVED row sums of a matrix gives posterior predictive
+    replicates of it.  ``clones``: an array [cells] of clone names or indices; default: drawn from the fit's ``alpha`` (uniform without it) with
+    ``numpy.random.Generator(PCG64(seed))``.  ``psi`` [cells, K]: default, for fits with ``K > 0``: ``Normal(0, 1)`` draws (the model's prior) from the
+    same generator, after the clones.  ``x`` [cells, P]: the covariates, required exactly when the fit has ``beta``.  ``n_cells`` is needed only when no
+    array gives the number of cells.  ``clones=fit["clone"], psi=fit["ml_params"]["psi"]`` replicates the fit's own cells; cells labelled
+    "unassigned" have no clone to draw from and are refused (ValueError) -- subset them away first.
+    ``seed`` and ``draw`` also key the counter-based stream of the draws: the same arguments give the same matrix bit for bit, another ``draw`` an
+    independent replicate with the same row sums.  ``host=True`` runs the numpy restatement (``_simulate_counts_host``) instead of the device; there
+    is no silent fallback otherwise.
+    Returns a dict: ``counts`` int32 [cells, genes], ``clone`` (names), ``clone_index``, ``psi`` [cells, K] and ``total_counts`` as used."""
+    Lm, cn = _parse_cnv(L)
+    G, C = Lm.shape
+    if total_counts is None:
+        raise ValueError("total_counts is required: a scalar or one library size per cell (the observed row sums give posterior predictive replicates)")
+    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(C)])
+    if len(names) != C:
+        raise ValueError(f"fit has {len(names)} clone names but L has {C} columns (clones)")
+    ml = fit["ml_params"]
+    if np.asarray(ml["mu"]).size != G:
+        raise ValueError(f"fit$ml_params$mu has length {np.asarray(ml['mu']).size} but L has {G} rows: simulate on the retained genes")
+    K = 0 if ml.get("W") is None else int(np.asarray(ml["W"]).size // G)           # (_fit_tables checks the shapes)
+    total = np.asarray(total_counts)
+    sizes = {"n_cells": None if n_cells is None else int(n_cells), "clones": None if clones is None else int(np.asarray(clones, dtype=object).reshape(-1).shape[0]),
+             "total_counts": int(total.reshape(-1).shape[0]) if total.ndim > 0 else None,
+             "psi": None if psi is None or isinstance(psi, str) or K == 0 else int(np.asarray(psi).size // K),
+             "x": None if x is None else int(np.asarray(x).shape[0])}
+    given = {k: v for k, v in sizes.items() if v is not None}
+    if not given:
+        raise ValueError("the number of cells is not given: pass n_cells, or clones, psi, x or total_counts as an array")
+    if len(set(given.values())) != 1:
+        raise ValueError("the arguments disagree on the number of cells: " + ", ".join(f"{k} {v}" for k, v in given.items()))
+    N = next(iter(given.values()))
+    if not np.all(np.isfinite(total.astype(np.float64))) or np.any(total != np.floor(total)):
+        raise ValueError("total_counts must be whole numbers")
+    total = np.array(np.broadcast_to(total.astype(np.int64).reshape(-1) if total.ndim > 0 else total.astype(np.int64), (N,)))
+    gen = np.random.Generator(np.random.PCG64(int(seed)))
+    if clones is None:
+        alpha = ml.get("alpha")
+        p = np.full(C, 1.0 / C) if alpha is None else np.asarray(alpha, dtype=np.float64).reshape(-1)
+        if p.shape[0] != C or not np.all(np.isfinite(p)) or np.any(p < 0) or p.sum() <= 0:
+            raise ValueError(f"fit$ml_params$alpha must hold {C} non-negative clone prevalences")
+        idx = gen.choice(C, size=N, p=p / p.sum()).astype(np.int32)
+    else:
+        cl = np.asarray(clones).reshape(-1)
+        if cl.dtype.kind in "iu":
+            if cl.size and (cl.min() < 0 or cl.max() >= C):
+                raise ValueError(f"clone index outside [0, {C})")
+            idx = cl.astype(np.int32)
+        else:
+            lut = {c: i for i, c in enumerate(names)}
+            n_un = sum(1 for c in cl if c == "unassigned")
+            if n_un:
+                raise ValueError(f"{n_un} cells are \"unassigned\": they have no clone to simulate from; pass the assigned cells only")
+            unknown = sorted({str(c) for c in cl if c not in lut})
+            if unknown:
+                raise ValueError("clone labels that are no column of L: " + ", ".join(unknown))
+            idx = np.array([lut[c] for c in cl], dtype=np.int32)
+    if K > 0 and psi is None:
+        psi = gen.standard_normal((N, K))
+    Ls, E, U, V = _fit_tables(fit, Lm, N, x, psi if K > 0 else None, saturate, saturation_threshold, what="the simulation")
+    psi_out = U[:, :K].copy() if K > 0 else np.zeros((N, 0))
+    if host:
+        counts, _flagged = _simulate_counts_host(E, V, U, idx, total, seed, draw)
+    else:
+        from . import engine as _engine
+        counts = _engine.simulate_counts(E, V, U, idx, total, seed, draw, device=device)
+    return {"counts": counts, "clone": np.asarray(names, dtype=object)[idx], "clone_index": idx, "psi": psi_out, "total_counts": total}
+
+
+def predictive_fit_mse(fit, Y, L, n_rep=20, *, seed=0, model_mu=False, x=None, engine_opts=None):
+    """Posterior predictive check of ``compute_ca_fit_mse``: the observed MSE of the fit's called clones beside the same statistic on ``n_rep`` count
+    matrices simulated from the fitted model itself, which gives the number a scale.  Cells labelled "unassigned" are left out on both sides.  A replicate
+    keeps the assigned cells' clones, their ``psi`` (``fit["ml_params"]["psi"]`` when the fit has ``K > 0``), their OBSERVED row sums and ``x``, and is
+    drawn by ``simulate_counts(..., seed=seed, draw=r)`` for ``r = 0 .. n_rep - 1``; each one is uploaded and evaluated as the observed matrix is
+    (``compute_ca_fit_mse`` -> ``HipEngine.fit_mse``; ``engine_opts`` go to the engines' constructor).  ``Y`` and ``L`` as for ``compute_ca_fit_mse``.
+    Returns a dict: ``observed``, ``replicates`` [n_rep], ``z`` = (observed - mean(replicates)) / sd(replicates) (sample sd), and per gene
+    ``observed_gene``, ``replicate_gene_mean``, ``replicate_gene_sd`` [genes].  A large positive ``z`` says the data are further from the fit than the
+    fit's own data would be."""
+    n_rep = int(n_rep)
+    if n_rep < 2:
+        raise ValueError("n_rep must be at least 2 (the replicates' spread is the scale)")
+    Lm, cn = _parse_cnv(L)
+    Ya = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N = Ya.shape[0]
+    clones = np.asarray(fit["clone"], dtype=object).reshape(-1)
+    if clones.shape[0] != N:
+        raise ValueError(f"fit has {clones.shape[0]} clone labels but Y has {N} rows (cells)")
+    used = np.flatnonzero(clones != "unassigned")
+    if used.size == 0:
+        raise ValueError("every cell is \"unassigned\": there is nothing to evaluate")
+    obs, obs_gene = compute_ca_fit_mse(fit, Ya, L, model_mu=model_mu, drop_unassigned=True, per_gene=True, engine_opts=engine_opts)
+    rows = np.asarray(Ya.sum(axis=1)).reshape(-1)[used]
+    ml = fit["ml_params"]
+    has_psi = ml.get("W") is not None and np.asarray(ml["W"]).size > 0
+    psi = np.asarray(ml["psi"], dtype=np.float64).reshape(N, -1)[used] if has_psi else None
+    xs = None
+    if x is not None:
+        xs = np.asarray(x, dtype=np.float64)
+        xs = (xs.reshape(-1, 1) if xs.ndim == 1 else xs)[used]
+    sub = {k: v for k, v in fit.items() if k != "clone"}
+    sub["clone"] = clones[used]
+    reps, rep_gene = np.empty(n_rep), np.empty((n_rep, Lm.shape[0]))
+    for r in range(n_rep):
+        sim = simulate_counts(fit, L, clones=clones[used], total_counts=rows, psi=psi, x=xs, seed=seed, draw=r)
+        reps[r], rep_gene[r] = compute_ca_fit_mse(sub, sim["counts"], L, model_mu=model_mu, per_gene=True, engine_opts=engine_opts)
+    sd = reps.std(ddof=1)
+    return {"observed": float(obs), "replicates": reps, "z": float((obs - reps.mean()) / sd) if sd > 0 else float("nan"),
+            "observed_gene": obs_gene, "replicate_gene_mean": rep_gene.mean(0), "replicate_gene_sd": rep_gene.std(0, ddof=1)}
 
 
 def _logexpr_sums_host(Y, group_idx, n_groups, size_factors=None, chunk=4096):

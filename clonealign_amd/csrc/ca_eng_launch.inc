@@ -343,3 +343,24 @@ int launch_proj_step(ca_engine* h, const ca_ps_ops& o) {
   if (o.K == 1) return proj_step_t<1>(h, o);
   return proj_step_t<2>(h, o);
 }
+
+// ---- k_simulate: one launch over a list of work items of ca_simulate_counts (no engine: the call owns its stream) ----
+// The search table's plan for G genes: S = genes per LDS entry (1: the whole table in LDS), whether the row's histogram fits in LDS beside it, the LDS bytes.
+struct ca_sim_plan { int S, nco, hist_lds; size_t lds; };
+inline ca_sim_plan sim_plan(int G) {
+  ca_sim_plan p;
+  p.hist_lds = (size_t)G * 4 + 8 * (size_t)cdiv(G, 64) <= CA_SIM_LDS ? 1 : 0;   // (it must fit beside a table of one entry per 64 genes)
+  const size_t room = CA_SIM_LDS - (p.hist_lds ? (size_t)G * 4 : 0);
+  p.S = 1;
+  while (8 * (size_t)cdiv(G, p.S) > room) p.S *= 2;
+  p.nco = cdiv(G, p.S);
+  p.lds = 8 * (size_t)p.nco + (p.hist_lds ? (size_t)G * 4 : 0);
+  return p;
+}
+struct ca_sim_ops { const double *Et, *Vt, *U; const int32_t* clone; const int64_t* total; const ca_sim_item* items; double* cumg; int32_t* Y; int64_t n_items; int G, D;
+                    ca_sim_plan plan; uint64_t seed, draw, q0; };
+inline hipError_t launch_simulate(hipStream_t stream, const ca_sim_ops& o) {
+  hipLaunchKernelGGL(k_simulate, dim3((unsigned)o.n_items), dim3(CA_SIM_TB), o.plan.lds, stream, o.Et, o.Vt, o.U, o.clone, o.total, o.items, o.plan.S > 1 ? o.cumg : nullptr, o.Y,
+                     o.G, o.D, o.plan.S, o.plan.nco, o.plan.hist_lds, (uint32_t)o.seed, (uint32_t)(o.seed >> 32), o.draw, o.q0);
+  return hipGetLastError();
+}

@@ -856,4 +856,6 @@ int ca_preprocess(int64_t N, int32_t G, int32_t C, int32_t layout, int32_t y_dty
   return rc == CA_OK ? CA_OK : fail(rc, msg);
 }
 
+#include "ca_eng_simulate.inc"   // C ABI without a handle: count rows drawn from a fitted model (ca_simulate_counts)
+
 }  // extern "C"

@@ -49,6 +49,8 @@ EXPORTS = (
     "ca_clone_loglik", "ca_group_clone_loglik",
     # per-cell MAP psi and clone posterior of cells outside the fit (project_cells), additions to ABI 6
     "ca_project_cells", "ca_group_project_cells",
+    # count rows drawn from a fitted model (simulate_counts), no handle, additions to ABI 6
+    "ca_simulate_counts", "ca_simulate_kernel_ms",
 )
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
@@ -158,6 +160,9 @@ def load_library(path=None):
     lib.ca_clone_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.ca_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ca_simulate_counts.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                       C.c_int64, C.c_int32, C.c_void_p, C.c_char_p]
+    lib.ca_simulate_kernel_ms.argtypes = [C.POINTER(C.c_double)]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -896,6 +901,47 @@ def allele_loglik(clone_allele, cov, ref, device=0, layout="row"):
     if rc != CA_OK:
         raise EngineError(rc, err.value.decode() or "ca_allele_loglik")
     return out
+
+
+def simulate_counts(E, V, U, clone, total, seed, draw=0, cell_offset=0, device=0, out=None):
+    """Count rows drawn from a fitted model on the device (ca_simulate_counts; include/clonealign_hip.h has the sampler): ``y_n ~ Multinomial(total[n],
+    p_n)``, ``p_ng ~ E[g, clone[n]] exp(U[n] . V[g])``.  ``E`` [G, C]; ``V`` [G, D] and ``U`` [N, D], or both None; ``clone`` [N] in [0, C); ``total`` [N].
+    Returns int32 [N, G] (``out``: a C-contiguous int32 [N, G] array to fill instead).  Row n depends on (seed, draw, cell_offset + n) and its own
+    arguments alone, so splitting the cells over calls (or devices) with ``cell_offset`` gives the same bits.  Refusals raise EngineError."""
+    lib = load_library()
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"simulate_counts: E is {E.shape}; expected (genes, clones)")
+    G, Cn = E.shape
+    clone = np.ascontiguousarray(clone, dtype=np.int32).reshape(-1)
+    N = clone.shape[0]
+    total = np.ascontiguousarray(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
+    D = 0
+    if (U is None) != (V is None):
+        raise ValueError("simulate_counts: U and V go together (both, or neither)")
+    if U is not None:
+        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"simulate_counts: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = int(U.shape[1])
+    if out is None:
+        out = np.zeros((N, G), dtype=np.int32)
+    elif out.dtype != np.int32 or out.shape != (N, G) or not out.flags.c_contiguous:
+        raise ValueError(f"simulate_counts: out must be a C-contiguous int32 array of shape ({N}, {G})")
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    err = C.create_string_buffer(256)
+    rc = lib.ca_simulate_counts(N, G, Cn, D, ptr(E), ptr(V) if D > 0 else None, ptr(U) if D > 0 else None, ptr(clone), ptr(total),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, int(cell_offset), int(device), ptr(out), err)
+    if rc != CA_OK:
+        raise EngineError(rc, err.value.decode() or "ca_simulate_counts")
+    return out
+
+
+def simulate_kernel_ms():
+    """Milliseconds the kernel launches of this thread's last ``simulate_counts`` call took (HIP events around each launch)."""
+    ms = C.c_double(0.0)
+    load_library().ca_simulate_kernel_ms(C.byref(ms))
+    return ms.value
 
 
 _NP_DTYPE = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2, np.dtype(np.uint16): 3, np.dtype(np.uint8): 4}

@@ -524,6 +524,38 @@ int ca_preprocess(int64_t N, int32_t G, int32_t C, int32_t layout, int32_t y_dty
                   const double* L, const ca_preprocess_params* params, int32_t device, uint8_t* keep_gene,
                   uint8_t* keep_cell, double* gene_sums, double* cell_sums, char* err);
 
+/* Simulate count rows from a fitted model on the device, needs no handle: the model's generative direction,
+ *   y_n ~ Multinomial(total_n, p_n),   p_ng proportional to E[g][clone_n] exp(U_n . V_g),
+ * with E (G x C) = mu L, V = [W | beta] (G x D) and U_n = [psi_n | x_n] (N x D) in the notation of ca_clone_loglik.  All matrices are ROW-MAJOR host
+ * arrays; Y (N x G, int32, row-major, host) receives the rows.  The sampler, per cell n with c = clone[n] and global index q = cell_offset + n:
+ *   1. eta_g = sum_d U[n][d] V[g][d], products and sums rounded one by one in ascending d (0 when D = 0); m = max of eta_g over the genes with E[g][c] > 0;
+ *      w_g = E[g][c] exp(eta_g - m), and w_g = 0 where E[g][c] = 0.  Float64 throughout.
+ *   2. cum_g = w_0 + ... + w_g, inclusive, float64.  The device sums by a parallel scan (64-lane wave scans, sixteen wave totals, a carry per 1024 genes) and
+ *      keeps the running maximum of the scanned values over the genes with w > 0, so that the table is non-decreasing and a gene with w = 0 has exactly its
+ *      predecessor's value.  Its values may differ from a sequential sum's in the last bits; see "which draws can differ" below.
+ *   3. draw j = 0 .. total[n] - 1: Philox4x32-10 (philox_host.h, Salmon et al., SC'11) with key (seed low 32 bits, seed high 32 bits) and counter
+ *        ( j >> 1,  q low 32 bits,  draw low 32 bits,  (draw bits 32..47) | ((q >> 32) << 16) );
+ *      output words (0, 1) serve even j, words (2, 3) odd j, as (lo, hi):  u = ((hi << 21 | lo >> 11) + 0.5) * 2^-53, 53 bits, in (0, 1].
+ *      (total <= 2^31 - 1, draw < 2^48 and q < 2^48 are enforced, so (seed, draw, q, j) -> (key, counter, word pair) is injective.)
+ *   4. t = min(u cum_{G-1}, the largest double below cum_{G-1}); the gene drawn is the first g with cum_g > t, so a gene with w_g = 0 is never drawn.
+ *      Y[n][g] = the number of the cell's draws that landed on g: a row sums to total[n] exactly; total[n] = 0 gives a row of zeros.
+ * Counts are integer sums of independent draws, each with its own counter: the result does not depend on the launch geometry, on the internal batching of
+ * cells (device buffers stay below 256 MB) or on how a caller splits the cells -- cells [0, N) in one call equal cells [0, h) and [h, N) in two calls with
+ * cell_offset = h, bit for bit, which is also how a caller shards over devices (there is no ca_group_* form).  The counters are raised with integer atomics
+ * (an LDS histogram per row, or the row itself for G above about 14 000); integer addition commutes, so -- unlike the float64 sums of every other entry
+ * point, which run in a fixed order without atomics -- they cannot change a bit.
+ * Which draws can differ from a sequential float64 restatement (api._simulate_counts_host): only those whose t lies within rounding (the restatement flags
+ * 1e-12 cum_{G-1}) of a cumulative boundary, where another grouping of the sums or the last bit of exp may pick the neighbouring gene.
+ * CA_ERR_INVALID (message in err, naming the argument; nothing is written to Y): a negative or non-finite entry of E; a non-finite entry of U or V;
+ * clone[n] outside [0, C); total[n] < 0 or > 2^31 - 1; total[n] > 0 for a cell whose clone has E = 0 in every gene; D outside [0, 8]; D > 0 with U or V
+ * NULL; N < 0, G < 1, C < 1; N G >= 2^62; cell_offset < 0 or cell_offset + N > 2^48; draw >= 2^48.
+ * err (optional, >= 256 bytes) receives the message on failure. */
+int ca_simulate_counts(int64_t N, int32_t G, int32_t C, int32_t D, const double* E /* G x C */, const double* V /* G x D, or NULL */,
+                       const double* U /* N x D, or NULL */, const int32_t* clone /* N */, const int64_t* total /* N */, uint64_t seed, uint64_t draw,
+                       int64_t cell_offset, int32_t device, int32_t* Y /* N x G */, char* err);
+/* milliseconds the k_simulate launches of the calling thread's last ca_simulate_counts took (HIP events around each launch, summed; 0 after a refusal) */
+int ca_simulate_kernel_ms(double* ms);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ONE fit, cell-sharded over several devices of ONE process (ABI 6; SURVEY.md section 8b "multi-GPU via one process / 8 devices,
  * communicator created per fit", section 8e).  The reference's caller is a single R session: inference_tflow() is called once
