@@ -5,7 +5,7 @@ callers ``clonealign`` / ``run_clonealign``): the TensorFlow ELBO loop is replac
 hand-written HIP kernels for gfx950 behind the C ABI in ``include/clonealign_hip.h``.
 """
 from .api import (ClonealignFit, ClonealignTracks, assign_cells, clone_assignment, clone_expression_profile, clone_loglik,  # noqa: F401
-                  clonealign, compute_ca_fit_mse, compute_correlations, plot_clonealign, predictive_fit_mse, project_cells, recompute_clone_assignment, run_clonealign,
+                  clonealign, compute_ca_fit_mse, compute_correlations, plot_clonealign, predictive_check, predictive_fit_mse, project_cells, recompute_clone_assignment, run_clonealign,
                   simulate_counts)
 from .hostprep import inverse_softplus, safe_inverse_softplus, saturate, softplus  # noqa: F401
 from .inference import inference_tflow  # noqa: F401

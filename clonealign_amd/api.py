@@ -796,6 +796,146 @@ def predictive_fit_mse(fit, Y, L, n_rep=20, *, seed=0, model_mu=False, x=None, e
             "observed_gene": obs_gene, "replicate_gene_mean": rep_gene.mean(0), "replicate_gene_sd": rep_gene.std(0, ddof=1)}
 
 
+def _predictive_stats_host(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=0, gene_totals=True, chunk=2048):
+    """Numpy float64 restatement of ``ca_predictive_stats`` (include/clonealign_hip.h states the outputs): replicate ``r`` is the matrix
+    ``_simulate_counts_host(..., seed, draw=draw0 + r, cell_offset)`` returns; ``ll_rep[n, r] = gammaln(total_n + 1) - sum_g gammaln(y_g + 1) +
+    sum over y_g > 0 of y_g (log E[g, c_n] + eta_g - m - log Z_n)`` with ``m`` the largest ``eta`` over the genes with ``E > 0`` and ``Z_n = sum_g E
+    exp(eta_g - m)`` (a sequential sum here); ``T_rep[r, g, c]`` = the rows of the cells of clone ``c`` summed.  ``total_n = 0`` gives exactly 0.
+    Returns ``(ll_rep float64 [N, n_rep], T_rep int64 [n_rep, G, C] or None)``.  Refusals are ``ca_predictive_stats``'s, as ValueError."""
+    from scipy.special import gammaln
+    n_rep, draw0 = int(n_rep), int(draw0)
+    if n_rep < 1:
+        raise ValueError(f"predictive_stats: n_rep = {n_rep} is below 1")
+    if draw0 < 0 or draw0 + n_rep > 2 ** 48:
+        raise ValueError(f"predictive_stats: draw0 = {draw0} with n_rep = {n_rep}: draw0 + n_rep must lie in [0, 2^48]")
+    rows = [_simulate_counts_host(E, V, U, clone, total, seed, draw0 + r, cell_offset)[0] for r in range(n_rep)]   # (also: every refusal on the inputs)
+    E = np.asarray(E, dtype=np.float64)
+    G, C = E.shape
+    clone = np.asarray(clone, dtype=np.int64).reshape(-1)
+    N = clone.shape[0]
+    total = np.array(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
+    ll = np.zeros((N, n_rep))
+    for lo in range(0, N, int(chunk)):
+        sl = slice(lo, min(lo + int(chunk), N))
+        e = E[:, clone[sl]].T                                        # [cells, G]
+        pos = e > 0
+        eta = np.zeros(e.shape)
+        if U is not None:
+            Uc, Vm = np.asarray(U, dtype=np.float64)[sl], np.asarray(V, dtype=np.float64)
+            for d in range(Uc.shape[1]):
+                eta = eta + Uc[:, d:d + 1] * Vm[None, :, d]
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            m = np.where(pos, eta, -np.inf).max(1, keepdims=True)
+            x = np.where(pos, eta - m, 0.0)
+            lw = np.where(pos, np.log(np.where(pos, e, 1.0)) + x, 0.0)
+            log_z = np.log(np.where(pos, e * np.exp(x), 0.0).sum(1))
+        live = total[sl] > 0                                         # (a cell without counts: exactly 0, whatever its clone)
+        for r in range(n_rep):
+            y = rows[r][sl].astype(np.float64)
+            with np.errstate(invalid="ignore"):
+                v = gammaln(total[sl] + 1.0) - gammaln(y + 1.0).sum(1) + (y * lw).sum(1) - total[sl] * log_z
+            ll[sl, r] = np.where(live, v, 0.0)
+    T = None
+    if gene_totals:
+        T = np.zeros((n_rep, G, C), dtype=np.int64)
+        for r in range(n_rep):
+            np.add.at(T[r].T, clone, rows[r])
+    return ll, T
+
+
+def predictive_check(fit, Y, L, n_rep=50, *, seed=0, x=None, saturate=True, saturation_threshold=6, gene_totals=True, engine_opts=None, host=False):
+    """Posterior predictive check of a fit on the model's own scale, per cell and per (gene, clone): the multinomial log-likelihood of every assigned
+    cell at its called clone, and the per-clone pseudo-bulk totals, beside the same statistics of ``n_rep`` count matrices drawn from the fitted model.
+    The replicates are drawn AND reduced on the device (``engine.predictive_stats`` / ``ca_predictive_stats``): no replicate matrix is stored, copied
+    or uploaded.  Cells labelled "unassigned" are left out on both sides (all of them: ValueError); ``n_rep`` is at least 2.
+
+    ``Y`` [cells, genes] and ``L`` [genes, clones] as for ``clone_loglik``; the cells are the fit's own (``fit["clone"]``, ``fit["ml_params"]["psi"]``
+    when the fit has ``K > 0``, ``x`` exactly when it has ``beta``).  Observed side, one engine with ``Y`` resident (``engine_opts`` go to its
+    constructor): ``ll_observed[n] = clone_loglik(...)[n, called clone]`` with ``const=True``, ``T_observed`` from ``clone_gene_sums``.  A replicate
+    keeps the used cells' clones, ``psi``, ``x`` and OBSERVED row sums; replicate ``r`` is the matrix ``predictive_fit_mse(seed=seed)`` evaluates as
+    its replicate ``r`` (``seed``, ``draw = r``).  ``host=True`` runs the numpy restatements on both sides instead of the device; there is no silent
+    fallback otherwise.
+
+    Returns a dict.  ``cells``: the indices used.  Per used cell: ``ll_observed``, ``ll_replicate_mean``, ``ll_replicate_sd`` (sample sd),
+    ``z_cell`` = (observed - mean) / sd (NaN where the sd is 0: a cell without counts), ``p_cell`` = (1 + #{r: ll_rep <= ll_obs}) / (n_rep + 1).
+    Over all used cells: ``ll_total_observed``, ``ll_total_replicates`` [n_rep], ``z``.  With ``gene_totals``: ``T_observed``,
+    ``T_replicate_mean``, ``T_replicate_sd``, ``z_gene_clone`` [genes, clones] (NaN where the sd is 0) and ``p_gene_clone`` = min(1, 2 min(p_low,
+    p_high)) with the same +1 rule on both tails.
+
+    What the numbers mean: a very negative ``z_cell`` (``p_cell`` at its floor 1 / (n_rep + 1)) is a cell the fitted model explains worse than it
+    explains its own data -- a cell of a clone absent from the copy-number data, a doublet, a contaminating normal cell --, also when every clone fits
+    it badly and the posterior probabilities say nothing.  A large ``|z_gene_clone|`` is a gene that departs from the dosage model in that clone.
+    What they do not mean: the clone and ``psi`` were chosen to fit the observed cell, so the observed side is favoured and the check is conservative;
+    and real counts are overdispersed against a multinomial, so on real data ``z_cell`` is a ranking on a depth-aware scale, not a calibrated test."""
+    n_rep = int(n_rep)
+    if n_rep < 2:
+        raise ValueError("n_rep must be at least 2 (the replicates' spread is the scale)")
+    Lm, cn = _parse_cnv(L)
+    Ya = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Ya.shape
+    if Lm.shape[0] != G:
+        raise ValueError(f"L has {Lm.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(Lm.shape[1])])
+    if len(names) != Lm.shape[1]:
+        raise ValueError(f"fit has {len(names)} clone names but L has {Lm.shape[1]} columns (clones)")
+    clones = np.asarray(fit["clone"], dtype=object).reshape(-1)
+    if clones.shape[0] != N:
+        raise ValueError(f"fit has {clones.shape[0]} clone labels but Y has {N} rows (cells)")
+    lut = {c: i for i, c in enumerate(names)}
+    unknown = sorted({str(c) for c in clones if c not in lut and c != "unassigned"})
+    if unknown:
+        raise ValueError("clone labels that are no column of L: " + ", ".join(unknown))
+    idx = np.array([lut.get(c, -1) for c in clones], dtype=np.int32)
+    used = np.flatnonzero(idx >= 0)
+    if used.size == 0:
+        raise ValueError("every cell is \"unassigned\": there is nothing to evaluate")
+    ml = fit["ml_params"]
+    has_psi = ml.get("W") is not None and np.asarray(ml["W"]).size > 0
+    Ls, E, U, V = _fit_tables(fit, Lm, N, x, "fit" if has_psi else None, saturate, saturation_threshold)
+    rows = np.asarray(Ya.sum(axis=1)).reshape(-1)
+    if np.any(rows != np.floor(rows)):
+        raise ValueError("Y must hold whole numbers: a replicate keeps the observed row sums")
+    rows = rows.astype(np.int64)[used]
+    Uu = None if U is None else U[used]
+    if host:
+        ll_all = _clone_loglik_host(Ya, E, U, V, const=True)
+        T_obs = None
+        if gene_totals:
+            T_obs = np.zeros((G, Lm.shape[1]))
+            dense = Ya[used].toarray() if _is_sparse(Ya) else np.asarray(Ya)[used]
+            np.add.at(T_obs.T, idx[used], dense.astype(np.float64))
+        ll_rep, T_rep = _predictive_stats_host(E, V, Uu, idx[used], rows, seed, 0, n_rep, gene_totals=gene_totals)
+    else:
+        from . import engine as _engine
+        opts = dict(engine_opts or {})
+        eng = _engine.HipEngine(Ya, Ls, np.zeros((N, 0)), None, 0, **opts)
+        try:
+            ll_all = eng.clone_loglik(E, U, V, const=True)
+            T_obs = np.ascontiguousarray(eng.clone_gene_sums(idx)[0]) if gene_totals else None
+        finally:
+            eng.close()
+        ll_rep, T_rep = _engine.predictive_stats(E, V, Uu, idx[used], rows, seed, 0, n_rep, device=int(opts.get("device", 0)), gene_totals=gene_totals)
+    ll_obs = ll_all[used, idx[used]]
+    mean, sd = ll_rep.mean(1), ll_rep.std(1, ddof=1)
+    tot_rep = ll_rep.sum(0)
+    tot_sd = tot_rep.std(ddof=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z_cell = np.where(sd > 0, (ll_obs - mean) / sd, np.nan)
+    out = {"cells": used, "ll_observed": ll_obs, "ll_replicate_mean": mean, "ll_replicate_sd": sd, "z_cell": z_cell,
+           "p_cell": (1.0 + (ll_rep <= ll_obs[:, None]).sum(1)) / (n_rep + 1.0),
+           "ll_total_observed": float(ll_obs.sum()), "ll_total_replicates": tot_rep,
+           "z": float((ll_obs.sum() - tot_rep.mean()) / tot_sd) if tot_sd > 0 else float("nan")}
+    if gene_totals:
+        T_mean, T_sd = T_rep.mean(0), T_rep.std(0, ddof=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z_gc = np.where(T_sd > 0, (T_obs - T_mean) / T_sd, np.nan)
+        p_low = (1.0 + (T_rep <= T_obs[None]).sum(0)) / (n_rep + 1.0)
+        p_high = (1.0 + (T_rep >= T_obs[None]).sum(0)) / (n_rep + 1.0)
+        out.update({"T_observed": T_obs, "T_replicate_mean": T_mean, "T_replicate_sd": T_sd, "z_gene_clone": z_gc,
+                    "p_gene_clone": np.minimum(1.0, 2.0 * np.minimum(p_low, p_high))})
+    return out
+
+
 def _logexpr_sums_host(Y, group_idx, n_groups, size_factors=None, chunk=4096):
     """Float64 host form of ``HipEngine.logexpr_sums`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time),
     ``group_idx`` in [-1, n_groups) with -1 = leave the cell out.  Same return value, same refusals (ValueError)."""

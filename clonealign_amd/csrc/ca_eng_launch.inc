@@ -364,3 +364,12 @@ inline hipError_t launch_simulate(hipStream_t stream, const ca_sim_ops& o) {
                      o.G, o.D, o.plan.S, o.plan.nco, o.plan.hist_lds, (uint32_t)o.seed, (uint32_t)(o.seed >> 32), o.draw, o.q0);
   return hipGetLastError();
 }
+
+// ---- k_predictive: one launch over a batch of cells of ca_predictive_stats, `blocks` blocks walking them with the grid's stride (no engine: the call owns its stream) ----
+struct ca_pred_ops { const double *Et, *Vt, *U; const int32_t* clone; const int64_t* total; const double* lgtab; double *cum_blk, *lw_blk; int32_t* row_blk; double* ll;
+                     unsigned long long* T; int64_t n_cnt; int blocks, G, C, D, n_rep; ca_sim_plan plan; uint64_t seed, draw0, q0; };
+inline hipError_t launch_predictive(hipStream_t stream, const ca_pred_ops& o) {
+  hipLaunchKernelGGL(k_predictive, dim3((unsigned)o.blocks), dim3(CA_SIM_TB), o.plan.lds, stream, o.Et, o.Vt, o.U, o.clone, o.total, o.lgtab, o.plan.S > 1 ? o.cum_blk : nullptr,
+                     o.lw_blk, o.row_blk, o.ll, o.T, o.n_cnt, o.G, o.C, o.D, o.plan.S, o.plan.nco, o.plan.hist_lds, (uint32_t)o.seed, (uint32_t)(o.seed >> 32), o.draw0, o.n_rep, o.q0);
+  return hipGetLastError();
+}

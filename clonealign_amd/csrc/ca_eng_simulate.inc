@@ -7,6 +7,52 @@ int ca_simulate_kernel_ms(double* ms) {
   return CA_OK;
 }
 
+// The refusals ca_simulate_counts and ca_predictive_stats share, in ca_simulate_counts's order; each returns the refusal's text (without the entry point's
+// name), empty when there is none.  sim_check_shape: the sizes and the pointers (out_null: an output the entry point needs is NULL; null_msg says which).
+// sim_check_values: every entry; fills Et [C][G] and Vt [D][G].
+extern "C++" {
+namespace {
+std::string sim_check_shape(int64_t N, int32_t G, int32_t C, int32_t D, const double* E, const double* V, const double* U, const int32_t* clone, const int64_t* total,
+                            bool out_null, const char* null_msg, int64_t cell_offset) {
+  if (N < 0 || G < 1 || C < 1) return std::string("N = " + std::to_string(N) + ", G = " + std::to_string(G) + ", C = " + std::to_string(C) + ": N must be >= 0, G and C >= 1");
+  if (D < 0 || D > CA_LL_DMAX) return std::string("D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]");
+  if (D > 0 && (!U || !V)) return std::string("D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)");
+  if ((double)N * (double)G >= 4611686018427387904.0) return std::string("N x G = " + std::to_string(N) + " x " + std::to_string(G) + " is 2^62 or more");
+  if (!E || (N > 0 && (!clone || !total || out_null))) return std::string(null_msg);
+  if (cell_offset < 0 || cell_offset > ((int64_t)1 << 48) - N) return std::string("cell_offset = " + std::to_string(cell_offset) + ": cell_offset + N must lie in [0, 2^48]");
+  return std::string();
+}
+std::string sim_check_values(int64_t N, int32_t G, int32_t C, int32_t D, const double* E, const double* V, const double* U, const int32_t* clone, const int64_t* total,
+                             std::vector<double>& Et, std::vector<double>& Vt) {
+  Et.assign((size_t)C * G, 0.0); Vt.assign((size_t)D * G, 0.0);
+  // E: transposed to [C][G] (a block reads one clone's column, gene by gene); which clones can be drawn from at all
+  std::vector<char> possible((size_t)C, 0);
+  for (int g = 0; g < G; ++g)
+    for (int c = 0; c < C; ++c) {
+      const double v = E[(size_t)g * C + c];
+      if (!std::isfinite(v) || v < 0.0) return std::string("E has a negative or non-finite entry (gene " + std::to_string(g) + ", clone " + std::to_string(c) + ")");
+      Et[(size_t)c * G + g] = v;
+      if (v > 0.0) possible[(size_t)c] = 1;
+    }
+  for (int g = 0; g < G; ++g)
+    for (int d = 0; d < D; ++d) {
+      const double v = V[(size_t)g * D + d];
+      if (!std::isfinite(v)) return std::string("V has a non-finite entry (gene " + std::to_string(g) + ", factor " + std::to_string(d) + ")");
+      Vt[(size_t)d * G + g] = v;
+    }
+  for (int64_t n = 0; n < N; ++n) {
+    for (int d = 0; d < D; ++d)
+      if (!std::isfinite(U[(size_t)n * D + d])) return std::string("U has a non-finite entry (cell " + std::to_string(n) + ", factor " + std::to_string(d) + ")");
+    if (clone[n] < 0 || clone[n] >= C) return std::string("clone[" + std::to_string(n) + "] = " + std::to_string(clone[n]) + " is outside [0, " + std::to_string(C) + ")");
+    if (total[n] < 0 || total[n] > 2147483647) return std::string("total[" + std::to_string(n) + "] = " + std::to_string(total[n]) + " is outside [0, 2^31 - 1]");
+    if (total[n] > 0 && !possible[(size_t)clone[n]])
+      return std::string("total[" + std::to_string(n) + "] = " + std::to_string(total[n]) + " but E is zero in every gene of the cell's clone " + std::to_string(clone[n]));
+  }
+  return std::string();
+}
+}  // namespace
+}  // extern "C++"
+
 // Validates everything on the host before the first byte of Y is written, then runs the cells in batches whose device buffers (the int32 rows, and the
 // float64 table slab when the search table has two levels) stay below a quarter of a gigabyte; a batch is one memset, one or more launches over its work
 // items and a copy of its rows through two pinned chunks (the DMA of one chunk runs while the host copies the other into Y).  A cell's row depends on
@@ -16,37 +62,12 @@ int ca_simulate_counts(int64_t N, int32_t G, int32_t C, int32_t D, const double*
   auto fail = [&](int code, const std::string& m) { if (err) { strncpy(err, m.c_str(), 255); err[255] = 0; } return code; };
   auto refuse = [&](const std::string& m) { return fail(CA_ERR_INVALID, "ca_simulate_counts: " + m); };
   sim_kernel_ms = 0.0;
-  if (N < 0 || G < 1 || C < 1) return refuse("N = " + std::to_string(N) + ", G = " + std::to_string(G) + ", C = " + std::to_string(C) + ": N must be >= 0, G and C >= 1");
-  if (D < 0 || D > CA_LL_DMAX) return refuse("D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]");
-  if (D > 0 && (!U || !V)) return refuse("D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)");
-  if ((double)N * (double)G >= 4611686018427387904.0) return refuse("N x G = " + std::to_string(N) + " x " + std::to_string(G) + " is 2^62 or more");
-  if (!E || (N > 0 && (!clone || !total || !Y))) return refuse("E, clone, total and Y must not be NULL");
-  if (cell_offset < 0 || cell_offset > ((int64_t)1 << 48) - N) return refuse("cell_offset = " + std::to_string(cell_offset) + ": cell_offset + N must lie in [0, 2^48]");
+  std::string bad = sim_check_shape(N, G, C, D, E, V, U, clone, total, !Y, "E, clone, total and Y must not be NULL", cell_offset);
+  if (!bad.empty()) return refuse(bad);
   if (draw >> 48) return refuse("draw = " + std::to_string(draw) + " is 2^48 or more");
-  // E: transposed to [C][G] (a block reads one clone's column, gene by gene); which clones can be drawn from at all
-  std::vector<double> Et((size_t)C * G), Vt((size_t)D * G);
-  std::vector<char> possible((size_t)C, 0);
-  for (int g = 0; g < G; ++g)
-    for (int c = 0; c < C; ++c) {
-      const double v = E[(size_t)g * C + c];
-      if (!std::isfinite(v) || v < 0.0) return refuse("E has a negative or non-finite entry (gene " + std::to_string(g) + ", clone " + std::to_string(c) + ")");
-      Et[(size_t)c * G + g] = v;
-      if (v > 0.0) possible[(size_t)c] = 1;
-    }
-  for (int g = 0; g < G; ++g)
-    for (int d = 0; d < D; ++d) {
-      const double v = V[(size_t)g * D + d];
-      if (!std::isfinite(v)) return refuse("V has a non-finite entry (gene " + std::to_string(g) + ", factor " + std::to_string(d) + ")");
-      Vt[(size_t)d * G + g] = v;
-    }
-  for (int64_t n = 0; n < N; ++n) {
-    for (int d = 0; d < D; ++d)
-      if (!std::isfinite(U[(size_t)n * D + d])) return refuse("U has a non-finite entry (cell " + std::to_string(n) + ", factor " + std::to_string(d) + ")");
-    if (clone[n] < 0 || clone[n] >= C) return refuse("clone[" + std::to_string(n) + "] = " + std::to_string(clone[n]) + " is outside [0, " + std::to_string(C) + ")");
-    if (total[n] < 0 || total[n] > 2147483647) return refuse("total[" + std::to_string(n) + "] = " + std::to_string(total[n]) + " is outside [0, 2^31 - 1]");
-    if (total[n] > 0 && !possible[(size_t)clone[n]])
-      return refuse("total[" + std::to_string(n) + "] = " + std::to_string(total[n]) + " but E is zero in every gene of the cell's clone " + std::to_string(clone[n]));
-  }
+  std::vector<double> Et, Vt;
+  bad = sim_check_values(N, G, C, D, E, V, U, clone, total, Et, Vt);
+  if (!bad.empty()) return refuse(bad);
   if (N == 0) return CA_OK;
 
   const ca_sim_plan plan = sim_plan(G);

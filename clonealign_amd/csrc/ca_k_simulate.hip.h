@@ -77,6 +77,8 @@ k_simulate(const double* __restrict__ Et /*[C][G]*/, const double* __restrict__ 
   int32_t* yrow = Y + (size_t)cell * G;
   const double* __restrict__ u = U + cell * D;
 
+  // (Steps 1 and 2 are repeated statement by statement in sim_table of ca_k_predictive.hip.h, whose replicate rows must be these rows bit for bit: a change
+  // here is made there too; tests/test_gpu_predictive.py compares the two.)
   // 1. the shift: the largest exponent over the genes that can be drawn
   double m = -HUGE_VAL;
   if (D > 0) {

@@ -51,6 +51,8 @@ EXPORTS = (
     "ca_project_cells", "ca_group_project_cells",
     # count rows drawn from a fitted model (simulate_counts), no handle, additions to ABI 6
     "ca_simulate_counts", "ca_simulate_kernel_ms",
+    # log-likelihoods and per-clone gene totals of replicate rows that never leave the device (predictive_stats), no handle, additions to ABI 6
+    "ca_predictive_stats", "ca_predictive_kernel_ms",
 )
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
@@ -163,6 +165,9 @@ def load_library(path=None):
     lib.ca_simulate_counts.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                        C.c_int64, C.c_int32, C.c_void_p, C.c_char_p]
     lib.ca_simulate_kernel_ms.argtypes = [C.POINTER(C.c_double)]
+    lib.ca_predictive_stats.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                        C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p]
+    lib.ca_predictive_kernel_ms.argtypes = [C.POINTER(C.c_double)]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -941,6 +946,57 @@ def simulate_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``simulate_counts`` call took (HIP events around each launch)."""
     ms = C.c_double(0.0)
     load_library().ca_simulate_kernel_ms(C.byref(ms))
+    return ms.value
+
+
+def predictive_stats(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=0, device=0, gene_totals=True, out=None):
+    """Statistics of ``n_rep`` replicate rows of ``simulate_counts`` without the rows (ca_predictive_stats; include/clonealign_hip.h states them): replicate
+    ``r`` is the matrix ``simulate_counts(..., seed, draw=draw0 + r, cell_offset)`` returns, drawn and reduced on the device.  Arguments as for
+    ``simulate_counts``.  Returns ``(ll_rep, T_rep)``: ``ll_rep`` float64 [N, n_rep], the multinomial log-probability of each replicate row under the
+    cell's own ``p``; ``T_rep`` int64 [n_rep, G, C], the rows summed per clone (None with ``gene_totals=False``).  ``out``: a pair of C-contiguous arrays
+    of these shapes and dtypes to fill instead (the second None without totals).  ``ll_rep[n, r]`` depends on (seed, draw0 + r, cell_offset + n) and the
+    cell's own arguments alone; ``T_rep`` of cells split over calls adds up.  Refusals raise EngineError."""
+    lib = load_library()
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"predictive_stats: E is {E.shape}; expected (genes, clones)")
+    G, Cn = E.shape
+    clone = np.ascontiguousarray(clone, dtype=np.int32).reshape(-1)
+    N = clone.shape[0]
+    total = np.ascontiguousarray(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
+    D = 0
+    if (U is None) != (V is None):
+        raise ValueError("predictive_stats: U and V go together (both, or neither)")
+    if U is not None:
+        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"predictive_stats: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = int(U.shape[1])
+    n_rep = int(n_rep)
+    if not -2 ** 31 <= n_rep < 2 ** 31:
+        raise ValueError(f"predictive_stats: n_rep = {n_rep} does not fit 32 bits")
+    R = max(n_rep, 0)
+    if out is None:
+        ll, T = np.zeros((N, R), dtype=np.float64), (np.zeros((R, G, Cn), dtype=np.int64) if gene_totals else None)
+    else:
+        ll, T = out
+        if ll.dtype != np.float64 or ll.shape != (N, R) or not ll.flags.c_contiguous:
+            raise ValueError(f"predictive_stats: out[0] must be a C-contiguous float64 array of shape ({N}, {R})")
+        if T is not None and (T.dtype != np.int64 or T.shape != (R, G, Cn) or not T.flags.c_contiguous):
+            raise ValueError(f"predictive_stats: out[1] must be None or a C-contiguous int64 array of shape ({R}, {G}, {Cn})")
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    err = C.create_string_buffer(256)
+    rc = lib.ca_predictive_stats(N, G, Cn, D, ptr(E), ptr(V) if D > 0 else None, ptr(U) if D > 0 else None, ptr(clone), ptr(total),
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0) & 0xFFFFFFFFFFFFFFFF, n_rep, int(cell_offset), int(device), ptr(ll), ptr(T), err)
+    if rc != CA_OK:
+        raise EngineError(rc, err.value.decode() or "ca_predictive_stats")
+    return ll, T
+
+
+def predictive_kernel_ms():
+    """Milliseconds the kernel launches of this thread's last ``predictive_stats`` call took (HIP events around each launch)."""
+    ms = C.c_double(0.0)
+    load_library().ca_predictive_kernel_ms(C.byref(ms))
     return ms.value
 
 

@@ -556,6 +556,31 @@ int ca_simulate_counts(int64_t N, int32_t G, int32_t C, int32_t D, const double*
 /* milliseconds the k_simulate launches of the calling thread's last ca_simulate_counts took (HIP events around each launch, summed; 0 after a refusal) */
 int ca_simulate_kernel_ms(double* ms);
 
+/* Predictive check on the device, needs no handle: the statistics of n_rep replicate rows of ca_simulate_counts WITHOUT the rows.  Notation, layouts and
+ * the sampler are ca_simulate_counts's.  For r = 0 .. n_rep - 1 let y^(r)_n be the row ca_simulate_counts(..., seed, draw = draw0 + r, cell_offset, ...)
+ * returns for cell n -- the same row bit for bit: same table, same Philox counters, same search; it is drawn and reduced inside one block and never
+ * written to global memory as a matrix.  Outputs (host, row-major):
+ *   ll_rep[n][r] = Multinomial(total_n, p_n).log_prob(y^(r)_n)
+ *                = lgamma(total_n + 1) - sum_g lgamma(y_g + 1) + sum over g with y_g > 0 of y_g (log E[g][c_n] + eta_g - m - log Z_n),
+ *     with eta_g, m and w_g as in steps 1-2 of the sampler and Z_n = cum_{G-1}, the table's own total of the w_g; log w_g is taken as log E + eta_g - m,
+ *     not as log(exp(...)).  total_n = 0 gives exactly 0; a drawn gene always has w > 0, so every value is finite.                  (N x n_rep float64)
+ *   T_rep[r][g][c] = sum over the call's cells with clone[n] == c of y^(r)_ng: the pseudo-bulk totals ca_clone_gene_sums gives for observed data.
+ *     May be NULL.  The caller's buffer is overwritten, not added to.                                                              (n_rep x G x C int64)
+ * Float64 throughout.  The float sums run in a fixed order without atomics (a thread's genes ascending, the wave by shuffles, the block's sixteen waves
+ * ascending): two calls agree bit for bit, and ll_rep of a cell depends on (seed, draw0 + r, cell_offset + n) and the cell's own inputs alone -- not on N,
+ * the internal batching, n_rep, or how a caller splits the cells or the replicates between calls: replicate r of a call at draw0 equals replicate 0 of a
+ * call at draw0 + r, and cells [0, N) in one call equal [0, h) and [h, N) with cell_offset = h, whose T_rep then add up.  T_rep is accumulated with
+ * integer atomics in int64: exact, whatever the order of arrival.  Device buffers stay below 256 MB (the replicates go in chunks and the cells in batches that fit) as long as one replicate's
+ * totals do, C x G x 8 bytes <= 64 MB; there is no ca_group_* form (shard with cell_offset).
+ * CA_ERR_INVALID (message in err, naming the argument; nothing is written to ll_rep or T_rep): everything ca_simulate_counts refuses (draw0 in the place
+ * of draw); n_rep < 1; draw0 + n_rep > 2^48; ll_rep NULL.  err (optional, >= 256 bytes) receives the message on failure. */
+int ca_predictive_stats(int64_t N, int32_t G, int32_t C, int32_t D, const double* E /* G x C */, const double* V /* G x D, or NULL */,
+                        const double* U /* N x D, or NULL */, const int32_t* clone /* N */, const int64_t* total /* N */, uint64_t seed, uint64_t draw0,
+                        int32_t n_rep, int64_t cell_offset, int32_t device, double* ll_rep /* N x n_rep */, int64_t* T_rep /* n_rep x G x C, or NULL */,
+                        char* err);
+/* milliseconds the k_predictive launches of the calling thread's last ca_predictive_stats took (HIP events around each launch, summed; 0 after a refusal) */
+int ca_predictive_kernel_ms(double* ms);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ONE fit, cell-sharded over several devices of ONE process (ABI 6; SURVEY.md section 8b "multi-GPU via one process / 8 devices,
  * communicator created per fit", section 8e).  The reference's caller is a single R session: inference_tflow() is called once
