@@ -236,7 +236,7 @@ struct ca_ys_io {
   const int* esc_off; const unsigned* esc;   // the 4-bit image's escape list (k_esc_fill); null: the image is the 1-byte one (Ys)
 };
 #ifndef CA_YS4_DEPTH
-#define CA_YS4_DEPTH 4   // pieces in flight per wave of the 4-bit image's own launch (2 KiB each)
+#define CA_YS4_DEPTH 4   // pieces in flight per wave of the 4-bit image's own launch (2 KiB each); round 12, at four waves per SIMD: 2 is 2 us per iteration slower, 8 spills
 #endif
 #ifndef CA_YS4_WAVES
 #define CA_YS4_WAVES 4   // waves per SIMD of the 4-bit image's own launch: 128 VGPRs, four blocks per CU -- the whole grid of cfg-3 in one round
@@ -306,11 +306,11 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wsrc), 0, NP * 1024, 0x00020000);
   const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(Pr + (c0 >> 6) * 64), 0, 0x7FFFFFFF, 0x00020000);
-  auto issue = [&](int slot, int st, int a) {
+  auto issue = [&](int slot, int st, int a, unsigned vo) {
     const int so = (st * (Gp / 64) + a) * PB;   // (scalar)
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
-      const ca_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(voff + 1024u * (unsigned)i), so, 2 /* nt: streamed once */);
+      const ca_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(vo + 1024u * (unsigned)i), so, 2 /* nt: streamed once */);
       R[slot][i] = (uint4){v.x, v.y, v.z, v.w};
     }
     if (!Y4L) {
@@ -329,9 +329,14 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
     wimg[1] = wsrc[threadIdx.x + CA_YM_TB];
     if (lane <= nsteps) eoff = io.esc_off[((int64_t)blk * 4 + wv) * RS + (64 * lane < RS ? 64 * lane : RS)];
   }
+  uint4 pr_nx = {0u, 0u, 0u, 0u};
   if (nsteps > 0) {
+    if (Y4L) {   // psi's digits of the first step, in front of its pieces
+      const ca_v4u pv = __builtin_amdgcn_raw_buffer_load_b128(rp, (int)voff, 0, 0);
+      pr_nx = (uint4){pv.x, pv.y, pv.z, pv.w};
+    }
 #pragma unroll
-    for (int d_ = 0; d_ < DEPTH; ++d_) issue(d_, 0, d_);
+    for (int d_ = 0; d_ < DEPTH; ++d_) issue(d_, 0, d_, voff);
   }
   if (Y4L) {
     static_assert(2 * CA_YM_TB == CA_YS_GW, "the block's threads hold the segment's W image and column sums in two halves");
@@ -371,7 +376,11 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
     const int64_t cs = c0 + (int64_t)st * 64;
     const bool more = st + 1 < nsteps;   // (wave-uniform)
     uint4 pr;
-    {
+    if (Y4L) {
+      pr = pr_nx;   // (loaded in front of the step's first pieces: the piece loop, below)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) acc_yw[t] = (ca_i32x4){0, 0, 0, 0};
+    } else {
       // (the wait for this load is also the wait for the step's first piece, which is needed next anyway; a stream wave has ~2000 cycles per piece)
       const ca_v4u pv = __builtin_amdgcn_raw_buffer_load_b128(rp, (int)voff, st * 1024, 0);
       pr = (uint4){pv.x, pv.y, pv.z, pv.w};
@@ -408,13 +417,24 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
           *reinterpret_cast<uint4*>(const_cast<unsigned char*>(rd_row) + 16 * t * CA_YS_PITCH) = av;
           acc_yw[t] = ca_mfma_i8(av, wr, acc_yw[t]);
         }
-        if (a + DEPTH < NP) issue(slot, st, a + DEPTH);
-        else if (more) issue(slot, st + 1, a + DEPTH - NP);
+        if (a + DEPTH < NP) issue(slot, st, a + DEPTH, voff);
+        else if (Y4L) {
+          // (round 12) the next step's first pieces WITHOUT a branch: the counter pass then waits for this step's last pieces with a counted vmcnt, not
+          // with the stricter wait of two paths.  Past the strip's last step the lanes' offsets lie beyond the resource's range: a buffer load out of range
+          // moves nothing and returns zeros.  psi's digits of the next step go out in front of its first piece, so their wait is that piece's and the escapes
+          // and the flush of this step run with DEPTH pieces in flight.
+          const unsigned vo = more ? voff : 0x80000000u + voff;
+          if (a + DEPTH == NP) {
+            const ca_v4u pv = __builtin_amdgcn_raw_buffer_load_b128(rp, (int)vo, (st + 1) * 1024, 0);
+            pr_nx = (uint4){pv.x, pv.y, pv.z, pv.w};
+          }
+          issue(slot, st + 1, a + DEPTH - NP, vo);
+        } else if (more) issue(slot, st + 1, a + DEPTH - NP, voff);
       } else {
 #pragma unroll
         for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(wr_dst + 16 * i * CA_YS_PITCH) = R[slot][i];
-        if (a + DEPTH < NP) issue(slot, st, a + DEPTH);
-        else if (more) issue(slot, st + 1, a + DEPTH - NP);
+        if (a + DEPTH < NP) issue(slot, st, a + DEPTH, voff);
+        else if (more) issue(slot, st + 1, a + DEPTH - NP, voff);
         // row products: the four cell tiles against this 64-gene block
 #pragma unroll
         for (int t = 0; t < 4; ++t) {

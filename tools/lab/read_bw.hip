@@ -1,9 +1,10 @@
 // tools/lab/read_bw.hip -- what a kernel that ONLY reads a 500 MB buffer reaches on this device, in the access shapes the count-matrix stream could take:
-//   hipcc -O3 --offload-arch=gfx950 -o tools/lab/read_bw.bin tools/lab/read_bw.hip && tools/lab/read_bw.bin
+//   hipcc -O3 --offload-arch=gfx950 -o tools/lab/read_bw.bin tools/lab/read_bw.hip && tools/lab/read_bw.bin        (all shapes; `read_bw.bin y4`: the 4-bit launch's walk only)
 // (lab: the ceiling the stream kernel's 5.5-5.8 TB/s is to be read against; MI355X_MICROARCH.md quotes 6.3 TB/s for a float4 COPY)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld_nt(const uint4* p) { const v4u v = __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p)); return (uint4){v.x, v.y, v.z, v.w}; }
@@ -72,7 +73,61 @@ __global__ void __launch_bounds__(256) k_read_engine(const uint4* __restrict__ p
   }
   if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) out[0] = 1;
 }
-int main() {
+// the 4-bit image's own launch (round 12): the same layout and walk in 2-KiB pieces (two 1-KiB loads), DEPTH pieces in flight per wave and ROLLING
+// (a piece is consumed, then the piece DEPTH further on is issued into its registers), across the cell steps of the strip without a drain
+template <int DEPTH>
+__global__ void __launch_bounds__(256, 4) k_read_engine4(const uint4* __restrict__ p, int nsteps_total, int gb, int steps, unsigned* __restrict__ out) {
+  const int nseg = gb / 8, rg = blockIdx.x / nseg, seg = blockIdx.x % nseg, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int st0 = (rg * 4 + wv) * steps;
+  const int ns = st0 + steps <= nsteps_total ? steps : (st0 < nsteps_total ? nsteps_total - st0 : 0);
+  const int np = ns * 8;
+  uint4 acc = {0, 0, 0, 0}, v[DEPTH][2];
+  auto issue = [&](int d, int k) {
+    const size_t pc = (size_t)(st0 + k / 8) * gb + seg * 8 + k % 8;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) v[d][i] = k < np ? ld_nt(p + pc * 128 + i * 64 + lane) : (uint4){0, 0, 0, 0};
+  };
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) issue(d, d);
+  for (int k = 0; k < np; k += DEPTH) {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) { acc.x ^= v[d][i].x; acc.y ^= v[d][i].y; acc.z ^= v[d][i].z; acc.w ^= v[d][i].w; }
+      issue(d, k + d + DEPTH);
+    }
+  }
+  if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) out[0] = 1;
+}
+template <int DEPTH>
+static int run_engine4(int ncells, hipEvent_t a, hipEvent_t b, unsigned* out) {
+  // ncells x 5120 genes at 4 bits: cell steps x 80 gene blocks x 2 KiB; strips of 4 cell steps (256 cells), 36 KiB of dynamic LDS: four blocks per CU
+  const int gb = 80, nst = (ncells + 63) / 64, steps = 4;
+  const size_t eb = (size_t)nst * gb * 2048;
+  uint4* big; CK(hipMalloc(&big, eb)); CK(hipMemset(big, 1, eb));
+  const int nrg = (nst + 4 * steps - 1) / (4 * steps), blocks = nrg * (gb / 8);
+  const size_t lds = 36 * 1024;
+  auto go = [&] { hipLaunchKernelGGL((k_read_engine4<DEPTH>), dim3(blocks), dim3(256), lds, 0, big, nst, gb, steps, out); };
+  for (int i = 0; i < 5; ++i) go();
+  CK(hipDeviceSynchronize());
+  float best = 1e9f, tot = 0.f;
+  const int reps = 20;
+  for (int r = 0; r < reps; ++r) { (void)hipEventRecord(a); go(); (void)hipEventRecord(b); (void)hipEventSynchronize(b); float ms; (void)hipEventElapsedTime(&ms, a, b); best = ms < best ? ms : best; tot += ms; }
+  printf("4-bit walk, %d cells (%d blocks, 4 per CU), 2-KiB pieces, %d in flight per wave: best %.1f us = %.2f TB/s, mean %.1f us (%.3f GB)\n", ncells, blocks, DEPTH, best * 1e3,
+         eb / (best * 1e-3) / 1e12, tot / reps * 1e3, eb * 1e-9);
+  CK(hipFree(big));
+  return 0;
+}
+int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "y4")) {   // only the 4-bit launch's walk (the floor its time is read against)
+    hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+    unsigned* out; CK(hipMalloc(&out, 4));
+    for (int rep = 0; rep < 2; ++rep) {
+      if (run_engine4<2>(100000, a, b, out) || run_engine4<4>(100000, a, b, out)) return 1;
+    }
+    for (int nc : {12500, 25000, 50000}) if (run_engine4<4>(nc, a, b, out)) return 1;
+    return 0;
+  }
   const size_t bytes = 500ull << 20;
   uint4* buf; unsigned* out;
   CK(hipMalloc(&buf, bytes)); CK(hipMalloc(&out, 4));
