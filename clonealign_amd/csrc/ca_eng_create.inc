@@ -444,6 +444,8 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   // the series form's forward moments ride on its in-line count-matrix stream's launch (CA_VAR_MOM_RIDE, ca_polymom.hip.h): wherever that stream exists and runs in
   // line -- every shape measured gains or is level (profiles/r11_mom_ride_ab.txt); a pass that launches no stream keeps the moments' own launches (run_fused)
   h->mom_ride = h->poly && h->y_ys && !h->poly_side && h->host_dev && variant_on(h, CA_VAR_MOM_RIDE, "CA_MOM_RIDE");
+  // the series form's cell launch without the memory and LDS-crossbar round trips inside its passes (CA_VAR_CELL_LEAN, ca_poly.hip): wherever the series form runs
+  h->cell_lean = h->poly && variant_on(h, CA_VAR_CELL_LEAN, "CA_CELL_LEAN");
   // the Y stream rides on the forward sweep's launch: 1-byte storage, K = 1, the fused sweep with its default block shapes
   h->ride_ok = h->ystore == CA_YSTORE_U8 && K == 1 && D <= 2 && h->fused_ok && !h->c16 && h->fwd_cell && (h->fc_tl == 6 || h->fc_tl == 8 || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
                !h->y_ys && variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE");

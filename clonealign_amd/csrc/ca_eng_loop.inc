@@ -825,7 +825,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     // the CELLS: no cells x genes sweep.  The count-matrix products of this state run as their own launch (in line).
     // Order: the forward moments ride as the first blocks of the count-matrix stream's launch (CA_VAR_MOM_RIDE, below); where they cannot, their launches come
     // FIRST, on an empty device, and the stream's launch behind them (lab, poly_side: on the side stream beside the cell launch, deferred since the update).
-    cp.etamax2 = h->poly_zero; cp.coefq = nullptr; cp.vmm_at = nullptr; cp.etamax_w = nullptr;
+    cp.etamax2 = h->poly_zero; cp.coefq = nullptr; cp.vmm_at = nullptr; cp.etamax_w = nullptr;   // (the zeros: read only with CA_VAR_CELL_LEAN off)
     ca_xsrc xs_m;
     CACK(poly_xsrc(h, &xs_m));
     // Lab (ca_options.reserved[1] = 4): the moment launches on a high-priority side stream BESIDE the count-matrix stream's launch, the cell launch waiting for both.
@@ -903,7 +903,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     }
     e = ca_poly_cells(h->stream, &h->pws, h->N, h->C, h->K, &cp, h->alpha_u, h->cell_part, h->dFpart, yfin_rides ? &yfin_ride : nullptr,
                       sh ? &ltail : nullptr, h->poly_xmax_ready ? h->poly_xpart : nullptr, (int)cdiv(h->N, CA_TB), h->F, sh ? h->red + h->off_x : nullptr,
-                      h->opt.rank, std::max(h->opt.world, 1));
+                      h->opt.rank, std::max(h->opt.world, 1), h->cell_lean);
     h->mon_tail_local = sh;   // (the tail set up below starts with its local sums made)
     if (sh) { h->poly_xslot_pending = true; h->poly_xglob_steps = -1; }   // (the slots hold THIS rank's number until the collective has summed them)
     HIPCK(h, e);

@@ -270,20 +270,71 @@ struct ca_cell_ptrs {
 // hoisted constant A_nc.  A small sweep block (<= 32 cells: ONE pass of the epilogue) loads them BEFORE its k-loop, so that the epilogue's fp64
 // chain starts from registers instead of from a round of loads behind the combine barrier (the block's CU has nothing else to hide it with).
 struct ca_cell_pre { float gl; double sn, Anc; };
-template <int CP, bool WR = true>   // WR = false (mc_samples = 2, four draws in one sweep): the monitor pass's pair of samples -- sums only, no coef / d logits
+// The series form's cell launch (CA_VAR_CELL_LEAN, ca_poly.hip) runs one pass of 32 or 64 cells as a single chain of latencies, and every trip to memory or through
+// the LDS crossbar inside the epilogue is a link of it.  Its lean form of the epilogue makes none: the exponent bound is the constant 0.0 (the series form has none:
+// ca_cell_ptrs::etamax2 points at zeros there), c_n and psi (D = K = 1: psi_n is the x the caller evaluated its series at) come with `pre`, loaded a pass ahead,
+// and the lane groups' reductions go through the DPP network.  Same operands, same pairing, same order: the same bits.
+struct ca_cell_pre_lean : ca_cell_pre { double cn, x; };
+// v of lane i ^ O, for O = 1, 2, 4 (inside a row of 16 lanes: what the lane groups of 4 and 8 need), in registers: __shfl_xor's pairing without its ds_bpermute.
+// (xor 1, 2: quad_perm; xor 4: the lanes of the even banks of four read four lanes up, row_shl:4, those of the odd banks four lanes down, row_shr:4)
+template <int O>
+__device__ __forceinline__ double ca_dpp_xor(double v) {
+  static_assert(O == 1 || O == 2 || O == 4, "inside a row of 16 lanes");
+  const uint64_t u = __builtin_bit_cast(uint64_t, v);
+  const int lo = (int)(uint32_t)u, hi = (int)(uint32_t)(u >> 32);
+  int rl, rh;
+  if constexpr (O == 1) {
+    rl = __builtin_amdgcn_update_dpp(lo, lo, 0xB1, 0xF, 0xF, false);   // quad_perm:[1,0,3,2]
+    rh = __builtin_amdgcn_update_dpp(hi, hi, 0xB1, 0xF, 0xF, false);
+  } else if constexpr (O == 2) {
+    rl = __builtin_amdgcn_update_dpp(lo, lo, 0x4E, 0xF, 0xF, false);   // quad_perm:[2,3,0,1]
+    rh = __builtin_amdgcn_update_dpp(hi, hi, 0x4E, 0xF, 0xF, false);
+  } else {
+    rl = __builtin_amdgcn_update_dpp(lo, lo, 0x104, 0xF, 0x5, false);  // row_shl:4, banks 0 and 2: lane i <- lane i + 4
+    rl = __builtin_amdgcn_update_dpp(rl, lo, 0x114, 0xF, 0xA, false);  // row_shr:4, banks 1 and 3: lane i <- lane i - 4
+    rh = __builtin_amdgcn_update_dpp(hi, hi, 0x104, 0xF, 0x5, false);
+    rh = __builtin_amdgcn_update_dpp(rh, hi, 0x114, 0xF, 0xA, false);
+  }
+  return __builtin_bit_cast(double, ((uint64_t)(uint32_t)rh << 32) | (uint64_t)(uint32_t)rl);
+}
+// sum / maximum over a group of CP lanes, every lane with the result: lane i with lane i ^ o, o = CP / 2 ... 1, as the __shfl_xor loops pair them
+template <int CP>
+__device__ __forceinline__ double ca_dpp_gsum(double v) {
+  static_assert(CP == 4 || CP == 8, "lane groups inside a row of 16");
+  if constexpr (CP == 8) v += ca_dpp_xor<4>(v);
+  v += ca_dpp_xor<2>(v);
+  v += ca_dpp_xor<1>(v);
+  return v;
+}
+template <int CP>
+__device__ __forceinline__ double ca_dpp_gmax(double v) {
+  static_assert(CP == 4 || CP == 8, "lane groups inside a row of 16");
+  if constexpr (CP == 8) v = fmax(v, ca_dpp_xor<4>(v));
+  v = fmax(v, ca_dpp_xor<2>(v));
+  v = fmax(v, ca_dpp_xor<1>(v));
+  return v;
+}
+template <int CP, bool WR = true,   // WR = false (mc_samples = 2, four draws in one sweep): the monitor pass's pair of samples -- sums only, no coef / d logits
+          bool LEAN = false>        // LEAN: `pre` is a ca_cell_pre_lean, D = 1 and K <= 1 (the series form's cell launch); every other caller gets the code it had
 __device__ __forceinline__ void ca_cell_fused_group(const ca_cell_ptrs& p, const double* la, int64_t n, int64_t N, int C, int D, int K,
                                                     double ZA, double ZB, ca_cell_acc& acc, const ca_cell_pre* pre = nullptr,
                                                     float* cf_out = nullptr /* this lane's coef as stored (0 where none), for a caller that goes on with it */) {
   const int c = threadIdx.x % CP;
   auto gmax = [](double v) {
+    if constexpr (LEAN) return ca_dpp_gmax<CP>(v);
+    else {
 #pragma unroll
     for (int o = CP / 2; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, CP));
     return v;
+    }
   };
   auto gsum = [](double v) {
+    if constexpr (LEAN) return ca_dpp_gsum<CP>(v);
+    else {
 #pragma unroll
     for (int o = CP / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, CP);
     return v;
+    }
   };
   const bool okn = n < N, ok = okn && c < C;
   const int64_t nn = okn ? n : N - 1;
@@ -296,7 +347,8 @@ __device__ __forceinline__ void ca_cell_fused_group(const ca_cell_ptrs& p, const
   const double lg = gl - lse;
   const double gam = ok ? ex / se : 0.0;
   const double sn = pre ? pre->sn : p.s64[nn];
-  const double em = (D > 0) ? (double)p.etamax2[nn] * CA_LN2 : 0.0;
+  double em = 0.0;   // (LEAN: the zero it would read, times ln 2)
+  if constexpr (!LEAN) em = (D > 0) ? (double)p.etamax2[nn] * CA_LN2 : 0.0;
   const double Anc = pre ? pre->Anc : p.A[nn * C + cc];
   double llpA = Anc - sn * (log(ZA) + em);
   double llpB = Anc - sn * (log(ZB) + em);
@@ -347,6 +399,14 @@ __device__ __forceinline__ void ca_cell_fused_group(const ca_cell_ptrs& p, const
   if (ok) { acc.ee += gam * llpA; acc.pr += gam * la[cc]; acc.eeB += gam * llpB; }
   if (live) acc.q += gam * lg;
   acc.gsumc += gam;
+  if constexpr (LEAN) {
+    const ca_cell_pre_lean* pl = static_cast<const ca_cell_pre_lean*>(pre);
+    if (okn && c == 0) {
+      acc.ee += pl->cn;
+      acc.eeB += pl->cn;
+      if (K > 0) acc.pr += -0.5 * pl->x * pl->x - 0.5 * CA_LOG2PI;   // (K = D = 1: psi_n is x)
+    }
+  } else
   if (okn && c == 0) {
     acc.ee += p.cn[nn];
     acc.eeB += p.cn[nn];

@@ -23,7 +23,7 @@ inline bool ca_poly_ok(int D, int S, int C) { return D == 1 && S == 1 && C >= 3 
 size_t ca_poly_workspace_bytes(int G, int n_cell_blocks);
 void ca_poly_bind(ca_poly_ws* w, void* base, int G, int n_cell_blocks);
 // forward, two steps: (1) the moments of both draws' M over the gene bins (three small launches); (2) per cell Z (both draws), dZ/dx (train draw), the cell
-// epilogue (cell_ptrs: a ca_cell_ptrs whose etamax2 is a zero vector), d/dF into dF[N] and the backward moments.  backward: red_g[g][0] = d/dmu,
+// epilogue (cell_ptrs: a ca_cell_ptrs whose etamax2 is a zero vector; the lean form does not read it), d/dF into dF[N] and the backward moments.  backward: red_g[g][0] = d/dmu,
 // red_g[g][1] = d/dV (the sweep's share, as k_bwd_mfma + k_colsum leave it).
 // (xpart / nx in either: max |x| of this state per piece of cells as the merged update that made the state left it, ca_merge_args::xpart -- no k_poly_xmax launch;
 //  NULL / 0: the launch is made)
@@ -46,6 +46,7 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
                          const void* local_tail /* cell-sharded: the pending monitor pass's ca_small_args with reduce_only (its local block sums ride on the moments'
                                                    reduction launch), or NULL */,
                          const float* xs_part, int xs_n, const float* xs_F, double* xs_slots /* cell-sharded: this rank's max |x| slot rides there too, or NULL */,
-                         int rank, int world);
+                         int rank, int world,
+                         bool lean /* CA_VAR_CELL_LEAN: the passes without their memory and LDS-crossbar round trips (k_poly_cell<CP, true>); the same bits either way */);
 hipError_t ca_poly_backward(hipStream_t st, const ca_poly_ws* w, const float* V, const float* mu, const float* Lb, int G, int C, double* red_g,
                             const void* small_tail /* a ca_small_args (pending monitor tail, run by an extra block) or NULL */);

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "ca_poly.h"
 
@@ -106,7 +107,16 @@ __global__ void __launch_bounds__(TB_B) k_poly_B(ca_pm_args a) {
 }
 
 // ---- K2: per cell: Z for both draws and dZ/dx for the train draw by Horner over the bins, the cell epilogue, d/dF, the backward moments --------------
-template <int CP>
+// A block's pass over its 32 (CP = 8) or 64 cells is ONE chain of latencies (two blocks per CU at 241 VGPRs: nothing else on the SIMD to fill it), so what a pass
+// costs is the number of round trips on that chain, not its arithmetic.  LEAN (CA_VAR_CELL_LEAN, the default) takes out those the result does not need:
+//   * no global load inside a pass but load_pass's prefetch of the NEXT pass -- the exponent bound the epilogue would read is a vector of zeros here, c_n travels
+//     with the prefetch, psi of the prior term is x (ca_cell_pre_lean); without them no s_waitcnt vmcnt(0) stands between the loop header and the first barrier,
+//     which on this ISA would also wait for the pass's own coef / d logits / dF stores;
+//   * the reductions over a cell's 4 or 8 lanes (two maxima / sums of the softmax, the epilogue's f-bar, d/dF) through DPP moves instead of ds_bpermute: twelve
+//     dependent trips through the LDS crossbar less per pass (ca_dpp_gsum / ca_dpp_gmax: __shfl_xor's pairing);
+//   * the powers x^k by selects into the (up to) RQ / CP values a lane keeps and unconditional stores, instead of 22 steps of "multiply, branch on exec, store".
+// Every sum keeps its operands and its order: LEAN = false is the launch as it was, and the two agree to the bit (tests/test_gpu_cell_lean.py).
+template <int CP, bool LEAN>
 __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restrict__ hdr, const double* __restrict__ tabB, ca_cell_ptrs p,
                                                      const float* __restrict__ alpha_u, double* __restrict__ cell_part, int64_t N, int C, int K,
                                                      float* __restrict__ dF /*[N]*/, double* __restrict__ Qpart /*[grid][nb][R+2][C]*/, int ncb, ca_yfin_args yfin) {
@@ -131,7 +141,9 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
   __shared__ double sm[CA_TB];
   __shared__ double la[64];
   __shared__ double s_eb[CPB][NB];            // exp(x v_b)
-  __shared__ double s_xp[CPB][RQ];            // x^k
+  constexpr int NXK = (RQ + CP - 1) / CP;     // powers a lane keeps (LEAN): k = c, c + CP, ...
+  constexpr int XS = LEAN ? NXK * CP : RQ;    // (LEAN: a row padded to whole rounds of the lane group, so that its stores need no bound; the padding is never read)
+  __shared__ double s_xp[CPB][XS];            // x^k
   __shared__ double s_cf[CPB][8];             // coef
   // the coefficient tables of the first NBL bins (the usual case has one to three) in LDS: every pass of the block reads them again, 42 loads per lane and bin,
   // and from global memory those loads -- not the arithmetic -- were what a pass took
@@ -154,16 +166,23 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
   const int64_t ngroups = (N + CPB - 1) / CPB;
   const int cc = c < C ? c : C - 1;
   // what the epilogue reads for this lane's (cell, clone) that nothing here produces: loaded a pass AHEAD, beside the arithmetic of the current one
-  auto load_pass = [&](int64_t grp, double& x_, ca_cell_pre& pre_) {
+  using pre_t = typename std::conditional<LEAN, ca_cell_pre_lean, ca_cell_pre>::type;
+  // (LEAN: x travels as the float it is and widens at the top of its own pass -- widened beside its load, the prefetch was waited for where it was issued)
+  using x_t = typename std::conditional<LEAN, float, double>::type;
+  auto load_pass = [&](int64_t grp, x_t& x_, pre_t& pre_) {
     const int64_t n_ = grp * CPB + slot, nn_ = n_ < N ? n_ : N - 1;
-    x_ = (double)p.F[nn_];
+    x_ = (x_t)p.F[nn_];
     pre_.gl = p.glogit[nn_ * C + cc]; pre_.sn = p.s64[nn_]; pre_.Anc = p.A[nn_ * C + cc];
+    if constexpr (LEAN) pre_.cn = p.cn[nn_];
   };
-  double x_next = 0.0; ca_cell_pre pre_next = {0.f, 0.0, 0.0};
+  x_t x_next = 0; pre_t pre_next = {};
   if ((int64_t)blockIdx.x < ngroups) load_pass(blockIdx.x, x_next, pre_next);
-  for (int64_t grp = blockIdx.x; grp < ngroups; grp += ncb) {
+  [[maybe_unused]] int pass = 0;   // (the timing lab's stamps)
+  for (int64_t grp = blockIdx.x; grp < ngroups; grp += ncb, ++pass) {
+    CA_LAB_CELL_PH(blockIdx.x, pass, 0);
     const int64_t n = grp * CPB + slot;
-    const double x = x_next; const ca_cell_pre pre = pre_next;
+    const double x = (double)x_next; pre_t pre = pre_next;
+    if constexpr (LEAN) pre.x = x;
     if (grp + ncb < ngroups) load_pass(grp + ncb, x_next, pre_next);
     double ZA = 0.0, ZB = 0.0, dZB = 0.0;
     for (int b = 0; b < nb; ++b) {
@@ -184,20 +203,35 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
       ZA += e * pa; ZB += e * pb; dZB += e * (vb * pb + dpb);
       if (c == 0) s_eb[slot][b] = e;
     }
-    {   // x^k, the lanes of a cell sharing the stores
+    CA_LAB_CELL_PH_AFTER(dZB, blockIdx.x, pass, 1);
+    if constexpr (LEAN) {   // x^k: every lane runs the chain, keeps its own k = c, c + CP, ... by selects and stores them without a condition
+      double xk = 1.0, keep[NXK];
+#pragma unroll
+      for (int j = 0; j < NXK; ++j) keep[j] = 0.0;
+#pragma unroll
+      for (int k = 0; k < RQ; ++k) { keep[k / CP] = (k % CP == c) ? xk : keep[k / CP]; xk *= x; }
+#pragma unroll
+      for (int j = 0; j < NXK; ++j) s_xp[slot][j * CP + c] = keep[j];
+    } else {   // x^k, the lanes of a cell sharing the stores
       double xk = 1.0;
       for (int k = 0; k < RQ; ++k) { if (k % CP == c) s_xp[slot][k] = xk; xk *= x; }
     }
+    CA_LAB_CELL_PH(blockIdx.x, pass, 2);
     float cff = 0.f;
-    ca_cell_fused_group<CP>(p, la, n, N, C, 1, K, ZA, ZB, acc, &pre, &cff);
+    ca_cell_fused_group<CP, true, LEAN>(p, la, n, N, C, 1, K, ZA, ZB, acc, &pre, &cff);
     // this lane's coef as the epilogue stored it (float: what the matrix-core way back reads as well); d/dF = sum_c coef dZ/dx
     const double cf = (double)cff;
     double df = cf * dZB;
+    if constexpr (LEAN) df = ca_dpp_gsum<CP>(df);
+    else {
 #pragma unroll
     for (int o = CP / 2; o > 0; o >>= 1) df += __shfl_xor(df, o, CP);
+    }
     if (c == 0 && n < N) dF[n] = (float)df;
     if (c < 8) s_cf[slot][c] = cf;
+    CA_LAB_CELL_PH_AFTER(df, blockIdx.x, pass, 3);
     __syncthreads();
+    CA_LAB_CELL_PH(blockIdx.x, pass, 4);
     if (qown) {
       // (loads batched eight cells at a time: a load per step waited for the one before, and that chain WAS this kernel; bins past nb hold zeros)
       if (nb == 1) {
@@ -216,7 +250,9 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
         mine[(b * RQ + qk) * C + qc] = a;
       }
     }
+    CA_LAB_CELL_PH_AFTER(qa[0], blockIdx.x, pass, 5);
     __syncthreads();
+    CA_LAB_CELL_PH(blockIdx.x, pass, 6);
   }
   ca_cell_fused_finish<CP>(acc, sm, cell_part, blockIdx.x, C);
   if (qown) {
@@ -371,7 +407,7 @@ hipError_t ca_poly_moments(hipStream_t st, const ca_poly_ws* w, const float* V, 
 }
 
 hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, int K, const void* cell_ptrs, const float* alpha_u, double* cell_part, float* dF,
-                         const void* yfin_args, const void* local_tail, const float* xs_part, int xs_n, const float* xs_F, double* xs_slots, int rank, int world) {
+                         const void* yfin_args, const void* local_tail, const float* xs_part, int xs_n, const float* xs_F, double* xs_slots, int rank, int world, bool lean) {
   const ca_cell_ptrs& p = *static_cast<const ca_cell_ptrs*>(cell_ptrs);
   ca_yfin_args yfin;
   if (yfin_args) memcpy(&yfin, yfin_args, sizeof(yfin)); else memset(&yfin, 0, sizeof(yfin));
@@ -379,9 +415,14 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
   while (CP < C) CP <<= 1;
   const int nextra = yfin_args ? cdiv_i(yfin.ncol, CA_TB / 64) + yfin.nrow : 0;
   const dim3 grid(w->n_cell_blocks + nextra);
-#define CA_PCELL(CPV) hipLaunchKernelGGL((k_poly_cell<CPV>), grid, dim3(CA_TB), 0, st, w->hdr, w->tabB, p, alpha_u, cell_part, N, C, K, dF, w->Qpart, \
+#define CA_PCELL(CPV, LV) hipLaunchKernelGGL((k_poly_cell<CPV, LV>), grid, dim3(CA_TB), 0, st, w->hdr, w->tabB, p, alpha_u, cell_part, N, C, K, dF, w->Qpart, \
                                          w->n_cell_blocks, yfin)
-  if (CP == 4) CA_PCELL(4); else CA_PCELL(8);   // (3 .. 8 clones: ca_poly_ok)
+  if (lean) {   // (3 .. 8 clones: ca_poly_ok)
+    if (K > 1) return hipErrorInvalidValue;   // (the lean epilogue takes psi of the prior term from x: one latent dimension, which is all ca_poly_ok admits)
+    if (CP == 4) CA_PCELL(4, true); else CA_PCELL(8, true);
+  } else {
+    if (CP == 4) CA_PCELL(4, false); else CA_PCELL(8, false);
+  }
 #undef CA_PCELL
   {
     ca_small_args tail;
@@ -402,3 +443,9 @@ hipError_t ca_poly_backward(hipStream_t st, const ca_poly_ws* w, const float* V,
   hipLaunchKernelGGL(k_poly_gene, dim3(ngblk + (tail.enabled ? 1 : 0)), dim3(CA_TB), 0, st, w->hdr, w->tabQ, V, mu, Lb, G, C, red_g, tail, ngblk);
   return hipGetLastError();
 }
+
+#ifdef CA_LAB   // timing-lab builds only: reader of the cell passes' phase stamps (tools/lab/ca_lab_hooks.inc, tools/cell_stamps.py)
+extern "C" int ca_lab_read_cell_stamps(unsigned long long* out, int n_words) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(ca_series::ca_lab_stamps4), (size_t)n_words * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
+}
+#endif

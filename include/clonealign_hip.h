@@ -126,6 +126,10 @@ enum ca_variant {
   CA_VAR_MOM_RIDE = 1 << 23,  /* the series form's forward moments (bin geometry, per-group partials, their fixed-order sums) as the first blocks of its count-matrix
                                  stream's launch instead of two launches in front of it: two launches and their boundaries less per iteration, the same additions
                                  in the same order; on wherever the series form runs its stream in line.  Off: k_poly_B + k_poly_red, then the stream */
+  CA_VAR_CELL_LEAN = 1 << 24, /* the series form's cell launch with nothing on a pass's chain of latencies that the result does not need: no global load inside a pass
+                                 but the prefetch of the next one (no read of the zero exponent bound; c_n and psi come with the prefetch), the 4- and 8-lane reductions
+                                 through DPP moves instead of the LDS crossbar, the powers of x without a branch per step; the same additions in the same order; on
+                                 wherever the series form runs.  Off: the launch as it was (k_poly_cell<CP, false>) */
   CA_VAR_RIDE_SEQ = 1 << 13   /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
 /* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
@@ -219,6 +223,7 @@ typedef struct ca_info {
   int64_t series_passes;     /* fused passes of this engine that ran in the series form ... */
   int64_t series_fallbacks;  /* ... and those the look ahead at the exponent range (max|psi| (max W - min W), plus what the Adam steps since can add) gave to the sweeps */
   int32_t mom_ride;          /* 1: the series form's forward moments ride on its count-matrix stream's launch (CA_VAR_MOM_RIDE) */
+  int32_t cell_lean;         /* 1: the series form's cell launch runs its lean passes (CA_VAR_CELL_LEAN) */
 } ca_info;
 enum ca_transport { CA_TRANSPORT_NONE = 0, CA_TRANSPORT_RCCL = 1, CA_TRANSPORT_HOST = 2, CA_TRANSPORT_P2P = 3 };
 
