@@ -364,6 +364,209 @@ def assign_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=N
                          clone_names=names, ml_params={"clone_probs": probs})
 
 
+def _pair_list(C):
+    """The unordered clone pairs ``a < b`` in lexicographic order, [M, 2]."""
+    return np.array([(a, b) for a in range(C) for b in range(a + 1, C)], dtype=np.int64).reshape(-1, 2)
+
+
+def _pair_weights(weights, what="clone_pair_loglik", limit=8):
+    """The mixture weights of a pair call: 1 to 8 finite values in the open interval (0, 1) (ValueError names the offender otherwise)."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if not 1 <= w.shape[0] <= limit:
+        raise ValueError(f"{what}: n_weights = {w.shape[0]} is outside [1, 8]")
+    for i, v in enumerate(w):
+        if not (np.isfinite(v) and 0.0 < v < 1.0):
+            raise ValueError(f"{what}: weight {i} is {v}: not inside the open interval (0, 1)")
+    return w
+
+
+def _pair_weight_grid(weights, what="clone_pair_loglik"):
+    """``weights`` closed under ``w -> 1 - w`` and sorted (values closer than 1e-12 are one; at most 8 after that): the pairs are unordered, so an
+    asymmetric grid would favour one parent."""
+    w = _pair_weights(weights, what, limit=1 << 30)
+    both = np.sort(np.concatenate([w, 1.0 - w]))
+    return _pair_weights(both[np.concatenate([[True], np.diff(both) > 1e-12])], what)
+
+
+def _clone_pair_loglik_host(Y, E, U=None, V=None, weights=(0.5,), const=True, chunk=512):
+    """Float64 host form of ``HipEngine.clone_pair_loglik`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time), E
+    [G, C], U [N, D] and V [G, D] or both None, ``weights`` as given.  Same return value (``{"ll", "pair_ll" [N, M, W], "pairs" [M, 2]}``), same rules
+    (the per-pair shift by ``min(log Z_a, log Z_b)``, zero counts skipped, ``-inf`` exactly where both clones have ``E = 0`` against a positive count, no
+    NaN), same refusals (ValueError)."""
+    from scipy.special import gammaln
+    w = _pair_weights(weights)
+    ll = _clone_loglik_host(Y, E, U, V, const=const, chunk=max(int(chunk), 1))      # (and its refusals on E, U and V)
+    E = np.asarray(E, dtype=np.float64)
+    N, G = Y.shape
+    C = E.shape[1]
+    if C < 2:
+        raise ValueError(f"clone_pair_loglik: C = {C} clones: a pair needs at least 2")
+    D = 0 if U is None else np.asarray(U).shape[1]
+    if D > 0:
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    pairs = _pair_list(C)
+    M, W = pairs.shape[0], w.shape[0]
+    pll = np.empty((N, M, W))
+    logz0 = np.log(E.sum(0))
+    for lo in range(0, N, int(chunk)):
+        Yc = Y[lo:lo + int(chunk)]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+        n = Yc.shape[0]
+        pos = Yc > 0
+        s = Yc.sum(1)
+        base = np.zeros(n)
+        if D > 0:
+            eta = U[lo:lo + int(chunk)] @ V.T
+            m = eta.max(1)
+            logz = m[:, None] + np.log(np.exp(eta - m[:, None]) @ E)
+            base += (Yc * eta).sum(1)
+        else:
+            logz = np.broadcast_to(logz0[None, :], (n, C))
+        if const:
+            base += gammaln(s + 1.0) - gammaln(Yc + 1.0).sum(1)
+        for p, (a, b) in enumerate(pairs):
+            lz = np.minimum(logz[:, a], logz[:, b])
+            ca, cb = np.exp(lz - logz[:, a]), np.exp(lz - logz[:, b])
+            for k, wk in enumerate(w):
+                br = (wk * ca)[:, None] * E[None, :, a] + ((1.0 - wk) * cb)[:, None] * E[None, :, b]
+                with np.errstate(divide="ignore"):
+                    lb = np.log(br, where=pos, out=np.zeros_like(br))          # zero counts are skipped: 0 * log 0 is never formed
+                    t = (Yc * lb).sum(1)
+                pll[lo:lo + n, p, k] = t + base - np.where(s > 0, s * lz, 0.0)
+    return {"ll": ll, "pair_ll": pll, "pairs": pairs}
+
+
+def _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, engine, engine_opts, what):
+    """(Y, E, U, V, weight grid, clone names, engine, whether it is ours) of a pair call: ``clone_loglik``'s arguments through ``_fit_tables``."""
+    L, cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if L.shape[0] != G:
+        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    if L.shape[1] < 2:
+        raise ValueError(f"{what}: C = {L.shape[1]} clones: a pair needs at least 2")
+    grid = _pair_weight_grid(weights, what)
+    L, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
+    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(L.shape[1])])
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    elif hasattr(engine, "clone_pair_loglik") and (engine.N, engine.G) != (N, G):
+        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+    return Y, E, U, V, grid, names, engine, own
+
+
+def _pair_call(engine, Y, E, U, V, grid, const, lo, hi):
+    """Cells [lo, hi) through the engine's ``clone_pair_loglik``, or through the host form when it has none."""
+    if hasattr(engine, "clone_pair_loglik"):
+        return engine.clone_pair_loglik(E, U, V, weights=grid, const=const, cells=(lo, hi))
+    return _clone_pair_loglik_host(Y[lo:hi], E, None if U is None else U[lo:hi], V, weights=grid, const=const)
+
+
+def clone_pair_loglik(fit, Y, L, *, weights=(0.3, 0.5, 0.7), x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
+    """Log-likelihood of the cells of ``Y`` under every MIXTURE of two clones of a fitted model -- a heterotypic doublet: two cells of clones ``a < b`` in one
+    droplet, whose summed counts are multinomial in ``w p_a + (1 - w) p_b`` -- at the fit's point estimates, for every weight of a grid
+    (``HipEngine.clone_pair_loglik``; include/clonealign_hip.h has the formula and the rules).  ``Y``, ``L``, ``x``, ``psi``, ``saturate``, ``const``,
+    ``engine`` and ``engine_opts`` as for ``clone_loglik``.  ``weights``: 1 to 8 values in (0, 1) after being closed under ``w -> 1 - w`` and sorted (the
+    pairs are unordered, so an asymmetric grid would favour one parent); ``w`` is the share of the pair's first clone.
+
+    Returns ``{"ll" [cells, clones] (clone_loglik's), "pair_ll" [cells, M, W], "pairs" [M, 2] (lexicographic), "weights" [W] (the grid used)}``.  An engine
+    without ``clone_pair_loglik`` gets the chunked float64 host form."""
+    Y, E, U, V, grid, _names, engine, own = _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, engine, engine_opts, "clone_pair_loglik")
+    try:
+        out = _pair_call(engine, Y, E, U, V, grid, const, 0, Y.shape[0])
+    finally:
+        if own:
+            engine.close()
+    out["weights"] = grid
+    return out
+
+
+def detect_doublets(fit, Y, L, doublet_rate=0.05, doublet_probability=0.5, clone_assignment_probability=0.95, *, weights=(0.3, 0.5, 0.7), extra_loglik=None,
+                    x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None, chunk_cells=None):
+    """Heterotypic doublets under a fitted model, without refitting: the exact posterior of every cell of ``Y`` over the hypotheses {singlet of clone c} and
+    {doublet of the clone pair (a, b)}, from ``clone_pair_loglik`` (same keywords).  Priors, with ``rho = doublet_rate``, ``alpha`` the fit's clone
+    prevalences (uniform when it has none) and ``het = 1 - sum_c alpha_c^2``: singlet ``c``: ``(1 - rho) alpha_c``; pair ``(a, b)``:
+    ``rho 2 alpha_a alpha_b / het`` (a homotypic doublet is indistinguishable from a singlet and counts as one); the weights of the grid: uniform.
+    ``extra_loglik`` [cells, clones] is added to the singlets; a pair gets ``logaddexp(extra_a, extra_b) - log 2``.  The cells are walked in ranges of
+    ``chunk_cells`` (default: so that a range's ``pair_ll`` block stays under 256 MB on the host).
+
+    Returns a :class:`ClonealignFit` with ``p_doublet`` [cells], ``pair_probs`` [cells, M], ``doublet_pair`` (``"A+B"`` for the cells labelled
+    ``"doublet"``, else None), ``doublet_weight`` (the posterior mean of ``w`` under the most probable pair: the share of its first-named clone),
+    ``clone_probs`` [cells, clones] (renormalised over the singlets: ``assign_cells``'s, so ``recompute_clone_assignment`` works), ``clone``
+    (``"doublet"`` where ``p_doublet >= doublet_probability``, else ``assign_cells``'s label), ``loglik`` [cells] (the marginal over all hypotheses),
+    ``log_bayes_factor`` [cells] (doublet against singlet, ``rho`` left out), ``clone_loglik``, ``clone_names``, ``pairs`` and ``weights``.  A cell that
+    is ``-inf`` under every hypothesis gets NaN probabilities and ``"unassigned"``; no other cell sees a NaN."""
+    rho = float(doublet_rate)
+    if not (np.isfinite(rho) and 0.0 <= rho <= 1.0):
+        raise ValueError(f"detect_doublets: doublet_rate = {doublet_rate} is outside [0, 1]")
+    Y, E, U, V, grid, names, engine, own = _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, engine, engine_opts, "detect_doublets")
+    N, C = Y.shape[0], E.shape[1]
+    pairs = _pair_list(C)
+    M, W = pairs.shape[0], grid.shape[0]
+    alpha = fit["ml_params"].get("alpha")
+    alpha = np.full(C, 1.0 / C) if alpha is None else np.asarray(alpha, dtype=np.float64).reshape(C)
+    ex = None
+    if extra_loglik is not None:
+        ex = np.asarray(extra_loglik, dtype=np.float64)
+        if ex.shape != (N, C):
+            if own:
+                engine.close()
+            raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
+    step = int(chunk_cells) if chunk_cells else max(1, (1 << 28) // (8 * M * W))
+    ll = np.empty((N, C))
+    pair_log = np.empty((N, M))                                      # log p(y | pair), the weights marginalised (uniform on the grid)
+    w_mean = np.empty((N, M))
+    try:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for lo in range(0, N, step):
+                hi = min(N, lo + step)
+                r = _pair_call(engine, Y, E, U, V, grid, const, lo, hi)
+                ll[lo:hi] = r["ll"]
+                pl = r["pair_ll"]
+                m = pl.max(2, keepdims=True)
+                e = np.exp(pl - np.where(np.isneginf(m), 0.0, m))    # (a pair at -inf for every weight: all zeros, no NaN)
+                tot = e.sum(2)
+                pair_log[lo:hi] = np.where(np.isneginf(m[:, :, 0]), -np.inf, m[:, :, 0] + np.log(tot)) - np.log(W)
+                w_mean[lo:hi] = (e * grid[None, None, :]).sum(2) / tot
+    finally:
+        if own:
+            engine.close()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        het = 1.0 - (alpha ** 2).sum()
+        t_s = ll + np.log(alpha)[None, :]                            # singlets, rho left out
+        t_p = pair_log + (np.log(2.0 * alpha[pairs[:, 0]] * alpha[pairs[:, 1]]) - np.log(het) if het > 0 else np.full(M, -np.inf))[None, :]
+        if ex is not None:
+            t_s = t_s + ex
+            t_p = t_p + np.logaddexp(ex[:, pairs[:, 0]], ex[:, pairs[:, 1]]) - np.log(2.0)
+
+        def lse(t):
+            m = t.max(1)
+            return np.where(np.isneginf(m), -np.inf, m + np.log(np.exp(t - np.where(np.isneginf(m), 0.0, m)[:, None]).sum(1)))
+        ls, lp = lse(t_s), lse(t_p)
+        a_s, a_p = np.log1p(-rho) + ls, np.log(rho) + lp
+        loglik = np.where(np.isneginf(a_s) & np.isneginf(a_p), -np.inf, np.logaddexp(a_s, a_p))
+        dead = np.isneginf(loglik)
+        clone_probs = np.exp(t_s - ls[:, None])                      # (a row of -inf: NaN - no clone is possible)
+        pair_probs = np.exp(np.log(rho) + t_p - loglik[:, None])
+        pair_probs[dead] = np.nan
+        p_doublet = np.where(dead, np.nan, np.exp(a_p - loglik))
+        lbf = np.where(np.isneginf(ls) & np.isneginf(lp), np.nan, lp - ls)
+    clone = clone_assignment(clone_probs, names, clone_assignment_probability)
+    clone[dead] = "unassigned"
+    is_d = p_doublet >= doublet_probability                          # (NaN: False)
+    clone[is_d] = "doublet"
+    best = np.where(np.isneginf(lp), 0, np.argmax(np.where(np.isnan(t_p), -np.inf, t_p), axis=1))
+    pair_names = np.asarray([f"{names[a]}+{names[b]}" for a, b in pairs], dtype=object)
+    doublet_pair = np.full(N, None, dtype=object)
+    doublet_pair[is_d] = pair_names[best[is_d]]
+    doublet_weight = np.where(np.isneginf(lp), np.nan, w_mean[np.arange(N), best])
+    return ClonealignFit(clone_probs=clone_probs, clone=clone, p_doublet=p_doublet, pair_probs=pair_probs, doublet_pair=doublet_pair,
+                         doublet_weight=doublet_weight, loglik=loglik, log_bayes_factor=lbf, clone_loglik=ll, clone_names=names, pairs=pairs,
+                         weights=grid, ml_params={"clone_probs": clone_probs})
+
+
 def _project_cells_host(Y, E, V, K, P, X, log_prior, psi_start, const=True, max_iter=25, tol=1e-9, max_step=1.0, chunk=2048):
     """Float64 numpy restatement of ``HipEngine.project_cells`` (ca_project_cells; the algorithm is stated in include/clonealign_hip.h), step for step,
     ``chunk`` cells at a time: Y [N, G] dense or scipy.sparse, E [G, C], V = [W | beta] [G, K + P] or None, X [N, P] or None, log_prior [N, C] or None,

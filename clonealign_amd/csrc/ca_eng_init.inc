@@ -450,19 +450,40 @@ std::string ll_sweep_table(ca_engine* h, const double* E, const double* V, int D
 // formula and the rules).  Like ca_fit_mse it reads the matrix, the row sums and the overflow list only: no wait for the loop's side stream, no variable, Adam
 // slot or draw index changes.  U and ll cover the local cells, so a sharded handle needs no sums from its peers; it still takes part in ONE small collective,
 // the verdict on the input (a non-finite U is local), so that every rank returns the same code instead of one of them leaving the others waiting.
-int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, double* ll) {
-  if (!h || !E || !ll) return CA_ERR_INVALID;
-  CA_NOT_IN_RUN(h);
-  if (D < 0 || D > CA_LL_DMAX) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
-  if (D > 0 && (!U || !V)) { h->err = "ca_clone_loglik: D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
-  HIPCK(h, hipSetDevice(h->device));
+// ONE body serves ca_clone_loglik and ca_clone_pair_loglik: the pair call runs the same launches over its cell range -- its ll is ca_clone_loglik's bit for bit,
+// and the pair-independent pieces (sum y eta, the lgamma sum, log Z) are those launches' -- and then, per batch, k_pair_cell and k_pair_ll (D > 0) or the
+// table sweep of k_clone_ll with k_pair_tab_finish (D = 0).
+extern "C++" {
+namespace {
+struct ca_pair_req { const double* weights; int W; double* pair_ll; };   // the pair part of a call: W weights in (0, 1), the output cell_cnt x (M W)
+int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, int64_t c_lo, int64_t c_cnt, double* ll,
+                  const ca_pair_req* pq) {
+  const std::string pre = std::string(who) + ": ";
+  if (D < 0 || D > CA_LL_DMAX) { h->err = pre + "D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
+  if (D > 0 && (!U || !V)) { h->err = pre + "D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
   const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg;
+  const int W = pq ? pq->W : 0;
+  if (pq) {   // (the same on every rank as well)
+    if (C < 2) { h->err = pre + "C = " + std::to_string(C) + " clones: a pair needs at least 2"; return CA_ERR_INVALID; }
+    if (W < 1 || W > CA_PLL_WMAX) { h->err = pre + "n_weights = " + std::to_string(W) + " is outside [1, " + std::to_string(CA_PLL_WMAX) + "]"; return CA_ERR_INVALID; }
+    if (!pq->weights) { h->err = pre + "weights is NULL"; return CA_ERR_INVALID; }
+    for (int i = 0; i < W; ++i)
+      if (!std::isfinite(pq->weights[i]) || !(pq->weights[i] > 0.0 && pq->weights[i] < 1.0)) {
+        h->err = pre + "weight " + std::to_string(i) + " is " + std::to_string(pq->weights[i]) + ": not inside the open interval (0, 1)";
+        return CA_ERR_INVALID;
+      }
+  }
+  HIPCK(h, hipSetDevice(h->device));
+  const int MP = C * (C - 1) / 2, MW = MP * W;
   // the sweep's table: per gene the columns [log E of the clones | V], in groups of NC columns, zero padded; where E = 0 the entry is 0 and the gene's mask has the bit
   const int ncol = C + D;
   const int NC = ncol <= 8 ? 8 : ncol <= 16 ? 16 : 32, ngrp = cdiv(ncol, NC), nct = ngrp * NC;
   std::vector<double> tab, logz0;
   std::vector<unsigned> zmask;
-  std::string bad = ll_sweep_table(h, E, V, D, NC, ngrp, tab, zmask, logz0);
+  std::string bad;
+  if (c_lo < 0 || c_cnt < 0 || c_lo > N || c_cnt > N - c_lo)
+    bad = "the cell range [" + std::to_string(c_lo) + ", " + std::to_string(c_lo) + " + " + std::to_string(c_cnt) + ") is outside [0, " + std::to_string(N) + "]";
+  if (bad.empty()) bad = ll_sweep_table(h, E, V, D, NC, ngrp, tab, zmask, logz0);
   // the contraction's operands (D > 0): U and V padded to CA_LL_DMAX factors, E in groups of NZ clone columns
   const int NZ = C <= 8 ? 8 : C <= 16 ? 16 : 32, ngz = cdiv(C, NZ), nzt = ngz * NZ, nzc = cdiv(G, CA_LL_ZCHUNK);
   std::vector<double> Ut, Vt, Ez;
@@ -479,6 +500,34 @@ int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double*
       for (int c = 0; c < C; ++c) Ez[((size_t)(c / NZ) * Gp + g) * NZ + c % NZ] = E[hidx(h->layout, g, c, G, C)];
     }
   }
+  // the pair part's operands: E compact [G][C] for k_pair_ll (D > 0); for D = 0 the table log(A P_ga + B P_gb) of M W columns in groups of NP, its both-zero masks
+  // and the slots' shifts lz = min(log Z_a, log Z_b)
+  const int NP = MW <= 8 ? 8 : MW <= 16 ? 16 : 32, ngp = pq ? cdiv(MW, NP) : 0, nctp = ngp * NP;
+  std::vector<double> Ec, wts, ptab, slot_lz;
+  std::vector<unsigned> pzm;
+  if (pq && bad.empty()) {
+    wts.assign(pq->weights, pq->weights + W);
+    Ec.resize((size_t)G * C);
+    for (int g = 0; g < G; ++g)
+      for (int c = 0; c < C; ++c) Ec[(size_t)g * C + c] = E[hidx(h->layout, g, c, G, C)];
+    if (D == 0) {
+      ptab.assign((size_t)ngp * Gp * NP, 0.0); pzm.assign((size_t)ngp * Gp, 0u); slot_lz.assign((size_t)MW, 0.0);
+      int j = 0;
+      for (int a = 0; a < C; ++a)
+        for (int b = a + 1; b < C; ++b)
+          for (int wi = 0; wi < W; ++wi, ++j) {
+            const double lz = std::min(logz0[(size_t)a], logz0[(size_t)b]), w = wts[(size_t)wi];
+            const double A = w * std::exp(lz - logz0[(size_t)a]), B = (1.0 - w) * std::exp(lz - logz0[(size_t)b]);
+            slot_lz[(size_t)j] = lz;
+            const int grp = j / NP, jc = j % NP;
+            for (int g = 0; g < G; ++g) {
+              const double v = std::fma(A, Ec[(size_t)g * C + a], B * Ec[(size_t)g * C + b]);
+              if (v > 0.0) ptab[((size_t)grp * Gp + g) * NP + jc] = std::log(v);
+              else pzm[(size_t)grp * Gp + g] |= 1u << jc;
+            }
+          }
+    }
+  }
   if (is_sharded(h)) {   // [ranks whose input was refused]
     std::vector<double> pack{bad.empty() ? 0.0 : 1.0};
     double* scratch = nullptr;
@@ -488,17 +537,22 @@ int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double*
     if (rc != CA_OK) return rc;
     if (pack[0] != 0.0 && bad.empty()) bad = "another rank refused its input";
   }
-  if (!bad.empty()) { h->err = "ca_clone_loglik: " + bad; return CA_ERR_INVALID; }
-  if (N == 0) return CA_OK;
+  if (!bad.empty()) { h->err = pre + bad; return CA_ERR_INVALID; }
+  if (c_cnt == 0) return CA_OK;
   std::vector<double> lgt;
   if (with_const) { lgt.resize(CA_LL_LGTAB); for (int k = 0; k < CA_LL_LGTAB; ++k) lgt[(size_t)k] = std::lgamma((double)k + 1.0); }
   // cells in batches, so that the partial slabs stay below a quarter of a gigabyte (a cell's sums do not depend on its batch)
-  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (D > 0 ? (int64_t)nzc * (nzt + 1) : 0)) * (int64_t)sizeof(double);
-  const int64_t NB = std::min<int64_t>(N, std::max<int64_t>(CA_TB, (((int64_t)1 << 28) / per_cell) / CA_TB * CA_TB));
-  std::vector<double> out((size_t)N * C);
+  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (D > 0 ? (int64_t)nzc * (nzt + 1) : 0) + (pq ? (int64_t)C + 1 + MW + (D == 0 ? (int64_t)nseg * nctp : 0) : 0)) * (int64_t)sizeof(double);
+  const int64_t NB = std::min<int64_t>(c_cnt, std::max<int64_t>(CA_TB, (((int64_t)1 << 28) / per_cell) / CA_TB * CA_TB));
+  std::vector<double> out(ll ? (size_t)c_cnt * C : 0), pout(pq && h->layout == CA_COL_MAJOR ? (size_t)c_cnt * MW : 0);
+  double* const phost = pq ? (h->layout == CA_COL_MAJOR ? pout.data() : pq->pair_ll) : nullptr;   // row-major [c_cnt][MW]
   double *tab_d = nullptr, *lgt_d = nullptr, *logz_d = nullptr, *Ut_d = nullptr, *Vt_d = nullptr, *Ez_d = nullptr, *part = nullptr, *lgpart = nullptr, *zpart = nullptr, *mpart = nullptr, *ll_d = nullptr;
-  unsigned* zm_d = nullptr;
-  auto cleanup = [&]() { hipFree(tab_d); hipFree(lgt_d); hipFree(logz_d); hipFree(Ut_d); hipFree(Vt_d); hipFree(Ez_d); hipFree(part); hipFree(lgpart); hipFree(zpart); hipFree(mpart); hipFree(ll_d); hipFree(zm_d); };
+  double *Ec_d = nullptr, *wts_d = nullptr, *ptab_d = nullptr, *slz_d = nullptr, *lzc_d = nullptr, *base_d = nullptr, *ppart = nullptr, *pll_d = nullptr;
+  unsigned *zm_d = nullptr, *pzm_d = nullptr;
+  auto cleanup = [&]() {
+    hipFree(tab_d); hipFree(lgt_d); hipFree(logz_d); hipFree(Ut_d); hipFree(Vt_d); hipFree(Ez_d); hipFree(part); hipFree(lgpart); hipFree(zpart); hipFree(mpart); hipFree(ll_d); hipFree(zm_d);
+    hipFree(Ec_d); hipFree(wts_d); hipFree(ptab_d); hipFree(slz_d); hipFree(lzc_d); hipFree(base_d); hipFree(ppart); hipFree(pll_d); hipFree(pzm_d);
+  };
 #define PCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return CA_ERR_HIP; } } while (0)
 #define UP(dst, vec) do { PCK(hipMalloc((void**)&dst, (vec).size() * sizeof((vec)[0]))); PCK(hipMemcpyAsync(dst, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, h->stream)); } while (0)
   UP(tab_d, tab); UP(zm_d, zmask); UP(logz_d, logz0);
@@ -511,8 +565,16 @@ int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double*
     PCK(hipMalloc((void**)&mpart, (size_t)nzc * NB * sizeof(double)));
   }
   PCK(hipMalloc((void**)&ll_d, (size_t)N * C * sizeof(double)));
-  for (int64_t n_lo = 0; n_lo < N; n_lo += NB) {
-    const int64_t n_cnt = std::min<int64_t>(NB, N - n_lo);
+  if (pq) {
+    UP(wts_d, wts);
+    if (D > 0) UP(Ec_d, Ec);
+    else { UP(ptab_d, ptab); UP(pzm_d, pzm); UP(slz_d, slot_lz); PCK(hipMalloc((void**)&ppart, (size_t)nseg * NB * nctp * sizeof(double))); }
+    PCK(hipMalloc((void**)&lzc_d, (size_t)NB * C * sizeof(double)));
+    PCK(hipMalloc((void**)&base_d, (size_t)NB * sizeof(double)));
+    PCK(hipMalloc((void**)&pll_d, (size_t)NB * MW * sizeof(double)));
+  }
+  for (int64_t n_lo = c_lo; n_lo < c_lo + c_cnt; n_lo += NB) {
+    const int64_t n_cnt = std::min<int64_t>(NB, c_lo + c_cnt - n_lo);
     ca_ll_ops o;
     o.tab = tab_d; o.zmask = zm_d; o.lgtab = lgt_d; o.part = part; o.lgpart = lgpart; o.n_lo = n_lo; o.n_cnt = n_cnt; o.NC = NC; o.ngrp = ngrp;
     { const int rc = launch_clone_ll(h, o); if (rc != CA_OK) { cleanup(); return rc; } }
@@ -521,18 +583,60 @@ int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double*
       z.Ut = Ut_d; z.Vt = Vt_d; z.Ez = Ez_d; z.zpart = zpart; z.mpart = mpart; z.n_lo = n_lo; z.n_cnt = n_cnt; z.NC = NZ; z.ngrp = ngz; z.nzc = nzc;
       { const int rc = launch_clone_ll_z(h, z); if (rc != CA_OK) { cleanup(); return rc; } }
     }
-    hipLaunchKernelGGL(k_clone_ll_finish, dim3((unsigned)cdiv(n_cnt * C, CA_TB)), dim3(CA_TB), 0, h->stream, part, lgpart, zpart, mpart, logz_d, Ut_d, h->s64, ll_d, n_lo, n_cnt, C,
-                       (int)D, (int)nseg, nct, nzc, nzt);
-    PCK(hipGetLastError());
+    if (ll) {
+      hipLaunchKernelGGL(k_clone_ll_finish, dim3((unsigned)cdiv(n_cnt * C, CA_TB)), dim3(CA_TB), 0, h->stream, part, lgpart, zpart, mpart, logz_d, Ut_d, h->s64, ll_d, n_lo, n_cnt, C,
+                         (int)D, (int)nseg, nct, nzc, nzt);
+      PCK(hipGetLastError());
+    }
+    if (pq) {
+      hipLaunchKernelGGL(k_pair_cell, dim3((unsigned)cdiv(n_cnt * (C + 1), CA_TB)), dim3(CA_TB), 0, h->stream, part, lgpart, zpart, mpart, logz_d, Ut_d, h->s64, lzc_d, base_d, n_lo, n_cnt,
+                         C, (int)D, (int)nseg, nct, nzc, nzt);
+      PCK(hipGetLastError());
+      if (D > 0) {
+        ca_pll_ops p;
+        p.Ec = Ec_d; p.lzc = lzc_d; p.base = base_d; p.wts = wts_d; p.out = pll_d; p.n_lo = n_lo; p.n_cnt = n_cnt; p.W = W; p.MW = MW;
+        { const int rc = launch_pair_ll(h, p); if (rc != CA_OK) { cleanup(); return rc; } }
+      } else {
+        ca_ll_ops t;   // the table route: no lgamma sum here (base has it)
+        t.tab = ptab_d; t.zmask = pzm_d; t.lgtab = nullptr; t.part = ppart; t.lgpart = nullptr; t.n_lo = n_lo; t.n_cnt = n_cnt; t.NC = NP; t.ngrp = ngp;
+        { const int rc = launch_clone_ll(h, t); if (rc != CA_OK) { cleanup(); return rc; } }
+        hipLaunchKernelGGL(k_pair_tab_finish, dim3((unsigned)cdiv(n_cnt * MW, CA_TB)), dim3(CA_TB), 0, h->stream, ppart, base_d, slz_d, h->s64, pll_d, n_lo, n_cnt, MW, (int)nseg, nctp);
+        PCK(hipGetLastError());
+      }
+      PCK(hipMemcpyAsync(phost + (size_t)(n_lo - c_lo) * MW, pll_d, (size_t)n_cnt * MW * sizeof(double), hipMemcpyDeviceToHost, h->stream));   // (in stream order: before the next batch overwrites it)
+    }
   }
-  PCK(hipMemcpyAsync(out.data(), ll_d, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (ll) PCK(hipMemcpyAsync(out.data(), ll_d + (size_t)c_lo * C, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   PCK(hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
   cleanup();
 #undef UP
 #undef PCK
-  if (h->layout == CA_COL_MAJOR) { for (int64_t n = 0; n < N; ++n) for (int c = 0; c < C; ++c) ll[hidx(h->layout, n, c, N, C)] = out[(size_t)n * C + c]; }
-  else std::copy(out.begin(), out.end(), ll);
+  if (ll) {
+    if (h->layout == CA_COL_MAJOR) { for (int64_t n = 0; n < c_cnt; ++n) for (int c = 0; c < C; ++c) ll[hidx(h->layout, n, c, c_cnt, C)] = out[(size_t)n * C + c]; }
+    else std::copy(out.begin(), out.end(), ll);
+  }
+  if (pq && h->layout == CA_COL_MAJOR)
+    for (int64_t n = 0; n < c_cnt; ++n) for (int j = 0; j < MW; ++j) pq->pair_ll[hidx(h->layout, n, j, c_cnt, MW)] = pout[(size_t)n * MW + j];
   return CA_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ca_clone_loglik(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, double* ll) {
+  if (!h || !E || !ll) return CA_ERR_INVALID;
+  CA_NOT_IN_RUN(h);
+  return clone_ll_impl(h, "ca_clone_loglik", E, U, V, D, with_const, 0, h->N, ll, nullptr);
+}
+
+// The log-likelihood of the resident cells [cell_lo, cell_lo + cell_cnt) under every mixture of two clones and every weight of the grid (a heterotypic doublet;
+// include/clonealign_hip.h has the formula and the rules).  Read-only like ca_clone_loglik, whose launches it shares; the only collective is the verdict on the input.
+int ca_clone_pair_loglik(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const double* weights, int32_t n_weights, int64_t cell_lo,
+                         int64_t cell_cnt, double* ll, double* pair_ll) {
+  if (!h) return CA_ERR_INVALID;
+  if (!E || !pair_ll) { h->err = std::string("ca_clone_pair_loglik: ") + (!E ? "E" : "pair_ll") + " is NULL"; return CA_ERR_INVALID; }
+  CA_NOT_IN_RUN(h);
+  ca_pair_req pq{weights, (int)n_weights, pair_ll};
+  return clone_ll_impl(h, "ca_clone_pair_loglik", E, U, V, D, with_const, cell_lo, cell_cnt, ll, &pq);
 }
 
 // Per-cell MAP psi and the clone posterior at it for the resident cells under a fit's gene-level parameters (include/clonealign_hip.h has the algorithm and the

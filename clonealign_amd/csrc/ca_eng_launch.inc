@@ -315,6 +315,21 @@ int launch_clone_ll_z(ca_engine* h, const ca_llz_ops& o) {
   if (o.NC == 16) return clone_ll_z_t<16>(h, o);
   return clone_ll_z_t<32>(h, o);
 }
+// ---- k_pair_ll<YT>: the pair-mixture sweep over the resident matrix in its storage (ca_clone_pair_loglik with D > 0; never the 4-bit loop image) ----
+// one batch of cells [n_lo, n_lo + n_cnt): E compact [G][C], the cells' log Z and base sums (k_pair_cell), the weights, the batch's rows of the output [n_cnt][MW]
+struct ca_pll_ops { const double *Ec, *lzc, *base, *wts; double* out; int64_t n_lo, n_cnt; int W, MW; };
+template <typename YT>
+int pair_ll_t(ca_engine* h, const ca_pll_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_pair_ll<YT>), dim3((unsigned)cdiv(o.n_cnt, CA_TB / 64), (unsigned)cdiv(o.MW, 64)), dim3(CA_TB), 0, h->stream, (const YT*)h->Y, o.Ec,
+                                                o.lzc, o.base, h->s64, o.wts, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, h->ovf_col, h->ovf_val, o.out, o.n_lo, o.n_cnt, h->G,
+                                                h->Gp, h->nseg, h->C, o.W, o.MW));
+  return CA_OK;
+}
+int launch_pair_ll(ca_engine* h, const ca_pll_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) return pair_ll_t<uint8_t>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return pair_ll_t<uint16_t>(h, o);
+  return pair_ll_t<float>(h, o);
+}
 
 // ---- k_proj_mom<NC, K> / k_proj_step<K>: one round of ca_project_cells on one batch of cells (neither reads the count matrix) ----
 // the moments' operands: U = [psi | x] and V = [W | beta] padded to CA_LL_DMAX factors, E in groups of NC clone columns, the frozen flags, the chunk slabs

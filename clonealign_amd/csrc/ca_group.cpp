@@ -713,6 +713,52 @@ int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U, c
   return CA_OK;
 }
 
+int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const double* weights, int32_t n_weights,
+                               int64_t cell_lo, int64_t cell_cnt, double* ll, double* pair_ll) {
+  GROUP_ALIVE(g);
+  if (!E || !pair_ll) { g->err = std::string("ca_clone_pair_loglik: ") + (!E ? "E" : "pair_ll") + " is NULL"; return CA_ERR_INVALID; }
+  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
+    g->err = "ca_clone_pair_loglik: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
+    return CA_ERR_INVALID;
+  }
+  if (cell_lo < 0 || cell_cnt < 0 || cell_lo > g->N || cell_cnt > g->N - cell_lo) {   // (what decides how the range is cut; the ranks refuse everything else in their own words)
+    g->err = "ca_clone_pair_loglik: the cell range [" + std::to_string(cell_lo) + ", " + std::to_string(cell_lo) + " + " + std::to_string(cell_cnt) + ") is outside [0, " +
+             std::to_string(g->N) + "]";
+    return CA_ERR_INVALID;
+  }
+  const size_t W = (size_t)g->W;
+  const int64_t MW = (int64_t)g->C * (g->C - 1) / 2 * std::max<int64_t>(0, std::min<int64_t>(n_weights, 8));
+  // rank r takes the cells of the range that lie in its shard: [lo[r], hi[r]) in the group's numbering (an empty part is still called: the verdict is collective)
+  std::vector<int64_t> lo(W), hi(W);
+  std::vector<std::vector<double>> us(W), o_ll(W), o_pl(W);
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t slo = g->shard[r].lo, shi = g->shard[r].hi;
+    lo[r] = std::min(std::max(cell_lo, slo), shi);
+    hi[r] = std::max(std::min(cell_lo + cell_cnt, shi), lo[r]);
+    if (D > 0) slice_rows(U, g->layout, g->N, D, slo, shi, us[r]);
+    if (ll) o_ll[r].resize((size_t)((hi[r] - lo[r]) * g->C) + 1);
+    o_pl[r].resize((size_t)((hi[r] - lo[r]) * MW) + 1);
+  }
+  const int s = settle(g, dispatch(g, [&](int ri) {
+    const size_t r = (size_t)ri;
+    return ca_clone_pair_loglik(g->h[r], E, D > 0 ? us[r].data() : nullptr, V, D, with_const, weights, n_weights, lo[r] - g->shard[r].lo, hi[r] - lo[r],
+                                ll ? o_ll[r].data() : nullptr, o_pl[r].data());
+  }), "ca_clone_pair_loglik");
+  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  if (s != CA_OK) return s;
+  for (size_t r = 0; r < W; ++r) {
+    if (ll) scatter_rows(o_ll[r].data(), g->layout, cell_cnt, g->C, lo[r] - cell_lo, hi[r] - cell_lo, ll);
+    scatter_rows(o_pl[r].data(), g->layout, cell_cnt, MW, lo[r] - cell_lo, hi[r] - cell_lo, pair_ll);
+  }
+  return CA_OK;
+}
+
 int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X, const double* log_prior, const double* psi_start,
                            int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi, double* ll, double* clone_probs, double* objective,
                            int32_t* rounds, uint8_t* converged) {

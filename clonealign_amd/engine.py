@@ -49,6 +49,8 @@ EXPORTS = (
     "ca_clone_loglik", "ca_group_clone_loglik",
     # per-cell MAP psi and clone posterior of cells outside the fit (project_cells), additions to ABI 6
     "ca_project_cells", "ca_group_project_cells",
+    # log-likelihood under every mixture of two clones on a weight grid (clone_pair_loglik / detect_doublets), additions to ABI 6
+    "ca_clone_pair_loglik", "ca_group_clone_pair_loglik",
     # count rows drawn from a fitted model (simulate_counts), no handle, additions to ABI 6
     "ca_simulate_counts", "ca_simulate_kernel_ms",
     # log-likelihoods and per-clone gene totals of replicate rows that never leave the device (predictive_stats), no handle, additions to ABI 6
@@ -160,6 +162,8 @@ def load_library(path=None):
     lib.ca_fit_mse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.ca_logexpr_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_clone_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+    lib.ca_clone_pair_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_void_p]
     lib.ca_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_simulate_counts.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
@@ -200,6 +204,7 @@ def load_library(path=None):
     lib.ca_group_logexpr_sums.argtypes = lib.ca_logexpr_sums.argtypes
     lib.ca_group_clone_loglik.argtypes = lib.ca_clone_loglik.argtypes
     lib.ca_group_project_cells.argtypes = lib.ca_project_cells.argtypes
+    lib.ca_group_clone_pair_loglik.argtypes = lib.ca_clone_pair_loglik.argtypes
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -682,6 +687,42 @@ class HipEngine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         self._ck(self._fn("clone_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(ll)))
         return ll
+
+    def clone_pair_loglik(self, E, U=None, V=None, weights=(0.5,), const=True, cells=None, want_ll=True):
+        """Log-likelihood of the resident cells under every MIXTURE of two clones ``a < b`` -- a heterotypic doublet, whose counts are multinomial in
+        ``w p_a + (1 - w) p_b`` -- for every weight ``w`` of ``weights`` (1 to 8 values in the open interval (0, 1); ``w`` is the share of clone ``a``), on
+        the device in float64 (ca_clone_pair_loglik; include/clonealign_hip.h has the formula and the rules).  ``E``, ``U``, ``V`` and ``const`` as for
+        ``clone_loglik`` (``U`` covers all resident cells); ``cells`` = ``(lo, hi)`` restricts the call to that range of cells (None: all) -- a cell's
+        values do not depend on the range.  Returns ``{"ll": [n, C] (clone_loglik's rows, bit for bit; None unless want_ll), "pair_ll": [n, M, W],
+        "pairs": [M, 2]}`` with the pairs in lexicographic order.  A positive count where both clones have ``E = 0`` gives exactly ``-inf``; no NaN.
+        Changes nothing in the engine; two calls agree bit for bit."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"clone_pair_loglik: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        if (U is None) != (V is None):
+            raise ValueError("clone_pair_loglik: U and V go together (both, or neither)")
+        D = 0
+        Um = Vm = None
+        if U is not None:
+            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
+                raise ValueError(f"clone_pair_loglik: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
+            D = int(U.shape[1])
+            if D > 0:
+                Um = np.require(U, requirements=[self._order, "A"])
+                Vm = np.require(V, requirements=[self._order, "A"])
+        lo, hi = (0, self.N) if cells is None else (int(cells[0]), int(cells[1]))
+        n = max(hi - lo, 0)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        Wn, Cn = int(w.shape[0]), self.C
+        pairs = np.array([(a, b) for a in range(Cn) for b in range(a + 1, Cn)], dtype=np.int64).reshape(-1, 2)
+        M = pairs.shape[0]
+        Em = np.require(E, requirements=[self._order, "A"])
+        ll = np.zeros((n, Cn), dtype=np.float64, order=self._order) if want_ll else None
+        pll = np.zeros((n, M * min(Wn, 8)), dtype=np.float64, order=self._order)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self._fn("clone_pair_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(w), Wn, lo, hi - lo, ptr(ll), ptr(pll)))
+        return {"ll": ll, "pair_ll": np.ascontiguousarray(pll).reshape(n, M, Wn), "pairs": pairs}
 
     def project_cells(self, E, V=None, K=0, X=None, log_prior=None, psi_start=None, const=True, max_iter=25, tol=1e-9, max_step=1.0, poll_every=None):
         """Per-cell MAP ``psi`` of the resident cells under a fit's gene-level parameters and the exact clone posterior at it (ca_project_cells;

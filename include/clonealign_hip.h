@@ -422,6 +422,29 @@ int ca_fit_mse(ca_handle h, const int32_t* clone_of_cell, const double* E, doubl
 int ca_clone_loglik(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */,
                     int32_t D, int32_t with_const, double* ll /* N x C */);
 
+/* Log-likelihood of the resident counts under a MIXTURE OF TWO CLONES -- a heterotypic doublet: the sum of two multinomial rows of clones a and b is
+ * multinomial in w p_a + (1 - w) p_b -- for every unordered pair a < b, every weight of a grid and the cells [cell_lo, cell_lo + cell_cnt).  Notation and
+ * arguments of ca_clone_loglik: E (G x C), eta_ng = U_n . V_g, Z_nc = sum_g E[g][c] exp(eta_ng), s_n = sum_g y_ng; U is N x D over ALL resident cells.
+ *   pair_ll[n][(a,b)][w] = sum_{g: y_ng > 0} y_ng log( w E[g][a] / Z_na + (1 - w) E[g][b] / Z_nb ) + sum_g y_ng eta_ng + const_n
+ * with const_n as in ca_clone_loglik.  Pairs in lexicographic order (0,1), (0,2), ..., (C-2,C-1), M = C (C - 1) / 2 of them; pair_ll is cell_cnt x (M n_weights)
+ * in the problem's layout, column = pair * n_weights + weight index, row = cell - cell_lo.  ll (cell_cnt x C, or NULL): ca_clone_loglik's rows of those
+ * cells, bit for bit.  Rules:
+ *   the bracket is evaluated under a per-pair shift: lz = min(log Z_na, log Z_nb), coefficients w exp(lz - log Z_na) and (1 - w) exp(lz - log Z_nb), both <= 1,
+ *     and s_n lz subtracted outside the sum; log Z_nc itself under the max_g eta_ng shift of ca_clone_loglik: nothing overflows while the result is representable.
+ *   a positive count on a gene where BOTH clones have E = 0 makes that entry exactly -inf; E = 0 in one clone only is finite; a zero count is skipped (0 log 0 is
+ *     never formed); no NaN anywhere; a cell with s_n = 0 gets 0 + const_n.
+ *   With D > 0 the weight a gene sees depends on the cell (through Z_na / Z_nb): one float64 log per (cell, non-zero count, pair, weight), a wave per cell over
+ *     its non-zero counts in ascending gene order, a lane per (pair, weight).  With D = 0 the logarithm is a per-gene table of M n_weights columns, swept like
+ *     ca_clone_loglik's.  Everything is float64, sums run in a fixed order (no atomics): two calls agree bit for bit, and a cell's values depend neither on the
+ *     cell range it was asked in nor on its place in the launch, so a cell-sharded group returns the single handle's bits.
+ * CA_ERR_INVALID (with a message naming the offender): everything ca_clone_loglik refuses; C < 2; n_weights outside [1, 8]; a weight that is non-finite or
+ * outside the open interval (0, 1); a cell range outside [0, N]; E or pair_ll NULL.
+ * Sharded handle: U, the cell range and the outputs are the local cells'; the only collective is the verdict on the input.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_clone_pair_loglik(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */, int32_t D,
+                         int32_t with_const, const double* weights /* n_weights, each in (0, 1) */, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt,
+                         double* ll /* cell_cnt x C, or NULL */, double* pair_ll /* cell_cnt x (M n_weights) */);
+
 /* Project cells onto a fitted model: for every resident cell the MAP value of its latent factor psi_n under the fit's GENE-LEVEL parameters, and the
  * exact clone posterior at it -- the per-cell part of the model for cells the fit never saw (no refit; every cell is independent).  Notation of
  * ca_clone_loglik: E (G x C) = mu L, V = [W | beta] (G x D, D = K + P), U_n = [psi_n | x_n] (the first K columns free, the last P given by X),
@@ -646,6 +669,11 @@ int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell /* N, all c
 /* ca_clone_loglik (R/inference-tflow.R:288-296) over the group: U and ll hold ALL cells (sliced by the shards); each cell's row is the single handle's, bit for bit */
 int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D,
                           int32_t with_const, double* ll /* N x C, all cells */);
+/* ca_clone_pair_loglik over the group: U holds ALL cells, the cell range counts the group's cells, ll and pair_ll hold the range's rows; each cell's values are the
+ * single handle's, bit for bit (every rank is called with its part of the range, an empty one included, for the verdict on the input) */
+int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
+                               const double* weights, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt, double* ll /* cell_cnt x C, or NULL */,
+                               double* pair_ll /* cell_cnt x (M n_weights) */);
 /* ca_project_cells over the group: X, log_prior, psi_start and every output hold ALL cells (sliced by the shards); each cell's results are the single handle's, bit for bit */
 int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X /* N x P, all cells, or NULL */,
                            const double* log_prior /* N x C, all cells, or NULL */, const double* psi_start /* N x K, all cells, or NULL */,
