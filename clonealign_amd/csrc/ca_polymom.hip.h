@@ -124,18 +124,21 @@ __device__ __forceinline__ void ca_pm_B_body(const ca_pm_args& a, int grp0, int 
   for (int w_ = 1; w_ < TB / 64; ++w_) { mn = fminf(mn, s.smn[w_]); mx = fmaxf(mx, s.smx[w_]); xm = fmaxf(xm, s.sxm[w_]); }
   double xmax = nx > 0 ? (double)xm : (double)__uint_as_float(*a.xbits);
   if (nglob > 0) { xmax = 0.0; for (int r = 0; r < nglob; ++r) xmax = fmax(xmax, a.xglob[r]); xmax += a.xadd; }   // (uniform; a handful of ranks)
-  const double vlo = (double)mn, width = (double)mx - (double)mn;
+  const double width = (double)mx - (double)mn;
   int nb = (int)ceil(xmax * width / (2.0 * CA_PL_A));
   nb = nb < 1 ? 1 : (nb > NB ? NB : nb);
   const double delta = width > 0.0 ? width / nb : 1.0;
-  // (all loadings equal -- W = 0 at the start of every fit -- is one bin of width zero: any |x| is covered)
+  // All loadings equal -- W = 0 at the start of every fit -- is one bin of width one CENTRED on the common value: vlo half a bin below it, so that the centre
+  // formula of the three kernels, vlo + (b + 0.5) delta, gives v_b = v exactly (a float minus and plus 0.5 in float64), every gene has v - v_b = 0 and the series
+  // is its first term: any |x| is covered.  (With vlo AT the common value the centre lay 0.5 above the genes and nothing bounded |0.5 x| by CA_PL_A.)
+  const double vlo = width > 0.0 ? (double)mn : (double)mn - 0.5;
   const int bad = !(xmax * (width > 0.0 ? delta : 0.0) * 0.5 <= CA_PL_A * 1.25) || !isfinite(xmax) || !isfinite(width);
   if (first && t == 0) {
     ca_poly_hdr* hdr = a.hdr;
     ca_pm_st<PUB>(&hdr->vlo, vlo); ca_pm_st<PUB>(&hdr->delta, delta); ca_pm_st<PUB>(&hdr->xmax, xmax);
     if (PUB) __hip_atomic_store(&hdr->nb, nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else hdr->nb = nb;
     if (bad) { hdr->bad = 1; if (a.bad_word) __hip_atomic_store(a.bad_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }   // (the host looks at its next synchronisation)
-    if (a.mirror) ca_poly_mirror_store(a.mirror, a.seq, xmax, vlo, (double)mx);
+    if (a.mirror) ca_poly_mirror_store(a.mirror, a.seq, xmax, (double)mn, (double)mx);   // (the host's look ahead gets the true range)
   }
   for (int gi = 0; gi < ngrp; ++gi) {
     if (gi > 0) {   // (the block's next group: its LDS tables are read no more)

@@ -555,6 +555,11 @@ class HipEngine:
         self._ck(self.lib.ca_gradients(self.h, p, C.byref(out)))
         return {n: self._get(self.lib.ca_get_gradient, n) for n in self.VAR_NAMES}, out.value
 
+    def last_gradients(self, names=None):
+        """The gradient buffers as the last pass left them (ca_get_gradient, no ca_gradients in front): after ``iterate`` / ``run`` the gradients
+        the loop's update launches applied -- include/clonealign_hip.h says which state and draw each buffer belongs to."""
+        return {n: self._get(self.lib.ca_get_gradient, n) for n in (names or self.VAR_NAMES)}
+
     def run(self, eps_stream, max_iter, rel_tol, poll=None):
         """Whole loop of R/inference-tflow.R:368-417 in one call; returns the ELBO trace.
 
@@ -906,7 +911,7 @@ class HipGroupEngine(HipEngine):
     def _no(self, *a, **k):
         raise NotImplementedError("not available on a device group (use the rank engines through rank_info / a single HipEngine)")
 
-    elbo_terms = gradients = set = kernel_times = set_profile = synchronize = stream_busy = _no
+    elbo_terms = gradients = last_gradients = set = kernel_times = set_profile = synchronize = stream_busy = _no
     comm_init = comm_benchmark = comm_selftest = _no
 
 

@@ -507,7 +507,15 @@ int ca_logexpr_sums(ca_handle h, const int32_t* group_of_cell, int32_t n_groups,
 int ca_get_param(ca_handle h, const char* name, double* out);
 /* Overwrite a raw variable (same names as above, raw set + "psi","W","beta"); resets nothing else. */
 int ca_set_param(ca_handle h, const char* name, const double* in);
-/* after ca_gradients(): d ELBO / d variable, raw-variable names as in ca_set_param */
+/* d ELBO / d variable as the last pass that made it left it, raw-variable names as in ca_set_param.  After ca_gradients(): all of them, at the current state
+ * and that call's draw.  The loop's passes store the gradients they make in the same buffers, whether or not they step, so after ca_iterate / ca_run they hold:
+ *   loc, ls, W, beta, psi      stored by a train pass's update launches only: the gradient the LAST train pass applied -- the state before its Adam step,
+ *                              its draw;
+ *   gamma_logits               stored by every cell epilogue.  ca_iterate ends on a monitor pass: the state AFTER the last step and that pass's draw (called
+ *                              with one draw more than the 2 n it consumes, that pass carries the next call's first forward half: then the carried draw);
+ *   v, alpha_unconstr          stored by the O(K + C) body of every pass, a monitor pass's tail included (neither depends on the draw): after ca_iterate
+ *                              the state AFTER the last step.
+ * tests/test_gpu_series_grad.py reads them this way. */
 int ca_get_gradient(ca_handle h, const char* name, double* out);
 
 /* A new restart on the same data: what run_clonealign()'s loop (R/clonealign.R:50-56) gets by calling inference_tflow() again --
