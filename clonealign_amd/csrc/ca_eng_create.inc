@@ -1,4 +1,49 @@
 // ca_eng_create.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): create_impl: buffers, decomposition picks (every threshold measured: DESIGN.md section 5), setup sums; find_param.
+
+// ---- CA_VAR_MOM_LAST: where the moment role of the count-matrix stream's launch goes (ca_polymom.hip.h) -- pure functions of numbers the engine has ------------
+// In front of the stream's blocks the role's nmb + nred blocks take slots first, and as many stream blocks as the grid then exceeds one round of slots by start only
+// when a block of the role leaves: the launch ends that much later (3.75 us at cfg-3, profiles/r14_mom_last_before.txt).  Behind the stream's blocks every stream
+// block is resident from the start and the role runs in the slots the stream leaves free.  What that is worth is set by the role's own chain of memory latencies,
+// which beside the stream's traffic runs several times slower than on an empty device (profiles/r14_mom_last_ab.txt):
+//   * the role's shape behind the stream: as many gene groups per moment block as make the moment blocks fit ONE round of the free slots of every XCD (blocks are
+//     dealt round-robin over the XCDs) -- a block then scans V and max|psi| once for its groups, where several rounds of one-group blocks scan them once per block --
+//     and twice the reducers, which cost no stream block a slot there.  At cfg-3 (44 free slots, 5 per XCD): 4 groups per block, 40 blocks, 42 reducers.  Measured
+//     at cfg-3 against one group and 21 reducers behind the stream: 4 groups -1.6 us, 42 reducers -1.0 us, both -2.8 us per iteration; 2 groups +1.3 us.
+//   * the order is kept as it was (false) where nothing would be displaced (the stream's blocks and the role fit one round of slots together: the orders are
+//     equivalent), where an XCD would have no free slot beside its stream blocks, where one round would need more than CA_ML_MAX_PER groups per block, and where the
+//     stream's estimated time is below CA_ML_MIN_STREAM_US: the role's chain in that shape ends about as late as a 52 us stream (cfg-3: the launch 1.5 - 2 us
+//     longer than the stream alone instead of 3.75), and later than a shorter one -- behind a 29 us stream (50k x 5k) it is level with the order in front or slower,
+//     behind an 18 us stream (25k x 5k) 4 - 9 us slower.
+// The stream's time from its stored bytes: fixed + bytes / rate, fitted to k_ys_mfma_ovf<true> alone at 25k / 50k / 100k x 5k (17.66 / 29.42 / 52.20 us).
+constexpr double CA_ML_STREAM_FIXED_US = 6.6;
+constexpr double CA_ML_STREAM_BYTES_PER_US = 5.62e6;
+constexpr double CA_ML_MIN_STREAM_US = 45.0;   // between the 29.4 us stream where the order does not pay and the 52.2 us stream where it does
+constexpr int CA_ML_MAX_PER = 4;               // the most gene groups per moment block that was measured
+struct ca_mom_last_in {
+  int slots;            // resident blocks of this kernel with its dynamic LDS: occupancy x n_cu, asked of the runtime
+  int n_cu;             // XCDs = n_cu / 32 on this part
+  int nb_stream, nb_ovf;   // the stream's blocks; the overflow list's (behind the role: they take no slot from it and do not enter the pick)
+  int ngrp, nred;       // gene groups (32 genes each); reducer blocks with the role in front
+  int64_t image_bytes;  // stored image bytes the launch reads
+};
+inline int ca_mom_last_free(const ca_mom_last_in& a) { return std::max(a.slots - a.nb_stream, 0); }
+inline int ca_mom_last_free_x(const ca_mom_last_in& a) {   // free slots of the XCD with the most stream blocks
+  const int xcd = std::max(a.n_cu / 32, 1);
+  return a.slots / xcd - cdiv(a.nb_stream, xcd);
+}
+// gene groups per moment block behind the stream: the fewest with which every XCD's moment blocks fit its free slots at once (0: no XCD-wide free slot)
+inline int ca_mom_last_per(const ca_mom_last_in& a) {
+  const int xcd = std::max(a.n_cu / 32, 1), free_x = ca_mom_last_free_x(a);
+  if (free_x < 1) return 0;
+  return std::max(1, cdiv(a.ngrp, free_x * xcd));
+}
+inline bool ca_mom_last_pick(const ca_mom_last_in& a) {
+  if (a.nb_stream + a.ngrp + a.nred <= a.slots) return false;
+  const int per = ca_mom_last_per(a);
+  if (per < 1 || per > CA_ML_MAX_PER) return false;
+  return CA_ML_STREAM_FIXED_US + (double)a.image_bytes / CA_ML_STREAM_BYTES_PER_US >= CA_ML_MIN_STREAM_US;
+}
+
 int create_impl(ca_engine* h, const ca_problem* p) {
   const int N = (int)h->N; (void)N;
   HIPCK(h, hipSetDevice(h->device));
@@ -444,6 +489,34 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   // the series form's forward moments ride on its in-line count-matrix stream's launch (CA_VAR_MOM_RIDE, ca_polymom.hip.h): wherever that stream exists and runs in
   // line -- every shape measured gains or is level (profiles/r11_mom_ride_ab.txt); a pass that launches no stream keeps the moments' own launches (run_fused)
   h->mom_ride = h->poly && h->y_ys && !h->poly_side && h->host_dev && variant_on(h, CA_VAR_MOM_RIDE, "CA_MOM_RIDE");
+  // ... behind the stream's blocks where ca_mom_last_pick (above) says so (CA_VAR_MOM_LAST), or wherever they ride (CA_VARX_MOM_LAST); off: in front, as before
+  if (h->mom_ride) {
+    ca_mom_last_in ml;
+    int per_cu = 0;
+    // (the slots of the launch that runs: the form with the overflow list's blocks where there is a list, the stream's dynamic LDS of the image in use)
+    const hipError_t oe = h->ys4 ? (h->n_ovf > 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ys_mfma_ovf_mom<true>, CA_YM_TB, CA_YS4_LDS_BYTES)
+                                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ys_mfma_mom<true>, CA_YM_TB, CA_YS4_LDS_BYTES))
+                                 : (h->n_ovf > 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ys_mfma_ovf_mom<false>, CA_YM_TB, CA_YS_LDS_BYTES)
+                                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ys_mfma_mom<false>, CA_YM_TB, CA_YS_LDS_BYTES));
+    if (oe != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }   // (no answer: no free slot is known of, the rule keeps the order as it was)
+    ml.slots = per_cu * h->n_cu; ml.n_cu = h->n_cu;
+    ml.nb_stream = h->ys_nrg * h->ys_nseg;
+    ml.nb_ovf = h->n_ovf > 0 ? cdiv(Nn, CA_TB) + cdiv(h->n_ovf_chunk, CA_TB / 64) : 0;
+    ml.ngrp = h->pws.n_gene_blocks; ml.nred = CA_MOM_NRED;
+    ml.image_bytes = h->ys_N64 * h->Gp / (h->ys4 ? 2 : 1);
+    h->mom_free_slots = ca_mom_last_free(ml);
+    h->mom_last = variantx_on(h, CA_VARX_MOM_LAST, "CA_MOM_LAST_ON") || (variant_on(h, CA_VAR_MOM_LAST, "CA_MOM_LAST") && ca_mom_last_pick(ml));
+    if (h->opt.variant_off & CA_VAR_MOM_LAST) h->mom_last = false;   // (off is off: the launch as it was, block for block, whatever else is asked)
+    if (h->mom_last) {   // the role's shape behind the stream (above); forced where no XCD-wide free slot exists: the shape it has in front
+      const int per = ca_mom_last_per(ml);
+      h->mom_per = per < 1 ? CA_MOM_PER : std::min(per, CA_ML_MAX_PER);
+      h->mom_nred = 2 * CA_MOM_NRED;
+      const int lab = (h->opt.reserved[1] & ~0xFF) ? h->opt.reserved[1] >> 8 : 0;   // (ca_options.reserved[1], bits 8 up, lab: groups per moment block | 16: the reducers of the order in front | 32: overflow blocks in front of the role)
+      if (lab & 15) h->mom_per = lab & 15;
+      if (lab & 16) h->mom_nred = CA_MOM_NRED;
+      h->mom_ovf_first = (lab & 32) != 0;
+    }
+  }
   // the series form's cell launch without the memory and LDS-crossbar round trips inside its passes (CA_VAR_CELL_LEAN, ca_poly.hip): wherever the series form runs
   h->cell_lean = h->poly && variant_on(h, CA_VAR_CELL_LEAN, "CA_CELL_LEAN");
   // the Y stream rides on the forward sweep's launch: 1-byte storage, K = 1, the fused sweep with its default block shapes

@@ -142,7 +142,8 @@ int ys_finish(ca_engine* h, bool defer = false) {
   h->ycache_valid = true;
   return CA_OK;
 }
-// (h->mom_args set: the series form's forward moments ride as the launch's first blocks, ca_polymom.hip.h -- taken here, so that the caller can tell)
+// (h->mom_args set: the series form's forward moments ride as blocks of this launch, ca_polymom.hip.h -- taken here, so that the caller can tell.  The grid is
+//  [role][stream][overflow] with pm->blk0 = 0 and [stream][role][overflow] with pm->blk0 = nb_main: the same block count, the kernels map the index)
 template <bool Y4>
 void launch_ys(ca_engine* h) {
   constexpr int lds = Y4 ? CA_YS4_LDS_BYTES : CA_YS_LDS_BYTES;
@@ -153,7 +154,11 @@ void launch_ys(ca_engine* h) {
   if (h->n_ovf > 0) {   // (the overflow list's blocks behind the stream's)
     const ca_ovf_args ovf = ys_ovf(h);
     const dim3 grid(nmom + nb_main + ovf.nb_rows + ovf.nb_chunks);
-    if (pm) hipLaunchKernelGGL(k_ys_mfma_ovf_mom<Y4>, grid, dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D, *pm);
+    if (pm) {
+      ca_pm_args pmo = *pm;
+      if (h->mom_last && h->mom_ovf_first) pmo.blk0 += ovf.nb_rows + ovf.nb_chunks;   // (lab: the overflow list's blocks between the stream's and the role)
+      hipLaunchKernelGGL(k_ys_mfma_ovf_mom<Y4>, grid, dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D, pmo);
+    }
     else hipLaunchKernelGGL(k_ys_mfma_ovf<Y4>, grid, dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D);
   } else {
     if (pm) hipLaunchKernelGGL(k_ys_mfma_mom<Y4>, dim3(nmom + nb_main), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, *pm);
@@ -854,8 +859,9 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
       pm.tabB = h->pws.tabB; pm.flags = h->pws.mflags;
       if (++h->mom_tag == 0u) h->mom_tag = 1u;
       pm.tag = h->mom_tag;
-      pm.ngrp = h->pws.n_gene_blocks; pm.per = CA_MOM_PER; pm.nmb = (int)cdiv(pm.ngrp, pm.per); pm.nred = CA_MOM_NRED;
-      pm.timeout_ticks = 50000000ull;   // 0.5 s: every block a reducer waits for was dispatched before it and depends on nobody
+      pm.ngrp = h->pws.n_gene_blocks; pm.per = h->mom_per; pm.nmb = (int)cdiv(pm.ngrp, pm.per); pm.nred = h->mom_nred;
+      pm.blk0 = h->mom_last ? h->ys_nrg * h->ys_nseg : 0;   // (CA_VAR_MOM_LAST: behind the stream's blocks, in front of the overflow list's; else the launch's first blocks)
+      pm.timeout_ticks = 50000000ull;   // 0.5 s: every block a reducer waits for depends on nobody and at worst queues for a slot until stream blocks leave (ca_polymom.hip.h)
       pm.err = reinterpret_cast<unsigned int*>(h->host_dev + 43);
       h->mom_args = &pm;
     } else {

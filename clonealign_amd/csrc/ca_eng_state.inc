@@ -159,6 +159,9 @@ struct ca_engine {
   // the series form's forward moments as the moment role of its count-matrix stream's launch (CA_VAR_MOM_RIDE, ca_polymom.hip.h): the pick, the launch tag, and the
   // arguments of the pass being queued (run_fused sets them, the stream's launch site takes them)
   bool mom_ride = false; unsigned mom_tag = 0; const ca_pm_args* mom_args = nullptr;
+  // the moment role behind the stream's blocks instead of in front of them (CA_VAR_MOM_LAST: ca_mom_last_pick, ca_eng_create.inc): the order in use, the slots the
+  // stream's blocks leave free in one round of the launch (what the pick saw), and the role's shape (groups per moment block, reducer blocks)
+  bool mom_last = false, mom_ovf_first = false; int mom_free_slots = 0, mom_per = CA_MOM_PER, mom_nred = CA_MOM_NRED;
   bool cell_lean = false;   // the series form's cell launch in its lean form (CA_VAR_CELL_LEAN, ca_poly.hip k_poly_cell<CP, true>)
   bool poly = false, poly_side = false, poly_y_defer = false, poly_fresh = false, poly_df = false /* the last backward half was the series form's: d/dF is ONE slab */; ca_poly_ws pws; float* poly_zero = nullptr; unsigned char* poly_mem = nullptr;
   float *Mb2 = nullptr, *mu32B = nullptr, *Zpart2 = nullptr; double* gene_partB = nullptr;

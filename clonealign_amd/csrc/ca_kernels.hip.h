@@ -837,27 +837,29 @@ __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_y
   ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 
-// The series form's forward moments RIDING on its count-matrix stream's launch (CA_VAR_MOM_RIDE): blocks 0 .. nmb + nred - 1 are the moment role
-// (ca_polymom.hip.h: moment blocks, then their reducers), dispatched first, so that they hold slots before the stream's blocks fill the chip; the stream's
-// blocks follow with their index moved down by that many -- nothing else of the stream changes (same body, same register budget, same dynamic LDS, out of
-// which the moment role carves its tables).  Neither role reads what the other writes.
+// The series form's forward moments RIDING on its count-matrix stream's launch (CA_VAR_MOM_RIDE): blocks pm.blk0 .. pm.blk0 + nmb + nred - 1 are the moment
+// role (ca_polymom.hip.h: moment blocks, then their reducers).  pm.blk0 = 0: dispatched first, so that they hold slots before the stream's blocks fill the chip,
+// the stream's blocks behind them.  pm.blk0 = nb_main (CA_VAR_MOM_LAST): the stream's blocks first -- all of them resident from the start where the grid is at
+// most one round of slots --, the role in the slots they leave free, the overflow list's blocks last.  Either way a block that is not of the role counts its
+// index without the role's blocks: the stream's body and the overflow list's get the index they get without the role -- nothing else of the stream changes
+// (same body, same register budget, same dynamic LDS, out of which the moment role carves its tables).  Neither role reads what the other writes.
 #include "ca_polymom.hip.h"
 static_assert(sizeof(ca_pm_lds) <= (size_t)CA_YS_LDS_BYTES && sizeof(ca_pm_lds) <= (size_t)CA_YS4_LDS_BYTES, "the moment role's tables fit the stream's dynamic LDS");
 template <bool Y4>
 __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_mom(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS, ca_pm_args pm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];   // Y4: CA_YS4_LDS_BYTES, else CA_YS_LDS_BYTES
-  const int nmom = pm.nmb + pm.nred;
-  if ((int)blockIdx.x < nmom) { ca_pm_ride_block<CA_YM_TB>(pm, (int)blockIdx.x, ca_ys_dyn); return; }
-  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x - nmom, Ys, io, N, Gp, RS, ca_ys_dyn);
+  const int nmom = pm.nmb + pm.nred, rb = (int)blockIdx.x - pm.blk0;
+  if (rb >= 0 && rb < nmom) { ca_pm_ride_block<CA_YM_TB>(pm, rb, ca_ys_dyn); return; }
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>(rb < 0 ? (int)blockIdx.x : (int)blockIdx.x - nmom, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 template <bool Y4>
 __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_ovf_mom(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS,
                                                                            int nb_main, ca_ovf_args ovf, const float* __restrict__ F,
                                                                            const float* __restrict__ V, int Dstride, ca_pm_args pm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];
-  const int nmom = pm.nmb + pm.nred;
-  if ((int)blockIdx.x < nmom) { ca_pm_ride_block<CA_YM_TB>(pm, (int)blockIdx.x, ca_ys_dyn); return; }
-  const int blk = (int)blockIdx.x - nmom;
+  const int nmom = pm.nmb + pm.nred, rb = (int)blockIdx.x - pm.blk0;
+  if (rb >= 0 && rb < nmom) { ca_pm_ride_block<CA_YM_TB>(pm, rb, ca_ys_dyn); return; }
+  const int blk = rb < 0 ? (int)blockIdx.x : (int)blockIdx.x - nmom;
   if (blk >= nb_main) {
     const int b = blk - nb_main;
     if (b < ovf.nb_rows) ca_ovf_rows_body(b, ovf.rowptr, ovf.col, ovf.val, V, Dstride, ovf.YWextra, N, 1, 0);

@@ -1,12 +1,13 @@
 // ca_polymom.hip.h -- the series form's forward moments as device bodies that two launches share:
 //   * ca_poly.hip's own kernels k_poly_B / k_poly_red (the fallback order: launches of their own in front of the count-matrix stream), and
-//   * the MOMENT ROLE of the count-matrix stream's launch (k_ys_mfma_mom / k_ys_mfma_ovf_mom, ca_kernels.hip.h): the lowest block indices of that launch
-//     make the moments while the stream's blocks fill the chip behind them -- two launches and their boundaries less per iteration.
+//   * the MOMENT ROLE of the count-matrix stream's launch (k_ys_mfma_mom / k_ys_mfma_ovf_mom, ca_kernels.hip.h): nmb + nred blocks of that launch, from block
+//     index blk0 on, make the moments beside the stream's blocks -- two launches and their boundaries less per iteration.  blk0 = 0: in front of the stream's
+//     blocks (they hold slots before the stream fills the chip); blk0 = the stream's block count: BEHIND them (CA_VAR_MOM_LAST), in the slots the stream leaves free.
 // One copy of the arithmetic: every output sees the same additions in the same order whichever launch runs it (32 genes per partial, genes in order inside an
 // accumulator; the reduction's lane stride over the partials, eight loads in flight, the wave tree), so the two orders give the same bits.
 //
-// Hand-over inside the merged launch (the idiom of ca_fwdbal.hip.h: device-scope atomics and tagged words, never a grid barrier).  Blocks [0, nmb) make the
-// partials, blocks [nmb, nmb + nred) reduce them.  A moment block stores its partials (and block 0 the header) with DEVICE-SCOPE atomic stores, every wave waits
+// Hand-over inside the merged launch (the idiom of ca_fwdbal.hip.h: device-scope atomics and tagged words, never a grid barrier).  Counted from blk0, blocks
+// [0, nmb) make the partials, blocks [nmb, nmb + nred) reduce them.  A moment block stores its partials (and block 0 the header) with DEVICE-SCOPE atomic stores, every wave waits
 // until its stores are acknowledged (s_waitcnt vmcnt(0)), the block meets at its barrier, and thread 0 stores this launch's tag into the block's flag word (a
 // device-scope atomic store as well).  A reducer polls the flag words of ALL moment blocks with relaxed device-scope loads until they hold the tag, passes ONE
 // device-scope acquire fence and its own barrier, and then reads header and partials with device-scope atomic loads.
@@ -16,8 +17,17 @@
 //   still hold of LAST iteration's slab, and the acquire fence drops such lines for good measure.  So flag == tag implies the partials of that block are at the
 //   memory side, and the reads behind the acquire go there.  (No release fence on the writer's side: every handed-over byte is a write-through store, and a
 //   fence would write back the whole L2 -- beside the stream's traffic, the cost the round-5 note on k_poly_B warned of.)
-//   Why the wait ends: every block a reducer waits for has a LOWER index, blocks are dispatched in index order, and a dispatched moment block depends on
-//   nobody -- it runs to its flag store whatever else is resident.  No residency assumption, no spin on a block that may not have been dispatched.
+//   Why the wait ends, in either order of the grid: every block a reducer waits for has a LOWER index than the reducer (the reducers are the role's last blocks
+//   wherever the role sits), and a moment block depends on nobody -- once dispatched it runs to its flag store whatever else is resident.  In front (blk0 = 0)
+//   the moment blocks are the launch's first and are dispatched before anything can hold a slot against them.  Behind the stream's blocks (CA_VAR_MOM_LAST) a
+//   moment block may QUEUE: every slot its XCD has can be taken by stream blocks, overflow blocks or reducers.  Stream and overflow blocks depend on nobody
+//   either and leave after a bounded time, and the nred reducers are far fewer than the launch's slots, so they alone can never hold every slot: a queued moment
+//   block is simply dispatched later, when a stream block of its XCD leaves, at the latest when the stream has drained -- a reducer then waits that much longer
+//   (a few tens of microseconds), in a slot no stream block is waiting for, because every stream block was dispatched before the first block of the role.  The
+//   argument needs no residency of the role and no order of dispatch beyond "a block that depends on nobody gets a slot when one frees".
+//   Nothing else waits on the role inside the launch: the stream's and the overflow list's blocks read nothing it writes.  Its other outputs are read after the
+//   launch's end whichever blocks made them last -- tabB and the header by the cell launch, the ranges ring (mirror) by a host decision four passes later, bad_word
+//   and the error word at the host's next synchronisation, and xbits (reset by reducer 0 once every moment block has published) by the next update launch.
 //   The wait is bounded all the same (timeout_ticks, the s_memrealtime clock): on expiry the block stores the sticky error word, takes no further part (tabB keeps
 //   what it held) and the host reports CA_ERR_STATE at its next synchronisation (comm_check).
 #pragma once
@@ -55,6 +65,7 @@ struct ca_pm_args {
   unsigned int* flags;               // [nmb] this launch's tag once the block's partials are published (the workspace starts zeroed)
   unsigned int tag;                  // never 0
   int ngrp, per, nmb, nred;          // gene groups (partials), groups per moment block, moment blocks = ceil(ngrp / per), reducer blocks
+  int blk0;                          // the role's first block index in the launch: 0 = in front of the stream's blocks, nb_main = behind them (CA_VAR_MOM_LAST)
   unsigned long long timeout_ticks;  // bound of a reducer's wait (s_memrealtime, 100 MHz)
   unsigned int* err;                 // mapped host word: set when a wait ran out
 };
@@ -233,7 +244,8 @@ __device__ __forceinline__ void ca_pm_red_body(const double* __restrict__ part, 
   }
 }
 
-// ---- the moment role of the count-matrix stream's launch: block blk < nmb + nred of a TB-thread launch, `lds` = the launch's dynamic buffer ------------------
+// ---- the moment role of the count-matrix stream's launch: block blk < nmb + nred of the role (counted from a.blk0 by the caller) in a TB-thread launch,
+// `lds` = the launch's dynamic buffer
 template <int TB>
 __device__ __forceinline__ void ca_pm_ride_block(const ca_pm_args& a, int blk, unsigned char* lds) {
   ca_pm_lds& s = *reinterpret_cast<ca_pm_lds*>(lds);
@@ -248,7 +260,7 @@ __device__ __forceinline__ void ca_pm_ride_block(const ca_pm_args& a, int blk, u
     if (t == 0) __hip_atomic_store(a.flags + blk, a.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ... and only then the block's tag
     return;
   }
-  // a reducer: all moment blocks have lower indices and were dispatched before this one
+  // a reducer: all moment blocks have lower indices; each runs to its flag store once dispatched, and none waits for a slot for ever (the header's argument)
   if (t == 0) s.gave_up = 0;
   __syncthreads();
   {

@@ -130,7 +130,12 @@ enum ca_variant {
                                  but the prefetch of the next one (no read of the zero exponent bound; c_n and psi come with the prefetch), the 4- and 8-lane reductions
                                  through DPP moves instead of the LDS crossbar, the powers of x without a branch per step; the same additions in the same order; on
                                  wherever the series form runs.  Off: the launch as it was (k_poly_cell<CP, false>) */
-  CA_VAR_RIDE_SEQ = 1 << 13   /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
+  CA_VAR_MOM_LAST = 1 << 25,  /* the moment role of CA_VAR_MOM_RIDE BEHIND the stream's blocks in the launch's grid instead of in front of them, where a host rule says
+                                 that this hides it (the stream's blocks and the role exceed one round of block slots, every XCD keeps a free slot, the role's chain
+                                 in the free slots fits under the stream's time): every stream block is resident from the start and none waits for a block of the
+                                 role to leave.  Scheduling only: the same bits.  Off: the role in front, block for block the launch as it was (CA_VARX_MOM_LAST
+                                 forces the order wherever the moments ride) */
+  CA_VAR_RIDE_SEQ = 1 << 13  /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
 /* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
  * code has been deleted; the constants keep their values and ca_create returns CA_ERR_INVALID for them, in every build. */
@@ -156,6 +161,7 @@ enum ca_variant_on {
                                  float64): moments over genes, evaluation over cells, the same form on the way back.  No cells x genes sweep: O(N nb R C + G R C)
                                  instead of O(N G C) per pass; the cell epilogue is the sweep's.  Other shapes keep the matrix-core sweeps */
   CA_VARX_Y4 = 1 << 9,        /* the 4-bit loop image (CA_VAR_Y4) at any escape fraction */
+  CA_VARX_MOM_LAST = 1 << 10, /* the moment role behind the stream's blocks (CA_VAR_MOM_LAST) wherever the moments ride, whatever the rule says (the bits are the same) */
   CA_VARX_ASYNC_SMALL = 1 << 1 /* side stream also below 4e7 counts (small shards run the Y stream in line: the two cross-stream
                                  events cost more than the overlap returns there) */
 };
@@ -224,6 +230,8 @@ typedef struct ca_info {
   int64_t series_fallbacks;  /* ... and those the look ahead at the exponent range (max|psi| (max W - min W), plus what the Adam steps since can add) gave to the sweeps */
   int32_t mom_ride;          /* 1: the series form's forward moments ride on its count-matrix stream's launch (CA_VAR_MOM_RIDE) */
   int32_t cell_lean;         /* 1: the series form's cell launch runs its lean passes (CA_VAR_CELL_LEAN) */
+  int32_t mom_last;          /* 1: the riding moment role sits behind the stream's blocks in the launch's grid (CA_VAR_MOM_LAST / CA_VARX_MOM_LAST); 0: in front */
+  int32_t mom_free_slots;    /* block slots of the stream's launch (occupancy x compute units, asked of the runtime) that its own blocks leave free: what the rule saw; 0 where no moments ride */
 } ca_info;
 enum ca_transport { CA_TRANSPORT_NONE = 0, CA_TRANSPORT_RCCL = 1, CA_TRANSPORT_HOST = 2, CA_TRANSPORT_P2P = 3 };
 
