@@ -519,6 +519,8 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   }
   // the series form's cell launch without the memory and LDS-crossbar round trips inside its passes (CA_VAR_CELL_LEAN, ca_poly.hip): wherever the series form runs
   h->cell_lean = h->poly && variant_on(h, CA_VAR_CELL_LEAN, "CA_CELL_LEAN");
+  // ... and with its backward moments gathered by fp64 MFMA per wave instead of the thread-owned chain between two block barriers (CA_VAR_CELL_MFMA): likewise
+  h->cell_mfma = h->poly && variant_on(h, CA_VAR_CELL_MFMA, "CA_CELL_MFMA");
   // the Y stream rides on the forward sweep's launch: 1-byte storage, K = 1, the fused sweep with its default block shapes
   h->ride_ok = h->ystore == CA_YSTORE_U8 && K == 1 && D <= 2 && h->fused_ok && !h->c16 && h->fwd_cell && (h->fc_tl == 6 || h->fc_tl == 8 || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
                !h->y_ys && variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE");

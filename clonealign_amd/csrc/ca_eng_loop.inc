@@ -909,7 +909,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     }
     e = ca_poly_cells(h->stream, &h->pws, h->N, h->C, h->K, &cp, h->alpha_u, h->cell_part, h->dFpart, yfin_rides ? &yfin_ride : nullptr,
                       sh ? &ltail : nullptr, h->poly_xmax_ready ? h->poly_xpart : nullptr, (int)cdiv(h->N, CA_TB), h->F, sh ? h->red + h->off_x : nullptr,
-                      h->opt.rank, std::max(h->opt.world, 1), h->cell_lean);
+                      h->opt.rank, std::max(h->opt.world, 1), h->cell_lean, h->cell_mfma);
     h->mon_tail_local = sh;   // (the tail set up below starts with its local sums made)
     if (sh) { h->poly_xslot_pending = true; h->poly_xglob_steps = -1; }   // (the slots hold THIS rank's number until the collective has summed them)
     HIPCK(h, e);

@@ -162,6 +162,7 @@ struct ca_engine {
   // the moment role behind the stream's blocks instead of in front of them (CA_VAR_MOM_LAST: ca_mom_last_pick, ca_eng_create.inc): the order in use, the slots the
   // stream's blocks leave free in one round of the launch (what the pick saw), and the role's shape (groups per moment block, reducer blocks)
   bool mom_last = false, mom_ovf_first = false; int mom_free_slots = 0, mom_per = CA_MOM_PER, mom_nred = CA_MOM_NRED;
+  bool cell_mfma = false;   // ... with the backward moments of its register bins gathered by fp64 MFMA per wave (CA_VAR_CELL_MFMA, k_poly_cell<CP, LEAN, true>)
   bool cell_lean = false;   // the series form's cell launch in its lean form (CA_VAR_CELL_LEAN, ca_poly.hip k_poly_cell<CP, true>)
   bool poly = false, poly_side = false, poly_y_defer = false, poly_fresh = false, poly_df = false /* the last backward half was the series form's: d/dF is ONE slab */; ca_poly_ws pws; float* poly_zero = nullptr; unsigned char* poly_mem = nullptr;
   float *Mb2 = nullptr, *mu32B = nullptr, *Zpart2 = nullptr; double* gene_partB = nullptr;

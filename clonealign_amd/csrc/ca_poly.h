@@ -47,6 +47,7 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
                                                    reduction launch), or NULL */,
                          const float* xs_part, int xs_n, const float* xs_F, double* xs_slots /* cell-sharded: this rank's max |x| slot rides there too, or NULL */,
                          int rank, int world,
-                         bool lean /* CA_VAR_CELL_LEAN: the passes without their memory and LDS-crossbar round trips (k_poly_cell<CP, true>); the same bits either way */);
+                         bool lean /* CA_VAR_CELL_LEAN: the passes without their memory and LDS-crossbar round trips (k_poly_cell<CP, true>); the same bits either way */,
+                         bool mfma /* CA_VAR_CELL_MFMA: the backward moments of the register bins by fp64 MFMA per wave; the chain's sums in another fixed association */);
 hipError_t ca_poly_backward(hipStream_t st, const ca_poly_ws* w, const float* V, const float* mu, const float* Lb, int G, int C, double* red_g,
                             const void* small_tail /* a ca_small_args (pending monitor tail, run by an extra block) or NULL */);

@@ -116,7 +116,18 @@ __global__ void __launch_bounds__(TB_B) k_poly_B(ca_pm_args a) {
 //     dependent trips through the LDS crossbar less per pass (ca_dpp_gsum / ca_dpp_gmax: __shfl_xor's pairing);
 //   * the powers x^k by selects into the (up to) RQ / CP values a lane keeps and unconditional stores, instead of 22 steps of "multiply, branch on exec, store".
 // Every sum keeps its operands and its order: LEAN = false is the launch as it was, and the two agree to the bit (tests/test_gpu_cell_lean.py).
-template <int CP, bool LEAN>
+//
+// MFMA (CA_VAR_CELL_MFMA, the default; independent of LEAN) is how the backward moments of the register bins 0 .. NBR - 1 are gathered.  What the gather computes,
+//     Q[b][k][c] += sum_{s in pass} x_s^k (coef_sc exp(x_s v_b)),
+// is a matrix product with M = k (RQ rows), N = (bin, clone) and the pass's cells as its inner dimension, and everything it reads a wave wrote itself: the wave owns
+// 64 / CP of the pass's cells and leaves s_xp, s_cf and s_eb for exactly those.  So each wave multiplies its own cells by v_mfma_f64_16x16x4_f64 -- four cells a step;
+// A[row = lane & 15][cell = lane >> 4] = x^k, B[cell = lane >> 4][column = lane & 15] = coef e_b with column = (bin in tile) CP + clone; two row tiles for k = 0 .. 15
+// and 16 .. RQ - 1, NBR CP / 16 column tiles -- into accumulators it keeps over all the block's passes; C/D[row = (lane >> 4) + 4 reg][column = lane & 15].  Nothing in
+// a pass then crosses a wave, and the two block barriers of the pass give way to wave barriers.  At the block's end the four waves' tiles are added in wave order
+// 0, 1, 2, 3 through LDS (the passes' own arrays, idle by then) into the block's slab: layout and meaning as before; the order inside an MFMA is the hardware's
+// and every other order is the code's, so the sums are the same from run to run, but not the thread-owned chain's association: fp64 rounding apart.  Bins past NBR
+// (a wide exponent range) keep that chain through the slab, and with it the pass's two barriers, under a uniform test.  MFMA = false is the launch as it was.
+template <int CP, bool LEAN, bool MFMA>
 __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restrict__ hdr, const double* __restrict__ tabB, ca_cell_ptrs p,
                                                      const float* __restrict__ alpha_u, double* __restrict__ cell_part, int64_t N, int C, int K,
                                                      float* __restrict__ dF /*[N]*/, double* __restrict__ Qpart /*[grid][nb][R+2][C]*/, int ncb, ca_yfin_args yfin) {
@@ -159,7 +170,18 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
   // backward moments: thread t < (R + 2) C owns (k, clone) = (t / C, t % C) of EVERY bin -- nobody else adds to its outputs, cells are added in cell order
   const bool qown = t < RQ * C;
   const int qk = qown ? t / C : 0, qc = qown ? t % C : 0;
-  double qa[NBR] = {0.0, 0.0, 0.0, 0.0};
+  [[maybe_unused]] double qa[NBR] = {0.0, 0.0, 0.0, 0.0};
+  using qtile_t = __attribute__((ext_vector_type(4))) double;
+  constexpr int BPT = 16 / CP;         // bins per column tile of the MFMA gather
+  constexpr int NCT = NBR / BPT;       // its column tiles: bins 0 .. NBR - 1
+  constexpr int KST = 64 / CP / 4;     // its steps per pass: four of the wave's cells each
+  static_assert(CP == 4 || CP == 8, "the MFMA gather's column map");
+  static_assert(CA_TB == 256, "four waves: each owns a quarter of a pass's cells, and the block's end adds four waves' tiles");
+  [[maybe_unused]] qtile_t qm[2][NCT];
+#pragma unroll
+  for (int j = 0; j < NCT; ++j) { qm[0][j] = qtile_t{0.0, 0.0, 0.0, 0.0}; qm[1][j] = qtile_t{0.0, 0.0, 0.0, 0.0}; }
+  const int wv = t >> 6, mrow = t & 15, mk = (t >> 4) & 3;   // the wave; this lane's row / column of a tile and its cell of a step
+  const int mcl = mrow % CP, mbl = mrow / CP;                // the column's clone and bin inside its tile
   double* mine = Qpart + (int64_t)blockIdx.x * (NB * RQ * 8);
   if (qown) for (int b = NBR; b < nb; ++b) mine[(b * RQ + qk) * C + qc] = 0.0;
   ca_cell_acc acc = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -230,6 +252,40 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
     if (c == 0 && n < N) dF[n] = (float)df;
     if (c < 8) s_cf[slot][c] = cf;
     CA_LAB_CELL_PH_AFTER(df, blockIdx.x, pass, 3);
+    if constexpr (MFMA) {
+      // (the wave reads what its own lanes stored: the LDS serves one wave's operations in order, the fences keep the compiler from moving them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+      for (int s = 0; s < KST; ++s) {
+        const int cell = wv * (64 / CP) + s * 4 + mk;
+        const double a0 = s_xp[cell][mrow];
+        const double a1 = s_xp[cell][16 + mrow < XS ? 16 + mrow : XS - 1];   // (rows RQ .. 31 of the second tile are never stored: whatever they multiply)
+        const double cfv = s_cf[cell][mcl];
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) {
+          if (j == 0 || nb > j * BPT) {   // (uniform: a column tile whose bins are all absent)
+            const double bv = cfv * s_eb[cell][j * BPT + mbl];
+            qm[0][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, bv, qm[0][j], 0, 0, 0);
+            qm[1][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, bv, qm[1][j], 0, 0, 0);
+          }
+        }
+      }
+      if (nb > NBR) {   // (uniform; a wide exponent range: the thread's own words of its block's slab, all the pass's cells in cell order, as before)
+        __syncthreads();
+        if (qown) {
+          for (int b = NBR; b < nb; ++b) {
+            double a = mine[(b * RQ + qk) * C + qc];
+            for (int s = 0; s < CPB; ++s) a += s_cf[s][qc] * s_xp[s][qk] * s_eb[s][b];
+            mine[(b * RQ + qk) * C + qc] = a;
+          }
+        }
+        __syncthreads();
+      } else {          // (the next pass's stores behind this pass's loads: one wave, in order)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+      CA_LAB_CELL_PH_AFTER(qm[0][0][0], blockIdx.x, pass, 4);
+      continue;
+    }
     __syncthreads();
     CA_LAB_CELL_PH(blockIdx.x, pass, 4);
     if (qown) {
@@ -255,7 +311,35 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
     CA_LAB_CELL_PH(blockIdx.x, pass, 6);
   }
   ca_cell_fused_finish<CP>(acc, sm, cell_part, blockIdx.x, C);
-  if (qown) {
+  if constexpr (MFMA) {   // the four waves' tiles, added in wave order, into the block's slab
+    // Waves 1, 2, 3 park theirs in LDS arrays of the passes, which nobody reads any more (every wave is past the barriers of ca_cell_fused_finish, so past its
+    // last pass); wave 0 adds them to its own, lane for lane in the tile map, and stores the sums.  No LDS of its own: the launch's extra blocks pay for none.
+    constexpr int QW = RQ * NBR * CP;   // one wave's tiles: [k][bin CP + clone]
+    static_assert(CPB * NB >= QW && CPB * XS >= QW && NBL * (R + 1) * 16 >= QW, "a wave's tiles fit each of the three arrays");
+    double* const p1 = &s_eb[0][0], * const p2 = &s_xp[0][0], * const p3 = &s_tb[0][0];
+    double* const pw = wv == 1 ? p1 : (wv == 2 ? p2 : p3);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < NCT; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int k = 16 * i + 4 * r + mk;
+          if (wv > 0 && k < RQ) pw[k * (NBR * CP) + j * 16 + mrow] = qm[i][j][r];   // (column j 16 + mrow = bin CP + clone)
+        }
+    __syncthreads();
+    if (wv == 0) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NCT; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int k = 16 * i + 4 * r + mk, col = j * 16 + mrow, b = j * BPT + mbl;
+            if (k < RQ && b < nb && mcl < C) mine[(b * RQ + k) * C + mcl] = ((qm[i][j][r] + p1[k * (NBR * CP) + col]) + p2[k * (NBR * CP) + col]) + p3[k * (NBR * CP) + col];
+          }
+    }
+  } else if (qown) {
 #pragma unroll
     for (int b = 0; b < NBR; ++b) if (b < nb) mine[(b * RQ + qk) * C + qc] = qa[b];
   }
@@ -407,7 +491,7 @@ hipError_t ca_poly_moments(hipStream_t st, const ca_poly_ws* w, const float* V, 
 }
 
 hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, int K, const void* cell_ptrs, const float* alpha_u, double* cell_part, float* dF,
-                         const void* yfin_args, const void* local_tail, const float* xs_part, int xs_n, const float* xs_F, double* xs_slots, int rank, int world, bool lean) {
+                         const void* yfin_args, const void* local_tail, const float* xs_part, int xs_n, const float* xs_F, double* xs_slots, int rank, int world, bool lean, bool mfma) {
   const ca_cell_ptrs& p = *static_cast<const ca_cell_ptrs*>(cell_ptrs);
   ca_yfin_args yfin;
   if (yfin_args) memcpy(&yfin, yfin_args, sizeof(yfin)); else memset(&yfin, 0, sizeof(yfin));
@@ -415,7 +499,8 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
   while (CP < C) CP <<= 1;
   const int nextra = yfin_args ? cdiv_i(yfin.ncol, CA_TB / 64) + yfin.nrow : 0;
   const dim3 grid(w->n_cell_blocks + nextra);
-#define CA_PCELL(CPV, LV) hipLaunchKernelGGL((k_poly_cell<CPV, LV>), grid, dim3(CA_TB), 0, st, w->hdr, w->tabB, p, alpha_u, cell_part, N, C, K, dF, w->Qpart, \
+#define CA_PCELL(CPV, LV) do { if (mfma) CA_PCELL_(CPV, LV, true); else CA_PCELL_(CPV, LV, false); } while (0)
+#define CA_PCELL_(CPV, LV, MV) hipLaunchKernelGGL((k_poly_cell<CPV, LV, MV>), grid, dim3(CA_TB), 0, st, w->hdr, w->tabB, p, alpha_u, cell_part, N, C, K, dF, w->Qpart, \
                                          w->n_cell_blocks, yfin)
   if (lean) {   // (3 .. 8 clones: ca_poly_ok)
     if (K > 1) return hipErrorInvalidValue;   // (the lean epilogue takes psi of the prior term from x: one latent dimension, which is all ca_poly_ok admits)
@@ -424,6 +509,7 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
     if (CP == 4) CA_PCELL(4, false); else CA_PCELL(8, false);
   }
 #undef CA_PCELL
+#undef CA_PCELL_
   {
     ca_small_args tail;
     if (local_tail) memcpy(&tail, local_tail, sizeof(tail)); else memset(&tail, 0, sizeof(tail));

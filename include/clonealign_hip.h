@@ -135,6 +135,11 @@ enum ca_variant {
                                  in the free slots fits under the stream's time): every stream block is resident from the start and none waits for a block of the
                                  role to leave.  Scheduling only: the same bits.  Off: the role in front, block for block the launch as it was (CA_VARX_MOM_LAST
                                  forces the order wherever the moments ride) */
+  CA_VAR_CELL_MFMA = 1 << 26, /* the series form's cell launch gathers the backward moments of its register bins as a matrix product per wave (v_mfma_f64_16x16x4_f64
+                                 over the wave's own cells, accumulators kept over the block's passes, the four waves' tiles added in wave order at the block's end)
+                                 instead of a 32-step chain on 176 threads between two block barriers: with at most four bins a pass has no block barrier left.  The
+                                 same sums in another, fixed association: fp64 rounding apart, the same bits from run to run; on wherever the series form runs.
+                                 Off: the thread-owned chain (k_poly_cell<CP, LEAN, false>), the launch as it was */
   CA_VAR_RIDE_SEQ = 1 << 13  /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
 /* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
@@ -232,6 +237,7 @@ typedef struct ca_info {
   int32_t cell_lean;         /* 1: the series form's cell launch runs its lean passes (CA_VAR_CELL_LEAN) */
   int32_t mom_last;          /* 1: the riding moment role sits behind the stream's blocks in the launch's grid (CA_VAR_MOM_LAST / CA_VARX_MOM_LAST); 0: in front */
   int32_t mom_free_slots;    /* block slots of the stream's launch (occupancy x compute units, asked of the runtime) that its own blocks leave free: what the rule saw; 0 where no moments ride */
+  int32_t cell_mfma;         /* 1: the series form's cell launch gathers its backward moments by fp64 MFMA per wave (CA_VAR_CELL_MFMA) */
 } ca_info;
 enum ca_transport { CA_TRANSPORT_NONE = 0, CA_TRANSPORT_RCCL = 1, CA_TRANSPORT_HOST = 2, CA_TRANSPORT_P2P = 3 };
 

@@ -1,7 +1,7 @@
 """Where a pass of the series form's cell launch (ca_series::k_poly_cell) spends its cycles, from the phase stamps wave 0 of the first 64 cell blocks leaves in a
 timing-lab build (CA_LAB_CELL_PH, tools/lab/ca_lab_hooks.inc):
     make -C clonealign_amd/csrc lab
-    CLONEALIGN_HIP_LIB=build_ab/libclonealign_hip_lab.so python tools/cell_stamps.py [--cells N --genes G --clones C] [--variant-off cell_lean]
+    CLONEALIGN_HIP_LIB=build_ab/libclonealign_hip_lab.so python tools/cell_stamps.py [--cells N --genes G --clones C] [--variant-off cell_lean,cell_mfma]
 One fit, a few iterations, the stamps of the LAST cell launch; shader clock cycles per phase over every stamped pass.  The stamps cost a clock read and a store by
 one thread each, so the phases compare between builds of the same stamps, not with a product build's kernel time."""
 import argparse
@@ -16,6 +16,9 @@ sys.path.insert(0, ROOT)
 
 PHASES = ("bins: exp and Horner over the gene bins", "powers x^k into LDS", "cell epilogue and d/dF", "wait at the first barrier",
           "gather of the backward moments", "wait at the second barrier")
+# CA_VAR_CELL_MFMA: the gather is the wave's own matrix product, a pass has no barrier to wait at (past four bins the slab chain and its two barriers are inside
+# the one phase), and the pass ends at stamp 4
+PHASES_MFMA = PHASES[:3] + ("moments: the wave's fp64 MFMA gather",)
 
 
 def main():
@@ -43,13 +46,14 @@ def main():
     st = np.zeros((64, 8, 8), dtype=np.uint64)
     assert lib.ca_lab_read_cell_stamps(st.ctypes.data_as(C.c_void_p), st.size) == 0
     eng.close()
-    print(f"# {N} x {G} x {Cn}; build {E.build_id()}; cell_lean {info['cell_lean']}; series passes {info['series_passes']}; cycles of the shader clock, wave 0 of cell blocks 0..63")
-    live = (st[:, :, 0] > 0) & (st[:, :, 6] > st[:, :, 0])
-    d = np.diff(st.astype(np.int64), axis=2)[:, :, :6]          # [block][pass][phase]
-    whole = (st[:, :, 6].astype(np.int64) - st[:, :, 0].astype(np.int64))
+    print(f"# {N} x {G} x {Cn}; build {E.build_id()}; cell_lean {info['cell_lean']}; cell_mfma {info['cell_mfma']}; series passes {info['series_passes']}; cycles of the shader clock, wave 0 of cell blocks 0..63")
+    phases, last = (PHASES_MFMA, 4) if info["cell_mfma"] else (PHASES, 6)
+    live = (st[:, :, 0] > 0) & (st[:, :, last] > st[:, :, 0])
+    d = np.diff(st.astype(np.int64), axis=2)[:, :, :last]       # [block][pass][phase]
+    whole = (st[:, :, last].astype(np.int64) - st[:, :, 0].astype(np.int64))
     print(f"# stamped passes: {int(live.sum())} (passes per block: {sorted(set(live.sum(1).tolist()))})")
     print("# phase: median / mean / p10 / p90 over the stamped passes; then the median per pass index 0, 1, 2, ...")
-    for j, nm in enumerate(PHASES):
+    for j, nm in enumerate(phases):
         a = d[:, :, j][live]
         per = [int(np.median(d[:, p, j][live[:, p]])) for p in range(8) if live[:, p].any()]
         print(f"{nm:44s} {int(np.median(a)):7d} {a.mean():9.1f} {int(np.percentile(a, 10)):7d} {int(np.percentile(a, 90)):7d}   {per}")

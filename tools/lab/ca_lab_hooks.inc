@@ -23,6 +23,7 @@ __device__ unsigned long long ca_lab_stamps3[2048 * 4];
 #define CA_LAB_PH_AFTER(value, blk, i) do { asm volatile("" ::"v"(value)); CA_LAB_PH(blk, i); } while (0)
 // phases inside a pass of the series form's cell launch (k_poly_cell, wave 0 of the first 64 blocks, their first 8 passes), shader clock cycles:
 // i = 0 top of the pass, 1 bins done, 2 powers stored (the epilogue starts), 3 epilogue and d/dF done, 4 past the first barrier, 5 gather done, 6 past the second
+// (CA_VAR_CELL_MFMA: 4 moments done -- the wave's own MFMA gather, no barrier to wait at -- and the pass ends there)
 __device__ unsigned long long ca_lab_stamps4[64 * 8 * 8];
 #define CA_LAB_CELL_PH(blk, pass, i) do { if (threadIdx.x == 0 && (blk) < 64 && (pass) < 8) ca_lab_stamps4[((blk) * 8 + (pass)) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 #define CA_LAB_CELL_PH_AFTER(value, blk, pass, i) do { asm volatile("" ::"v"(value)); CA_LAB_CELL_PH(blk, pass, i); } while (0)
