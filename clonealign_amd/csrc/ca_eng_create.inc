@@ -383,8 +383,10 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   //  12.5k x 5k x 8 69 / 72; 25k x 5k 96 / 94; 50k x 5k 149 / 126 -- so the rank's own cell count has to carry three times as much)
   const bool series_auto = Nn >= 6000 && (double)G >= 2000.0 + (h->opt.world > 1 ? 7.5e7 : 2.5e7) / (double)Nn;
 #endif
+  h->adam_bound = ca_adam_step_bound(h->opt.learning_rate, h->opt.beta1, h->opt.beta2);
   // (poly_shape: what does not depend on the rank's own cell count -- the same on every rank of a sharded fit)
-  h->poly_shape = ca_poly_ok(D, S, C) && h->fused_ok && !h->c16 && !h->s2 && K == 1 &&
+  // (Adam settings without a step bound, beta1^2 >= beta2: no series form -- its look ahead counts on one)
+  h->poly_shape = ca_poly_ok(D, S, C) && h->fused_ok && !h->c16 && !h->s2 && K == 1 && h->adam_bound > 0 &&
                   (variant_on(h, CA_VAR_SERIES, "CA_SERIES") || variantx_on(h, CA_VARX_SERIES, "CA_SERIES_ON"));
   h->poly = h->poly_shape && ((series_auto && variant_on(h, CA_VAR_SERIES, "CA_SERIES")) || variantx_on(h, CA_VARX_SERIES, "CA_SERIES_ON"));
   if (h->poly) {
@@ -473,16 +475,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
       hipLaunchKernelGGL(k_bias_y, dim3(cdiv(h->ys_N64 * (h->Gp / 16), CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, (uint4*)h->Ys, Nn,
                          h->ys_N64, h->Gp);
     HIPCK(h, hipGetLastError());
-    {
-      // what ONE TF1-Adam step can add to a magnitude: lr_t |m| / sqrt(v) <= lr_t (1 - b1) / sqrt((1 - b2)(1 - b1^2 / b2)) (Cauchy-
-      // Schwarz on the two moving averages), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) maximised over t
-      const double b1 = h->opt.beta1, b2 = h->opt.beta2, lr = h->opt.learning_rate;
-      if (b1 >= 0 && b2 > 0 && b1 * b1 < b2 && b2 < 1 && lr > 0) {
-        double sup = 0.0, p1 = 1.0, p2 = 1.0;
-        for (int t = 1; t <= 200000; ++t) { p1 *= b1; p2 *= b2; sup = std::max(sup, std::sqrt(1.0 - p2) / (1.0 - p1)); }
-        h->ys_step_bound = (float)(1.02 * lr * sup * (1.0 - b1) / std::sqrt((1.0 - b2) * (1.0 - b1 * b1 / b2)));
-      }
-    }
+    if (h->adam_bound > 0) h->ys_step_bound = (float)(1.02 * h->adam_bound);   // (ca_adam_step_bound; none: the quantiser never runs on lagged maxima)
     h->y_ys = true;
     h->y_dev_bytes += h->ys4 ? h->ys_N64 * h->Gp / 2 + 4 * h->n_esc + 4 * ((int64_t)h->ys_nrg * h->ys_nseg * 4 * h->ys_RS + 1) : h->ys_N64 * h->Gp;
   }

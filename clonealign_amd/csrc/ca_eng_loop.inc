@@ -720,8 +720,8 @@ int poly_wait_entry(ca_engine* h, uint64_t want, double out[3]) {
 // up to this point having been the same on all of them.
 struct ca_xsrc { const float* xpart; int nx; const double* xglob; int nglob; double xadd; };
 inline double poly_step_bound(const ca_engine* h) {
-  const double lr = h->opt.learning_rate;
-  return std::max(lr, lr * (1.0 - h->opt.beta1) / std::sqrt(1.0 - h->opt.beta2)) * 1.0001;   // no Adam step moves a variable further (TF1 form, lr_t <= lr / sqrt(1 - beta2) ...)
+  // no Adam step moves a variable further (ca_adam_step_bound: the bound the int8 stream's lagged exponents rest on too; > 0 wherever the series form exists, create_impl)
+  return h->adam_bound * 1.0001;
 }
 int poly_xsrc(ca_engine* h, ca_xsrc* x) {
   memset(x, 0, sizeof(*x));

@@ -59,6 +59,16 @@ struct ca_p2p_wire {   // what travels in a CA_P2P_HANDLE_BYTES handle
 };
 static_assert(sizeof(ca_p2p_wire) <= CA_P2P_HANDLE_BYTES, "handle too small");
 
+// What ONE TF1-Adam step can add to a magnitude, whatever the gradients were: lr_t |m| / (sqrt(v) + eps) <= lr_t (1 - b1) / sqrt((1 - b2)(1 - b1^2 / b2))
+// (Cauchy-Schwarz on the two moving averages: m = (1 - b1) sum b1^i g_i, v = (1 - b2) sum b2^i g_i^2), lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) maximised over t:
+// 0.727 at the defaults.  Gradients that grow by b2 / b1 per step behind a long constant run come arbitrarily close to it; max(lr, lr (1 - b1) /
+// sqrt(1 - b2)) = 0.316 -- constant gradients, or one gradient after none -- is NOT a bound (tests/test_adam_bound_host.py).  < 0: no such bound (b1^2 >= b2).
+inline double ca_adam_step_bound(double lr, double b1, double b2) {
+  if (!(b1 >= 0 && b2 > 0 && b1 * b1 < b2 && b2 < 1 && lr > 0)) return -1.0;
+  double sup = 0.0, p1 = 1.0, p2 = 1.0;
+  for (int t = 1; t <= 200000; ++t) { p1 *= b1; p2 *= b2; sup = std::max(sup, std::sqrt(1.0 - p2) / (1.0 - p1)); }
+  return lr * sup * (1.0 - b1) / std::sqrt((1.0 - b2) * (1.0 - b1 * b1 / b2));
+}
 struct ca_engine {
   // ---- problem
   int64_t N = 0;
@@ -211,6 +221,7 @@ struct ca_engine {
   int ys_ncap = 0, ys_namax[3] = {0, 0, 0};   // pairs a slot can hold / holds (a merged update leaves one pair per gene block and per psi block)
   bool ys_quant_ready = false;   // the images of the CURRENT parameter state were made by the quantiser riding on k_adam_cell
   int ys_slot = 0, ys_steps = -1, ys_RS = 256, ys_nrg = 0, ys_nseg = 0; int64_t ys_N64 = 0; float ys_step_bound = -1.f;
+  double adam_bound = -1.0;      // ca_adam_step_bound of this fit's Adam settings (create_impl); < 0: none holds.  Both look-aheads rest on it: ys_step_bound, poly_step_bound
   // one-shot peer-to-peer all-reduce (ca_p2p_export / ca_p2p_connect)
   ca_p2p* p2p = nullptr;
   // ---- comm

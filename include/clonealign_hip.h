@@ -525,11 +525,15 @@ int ca_set_param(ca_handle h, const char* name, const double* in);
  * and that call's draw.  The loop's passes store the gradients they make in the same buffers, whether or not they step, so after ca_iterate / ca_run they hold:
  *   loc, ls, W, beta, psi      stored by a train pass's update launches only: the gradient the LAST train pass applied -- the state before its Adam step,
  *                              its draw;
- *   gamma_logits               stored by every cell epilogue.  ca_iterate ends on a monitor pass: the state AFTER the last step and that pass's draw (called
- *                              with one draw more than the 2 n it consumes, that pass carries the next call's first forward half: then the carried draw);
+ *   gamma_logits               fused loop (ca_info.fused_sweep = 1: S = 1 up to 16 clones, mc_samples = 2 up to 8; series form or sweeps): stored by every
+ *                              cell epilogue.  ca_iterate ends on a monitor pass: the state AFTER the last step and that pass's draw (called with one draw
+ *                              more than the 2 n it consumes, that pass carries the next call's first forward half: then the carried draw).
+ *                              Plain passes (fused_sweep = 0: mc_samples >= 3, more than 16 clones, 9..16 clones with S >= 2, the fused form switched
+ *                              off): the cell epilogue stores d logits in a TRAIN pass only; a monitor pass leaves them.  After ca_iterate: with the
+ *                              train variables, the state BEFORE the last step and the last train pass's draw;
  *   v, alpha_unconstr          stored by the O(K + C) body of every pass, a monitor pass's tail included (neither depends on the draw): after ca_iterate
  *                              the state AFTER the last step.
- * tests/test_gpu_series_grad.py reads them this way. */
+ * tests/test_gpu_series_grad.py and tests/test_gpu_loop_grad.py read them this way, the latter for every kernel family of the loop. */
 int ca_get_gradient(ca_handle h, const char* name, double* out);
 
 /* A new restart on the same data: what run_clonealign()'s loop (R/clonealign.R:50-56) gets by calling inference_tflow() again --

@@ -296,9 +296,41 @@ def poly_covers(xmax, vlo, vhi, steps, step_bound, consts=None):
     return x * wdt <= 2.0 * c["CA_PL_A"] * c["CA_PL_NB"]
 
 
+def adam_step_bound(lr=0.1, b1=0.9, b2=0.999):
+    """ca_adam_step_bound (ca_eng_state.inc), restated: the Cauchy-Schwarz bound of |m| / sqrt(v) times the supremum over t of the bias correction."""
+    if not (b1 >= 0 and 0 < b2 < 1 and b1 * b1 < b2 and lr > 0):
+        return -1.0
+    sup, p1, p2 = 0.0, 1.0, 1.0
+    for _ in range(200000):
+        p1 *= b1
+        p2 *= b2
+        sup = max(sup, math.sqrt(1.0 - p2) / (1.0 - p1))
+    return lr * sup * (1.0 - b1) / math.sqrt((1.0 - b2) * (1.0 - b1 * b1 / b2))
+
+
+def step_bound_margins():
+    """The factors the engine's two uses put on ca_adam_step_bound, read from the sources: (poly_step_bound's, ca_eng_loop.inc; ys_step_bound's, ca_eng_create.inc).
+    Fails where either use is not written as that one function times a constant."""
+    loop = open(os.path.join(_CSRC, "ca_eng_loop.inc")).read()
+    create = open(os.path.join(_CSRC, "ca_eng_create.inc")).read()
+    body = re.search(r"inline double poly_step_bound\(const ca_engine\* h\) \{(.*?)\n\}", loop, re.S)
+    assert body, "poly_step_bound"
+    mp = re.search(r"return h->adam_bound \* ([0-9.]+);", body.group(1))
+    my = re.search(r"h->ys_step_bound = \(float\)\(([0-9.]+) \* h->adam_bound\)", create)
+    one = re.search(r"h->adam_bound = ca_adam_step_bound\(h->opt\.learning_rate, h->opt\.beta1, h->opt\.beta2\)", create)
+    assert mp and my and one, ("poly_step_bound (ca_eng_loop.inc) / ys_step_bound (ca_eng_create.inc) are no longer written as h->adam_bound times a constant, or "
+                               "adam_bound no longer comes from ca_adam_step_bound: update this restatement and adam_step_bound above to the sources", bool(mp), bool(my), bool(one))
+    return float(mp.group(1)), float(my.group(1))
+
+
 def poly_step_bound(lr=0.1, b1=0.9, b2=0.999):
     """poly_step_bound (ca_eng_loop.inc): no Adam step moves a variable further."""
-    return max(lr, lr * (1.0 - b1) / math.sqrt(1.0 - b2)) * 1.0001
+    return adam_step_bound(lr, b1, b2) * step_bound_margins()[0]
+
+
+def ys_step_bound(lr=0.1, b1=0.9, b2=0.999):
+    """ca_engine::ys_step_bound (ca_eng_create.inc): what the int8 stream's lagged exponents allow per step."""
+    return float(np.float32(adam_step_bound(lr, b1, b2) * step_bound_margins()[1]))
 
 
 def state_for(model_cls, case, st, **kw):
