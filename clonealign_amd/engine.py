@@ -906,6 +906,26 @@ class HipGroupEngine(HipEngine):
         return {f[0]: getattr(i, f[0]) for f in CaInfo._fields_} | {"y_storage_name": YSTORE_NAME[i.y_storage],
                                                                     "transport_name": TRANSPORT_NAME.get(i.transport, "?")}
 
+    def rank_last_gradients(self, rank, names=None):
+        """``HipEngine.last_gradients`` of one rank's engine (ca_get_gradient on the rank handle; read-only, runs nothing): psi and gamma_logits for the rank's
+        own cells, every other variable whole.  Between two group calls no rank thread touches its engine, so the read from the calling thread is safe."""
+        h = C.c_void_p()
+        self._ck(self.lib.ca_group_rank_handle(self.h, int(rank), C.byref(h)))
+        i = CaInfo()
+        rc = self.lib.ca_get_info(h, C.byref(i))
+        if rc != CA_OK:
+            raise EngineError(rc, "ca_get_info")
+        out = {}
+        for name in (names or self.VAR_NAMES):
+            shape = tuple(int(i.N) if (d == 0 and name in ("psi", "gamma_logits")) else s for d, s in enumerate(self._shape(name)))
+            a = np.zeros(shape, dtype=np.float64, order=self._order)
+            if a.size:
+                rc = self.lib.ca_get_gradient(h, name.encode(), a.ctypes.data_as(C.c_void_p))
+                if rc != CA_OK:
+                    raise EngineError(rc, (self.lib.ca_last_error(h) or b"").decode())
+            out[name] = a
+        return out
+
     def info(self):
         return self.rank_info(0) | {"N": self.N, "group": self.group_info()}
 

@@ -533,7 +533,15 @@ int ca_set_param(ca_handle h, const char* name, const double* in);
  *                              train variables, the state BEFORE the last step and the last train pass's draw;
  *   v, alpha_unconstr          stored by the O(K + C) body of every pass, a monitor pass's tail included (neither depends on the draw): after ca_iterate
  *                              the state AFTER the last step.
- * tests/test_gpu_series_grad.py and tests/test_gpu_loop_grad.py read them this way, the latter for every kernel family of the loop. */
+ * A cell-sharded handle (world > 1) holds the same gradients at the same states and draws: loc, ls, W, beta, v, alpha_unconstr are the gradients of the WHOLE fit
+ * (made from the all-reduced sums; bit-identical on every rank), psi and gamma_logits those of the rank's own cells.  Two things differ in how it gets there:
+ *   - with the vector unit's way back (ca_info.bwd_mfma = 0; K = 0 among them) a sharded ca_iterate carries no half from call to call and its train passes are
+ *     plain passes even where fused_sweep = 1; its monitor passes stay fused, so gamma_logits still ends at the state AFTER the last step and the last
+ *     monitor pass's draw;
+ *   - ca_run ends on a plain monitor pass (no next train pass to share a sweep with), which stores no d logits: after ca_run gamma_logits belongs with the
+ *     train variables -- the state before the last step and the last train pass's draw (sharded or not; 9..16 clones and mc_samples = 2 end on a fused pass).
+ * tests/test_gpu_series_grad.py and tests/test_gpu_loop_grad.py read them this way, the latter for every kernel family of the loop; tests/test_gpu_shard_grad.py
+ * for every rank of a sharded fit and, through ca_group_rank_handle, of a device group. */
 int ca_get_gradient(ca_handle h, const char* name, double* out);
 
 /* A new restart on the same data: what run_clonealign()'s loop (R/clonealign.R:50-56) gets by calling inference_tflow() again --
@@ -675,7 +683,7 @@ int ca_group_create_sparse(const ca_problem* problem, const ca_sparse* y, const 
 int ca_group_destroy(ca_group_handle g);
 const char* ca_group_last_error(ca_group_handle g);   /* g may be NULL: the last failed ca_group_create on this thread */
 int ca_group_get_info(ca_group_handle g, ca_group_info* info);
-int ca_group_rank_handle(ca_group_handle g, int32_t rank, ca_handle* h);   /* read-only use (ca_get_info, ca_get_kernel_times ...) */
+int ca_group_rank_handle(ca_group_handle g, int32_t rank, ca_handle* h);   /* read-only use (ca_get_info, ca_get_gradient, ca_get_kernel_times ...), between two group calls */
 /* the one-handle calls, collectively on every rank; eps arguments are shared by the ranks (every rank must see the same draws) */
 int ca_group_init_psi_pca(ca_group_handle g, const double* noise /* N x K, all cells, or NULL */, int32_t n_iter, uint64_t seed, double* pcs_out);
 int ca_group_gamma_init(ca_group_handle g, const float* eps);

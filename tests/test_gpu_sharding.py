@@ -8,29 +8,9 @@ import pytest
 
 from clonealign_amd.sharding import cell_range
 from tests._cases import eps_for, make_case
+from tests._shard_rig import HostAllreduce as _HostAllreduce      # (the rig, shared with tests/test_gpu_shard_grad.py)
 
 pytestmark = pytest.mark.gpu
-
-
-class _HostAllreduce:
-    def __init__(self, world):
-        self.world = world
-        self.bar = threading.Barrier(world)
-        self.slots = [None] * world
-        self.sizes = []
-
-    def make(self, rank):
-        def fn(buf):
-            self.slots[rank] = buf.copy()
-            self.bar.wait()
-            tot = self.slots[0].copy()
-            for r in range(1, self.world):
-                tot += self.slots[r]
-            self.bar.wait()
-            buf[:] = tot
-            if rank == 0:
-                self.sizes.append(len(buf))
-        return fn
 
 
 @pytest.mark.parametrize("kw", [dict(N=301, G=140, C=3, K=1), dict(N=260, G=90, C=4, K=2, P=1, S=2, extra=True)])
