@@ -199,36 +199,42 @@ def compute_ca_fit_mse(fit, Y, L, model_mu=False, random_clones=False, *, seed=N
     return out["mse"]
 
 
+def _ll_inputs(Y, E, U, V, what):
+    """(E, U, V, D, esum) of a log-likelihood host form as float64 after the refusals the library makes (ValueError names the offender)."""
+    E = np.asarray(E, dtype=np.float64)
+    N, G = Y.shape
+    if E.ndim != 2 or E.shape[0] != G:
+        raise ValueError(f"{what}: Y is {N} x {G} but E is {E.shape}")
+    D = 0
+    if (U is None) != (V is None):
+        raise ValueError(f"{what}: U and V go together (both, or neither)")
+    if U is not None:
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"{what}: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = U.shape[1]
+    if D > 8:
+        raise ValueError(f"{what}: D = {D} is outside [0, 8]")
+    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
+    if wrong.size:
+        raise ValueError(f"{what}: expected expression has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
+    esum = E.sum(0)
+    wrong = np.flatnonzero(~np.isfinite(esum) | (esum == 0))
+    if wrong.size:
+        raise ValueError(f"{what}: expected expression of clone {wrong[0]} sums to {esum[wrong[0]]} over the genes")
+    for name, M, row in (("V", V, "gene"), ("U", U, "cell")):
+        if D > 0 and not np.isfinite(M).all():
+            r, d = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"{what}: {name} has a non-finite entry ({row} {r}, factor {d})")
+    return E, U, V, D, esum
+
+
 def _clone_loglik_host(Y, E, U=None, V=None, const=True, chunk=2048):
     """Float64 host form of ``HipEngine.clone_loglik`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time), E
     [G, C], U [N, D] and V [G, D] or both None.  Same return value, same rules (xlogy, the shift by the largest exponent), same refusals (ValueError)."""
     from scipy.special import gammaln
-    E = np.asarray(E, dtype=np.float64)
-    N, G = Y.shape
-    if E.ndim != 2 or E.shape[0] != G:
-        raise ValueError(f"clone_loglik: Y is {N} x {G} but E is {E.shape}")
-    C = E.shape[1]
-    D = 0
-    if (U is None) != (V is None):
-        raise ValueError("clone_loglik: U and V go together (both, or neither)")
-    if U is not None:
-        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
-            raise ValueError(f"clone_loglik: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
-        D = U.shape[1]
-    if D > 8:
-        raise ValueError(f"clone_loglik: D = {D} is outside [0, 8]")
-    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
-    if wrong.size:
-        raise ValueError(f"clone_loglik: expected expression has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
-    esum = E.sum(0)
-    wrong = np.flatnonzero(~np.isfinite(esum) | (esum == 0))
-    if wrong.size:
-        raise ValueError(f"clone_loglik: expected expression of clone {wrong[0]} sums to {esum[wrong[0]]} over the genes")
-    for name, M, row in (("V", V, "gene"), ("U", U, "cell")):
-        if D > 0 and not np.isfinite(M).all():
-            r, d = np.argwhere(~np.isfinite(M))[0]
-            raise ValueError(f"clone_loglik: {name} has a non-finite entry ({row} {r}, factor {d})")
+    E, U, V, D, esum = _ll_inputs(Y, E, U, V, "clone_loglik")
+    N, C = Y.shape[0], E.shape[1]
     zero = E == 0
     logE = np.log(np.where(zero, 1.0, E))                            # xlogy: 0 where E = 0, put right below
     ll = np.empty((N, C))
@@ -345,6 +351,11 @@ def assign_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=N
     probabilities and the label "unassigned"; ``-inf`` in some clones gives probability 0 there."""
     ll = clone_loglik(fit, Y, L, x=x, psi=psi, saturate=saturate, saturation_threshold=saturation_threshold, const=const, engine=engine,
                       engine_opts=engine_opts)
+    return _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability)
+
+
+def _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability):
+    """``assign_cells``' result from the log-likelihood ``ll`` [cells, clones]."""
     N, C = ll.shape
     _L, cn = _parse_cnv(L)
     names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(C)])
@@ -362,6 +373,237 @@ def assign_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=N
     loglik = np.where(np.isneginf(m[:, 0]), -np.inf, lse[:, 0])
     return ClonealignFit(clone_probs=probs, clone=clone_assignment(probs, names, clone_assignment_probability), loglik=loglik, clone_loglik=ll,
                          clone_names=names, ml_params={"clone_probs": probs})
+
+
+def _block_labels(blocks, G):
+    """(block_names, block_of_gene [G] int32) of a length-G sequence of labels (chromosome names, segment ids): blocks in order of first appearance;
+    ``None`` / NaN labels form a last block ``"NA"``."""
+    labels = list(blocks.tolist() if hasattr(blocks, "tolist") else blocks)
+    if len(labels) != G:
+        raise ValueError(f"blocks has {len(labels)} labels but there are {G} genes")
+    index, names, missing = {}, [], []
+    bg = np.empty(G, dtype=np.int32)
+    for g, v in enumerate(labels):
+        if v is None or (isinstance(v, (float, np.floating)) and np.isnan(v)):
+            missing.append(g)
+            continue
+        if v not in index:
+            index[v] = len(names)
+            names.append(v)
+        bg[g] = index[v]
+    if missing:
+        bg[missing] = len(names)
+        names.append("NA")
+    return names, bg
+
+
+def _clone_loglik_by_block_host(Y, E, U, V, block_of_gene, n_blocks, const=True, chunk=2048):
+    """Float64 host form of ``HipEngine.clone_loglik_by_block`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time),
+    E [G, C], U [N, D] and V [G, D] or both None, ``block_of_gene`` [G] in ``[0, n_blocks)``.  Same return value (``{"A" [N, B, C], "logZ" [N, B, C],
+    "s" [N, B], "lg" [N, B] or None}``), same rules (xlogy, the shift by the block's largest exponent, an empty block gives 0, 0, 0 and ``-inf``), same
+    refusals (ValueError)."""
+    from scipy.special import gammaln
+    what = "clone_loglik_by_block"
+    E, U, V, D, _esum = _ll_inputs(Y, E, U, V, what)
+    N, G = Y.shape
+    C, B = E.shape[1], int(n_blocks)
+    if B < 1:
+        raise ValueError(f"{what}: n_blocks = {B} is below 1")
+    bg = np.asarray(block_of_gene).reshape(-1)
+    if bg.shape[0] != G:
+        raise ValueError(f"{what}: block_of_gene has {bg.shape[0]} labels but there are {G} genes")
+    wrong = np.flatnonzero((bg < 0) | (bg >= B))
+    if wrong.size:
+        raise ValueError(f"{what}: block_of_gene[{wrong[0]}] = {bg[wrong[0]]} is outside [0, {B})")
+    genes = [np.flatnonzero(bg == b) for b in range(B)]              # (ascending within a block)
+    zero = E == 0
+    logE = np.log(np.where(zero, 1.0, E))                            # xlogy: 0 where E = 0, put right below
+    A, logZ = np.zeros((N, B, C)), np.full((N, B, C), -np.inf)
+    s, lg = np.zeros((N, B)), (np.zeros((N, B)) if const else None)
+    for lo in range(0, N, int(chunk)):
+        Yc = Y[lo:lo + int(chunk)]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+        hi = lo + Yc.shape[0]
+        eta = U[lo:hi] @ V.T if D > 0 else None
+        for b, idx in enumerate(genes):
+            if idx.size == 0:
+                continue
+            Yb = Yc[:, idx]
+            a = Yb @ logE[idx]
+            if zero[idx].any():
+                a[((Yb > 0).astype(np.float64) @ zero[idx].astype(np.float64)) > 0] = -np.inf
+            with np.errstate(divide="ignore"):
+                if D > 0:
+                    eb = eta[:, idx]
+                    m = eb.max(1)
+                    logZ[lo:hi, b] = m[:, None] + np.log(np.exp(eb - m[:, None]) @ E[idx])
+                    a += (Yb * eb).sum(1)[:, None]
+                else:
+                    logZ[lo:hi, b] = np.log(E[idx].sum(0))[None, :]
+            A[lo:hi, b] = a
+            s[lo:hi, b] = Yb.sum(1)
+            if const:
+                lg[lo:hi, b] = gammaln(Yb + 1.0).sum(1)
+    return {"A": A, "logZ": logZ, "s": s, "lg": lg}
+
+
+def _excluding_each(x, axis, op, empty):
+    """``op`` over all entries of ``axis`` but one, for every one left out, by a prefix and a suffix scan: no difference ``total - x`` is ever formed."""
+    x = np.moveaxis(x, axis, 0)
+    pre, suf = np.full_like(x, empty), np.full_like(x, empty)
+    for b in range(1, x.shape[0]):
+        pre[b] = op(pre[b - 1], x[b - 1])
+        suf[-1 - b] = op(suf[-b], x[-b])
+    return np.moveaxis(op(pre, suf), 0, axis)
+
+
+def _by_block_terms(A, logZ, s, lg):
+    """``within`` [n, B, C], ``between`` [n, C], ``without`` [n, B, C] and ``clone_loglik`` [n, C] from the four sufficient statistics per (cell, block)
+    (``lg`` None: without the multinomial coefficients).  ``s * logZ`` with ``s = 0`` is 0 even where ``logZ = -inf``; where ``A = -inf`` (a positive
+    count against ``E = 0``) the result is ``-inf`` whatever ``logZ`` is, so no ``inf - inf`` is formed; the sums and logsumexps over the other blocks
+    come from prefix / suffix scans, O(n B C)."""
+    from scipy.special import gammaln
+    sb = s[:, :, None]
+
+    def times(cnt, lz):                                              # cnt * lz, 0 where cnt = 0
+        return np.where(cnt > 0, cnt * np.where(cnt > 0, lz, 0.0), 0.0)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        within = np.where(np.isneginf(A), -np.inf, A - times(sb, np.where(np.isneginf(A), 0.0, logZ)))
+        lz_all = np.logaddexp.reduce(logZ, axis=1)                   # [n, C]
+        st = s.sum(1)
+        between = times(sb, logZ - lz_all[:, None, :]).sum(1)
+        a_wo = _excluding_each(A, 1, np.add, 0.0)
+        s_wo = _excluding_each(s, 1, np.add, 0.0)[:, :, None]
+        lz_wo = _excluding_each(logZ, 1, np.logaddexp, -np.inf)
+        without = np.where(np.isneginf(a_wo), -np.inf, a_wo - times(s_wo, np.where(np.isneginf(a_wo), 0.0, lz_wo)))
+        if lg is not None:
+            within = within + (gammaln(s + 1.0) - lg)[:, :, None]
+            between = between + (gammaln(st + 1.0) - gammaln(s + 1.0).sum(1))[:, None]
+            without = without + (gammaln(s_wo[:, :, 0] + 1.0) - _excluding_each(lg, 1, np.add, 0.0))[:, :, None]
+    return {"within": within, "between": between, "without": without, "clone_loglik": within.sum(1) + between}
+
+
+def _by_block_setup(fit, Y, L, blocks, x, psi, saturate, saturation_threshold, engine, engine_opts):
+    """(Y, L, E, U, V, block names, block_of_gene, clone names, engine, whether it is ours) of a by-block call: ``clone_loglik``'s arguments through
+    ``_fit_tables``."""
+    L, cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if L.shape[0] != G:
+        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    block_names, bg = _block_labels(blocks, G)
+    L, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
+    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(L.shape[1])])
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    elif hasattr(engine, "clone_loglik_by_block") and (engine.N, engine.G) != (N, G):
+        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+    return Y, L, E, U, V, block_names, bg, names, engine, own
+
+
+def _by_block_call(engine, Y, E, U, V, bg, B, const, cells):
+    """The result dict of ``clone_loglik_by_block`` but for the names: through the engine's method, or through the host form when it has none."""
+    lo, hi = (0, Y.shape[0]) if cells is None else (int(cells[0]), int(cells[1]))
+    if hasattr(engine, "clone_loglik_by_block"):
+        st = engine.clone_loglik_by_block(E, U, V, bg, B, const=const, cells=(lo, hi))
+    else:
+        if not 0 <= lo <= hi <= Y.shape[0]:
+            raise ValueError(f"clone_loglik_by_block: the cell range [{lo}, {hi}) is outside [0, {Y.shape[0]}]")
+        st = _clone_loglik_by_block_host(Y[lo:hi], E, None if U is None else U[lo:hi], V, bg, B, const=const)
+    out = _by_block_terms(st["A"], st["logZ"], st["s"], st["lg"])
+    out["counts"] = st["s"]
+    return out
+
+
+def clone_loglik_by_block(fit, Y, L, blocks, *, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, cells=None, engine=None,
+                          engine_opts=None):
+    """WHICH PART OF THE GENOME carries a cell's likelihood: ``clone_loglik`` split exactly over a partition of the genes into blocks (chromosomes, arms,
+    copy-number segments).  The multinomial factorises as ``ll[n][c] = sum_b within[n][b][c] + between[n][c]``: ``within`` is the conditional multinomial
+    of block b's counts given their total ("what block b alone says"), ``between`` the multinomial of the block totals ("how the cell's reads are split
+    between blocks"); ``without[n][b][c]`` is the log-likelihood of the cell with block b's genes deleted -- again a multinomial, over the remaining genes.
+    Everything comes from ONE sweep over the resident matrix (``HipEngine.clone_loglik_by_block``; include/clonealign_hip.h has the four sums it returns),
+    not from one engine per block.
+
+    ``blocks``: a length-G sequence of labels; block order is order of first appearance, ``None`` / NaN labels form a last block ``"NA"``.  Any
+    labelling is legal; one whose genes are not sorted by block is only slower.  ``cells`` = ``(lo, hi)`` restricts the call to that range of cells.
+    Every other keyword as for ``clone_loglik``, with the same refusals and the same throwaway-engine rule; an engine without the method gets the chunked
+    float64 host form.
+
+    Returns a dict: ``block_names`` [B], ``counts`` [n, B] (reads per block), ``within`` [n, B, C] (0 where the cell has no reads in b), ``between``
+    [n, C], ``without`` [n, B, C], ``clone_loglik`` [n, C] (``sum_b within + between``: ``clone_loglik``'s value up to rounding).  ``-inf`` exactly where a
+    positive count meets copy number 0 among the genes that enter; no NaN."""
+    Y, _L, E, U, V, block_names, bg, _names, engine, own = _by_block_setup(fit, Y, L, blocks, x, psi, saturate, saturation_threshold, engine, engine_opts)
+    try:
+        out = _by_block_call(engine, Y, E, U, V, bg, len(block_names), const, cells)
+    finally:
+        if own:
+            engine.close()
+    out["block_names"] = block_names
+    return out
+
+
+def _margin(t, cstar):
+    """``t[..., c*] - max_{c != c*} t[..., c]`` along the last axis (``cstar`` [n] indexes the first): ``+inf`` where every rival is ``-inf``, NaN where
+    ``c*`` is too."""
+    idx = cstar.reshape((-1,) + (1,) * (t.ndim - 1))
+    own = np.take_along_axis(t, np.broadcast_to(idx, t.shape[:-1] + (1,)), axis=-1)[..., 0]
+    rivals = np.where(np.arange(t.shape[-1]) == idx, -np.inf, t)
+    with np.errstate(invalid="ignore"):
+        return own - rivals.max(-1)
+
+
+def assignment_support(fit, Y, L, blocks, clone_assignment_probability=0.95, *, extra_loglik=None, x=None, psi=None, saturate=True, saturation_threshold=6,
+                       const=True, cells=None, engine=None, engine_opts=None):
+    """``assign_cells`` with the evidence behind every call, by block of genes: does a call rest on one amplified segment, or is it supported by every
+    segment where the clones differ?  ``blocks`` as for ``clone_loglik_by_block``, every other argument as for ``assign_cells`` (``cells`` = ``(lo, hi)``
+    restricts both to that range; ``extra_loglik`` then has the range's rows).  One upload: a throwaway engine serves both sweeps.
+
+    Returns a :class:`ClonealignFit` that holds everything ``assign_cells`` returns, identically (``clone_probs``, ``clone``, ``loglik``,
+    ``clone_loglik``, ``clone_names``), plus, with ``t = ll + log alpha + extra_loglik`` and ``c*`` its argmax on the full data:
+    ``block_names`` [B]; ``probs_without`` [n, B, C] and ``clone_without`` [n, B]: posterior and label with block b left out; ``margin`` [n]:
+    ``t[c*] - max_{c != c*} t[c]``, the log odds of the call against its best rival; ``margin_without`` [n, B]: the same odds, still for ``c*``, with block
+    b left out -- negative means the call flips without b; ``margin_within`` [n, B]: the same difference of block b's ``within`` term alone (the evidence
+    of b's genes given their total; no prior enters); ``n_flips`` [B]: cells whose argmax changes without b.  Rivals all ``-inf`` give ``+inf``; a cell
+    with every clone ``-inf`` gets NaN margins and is "unassigned".  ``C < 2`` is a ValueError."""
+    Y, L, E, U, V, block_names, bg, _names, engine, own = _by_block_setup(fit, Y, L, blocks, x, psi, saturate, saturation_threshold, engine, engine_opts)
+    try:
+        C = L.shape[1]
+        if C < 2:
+            raise ValueError(f"assignment_support: C = {C} clones: a margin needs at least 2")
+        lo, hi = (0, Y.shape[0]) if cells is None else (int(cells[0]), int(cells[1]))
+        by = _by_block_call(engine, Y, E, U, V, bg, len(block_names), const, (lo, hi))
+        if hasattr(engine, "clone_loglik"):
+            ll = engine.clone_loglik(E, U, V, const=const)[lo:hi]
+        else:
+            ll = _clone_loglik_host(Y[lo:hi], E, None if U is None else U[lo:hi], V, const=const)
+    finally:
+        if own:
+            engine.close()
+    n = ll.shape[0]
+    base = _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability)
+    names = base["clone_names"]
+    alpha = fit["ml_params"].get("alpha")
+    prior = np.zeros((n, C))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if alpha is not None:
+            prior = prior + np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C))
+        if extra_loglik is not None:
+            prior = prior + np.asarray(extra_loglik, dtype=np.float64)
+        t = ll + prior
+        cstar = np.argmax(np.where(np.isnan(t), -np.inf, t), axis=1)
+        tw = by["without"] + prior[:, None, :]
+        m = tw.max(2, keepdims=True)
+        probs_without = np.exp(tw - (m + np.log(np.exp(tw - m).sum(2, keepdims=True))))   # (a row of -inf: NaN, as in assign_cells)
+    B = len(block_names)
+    clone_without = np.stack([clone_assignment(probs_without[:, b], names, clone_assignment_probability) for b in range(B)], axis=1) if B else np.empty((n, 0), dtype=object)
+    alive = ~np.isneginf(t.max(1))
+    flips = (np.argmax(tw, axis=2) != cstar[:, None]) & alive[:, None] & ~np.isneginf(m[:, :, 0])
+    base.update(block_names=block_names, counts=by["counts"], within=by["within"], between=by["between"], without=by["without"],
+                probs_without=probs_without, clone_without=clone_without, margin=_margin(t, cstar), margin_without=_margin(tw, cstar),
+                margin_within=_margin(by["within"], cstar), n_flips=flips.sum(0).astype(np.int64))
+    return base
 
 
 def _pair_list(C):

@@ -639,6 +639,159 @@ int ca_clone_pair_loglik(ca_handle h, const double* E, const double* U, const do
   return clone_ll_impl(h, "ca_clone_pair_loglik", E, U, V, D, with_const, cell_lo, cell_cnt, ll, &pq);
 }
 
+// The sufficient statistics of ca_clone_loglik by block of genes for the resident cells [cell_lo, cell_lo + cell_cnt) (include/clonealign_hip.h has the formulas and
+// the rules; ca_k_blockll.hip.h the kernels).  The table, the masks and the lgamma table are ca_clone_loglik's.  The host turns the labelling into the RUN LIST
+// (maximal ranges of consecutive genes with one label, cut again at the segment boundaries), the chunk list of the contraction (the same ranges cut at every
+// CA_LL_ZCHUNK genes of the axis) and the lists block -> runs, block -> chunks in ascending gene order.  The slab is n_runs x cells x (C + D + 2) doubles, so the
+// cell batch follows from a fixed byte budget: a chromosome-sorted axis (n_runs about n_blocks + nseg) takes the usual batch, a fully interleaved labelling
+// (n_runs = G) small ones; a cell's values do not depend on its batch.  Read-only like ca_clone_loglik; the only collective is the verdict on the input.
+int ca_clone_loglik_by_block(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const int32_t* block_of_gene, int32_t n_blocks,
+                             int64_t c_lo, int64_t c_cnt, double* A, double* logZ, double* s, double* lg) {
+  if (!h) return CA_ERR_INVALID;
+  const std::string pre = "ca_clone_loglik_by_block: ";
+  {
+    const char* null_arg = !E ? "E" : !block_of_gene ? "block_of_gene" : !A ? "A" : !logZ ? "logZ" : !s ? "s" : (with_const && !lg) ? "lg (with_const != 0)" : nullptr;
+    if (null_arg) { h->err = pre + null_arg + " is NULL"; return CA_ERR_INVALID; }
+  }
+  CA_NOT_IN_RUN(h);
+  if (D < 0 || D > CA_LL_DMAX) { h->err = pre + "D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
+  if (D > 0 && (!U || !V)) { h->err = pre + "D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
+  if (n_blocks < 1) { h->err = pre + "n_blocks = " + std::to_string(n_blocks) + " is below 1"; return CA_ERR_INVALID; }
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg, B = n_blocks;
+  for (int g = 0; g < G; ++g)
+    if (block_of_gene[g] < 0 || block_of_gene[g] >= B) {
+      h->err = pre + "block_of_gene[" + std::to_string(g) + "] = " + std::to_string(block_of_gene[g]) + " is outside [0, " + std::to_string(B) + ")";
+      return CA_ERR_INVALID;
+    }
+  HIPCK(h, hipSetDevice(h->device));
+  const int ncol = C + D;
+  const int NC = ncol <= 8 ? 8 : ncol <= 16 ? 16 : 32, ngrp = cdiv(ncol, NC);
+  std::vector<double> tab, logz0;
+  std::vector<unsigned> zmask;
+  std::string bad;
+  if (c_lo < 0 || c_cnt < 0 || c_lo > N || c_cnt > N - c_lo)
+    bad = "the cell range [" + std::to_string(c_lo) + ", " + std::to_string(c_lo) + " + " + std::to_string(c_cnt) + ") is outside [0, " + std::to_string(N) + "]";
+  if (bad.empty()) bad = ll_sweep_table(h, E, V, D, NC, ngrp, tab, zmask, logz0);
+  const int NZ = C <= 8 ? 8 : C <= 16 ? 16 : 32, ngz = cdiv(C, NZ);
+  std::vector<double> Ut, Vt, Ez;
+  if (D > 0 && bad.empty()) {
+    Ut.assign((size_t)N * CA_LL_DMAX, 0.0); Vt.assign((size_t)Gp * CA_LL_DMAX, 0.0); Ez.assign((size_t)ngz * Gp * NZ, 0.0);
+    for (int64_t n = 0; n < N && bad.empty(); ++n)
+      for (int d = 0; d < D; ++d) {
+        const double v = U[hidx(h->layout, n, d, N, D)];
+        if (!std::isfinite(v)) { bad = "U has a non-finite entry (cell " + std::to_string(n) + ", factor " + std::to_string(d) + ")"; break; }
+        Ut[(size_t)n * CA_LL_DMAX + d] = v;
+      }
+    for (int g = 0; g < G; ++g) {
+      for (int d = 0; d < D; ++d) Vt[(size_t)g * CA_LL_DMAX + d] = V[hidx(h->layout, g, d, G, D)];
+      for (int c = 0; c < C; ++c) Ez[((size_t)(c / NZ) * Gp + g) * NZ + c % NZ] = E[hidx(h->layout, g, c, G, C)];
+    }
+  }
+  if (is_sharded(h)) {   // [ranks whose input was refused]
+    std::vector<double> pack{bad.empty() ? 0.0 : 1.0};
+    double* scratch = nullptr;
+    HIPCK(h, hipMalloc((void**)&scratch, sizeof(double)));
+    const int rc = allreduce_host_vec(h, pack, scratch);
+    hipFree(scratch);
+    if (rc != CA_OK) return rc;
+    if (pack[0] != 0.0 && bad.empty()) bad = "another rank refused its input";
+  }
+  if (!bad.empty()) { h->err = pre + bad; return CA_ERR_INVALID; }
+  if (c_cnt == 0) return CA_OK;
+  // the run list and the chunk list: cuts where the label changes, and at the segment boundaries (runs) or at every CA_LL_ZCHUNK genes (chunks)
+  const int segw = 64 * h->VEC;
+  std::vector<int> rcut, rseg((size_t)nseg + 1, 0), zcut, run_blk, zk_blk;
+  for (int g = 0; g < G; ++g) {
+    const bool change = g == 0 || block_of_gene[g] != block_of_gene[g - 1];
+    if (g % segw == 0) rseg[(size_t)(g / segw)] = (int)rcut.size();
+    if (change || g % segw == 0) { rcut.push_back(g); run_blk.push_back(block_of_gene[g]); }
+    if (change || g % CA_LL_ZCHUNK == 0) { zcut.push_back(g); zk_blk.push_back(block_of_gene[g]); }
+  }
+  const int n_runs = (int)rcut.size(), nzk = (int)zcut.size();
+  rseg[(size_t)nseg] = n_runs;
+  rcut.push_back(G); rcut.push_back(INT32_MAX);   // (the kernel reads one entry past the run it has just finished)
+  zcut.push_back(G);
+  // block -> its runs / chunks in ascending gene order (a counting sort keeps the order)
+  auto by_block = [&](const std::vector<int>& blk, std::vector<int>& ptr, std::vector<int>& list) {
+    ptr.assign((size_t)B + 1, 0); list.resize(blk.size());
+    for (int b : blk) ++ptr[(size_t)b + 1];
+    for (int b = 0; b < B; ++b) ptr[(size_t)b + 1] += ptr[(size_t)b];
+    std::vector<int> at(ptr.begin(), ptr.end() - 1);
+    for (size_t i = 0; i < blk.size(); ++i) list[(size_t)at[(size_t)blk[i]]++] = (int)i;
+  };
+  std::vector<int> brp, bruns, bzp, bzk;
+  by_block(run_blk, brp, bruns);
+  by_block(zk_blk, bzp, bzk);
+  // D = 0: log Z of a block does not depend on the cell -- a float64 sum over the block's genes in ascending order, -inf where it is 0 (an empty block included)
+  std::vector<double> logz0b;
+  if (D == 0) {
+    std::vector<double> sum((size_t)B * C, 0.0);
+    for (int g = 0; g < G; ++g)
+      for (int c = 0; c < C; ++c) sum[(size_t)block_of_gene[g] * C + c] += E[hidx(h->layout, g, c, G, C)];
+    logz0b.resize(sum.size());
+    for (size_t i = 0; i < sum.size(); ++i) logz0b[i] = sum[i] > 0.0 ? std::log(sum[i]) : -INFINITY;
+  }
+  std::vector<double> lgt;
+  if (with_const) { lgt.resize(CA_LL_LGTAB); for (int k = 0; k < CA_LL_LGTAB; ++k) lgt[(size_t)k] = std::lgamma((double)k + 1.0); }
+  // cells in batches under the byte budget: the two slabs and the batch's outputs
+  const int64_t BC = (int64_t)B * C;
+  const int64_t per_cell = ((int64_t)n_runs * (ncol + 2) + (D > 0 ? (int64_t)nzk * (C + 1) : 0) + 2 * BC + 2 * B) * (int64_t)sizeof(double);
+  const int64_t NB = std::min<int64_t>(c_cnt, std::max<int64_t>(CA_TB, (CA_BLL_BUDGET / per_cell) / CA_TB * CA_TB));
+  const bool colmaj = h->layout == CA_COL_MAJOR;
+  std::vector<double> tA(colmaj ? (size_t)(c_cnt * BC) : 0), tZ(tA.size()), tS(colmaj ? (size_t)(c_cnt * B) : 0), tL(colmaj && with_const ? tS.size() : 0);
+  double* const hA = colmaj ? tA.data() : A; double* const hZ = colmaj ? tZ.data() : logZ; double* const hS = colmaj ? tS.data() : s;
+  double* const hL = !with_const ? nullptr : colmaj ? tL.data() : lg;   // row-major [c_cnt][...]
+  double *tab_d = nullptr, *lgt_d = nullptr, *lzb_d = nullptr, *Ut_d = nullptr, *Vt_d = nullptr, *Ez_d = nullptr, *part = nullptr, *zpart = nullptr;
+  double *A_d = nullptr, *Z_d = nullptr, *S_d = nullptr, *L_d = nullptr;
+  unsigned* zm_d = nullptr;
+  int *rcut_d = nullptr, *rseg_d = nullptr, *zcut_d = nullptr, *brp_d = nullptr, *bruns_d = nullptr, *bzp_d = nullptr, *bzk_d = nullptr;
+  auto cleanup = [&]() {
+    hipFree(tab_d); hipFree(lgt_d); hipFree(lzb_d); hipFree(Ut_d); hipFree(Vt_d); hipFree(Ez_d); hipFree(part); hipFree(zpart); hipFree(A_d); hipFree(Z_d); hipFree(S_d); hipFree(L_d);
+    hipFree(zm_d); hipFree(rcut_d); hipFree(rseg_d); hipFree(zcut_d); hipFree(brp_d); hipFree(bruns_d); hipFree(bzp_d); hipFree(bzk_d);
+  };
+#define PCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return CA_ERR_HIP; } } while (0)
+#define UP(dst, vec) do { PCK(hipMalloc((void**)&dst, (vec).size() * sizeof((vec)[0]))); PCK(hipMemcpyAsync(dst, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, h->stream)); } while (0)
+  UP(tab_d, tab); UP(zm_d, zmask); UP(rcut_d, rcut); UP(rseg_d, rseg); UP(brp_d, brp); UP(bruns_d, bruns);
+  if (with_const) UP(lgt_d, lgt);
+  if (D > 0) { UP(Ut_d, Ut); UP(Vt_d, Vt); UP(Ez_d, Ez); UP(zcut_d, zcut); UP(bzp_d, bzp); UP(bzk_d, bzk); }
+  else UP(lzb_d, logz0b);
+  PCK(hipMalloc((void**)&part, (size_t)n_runs * (ncol + 2) * NB * sizeof(double)));   // (the columns in use: the padding of the last group is not stored)
+  if (D > 0) PCK(hipMalloc((void**)&zpart, (size_t)nzk * (C + 1) * NB * sizeof(double)));
+  PCK(hipMalloc((void**)&A_d, (size_t)(NB * BC) * sizeof(double)));
+  PCK(hipMalloc((void**)&Z_d, (size_t)(NB * BC) * sizeof(double)));
+  PCK(hipMalloc((void**)&S_d, (size_t)(NB * B) * sizeof(double)));
+  if (with_const) PCK(hipMalloc((void**)&L_d, (size_t)(NB * B) * sizeof(double)));
+  for (int64_t n_lo = c_lo; n_lo < c_lo + c_cnt; n_lo += NB) {
+    const int64_t n_cnt = std::min<int64_t>(NB, c_lo + c_cnt - n_lo);
+    ca_bll_ops o;
+    o.tab = tab_d; o.zmask = zm_d; o.lgtab = lgt_d; o.rcut = rcut_d; o.rseg = rseg_d; o.part = part; o.n_lo = n_lo; o.n_cnt = n_cnt; o.NC = NC; o.ngrp = ngrp; o.nuse = ncol;
+    { const int rc = launch_block_ll(h, o); if (rc != CA_OK) { cleanup(); return rc; } }
+    if (D > 0) {
+      ca_bllz_ops z;
+      z.Ut = Ut_d; z.Vt = Vt_d; z.Ez = Ez_d; z.zcut = zcut_d; z.zpart = zpart; z.n_lo = n_lo; z.n_cnt = n_cnt; z.NC = NZ; z.ngrp = ngz; z.nzk = nzk;
+      { const int rc = launch_block_ll_z(h, z); if (rc != CA_OK) { cleanup(); return rc; } }
+    }
+    hipLaunchKernelGGL(k_block_ll_finish, dim3((unsigned)cdiv(n_cnt * BC, CA_TB)), dim3(CA_TB), 0, h->stream, part, zpart, lzb_d, Ut_d, brp_d, bruns_d, bzp_d, bzk_d, A_d, Z_d, S_d, L_d,
+                       n_lo, n_cnt, (int)B, C, (int)D);
+    PCK(hipGetLastError());
+    const size_t row = (size_t)(n_lo - c_lo);   // (the copies run in stream order: before the next batch overwrites the buffers)
+    PCK(hipMemcpyAsync(hA + row * BC, A_d, (size_t)(n_cnt * BC) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipMemcpyAsync(hZ + row * BC, Z_d, (size_t)(n_cnt * BC) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipMemcpyAsync(hS + row * B, S_d, (size_t)(n_cnt * B) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (with_const) PCK(hipMemcpyAsync(hL + row * B, L_d, (size_t)(n_cnt * B) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  }
+  PCK(hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
+  cleanup();
+#undef UP
+#undef PCK
+  if (colmaj)
+    for (int64_t n = 0; n < c_cnt; ++n) {
+      for (int64_t j = 0; j < BC; ++j) { A[hidx(h->layout, n, j, c_cnt, BC)] = tA[(size_t)(n * BC + j)]; logZ[hidx(h->layout, n, j, c_cnt, BC)] = tZ[(size_t)(n * BC + j)]; }
+      for (int b = 0; b < B; ++b) { s[hidx(h->layout, n, b, c_cnt, B)] = tS[(size_t)(n * B + b)]; if (with_const) lg[hidx(h->layout, n, b, c_cnt, B)] = tL[(size_t)(n * B + b)]; }
+    }
+  return CA_OK;
+}
+
 // Per-cell MAP psi and the clone posterior at it for the resident cells under a fit's gene-level parameters (include/clonealign_hip.h has the algorithm and the
 // rules).  ONE sweep over the matrix (k_clone_ll against [log E | V]: A, B and the constant), then rounds of two launches that never read it, queued back to
 // back; every few rounds the host reads the frozen flags and stops queuing when no cell is left -- freezing is per cell, so WHEN the host looks changes no

@@ -315,6 +315,40 @@ int launch_clone_ll_z(ca_engine* h, const ca_llz_ops& o) {
   if (o.NC == 16) return clone_ll_z_t<16>(h, o);
   return clone_ll_z_t<32>(h, o);
 }
+// ---- k_block_ll<YT, NC> / k_block_ll_z<NC>: the log-likelihood sweep by block of genes and the contraction beside it (ca_clone_loglik_by_block; never the 4-bit loop image) ----
+// one batch of cells [n_lo, n_lo + n_cnt): k_clone_ll's table and masks, the run list (cuts, first run of every segment), the slab part[run][column][cell] of the nuse table columns in use + 2
+struct ca_bll_ops { const double* tab; const unsigned* zmask; const double* lgtab; const int *rcut, *rseg; double* part; int64_t n_lo, n_cnt; int NC, ngrp, nuse; };
+template <typename YT, int NC>
+int block_ll_t(ca_engine* h, const ca_bll_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_block_ll<YT, NC>), dim3((unsigned)((int64_t)cdiv(o.n_cnt, CA_TB) * h->nseg), (unsigned)o.ngrp), dim3(CA_TB), 0, h->stream,
+                                                (const YT*)h->Y, o.tab, o.zmask, o.lgtab, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, h->ovf_col, h->ovf_val, o.rcut, o.rseg, o.part,
+                                                h->N, o.n_lo, o.n_cnt, h->G, h->Gp, h->nseg, o.nuse));
+  return CA_OK;
+}
+template <typename YT>
+int block_ll_nc(ca_engine* h, const ca_bll_ops& o) {
+  if (o.NC == 8) return block_ll_t<YT, 8>(h, o);
+  if (o.NC == 16) return block_ll_t<YT, 16>(h, o);
+  return block_ll_t<YT, 32>(h, o);
+}
+int launch_block_ll(ca_engine* h, const ca_bll_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) return block_ll_nc<uint8_t>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return block_ll_nc<uint16_t>(h, o);
+  return block_ll_nc<float>(h, o);
+}
+// the contraction Z of one batch by chunk (D > 0): NC clone columns per group of the table E, nzk chunks cut at label changes
+struct ca_bllz_ops { const double *Ut, *Vt, *Ez; const int* zcut; double* zpart; int64_t n_lo, n_cnt; int NC, ngrp, nzk; };
+template <int NC>
+int block_ll_z_t(ca_engine* h, const ca_bllz_ops& o) {
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_block_ll_z<NC>), dim3((unsigned)((int64_t)cdiv(o.n_cnt, CA_TB) * o.nzk), (unsigned)o.ngrp), dim3(CA_TB), 0, h->stream, o.Ut, o.Vt,
+                                                o.Ez, o.zcut, o.zpart, o.n_lo, o.n_cnt, h->Gp, o.nzk, h->C));
+  return CA_OK;
+}
+int launch_block_ll_z(ca_engine* h, const ca_bllz_ops& o) {
+  if (o.NC == 8) return block_ll_z_t<8>(h, o);
+  if (o.NC == 16) return block_ll_z_t<16>(h, o);
+  return block_ll_z_t<32>(h, o);
+}
 // ---- k_pair_ll<YT>: the pair-mixture sweep over the resident matrix in its storage (ca_clone_pair_loglik with D > 0; never the 4-bit loop image) ----
 // one batch of cells [n_lo, n_lo + n_cnt): E compact [G][C], the cells' log Z and base sums (k_pair_cell), the weights, the batch's rows of the output [n_cnt][MW]
 struct ca_pll_ops { const double *Ec, *lzc, *base, *wts; double* out; int64_t n_lo, n_cnt; int W, MW; };

@@ -759,6 +759,60 @@ int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double*
   return CA_OK;
 }
 
+int ca_group_clone_loglik_by_block(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const int32_t* block_of_gene,
+                                   int32_t n_blocks, int64_t cell_lo, int64_t cell_cnt, double* A, double* logZ, double* s, double* lg) {
+  GROUP_ALIVE(g);
+  {
+    const char* null_arg = !E ? "E" : !block_of_gene ? "block_of_gene" : !A ? "A" : !logZ ? "logZ" : !s ? "s" : (with_const && !lg) ? "lg (with_const != 0)" : nullptr;
+    if (null_arg) { g->err = std::string("ca_clone_loglik_by_block: ") + null_arg + " is NULL"; return CA_ERR_INVALID; }
+  }
+  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
+    g->err = "ca_clone_loglik_by_block: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
+    return CA_ERR_INVALID;
+  }
+  if (n_blocks < 1) { g->err = "ca_clone_loglik_by_block: n_blocks = " + std::to_string(n_blocks) + " is below 1"; return CA_ERR_INVALID; }   // (it sizes the ranks' outputs)
+  if (cell_lo < 0 || cell_cnt < 0 || cell_lo > g->N || cell_cnt > g->N - cell_lo) {   // (what decides how the range is cut; the ranks refuse everything else in their own words)
+    g->err = "ca_clone_loglik_by_block: the cell range [" + std::to_string(cell_lo) + ", " + std::to_string(cell_lo) + " + " + std::to_string(cell_cnt) + ") is outside [0, " +
+             std::to_string(g->N) + "]";
+    return CA_ERR_INVALID;
+  }
+  const size_t W = (size_t)g->W;
+  const int64_t B = n_blocks, BC = B * g->C;
+  // rank r takes the cells of the range that lie in its shard: [lo[r], hi[r]) in the group's numbering (an empty part is still called: the verdict is collective)
+  std::vector<int64_t> lo(W), hi(W);
+  std::vector<std::vector<double>> us(W), o_a(W), o_z(W), o_s(W), o_l(W);
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t slo = g->shard[r].lo, shi = g->shard[r].hi;
+    lo[r] = std::min(std::max(cell_lo, slo), shi);
+    hi[r] = std::max(std::min(cell_lo + cell_cnt, shi), lo[r]);
+    if (D > 0) slice_rows(U, g->layout, g->N, D, slo, shi, us[r]);
+    o_a[r].resize((size_t)((hi[r] - lo[r]) * BC) + 1);
+    o_z[r].resize((size_t)((hi[r] - lo[r]) * BC) + 1);
+    o_s[r].resize((size_t)((hi[r] - lo[r]) * B) + 1);
+    o_l[r].resize((size_t)((hi[r] - lo[r]) * B) + 1);
+  }
+  const int st = settle(g, dispatch(g, [&](int ri) {
+    const size_t r = (size_t)ri;
+    return ca_clone_loglik_by_block(g->h[r], E, D > 0 ? us[r].data() : nullptr, V, D, with_const, block_of_gene, n_blocks, lo[r] - g->shard[r].lo, hi[r] - lo[r],
+                                    o_a[r].data(), o_z[r].data(), o_s[r].data(), with_const ? o_l[r].data() : nullptr);
+  }), "ca_clone_loglik_by_block");
+  if (st == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  if (st != CA_OK) return st;
+  for (size_t r = 0; r < W; ++r) {
+    scatter_rows(o_a[r].data(), g->layout, cell_cnt, BC, lo[r] - cell_lo, hi[r] - cell_lo, A);
+    scatter_rows(o_z[r].data(), g->layout, cell_cnt, BC, lo[r] - cell_lo, hi[r] - cell_lo, logZ);
+    scatter_rows(o_s[r].data(), g->layout, cell_cnt, B, lo[r] - cell_lo, hi[r] - cell_lo, s);
+    if (with_const) scatter_rows(o_l[r].data(), g->layout, cell_cnt, B, lo[r] - cell_lo, hi[r] - cell_lo, lg);
+  }
+  return CA_OK;
+}
+
 int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X, const double* log_prior, const double* psi_start,
                            int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi, double* ll, double* clone_probs, double* objective,
                            int32_t* rounds, uint8_t* converged) {

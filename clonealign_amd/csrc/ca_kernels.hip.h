@@ -948,6 +948,7 @@ __global__ void __launch_bounds__(CA_TB, (DEPTH == 1 && !C16 && !S2F) ? CA_YS_RI
 #include "ca_fwdbal.hip.h"   // the balanced forward sweep for small problems (round 5)
 #include "ca_k_mse.hip.h"   // the squared error of a fit on the resident matrix (ca_fit_mse): one float64 sweep, gathered by clone
 #include "ca_k_loglik.hip.h"   // per-cell, per-clone log-likelihood of the resident matrix under a fitted model (ca_clone_loglik): one float64 sweep, a lane per cell
+#include "ca_k_blockll.hip.h"   // the log-likelihood's sufficient statistics by block of genes (ca_clone_loglik_by_block): k_clone_ll's walk with a run list, sums stored at run ends
 #include "ca_k_pairll.hip.h"   // log-likelihood under a mixture of two clones (ca_clone_pair_loglik): a wave per cell over its compacted non-zero counts, a lane per (pair, weight)
 #include "ca_k_project.hip.h"  // per-cell MAP psi and clone posterior for cells outside the fit (ca_project_cells): moments over the genes, a lane per cell; never reads Y
 #include "ca_k_simulate.hip.h"   // count rows drawn from a fitted model (ca_simulate_counts): per-cell cumulative weights in LDS, Philox draws, binary search, integer histogram; never reads Y

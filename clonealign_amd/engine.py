@@ -51,6 +51,8 @@ EXPORTS = (
     "ca_project_cells", "ca_group_project_cells",
     # log-likelihood under every mixture of two clones on a weight grid (clone_pair_loglik / detect_doublets), additions to ABI 6
     "ca_clone_pair_loglik", "ca_group_clone_pair_loglik",
+    # the log-likelihood's sufficient statistics by block of genes (clone_loglik_by_block / assignment_support), additions to ABI 6
+    "ca_clone_loglik_by_block", "ca_group_clone_loglik_by_block",
     # count rows drawn from a fitted model (simulate_counts), no handle, additions to ABI 6
     "ca_simulate_counts", "ca_simulate_kernel_ms",
     # log-likelihoods and per-clone gene totals of replicate rows that never leave the device (predictive_stats), no handle, additions to ABI 6
@@ -165,6 +167,8 @@ def load_library(path=None):
     lib.ca_clone_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.ca_clone_pair_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                          C.c_void_p, C.c_void_p]
+    lib.ca_clone_loglik_by_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_simulate_counts.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
@@ -206,6 +210,7 @@ def load_library(path=None):
     lib.ca_group_clone_loglik.argtypes = lib.ca_clone_loglik.argtypes
     lib.ca_group_project_cells.argtypes = lib.ca_project_cells.argtypes
     lib.ca_group_clone_pair_loglik.argtypes = lib.ca_clone_pair_loglik.argtypes
+    lib.ca_group_clone_loglik_by_block.argtypes = lib.ca_clone_loglik_by_block.argtypes
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -729,6 +734,46 @@ class HipEngine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         self._ck(self._fn("clone_pair_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(w), Wn, lo, hi - lo, ptr(ll), ptr(pll)))
         return {"ll": ll, "pair_ll": np.ascontiguousarray(pll).reshape(n, M, Wn), "pairs": pairs}
+
+    def clone_loglik_by_block(self, E, U, V, block_of_gene, n_blocks, const=True, cells=None):
+        """The sufficient statistics of ``clone_loglik`` BY BLOCK OF GENES (chromosomes, arms, copy-number segments), on the device in float64
+        (ca_clone_loglik_by_block; include/clonealign_hip.h has the formulas and the rules).  ``E``, ``U``, ``V`` and ``const`` as for ``clone_loglik``
+        (``U`` covers all resident cells; both None for D = 0); ``block_of_gene`` [G] int in ``[0, n_blocks)`` -- any labelling, interleaved labels are
+        only slower; ``cells`` = ``(lo, hi)`` restricts the call to that range of cells (None: all) -- a cell's values do not depend on the range.
+        Returns ``{"A": [n, B, C], "logZ": [n, B, C], "s": [n, B], "lg": [n, B] (None unless const)}``: per block ``sum xlogy(y, E) + sum y eta``,
+        ``log sum E exp(eta)``, ``sum y`` and ``sum lgamma(y + 1)``.  A positive count against ``E = 0`` gives ``A = -inf`` exactly; an empty block gives
+        ``A = s = lg = 0`` and ``logZ = -inf``; no NaN.  Changes nothing in the engine; two calls agree bit for bit."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"clone_loglik_by_block: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        if (U is None) != (V is None):
+            raise ValueError("clone_loglik_by_block: U and V go together (both, or neither)")
+        D = 0
+        Um = Vm = None
+        if U is not None:
+            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
+                raise ValueError(f"clone_loglik_by_block: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
+            D = int(U.shape[1])
+            if D > 0:
+                Um = np.require(U, requirements=[self._order, "A"])
+                Vm = np.require(V, requirements=[self._order, "A"])
+        bg = np.asarray(block_of_gene)
+        if bg.shape != (self.G,) or bg.dtype.kind not in "iu":
+            raise ValueError(f"clone_loglik_by_block: block_of_gene must be {self.G} integers, got {bg.dtype} {bg.shape}")
+        bg = np.ascontiguousarray(np.clip(bg, -1, 2 ** 31 - 1).astype(np.int32))   # (a label out of range stays out of range: the library names it)
+        B = int(n_blocks)
+        lo, hi = (0, self.N) if cells is None else (int(cells[0]), int(cells[1]))
+        n, Bn, Cn = max(hi - lo, 0), max(B, 0), self.C
+        Em = np.require(E, requirements=[self._order, "A"])
+        A = np.zeros((n, Bn * Cn), dtype=np.float64, order=self._order)
+        logZ = np.zeros((n, Bn * Cn), dtype=np.float64, order=self._order)
+        s = np.zeros((n, Bn), dtype=np.float64, order=self._order)
+        lg = np.zeros((n, Bn), dtype=np.float64, order=self._order) if const else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self._fn("clone_loglik_by_block")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(bg), B, lo, hi - lo, ptr(A), ptr(logZ), ptr(s), ptr(lg)))
+        return {"A": np.ascontiguousarray(A).reshape(n, Bn, Cn), "logZ": np.ascontiguousarray(logZ).reshape(n, Bn, Cn), "s": np.ascontiguousarray(s),
+                "lg": None if lg is None else np.ascontiguousarray(lg)}
 
     def project_cells(self, E, V=None, K=0, X=None, log_prior=None, psi_start=None, const=True, max_iter=25, tol=1e-9, max_step=1.0, poll_every=None):
         """Per-cell MAP ``psi`` of the resident cells under a fit's gene-level parameters and the exact clone posterior at it (ca_project_cells;

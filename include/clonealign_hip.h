@@ -459,6 +459,33 @@ int ca_clone_pair_loglik(ca_handle h, const double* E /* G x C */, const double*
                          int32_t with_const, const double* weights /* n_weights, each in (0, 1) */, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt,
                          double* ll /* cell_cnt x C, or NULL */, double* pair_ll /* cell_cnt x (M n_weights) */);
 
+/* The log-likelihood of ca_clone_loglik BY BLOCK OF GENES (chromosomes, arms, copy-number segments): its four sufficient statistics per cell and block, for the
+ * cells [cell_lo, cell_lo + cell_cnt).  The multinomial factorises exactly over any partition of the genes, ll[n][c] = sum_b within[n][b][c] + between[n][c], and
+ * the likelihood with one block left out is again a multinomial over the remaining genes; both follow from
+ *   A[n][b][c]    = sum_{g in b} xlogy(y_ng, E[g][c]) + sum_{g in b} y_ng eta_ng
+ *   s[n][b]       = sum_{g in b} y_ng
+ *   lg[n][b]      = sum_{g in b} lgamma(y_ng + 1)
+ *   logZ[n][b][c] = log sum_{g in b} E[g][c] exp(eta_ng)
+ * Notation and input rules of ca_clone_loglik (eta_ng = U_n . V_g; U is N x D over ALL resident cells).  block_of_gene[g] in [0, n_blocks) is the gene's block.
+ * A and logZ are cell_cnt x (n_blocks C), column = block * C + clone; s and lg are cell_cnt x n_blocks; all in the problem's layout, row = cell - cell_lo.  Rules:
+ *   a positive count against E = 0 makes that A[n][b][c] exactly -inf, a zero count adds 0; no NaN anywhere.
+ *   logZ is taken under a shift by the block's max of eta (nothing overflows while the result is representable) and is -inf where the sum is 0.
+ *   an empty block (a label no gene carries) gives A = 0, s = 0, lg = 0, logZ = -inf.
+ *   block_of_gene may be ANY labelling: interleaved labels are legal, only slower (the sweep stores its sums at every change of label, and the cells are
+ *     taken in smaller batches).
+ *   Everything is float64, sums run in a fixed order (ascending genes within a block; no atomics): two calls agree bit for bit, and a cell's values depend
+ *     neither on the cell range it was asked in, nor on the engine's internal batching, nor on its place in the launch, so a cell-sharded group returns the
+ *     single handle's bits.
+ * One sweep over the resident matrix in its storage for A, s and lg; logZ never reads it (D > 0: a contraction per block; D = 0: a host table).
+ * CA_ERR_INVALID (with a message naming the offender): everything ca_clone_loglik refuses; n_blocks < 1; a label outside [0, n_blocks); a cell range outside
+ * [0, N]; E, block_of_gene or an output NULL (lg may be NULL only with with_const == 0, and is not written then).
+ * Sharded handle: U, the cell range and the outputs are the local cells'; the only collective is the verdict on the input.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_clone_loglik_by_block(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */, int32_t D,
+                             int32_t with_const, const int32_t* block_of_gene /* G, each in [0, n_blocks) */, int32_t n_blocks, int64_t cell_lo, int64_t cell_cnt,
+                             double* A /* cell_cnt x (n_blocks C) */, double* logZ /* cell_cnt x (n_blocks C) */, double* s /* cell_cnt x n_blocks */,
+                             double* lg /* cell_cnt x n_blocks, or NULL when with_const == 0 */);
+
 /* Project cells onto a fitted model: for every resident cell the MAP value of its latent factor psi_n under the fit's GENE-LEVEL parameters, and the
  * exact clone posterior at it -- the per-cell part of the model for cells the fit never saw (no refit; every cell is independent).  Notation of
  * ca_clone_loglik: E (G x C) = mu L, V = [W | beta] (G x D, D = K + P), U_n = [psi_n | x_n] (the first K columns free, the last P given by X),
@@ -708,6 +735,11 @@ int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U /*
 int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
                                const double* weights, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt, double* ll /* cell_cnt x C, or NULL */,
                                double* pair_ll /* cell_cnt x (M n_weights) */);
+/* ca_clone_loglik_by_block over the group: U holds ALL cells, the cell range counts the group's cells, the outputs hold the range's rows; each cell's values are the
+ * single handle's, bit for bit (every rank is called with its part of the range, an empty one included, for the verdict on the input) */
+int ca_group_clone_loglik_by_block(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
+                                   const int32_t* block_of_gene, int32_t n_blocks, int64_t cell_lo, int64_t cell_cnt, double* A, double* logZ, double* s,
+                                   double* lg /* or NULL when with_const == 0 */);
 /* ca_project_cells over the group: X, log_prior, psi_start and every output hold ALL cells (sliced by the shards); each cell's results are the single handle's, bit for bit */
 int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X /* N x P, all cells, or NULL */,
                            const double* log_prior /* N x C, all cells, or NULL */, const double* psi_start /* N x K, all cells, or NULL */,
