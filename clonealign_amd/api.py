@@ -809,6 +809,229 @@ def detect_doublets(fit, Y, L, doublet_rate=0.05, doublet_probability=0.5, clone
                          weights=grid, ml_params={"clone_probs": clone_probs})
 
 
+DM_DEFAULT_GRID = tuple(10.0 ** np.arange(1.0, 4.75, 0.5))         # 8 concentrations, 10 .. 10^4.5
+
+
+def _dm_concentrations(concentration, what="clone_loglik_dm", limit=16):
+    """The concentrations of a Dirichlet-multinomial call: 1 to 16 finite values > 0 (ValueError names the offender otherwise)."""
+    phi = np.asarray(concentration, dtype=np.float64).reshape(-1)
+    if not 1 <= phi.shape[0] <= limit:
+        raise ValueError(f"{what}: n_conc = {phi.shape[0]} is outside [1, 16]")
+    for i, v in enumerate(phi):
+        if not (np.isfinite(v) and v > 0.0):
+            raise ValueError(f"{what}: concentration {i} is {v}: not finite and > 0")
+        if v > 1e300:
+            raise ValueError(f"{what}: concentration {i} is above 1e300: lgamma of it overflows")
+    return phi
+
+
+def _clone_loglik_dm_host(Y, E, U=None, V=None, concentration=(100.,), const=True, chunk=512, with_scale=False):
+    """Float64 host form of ``HipEngine.clone_loglik_dm`` (numpy and ``scipy.special.gammaln`` over the non-zero counts): Y [N, G] dense or scipy.sparse
+    (densified ``chunk`` cells at a time), E [G, C], U [N, D] and V [G, D] or both None, ``concentration`` as given.  Same return value (``{"ll", "dm_ll"
+    [N, C, n_conc]}``), same rules (zero counts never visited, ``-inf`` exactly where ``a = phi p`` is 0 against a positive count, ``0 + const`` for a
+    cell without counts, no NaN), same refusals (ValueError).  It is the yardstick of the device form and the only CPU route.  ``with_scale`` adds
+    ``"scale"`` [N, C, n_conc]: per entry the sum of the magnitudes that went into it -- ``|gammaln(y + a)| + |gammaln(a)| + 1 + |eta| + |log Z|`` per
+    non-zero count (the relative error of ``a`` enters each term with a factor of about 1), ``|gammaln(phi)| + |gammaln(phi + s)|`` and, with the constant,
+    ``gammaln(s + 1) + sum gammaln(y + 1)`` -- against which the tests bound the rounding error of another evaluation."""
+    from scipy.special import gammaln
+    phi = _dm_concentrations(concentration)
+    ll = _clone_loglik_host(Y, E, U, V, const=const, chunk=max(int(chunk), 1))      # (and its refusals on E, U and V)
+    E = np.asarray(E, dtype=np.float64)
+    N, C = Y.shape[0], E.shape[1]
+    D = 0 if U is None else np.asarray(U).shape[1]
+    if D > 0:
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+    K = phi.shape[0]
+    dm = np.empty((N, C, K))
+    scale = np.empty((N, C, K)) if with_scale else None
+    logz0 = np.log(E.sum(0))
+    for lo in range(0, N, int(chunk)):
+        Yc = Y[lo:lo + int(chunk)]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+        n = Yc.shape[0]
+        s = Yc.sum(1)
+        r, g = np.nonzero(Yc > 0)                                    # the non-zero counts, rows ascending and genes ascending within a row
+        y = Yc[r, g]
+        if D > 0:
+            eta = U[lo:lo + int(chunk)] @ V.T
+            m = eta.max(1)
+            logz = m[:, None] + np.log(np.exp(eta - m[:, None]) @ E)
+            t = np.exp(eta[r, g] - m[r])
+        else:
+            m, logz, t = np.zeros(n), np.broadcast_to(logz0[None, :], (n, C)), np.ones(y.shape[0])
+        head = np.where(s[:, None] > 0, gammaln(phi)[None, :] - gammaln(phi[None, :] + s[:, None]), 0.0)
+        hsc = np.abs(gammaln(phi))[None, :] + np.abs(gammaln(phi[None, :] + s[:, None]))
+        if const:
+            lg = gammaln(Yc + 1.0).sum(1)
+            head = head + (gammaln(s + 1.0) - lg)[:, None]
+            hsc = hsc + (gammaln(s + 1.0) + lg)[:, None]
+        aeta = np.abs(eta[r, g]) if D > 0 else 0.0
+        for c in range(C):
+            a = (np.exp(m - logz[:, c])[r] * E[g, c] * t)[:, None] * phi[None, :]            # phi p, [non-zero counts, K]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                g1, g0 = gammaln(y[:, None] + a), gammaln(a)
+                term = np.where(a > 0, g1 - g0, -np.inf)
+            for k in range(K):
+                dm[lo:lo + n, c, k] = np.bincount(r, weights=term[:, k], minlength=n) + head[:, k]
+            if scale is not None:                                    # the magnitudes of what was added, per entry (the tests' yardstick of rounding)
+                per = np.abs(g1) + np.abs(g0) + (1.0 + aeta + np.abs(logz[r, c]))[:, None]
+                for k in range(K):
+                    scale[lo:lo + n, c, k] = np.bincount(r, weights=per[:, k], minlength=n) + hsc[:, k]
+    return {"ll": ll, "dm_ll": dm} if scale is None else {"ll": ll, "dm_ll": dm, "scale": scale}
+
+
+def _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts):
+    """(Y, L, E, U, V, engine, whether it is ours) of a Dirichlet-multinomial call: ``clone_loglik``'s arguments through ``_fit_tables``."""
+    L, _cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if L.shape[0] != G:
+        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    Ls, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, Ls, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    elif hasattr(engine, "clone_loglik_dm") and (engine.N, engine.G) != (N, G):
+        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+    return Y, E, U, V, engine, own
+
+
+def _dm_call(engine, Y, E, U, V, phi, const):
+    """All cells through the engine's ``clone_loglik_dm``, or through the host form when it has none."""
+    if hasattr(engine, "clone_loglik_dm"):
+        return engine.clone_loglik_dm(E, U, V, concentration=phi, const=const)
+    return _clone_loglik_dm_host(Y, E, U, V, concentration=phi, const=const)
+
+
+def clone_loglik_dm(fit, Y, L, *, concentration, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
+    """DIRICHLET-MULTINOMIAL log-likelihood of the cells of ``Y`` under every clone of a fitted model at every value of ``concentration`` (1 to 16 finite
+    values ``phi`` > 0): ``DirichletMultinomial(total = s_n, alpha = phi * p_n.c).log_prob(y_n)`` with ``p_n.c`` the multinomial probabilities of
+    ``clone_loglik`` -- the same model with overdispersed counts; ``phi -> inf`` gives ``clone_loglik`` back (``HipEngine.clone_loglik_dm``;
+    include/clonealign_hip.h has the formula and the rules).  ``Y``, ``L``, ``x``, ``psi``, ``saturate``, ``const``, ``engine`` and ``engine_opts`` as for
+    ``clone_loglik``.
+
+    Returns ``{"ll" [cells, clones] (clone_loglik's), "dm_ll" [cells, clones, n_conc], "concentration" [n_conc]}``.  An engine without
+    ``clone_loglik_dm`` gets the chunked float64 host form."""
+    phi = _dm_concentrations(concentration)
+    Y, E, U, V, engine, own = _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts)
+    try:
+        out = _dm_call(engine, Y, E, U, V, phi, const)
+    finally:
+        if own:
+            engine.close()
+    out["concentration"] = phi
+    return out
+
+
+def _dm_prior(fit, extra_loglik, N, C):
+    """The [N, C] (or [1, C]) addend ``log alpha + extra_loglik`` of the clone posterior."""
+    alpha = fit["ml_params"].get("alpha")
+    with np.errstate(divide="ignore"):
+        lp = np.zeros((1, C)) if alpha is None else np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C))
+    if extra_loglik is not None:
+        ex = np.asarray(extra_loglik, dtype=np.float64)
+        if ex.shape != (N, C):
+            raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
+        lp = lp + ex
+    return lp
+
+
+def _lse_clones(t):
+    """logsumexp over axis 1 of ``t`` [N, C, ...]; ``-inf`` where every clone is (no NaN)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = t.max(1)
+        return np.where(np.isneginf(m), -np.inf, m + np.log(np.exp(t - np.where(np.isneginf(m), 0.0, m)[:, None]).sum(1)))
+
+
+def _estimate_concentration(fit, engine, Y, E, U, V, grid, refine, extra_loglik, const):
+    """``estimate_concentration`` on a live engine; also returns the log-likelihoods at the chosen concentration (``assign_cells_dm`` reuses them)."""
+    grid = np.unique(_dm_concentrations(DM_DEFAULT_GRID if grid is None else grid, "estimate_concentration", limit=1 << 30))
+    N, C = Y.shape[0], E.shape[1]
+    lp = _dm_prior(fit, extra_loglik, N, C)
+    seen, ll = {}, None                                              # concentration -> (marginal, dm_ll [N, C])
+
+    def visit(values):
+        nonlocal ll
+        for lo in range(0, len(values), 16):                         # (16 concentrations per device call)
+            phi = np.asarray(values[lo:lo + 16], dtype=np.float64)
+            r = _dm_call(engine, Y, E, U, V, phi, const)
+            ll = r["ll"]
+            cell = _lse_clones(r["dm_ll"] + lp[:, :, None])         # [N, n_conc]
+            for k, v in enumerate(phi):
+                seen[float(v)] = (cell[:, k], r["dm_ll"][:, :, k].copy())
+    visit(grid)
+    multi = _lse_clones(ll + lp)
+    live = ~np.isneginf(multi)                                       # a cell that is impossible under every clone says nothing about phi
+
+    def marginal(v):
+        return float(seen[v][0][live].sum())
+    best = max(grid.tolist(), key=marginal)                          # (the first maximum)
+    at_edge = len(grid) > 1 and best in (float(grid[0]), float(grid[-1])) or len(grid) == 1
+    for _ in range(0 if at_edge else int(refine)):
+        vs = sorted(seen)
+        i = vs.index(best)
+        visit(np.geomspace(vs[i - 1], vs[i + 1], 10)[1:-1].tolist())  # 8 log-spaced values between the maximum's two neighbours, one device call
+        best = max(sorted(seen), key=marginal)
+    vs = np.asarray(sorted(seen))
+    return {"concentration": float(best), "grid": vs, "marginal_loglik": np.asarray([marginal(float(v)) for v in vs]),
+            "multinomial_marginal_loglik": float(multi[live].sum()), "at_edge": bool(at_edge), "n_cells_used": int(live.sum())}, seen[best][1], ll
+
+
+def estimate_concentration(fit, Y, L, *, grid=None, refine=2, extra_loglik=None, x=None, psi=None, saturate=True, saturation_threshold=6, const=True,
+                           engine=None, engine_opts=None):
+    """The Dirichlet-multinomial concentration ``phi`` of the cells of ``Y`` under a fitted model, by marginal likelihood over a grid, without refitting:
+    ``M(phi) = sum_n logsumexp_c(log alpha_c + extra_loglik_nc + dm_ll[n, c, phi])`` with ``dm_ll`` of ``clone_loglik_dm`` (same keywords).  ``grid``:
+    the concentrations tried first (default 8 values, ``10 ** arange(1, 4.75, 0.5)``; more than 16 take several device calls); each of ``refine``
+    rounds then makes one more device call on 8 log-spaced values between the two neighbours of the best value so far.
+
+    Returns a dict: ``concentration`` (the arg-max), ``grid`` (every value visited, ascending) and ``marginal_loglik`` (``M`` at each),
+    ``multinomial_marginal_loglik`` (the same sum under ``clone_loglik``: the limit ``phi -> inf``, from the same call), ``at_edge`` -- True when the
+    arg-max of the first grid is its largest value (no detectable overdispersion: the multinomial is adequate) or its smallest; no refinement is made then --
+    and ``n_cells_used`` (cells that are ``-inf`` under every clone are left out of every sum)."""
+    Y, E, U, V, engine, own = _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts)
+    try:
+        return _estimate_concentration(fit, engine, Y, E, U, V, grid, refine, extra_loglik, const)[0]
+    finally:
+        if own:
+            engine.close()
+
+
+def assign_cells_dm(fit, Y, L, concentration="auto", clone_assignment_probability=0.95, *, grid=None, refine=2, extra_loglik=None, x=None, psi=None,
+                    saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
+    """``assign_cells`` under the DIRICHLET-MULTINOMIAL likelihood of ``clone_loglik_dm``: posteriors that allow for the overdispersion of the counts, so
+    that the threshold ``clone_assignment_probability`` rejects what a multinomial over thousands of genes calls certain.  ``concentration``: a value
+    > 0, or ``"auto"`` for ``estimate_concentration`` (``grid``, ``refine``) on the same engine -- the matrix is uploaded once.  Other keywords as for
+    ``assign_cells``.
+
+    Returns everything ``assign_cells`` returns, computed from ``dm_ll`` at the chosen concentration (``clone_loglik`` holds it), plus ``concentration``,
+    ``multinomial_clone_loglik``, ``multinomial_clone_probs`` and ``multinomial_clone`` (``assign_cells``'s own answer, from the same device call),
+    ``n_calls_changed`` (cells whose label differs between the two), ``n_newly_unassigned`` (cells the multinomial assigns and this does not) and, with
+    ``"auto"``, ``concentration_estimate`` (``estimate_concentration``'s dict)."""
+    auto = isinstance(concentration, str)
+    if auto and concentration != "auto":
+        raise ValueError(f"assign_cells_dm: concentration must be a value > 0 or \"auto\", got {concentration!r}")
+    phi = None if auto else _dm_concentrations([concentration], "assign_cells_dm")
+    Yc, E, U, V, engine, own = _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts)
+    try:
+        if auto:
+            est, dm, ll = _estimate_concentration(fit, engine, Yc, E, U, V, grid, refine, extra_loglik, const)
+        else:
+            r = _dm_call(engine, Yc, E, U, V, phi, const)
+            est, dm, ll = None, r["dm_ll"][:, :, 0], r["ll"]
+    finally:
+        if own:
+            engine.close()
+    out = _assign_from_loglik(fit, dm, L, extra_loglik, clone_assignment_probability)
+    multi = _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability)
+    out.update(concentration=est["concentration"] if auto else float(phi[0]), multinomial_clone_loglik=ll, multinomial_clone_probs=multi["clone_probs"],
+               multinomial_clone=multi["clone"], n_calls_changed=int((out["clone"] != multi["clone"]).sum()),
+               n_newly_unassigned=int(((out["clone"] == "unassigned") & (multi["clone"] != "unassigned")).sum()))
+    if auto:
+        out["concentration_estimate"] = est
+    return out
+
+
 def _project_cells_host(Y, E, V, K, P, X, log_prior, psi_start, const=True, max_iter=25, tol=1e-9, max_step=1.0, chunk=2048):
     """Float64 numpy restatement of ``HipEngine.project_cells`` (ca_project_cells; the algorithm is stated in include/clonealign_hip.h), step for step,
     ``chunk`` cells at a time: Y [N, G] dense or scipy.sparse, E [G, C], V = [W | beta] [G, K + P] or None, X [N, P] or None, log_prior [N, C] or None,

@@ -452,12 +452,13 @@ std::string ll_sweep_table(ca_engine* h, const double* E, const double* V, int D
 // the verdict on the input (a non-finite U is local), so that every rank returns the same code instead of one of them leaving the others waiting.
 // ONE body serves ca_clone_loglik and ca_clone_pair_loglik: the pair call runs the same launches over its cell range -- its ll is ca_clone_loglik's bit for bit,
 // and the pair-independent pieces (sum y eta, the lgamma sum, log Z) are those launches' -- and then, per batch, k_pair_cell and k_pair_ll (D > 0) or the
-// table sweep of k_clone_ll with k_pair_tab_finish (D = 0).
+// table sweep of k_clone_ll with k_pair_tab_finish (D = 0).  ca_clone_loglik_dm is a third caller: after the same launches, per batch, k_dm_cell and k_dm_ll (every D).
 extern "C++" {
 namespace {
 struct ca_pair_req { const double* weights; int W; double* pair_ll; };   // the pair part of a call: W weights in (0, 1), the output cell_cnt x (M W)
+struct ca_dm_req { const double* conc; int K; double* dm_ll; };          // the Dirichlet-multinomial part of a call: K concentrations > 0, the output cell_cnt x (C K)
 int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, int64_t c_lo, int64_t c_cnt, double* ll,
-                  const ca_pair_req* pq) {
+                  const ca_pair_req* pq, const ca_dm_req* dq = nullptr) {
   const std::string pre = std::string(who) + ": ";
   if (D < 0 || D > CA_LL_DMAX) { h->err = pre + "D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
   if (D > 0 && (!U || !V)) { h->err = pre + "D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
@@ -472,6 +473,18 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
         h->err = pre + "weight " + std::to_string(i) + " is " + std::to_string(pq->weights[i]) + ": not inside the open interval (0, 1)";
         return CA_ERR_INVALID;
       }
+  }
+  const int K = dq ? dq->K : 0, CK = C * K;
+  double phi_max = 0.0;
+  if (dq) {   // (the same on every rank as well)
+    if (K < 1 || K > CA_DM_KMAX) { h->err = pre + "n_conc = " + std::to_string(K) + " is outside [1, " + std::to_string(CA_DM_KMAX) + "]"; return CA_ERR_INVALID; }
+    if (!dq->conc) { h->err = pre + "conc is NULL"; return CA_ERR_INVALID; }
+    for (int i = 0; i < K; ++i) {
+      const double v = dq->conc[i];
+      if (!std::isfinite(v) || !(v > 0.0)) { h->err = pre + "concentration " + std::to_string(i) + " is " + std::to_string(v) + ": not finite and > 0"; return CA_ERR_INVALID; }
+      if (v > CA_DM_PHI_MAX) { h->err = pre + "concentration " + std::to_string(i) + " is above 1e300: lgamma of it overflows"; return CA_ERR_INVALID; }
+      phi_max = std::max(phi_max, v);
+    }
   }
   HIPCK(h, hipSetDevice(h->device));
   const int MP = C * (C - 1) / 2, MW = MP * W;
@@ -503,13 +516,16 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
   // the pair part's operands: E compact [G][C] for k_pair_ll (D > 0); for D = 0 the table log(A P_ga + B P_gb) of M W columns in groups of NP, its both-zero masks
   // and the slots' shifts lz = min(log Z_a, log Z_b)
   const int NP = MW <= 8 ? 8 : MW <= 16 ? 16 : 32, ngp = pq ? cdiv(MW, NP) : 0, nctp = ngp * NP;
-  std::vector<double> Ec, wts, ptab, slot_lz;
+  std::vector<double> Ec, wts, ptab, slot_lz, cv;   // (cv: the concentrations of a Dirichlet-multinomial call)
+  if (dq) cv.assign(dq->conc, dq->conc + K);
   std::vector<unsigned> pzm;
-  if (pq && bad.empty()) {
-    wts.assign(pq->weights, pq->weights + W);
+  if ((pq || dq) && bad.empty()) {
     Ec.resize((size_t)G * C);
     for (int g = 0; g < G; ++g)
       for (int c = 0; c < C; ++c) Ec[(size_t)g * C + c] = E[hidx(h->layout, g, c, G, C)];
+  }
+  if (pq && bad.empty()) {
+    wts.assign(pq->weights, pq->weights + W);
     if (D == 0) {
       ptab.assign((size_t)ngp * Gp * NP, 0.0); pzm.assign((size_t)ngp * Gp, 0u); slot_lz.assign((size_t)MW, 0.0);
       int j = 0;
@@ -542,14 +558,18 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
   std::vector<double> lgt;
   if (with_const) { lgt.resize(CA_LL_LGTAB); for (int k = 0; k < CA_LL_LGTAB; ++k) lgt[(size_t)k] = std::lgamma((double)k + 1.0); }
   // cells in batches, so that the partial slabs stay below a quarter of a gigabyte (a cell's sums do not depend on its batch)
-  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (D > 0 ? (int64_t)nzc * (nzt + 1) : 0) + (pq ? (int64_t)C + 1 + MW + (D == 0 ? (int64_t)nseg * nctp : 0) : 0)) * (int64_t)sizeof(double);
+  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (D > 0 ? (int64_t)nzc * (nzt + 1) : 0) + (pq ? (int64_t)C + 1 + MW + (D == 0 ? (int64_t)nseg * nctp : 0) : 0) + (dq ? (int64_t)C + 1 + K + CK : 0)) * (int64_t)sizeof(double);
   const int64_t NB = std::min<int64_t>(c_cnt, std::max<int64_t>(CA_TB, (((int64_t)1 << 28) / per_cell) / CA_TB * CA_TB));
-  std::vector<double> out(ll ? (size_t)c_cnt * C : 0), pout(pq && h->layout == CA_COL_MAJOR ? (size_t)c_cnt * MW : 0);
+  std::vector<double> out(ll ? (size_t)c_cnt * C : 0), pout(pq && h->layout == CA_COL_MAJOR ? (size_t)c_cnt * MW : 0),
+                      dout(dq && h->layout == CA_COL_MAJOR ? (size_t)c_cnt * CK : 0);
+  double* const dhost = dq ? (h->layout == CA_COL_MAJOR ? dout.data() : dq->dm_ll) : nullptr;   // row-major [c_cnt][CK]
   double* const phost = pq ? (h->layout == CA_COL_MAJOR ? pout.data() : pq->pair_ll) : nullptr;   // row-major [c_cnt][MW]
   double *tab_d = nullptr, *lgt_d = nullptr, *logz_d = nullptr, *Ut_d = nullptr, *Vt_d = nullptr, *Ez_d = nullptr, *part = nullptr, *lgpart = nullptr, *zpart = nullptr, *mpart = nullptr, *ll_d = nullptr;
   double *Ec_d = nullptr, *wts_d = nullptr, *ptab_d = nullptr, *slz_d = nullptr, *lzc_d = nullptr, *base_d = nullptr, *ppart = nullptr, *pll_d = nullptr;
+  double *conc_d = nullptr, *mrow_d = nullptr, *head_d = nullptr, *dll_d = nullptr;
   unsigned *zm_d = nullptr, *pzm_d = nullptr;
   auto cleanup = [&]() {
+    hipFree(conc_d); hipFree(mrow_d); hipFree(head_d); hipFree(dll_d);
     hipFree(tab_d); hipFree(lgt_d); hipFree(logz_d); hipFree(Ut_d); hipFree(Vt_d); hipFree(Ez_d); hipFree(part); hipFree(lgpart); hipFree(zpart); hipFree(mpart); hipFree(ll_d); hipFree(zm_d);
     hipFree(Ec_d); hipFree(wts_d); hipFree(ptab_d); hipFree(slz_d); hipFree(lzc_d); hipFree(base_d); hipFree(ppart); hipFree(pll_d); hipFree(pzm_d);
   };
@@ -572,6 +592,13 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
     PCK(hipMalloc((void**)&lzc_d, (size_t)NB * C * sizeof(double)));
     PCK(hipMalloc((void**)&base_d, (size_t)NB * sizeof(double)));
     PCK(hipMalloc((void**)&pll_d, (size_t)NB * MW * sizeof(double)));
+  }
+  if (dq) {
+    UP(conc_d, cv); UP(Ec_d, Ec);
+    PCK(hipMalloc((void**)&lzc_d, (size_t)NB * C * sizeof(double)));
+    PCK(hipMalloc((void**)&mrow_d, (size_t)NB * sizeof(double)));
+    PCK(hipMalloc((void**)&head_d, (size_t)NB * K * sizeof(double)));
+    PCK(hipMalloc((void**)&dll_d, (size_t)NB * CK * sizeof(double)));
   }
   for (int64_t n_lo = c_lo; n_lo < c_lo + c_cnt; n_lo += NB) {
     const int64_t n_cnt = std::min<int64_t>(NB, c_lo + c_cnt - n_lo);
@@ -605,6 +632,16 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
       }
       PCK(hipMemcpyAsync(phost + (size_t)(n_lo - c_lo) * MW, pll_d, (size_t)n_cnt * MW * sizeof(double), hipMemcpyDeviceToHost, h->stream));   // (in stream order: before the next batch overwrites it)
     }
+    if (dq) {
+      hipLaunchKernelGGL(k_dm_cell, dim3((unsigned)cdiv(n_cnt * (C + K), CA_TB)), dim3(CA_TB), 0, h->stream, lgpart, zpart, mpart, logz_d, h->s64, conc_d, lzc_d, mrow_d, head_d, n_lo,
+                         n_cnt, C, K, (int)D, (int)nseg, nzc, nzt);
+      PCK(hipGetLastError());
+      ca_dml_ops p;
+      p.Ec = Ec_d; p.lzc = lzc_d; p.mrow = mrow_d; p.head = head_d; p.conc = conc_d; p.Ut = D > 0 ? Ut_d : nullptr; p.Vt = Vt_d; p.out = dll_d; p.n_lo = n_lo; p.n_cnt = n_cnt;
+      p.K = K; p.CK = CK; p.ysmall = phi_max <= CA_DM_PHI_PROD ? CA_DM_YSMALL : 0;
+      { const int rc = launch_dm_ll(h, p); if (rc != CA_OK) { cleanup(); return rc; } }
+      PCK(hipMemcpyAsync(dhost + (size_t)(n_lo - c_lo) * CK, dll_d, (size_t)n_cnt * CK * sizeof(double), hipMemcpyDeviceToHost, h->stream));   // (in stream order: before the next batch overwrites it)
+    }
   }
   if (ll) PCK(hipMemcpyAsync(out.data(), ll_d + (size_t)c_lo * C, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   PCK(hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
@@ -617,6 +654,8 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
   }
   if (pq && h->layout == CA_COL_MAJOR)
     for (int64_t n = 0; n < c_cnt; ++n) for (int j = 0; j < MW; ++j) pq->pair_ll[hidx(h->layout, n, j, c_cnt, MW)] = pout[(size_t)n * MW + j];
+  if (dq && h->layout == CA_COL_MAJOR)
+    for (int64_t n = 0; n < c_cnt; ++n) for (int j = 0; j < CK; ++j) dq->dm_ll[hidx(h->layout, n, j, c_cnt, CK)] = dout[(size_t)n * CK + j];
   return CA_OK;
 }
 }  // namespace
@@ -637,6 +676,18 @@ int ca_clone_pair_loglik(ca_handle h, const double* E, const double* U, const do
   CA_NOT_IN_RUN(h);
   ca_pair_req pq{weights, (int)n_weights, pair_ll};
   return clone_ll_impl(h, "ca_clone_pair_loglik", E, U, V, D, with_const, cell_lo, cell_cnt, ll, &pq);
+}
+
+// The Dirichlet-multinomial log-likelihood of the resident cells [cell_lo, cell_lo + cell_cnt) under every clone at every concentration of the grid (overdispersed
+// cell scoring; include/clonealign_hip.h has the formula and the rules, ca_k_dmll.hip.h the kernel).  Read-only like ca_clone_loglik, whose launches it shares
+// (ll, the lgamma sums, log Z and the max of eta are theirs); the only collective is the verdict on the input.
+int ca_clone_loglik_dm(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const double* conc, int32_t n_conc, int64_t cell_lo,
+                       int64_t cell_cnt, double* ll, double* dm_ll) {
+  if (!h) return CA_ERR_INVALID;
+  if (!E || !conc || !dm_ll) { h->err = std::string("ca_clone_loglik_dm: ") + (!E ? "E" : !conc ? "conc" : "dm_ll") + " is NULL"; return CA_ERR_INVALID; }
+  CA_NOT_IN_RUN(h);
+  ca_dm_req dq{conc, (int)n_conc, dm_ll};
+  return clone_ll_impl(h, "ca_clone_loglik_dm", E, U, V, D, with_const, cell_lo, cell_cnt, ll, nullptr, &dq);
 }
 
 // The sufficient statistics of ca_clone_loglik by block of genes for the resident cells [cell_lo, cell_lo + cell_cnt) (include/clonealign_hip.h has the formulas and

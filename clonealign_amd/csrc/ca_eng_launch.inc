@@ -364,6 +364,22 @@ int launch_pair_ll(ca_engine* h, const ca_pll_ops& o) {
   if (h->ystore == CA_YSTORE_U16) return pair_ll_t<uint16_t>(h, o);
   return pair_ll_t<float>(h, o);
 }
+// ---- k_dm_ll<YT>: the Dirichlet-multinomial sweep over the resident matrix in its storage (ca_clone_loglik_dm, every D; never the 4-bit loop image) ----
+// one batch of cells [n_lo, n_lo + n_cnt): E compact [G][C], the cells' log Z, max of eta and heads (k_dm_cell), the concentrations, the padded factors (null: D = 0),
+// the batch's rows of the output [n_cnt][CK]; ysmall: the largest integer count on the product route (0: none)
+struct ca_dml_ops { const double *Ec, *lzc, *mrow, *head, *conc, *Ut, *Vt; double* out; int64_t n_lo, n_cnt; int K, CK, ysmall; };
+template <typename YT>
+int dm_ll_t(ca_engine* h, const ca_dml_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_dm_ll<YT>), dim3((unsigned)cdiv(o.n_cnt, CA_TB / 64), (unsigned)cdiv(o.CK, 64)), dim3(CA_TB), 0, h->stream, (const YT*)h->Y, o.Ec,
+                                                o.lzc, o.mrow, o.head, o.conc, o.Ut, o.Vt, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, h->ovf_col, h->ovf_val, o.out, o.n_lo, o.n_cnt,
+                                                h->G, h->Gp, h->nseg, h->C, o.K, o.CK, o.ysmall));
+  return CA_OK;
+}
+int launch_dm_ll(ca_engine* h, const ca_dml_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) return dm_ll_t<uint8_t>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return dm_ll_t<uint16_t>(h, o);
+  return dm_ll_t<float>(h, o);
+}
 
 // ---- k_proj_mom<NC, K> / k_proj_step<K>: one round of ca_project_cells on one batch of cells (neither reads the count matrix) ----
 // the moments' operands: U = [psi | x] and V = [W | beta] padded to CA_LL_DMAX factors, E in groups of NC clone columns, the frozen flags, the chunk slabs

@@ -759,6 +759,52 @@ int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double*
   return CA_OK;
 }
 
+int ca_group_clone_loglik_dm(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const double* conc, int32_t n_conc,
+                             int64_t cell_lo, int64_t cell_cnt, double* ll, double* dm_ll) {
+  GROUP_ALIVE(g);
+  if (!E || !conc || !dm_ll) { g->err = std::string("ca_clone_loglik_dm: ") + (!E ? "E" : !conc ? "conc" : "dm_ll") + " is NULL"; return CA_ERR_INVALID; }
+  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
+    g->err = "ca_clone_loglik_dm: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
+    return CA_ERR_INVALID;
+  }
+  if (cell_lo < 0 || cell_cnt < 0 || cell_lo > g->N || cell_cnt > g->N - cell_lo) {   // (what decides how the range is cut; the ranks refuse everything else in their own words)
+    g->err = "ca_clone_loglik_dm: the cell range [" + std::to_string(cell_lo) + ", " + std::to_string(cell_lo) + " + " + std::to_string(cell_cnt) + ") is outside [0, " +
+             std::to_string(g->N) + "]";
+    return CA_ERR_INVALID;
+  }
+  const size_t W = (size_t)g->W;
+  const int64_t CK = (int64_t)g->C * std::max<int64_t>(0, std::min<int64_t>(n_conc, 16));
+  // rank r takes the cells of the range that lie in its shard: [lo[r], hi[r]) in the group's numbering (an empty part is still called: the verdict is collective)
+  std::vector<int64_t> lo(W), hi(W);
+  std::vector<std::vector<double>> us(W), o_ll(W), o_dm(W);
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t slo = g->shard[r].lo, shi = g->shard[r].hi;
+    lo[r] = std::min(std::max(cell_lo, slo), shi);
+    hi[r] = std::max(std::min(cell_lo + cell_cnt, shi), lo[r]);
+    if (D > 0) slice_rows(U, g->layout, g->N, D, slo, shi, us[r]);
+    if (ll) o_ll[r].resize((size_t)((hi[r] - lo[r]) * g->C) + 1);
+    o_dm[r].resize((size_t)((hi[r] - lo[r]) * CK) + 1);
+  }
+  const int s = settle(g, dispatch(g, [&](int ri) {
+    const size_t r = (size_t)ri;
+    return ca_clone_loglik_dm(g->h[r], E, D > 0 ? us[r].data() : nullptr, V, D, with_const, conc, n_conc, lo[r] - g->shard[r].lo, hi[r] - lo[r],
+                              ll ? o_ll[r].data() : nullptr, o_dm[r].data());
+  }), "ca_clone_loglik_dm");
+  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  if (s != CA_OK) return s;
+  for (size_t r = 0; r < W; ++r) {
+    if (ll) scatter_rows(o_ll[r].data(), g->layout, cell_cnt, g->C, lo[r] - cell_lo, hi[r] - cell_lo, ll);
+    scatter_rows(o_dm[r].data(), g->layout, cell_cnt, CK, lo[r] - cell_lo, hi[r] - cell_lo, dm_ll);
+  }
+  return CA_OK;
+}
+
 int ca_group_clone_loglik_by_block(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const int32_t* block_of_gene,
                                    int32_t n_blocks, int64_t cell_lo, int64_t cell_cnt, double* A, double* logZ, double* s, double* lg) {
   GROUP_ALIVE(g);

@@ -51,6 +51,8 @@ EXPORTS = (
     "ca_project_cells", "ca_group_project_cells",
     # log-likelihood under every mixture of two clones on a weight grid (clone_pair_loglik / detect_doublets), additions to ABI 6
     "ca_clone_pair_loglik", "ca_group_clone_pair_loglik",
+    # Dirichlet-multinomial log-likelihood per clone on a grid of concentrations (clone_loglik_dm / estimate_concentration / assign_cells_dm), additions to ABI 6
+    "ca_clone_loglik_dm", "ca_group_clone_loglik_dm",
     # the log-likelihood's sufficient statistics by block of genes (clone_loglik_by_block / assignment_support), additions to ABI 6
     "ca_clone_loglik_by_block", "ca_group_clone_loglik_by_block",
     # count rows drawn from a fitted model (simulate_counts), no handle, additions to ABI 6
@@ -167,6 +169,7 @@ def load_library(path=None):
     lib.ca_clone_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     lib.ca_clone_pair_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                          C.c_void_p, C.c_void_p]
+    lib.ca_clone_loglik_dm.argtypes = lib.ca_clone_pair_loglik.argtypes
     lib.ca_clone_loglik_by_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
@@ -211,6 +214,7 @@ def load_library(path=None):
     lib.ca_group_project_cells.argtypes = lib.ca_project_cells.argtypes
     lib.ca_group_clone_pair_loglik.argtypes = lib.ca_clone_pair_loglik.argtypes
     lib.ca_group_clone_loglik_by_block.argtypes = lib.ca_clone_loglik_by_block.argtypes
+    lib.ca_group_clone_loglik_dm.argtypes = lib.ca_clone_loglik_dm.argtypes
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -734,6 +738,40 @@ class HipEngine:
         ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         self._ck(self._fn("clone_pair_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(w), Wn, lo, hi - lo, ptr(ll), ptr(pll)))
         return {"ll": ll, "pair_ll": np.ascontiguousarray(pll).reshape(n, M, Wn), "pairs": pairs}
+
+    def clone_loglik_dm(self, E, U=None, V=None, concentration=(100.,), const=True, cells=None, want_ll=True):
+        """DIRICHLET-MULTINOMIAL log-likelihood of the resident cells under every clone at every concentration ``phi`` of ``concentration`` (1 to 16 finite
+        values > 0), on the device in float64 (ca_clone_loglik_dm; include/clonealign_hip.h has the formula and the rules):
+        ``DirichletMultinomial(total = s_n, alpha = phi * p_n.c).log_prob(y_n)`` with ``p_n.c ~ E[:, c] * exp(U[n] @ V.T)`` -- ``clone_loglik``'s
+        multinomial with overdispersion; ``phi -> inf`` gives it back.  ``E``, ``U``, ``V`` and ``const`` as for ``clone_loglik`` (``U`` covers all resident
+        cells); ``cells`` = ``(lo, hi)`` restricts the call to that range of cells (None: all) -- a cell's values do not depend on the range.  Returns
+        ``{"ll": [n, C] (clone_loglik's rows, bit for bit; None unless want_ll), "dm_ll": [n, C, n_conc]}``.  A positive count against ``E = 0`` gives
+        exactly ``-inf``; no NaN.  Changes nothing in the engine; two calls agree bit for bit."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"clone_loglik_dm: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        if (U is None) != (V is None):
+            raise ValueError("clone_loglik_dm: U and V go together (both, or neither)")
+        D = 0
+        Um = Vm = None
+        if U is not None:
+            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
+                raise ValueError(f"clone_loglik_dm: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
+            D = int(U.shape[1])
+            if D > 0:
+                Um = np.require(U, requirements=[self._order, "A"])
+                Vm = np.require(V, requirements=[self._order, "A"])
+        lo, hi = (0, self.N) if cells is None else (int(cells[0]), int(cells[1]))
+        n = max(hi - lo, 0)
+        phi = np.ascontiguousarray(np.asarray(concentration, dtype=np.float64).reshape(-1))
+        Kn, Cn = int(phi.shape[0]), self.C
+        Em = np.require(E, requirements=[self._order, "A"])
+        ll = np.zeros((n, Cn), dtype=np.float64, order=self._order) if want_ll else None
+        dm = np.zeros((n, Cn * min(Kn, 16)), dtype=np.float64, order=self._order)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        self._ck(self._fn("clone_loglik_dm")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(phi), Kn, lo, hi - lo, ptr(ll), ptr(dm)))
+        return {"ll": ll, "dm_ll": np.ascontiguousarray(dm).reshape(n, Cn, Kn)}
 
     def clone_loglik_by_block(self, E, U, V, block_of_gene, n_blocks, const=True, cells=None):
         """The sufficient statistics of ``clone_loglik`` BY BLOCK OF GENES (chromosomes, arms, copy-number segments), on the device in float64

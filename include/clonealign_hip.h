@@ -459,6 +459,31 @@ int ca_clone_pair_loglik(ca_handle h, const double* E /* G x C */, const double*
                          int32_t with_const, const double* weights /* n_weights, each in (0, 1) */, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt,
                          double* ll /* cell_cnt x C, or NULL */, double* pair_ll /* cell_cnt x (M n_weights) */);
 
+/* DIRICHLET-MULTINOMIAL log-likelihood of the resident counts under every clone at a grid of concentrations, for the cells [cell_lo, cell_lo + cell_cnt):
+ * scoring that allows for the overdispersion of the counts relative to ca_clone_loglik's multinomial.  Notation and arguments of ca_clone_loglik: E (G x C),
+ * eta_ng = U_n . V_g, Z_nc = sum_g E[g][c] exp(eta_ng), s_n = sum_g y_ng, p_ngc = E[g][c] exp(eta_ng) / Z_nc; U is N x D over ALL resident cells.  For a
+ * concentration phi_k > 0, with a_ngc = phi_k p_ngc:
+ *   dm_ll[n][c][k] = lgamma(phi_k) - lgamma(phi_k + s_n) + sum_{g: y_ng > 0} [ lgamma(y_ng + a_ngc) - lgamma(a_ngc) ] + const_n
+ * with const_n as in ca_clone_loglik, i.e. DirichletMultinomial(total = s_n, alpha = phi_k p_n.c).log_prob(y_n).  As phi -> inf it tends to ca_clone_loglik's
+ * value; for a cell with one read it is log p_ngc at every phi.  dm_ll is cell_cnt x (C n_conc) in the problem's layout, column = clone * n_conc + k,
+ * row = cell - cell_lo.  ll (cell_cnt x C, or NULL): ca_clone_loglik's rows of those cells, bit for bit.  Rules:
+ *   a zero count adds nothing and is never visited; a positive count against E[g][c] = 0 makes that entry exactly -inf; no NaN anywhere; a cell with s_n = 0
+ *     gets 0 + const_n.  An a_ngc that UNDERFLOWS to 0 although E > 0 (an exponent far below the cell's largest, or a vanishing share of E) is treated like E = 0.
+ *   log Z_nc is ca_clone_loglik's, under the max_g eta_ng shift m_n, and is not computed a second time; the coefficient phi_k exp(m_n - log Z_nc) of a
+ *     (clone, concentration) is formed once per cell and is at most phi_k, exp(eta_ng - m_n) at most 1: nothing overflows.
+ *   counts may be non-integer (f32 storage) and as large as the storage allows.  An integer count y <= 8 is evaluated as log prod_{j < y} (a + j) while every
+ *     concentration is at most 2^100 (the product of 8 factors below 2^101 cannot overflow); every other count by two lgamma.
+ *   Everything is float64, one transcendental per (cell, non-zero count, clone, concentration), a wave per cell over its non-zero counts in ascending gene
+ *     order, a lane per (clone, concentration); sums run in a fixed order (no atomics): two calls agree bit for bit, and a cell's values depend neither on the
+ *     cell range it was asked in, nor on the batching, nor on its place in the launch, so a cell-sharded group returns the single handle's bits.
+ * CA_ERR_INVALID (with a message naming the offender): everything ca_clone_loglik refuses; n_conc outside [1, 16]; a concentration that is non-finite or <= 0
+ * (or above 1e300, where lgamma of it overflows); a cell range outside [0, N]; E, conc or dm_ll NULL.
+ * Sharded handle: U, the cell range and the outputs are the local cells'; the only collective is the verdict on the input.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_clone_loglik_dm(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */, int32_t D,
+                       int32_t with_const, const double* conc /* n_conc, each finite and > 0 */, int32_t n_conc, int64_t cell_lo, int64_t cell_cnt,
+                       double* ll /* cell_cnt x C, or NULL */, double* dm_ll /* cell_cnt x (C n_conc), column = clone * n_conc + k */);
+
 /* The log-likelihood of ca_clone_loglik BY BLOCK OF GENES (chromosomes, arms, copy-number segments): its four sufficient statistics per cell and block, for the
  * cells [cell_lo, cell_lo + cell_cnt).  The multinomial factorises exactly over any partition of the genes, ll[n][c] = sum_b within[n][b][c] + between[n][c], and
  * the likelihood with one block left out is again a multinomial over the remaining genes; both follow from
@@ -735,6 +760,11 @@ int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U /*
 int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
                                const double* weights, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt, double* ll /* cell_cnt x C, or NULL */,
                                double* pair_ll /* cell_cnt x (M n_weights) */);
+/* ca_clone_loglik_dm over the group: U holds ALL cells, the cell range counts the group's cells, ll and dm_ll hold the range's rows; each cell's values are the
+ * single handle's, bit for bit (every rank is called with its part of the range, an empty one included, for the verdict on the input) */
+int ca_group_clone_loglik_dm(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
+                             const double* conc, int32_t n_conc, int64_t cell_lo, int64_t cell_cnt, double* ll /* cell_cnt x C, or NULL */,
+                             double* dm_ll /* cell_cnt x (C n_conc) */);
 /* ca_clone_loglik_by_block over the group: U holds ALL cells, the cell range counts the group's cells, the outputs hold the range's rows; each cell's values are the
  * single handle's, bit for bit (every rank is called with its part of the range, an empty one included, for the verdict on the input) */
 int ca_group_clone_loglik_by_block(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
