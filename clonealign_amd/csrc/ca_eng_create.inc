@@ -44,6 +44,41 @@ inline bool ca_mom_last_pick(const ca_mom_last_in& a) {
   return CA_ML_STREAM_FIXED_US + (double)a.image_bytes / CA_ML_STREAM_BYTES_PER_US >= CA_ML_MIN_STREAM_US;
 }
 
+// ---- CA_VAR_Y2: the host's share of the 2-bit / 4-bit image (ca_ymfma.hip.h) -- a pure function of the per-gene counts k_y2_hist leaves (ca_y2_plan in the C ABI) --------
+// Per 512-gene segment the genes sorted by their stored counts >= 3, ascending, ties by gene index (padded genes count 0); the list of N2 narrow blocks holds the
+// counts >= 3 of the genes in them and the counts >= 15 of the others.  N2 without force: the larger of 6 and 5 (the values the stream is instantiated for) whose
+// list is at most 1 in 256 of the matrix's counts -- the 4-bit image's budget --, else 0.
+constexpr int CA_Y2_NS[2] = {6, 5};
+// the matrix size (padded counts N64 x Gp) from which the image is picked: between 25k x 5k (1.28e8), where the forced image gains 1.5 us per iteration of 64 -- about
+// the spread of a run --, and 50k x 5k (2.56e8), where it gains 4.5 of 81; 100k x 5k gains 8.8 of 109.7 (profiles/r18_y2_ab.txt)
+constexpr double CA_Y2_MIN_COUNTS = 2.0e8;
+inline int ca_y2_plan_impl(const int32_t* cnt3, const int32_t* cnt15, int Gp, int64_t counts, int force_n2, uint16_t* perm, uint16_t* pos, int64_t* n_esc) {
+  const int nseg = Gp / CA_YS_GW;
+  int64_t e15 = 0, e3[CA_YS_GW / 64 + 1];   // e3[b]: what the list grows by when blocks 0 .. b-1 are narrow
+  for (int b = 0; b <= CA_YS_GW / 64; ++b) e3[b] = 0;
+  std::vector<int> idx(CA_YS_GW);
+  for (int s = 0; s < nseg; ++s) {
+    const int32_t* c3 = cnt3 + (size_t)s * CA_YS_GW;
+    const int32_t* c15 = cnt15 + (size_t)s * CA_YS_GW;
+    for (int i = 0; i < CA_YS_GW; ++i) idx[i] = i;
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return c3[a] < c3[b]; });
+    for (int i = 0; i < CA_YS_GW; ++i) {
+      perm[(size_t)s * CA_YS_GW + i] = (uint16_t)idx[i];
+      pos[(size_t)s * CA_YS_GW + idx[i]] = (uint16_t)i;
+      e15 += c15[idx[i]];
+      e3[i / 64 + 1] += (int64_t)c3[idx[i]] - c15[idx[i]];
+    }
+  }
+  for (int b = 1; b <= CA_YS_GW / 64; ++b) e3[b] += e3[b - 1];
+  int n2 = 0;
+  if (force_n2 > 0) n2 = force_n2 < CA_YS_GW / 64 ? force_n2 : CA_YS_GW / 64 - 1;
+  else
+    for (int k = 0; k < 2 && n2 == 0; ++k)
+      if ((e15 + e3[CA_Y2_NS[k]]) * 256 <= counts) n2 = CA_Y2_NS[k];
+  *n_esc = e15 + e3[n2];
+  return n2;
+}
+
 int create_impl(ca_engine* h, const ca_problem* p) {
   const int N = (int)h->N; (void)N;
   HIPCK(h, hipSetDevice(h->device));
@@ -428,7 +463,7 @@ int create_impl(ca_engine* h, const ca_problem* p) {
     // forms keep the 1-byte body) and where the escape list (stored counts >= 15) is at most 1 in 256 counts -- the shapes measured, at about
     // 1 in 370 (profiles/r07_*); CA_VARX_Y4 forces it at any shape and fraction.  A deterministic function of the shape and the matrix (int
     // offsets: below 2^31 counts)
-    const bool y4_force = variantx_on(h, CA_VARX_Y4, "CA_Y4_ON");
+    const bool y4_force = variantx_on(h, CA_VARX_Y4, "CA_Y4_ON") || variantx_on(h, CA_VARX_Y2, "CA_Y2_ON");   // (a forced 2-bit / 4-bit image needs the 4-bit one beside it)
     if (variant_on(h, CA_VAR_Y4, "CA_Y4") && (h->poly || y4_force) && (double)Nn * (double)h->Gp < 2.0e9) {
       const int64_t nkeys = (int64_t)h->ys_nrg * h->ys_nseg * 4 * h->ys_RS;
       CACK(dalloc(h, &h->esc_off, nkeys + 1));
@@ -475,6 +510,51 @@ int create_impl(ca_engine* h, const ca_problem* p) {
       hipLaunchKernelGGL(k_bias_y, dim3(cdiv(h->ys_N64 * (h->Gp / 16), CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, (uint4*)h->Ys, Nn,
                          h->ys_N64, h->Gp);
     HIPCK(h, hipGetLastError());
+    // the 2-bit / 4-bit image beside the 4-bit one (CA_VAR_Y2), for the series form's own stream launch: from the resident u8 matrix, whatever the ingest was
+    if (h->ys4 && h->poly && variant_on(h, CA_VAR_Y2, "CA_Y2")) {
+      const bool y2_force = variantx_on(h, CA_VARX_Y2, "CA_Y2_ON");
+      const int lab_n2 = (h->opt.reserved[0] >> 8) & 15;   // (ca_options.reserved[0], bits 8 up, lab: N2 of a forced image, 5 or 6)
+      if (y2_force || (double)h->ys_N64 * (double)h->Gp >= CA_Y2_MIN_COUNTS) {
+        int* hist = nullptr;
+        CACK(dalloc(h, &hist, 2 * (int64_t)h->Gp));
+        hipLaunchKernelGGL(k_y2_hist, dim3(cdiv(h->Gp / 4, CA_YM_TB), (unsigned)cdiv(Nn, 64)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, Nn, h->Gp, hist);
+        HIPCK(h, hipGetLastError());
+        std::vector<int32_t> hc(2 * (size_t)h->Gp);
+        HIPCK(h, hipMemcpyAsync(hc.data(), hist, hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        SYNC(h);
+        std::vector<uint16_t> perm(h->Gp), pos(h->Gp);
+        int64_t ne = 0;
+        const int n2 = ca_y2_plan_impl(hc.data(), hc.data() + h->Gp, h->Gp, Nn * (int64_t)h->G, y2_force ? (lab_n2 == 5 || lab_n2 == 6 ? lab_n2 : 6) : 0, perm.data(), pos.data(), &ne);
+        if (n2 > 0 && ne < ((int64_t)1 << 31)) {
+          CACK(dalloc(h, &h->y2_perm, (int64_t)h->Gp));
+          CACK(dalloc(h, &h->y2_pos, (int64_t)h->Gp));
+          HIPCK(h, hipMemcpyAsync(h->y2_perm, perm.data(), (size_t)h->Gp * 2, hipMemcpyHostToDevice, h->stream));
+          HIPCK(h, hipMemcpyAsync(h->y2_pos, pos.data(), (size_t)h->Gp * 2, hipMemcpyHostToDevice, h->stream));
+          const int64_t nkeys = (int64_t)h->ys_nrg * h->ys_nseg * 4 * h->ys_RS, nw = Nn * h->ys_nseg;
+          CACK(dalloc(h, &h->esc2_off, nkeys + 1));
+          hipLaunchKernelGGL(k_esc_count, dim3(cdiv(nw * 64, CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, Nn, h->Gp, h->ys_nseg, h->ys_RS,
+                             h->esc2_off, (const uint4*)h->y2_pos, n2);
+          hipLaunchKernelGGL(k_esc_scan, dim3(1), dim3(1024), 0, h->stream, h->esc2_off, nkeys);
+          HIPCK(h, hipGetLastError());
+          int total = 0;
+          HIPCK(h, hipMemcpyAsync(&total, h->esc2_off + nkeys, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+          SYNC(h);
+          if ((int64_t)total != ne) { h->err = "2-bit image: the device's escape count differs from the host plan's"; return CA_ERR_STATE; }
+          h->n_esc2 = total;
+          CACK(dalloc(h, &h->esc2, h->n_esc2));
+          hipLaunchKernelGGL(k_esc_fill, dim3(cdiv(nw * 64, CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, Nn, h->Gp, h->ys_nseg, h->ys_RS,
+                             h->esc2_off, h->esc2, (const uint4*)h->y2_pos, n2);
+          const int64_t sb = n2 * 1024 + (8 - n2) * 2048, ib = (h->ys_N64 / 64) * h->ys_nseg * sb;
+          CACK(dalloc(h, &h->Ys2, ib));
+          hipLaunchKernelGGL(k_pack_y2, dim3(cdiv(ib / 16, CA_YM_TB)), dim3(CA_YM_TB), 0, h->stream, (const uint8_t*)h->Y, (uint4*)h->Ys2, Nn, h->ys_N64, h->Gp, n2,
+                             h->y2_perm);
+          HIPCK(h, hipGetLastError());
+          SYNC(h);   // (the host's vectors were the copies' sources)
+          h->ys_n2 = n2;
+          h->y_dev_bytes += ib + 4 * h->n_esc2 + 4 * (nkeys + 1) + 4 * (int64_t)h->Gp;
+        }
+      }
+    }
     if (h->adam_bound > 0) h->ys_step_bound = (float)(1.02 * h->adam_bound);   // (ca_adam_step_bound; none: the quantiser never runs on lagged maxima)
     h->y_ys = true;
     h->y_dev_bytes += h->ys4 ? h->ys_N64 * h->Gp / 2 + 4 * h->n_esc + 4 * ((int64_t)h->ys_nrg * h->ys_nseg * 4 * h->ys_RS + 1) : h->ys_N64 * h->Gp;

@@ -122,6 +122,7 @@ ca_ys_io ys_io(ca_engine* h) {
   io.Wr = h->Wr; io.Pr = h->Pr; io.Wsum = h->Wsum; io.Psum = h->Psum; io.exps = h->ys_exps + 2 * h->ys_slot;
   io.YWpart = h->YWpart; io.YTpart = h->YTpart;
   io.esc_off = h->ys4 ? h->esc_off : nullptr; io.esc = h->ys4 ? h->esc : nullptr;
+  io.perm = nullptr;
   return io;
 }
 ca_ovf_args ys_ovf(ca_engine* h) { return ovf_args(h, h->YWpart + (int64_t)h->ys_nseg * h->N); }
@@ -144,9 +145,13 @@ int ys_finish(ca_engine* h, bool defer = false) {
 }
 // (h->mom_args set: the series form's forward moments ride as blocks of this launch, ca_polymom.hip.h -- taken here, so that the caller can tell.  The grid is
 //  [role][stream][overflow] with pm->blk0 = 0 and [stream][role][overflow] with pm->blk0 = nb_main: the same block count, the kernels map the index)
-template <bool Y4>
+// (N2 > 0: the 2-bit / 4-bit image, its escape list and its gene order in place of the 4-bit image's -- CA_VAR_Y2; everything else of the launch as it is)
+template <bool Y4, int N2 = 0>
 void launch_ys(ca_engine* h) {
   constexpr int lds = Y4 ? CA_YS4_LDS_BYTES : CA_YS_LDS_BYTES;
+  ca_ys_io yio = ys_io(h);
+  const uint8_t* Yimg = h->Ys;
+  if (N2 > 0) { Yimg = h->Ys2; yio.esc_off = h->esc2_off; yio.esc = h->esc2; yio.perm = h->y2_perm; }
   const int nb_main = h->ys_nrg * h->ys_nseg;
   const ca_pm_args* pm = h->mom_args;
   h->mom_args = nullptr;
@@ -157,17 +162,19 @@ void launch_ys(ca_engine* h) {
     if (pm) {
       ca_pm_args pmo = *pm;
       if (h->mom_last && h->mom_ovf_first) pmo.blk0 += ovf.nb_rows + ovf.nb_chunks;   // (lab: the overflow list's blocks between the stream's and the role)
-      hipLaunchKernelGGL(k_ys_mfma_ovf_mom<Y4>, grid, dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D, pmo);
+      hipLaunchKernelGGL((k_ys_mfma_ovf_mom<Y4, N2>), grid, dim3(CA_YM_TB), lds, h->stream, Yimg, yio, h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D, pmo);
     }
-    else hipLaunchKernelGGL(k_ys_mfma_ovf<Y4>, grid, dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D);
+    else hipLaunchKernelGGL((k_ys_mfma_ovf<Y4, N2>), grid, dim3(CA_YM_TB), lds, h->stream, Yimg, yio, h->N, h->Gp, h->ys_RS, nb_main, ovf, h->F, h->V, h->D);
   } else {
-    if (pm) hipLaunchKernelGGL(k_ys_mfma_mom<Y4>, dim3(nmom + nb_main), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS, *pm);
-    else hipLaunchKernelGGL(k_ys_mfma<Y4>, dim3(nb_main), dim3(CA_YM_TB), lds, h->stream, h->Ys, ys_io(h), h->N, h->Gp, h->ys_RS);
+    if (pm) hipLaunchKernelGGL((k_ys_mfma_mom<Y4, N2>), dim3(nmom + nb_main), dim3(CA_YM_TB), lds, h->stream, Yimg, yio, h->N, h->Gp, h->ys_RS, *pm);
+    else hipLaunchKernelGGL((k_ys_mfma<Y4, N2>), dim3(nb_main), dim3(CA_YM_TB), lds, h->stream, Yimg, yio, h->N, h->Gp, h->ys_RS);
   }
 }
 int ycache_ys(ca_engine* h) {
   CACK(ys_quant(h));
-  if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, launch_ys<true>(h));
+  if (h->ys4 && h->ys_n2 == 6) LAUNCH(h, CA_KERNEL_YPASS, (launch_ys<true, 6>(h)));
+  else if (h->ys4 && h->ys_n2 == 5) LAUNCH(h, CA_KERNEL_YPASS, (launch_ys<true, 5>(h)));
+  else if (h->ys4) LAUNCH(h, CA_KERNEL_YPASS, launch_ys<true>(h));
   else LAUNCH(h, CA_KERNEL_YPASS, launch_ys<false>(h));
   const bool defer = h->ys_defer_next;
   h->ys_defer_next = false;

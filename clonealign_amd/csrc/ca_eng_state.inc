@@ -214,6 +214,9 @@ struct ca_engine {
   hipEvent_t ev_ywdone = nullptr; bool yw_pending = false, on_side = false;
   // count-matrix products on the int8 matrix cores (ca_ymfma.hip.h): ONE tiled copy through the transposing LDS read (k_ys_mfma; K = 1), fixed-point parameter images
   bool y_ys = false, ys4 = false; int* esc_off = nullptr; unsigned* esc = nullptr; int64_t n_esc = 0;
+  // the 2-bit / 4-bit image of the series form's own stream launch (CA_VAR_Y2, ca_ymfma.hip.h): n2 of a segment's eight gene blocks at 2 bits (0: no such image), the
+  // private gene order per segment both ways, its own escape list; the 4-bit image stays resident beside it for the riding forms of handed-over passes
+  int ys_n2 = 0; uint8_t* Ys2 = nullptr; unsigned short *y2_perm = nullptr, *y2_pos = nullptr; int* esc2_off = nullptr; unsigned* esc2 = nullptr; int64_t n_esc2 = 0;
   uint8_t* Ys = nullptr; uint4 *Wr = nullptr, *Pr = nullptr; int *Wsum = nullptr, *Psum = nullptr;
   int* ys_exps = nullptr;        // [3][2]: rotating slots, see ca_ys_quant_body
   unsigned* ys_amax = nullptr;   // [2]: exact maxima of a fresh state (k_ym_absmax), float bit patterns

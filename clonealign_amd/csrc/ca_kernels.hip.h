@@ -823,7 +823,7 @@ __global__ void __launch_bounds__(CA_TB) k_p2p_allreduce(double* __restrict__ bu
 }
 
 // the one-copy stream with the overflow list's per-entry work (cell side, then gene side) as extra blocks, like k_ypass
-template <bool Y4>
+template <bool Y4, int N2 = 0>
 __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_ovf(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS,
                                                                        int nb_main, ca_ovf_args ovf, const float* __restrict__ F,
                                                                        const float* __restrict__ V, int Dstride) {
@@ -834,7 +834,7 @@ __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_y
     return;
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];   // Y4: CA_YS4_LDS_BYTES, else CA_YS_LDS_BYTES
-  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true, N2>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 
 // The series form's forward moments RIDING on its count-matrix stream's launch (CA_VAR_MOM_RIDE): blocks pm.blk0 .. pm.blk0 + nmb + nred - 1 are the moment
@@ -845,14 +845,14 @@ __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_y
 // (same body, same register budget, same dynamic LDS, out of which the moment role carves its tables).  Neither role reads what the other writes.
 #include "ca_polymom.hip.h"
 static_assert(sizeof(ca_pm_lds) <= (size_t)CA_YS_LDS_BYTES && sizeof(ca_pm_lds) <= (size_t)CA_YS4_LDS_BYTES, "the moment role's tables fit the stream's dynamic LDS");
-template <bool Y4>
+template <bool Y4, int N2 = 0>
 __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_mom(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS, ca_pm_args pm) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];   // Y4: CA_YS4_LDS_BYTES, else CA_YS_LDS_BYTES
   const int nmom = pm.nmb + pm.nred, rb = (int)blockIdx.x - pm.blk0;
   if (rb >= 0 && rb < nmom) { ca_pm_ride_block<CA_YM_TB>(pm, rb, ca_ys_dyn); return; }
-  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>(rb < 0 ? (int)blockIdx.x : (int)blockIdx.x - nmom, Ys, io, N, Gp, RS, ca_ys_dyn);
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true, N2>(rb < 0 ? (int)blockIdx.x : (int)blockIdx.x - nmom, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
-template <bool Y4>
+template <bool Y4, int N2 = 0>
 __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma_ovf_mom(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS,
                                                                            int nb_main, ca_ovf_args ovf, const float* __restrict__ F,
                                                                            const float* __restrict__ V, int Dstride, ca_pm_args pm) {
@@ -866,7 +866,7 @@ __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_y
     else ca_ovf_chunks_body(b - ovf.nb_rows, ovf.chunk_start, ovf.row2, ovf.val2, F, Dstride, ovf.csum, ovf.nchunk, 1, 0);
     return;
   }
-  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>(blk, Ys, io, N, Gp, RS, ca_ys_dyn);
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true, N2>(blk, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 
 // The one-copy int8 matrix-core stream RIDING on the forward sweep's launch (round 3).  The vector stream of k_fwd_cell_mix_y

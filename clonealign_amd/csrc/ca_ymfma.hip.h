@@ -114,13 +114,27 @@ __device__ __forceinline__ int ca_esc_count8(uint2 v) {
   for (int b = 0; b < 4; ++b) c += (((v.x >> (8 * b)) & 0xFFu) >= 15u) + (((v.y >> (8 * b)) & 0xFFu) >= 15u);
   return c;
 }
-__global__ void __launch_bounds__(CA_YM_TB) k_esc_count(const uint8_t* __restrict__ Y, int64_t N, int Gp, int nseg, int RS, int* __restrict__ off) {
+// The 2-bit / 4-bit image's list (CA_VAR_Y2; pos8 non-null): a gene's field is its POSITION in the segment's private order (pos8: eight 16-bit positions per lane,
+// [Gp] by gene index), and a gene whose position lies in the first n2 64-gene blocks escapes from 3 up with excess y - 3 (its block stores min(y, 3) in 2 bits).
+__device__ __forceinline__ unsigned ca_esc_pos(const uint4& p8, int b) { return ((b < 2 ? p8.x : b < 4 ? p8.y : b < 6 ? p8.z : p8.w) >> (16 * (b & 1))) & 0xFFFFu; }
+__device__ __forceinline__ int ca_esc_count8_y2(uint2 v, uint4 p8, int n2) {
+  int c = 0;
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const unsigned y = ((b < 4 ? v.x : v.y) >> (8 * (b & 3))) & 0xFFu;
+    c += y >= ((int)ca_esc_pos(p8, b) < 64 * n2 ? 3u : 15u);
+  }
+  return c;
+}
+__global__ void __launch_bounds__(CA_YM_TB) k_esc_count(const uint8_t* __restrict__ Y, int64_t N, int Gp, int nseg, int RS, int* __restrict__ off,
+                                                        const uint4* __restrict__ pos8 = nullptr, int n2 = 0) {
   const int64_t w = ((int64_t)blockIdx.x * CA_YM_TB + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (w >= N * nseg) return;
   const int64_t n = w / nseg;
   const int seg = (int)(w - n * nseg);
-  int c = ca_esc_count8(*reinterpret_cast<const uint2*>(Y + n * (int64_t)Gp + seg * 512 + 8 * lane));
+  const uint2 v = *reinterpret_cast<const uint2*>(Y + n * (int64_t)Gp + seg * 512 + 8 * lane);
+  int c = pos8 ? ca_esc_count8_y2(v, pos8[seg * 64 + lane], n2) : ca_esc_count8(v);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
   if (lane == 0) off[ca_esc_key(n, seg, nseg, RS)] = c;
@@ -145,14 +159,16 @@ __global__ void __launch_bounds__(1024) k_esc_scan(int* __restrict__ off, int64_
   if (t == 1023) off[n] = (int)sm[1023];
 }
 __global__ void __launch_bounds__(CA_YM_TB) k_esc_fill(const uint8_t* __restrict__ Y, int64_t N, int Gp, int nseg, int RS, const int* __restrict__ off,
-                                                       unsigned* __restrict__ esc) {
+                                                       unsigned* __restrict__ esc, const uint4* __restrict__ pos8 = nullptr, int n2 = 0) {
   const int64_t w = ((int64_t)blockIdx.x * CA_YM_TB + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (w >= N * nseg) return;
   const int64_t n = w / nseg;
   const int seg = (int)(w - n * nseg);
   const uint2 v = *reinterpret_cast<const uint2*>(Y + n * (int64_t)Gp + seg * 512 + 8 * lane);
-  const int c = ca_esc_count8(v);
+  uint4 p8 = {0u, 0u, 0u, 0u};
+  if (pos8) p8 = pos8[seg * 64 + lane];
+  const int c = pos8 ? ca_esc_count8_y2(v, p8, n2) : ca_esc_count8(v);
   int x = c;   // inclusive prefix over the lanes
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(x, o, 64); if (lane >= o) x += u; }
@@ -161,8 +177,76 @@ __global__ void __launch_bounds__(CA_YM_TB) k_esc_fill(const uint8_t* __restrict
 #pragma unroll
   for (int b = 0; b < 8; ++b) {
     const unsigned y = ((b < 4 ? v.x : v.y) >> (8 * (b & 3))) & 0xFFu;
-    if (y >= 15u) esc[e++] = cl | ((unsigned)(8 * lane + b) << 9) | ((y - 15u) << 18);
+    const unsigned pos = pos8 ? ca_esc_pos(p8, b) : (unsigned)(8 * lane + b);
+    const unsigned thr = (pos8 && (int)pos < 64 * n2) ? 3u : 15u;
+    if (y >= thr) esc[e++] = cl | (pos << 9) | ((y - thr) << 18);
   }
+}
+// ---------------------------------------------------------------- the 2-bit / 4-bit loop image (CA_VAR_Y2)
+// A third loop image, for the series form's own stream launch only.  Within each 512-gene segment the genes are ordered by their number of stored counts >= 3
+// (ascending, ties by gene index; the host sorts 512 keys per segment from k_y2_hist's counts); the first n2 64-gene blocks of every segment hold min(y, 3) in
+// 2 bits (1-KiB pieces), the others keep the 4-bit image's 2-KiB nibble pieces.  No gene changes segment and no cell moves: the stream's sums are the same
+// integers.  Layout [N64/64][nseg][n2 x 1 KiB | (8 - n2) x 2 KiB].  Narrow piece, lane l = (j = l & 15, q = l >> 4), dword d, byte b: bits 2t .. 2t+1 = cell
+// 64 cs + 16 t + j, position 64 a + 16 q + 4 d + b -- so (v >> 2t) & 0x03030303 is cell tile t's A operand.  Wide piece: k_pack_y4's, by position.
+// per-gene counts of stored y >= 3 (hist[g]) and y >= 15 (hist[Gp + g]); hist zeroed before.  Four genes per thread, 64 cells per block: integer sums, any order.
+__global__ void __launch_bounds__(CA_YM_TB) k_y2_hist(const uint8_t* __restrict__ Y, int64_t N, int Gp, int* __restrict__ hist) {
+  const int g = 4 * ((int)blockIdx.x * CA_YM_TB + threadIdx.x);
+  if (g >= Gp) return;
+  const int64_t n0 = (int64_t)blockIdx.y * 64, n1 = n0 + 64 < N ? n0 + 64 : N;
+  unsigned c3 = 0u, c15 = 0u;   // four byte-wide counters each (at most 64)
+  for (int64_t n = n0; n < n1; ++n) {
+    const unsigned v = *reinterpret_cast<const unsigned*>(Y + n * (int64_t)Gp + g);
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const unsigned y = (v >> (8 * b)) & 0xFFu;
+      c3 += (unsigned)(y >= 3u) << (8 * b);
+      c15 += (unsigned)(y >= 15u) << (8 * b);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int a3 = (int)((c3 >> (8 * b)) & 0xFFu), a15 = (int)((c15 >> (8 * b)) & 0xFFu);
+    if (a3) atomicAdd(hist + g + b, a3);
+    if (a15) atomicAdd(hist + Gp + g + b, a15);
+  }
+}
+// one thread per 16 bytes of the image; perm[seg * 512 + position] = the gene's index in its segment
+__global__ void __launch_bounds__(CA_YM_TB) k_pack_y2(const uint8_t* __restrict__ Y, uint4* __restrict__ Y2, int64_t N, int64_t N64, int Gp, int n2,
+                                                      const unsigned short* __restrict__ perm) {
+  const int64_t i = (int64_t)blockIdx.x * CA_YM_TB + threadIdx.x;
+  const int nseg = Gp / 512, sb = n2 * 64 + (8 - n2) * 128;   // 16-byte units per (cell step, segment)
+  if (i >= (N64 / 64) * nseg * sb) return;
+  const int64_t unit = i / sb, cs = unit / nseg;
+  const int seg = (int)(unit - cs * nseg), r = (int)(i - unit * sb);
+  const bool nar = r < n2 * 64;
+  const int rw = r - n2 * 64;
+  const int a = nar ? r >> 6 : n2 + (rw >> 7), l = nar ? r & 63 : rw & 63, ld = nar ? 0 : (rw >> 6) & 1;
+  const int j = l & 15, q = l >> 4;
+  const unsigned short* pp = perm + seg * 512 + 64 * a + 16 * q;
+  const uint8_t* base = Y + seg * 512;
+  unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int gb = 0; gb < 16; ++gb) {
+    const uint8_t* col = base + pp[gb];
+    unsigned x = 0u;
+    if (nar) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int64_t n = cs * 64 + 16 * t + j;
+        const unsigned y = n < N ? col[n * (int64_t)Gp] : 0u;
+        x |= (y < 3u ? y : 3u) << (2 * t);
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int64_t n = cs * 64 + 32 * ld + 16 * t + j;
+        const unsigned y = n < N ? col[n * (int64_t)Gp] : 0u;
+        x |= (y < 15u ? y : 15u) << (4 * t);
+      }
+    }
+    w[gb >> 2] |= x << (8 * (gb & 3));
+  }
+  Y2[i] = (uint4){w[0], w[1], w[2], w[3]};
 }
 
 // ---------------------------------------------------------------- the stream
@@ -234,6 +318,7 @@ struct ca_ys_io {
   const uint4* Wr; const uint4* Pr; const int* Wsum; const int* Psum; const int* exps;   // exps[0] for W, exps[1] for psi
   float* YWpart; float* YTpart;
   const int* esc_off; const unsigned* esc;   // the 4-bit image's escape list (k_esc_fill); null: the image is the 1-byte one (Ys)
+  const unsigned short* perm;                // the 2-bit / 4-bit image (N2 > 0): [Gp] position in the segment -> gene index in the segment
 };
 #ifndef CA_YS4_DEPTH
 #define CA_YS4_DEPTH 4   // pieces in flight per wave of the 4-bit image's own launch (2 KiB each); round 12, at four waves per SIMD: 2 is 2 us per iteration slower, 8 spills
@@ -258,7 +343,10 @@ static_assert(4 * CA_YS4_LDS_BYTES <= 160 * 1024, "four blocks of the 4-bit laun
 // both sides of an entry are LDS operations (fix(W_g) from the block's W image, fix(psi_n) from the step's digits, row and column sums
 // in LDS int64) -- and the register budget is the one of four waves per SIMD: W from LDS, psi masked per MFMA.  The riding forms keep OWN
 // = false: the same sums, the layout of CA_YS_LDS_BYTES.
-template <int DEPTH = CA_YS_DEPTH, bool Y4 = false, bool OWN = false>
+// N2 > 0 (OWN with Y4 only, CA_VAR_Y2): the image is the 2-bit / 4-bit one (k_pack_y2) -- the first N2 gene blocks of the segment arrive as 1-KiB pieces of 2-bit
+// counts, the segment's W image in LDS is gathered into the image's private gene order at the block's head, the escape list's gene fields are positions in that
+// order, and YTpart is written at the gene's own index through io.perm.  The same integers as N2 = 0, which compiles to the launch as it was.
+template <int DEPTH = CA_YS_DEPTH, bool Y4 = false, bool OWN = false, int N2 = 0>
 __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restrict__ Ys, const ca_ys_io& io, int64_t N, int Gp,
                                                 int RS /* cells per strip, multiple of 64 */,
                                                 unsigned char* ca_ys_lds /* 16-byte aligned, CA_YS_LDS_BYTES: [4 waves][64][CA_YS_PITCH], reused for the combine */) {
@@ -267,6 +355,8 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   constexpr bool Y4L = Y4 && OWN;
   constexpr int NP = CA_YS_GW / 64;
   static_assert(NP % DEPTH == 0, "pieces per cell step must be a multiple of the pipeline depth");
+  static_assert(N2 == 0 || (Y4 && OWN && N2 < NP), "the 2-bit blocks belong to the 4-bit image's own launch");
+  constexpr int SB2 = N2 * 1024 + (NP - N2) * 2048;   // (N2 > 0) bytes of a (cell step, segment): N2 narrow pieces, then the wide ones
   const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
   // the wave index as a SCALAR: strip bounds, piece addresses and the piece loop are then wave-uniform (scalar registers, scalar
   // branches, loads of the form global_load v, v_off, s[base]) instead of 64-bit vector arithmetic per lane -- the kernel that rides
@@ -293,7 +383,8 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   const unsigned char* rd_row = my + j * CA_YS_PITCH + 16 * q;
   const unsigned rd_tr = (unsigned)(size_t)my + (unsigned)((16 * q + (j >> 1)) * CA_YS_PITCH + 8 * (j & 1));
   constexpr int PB = Y4 ? 2048 : 4096, NL = PB / 1024;                              // bytes of a piece, 1-KiB loads per piece
-  const uint8_t* src = Ys + ((c0 >> 6) * (int64_t)(Gp / 64) + (g0 >> 6)) * PB;     // (scalar) piece (cell step, gene block), 1 KiB per load
+  const uint8_t* src = N2 > 0 ? Ys + ((c0 >> 6) * (int64_t)nseg + seg) * SB2        // (scalar) the strip's first (cell step, segment) of the 2-bit / 4-bit image
+                              : Ys + ((c0 >> 6) * (int64_t)(Gp / 64) + (g0 >> 6)) * PB;     // (scalar) piece (cell step, gene block), 1 KiB per load
   const uint4* wsrc = Wr + (int64_t)(g0 >> 6) * 64;                                 // (scalar)
   const unsigned voff = 16u * (unsigned)lane;                                       // the lane's 16 bytes of a 1-KiB load
   uint4 R[DEPTH][NL], W[DEPTH];
@@ -307,9 +398,10 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wsrc), 0, NP * 1024, 0x00020000);
   const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(Pr + (c0 >> 6) * 64), 0, 0x7FFFFFFF, 0x00020000);
   auto issue = [&](int slot, int st, int a, unsigned vo) {
-    const int so = (st * (Gp / 64) + a) * PB;   // (scalar)
+    const int so = N2 > 0 ? st * nseg * SB2 + (a < N2 ? a * 1024 : N2 * 1024 + (a - N2) * 2048) : (st * (Gp / 64) + a) * PB;   // (scalar)
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
+      if (N2 > 0 && i > 0 && a < N2) continue;   // (a narrow piece is one load; `a` is a constant wherever this is called)
       const ca_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(vo + 1024u * (unsigned)i), so, 2 /* nt: streamed once */);
       R[slot][i] = (uint4){v.x, v.y, v.z, v.w};
     }
@@ -322,11 +414,18 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   // sums zeroed), and the strip's escape offsets at its cell steps, lane st = the first entry of step st (lane nsteps: the end)
   uint4* wl = reinterpret_cast<uint4*>(ca_ys_lds + CA_YS4_OFF_W);
   unsigned long long* colesc = reinterpret_cast<unsigned long long*>(ca_ys_lds + CA_YS4_OFF_COL);
-  uint4 wimg[2];
+  uint4 wimg[2], pidx[2][2];
   int eoff = 0;
   if (Y4L) {
     wimg[0] = wsrc[threadIdx.x];
     wimg[1] = wsrc[threadIdx.x + CA_YM_TB];
+    if (N2 > 0) {   // the sixteen genes behind each of the thread's two 16-byte rows of the permuted image: positions 16 (x >> 4) .. + 15 of the segment, x = the row
+#pragma unroll
+      for (int h2 = 0; h2 < 2; ++h2) {
+        const uint4* pq = reinterpret_cast<const uint4*>(io.perm + g0 + 16 * (((int)threadIdx.x + h2 * CA_YM_TB) >> 4));
+        pidx[h2][0] = pq[0]; pidx[h2][1] = pq[1];
+      }
+    }
     if (lane <= nsteps) eoff = io.esc_off[((int64_t)blk * 4 + wv) * RS + (64 * lane < RS ? 64 * lane : RS)];
   }
   uint4 pr_nx = {0u, 0u, 0u, 0u};
@@ -340,6 +439,28 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   }
   if (Y4L) {
     static_assert(2 * CA_YM_TB == CA_YS_GW, "the block's threads hold the segment's W image and column sums in two halves");
+    if (N2 > 0) {
+      // gather the W image into the private order: the image as the quantiser left it goes through the staging regions (8 KiB of their 20, no piece is parked yet),
+      // and row x = (block a, lane 16 q + j) takes byte (digit j & 3, gene) of each of its sixteen genes -- the address the escapes use
+      uint4* tmp = reinterpret_cast<uint4*>(ca_ys_lds);
+      tmp[threadIdx.x] = wimg[0];
+      tmp[threadIdx.x + CA_YM_TB] = wimg[1];
+      __syncthreads();
+      const unsigned char* tb = reinterpret_cast<const unsigned char*>(tmp) + 16 * ((int)threadIdx.x & 3);
+#pragma unroll
+      for (int h2 = 0; h2 < 2; ++h2) {
+        unsigned w4[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+          const uint4& pv = pidx[h2][b >> 3];
+          const unsigned two = (b & 7) < 2 ? pv.x : (b & 7) < 4 ? pv.y : (b & 7) < 6 ? pv.z : pv.w;
+          const int gi = (int)((two >> (16 * (b & 1))) & 511u);
+          w4[b >> 2] |= (unsigned)tb[((gi >> 6) * 64 + 16 * ((gi >> 4) & 3)) * 16 + (gi & 15)] << (8 * (b & 3));
+        }
+        wimg[h2] = (uint4){w4[0], w4[1], w4[2], w4[3]};
+      }
+      // (the barrier below also orders these reads of the staging regions before any wave parks a piece there)
+    }
     wl[threadIdx.x] = wimg[0];
     wl[threadIdx.x + CA_YM_TB] = wimg[1];
     colesc[threadIdx.x] = 0ull;
@@ -411,9 +532,10 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
         // (one tile at a time: four registers of unpacked bytes live, not sixteen -- the riding form's budget is 128)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          const uint4 v = R[slot][t >> 1];
-          const int sh = 4 * (t & 1);
-          const uint4 av = ca_and4((uint4){v.x >> sh, v.y >> sh, v.z >> sh, v.w >> sh}, 0x0F0F0F0Fu);
+          const bool nar = N2 > 0 && a < N2;   // (compile time: the block loop is unrolled) a narrow piece holds the four tiles in one load, two bits each
+          const uint4 v = R[slot][nar ? 0 : t >> 1];
+          const int sh = nar ? 2 * t : 4 * (t & 1);
+          const uint4 av = ca_and4((uint4){v.x >> sh, v.y >> sh, v.z >> sh, v.w >> sh}, nar ? 0x03030303u : 0x0F0F0F0Fu);
           *reinterpret_cast<uint4*>(const_cast<unsigned char*>(rd_row) + 16 * t * CA_YS_PITCH) = av;
           acc_yw[t] = ca_mfma_i8(av, wr, acc_yw[t]);
         }
@@ -553,15 +675,15 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
       const int sr = (comb[o] + comb[o + NP * 256]) + (comb[o + 2 * NP * 256] + comb[o + 3 * NP * 256]);
       v = v * 256.0 + (double)((long long)sr + 128 * pb[r]);
     }
-    const int gl = 16 * (4 * a + (l >> 4)) + (l & 15), gene = g0 + gl;
+    const int gl = 16 * (4 * a + (l >> 4)) + (l & 15), gene = g0 + (N2 > 0 ? (int)io.perm[g0 + gl] : gl);   // (N2 > 0: gl is a position, the gene's own index through the map)
     if (Y4L) v += (double)(long long)colesc[gl];   // (integers below 2^53 throughout: the same total as the escapes added digit by digit)
     io.YTpart[(int64_t)rg * Gp + gene] = (float)(v * inv_p);
   }
 }
-template <bool Y4>
+template <bool Y4, int N2 = 0>
 __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_ys_mfma(const uint8_t* __restrict__ Ys, ca_ys_io io, int64_t N, int Gp, int RS) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ca_ys_dyn[];   // Y4: CA_YS4_LDS_BYTES, else CA_YS_LDS_BYTES
-  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
+  ca_ys_mfma_body<Y4 ? CA_YS4_DEPTH : CA_YS_DEPTH, Y4, true, N2>((int)blockIdx.x, Ys, io, N, Gp, RS, ca_ys_dyn);
 }
 // (the riding forms -- k_fwd_cell_mix_ys, k_fwd_bal_ys -- are instantiated per format: the 1-byte ones are round 6's code; the 4-bit ones exist
 //  only for the series form's rank-one shapes (D = 1, no c16 / s2), whose sweeps run only in the passes the series form hands over)

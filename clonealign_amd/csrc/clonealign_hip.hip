@@ -243,6 +243,14 @@ static const char* sparse_descriptor_error(const ca_sparse* sp) {
 extern "C" {
 
 int ca_abi_version(void) { return CA_ABI_VERSION; }
+/* Not part of the ABI the header declares (a test entry, tests/test_y2_plan_host.py): the host-side plan of the 2-bit / 4-bit image (CA_VAR_Y2), a pure function: cnt3[g] / cnt15[g] = stored counts >= 3 / >= 15 of gene g (Gp genes, a multiple of 512, padded
+ * genes 0).  Per 512-gene segment the genes are ordered by cnt3 ascending, ties by index: perm[seg 512 + position] = gene index in the segment, pos = its inverse.  The escape
+ * list of N2 narrow blocks holds cnt3 of the genes at positions below 64 N2 and cnt15 of the others.  force_n2 > 0: that N2; else the larger of 6 and 5 whose list is at most
+ * 1 in 256 of `counts`, else 0.  Returns N2; *n_esc = its list's length (the 4-bit image's, all cnt15, for 0). */
+int ca_y2_plan(const int32_t* cnt3, const int32_t* cnt15, int32_t Gp, int64_t counts, int32_t force_n2, uint16_t* perm, uint16_t* pos, int64_t* n_esc) {
+  if (!cnt3 || !cnt15 || !perm || !pos || !n_esc || Gp <= 0 || Gp % CA_YS_GW != 0 || force_n2 < 0) return CA_ERR_INVALID;
+  return ca_y2_plan_impl(cnt3, cnt15, Gp, counts, force_n2, perm, pos, n_esc);
+}
 #ifdef CA_LAB   // timing-lab builds only: readers of the block stamps (tools/lab/)
 #include "../../tools/lab/ca_lab_host.inc"
 #endif
@@ -361,6 +369,10 @@ int ca_get_info(ca_handle h, ca_info* i) {
   i->fwd_mfma = ((h->fused_ok && h->fwd_mfma) || h->pfwd) ? 1 : 0; i->bwd_mfma = h->bwd_mfma ? 1 : 0; i->fsplit = h->fsplit; i->fwd_cell = (h->fused_ok && h->fwd_cell) ? 1 : 0;
   i->y_mfma = h->y_ys ? 2 : 0;
   i->y_stream_bits = h->y_ys ? (h->ys4 ? 4 : 8) : 0;
+  i->y_stream_n2 = h->ys_n2;
+  i->y_stream_esc = h->ys_n2 > 0 ? h->n_esc2 : h->ys4 ? h->n_esc : 0;
+  i->y_stream_bytes = !h->y_ys ? 0 : h->ys_n2 > 0 ? (h->ys_N64 / 64) * (int64_t)h->ys_nseg * (h->ys_n2 * 1024 + (8 - h->ys_n2) * 2048) + 4 * h->n_esc2
+                                   : h->ys4 ? h->ys_N64 * h->Gp / 2 + 4 * h->n_esc : h->ys_N64 * h->Gp;
   i->y_ride = (h->ride_ok || h->ride_ys) ? 1 : 0;
   i->transport = (h->p2p && h->p2p->connected) ? CA_TRANSPORT_P2P : h->comm ? CA_TRANSPORT_RCCL : h->host_ar ? CA_TRANSPORT_HOST : CA_TRANSPORT_NONE;
   i->red_n = h->red_n;

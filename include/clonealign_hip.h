@@ -140,6 +140,11 @@ enum ca_variant {
                                  instead of a 32-step chain on 176 threads between two block barriers: with at most four bins a pass has no block barrier left.  The
                                  same sums in another, fixed association: fp64 rounding apart, the same bits from run to run; on wherever the series form runs.
                                  Off: the thread-owned chain (k_poly_cell<CP, LEAN, false>), the launch as it was */
+  CA_VAR_Y2 = 1 << 27,        /* the series form's own count-matrix stream launch reads a third loop image in which the genes of each 512-gene segment are ordered by how
+                                 often they reach 3 and the first N2 64-gene blocks of every segment hold min(y, 3) in 2 bits (the counts from 3 up in its own escape
+                                 list), the others 4 bits as before: fewer bytes per pass, the same integer sums.  Picked where the 4-bit image is, the matrix is
+                                 large enough for the launch to follow its bytes, and N2 = 6 or 5 keeps the escapes at 1 in 256 counts (CA_VARX_Y2 forces N2 = 6).
+                                 Off: the 4-bit image's launch as it was */
   CA_VAR_RIDE_SEQ = 1 << 13  /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
 /* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
@@ -167,6 +172,7 @@ enum ca_variant_on {
                                  instead of O(N G C) per pass; the cell epilogue is the sweep's.  Other shapes keep the matrix-core sweeps */
   CA_VARX_Y4 = 1 << 9,        /* the 4-bit loop image (CA_VAR_Y4) at any escape fraction */
   CA_VARX_MOM_LAST = 1 << 10, /* the moment role behind the stream's blocks (CA_VAR_MOM_LAST) wherever the moments ride, whatever the rule says (the bits are the same) */
+  CA_VARX_Y2 = 1 << 11,       /* the 2-bit / 4-bit image (CA_VAR_Y2) wherever the series form streams the 4-bit image, at any size and escape fraction, N2 = 6 */
   CA_VARX_ASYNC_SMALL = 1 << 1 /* side stream also below 4e7 counts (small shards run the Y stream in line: the two cross-stream
                                  events cost more than the overlap returns there) */
 };
@@ -238,6 +244,10 @@ typedef struct ca_info {
   int32_t mom_last;          /* 1: the riding moment role sits behind the stream's blocks in the launch's grid (CA_VAR_MOM_LAST / CA_VARX_MOM_LAST); 0: in front */
   int32_t mom_free_slots;    /* block slots of the stream's launch (occupancy x compute units, asked of the runtime) that its own blocks leave free: what the rule saw; 0 where no moments ride */
   int32_t cell_mfma;         /* 1: the series form's cell launch gathers its backward moments by fp64 MFMA per wave (CA_VAR_CELL_MFMA) */
+  int32_t y_stream_n2;       /* > 0: the series form's own stream launch reads the 2-bit / 4-bit image (CA_VAR_Y2): that many of a segment's eight 64-gene blocks hold 2 bits per
+                                count, the others y_stream_bits (which stays the width of the wide blocks); 0: no 2-bit blocks */
+  int64_t y_stream_esc;      /* entries of the escape list the series form's own stream launch reads (the 2-bit / 4-bit image's where y_stream_n2 > 0, else the 4-bit image's; 0 at 8 bits) */
+  int64_t y_stream_bytes;    /* bytes that launch reads per pass: its image plus its escape list */
 } ca_info;
 enum ca_transport { CA_TRANSPORT_NONE = 0, CA_TRANSPORT_RCCL = 1, CA_TRANSPORT_HOST = 2, CA_TRANSPORT_P2P = 3 };
 

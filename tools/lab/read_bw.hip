@@ -1,5 +1,5 @@
 // tools/lab/read_bw.hip -- what a kernel that ONLY reads a 500 MB buffer reaches on this device, in the access shapes the count-matrix stream could take:
-//   hipcc -O3 --offload-arch=gfx950 -o tools/lab/read_bw.bin tools/lab/read_bw.hip && tools/lab/read_bw.bin        (all shapes; `read_bw.bin y4`: the 4-bit launch's walk only)
+//   hipcc -O3 --offload-arch=gfx950 -o tools/lab/read_bw.bin tools/lab/read_bw.hip && tools/lab/read_bw.bin        (all shapes; `read_bw.bin y4`: the 4-bit launch's walk only; `read_bw.bin y2`: that walk beside the 2-bit / 4-bit image's mixed walk)
 // (lab: the ceiling the stream kernel's 5.5-5.8 TB/s is to be read against; MI355X_MICROARCH.md quotes 6.3 TB/s for a float4 COPY)
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -118,7 +118,63 @@ static int run_engine4(int ncells, hipEvent_t a, hipEvent_t b, unsigned* out) {
   CK(hipFree(big));
   return 0;
 }
+// the mixed walk of a 2-bit / 4-bit image (`read_bw.bin y2`): per (cell step, segment) N2 narrow 1-KiB pieces (one load) then 8 - N2 wide 2-KiB pieces (two loads),
+// contiguous, [cell step][segment]; the same blocks, strips and LDS as k_read_engine4, DEPTH pieces rolling (a narrow piece holds half the bytes of a wide one in flight)
+template <int DEPTH, int N2>
+__global__ void __launch_bounds__(256, 4) k_read_engine_mix(const uint4* __restrict__ p, int nsteps_total, int nseg, int steps, unsigned* __restrict__ out) {
+  static_assert(8 % DEPTH == 0 && N2 >= 0 && N2 <= 8, "the eight pieces of a step are unrolled over the slots");
+  const int rg = blockIdx.x / nseg, seg = blockIdx.x % nseg, wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int st0 = (rg * 4 + wv) * steps;
+  const int ns = st0 + steps <= nsteps_total ? steps : (st0 < nsteps_total ? nsteps_total - st0 : 0);
+  constexpr int SB = N2 * 64 + (8 - N2) * 128;   // uint4 per (cell step, segment)
+  uint4 acc = {0, 0, 0, 0}, v[DEPTH][2];
+  auto issue = [&](int d, int st, int a, bool ok) {
+    const size_t base = ((size_t)(st0 + st) * nseg + seg) * SB + (a < N2 ? a * 64 : N2 * 64 + (a - N2) * 128);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) if (i == 0 || a >= N2) v[d][i] = ok ? ld_nt(p + base + i * 64 + lane) : (uint4){0, 0, 0, 0};
+  };
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) issue(d, 0, d, ns > 0);
+  for (int st = 0; st < ns; ++st) {
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+      const int d = a % DEPTH;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) if (i == 0 || a >= N2) { acc.x ^= v[d][i].x; acc.y ^= v[d][i].y; acc.z ^= v[d][i].z; acc.w ^= v[d][i].w; }
+      if (a + DEPTH < 8) issue(d, st, a + DEPTH, true); else issue(d, st + 1, a + DEPTH - 8, st + 1 < ns);
+    }
+  }
+  if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) out[0] = 1;
+}
+template <int DEPTH, int N2>
+static int run_engine_mix(int ncells, hipEvent_t a, hipEvent_t b, unsigned* out) {
+  const int nseg = 10, nst = (ncells + 63) / 64, steps = 4;
+  const size_t eb = (size_t)nst * nseg * (N2 * 1024 + (8 - N2) * 2048);
+  uint4* big; CK(hipMalloc(&big, eb)); CK(hipMemset(big, 1, eb));
+  const int nrg = (nst + 4 * steps - 1) / (4 * steps), blocks = nrg * nseg;
+  const size_t lds = 36 * 1024;
+  auto go = [&] { hipLaunchKernelGGL((k_read_engine_mix<DEPTH, N2>), dim3(blocks), dim3(256), lds, 0, big, nst, nseg, steps, out); };
+  for (int i = 0; i < 5; ++i) go();
+  CK(hipDeviceSynchronize());
+  float best = 1e9f, tot = 0.f;
+  const int reps = 20;
+  for (int r = 0; r < reps; ++r) { (void)hipEventRecord(a); go(); (void)hipEventRecord(b); (void)hipEventSynchronize(b); float ms; (void)hipEventElapsedTime(&ms, a, b); best = ms < best ? ms : best; tot += ms; }
+  printf("mixed walk, %d cells (%d blocks, 4 per CU), %d narrow + %d wide pieces per step and segment, %d in flight per wave: best %.1f us = %.2f TB/s, mean %.1f us (%.3f GB)\n", ncells, blocks,
+         N2, 8 - N2, DEPTH, best * 1e3, eb / (best * 1e-3) / 1e12, tot / reps * 1e3, eb * 1e-9);
+  CK(hipFree(big));
+  return 0;
+}
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "y2")) {   // the 4-bit walk beside the mixed walk at N2 = 0 (the same bytes: a check of the reader), 5 and 6
+    hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
+    unsigned* out; CK(hipMalloc(&out, 4));
+    for (int rep = 0; rep < 2; ++rep) {
+      if (run_engine4<4>(100000, a, b, out) || run_engine_mix<4, 0>(100000, a, b, out)) return 1;
+      if (run_engine_mix<4, 5>(100000, a, b, out) || run_engine_mix<8, 5>(100000, a, b, out)) return 1;
+      if (run_engine_mix<4, 6>(100000, a, b, out) || run_engine_mix<8, 6>(100000, a, b, out)) return 1;
+    }
+    return 0;
+  }
   if (argc > 1 && !strcmp(argv[1], "y4")) {   // only the 4-bit launch's walk (the floor its time is read against)
     hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
     unsigned* out; CK(hipMalloc(&out, 4));
