@@ -1257,6 +1257,389 @@ def project_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=
                          converged=r["converged"], clone_names=names, ml_params={"psi": psi, "clone_probs": probs})
 
 
+def gauss_hermite_rule(K, n_nodes=8):
+    """A quadrature rule for the standard normal measure in ``K`` dimensions: the tensor product of the ``n_nodes``-point Gauss-Hermite rule per axis
+    (``numpy.polynomial.hermite_e.hermegauss``), weights normalised to sum 1.  Returns ``(nodes [n_nodes ** K, K], weights [n_nodes ** K])``; ``K = 0``
+    gives the single empty node with weight 1."""
+    K, n = int(K), int(n_nodes)
+    if K < 0 or n < 1:
+        raise ValueError(f"gauss_hermite_rule: K = {K} and n_nodes = {n} must be >= 0 and >= 1")
+    z, w = np.polynomial.hermite_e.hermegauss(n)
+    w = w / w.sum()
+    if K == 0:
+        return np.zeros((1, 0)), np.ones(1)
+    grids = np.meshgrid(*([z] * K), indexing="ij")
+    nodes = np.stack([g.reshape(-1) for g in grids], axis=1)
+    weights = np.ones(n ** K)
+    for k, g in enumerate(np.meshgrid(*([w] * K), indexing="ij")):
+        weights = weights * g.reshape(-1)
+    return nodes, weights / weights.sum()
+
+
+def _evidence_rule(K, nodes, weights):
+    """(nodes [Q, K], weights [Q]) of a ``clone_evidence`` call after the library's refusals (ValueError names the offender)."""
+    if nodes is None or weights is None:
+        raise ValueError(f"clone_evidence: {'nodes' if nodes is None else 'weights'} is None (n_nodes x K nodes and n_nodes weights are needed)")
+    wt = np.asarray(weights, dtype=np.float64).reshape(-1)
+    Q = wt.shape[0]
+    if Q < 1 or Q > 64:
+        raise ValueError(f"clone_evidence: n_nodes = {Q} is outside [1, 64]")
+    nd = np.asarray(nodes, dtype=np.float64)
+    if nd.size != Q * K:
+        raise ValueError(f"clone_evidence: nodes is {nd.shape}; {Q} weights and K = {K} need ({Q}, {K})")
+    nd = nd.reshape(Q, K)
+    for q in range(Q):
+        if not np.isfinite(nd[q]).all():
+            raise ValueError(f"clone_evidence: node {q} has a non-finite coordinate (factor {int(np.flatnonzero(~np.isfinite(nd[q]))[0])})")
+        if not (np.isfinite(wt[q]) and wt[q] > 0):
+            raise ValueError(f"clone_evidence: weight {q} is {wt[q]}: not positive and finite")
+    total = 0.0
+    for q in range(Q):
+        total += float(wt[q])
+    if not abs(total - 1.0) <= 1e-12:
+        raise ValueError(f"clone_evidence: the weights sum to {total}: off 1 by more than 1e-12")
+    return nd, wt
+
+
+def _clone_evidence_host(Y, E, V, K, P, X, psi_start, nodes, weights, const=True, max_iter=50, tol=1e-9, max_step=1.0, chunk=None):
+    """Float64 numpy restatement of ``HipEngine.clone_evidence`` (ca_clone_evidence; the algorithm is stated in include/clonealign_hip.h), step for step,
+    ``chunk`` cells at a time (None: so that cells x clones x genes stays near 4e6), vectorised over the (cell, clone) pairs and the genes: Y [N, G] dense
+    or scipy.sparse, E [G, C], V = [W | beta] [G, K + P] or None, X [N, P] or None, psi_start [N, K] or None, nodes [Q, K], weights [Q].  Any K (general
+    solve and Cholesky beyond the device's closed forms for K <= 2).  Same return value, same rules, same refusals (ValueError)."""
+    from scipy.special import gammaln
+    E = np.asarray(E, dtype=np.float64)
+    N, G = Y.shape
+    K, P = int(K), int(P)
+    D = K + P
+    what = "clone_evidence"
+    if E.ndim != 2 or E.shape[0] != G:
+        raise ValueError(f"{what}: Y is {N} x {G} but E is {E.shape}")
+    C = E.shape[1]
+    if K < 0:
+        raise ValueError(f"{what}: K = {K} is negative")
+    if P < 0 or D > 8:
+        raise ValueError(f"{what}: K + P = {D} is outside [0, 8]")
+    if D > 0 and V is None:
+        raise ValueError(f"{what}: K + P = {D} needs V (genes x (K + P))")
+    if P > 0 and X is None:
+        raise ValueError(f"{what}: P = {P} needs X (cells x P)")
+    if max_iter < 0:
+        raise ValueError(f"{what}: max_iter = {max_iter} is negative")
+    for name, v in (("tol", tol), ("max_step", max_step)):
+        if not (np.isfinite(v) and v > 0):
+            raise ValueError(f"{what}: {name} = {v} is not a positive finite number")
+    nd, wt = _evidence_rule(K, nodes, weights)
+    Q = wt.shape[0]
+    V = np.zeros((G, 0)) if D == 0 else np.asarray(V, dtype=np.float64)
+    X = np.zeros((N, 0)) if P == 0 else np.asarray(X, dtype=np.float64)
+    start = np.zeros((N, K)) if psi_start is None or K == 0 else np.array(psi_start, dtype=np.float64)
+    if V.shape != (G, D) or X.shape != (N, P) or start.shape != (N, K):
+        raise ValueError(f"{what}: V is {V.shape}, X {X.shape}, psi_start {start.shape}; expected ({G}, {D}), ({N}, {P}), ({N}, {K})")
+    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
+    if wrong.size:
+        raise ValueError(f"{what}: expected expression has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
+    esum = E.sum(0)
+    wrong = np.flatnonzero(~np.isfinite(esum) | (esum == 0))
+    if wrong.size:
+        raise ValueError(f"{what}: expected expression of clone {wrong[0]} sums to {esum[wrong[0]]} over the genes")
+    for name, M, row, colname in (("V", V, "gene", "factor"), ("psi_start", start, "cell", "factor"), ("X", X, "cell", "covariate")):
+        if M.size and not np.isfinite(M).all():
+            r, d = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"{what}: {name} has a non-finite entry ({row} {r}, {colname} {d})")
+    NH = K * (K + 1) // 2
+    tri = [(k, l) for k in range(K) for l in range(k, K)]
+    out = {"evidence": np.empty((N, C)), "laplace": np.empty((N, C)), "psi_mode": np.zeros((N, C, K)), "psi_prec": np.zeros((N, C, NH)),
+           "rounds": np.zeros((N, C), dtype=np.int32), "converged": np.zeros((N, C), dtype=bool)}
+    if K == 0:                                                       # nothing to integrate: clone_loglik's value
+        ll = _clone_loglik_host(Y, E, X if P > 0 else None, V if P > 0 else None, const=const)
+        out["evidence"][:], out["laplace"][:] = ll, ll
+        out["converged"][:] = ~np.isneginf(ll)
+        return out
+    zero = E == 0
+    logE = np.log(np.where(zero, 1.0, E))                            # xlogy: 0 where E = 0, put right below
+    W, beta = V[:, :K], V[:, K:]
+    Et = np.ascontiguousarray(E.T)
+    step = int(chunk) if chunk is not None else max(1, 4_000_000 // max(1, C * G))
+    for lo in range(0, N, step):
+        Yc = Y[lo:lo + step]
+        Yc = np.ascontiguousarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)   # (one memory order: the products below sum the same way)
+        n = Yc.shape[0]
+        s = Yc.sum(1)
+        A = Yc @ logE                                                # the sweep: A, B, s and the constant
+        if zero.any():
+            A[((Yc > 0).astype(np.float64) @ zero.astype(np.float64)) > 0] = -np.inf
+        if const:
+            A += (gammaln(s + 1.0) - gammaln(Yc + 1.0).sum(1))[:, None]
+        B = Yc @ V
+        xB = (X[lo:lo + n] * B[:, K:]).sum(1)
+        xbeta = X[lo:lo + n] @ beta.T                                # [n, G]: the covariates' part of the exponent, once per (cell, gene)
+        ni, ci = np.repeat(np.arange(n), C), np.tile(np.arange(C), n)   # the pairs, cell-major
+        Ap, sp = A[ni, ci], s[ni]
+        psi = start[lo:lo + n][ni].copy()
+        dead = np.isneginf(Ap)
+        frozen = dead.copy()
+        rounds = np.zeros(n * C, dtype=np.int32)
+        conv = np.zeros(n * C, dtype=bool)
+        fstar = np.full(n * C, -np.inf)
+        H = np.zeros((n * C, K, K)) + np.eye(K)
+
+        def moments(i, ps, full):
+            """m, Z0 (and mean, cov) of the pairs i at their psi ``ps``"""
+            eta = xbeta[ni[i]].copy() if P > 0 else np.zeros((i.size, G))
+            for k in range(K):
+                eta += ps[:, k, None] * W[None, :, k]
+            m = eta.max(1)
+            wE = np.exp(eta - m[:, None]) * Et[ci[i]]
+            Z0 = wE.sum(1)
+            if not full:
+                return m, Z0, None, None
+            mean = np.empty((i.size, K))
+            cov = np.empty((i.size, K, K))
+            for k in range(K):
+                wk = wE * W[:, k]
+                mean[:, k] = wk.sum(1) / Z0
+                for l in range(k, K):
+                    cov[:, k, l] = cov[:, l, k] = (wk * W[:, l]).sum(1) / Z0
+            cov -= mean[:, :, None] * mean[:, None, :]
+            return m, Z0, mean, cov
+
+        def fval(i, ps, m, Z0):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                return Ap[i] + ((ps * B[ni[i], :K]).sum(1) + xB[ni[i]]) - np.where(sp[i] > 0, sp[i] * (m + np.log(Z0)), 0.0) - 0.5 * (ps ** 2).sum(1)
+
+        def newton(i):
+            m, Z0, mean, cov = moments(i, psi[i], True)
+            f = fval(i, psi[i], m, Z0)
+            g = B[ni[i], :K] - sp[i, None] * mean - psi[i]
+            Hi = np.eye(K)[None] + sp[i, None, None] * cov
+            with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+                if K == 1:
+                    d = g / Hi[:, 0]
+                elif K == 2:                                         # the closed form the device uses
+                    det = Hi[:, 0, 0] * Hi[:, 1, 1] - Hi[:, 0, 1] * Hi[:, 0, 1]
+                    d = np.stack([(Hi[:, 1, 1] * g[:, 0] - Hi[:, 0, 1] * g[:, 1]) / det, (Hi[:, 0, 0] * g[:, 1] - Hi[:, 0, 1] * g[:, 0]) / det], axis=1)
+                else:
+                    d = np.linalg.solve(Hi, g[:, :, None])[:, :, 0]
+            return f, Hi, d
+
+        for t in range(int(max_iter)):
+            i = np.flatnonzero(~frozen)
+            if i.size == 0:
+                break
+            f, Hi, d = newton(i)
+            dmax = np.abs(d).max(1)
+            nan = ~(dmax < np.inf)                                   # a step that is no number: the pair stops where it is, not converged
+            stop = nan | (dmax <= tol)
+            j = i[stop]
+            frozen[j], rounds[j], conv[j], fstar[j], H[j] = True, t + 1, (dmax <= tol)[stop], f[stop], Hi[stop]
+            go = ~stop
+            sc = np.where(dmax[go] > max_step, max_step / dmax[go], 1.0)
+            psi[i[go]] += d[go] * sc[:, None]
+        i = np.flatnonzero(~frozen)
+        if i.size:                                                   # the pairs that never froze: f and H at the psi they hold
+            f, Hi, _d = newton(i)
+            frozen[i], rounds[i], fstar[i], H[i] = True, int(max_iter), f, Hi
+        a = np.flatnonzero(~dead)
+        lap = np.full(n * C, -np.inf)
+        ev = np.full(n * C, -np.inf)
+        if a.size:
+            Ha = H[a]
+            if K == 1:
+                Lc = np.sqrt(Ha)
+            elif K == 2:                                             # the closed form the device uses
+                l00 = np.sqrt(Ha[:, 0, 0])
+                l10 = Ha[:, 0, 1] / l00
+                l11 = np.sqrt(Ha[:, 1, 1] - l10 * l10)
+                Lc = np.zeros_like(Ha)
+                Lc[:, 0, 0], Lc[:, 1, 0], Lc[:, 1, 1] = l00, l10, l11
+            else:
+                Lc = np.linalg.cholesky(Ha)
+            hld = np.zeros(a.size)
+            for k in range(K):
+                hld = hld + np.log(Lc[:, k, k])
+            lap[a] = fstar[a] - hld
+            M = np.full(a.size, -np.inf)
+            S = np.zeros(a.size)
+            for q in range(Q):                                       # psi_q = psi* + L^-T z_q; the sum under a running maximum, q ascending
+                z = nd[q]
+                if K == 1:
+                    y = (z[0] / Lc[:, 0, 0])[:, None]
+                elif K == 2:
+                    y1 = z[1] / Lc[:, 1, 1]
+                    y = np.stack([(z[0] - Lc[:, 1, 0] * y1) / Lc[:, 0, 0], y1], axis=1)
+                else:
+                    y = np.linalg.solve(np.swapaxes(Lc, 1, 2), np.broadcast_to(z, (a.size, K))[:, :, None])[:, :, 0]
+                pq = psi[a] + y
+                m, Z0, _m, _c = moments(a, pq, False)
+                tq = fval(a, pq, m, Z0) - fstar[a] + 0.5 * float((z * z).sum())
+                with np.errstate(invalid="ignore"):
+                    up = tq > M
+                    S = np.where(up, S * np.exp(np.where(up, M - tq, 0.0)), S)
+                    M = np.where(up, tq, M)
+                    S = S + wt[q] * np.exp(tq - M)
+            ev[a] = lap[a] + (M + np.log(S))
+        sl = slice(lo, lo + n)
+        out["evidence"][sl], out["laplace"][sl] = ev.reshape(n, C), lap.reshape(n, C)
+        out["psi_mode"][sl] = psi.reshape(n, C, K)
+        out["psi_prec"][sl] = np.stack([H[:, k, l] for k, l in tri], axis=1).reshape(n, C, NH)
+        out["rounds"][sl], out["converged"][sl] = rounds.reshape(n, C), conv.reshape(n, C)
+    return out
+
+
+def _prec_to_cov(prec, K):
+    """[N, C, K, K] inverse of the precision matrices given by their entries k <= l [N, C, K (K + 1) / 2]."""
+    N, C = prec.shape[:2]
+    H = np.zeros((N, C, K, K))
+    for j, (k, l) in enumerate([(k, l) for k in range(K) for l in range(k, K)]):
+        H[:, :, k, l] = H[:, :, l, k] = prec[:, :, j]
+    return np.linalg.inv(H) if K else H
+
+
+def _evidence_setup(fit, Y, L, x, saturate, saturation_threshold, engine, engine_opts):
+    """(Y, L parsed, clone names or None, engine, whether it is ours) shared by the evidence calls: the upload happens once."""
+    Lm, cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if Lm.shape[0] != G:
+        raise ValueError(f"L has {Lm.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        Ls = hostprep.saturate(Lm, saturation_threshold) if saturate else Lm
+        engine = HipEngine(Y, Ls, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    elif hasattr(engine, "clone_evidence") and (engine.N, engine.G) != (N, G):
+        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+    return Y, Lm, cn, engine, own
+
+
+def _clone_evidence_on(engine, fit, Y, Lm, n_nodes, x, psi_start, saturate, saturation_threshold, const, max_iter, tol, max_step):
+    """``clone_evidence`` of one fit on a live engine (or the host form for an engine without the method)."""
+    N, G = Y.shape
+    _Ls, E, _U, _V = _fit_tables(fit, Lm, N, x, None, saturate, saturation_threshold)
+    ml = fit["ml_params"]
+    W = np.asarray(ml["W"], dtype=np.float64).reshape(G, -1) if ml.get("W") is not None else np.zeros((G, 0))
+    beta = np.asarray(ml["beta"], dtype=np.float64).reshape(G, -1) if ml.get("beta") is not None else np.zeros((G, 0))
+    K, P = W.shape[1], beta.shape[1]
+    if K + P > 8:
+        raise ValueError(f"the fit has {K + P} exponent factors (K + P); at most 8 are supported")
+    X = None
+    if P > 0:
+        X = np.asarray(x, dtype=np.float64)
+        X = X.reshape(-1, 1) if X.ndim == 1 else X
+    if psi_start is not None:
+        psi_start = np.asarray(psi_start, dtype=np.float64)
+        if psi_start.size != N * K:
+            raise ValueError(f"psi_start has {psi_start.size} entries but Y has {N} rows (cells) and the fit K = {K}")
+        psi_start = psi_start.reshape(N, K)
+    per_axis = int(n_nodes) if n_nodes is not None else (8 if K <= 1 else 5)
+    nodes, weights = gauss_hermite_rule(K, per_axis)
+    V = np.concatenate([W, beta], axis=1) if K + P > 0 else None
+    if hasattr(engine, "clone_evidence"):
+        if K > 2:
+            raise ValueError(f"the fit has K = {K} latent factors; the device form of clone_evidence takes K <= 2")
+        r = engine.clone_evidence(E, V, K, X=X, psi_start=psi_start, nodes=nodes, weights=weights, const=const, max_iter=max_iter, tol=tol,
+                                  max_step=max_step)
+    else:
+        r = _clone_evidence_host(Y, E, V, K, P, X, psi_start, nodes, weights, const, max_iter, tol, max_step)
+    r = dict(r)
+    r["psi_cov"] = _prec_to_cov(r.pop("psi_prec"), K)
+    return r
+
+
+def clone_evidence(fit, Y, L, *, n_nodes=None, x=None, psi_start=None, saturate=True, saturation_threshold=6, const=True, max_iter=50, tol=1e-9,
+                   max_step=1.0, engine=None, engine_opts=None):
+    """The EVIDENCE of the cells of ``Y`` under every clone of a fitted model, with the cell's latent factor integrated out:
+    ``evidence[n, c] = log Integral Normal(psi; 0, I) Multinomial(y_n | clone c, psi) dpsi`` under the fit's gene-level parameters.  Unlike the value at
+    the MAP ``psi`` (``project_cells``: a maximum over ``psi``, which a fit with more factors never loses) this can be compared between fits on held-out
+    cells, so it chooses the number of factors ``K`` (``heldout_evidence``); it also gives each cell's posterior uncertainty in ``psi``.  On easy data the
+    clone calls barely move against ``project_cells`` -- the value of this is model choice and uncertainty, not new calls.
+
+    Per (cell, clone): the mode of the integrand by safeguarded Newton from ``psi_start`` (default 0), the Laplace value, and a Gauss-Hermite tensor rule
+    of ``n_nodes`` points per axis (default 8 for K <= 1, 5 for K = 2; at most 64 nodes in all) centred at the mode and scaled by the Cholesky factor of the
+    precision (include/clonealign_hip.h states the algorithm).  Other keywords as for ``project_cells``.  One float64 sweep over the matrix on the
+    device, then launches that do not read it (``HipEngine.clone_evidence``, ``K <= 2``); an engine without the method gets the float64 host form.
+
+    Returns a dict: ``evidence`` and ``laplace`` [cells, clones], ``psi_mode`` [cells, clones, K], ``psi_cov`` [cells, clones, K, K] (the inverse
+    precision at the mode: the Laplace covariance), ``rounds`` and ``converged`` [cells, clones].  A pair with ``converged`` False (``max_iter`` reached)
+    holds a value that is deterministic but NOT to be trusted."""
+    Yc, Lm, _cn, engine, own = _evidence_setup(fit, Y, L, x, saturate, saturation_threshold, engine, engine_opts)
+    try:
+        return _clone_evidence_on(engine, fit, Yc, Lm, n_nodes, x, psi_start, saturate, saturation_threshold, const, max_iter, tol, max_step)
+    finally:
+        if own:
+            engine.close()
+
+
+def _marginal_from_evidence(fit, r, L, extra_loglik, clone_assignment_probability):
+    """``assign_cells_marginal``'s result from ``clone_evidence``'s."""
+    out = _assign_from_loglik(fit, r["evidence"], L, extra_loglik, clone_assignment_probability)
+    probs = out["clone_probs"]
+    g = np.where(np.isfinite(probs), probs, 0.0)
+    mode, cov = r["psi_mode"], r["psi_cov"]
+    K = mode.shape[2]
+    psi = np.einsum("nc,nck->nk", g, mode)                           # the mixture of Laplace Gaussians: its mean and its marginal standard deviations
+    second = np.einsum("nc,nck->nk", g, np.einsum("nckk->nck", cov) + mode ** 2) if K else np.zeros_like(psi)
+    sd = np.sqrt(np.maximum(second - psi ** 2, 0.0))
+    out.update(laplace_loglik=r["laplace"], clone_evidence=r["evidence"], psi=psi, psi_sd=sd,
+               converged=(r["converged"] | ~(g > 1e-12)).all(1) & np.isfinite(out["loglik"]), rounds=r["rounds"])
+    out["ml_params"] = {"psi": psi, "clone_probs": probs}
+    return out
+
+
+def assign_cells_marginal(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=None, n_nodes=None, x=None, psi_start=None, saturate=True,
+                          saturation_threshold=6, const=True, max_iter=50, tol=1e-9, max_step=1.0, engine=None, engine_opts=None):
+    """``assign_cells`` with the cell's latent factor INTEGRATED OUT clone by clone: ``clone_probs = softmax_c(evidence + log alpha + extra_loglik)`` with
+    ``clone_evidence``'s value (same keywords), so that every clone is judged at its own best ``psi`` and with its own volume, not at one ``psi`` shared
+    by all clones (``project_cells``) or at ``psi = 0`` (``assign_cells``).  On easy data the calls barely move; what is new is ``loglik`` -- the cell's
+    evidence, comparable between fits (``heldout_evidence``) -- and the uncertainty of ``psi``.
+
+    Returns a :class:`ClonealignFit` with ``clone_probs``, ``clone``, ``loglik`` [cells] (the logsumexp of the same sum), ``clone_loglik`` and
+    ``clone_evidence`` [cells, clones] (the evidence), ``laplace_loglik``, ``psi`` [cells, K] (the posterior-weighted mean of the clones' modes),
+    ``psi_sd`` [cells, K] (from the mixture of the clones' Laplace Gaussians), ``rounds`` [cells, clones], ``converged`` [cells] (every clone with
+    posterior above 1e-12 converged) and ``clone_names``; ``recompute_clone_assignment`` works on it."""
+    r = clone_evidence(fit, Y, L, n_nodes=n_nodes, x=x, psi_start=psi_start, saturate=saturate, saturation_threshold=saturation_threshold, const=const,
+                       max_iter=max_iter, tol=tol, max_step=max_step, engine=engine, engine_opts=engine_opts)
+    return _marginal_from_evidence(fit, r, L, extra_loglik, clone_assignment_probability)
+
+
+def heldout_evidence(fits, Y, L, *, x=None, extra_loglik=None, n_nodes=None, saturate=True, saturation_threshold=6, const=True, max_iter=50, tol=1e-9,
+                     max_step=1.0, engine=None, engine_opts=None):
+    """Compare fitted models on cells none of them saw: for every fit of ``fits`` (a dict name -> fit, or a list; the numbers of factors K may differ) the
+    held-out evidence ``sum_n logsumexp_c(evidence_nc + log alpha_c + extra_loglik_nc)`` with ``clone_evidence``'s value (same keywords).  ONE engine and
+    ONE upload of ``Y`` serve all fits.
+
+    Returns a dict ``name -> {"total", "per_cell" [cells], "n_unconverged" (pairs), "delta" (total minus the best total, <= 0), "delta_se" (the paired
+    standard error of that difference: sqrt(cells) times the standard deviation of the per-cell differences; 0 for the best fit)}`` plus ``"best"`` (the
+    name with the largest total) and ``"ranking"`` (names, best first).  Cells that are impossible under every clone of some fit are left out of every sum."""
+    items = list(fits.items()) if isinstance(fits, dict) else [(i, f) for i, f in enumerate(fits)]
+    if not items:
+        raise ValueError("heldout_evidence: no fit given")
+    Yc, Lm, _cn, engine, own = _evidence_setup(items[0][1], Y, L, x, saturate, saturation_threshold, engine, engine_opts)
+    N = Yc.shape[0]
+    res = {}
+    try:
+        for name, fit in items:
+            r = _clone_evidence_on(engine, fit, Yc, Lm, n_nodes, x, None, saturate, saturation_threshold, const, max_iter, tol, max_step)
+            cell = _lse_clones(r["evidence"] + _dm_prior(fit, extra_loglik, N, r["evidence"].shape[1]))
+            res[name] = {"per_cell": cell, "n_unconverged": int((~r["converged"] & np.isfinite(r["evidence"])).sum())}
+    finally:
+        if own:
+            engine.close()
+    live = np.ones(N, dtype=bool)
+    for v in res.values():
+        live &= np.isfinite(v["per_cell"])
+    for v in res.values():
+        v["total"] = float(v["per_cell"][live].sum())
+    ranking = sorted(res, key=lambda k: -res[k]["total"])
+    best = ranking[0]
+    for v in res.values():
+        d = (v["per_cell"] - res[best]["per_cell"])[live]
+        v["delta"] = float(d.sum())
+        v["delta_se"] = float(np.sqrt(d.size) * d.std(ddof=1)) if d.size > 1 else 0.0
+    res["best"], res["ranking"] = best, ranking
+    return res
+
+
 def _simulate_counts_host(E, V, U, clone, total, seed, draw=0, cell_offset=0, chunk=1 << 20, _cumsum=None):
     """Numpy float64 restatement of ``ca_simulate_counts`` (include/clonealign_hip.h states the sampler): rows ``y_n ~ Multinomial(total[n], p_n)`` with
     ``p_ng ~ E[g, clone[n]] exp(U[n] . V[g])``.  Per cell: ``eta`` summed factor by factor, the shift by its maximum over the genes with ``E > 0``,

@@ -990,6 +990,184 @@ int ca_project_cells(ca_handle h, const double* E, const double* V, int32_t K, i
   return CA_OK;
 }
 
+// The clone evidence with psi integrated out, per resident cell and clone (include/clonealign_hip.h has the algorithm and the rules; ca_k_evidence.hip.h the
+// kernels).  ONE sweep over the matrix, ca_project_cells' (k_clone_ll against [log E | V], k_proj_sums: A, B and the constant); then per batch of cells Newton
+// rounds of two launches (k_ev_mom with all moments, k_ev_step) that never read it, queued back to back with the host looking at the pairs' states every few
+// rounds -- freezing is per (cell, clone), so WHEN the host looks changes no result -- and the quadrature: k_ev_nodes, ONE k_ev_mom over the (clone, node) slots
+// (Z0 only), k_ev_reduce.  K = 0 is ca_clone_loglik itself.  Read-only; a sharded handle takes part in ONE small collective, the verdict on the input.
+int ca_clone_evidence(ca_handle h, const double* E, const double* V, int32_t K, int32_t P, const double* X, const double* psi_start, int32_t with_const,
+                      int32_t n_nodes, const double* nodes, const double* weights, int32_t max_iter, double tol, double max_step, double* evidence, double* laplace,
+                      double* psi_mode, double* psi_prec, int32_t* rounds, uint8_t* converged) {
+  if (!h || !E || !evidence || !laplace || !rounds || !converged || (K > 0 && (!psi_mode || !psi_prec))) return CA_ERR_INVALID;
+  CA_NOT_IN_RUN(h);
+  const int D = K + P, Q = n_nodes;
+  auto refuse = [&](const std::string& why) { h->err = "ca_clone_evidence: " + why; return CA_ERR_INVALID; };   // (these are the same on every rank: no collective)
+  if (K < 0 || K > CA_PROJ_KMAX) return refuse("K = " + std::to_string(K) + " is outside [0, " + std::to_string(CA_PROJ_KMAX) + "] (the device limit of the moment kernel)");
+  if (P < 0 || D > CA_LL_DMAX) return refuse("K + P = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]");
+  if (D > 0 && !V) return refuse("K + P = " + std::to_string(D) + " needs V (genes x (K + P))");
+  if (P > 0 && !X) return refuse("P = " + std::to_string(P) + " needs X (cells x P)");
+  if (max_iter < 0) return refuse("max_iter = " + std::to_string(max_iter) + " is negative");
+  if (!(tol > 0.0) || !std::isfinite(tol)) return refuse("tol = " + std::to_string(tol) + " is not a positive finite number");
+  if (!(max_step > 0.0) || !std::isfinite(max_step)) return refuse("max_step = " + std::to_string(max_step) + " is not a positive finite number");
+  if (Q < 1 || Q > CA_EV_QMAX) return refuse("n_nodes = " + std::to_string(Q) + " is outside [1, " + std::to_string(CA_EV_QMAX) + "]");
+  if (!nodes && K > 0) return refuse("nodes is NULL (n_nodes x K)");
+  if (!weights) return refuse("weights is NULL (n_nodes)");
+  {
+    double wsum = 0.0;
+    for (int q = 0; q < Q; ++q) {
+      for (int k = 0; k < K; ++k)
+        if (!std::isfinite(nodes[(size_t)q * K + k])) return refuse("node " + std::to_string(q) + " has a non-finite coordinate (factor " + std::to_string(k) + ")");
+      if (!std::isfinite(weights[q]) || !(weights[q] > 0.0)) return refuse("weight " + std::to_string(q) + " is " + std::to_string(weights[q]) + ": not positive and finite");
+      wsum += weights[q];
+    }
+    if (!(std::fabs(wsum - 1.0) <= 1e-12)) return refuse("the weights sum to " + std::to_string(wsum) + ": off 1 by more than 1e-12");
+  }
+  const int poll_set = (with_const >> 8) & 0xFF, poll = poll_set ? poll_set : 4;   // rounds between two looks at the pairs' states (255: practically never)
+  const bool lgc = (with_const & 1) != 0;
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C, nseg = h->nseg;
+  if (K == 0) {   // nothing to integrate: ca_clone_loglik's value, bit for bit (its launches, its collective)
+    std::vector<double> ll((size_t)N * C + 1);
+    const int rc = clone_ll_impl(h, "ca_clone_evidence", E, X, V, P, lgc ? 1 : 0, 0, N, ll.data(), nullptr);
+    if (rc != CA_OK) return rc;
+    for (int64_t n = 0; n < N; ++n)
+      for (int c = 0; c < C; ++c) {
+        const size_t i = hidx(h->layout, n, c, N, C);
+        evidence[i] = laplace[i] = ll[i];
+        rounds[i] = 0;
+        converged[i] = ll[i] > -HUGE_VAL ? 1 : 0;
+      }
+    return CA_OK;
+  }
+  HIPCK(h, hipSetDevice(h->device));
+  const int ncol = C + D;
+  const int NC = ncol <= 8 ? 8 : ncol <= 16 ? 16 : 32, ngrp = cdiv(ncol, NC), nct = ngrp * NC;
+  std::vector<double> tab, logz0;
+  std::vector<unsigned> zmask;
+  std::string bad = ll_sweep_table(h, E, V, D, NC, ngrp, tab, zmask, logz0);
+  const int NM = 1 + K + K * (K + 1) / 2, NH = K * (K + 1) / 2, nzc = cdiv(G, CA_LL_ZCHUNK), CQ = C * Q;
+  std::vector<double> Ut((size_t)N * CA_LL_DMAX, 0.0), Vt((size_t)Gp * CA_LL_DMAX, 0.0), Ec((size_t)Gp * C, 0.0);   // U = [start | x]
+  for (int64_t n = 0; n < N && bad.empty(); ++n) {
+    for (int k = 0; k < K && psi_start; ++k) {
+      const double v = psi_start[hidx(h->layout, n, k, N, K)];
+      if (!std::isfinite(v)) { bad = "psi_start has a non-finite entry (cell " + std::to_string(n) + ", factor " + std::to_string(k) + ")"; break; }
+      Ut[(size_t)n * CA_LL_DMAX + k] = v;
+    }
+    for (int p = 0; p < P && bad.empty(); ++p) {
+      const double v = X[hidx(h->layout, n, p, N, P)];
+      if (!std::isfinite(v)) { bad = "X has a non-finite entry (cell " + std::to_string(n) + ", covariate " + std::to_string(p) + ")"; break; }
+      Ut[(size_t)n * CA_LL_DMAX + K + p] = v;
+    }
+  }
+  if (bad.empty())
+    for (int g = 0; g < G; ++g) {
+      for (int d = 0; d < D; ++d) Vt[(size_t)g * CA_LL_DMAX + d] = V[hidx(h->layout, g, d, G, D)];
+      for (int c = 0; c < C; ++c) Ec[(size_t)g * C + c] = E[hidx(h->layout, g, c, G, C)];
+    }
+  if (is_sharded(h)) {   // [ranks whose input was refused]
+    std::vector<double> pack{bad.empty() ? 0.0 : 1.0};
+    double* scratch = nullptr;
+    HIPCK(h, hipMalloc((void**)&scratch, sizeof(double)));
+    const int rc = allreduce_host_vec(h, pack, scratch);
+    hipFree(scratch);
+    if (rc != CA_OK) return rc;
+    if (pack[0] != 0.0 && bad.empty()) bad = "another rank refused its input";
+  }
+  if (!bad.empty()) return refuse(bad);
+  if (N == 0) return CA_OK;
+  std::vector<double> lgt, nd(nodes, nodes + (size_t)Q * K), wt(weights, weights + Q);
+  if (lgc) { lgt.resize(CA_LL_LGTAB); for (int k = 0; k < CA_LL_LGTAB; ++k) lgt[(size_t)k] = std::lgamma((double)k + 1.0); }
+  // cells in batches, so that the partial slabs stay below a quarter of a gigabyte (a cell's results do not depend on its batch)
+  const int zcols = std::max(C * NM, CQ), mcols = CQ;   // (one pair of slabs serves the rounds and the quadrature pass)
+  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (int64_t)nzc * (zcols + mcols) + (int64_t)CQ * K + (int64_t)C * (K + NH + 5)) * (int64_t)sizeof(double);
+  const int64_t NB = std::min<int64_t>(N, std::max<int64_t>(CA_TB, (((int64_t)1 << 28) / per_cell) / CA_TB * CA_TB));
+  std::vector<double> b_ev((size_t)NB * C), b_lap((size_t)NB * C), b_ps((size_t)NB * C * K), b_H((size_t)NB * C * NH);
+  std::vector<int> b_rd((size_t)NB * C);
+  std::vector<unsigned char> b_cv((size_t)NB * C), fr((size_t)NB * C);
+  double *tab_d = nullptr, *lgt_d = nullptr, *Ut_d = nullptr, *Vt_d = nullptr, *Ec_d = nullptr, *nd_d = nullptr, *wt_d = nullptr, *part = nullptr, *lgpart = nullptr, *zpart = nullptr,
+         *mpart = nullptr, *A_d = nullptr, *B_d = nullptr, *ps_d = nullptr, *pq_d = nullptr, *fs_d = nullptr, *H_d = nullptr, *lap_d = nullptr, *ev_d = nullptr;
+  unsigned* zm_d = nullptr; unsigned char *fz_d = nullptr, *cv_d = nullptr; int* rd_d = nullptr;
+  auto cleanup = [&]() { hipFree(tab_d); hipFree(lgt_d); hipFree(Ut_d); hipFree(Vt_d); hipFree(Ec_d); hipFree(nd_d); hipFree(wt_d); hipFree(part); hipFree(lgpart); hipFree(zpart);
+                         hipFree(mpart); hipFree(A_d); hipFree(B_d); hipFree(ps_d); hipFree(pq_d); hipFree(fs_d); hipFree(H_d); hipFree(lap_d); hipFree(ev_d); hipFree(zm_d);
+                         hipFree(fz_d); hipFree(cv_d); hipFree(rd_d); };
+#define PCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); cleanup(); return CA_ERR_HIP; } } while (0)
+#define UP(dst, vec) do { PCK(hipMalloc((void**)&dst, (vec).size() * sizeof((vec)[0]))); PCK(hipMemcpyAsync(dst, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, h->stream)); } while (0)
+  UP(tab_d, tab); UP(zm_d, zmask); UP(Ut_d, Ut); UP(Vt_d, Vt); UP(Ec_d, Ec); UP(nd_d, nd); UP(wt_d, wt);
+  if (lgc) UP(lgt_d, lgt);
+  PCK(hipMalloc((void**)&part, (size_t)nseg * NB * nct * sizeof(double)));
+  if (lgc) PCK(hipMalloc((void**)&lgpart, (size_t)nseg * NB * sizeof(double)));
+  PCK(hipMalloc((void**)&zpart, (size_t)nzc * NB * zcols * sizeof(double)));
+  PCK(hipMalloc((void**)&mpart, (size_t)nzc * NB * mcols * sizeof(double)));
+  PCK(hipMalloc((void**)&A_d, (size_t)N * C * sizeof(double)));
+  PCK(hipMalloc((void**)&B_d, (size_t)N * CA_LL_DMAX * sizeof(double)));
+  PCK(hipMalloc((void**)&ps_d, (size_t)NB * C * K * sizeof(double)));
+  PCK(hipMalloc((void**)&pq_d, (size_t)NB * CQ * K * sizeof(double)));
+  PCK(hipMalloc((void**)&fs_d, (size_t)NB * C * sizeof(double)));
+  PCK(hipMalloc((void**)&H_d, (size_t)NB * C * NH * sizeof(double)));
+  PCK(hipMalloc((void**)&lap_d, (size_t)NB * C * sizeof(double)));
+  PCK(hipMalloc((void**)&ev_d, (size_t)NB * C * sizeof(double)));
+  PCK(hipMalloc((void**)&fz_d, (size_t)NB * C));
+  PCK(hipMalloc((void**)&cv_d, (size_t)NB * C));
+  PCK(hipMalloc((void**)&rd_d, (size_t)NB * C * sizeof(int)));
+  PCK(hipMemsetAsync(B_d, 0, (size_t)N * CA_LL_DMAX * sizeof(double), h->stream));   // (the padding factors)
+  for (int64_t n_lo = 0; n_lo < N; n_lo += NB) {
+    const int64_t n_cnt = std::min<int64_t>(NB, N - n_lo);
+    ca_ll_ops o;
+    o.tab = tab_d; o.zmask = zm_d; o.lgtab = lgt_d; o.part = part; o.lgpart = lgpart; o.n_lo = n_lo; o.n_cnt = n_cnt; o.NC = NC; o.ngrp = ngrp;
+    { const int rc = launch_clone_ll(h, o); if (rc != CA_OK) { cleanup(); return rc; } }
+    hipLaunchKernelGGL(k_proj_sums, dim3((unsigned)cdiv(n_cnt * ncol, CA_TB)), dim3(CA_TB), 0, h->stream, part, lgpart, h->s64, A_d, B_d, n_lo, n_cnt, C, D, (int)nseg, nct);
+    PCK(hipGetLastError());
+    ca_evm_ops m;
+    m.Ut = Ut_d; m.Vt = Vt_d; m.Ec = Ec_d; m.ps = ps_d; m.fz = fz_d; m.zpart = zpart; m.mpart = mpart; m.n_lo = n_lo; m.n_cnt = n_cnt; m.K = K; m.Q = 1; m.nslot = C; m.nzc = nzc;
+    m.full = true;
+    ca_evs_ops s;
+    s.zpart = zpart; s.mpart = mpart; s.A = A_d; s.B = B_d; s.Ut = Ut_d; s.nodes = nd_d; s.wts = wt_d; s.ps = ps_d; s.pq = pq_d; s.fz = fz_d; s.conv = cv_d; s.rounds = rd_d;
+    s.fstar = fs_d; s.Hm = H_d; s.lap = lap_d; s.ev = ev_d; s.n_lo = n_lo; s.n_cnt = n_cnt; s.K = K; s.Q = Q; s.nzc = nzc; s.round = 0; s.final = 0; s.tol = tol; s.max_step = max_step;
+    { const int rc = launch_ev_fin(h, s, CA_EV_INIT); if (rc != CA_OK) { cleanup(); return rc; } }
+    bool all_frozen = false;
+    for (int t = 0; t < max_iter && !all_frozen; ++t) {
+      s.round = t;
+      { const int rc = launch_ev_mom(h, m); if (rc != CA_OK) { cleanup(); return rc; } }
+      { const int rc = launch_ev_fin(h, s, CA_EV_STEP); if (rc != CA_OK) { cleanup(); return rc; } }
+      if ((t + 1) % poll == 0 && t + 1 < max_iter) {
+        PCK(hipMemcpyAsync(fr.data(), fz_d, (size_t)n_cnt * C, hipMemcpyDeviceToHost, h->stream));
+        PCK(hipStreamSynchronize(h->stream));
+        all_frozen = std::find(fr.begin(), fr.begin() + n_cnt * C, (unsigned char)CA_EV_LIVE) == fr.begin() + n_cnt * C;
+      }
+    }
+    if (!all_frozen) {   // the pairs that never froze (all of them when max_iter = 0): f and H at the psi they hold
+      s.round = max_iter; s.final = 1;
+      { const int rc = launch_ev_mom(h, m); if (rc != CA_OK) { cleanup(); return rc; } }
+      { const int rc = launch_ev_fin(h, s, CA_EV_STEP); if (rc != CA_OK) { cleanup(); return rc; } }
+    }
+    // the quadrature: the nodes' psi, Z0 of every (clone, node) slot in one launch, the reduction over the nodes
+    { const int rc = launch_ev_fin(h, s, CA_EV_NODES); if (rc != CA_OK) { cleanup(); return rc; } }
+    m.ps = pq_d; m.Q = Q; m.nslot = CQ; m.full = false;
+    { const int rc = launch_ev_mom(h, m); if (rc != CA_OK) { cleanup(); return rc; } }
+    { const int rc = launch_ev_fin(h, s, CA_EV_REDUCE); if (rc != CA_OK) { cleanup(); return rc; } }
+    const size_t nc = (size_t)n_cnt * C;
+    PCK(hipMemcpyAsync(b_ev.data(), ev_d, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipMemcpyAsync(b_lap.data(), lap_d, nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipMemcpyAsync(b_ps.data(), ps_d, nc * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipMemcpyAsync(b_H.data(), H_d, nc * NH * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipMemcpyAsync(b_rd.data(), rd_d, nc * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PCK(hipMemcpyAsync(b_cv.data(), cv_d, nc, hipMemcpyDeviceToHost, h->stream));
+    PCK(hipStreamSynchronize(h->stream));
+    for (int64_t li = 0; li < n_cnt; ++li) {   // the batch's slabs are [column][cell]
+      const int64_t n = n_lo + li;
+      for (int c = 0; c < C; ++c) {
+        const size_t i = hidx(h->layout, n, c, N, C), j = (size_t)c * n_cnt + li;
+        evidence[i] = b_ev[j]; laplace[i] = b_lap[j]; rounds[i] = b_rd[j]; converged[i] = b_cv[j];
+        for (int k = 0; k < K; ++k) psi_mode[hidx(h->layout, n, c * K + k, N, C * K)] = b_ps[((size_t)c * K + k) * n_cnt + li];
+        for (int k = 0; k < NH; ++k) psi_prec[hidx(h->layout, n, c * NH + k, N, C * NH)] = b_H[((size_t)c * NH + k) * n_cnt + li];
+      }
+    }
+  }
+  cleanup();
+#undef UP
+#undef PCK
+  return CA_OK;
+}
+
 // The data side of plot_clonealign (R/plotting.R:177-205) on the resident matrix: S1[g][q] = sum over the cells of group q of lc_ng, S2[g] = sum over all used
 // cells of lc_ng^2, lc_ng = log2(y_ng / sf_n + 1).  Like ca_fit_mse it reads the matrix, the row sums and the overflow list only: no wait for the loop's side
 // stream, no variable, Adam slot or draw index changes.  A sharded handle takes part in both collectives (the used cells' library sizes for the default size

@@ -409,6 +409,42 @@ int launch_proj_step(ca_engine* h, const ca_ps_ops& o) {
   return proj_step_t<2>(h, o);
 }
 
+// ---- k_ev_mom<NS, K, FULL> and the finishers of ca_clone_evidence on one batch of cells (none reads the count matrix) ----
+// Slots per group from the register budget (DESIGN section 7): Newton rounds (all moments) eight clones at K = 1 and four at K = 2, the quadrature pass (Z0 only)
+// sixteen (clone, node) slots at K = 1 and eight at K = 2.
+// the batch's operands: x in U's last columns, V = [W | beta] padded, E compact [Gp][C], the slots' psi, the pairs' states, the chunk slabs
+struct ca_evm_ops { const double *Ut, *Vt, *Ec, *ps; const unsigned char* fz; double *zpart, *mpart; int64_t n_lo, n_cnt; int K, Q, nslot, nzc; bool full; };
+template <int NS, int K, bool FULL>
+int ev_mom_t(ca_engine* h, const ca_evm_ops& o) {
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_ev_mom<NS, K, FULL>), dim3((unsigned)cdiv(o.n_cnt, CA_TB), (unsigned)o.nzc, (unsigned)cdiv(o.nslot, NS)), dim3(CA_TB), 0, h->stream,
+                                                o.Ut, o.Vt, o.Ec, o.ps, o.fz, o.zpart, o.mpart, o.n_lo, o.n_cnt, h->G, h->C, o.Q, o.nslot));
+  return CA_OK;
+}
+int launch_ev_mom(ca_engine* h, const ca_evm_ops& o) {
+  if (o.full) return o.K == 1 ? ev_mom_t<8, 1, true>(h, o) : ev_mom_t<4, 2, true>(h, o);
+  return o.K == 1 ? ev_mom_t<16, 1, false>(h, o) : ev_mom_t<8, 2, false>(h, o);   // (sixteen slots at K = 2 spill: 32 psi registers beside the 32 of m and Z0)
+}
+// the per-pair state of a batch: psi of the clones, state, rounds, converged, f*, H, laplace, evidence; the quadrature's nodes, weights and node psi
+struct ca_evs_ops { const double *zpart, *mpart, *A, *B, *Ut, *nodes, *wts; double *ps, *pq; unsigned char *fz, *conv; int* rounds; double *fstar, *Hm, *lap, *ev;
+                    int64_t n_lo, n_cnt; int K, Q, nzc, round, final; double tol, max_step; };
+template <int K>
+int ev_fin_t(ca_engine* h, const ca_evs_ops& o, int what) {
+  const dim3 grid((unsigned)cdiv(o.n_cnt * h->C, CA_TB));
+  if (what == 0)
+    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_ev_init<K>), grid, dim3(CA_TB), 0, h->stream, o.A, o.Ut, o.ps, o.fz, o.rounds, o.conv, o.fstar, o.Hm, o.ev, o.lap, o.n_lo, o.n_cnt, h->C));
+  else if (what == 1)
+    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_ev_step<K>), grid, dim3(CA_TB), 0, h->stream, o.zpart, o.mpart, o.A, o.B, o.Ut, h->s64, o.ps, o.fz, o.rounds, o.conv, o.fstar, o.Hm,
+                                                  o.n_lo, o.n_cnt, h->C, o.nzc, o.round, o.final, o.tol, o.max_step));
+  else if (what == 2)
+    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_ev_nodes<K>), grid, dim3(CA_TB), 0, h->stream, o.ps, o.fz, o.fstar, o.Hm, o.nodes, o.pq, o.lap, o.n_cnt, h->C, o.Q));
+  else
+    LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL((k_ev_reduce<K>), grid, dim3(CA_TB), 0, h->stream, o.zpart, o.mpart, o.A, o.B, o.Ut, h->s64, o.pq, o.fz, o.fstar, o.lap, o.nodes, o.wts,
+                                                  o.ev, o.n_lo, o.n_cnt, h->C, o.Q, o.nzc));
+  return CA_OK;
+}
+enum { CA_EV_INIT = 0, CA_EV_STEP = 1, CA_EV_NODES = 2, CA_EV_REDUCE = 3 };
+int launch_ev_fin(ca_engine* h, const ca_evs_ops& o, int what) { return o.K == 1 ? ev_fin_t<1>(h, o, what) : ev_fin_t<2>(h, o, what); }
+
 // ---- k_simulate: one launch over a list of work items of ca_simulate_counts (no engine: the call owns its stream) ----
 // The search table's plan for G genes: S = genes per LDS entry (1: the whole table in LDS), whether the row's histogram fits in LDS beside it, the LDS bytes.
 struct ca_sim_plan { int S, nco, hist_lds; size_t lds; };

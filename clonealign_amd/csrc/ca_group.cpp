@@ -900,6 +900,54 @@ int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, 
   return CA_OK;
 }
 
+int ca_group_clone_evidence(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X, const double* psi_start, int32_t with_const,
+                            int32_t n_nodes, const double* nodes, const double* weights, int32_t max_iter, double tol, double max_step, double* evidence, double* laplace,
+                            double* psi_mode, double* psi_prec, int32_t* rounds, uint8_t* converged) {
+  GROUP_ALIVE(g);
+  if (!E || !evidence || !laplace || !rounds || !converged || (K > 0 && (!psi_mode || !psi_prec))) return CA_ERR_INVALID;
+  if (K < 0 || P < 0 || K + P > 8 || (P > 0 && !X)) {   // (what decides how the cell arrays are sliced; the ranks refuse everything else in their own words)
+    g->err = K < 0 || P < 0 || K + P > 8 ? "ca_clone_evidence: K + P = " + std::to_string(K + P) + " is outside [0, 8]" : "ca_clone_evidence: P = " + std::to_string(P) + " needs X (cells x P)";
+    return CA_ERR_INVALID;
+  }
+  const size_t W = (size_t)g->W;
+  const int64_t C = g->C, CK = C * K, CH = C * (K * (K + 1) / 2);
+  std::vector<std::vector<double>> xs(W), pss(W), o_ev(W), o_lap(W), o_ps(W), o_H(W);
+  std::vector<std::vector<int32_t>> o_rd(W);
+  std::vector<std::vector<uint8_t>> o_cv(W);
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t lo = g->shard[r].lo, hi = g->shard[r].hi, n = hi - lo;
+    if (P > 0) slice_rows(X, g->layout, g->N, P, lo, hi, xs[r]);
+    if (K > 0 && psi_start) slice_rows(psi_start, g->layout, g->N, K, lo, hi, pss[r]);
+    o_ev[r].resize((size_t)(n * C) + 1); o_lap[r].resize((size_t)(n * C) + 1); o_ps[r].resize((size_t)(n * CK) + 1); o_H[r].resize((size_t)(n * CH) + 1);
+    o_rd[r].resize((size_t)(n * C) + 1); o_cv[r].resize((size_t)(n * C) + 1);
+  }
+  const int s = settle(g, dispatch(g, [&](int ri) {
+    const size_t r = (size_t)ri;
+    return ca_clone_evidence(g->h[r], E, V, K, P, P > 0 ? xs[r].data() : nullptr, K > 0 && psi_start ? pss[r].data() : nullptr, with_const, n_nodes, nodes, weights, max_iter, tol,
+                             max_step, o_ev[r].data(), o_lap[r].data(), o_ps[r].data(), o_H[r].data(), o_rd[r].data(), o_cv[r].data());
+  }), "ca_clone_evidence");
+  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  if (s != CA_OK) return s;
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t lo = g->shard[r].lo, hi = g->shard[r].hi, n = hi - lo;
+    scatter_rows(o_ev[r].data(), g->layout, g->N, C, lo, hi, evidence);
+    scatter_rows(o_lap[r].data(), g->layout, g->N, C, lo, hi, laplace);
+    if (K > 0) { scatter_rows(o_ps[r].data(), g->layout, g->N, CK, lo, hi, psi_mode); scatter_rows(o_H[r].data(), g->layout, g->N, CH, lo, hi, psi_prec); }
+    for (int64_t c = 0; c < C; ++c)
+      for (int64_t i = 0; i < n; ++i) {
+        rounds[hidx(g->layout, lo + i, c, g->N, C)] = o_rd[r][(size_t)hidx(g->layout, i, c, n, C)];
+        converged[hidx(g->layout, lo + i, c, g->N, C)] = o_cv[r][(size_t)hidx(g->layout, i, c, n, C)];
+      }
+  }
+  return CA_OK;
+}
+
 int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell, int32_t n_groups, const double* size_factor, double* S1, double* S2, int64_t* n_group) {
   GROUP_ALIVE(g);
   if (!group_of_cell || !S1 || !S2 || !n_group) return CA_ERR_INVALID;

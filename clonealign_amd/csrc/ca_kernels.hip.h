@@ -952,6 +952,7 @@ __global__ void __launch_bounds__(CA_TB, (DEPTH == 1 && !C16 && !S2F) ? CA_YS_RI
 #include "ca_k_pairll.hip.h"   // log-likelihood under a mixture of two clones (ca_clone_pair_loglik): a wave per cell over its compacted non-zero counts, a lane per (pair, weight)
 #include "ca_k_dmll.hip.h"   // Dirichlet-multinomial log-likelihood per clone on a grid of concentrations (ca_clone_loglik_dm): k_pair_ll's walk, a lane per (clone, concentration), exp(eta) at compaction time
 #include "ca_k_project.hip.h" // per-cell MAP psi and clone posterior for cells outside the fit (ca_project_cells): moments over the genes, a lane per cell; never reads Y
+#include "ca_k_evidence.hip.h"  // clone evidence with psi integrated out (ca_clone_evidence): per (cell, clone) Newton mode, Laplace value and quadrature; moments per slot, a lane per cell; never reads Y
 #include "ca_k_simulate.hip.h"   // count rows drawn from a fitted model (ca_simulate_counts): per-cell cumulative weights in LDS, Philox draws, binary search, integer histogram; never reads Y
 #include "ca_k_predictive.hip.h"   // replicate rows of ca_simulate_counts reduced where they are drawn (ca_predictive_stats): the table once per cell, per replicate one float64 and int64 per-gene totals; the rows are never stored
 #include "ca_k_logexpr.hip.h"   // log-expression sums per gene and cell group on the resident matrix (ca_logexpr_sums): one float64 sweep, pieces cut at group boundaries

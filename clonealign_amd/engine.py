@@ -59,6 +59,8 @@ EXPORTS = (
     "ca_simulate_counts", "ca_simulate_kernel_ms",
     # log-likelihoods and per-clone gene totals of replicate rows that never leave the device (predictive_stats), no handle, additions to ABI 6
     "ca_predictive_stats", "ca_predictive_kernel_ms",
+    # clone evidence with psi integrated out: Newton mode, Laplace value and quadrature per (cell, clone) (clone_evidence / heldout_evidence), additions to ABI 6
+    "ca_clone_evidence", "ca_group_clone_evidence",
 )
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
@@ -175,6 +177,8 @@ def load_library(path=None):
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ca_clone_evidence.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_simulate_counts.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                        C.c_int64, C.c_int32, C.c_void_p, C.c_char_p]
     lib.ca_simulate_kernel_ms.argtypes = [C.POINTER(C.c_double)]
@@ -213,6 +217,7 @@ def load_library(path=None):
     lib.ca_group_logexpr_sums.argtypes = lib.ca_logexpr_sums.argtypes
     lib.ca_group_clone_loglik.argtypes = lib.ca_clone_loglik.argtypes
     lib.ca_group_project_cells.argtypes = lib.ca_project_cells.argtypes
+    lib.ca_group_clone_evidence.argtypes = lib.ca_clone_evidence.argtypes
     lib.ca_group_clone_pair_loglik.argtypes = lib.ca_clone_pair_loglik.argtypes
     lib.ca_group_clone_loglik_by_block.argtypes = lib.ca_clone_loglik_by_block.argtypes
     lib.ca_group_clone_loglik_dm.argtypes = lib.ca_clone_loglik_dm.argtypes
@@ -867,6 +872,71 @@ class HipEngine:
         self._ck(self._fn("project_cells")(self.h, ptr(Em), ptr(Vm), K, P, ptr(Xm), ptr(lpm), ptr(psm), flags, int(max_iter), float(tol), float(max_step),
                                            ptr(psi) if K > 0 else None, ptr(ll), ptr(pr), ptr(obj), ptr(rounds), ptr(conv)))
         return {"psi": psi, "ll": ll, "clone_probs": pr, "objective": obj, "rounds": rounds, "converged": conv.astype(bool)}
+
+    def clone_evidence(self, E, V=None, K=0, X=None, psi_start=None, nodes=None, weights=None, const=True, max_iter=50, tol=1e-9, max_step=1.0,
+                       poll_every=None):
+        """Clone evidence of the resident cells with ``psi`` integrated out (ca_clone_evidence; include/clonealign_hip.h has the algorithm): per (cell,
+        clone) the mode of ``f(psi) = log Multinomial(y | c, psi) - |psi|^2 / 2`` by safeguarded Newton, the Laplace value and a quadrature at the caller's
+        rule for the standard normal measure, centred at the mode and scaled by the Cholesky factor of the precision.  ``E`` [G, C]; ``V`` = ``[W | beta]``
+        [G, K + P] with ``K`` <= 2 free factors (the device limit); ``X`` [N, P]; ``psi_start`` [N, K] or None = 0 (one start for every clone); ``nodes``
+        [Q, K] and ``weights`` [Q] (``api.gauss_hermite_rule``; None: the single node 0, the Laplace value), Q <= 64.  One sweep over the resident matrix,
+        then launches that do not read it.  Returns a dict: ``evidence`` and ``laplace`` [N, C], ``psi_mode`` [N, C, K], ``psi_prec`` [N, C, K (K + 1) / 2]
+        (the precision's entries k <= l), ``rounds`` [N, C] int32, ``converged`` [N, C] bool -- a pair with ``converged`` False holds a value that is
+        deterministic but not to be trusted.  ``poll_every``: rounds between two host reads of the pairs' states (None = 4); no result depends on it.
+        Changes nothing in the engine; two calls agree bit for bit."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"clone_evidence: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        K = int(K)
+        Vm = Xm = psm = None
+        D = 0
+        if V is not None:
+            V = np.asarray(V, dtype=np.float64)
+            if V.ndim != 2 or V.shape[0] != self.G:
+                raise ValueError(f"clone_evidence: V is {V.shape}; expected ({self.G}, K + P)")
+            D = int(V.shape[1])
+        P = D - K
+        if P < 0:
+            raise ValueError(f"clone_evidence: V has {D} columns but K = {K}")
+        if D > 0:
+            Vm = np.require(V, requirements=[self._order, "A"])
+        if X is not None or P > 0:
+            X = np.zeros((self.N, 0)) if X is None else np.asarray(X, dtype=np.float64)
+            if X.shape != (self.N, P):
+                raise ValueError(f"clone_evidence: X is {X.shape}; V has K + P = {D} columns with K = {K}, so X must be ({self.N}, {P})")
+            Xm = np.require(X, requirements=[self._order, "A"]) if P > 0 else None
+        if psi_start is not None and K > 0:
+            psi_start = np.asarray(psi_start, dtype=np.float64)
+            if psi_start.shape != (self.N, K):
+                raise ValueError(f"clone_evidence: psi_start is {psi_start.shape}; expected ({self.N}, {K})")
+            psm = np.require(psi_start, requirements=[self._order, "A"])
+        if (nodes is None) != (weights is None):
+            raise ValueError("clone_evidence: nodes and weights go together (both, or neither)")
+        if nodes is None:
+            nodes, weights = np.zeros((1, max(K, 0))), np.ones(1)
+        wts = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        nd = np.ascontiguousarray(nodes, dtype=np.float64)             # (row-major always: node by node)
+        Q = int(wts.shape[0])
+        if nd.size != Q * max(K, 0):
+            raise ValueError(f"clone_evidence: nodes is {nd.shape}; {Q} weights and K = {K} need ({Q}, {K})")
+        if poll_every is not None and not 1 <= int(poll_every) <= 255:
+            raise ValueError("clone_evidence: poll_every must be in [1, 255]")
+        Kp = max(K, 0)
+        NH = Kp * (Kp + 1) // 2
+        Em = np.require(E, requirements=[self._order, "A"])
+        ev = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
+        lap = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
+        mode = np.zeros((self.N, self.C * Kp), dtype=np.float64, order=self._order)
+        prec = np.zeros((self.N, self.C * NH), dtype=np.float64, order=self._order)
+        rounds = np.zeros((self.N, self.C), dtype=np.int32, order=self._order)
+        conv = np.zeros((self.N, self.C), dtype=np.uint8, order=self._order)
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        flags = int(bool(const)) | ((int(poll_every) if poll_every is not None else 0) << 8)
+        self._ck(self._fn("clone_evidence")(self.h, ptr(Em), ptr(Vm), K, P, ptr(Xm), ptr(psm), flags, Q, ptr(nd), ptr(wts), int(max_iter), float(tol),
+                                            float(max_step), ptr(ev), ptr(lap), ptr(mode), ptr(prec), ptr(rounds), ptr(conv)))
+        return {"evidence": np.ascontiguousarray(ev), "laplace": np.ascontiguousarray(lap), "psi_mode": np.ascontiguousarray(mode).reshape(self.N, self.C, Kp),
+                "psi_prec": np.ascontiguousarray(prec).reshape(self.N, self.C, NH), "rounds": np.ascontiguousarray(rounds),
+                "converged": np.ascontiguousarray(conv).astype(bool)}
 
     def synchronize(self):
         self._ck(self.lib.ca_synchronize(self.h))

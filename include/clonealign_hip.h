@@ -556,6 +556,45 @@ int ca_project_cells(ca_handle h, const double* E /* G x C */, const double* V /
                      int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi /* N x K */, double* ll /* N x C */,
                      double* clone_probs /* N x C */, double* objective /* N */, int32_t* rounds /* N */, uint8_t* converged /* N */);
 
+/* The clone evidence with psi integrated out: for every resident cell n and clone c
+ *   evidence_nc = log Integral Normal(psi; 0, I_K) Multinomial(y_n | p_n.c(psi)) dpsi
+ * under a fit's GENE-LEVEL parameters -- the quantity that can be compared between fits (and between numbers of factors K) on cells the fits never saw;
+ * ca_project_cells' value at the MAP psi is a maximum over psi and never prefers the smaller model.  Notation of ca_project_cells.  With psi in R^K
+ *   f_nc(psi) = A_nc + psi . B_n[:K] + x_n . B_n[K:] - s_n log Z_c(psi, x_n) - |psi|^2 / 2,   Z_c = sum_g E_gc exp(psi . W_g + x_n . beta_g)
+ * is strictly concave in psi.  Per (cell, clone):
+ *   once, one sweep over the resident counts:  A, B, s as in ca_project_cells
+ *   1. MODE: safeguarded Newton from psi_start_n (the same start for every clone; NULL = 0).  Round t = 0 .. max_iter - 1, for every pair not yet frozen:
+ *      m = max_g eta_g, Z0, Z1[k], Z2[k][l] as in ca_project_cells but at the PAIR's psi;  mean = Z1 / Z0, cov = Z2 / Z0 - mean mean^T;
+ *      g = B_n[:K] - s_n mean - psi,  H = I + s_n cov,  d = H^-1 g (closed form for K <= 2), scaled to max-norm max_step when max|d| exceeds it;  psi += d.
+ *      The pair is FROZEN when max|d| (before scaling) <= tol -- before the update is applied; f* = f(psi) and H are that round's.
+ *      A pair that reaches max_iter without freezing gets one more evaluation of f and H at the psi it holds and converged = 0: H is positive definite
+ *      everywhere, so its values below are deterministic, but they are NOT to be trusted.
+ *   2. LAPLACE: H = L L^T (Cholesky, closed form), laplace_nc = f* - sum_k log L_kk  (the (2 pi)^(K/2) factors cancel against the prior's normaliser).
+ *   3. QUADRATURE: nodes z_q (n_nodes x K, row-major ALWAYS) and weights w_q of a rule for the standard normal measure (sum w_q = 1; a Gauss-Hermite tensor
+ *      rule, say).  psi_q = psi* + L^-T z_q, and
+ *        evidence_nc = laplace_nc + log sum_q w_q exp( f(psi_q) - f* + |z_q|^2 / 2 ),   the sum under a running maximum in ascending q.
+ *      n_nodes = 1 with z = 0 and w = 1 gives the Laplace value, bit for bit.
+ * Outputs: evidence, laplace (N x C), psi_mode (N x (C K), column c K + k), psi_prec (N x (C K (K + 1) / 2), column c K (K + 1) / 2 + j: the entries of H with
+ * k <= l, row by row), rounds (N x C: rounds evaluated -- t + 1 for a pair frozen in round t, max_iter otherwise), converged (N x C).  Rules:
+ *   a pair with A_nc = -inf (a positive count against E = 0): evidence = laplace = -inf, rounds 0, converged 0, psi_mode = the start, psi_prec = I; no NaN anywhere.
+ *   s_n = 0: the mode is 0 and evidence = laplace = 0 (to the rounding of sum w_q).
+ *   K = 0: evidence = laplace = ca_clone_loglik's value bit for bit, zero rounds, converged 1 (0 where the value is -inf); nodes may be NULL.
+ * with_const: bit 0 as in ca_clone_loglik; bits 8..15: rounds between two host reads of the pairs' states, as in ca_project_cells -- no result depends on it.
+ * Matrices in the problem's layout; everything float64, sums in a fixed order, no atomics: two calls agree bit for bit, a cell's outputs depend on its own row
+ * alone, and a cell-sharded group returns the single handle's bits.  K <= 2 is the device limit, as for ca_project_cells.
+ * CA_ERR_INVALID (with a message naming the offender): everything ca_project_cells refuses (K outside [0, 2]; K + P outside [0, 8]; V NULL with K + P > 0; X NULL
+ * with P > 0; max_iter < 0; tol or max_step non-positive or non-finite; ca_clone_loglik's refusals on E and V; a non-finite entry of X or psi_start); n_nodes
+ * outside [1, 64]; nodes (K > 0) or weights NULL; a non-finite node; a weight that is not positive and finite; weights whose sum is off 1 by more than 1e-12.
+ * Sharded handle: the cell-indexed arrays cover the local cells; the only collective is the verdict on the input.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_clone_evidence(ca_handle h, const double* E /* G x C */, const double* V /* G x (K + P), or NULL */, int32_t K, int32_t P,
+                      const double* X /* N x P, or NULL */, const double* psi_start /* N x K, or NULL = 0 */, int32_t with_const,
+                      int32_t n_nodes, const double* nodes /* n_nodes x K */, const double* weights /* n_nodes */,
+                      int32_t max_iter, double tol, double max_step,
+                      double* evidence /* N x C */, double* laplace /* N x C */,
+                      double* psi_mode /* N x (C K) */, double* psi_prec /* N x (C K(K+1)/2), H entries k <= l */,
+                      int32_t* rounds /* N x C */, uint8_t* converged /* N x C */);
+
 /* The data side of plot_clonealign() (R/plotting.R:177-205: the dense t(logcounts), its N*G-row long table, the per-gene mean and
  * sd and the per (clone, gene) means of the z-scores) as sums from ONE sweep over the resident counts (any storage; nothing N x G
  * is made on the host).  group_of_cell[n] in [0, n_groups), or -1 for a cell left out of every sum and count; n_groups in [1, 64].
@@ -785,6 +824,11 @@ int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, 
                            const double* log_prior /* N x C, all cells, or NULL */, const double* psi_start /* N x K, all cells, or NULL */,
                            int32_t with_const, int32_t max_iter, double tol, double max_step, double* psi, double* ll, double* clone_probs,
                            double* objective, int32_t* rounds, uint8_t* converged);
+/* ca_clone_evidence over the group: X, psi_start and every output hold ALL cells (sliced by the shards); each cell's results are the single handle's, bit for bit */
+int ca_group_clone_evidence(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X /* N x P, all cells, or NULL */,
+                            const double* psi_start /* N x K, all cells, or NULL */, int32_t with_const, int32_t n_nodes, const double* nodes, const double* weights,
+                            int32_t max_iter, double tol, double max_step, double* evidence, double* laplace, double* psi_mode, double* psi_prec,
+                            int32_t* rounds, uint8_t* converged);
 /* ca_logexpr_sums (R/plotting.R:177-205) over the group: group_of_cell and size_factor (or NULL) hold ALL cells; the totals are rank 0's (every rank has the same) */
 int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell /* N, all cells */, int32_t n_groups,
                           const double* size_factor /* N, all cells, or NULL */, double* S1, double* S2, int64_t* n_group);
