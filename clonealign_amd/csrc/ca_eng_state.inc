@@ -306,6 +306,41 @@ int dalloc(ca_engine* h, T** p, int64_t n) {
   return CA_OK;
 }
 
+// The device memory of ONE CALL on the resident matrix (ca_eng_init.inc, ca_eng_score.inc; the engine's own buffers are dalloc's): what the call allocated,
+// freed when it returns -- on every path, after waiting for the stream (queued copies read the call's host vectors until then: declare the owner AFTER them).
+// A failed allocation or copy is kept in rc with the engine's message; later requests do nothing, so a block of requests is checked once.
+struct ca_call_mem {
+  ca_engine* h;
+  std::vector<void*> owned;
+  int rc = CA_OK;
+  explicit ca_call_mem(ca_engine* h_) : h(h_) {}
+  ca_call_mem(const ca_call_mem&) = delete;
+  ca_call_mem& operator=(const ca_call_mem&) = delete;
+  ~ca_call_mem() {
+    if (!owned.empty()) hipStreamSynchronize(h->stream);
+    for (void* p : owned) hipFree(p);
+  }
+  bool ok(hipError_t e, const char* what, size_t bytes) {
+    if (e == hipSuccess) return true;
+    h->err = std::string(what) + " of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e);
+    rc = CA_ERR_HIP;
+    return false;
+  }
+  template <typename T>
+  T* alloc(int64_t count) {
+    void* p = nullptr;
+    if (rc != CA_OK || !ok(hipMalloc(&p, (size_t)count * sizeof(T)), "hipMalloc", (size_t)count * sizeof(T))) return nullptr;
+    if (p) owned.push_back(p);
+    return static_cast<T*>(p);
+  }
+  template <typename T>
+  T* upload(const std::vector<T>& v) {   // (the copy is queued on h->stream)
+    T* p = alloc<T>((int64_t)v.size());
+    if (p) ok(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync", v.size() * sizeof(T));
+    return rc == CA_OK ? p : nullptr;
+  }
+};
+
 // ---- profiling wrappers ------------------------------------------------------------------
 int prof_flush(ca_engine* h) {
   if (h->ev_used == 0) return CA_OK;

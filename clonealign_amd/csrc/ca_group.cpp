@@ -208,6 +208,65 @@ void scatter_rows(const double* src, int layout, int64_t N, int64_t cols, int64_
     for (int64_t i = 0; i < n; ++i) dst[hidx(layout, lo + i, c, N, cols)] = src[hidx(layout, i, c, n, cols)];
 }
 
+// settle() for a call whose ranks vote on their inputs (one collective in the engine: every rank returns the same code).  When every rank refused, the group
+// speaks with the words of the first rank whose OWN input it was; that rank numbers its cells from its shard's start.
+int settle_verdict(ca_group* g, const std::vector<int>& rc, const char* what) {
+  const int s = settle(g, rc, what);
+  if (s == CA_ERR_INVALID && !g->dead)
+    for (int r = 0; r < g->W; ++r) {
+      const std::string why = ca_last_error(g->h[(size_t)r]);
+      if (why.find("another rank refused") != std::string::npos) continue;
+      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
+      break;
+    }
+  return s;
+}
+
+// the scoring calls' D / U / V rule, in the engine's words (U is sliced by it before any rank is called)
+bool duv_ok(ca_group* g, const char* who, int32_t D, const double* U, const double* V) {
+  if (D >= 0 && D <= 8 && (D == 0 || (U && V))) return true;
+  g->err = std::string(who) + ": D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
+  return false;
+}
+
+// How a call over the cells [cell_lo, cell_lo + cell_cnt) is cut: rank r takes the cells of the range that lie in its shard, [lo[r], hi[r]) in the group's
+// numbering (an empty part is still called: the verdict is collective), with its shard's rows of U.
+struct RangePlan {
+  const ca_group* g;
+  int64_t cell_lo, cell_cnt;
+  std::vector<int64_t> lo, hi;
+  std::vector<std::vector<double>> us;
+  int64_t rows(size_t r) const { return hi[r] - lo[r]; }
+  int64_t local_lo(size_t r) const { return lo[r] - g->shard[r].lo; }
+  const double* u(size_t r) const { return us[r].empty() ? nullptr : us[r].data(); }
+  std::vector<std::vector<double>> outputs(int64_t cols) const {   // one buffer of rows(r) x cols per rank (never empty)
+    std::vector<std::vector<double>> o(lo.size());
+    for (size_t r = 0; r < o.size(); ++r) o[r].resize((size_t)(rows(r) * cols) + 1);
+    return o;
+  }
+  void scatter(const std::vector<std::vector<double>>& o, int64_t cols, double* dst) const {
+    for (size_t r = 0; r < o.size(); ++r) scatter_rows(o[r].data(), g->layout, cell_cnt, cols, lo[r] - cell_lo, hi[r] - cell_lo, dst);
+  }
+};
+// false: the range is refused (it decides how the call is cut; the ranks refuse everything else in their own words)
+bool plan_range(ca_group* g, const char* who, int64_t cell_lo, int64_t cell_cnt, const double* U, int32_t D, RangePlan& p) {
+  if (cell_lo < 0 || cell_cnt < 0 || cell_lo > g->N || cell_cnt > g->N - cell_lo) {
+    g->err = std::string(who) + ": the cell range [" + std::to_string(cell_lo) + ", " + std::to_string(cell_lo) + " + " + std::to_string(cell_cnt) + ") is outside [0, " +
+             std::to_string(g->N) + "]";
+    return false;
+  }
+  const size_t W = (size_t)g->W;
+  p.g = g; p.cell_lo = cell_lo; p.cell_cnt = cell_cnt;
+  p.lo.resize(W); p.hi.resize(W); p.us.resize(W);
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t slo = g->shard[r].lo, shi = g->shard[r].hi;
+    p.lo[r] = std::min(std::max(cell_lo, slo), shi);
+    p.hi[r] = std::max(std::min(cell_lo + cell_cnt, shi), p.lo[r]);
+    if (D > 0) slice_rows(U, g->layout, g->N, D, slo, shi, p.us[r]);
+  }
+  return true;
+}
+
 size_t dtype_bytes(int dt) { return dt == CA_F64 ? 8 : (dt == CA_F32 || dt == CA_I32) ? 4 : dt == CA_U16 ? 2 : 1; }
 
 // a sparse shard: its cells as a cell_index subset over the caller's compressed arrays; a host CSR matrix is rebased to the rank's rows
@@ -689,27 +748,14 @@ int ca_group_fit_mse(ca_group_handle g, const int32_t* clone_of_cell, const doub
 int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, double* ll) {
   GROUP_ALIVE(g);
   if (!E || !ll) return CA_ERR_INVALID;
-  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
-    g->err = "ca_clone_loglik: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
-    return CA_ERR_INVALID;
-  }
-  std::vector<std::vector<double>> us((size_t)g->W), part((size_t)g->W);
-  for (int r = 0; r < g->W; ++r) {
-    if (D > 0) slice_rows(U, g->layout, g->N, D, g->shard[(size_t)r].lo, g->shard[(size_t)r].hi, us[(size_t)r]);
-    part[(size_t)r].resize((size_t)((g->shard[(size_t)r].hi - g->shard[(size_t)r].lo) * g->C));
-  }
-  const int s = settle(g, dispatch(g, [&](int r) {
-    return ca_clone_loglik(g->h[(size_t)r], E, D > 0 ? us[(size_t)r].data() : nullptr, V, D, with_const, part[(size_t)r].data());
+  RangePlan p;   // (every cell: each rank's part is its shard)
+  if (!duv_ok(g, "ca_clone_loglik", D, U, V) || !plan_range(g, "ca_clone_loglik", 0, g->N, U, D, p)) return CA_ERR_INVALID;
+  auto part = p.outputs(g->C);
+  const int s = settle_verdict(g, dispatch(g, [&](int r) {
+    return ca_clone_loglik(g->h[(size_t)r], E, p.u((size_t)r), V, D, with_const, part[(size_t)r].data());
   }), "ca_clone_loglik");
-  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
-    for (int r = 0; r < g->W; ++r) {
-      const std::string why = ca_last_error(g->h[(size_t)r]);
-      if (why.find("another rank refused") != std::string::npos) continue;
-      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
-      break;
-    }
   if (s != CA_OK) return s;
-  for (int r = 0; r < g->W; ++r) scatter_rows(part[(size_t)r].data(), g->layout, g->N, g->C, g->shard[(size_t)r].lo, g->shard[(size_t)r].hi, ll);
+  p.scatter(part, g->C, ll);
   return CA_OK;
 }
 
@@ -717,45 +763,17 @@ int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double*
                                int64_t cell_lo, int64_t cell_cnt, double* ll, double* pair_ll) {
   GROUP_ALIVE(g);
   if (!E || !pair_ll) { g->err = std::string("ca_clone_pair_loglik: ") + (!E ? "E" : "pair_ll") + " is NULL"; return CA_ERR_INVALID; }
-  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
-    g->err = "ca_clone_pair_loglik: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
-    return CA_ERR_INVALID;
-  }
-  if (cell_lo < 0 || cell_cnt < 0 || cell_lo > g->N || cell_cnt > g->N - cell_lo) {   // (what decides how the range is cut; the ranks refuse everything else in their own words)
-    g->err = "ca_clone_pair_loglik: the cell range [" + std::to_string(cell_lo) + ", " + std::to_string(cell_lo) + " + " + std::to_string(cell_cnt) + ") is outside [0, " +
-             std::to_string(g->N) + "]";
-    return CA_ERR_INVALID;
-  }
-  const size_t W = (size_t)g->W;
+  RangePlan p;
+  if (!duv_ok(g, "ca_clone_pair_loglik", D, U, V) || !plan_range(g, "ca_clone_pair_loglik", cell_lo, cell_cnt, U, D, p)) return CA_ERR_INVALID;
   const int64_t MW = (int64_t)g->C * (g->C - 1) / 2 * std::max<int64_t>(0, std::min<int64_t>(n_weights, 8));
-  // rank r takes the cells of the range that lie in its shard: [lo[r], hi[r]) in the group's numbering (an empty part is still called: the verdict is collective)
-  std::vector<int64_t> lo(W), hi(W);
-  std::vector<std::vector<double>> us(W), o_ll(W), o_pl(W);
-  for (size_t r = 0; r < W; ++r) {
-    const int64_t slo = g->shard[r].lo, shi = g->shard[r].hi;
-    lo[r] = std::min(std::max(cell_lo, slo), shi);
-    hi[r] = std::max(std::min(cell_lo + cell_cnt, shi), lo[r]);
-    if (D > 0) slice_rows(U, g->layout, g->N, D, slo, shi, us[r]);
-    if (ll) o_ll[r].resize((size_t)((hi[r] - lo[r]) * g->C) + 1);
-    o_pl[r].resize((size_t)((hi[r] - lo[r]) * MW) + 1);
-  }
-  const int s = settle(g, dispatch(g, [&](int ri) {
+  auto o_ll = p.outputs(ll ? g->C : 0), o_pl = p.outputs(MW);
+  const int s = settle_verdict(g, dispatch(g, [&](int ri) {
     const size_t r = (size_t)ri;
-    return ca_clone_pair_loglik(g->h[r], E, D > 0 ? us[r].data() : nullptr, V, D, with_const, weights, n_weights, lo[r] - g->shard[r].lo, hi[r] - lo[r],
-                                ll ? o_ll[r].data() : nullptr, o_pl[r].data());
+    return ca_clone_pair_loglik(g->h[r], E, p.u(r), V, D, with_const, weights, n_weights, p.local_lo(r), p.rows(r), ll ? o_ll[r].data() : nullptr, o_pl[r].data());
   }), "ca_clone_pair_loglik");
-  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
-    for (int r = 0; r < g->W; ++r) {
-      const std::string why = ca_last_error(g->h[(size_t)r]);
-      if (why.find("another rank refused") != std::string::npos) continue;
-      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
-      break;
-    }
   if (s != CA_OK) return s;
-  for (size_t r = 0; r < W; ++r) {
-    if (ll) scatter_rows(o_ll[r].data(), g->layout, cell_cnt, g->C, lo[r] - cell_lo, hi[r] - cell_lo, ll);
-    scatter_rows(o_pl[r].data(), g->layout, cell_cnt, MW, lo[r] - cell_lo, hi[r] - cell_lo, pair_ll);
-  }
+  if (ll) p.scatter(o_ll, g->C, ll);
+  p.scatter(o_pl, MW, pair_ll);
   return CA_OK;
 }
 
@@ -763,45 +781,17 @@ int ca_group_clone_loglik_dm(ca_group_handle g, const double* E, const double* U
                              int64_t cell_lo, int64_t cell_cnt, double* ll, double* dm_ll) {
   GROUP_ALIVE(g);
   if (!E || !conc || !dm_ll) { g->err = std::string("ca_clone_loglik_dm: ") + (!E ? "E" : !conc ? "conc" : "dm_ll") + " is NULL"; return CA_ERR_INVALID; }
-  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
-    g->err = "ca_clone_loglik_dm: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
-    return CA_ERR_INVALID;
-  }
-  if (cell_lo < 0 || cell_cnt < 0 || cell_lo > g->N || cell_cnt > g->N - cell_lo) {   // (what decides how the range is cut; the ranks refuse everything else in their own words)
-    g->err = "ca_clone_loglik_dm: the cell range [" + std::to_string(cell_lo) + ", " + std::to_string(cell_lo) + " + " + std::to_string(cell_cnt) + ") is outside [0, " +
-             std::to_string(g->N) + "]";
-    return CA_ERR_INVALID;
-  }
-  const size_t W = (size_t)g->W;
+  RangePlan p;
+  if (!duv_ok(g, "ca_clone_loglik_dm", D, U, V) || !plan_range(g, "ca_clone_loglik_dm", cell_lo, cell_cnt, U, D, p)) return CA_ERR_INVALID;
   const int64_t CK = (int64_t)g->C * std::max<int64_t>(0, std::min<int64_t>(n_conc, 16));
-  // rank r takes the cells of the range that lie in its shard: [lo[r], hi[r]) in the group's numbering (an empty part is still called: the verdict is collective)
-  std::vector<int64_t> lo(W), hi(W);
-  std::vector<std::vector<double>> us(W), o_ll(W), o_dm(W);
-  for (size_t r = 0; r < W; ++r) {
-    const int64_t slo = g->shard[r].lo, shi = g->shard[r].hi;
-    lo[r] = std::min(std::max(cell_lo, slo), shi);
-    hi[r] = std::max(std::min(cell_lo + cell_cnt, shi), lo[r]);
-    if (D > 0) slice_rows(U, g->layout, g->N, D, slo, shi, us[r]);
-    if (ll) o_ll[r].resize((size_t)((hi[r] - lo[r]) * g->C) + 1);
-    o_dm[r].resize((size_t)((hi[r] - lo[r]) * CK) + 1);
-  }
-  const int s = settle(g, dispatch(g, [&](int ri) {
+  auto o_ll = p.outputs(ll ? g->C : 0), o_dm = p.outputs(CK);
+  const int s = settle_verdict(g, dispatch(g, [&](int ri) {
     const size_t r = (size_t)ri;
-    return ca_clone_loglik_dm(g->h[r], E, D > 0 ? us[r].data() : nullptr, V, D, with_const, conc, n_conc, lo[r] - g->shard[r].lo, hi[r] - lo[r],
-                              ll ? o_ll[r].data() : nullptr, o_dm[r].data());
+    return ca_clone_loglik_dm(g->h[r], E, p.u(r), V, D, with_const, conc, n_conc, p.local_lo(r), p.rows(r), ll ? o_ll[r].data() : nullptr, o_dm[r].data());
   }), "ca_clone_loglik_dm");
-  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
-    for (int r = 0; r < g->W; ++r) {
-      const std::string why = ca_last_error(g->h[(size_t)r]);
-      if (why.find("another rank refused") != std::string::npos) continue;
-      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
-      break;
-    }
   if (s != CA_OK) return s;
-  for (size_t r = 0; r < W; ++r) {
-    if (ll) scatter_rows(o_ll[r].data(), g->layout, cell_cnt, g->C, lo[r] - cell_lo, hi[r] - cell_lo, ll);
-    scatter_rows(o_dm[r].data(), g->layout, cell_cnt, CK, lo[r] - cell_lo, hi[r] - cell_lo, dm_ll);
-  }
+  if (ll) p.scatter(o_ll, g->C, ll);
+  p.scatter(o_dm, CK, dm_ll);
   return CA_OK;
 }
 
@@ -812,50 +802,22 @@ int ca_group_clone_loglik_by_block(ca_group_handle g, const double* E, const dou
     const char* null_arg = !E ? "E" : !block_of_gene ? "block_of_gene" : !A ? "A" : !logZ ? "logZ" : !s ? "s" : (with_const && !lg) ? "lg (with_const != 0)" : nullptr;
     if (null_arg) { g->err = std::string("ca_clone_loglik_by_block: ") + null_arg + " is NULL"; return CA_ERR_INVALID; }
   }
-  if (D < 0 || D > 8 || (D > 0 && (!U || !V))) {
-    g->err = "ca_clone_loglik_by_block: D = " + std::to_string(D) + (D < 0 || D > 8 ? " is outside [0, 8]" : " needs both U (cells x D) and V (genes x D)");
-    return CA_ERR_INVALID;
-  }
+  if (!duv_ok(g, "ca_clone_loglik_by_block", D, U, V)) return CA_ERR_INVALID;
   if (n_blocks < 1) { g->err = "ca_clone_loglik_by_block: n_blocks = " + std::to_string(n_blocks) + " is below 1"; return CA_ERR_INVALID; }   // (it sizes the ranks' outputs)
-  if (cell_lo < 0 || cell_cnt < 0 || cell_lo > g->N || cell_cnt > g->N - cell_lo) {   // (what decides how the range is cut; the ranks refuse everything else in their own words)
-    g->err = "ca_clone_loglik_by_block: the cell range [" + std::to_string(cell_lo) + ", " + std::to_string(cell_lo) + " + " + std::to_string(cell_cnt) + ") is outside [0, " +
-             std::to_string(g->N) + "]";
-    return CA_ERR_INVALID;
-  }
-  const size_t W = (size_t)g->W;
+  RangePlan p;
+  if (!plan_range(g, "ca_clone_loglik_by_block", cell_lo, cell_cnt, U, D, p)) return CA_ERR_INVALID;
   const int64_t B = n_blocks, BC = B * g->C;
-  // rank r takes the cells of the range that lie in its shard: [lo[r], hi[r]) in the group's numbering (an empty part is still called: the verdict is collective)
-  std::vector<int64_t> lo(W), hi(W);
-  std::vector<std::vector<double>> us(W), o_a(W), o_z(W), o_s(W), o_l(W);
-  for (size_t r = 0; r < W; ++r) {
-    const int64_t slo = g->shard[r].lo, shi = g->shard[r].hi;
-    lo[r] = std::min(std::max(cell_lo, slo), shi);
-    hi[r] = std::max(std::min(cell_lo + cell_cnt, shi), lo[r]);
-    if (D > 0) slice_rows(U, g->layout, g->N, D, slo, shi, us[r]);
-    o_a[r].resize((size_t)((hi[r] - lo[r]) * BC) + 1);
-    o_z[r].resize((size_t)((hi[r] - lo[r]) * BC) + 1);
-    o_s[r].resize((size_t)((hi[r] - lo[r]) * B) + 1);
-    o_l[r].resize((size_t)((hi[r] - lo[r]) * B) + 1);
-  }
-  const int st = settle(g, dispatch(g, [&](int ri) {
+  auto o_a = p.outputs(BC), o_z = p.outputs(BC), o_s = p.outputs(B), o_l = p.outputs(B);
+  const int st = settle_verdict(g, dispatch(g, [&](int ri) {
     const size_t r = (size_t)ri;
-    return ca_clone_loglik_by_block(g->h[r], E, D > 0 ? us[r].data() : nullptr, V, D, with_const, block_of_gene, n_blocks, lo[r] - g->shard[r].lo, hi[r] - lo[r],
-                                    o_a[r].data(), o_z[r].data(), o_s[r].data(), with_const ? o_l[r].data() : nullptr);
+    return ca_clone_loglik_by_block(g->h[r], E, p.u(r), V, D, with_const, block_of_gene, n_blocks, p.local_lo(r), p.rows(r), o_a[r].data(), o_z[r].data(), o_s[r].data(),
+                                    with_const ? o_l[r].data() : nullptr);
   }), "ca_clone_loglik_by_block");
-  if (st == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
-    for (int r = 0; r < g->W; ++r) {
-      const std::string why = ca_last_error(g->h[(size_t)r]);
-      if (why.find("another rank refused") != std::string::npos) continue;
-      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
-      break;
-    }
   if (st != CA_OK) return st;
-  for (size_t r = 0; r < W; ++r) {
-    scatter_rows(o_a[r].data(), g->layout, cell_cnt, BC, lo[r] - cell_lo, hi[r] - cell_lo, A);
-    scatter_rows(o_z[r].data(), g->layout, cell_cnt, BC, lo[r] - cell_lo, hi[r] - cell_lo, logZ);
-    scatter_rows(o_s[r].data(), g->layout, cell_cnt, B, lo[r] - cell_lo, hi[r] - cell_lo, s);
-    if (with_const) scatter_rows(o_l[r].data(), g->layout, cell_cnt, B, lo[r] - cell_lo, hi[r] - cell_lo, lg);
-  }
+  p.scatter(o_a, BC, A);
+  p.scatter(o_z, BC, logZ);
+  p.scatter(o_s, B, s);
+  if (with_const) p.scatter(o_l, B, lg);
   return CA_OK;
 }
 
@@ -877,19 +839,12 @@ int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, 
     if (K > 0 && psi_start) slice_rows(psi_start, g->layout, g->N, K, lo, hi, pss[r]);
     o_psi[r].resize((size_t)((hi - lo) * std::max(K, 1))); o_ll[r].resize((size_t)((hi - lo) * g->C)); o_pr[r].resize((size_t)((hi - lo) * g->C));
   }
-  const int s = settle(g, dispatch(g, [&](int ri) {
+  const int s = settle_verdict(g, dispatch(g, [&](int ri) {
     const size_t r = (size_t)ri;
     const int64_t lo = g->shard[r].lo;   // (objective, rounds and converged are one value per cell: a rank writes its own stretch in place)
     return ca_project_cells(g->h[r], E, V, K, P, P > 0 ? xs[r].data() : nullptr, log_prior ? lps[r].data() : nullptr, K > 0 && psi_start ? pss[r].data() : nullptr, with_const,
                             max_iter, tol, max_step, o_psi[r].data(), o_ll[r].data(), o_pr[r].data(), objective + lo, rounds + lo, converged + lo);
   }), "ca_project_cells");
-  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
-    for (int r = 0; r < g->W; ++r) {
-      const std::string why = ca_last_error(g->h[(size_t)r]);
-      if (why.find("another rank refused") != std::string::npos) continue;
-      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
-      break;
-    }
   if (s != CA_OK) return s;
   for (size_t r = 0; r < W; ++r) {
     const int64_t lo = g->shard[r].lo, hi = g->shard[r].hi;
@@ -921,18 +876,11 @@ int ca_group_clone_evidence(ca_group_handle g, const double* E, const double* V,
     o_ev[r].resize((size_t)(n * C) + 1); o_lap[r].resize((size_t)(n * C) + 1); o_ps[r].resize((size_t)(n * CK) + 1); o_H[r].resize((size_t)(n * CH) + 1);
     o_rd[r].resize((size_t)(n * C) + 1); o_cv[r].resize((size_t)(n * C) + 1);
   }
-  const int s = settle(g, dispatch(g, [&](int ri) {
+  const int s = settle_verdict(g, dispatch(g, [&](int ri) {
     const size_t r = (size_t)ri;
     return ca_clone_evidence(g->h[r], E, V, K, P, P > 0 ? xs[r].data() : nullptr, K > 0 && psi_start ? pss[r].data() : nullptr, with_const, n_nodes, nodes, weights, max_iter, tol,
                              max_step, o_ev[r].data(), o_lap[r].data(), o_ps[r].data(), o_H[r].data(), o_rd[r].data(), o_cv[r].data());
   }), "ca_clone_evidence");
-  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
-    for (int r = 0; r < g->W; ++r) {
-      const std::string why = ca_last_error(g->h[(size_t)r]);
-      if (why.find("another rank refused") != std::string::npos) continue;
-      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
-      break;
-    }
   if (s != CA_OK) return s;
   for (size_t r = 0; r < W; ++r) {
     const int64_t lo = g->shard[r].lo, hi = g->shard[r].hi, n = hi - lo;
@@ -956,19 +904,11 @@ int ca_group_logexpr_sums(ca_group_handle g, const int32_t* group_of_cell, int32
   std::vector<std::vector<double>> s1((size_t)g->W), s2((size_t)g->W);
   std::vector<std::vector<int64_t>> ng((size_t)g->W);
   for (int r = 1; r < g->W; ++r) { s1[(size_t)r].resize((size_t)g->G * n_groups); s2[(size_t)r].resize((size_t)g->G); ng[(size_t)r].resize((size_t)n_groups); }
-  const int s = settle(g, dispatch(g, [&](int r) {
+  return settle_verdict(g, dispatch(g, [&](int r) {
     const int64_t lo = g->shard[(size_t)r].lo;
     return ca_logexpr_sums(g->h[(size_t)r], group_of_cell + lo, n_groups, size_factor ? size_factor + lo : nullptr, r == 0 ? S1 : s1[(size_t)r].data(),
                            r == 0 ? S2 : s2[(size_t)r].data(), r == 0 ? n_group : ng[(size_t)r].data());
   }), "ca_logexpr_sums");
-  if (s == CA_ERR_INVALID && !g->dead)   // every rank refused: the words of the first rank whose OWN input it was (it numbers its cells from its shard's start)
-    for (int r = 0; r < g->W; ++r) {
-      const std::string why = ca_last_error(g->h[(size_t)r]);
-      if (why.find("another rank refused") != std::string::npos) continue;
-      g->err = r == 0 ? why : why + " (rank " + std::to_string(r) + ": its cell 0 is cell " + std::to_string(g->shard[(size_t)r].lo) + " of the group)";
-      break;
-    }
-  return s;
 }
 
 }  // extern "C"

@@ -10,8 +10,8 @@
 // segment's in flight) and COMPACTS the segment's non-zero counts into a list of its own in LDS, in ASCENDING gene order (ballot + mbcnt, no atomic; u8 escapes
 // resolved here).  A segment wider than CA_DM_LIST columns (u8: 1024) is listed and walked in parts of CA_DM_LIST columns -- the lanes of a part hold consecutive
 // columns, so the order stays ascending -- which keeps the list at 9 KB per wave.  Two things differ from k_pair_ll:
-//   eta at compaction time: the lane that lists an entry also computes t = exp(eta_ng - m_n), eta_ng by the CA_LL_DMAX FMAs of k_clone_ll_z's eta_of against
-//     the padded rows of Ut and Vt (the same bits that went into m_n = max_g eta_ng, so t <= 1), and stores t beside the count: one exp per non-zero count,
+//   eta at compaction time: the lane that lists an entry also computes t = exp(eta_ng - m_n), eta_ng by ca_ll_eta (ca_k_loglik.hip.h) against the padded
+//     rows of Ut and Vt (the routine, hence the bits, that went into m_n = max_g eta_ng in k_clone_ll_z, so t <= 1), and stores t beside the count: one exp per non-zero count,
 //     shared by all slots.  D = 0 stores 1: one route for every D.
 //   the term: a = coef * E[g][c] * t with the slot's coef = phi_k exp(m_n - log Z_nc) (<= phi_k: nothing overflows), held in a register since before the first
 //     gene.  For an INTEGER count y <= CA_DM_YSMALL the term is log prod_{j < y} (a + j): at most CA_DM_YSMALL factors and one log.  Otherwise (a larger
@@ -26,7 +26,7 @@
 // Sums: a lane adds its slot over the cell's non-zero genes in ascending order, alone -- no cross-lane reduction, no atomic, no partial slab.  The value depends
 // on the cell's row and the inputs only: not on its place in the launch, the batch or the cell range of the call; a cell-sharded group returns the single handle's bits.
 //
-// k_dm_cell (before it): per cell log Z_nc and m_n, merged from k_clone_ll_z's chunks exactly as k_pair_cell merges them (D = 0: the host's log sum_g E, m = 0),
+// k_dm_cell (before it): per cell log Z_nc and m_n, merged from k_clone_ll_z's chunks by ca_ll_logz (ca_k_loglik.hip.h) like every other call's (D = 0: the host's log sum_g E, m = 0),
 // and per (cell, concentration) the head lgamma(phi_k) - lgamma(phi_k + s_n) + const_n, const_n from k_clone_ll's lgamma sums: none of it is computed again.
 #define CA_DM_LIST 512             // entries of a wave's list in LDS (9 KB per wave: four waves per SIMD fit)
 #define CA_DM_KMAX 16              // concentrations per call
@@ -45,15 +45,8 @@ __global__ void __launch_bounds__(CA_TB) k_dm_cell(const double* __restrict__ lg
   const int64_t n = n_lo + li;
   if (c < C) {
     double logz, m = 0.0;
-    if (D > 0) {
-      m = -__builtin_inf();
-      for (int k = 0; k < nzc; ++k) m = fmax(m, mpart[(int64_t)k * n_cnt + li]);
-      double z = 0.0;
-      for (int k = 0; k < nzc; ++k) z = fma(zpart[((int64_t)k * n_cnt + li) * nzt + c], exp(mpart[(int64_t)k * n_cnt + li] - m), z);
-      logz = m + log(z);
-    } else {
-      logz = logz0[c];
-    }
+    if (D > 0) logz = ca_ll_logz(mpart + li, n_cnt, zpart + li * nzt + c, n_cnt * nzt, nullptr, 0, nzc, &m);
+    else logz = logz0[c];
     lzc[li * C + c] = logz;
     if (c == 0) mrow[li] = m;
     return;
@@ -61,11 +54,7 @@ __global__ void __launch_bounds__(CA_TB) k_dm_cell(const double* __restrict__ lg
   const int k = c - C;
   const double s = s64[n], phi = conc[k];
   double h = s > 0.0 ? lgamma(phi) - lgamma(phi + s) : 0.0;   // (a cell without counts: exactly 0)
-  if (lgpart) {
-    double l = 0.0;
-    for (int sg = 0; sg < nseg; ++sg) l += lgpart[(int64_t)sg * n_cnt + li];
-    h += lgamma(s + 1.0) - l;
-  }
+  if (lgpart) h += lgamma(s + 1.0) - ca_ll_colsum(lgpart + li, n_cnt, nullptr, 0, nseg);
   head[li * K + k] = h;
 }
 
@@ -150,13 +139,7 @@ __global__ void __launch_bounds__(CA_TB) __attribute__((amdgpu_waves_per_eu(4)))
           if (y[k] == 255.f && noe > 0) yd += ca_mse_excess(ocol, oval, oe0, noe, g0 + k);   // rare: 255 + an entry of the overflow list
         }
         double t = 1.0;
-        if (Ut) {   // wave-uniform
-          const double* __restrict__ v = Vt + (int64_t)(g0 + k) * CA_LL_DMAX;
-          double e = 0.0;
-#pragma unroll
-          for (int d = 0; d < CA_LL_DMAX; ++d) e = fma(u[d], v[d], e);   // k_clone_ll_z's eta_of, bit for bit
-          t = exp(e - m);
-        }
+        if (Ut) t = exp(ca_ll_eta(u, Vt + (int64_t)(g0 + k) * CA_LL_DMAX) - m);   // wave-uniform; the eta that went into m (k_clone_ll_z's: the same routine)
         myv[pos] = yd;
         mtv[pos] = t;
         mgi[pos] = (unsigned short)(c0 + k);

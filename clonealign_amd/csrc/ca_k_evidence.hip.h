@@ -10,7 +10,8 @@
 //   gene, slot).  Per chunk first the largest exponent of every slot, then the shifted sums in ascending gene order.  A wave none of whose pairs is live
 //   (Newton: not frozen; quadrature: possible) returns at once.
 // k_ev_init: one thread per (cell, clone): psi = start; a pair with A = -inf is DEAD (evidence = laplace = -inf, rounds 0, converged 0, precision I).
-// k_ev_step<K>: one thread per (cell, clone): merges the chunks under the pair's overall maximum (ascending), f, the gradient and the K x K Hessian, the
+// k_ev_step<K>: one thread per (cell, clone): merges the chunks under the pair's overall maximum (ascending; ca_ll_merge of ca_k_loglik.hip.h with all moments,
+//   k_ev_reduce with one), f, the gradient and the K x K Hessian, the
 //   closed-form solve, the step limited to max_step in max-norm; freezes the pair when max|d| <= tol BEFORE the update (f and H are this round's).
 // k_ev_nodes<K>: one thread per (cell, clone): the Cholesky factor of H in closed form, laplace = f* - sum log diag L, psi_q = psi* + L^-T z_q for every node.
 // k_ev_reduce<K>: one thread per (cell, clone): f(psi_q) for q ascending, log sum_q w_q exp(f_q - f* + |z_q|^2 / 2) under a running maximum.
@@ -169,16 +170,8 @@ __global__ void __launch_bounds__(CA_TB) k_ev_step(const double* __restrict__ zp
   if (fz[i] != CA_EV_LIVE) return;
   const int c = (int)(i / n_cnt);
   const int64_t li = i - (int64_t)c * n_cnt, n = n_lo + li;
-  double m = -__builtin_inf();
-  for (int k = 0; k < nzc; ++k) m = fmax(m, mpart[((int64_t)k * C + c) * n_cnt + li]);
   double z[NM];
-#pragma unroll
-  for (int j = 0; j < NM; ++j) z[j] = 0.0;
-  for (int k = 0; k < nzc; ++k) {
-    const double wk = exp(mpart[((int64_t)k * C + c) * n_cnt + li] - m);
-#pragma unroll
-    for (int j = 0; j < NM; ++j) z[j] = fma(zpart[(((int64_t)k * C + c) * NM + j) * n_cnt + li], wk, z[j]);
-  }
+  const double m = ca_ll_merge<NM>(mpart + (int64_t)c * n_cnt + li, (int64_t)C * n_cnt, zpart + (int64_t)c * NM * n_cnt + li, (int64_t)C * NM * n_cnt, n_cnt, nullptr, 0, nzc, z);
   const double s = s64[n];
   const double* __restrict__ Bn = B + n * CA_LL_DMAX;
   double psi[K], h[NH], g[K], d[K], dmax;
@@ -279,14 +272,12 @@ __global__ void __launch_bounds__(CA_TB) k_ev_reduce(const double* __restrict__ 
   double M = -__builtin_inf(), S = 0.0;
   for (int q = 0; q < Q; ++q) {
     const int64_t sl = (int64_t)c * Q + q;
-    double m = -__builtin_inf();
-    for (int k = 0; k < nzc; ++k) m = fmax(m, mpart[((int64_t)k * nslot + sl) * n_cnt + li]);
-    double z0 = 0.0;
-    for (int k = 0; k < nzc; ++k) z0 = fma(zpart[((int64_t)k * nslot + sl) * n_cnt + li], exp(mpart[((int64_t)k * nslot + sl) * n_cnt + li] - m), z0);
+    double z0[1];
+    const double m = ca_ll_merge<1>(mpart + sl * n_cnt + li, nslot * n_cnt, zpart + sl * n_cnt + li, nslot * n_cnt, 0, nullptr, 0, nzc, z0);
     double psi[K], zz = 0.0;
 #pragma unroll
     for (int k = 0; k < K; ++k) { psi[k] = pq[(sl * K + k) * n_cnt + li]; zz = fma(nodes[q * K + k], nodes[q * K + k], zz); }
-    const double t = ca_ev_f<K>(a, psi, Bn, xB, s, m, z0) - f0 + 0.5 * zz;
+    const double t = ca_ev_f<K>(a, psi, Bn, xB, s, m, z0[0]) - f0 + 0.5 * zz;
     if (t > M) { S *= exp(M - t); M = t; }
     S = fma(wts[q], exp(t - M), S);
   }

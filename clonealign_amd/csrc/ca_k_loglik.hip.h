@@ -21,6 +21,10 @@
 //
 // k_clone_ll_z<NC> (D > 0 only; never reads Y): Z[n][c] = sum_g E[g][c] exp(eta_ng - m), again a lane per cell with V's and E's rows as scalar operands, per
 // chunk of CA_LL_ZCHUNK genes: first the chunk's max of eta (m), then the sum; the finishing kernel merges the chunks in ascending order under the overall max.
+//
+// This file also holds what the other scoring kernels (ca_k_blockll / pairll / dmll / project / evidence.hip.h) share with these: eta (ca_ll_eta), the chunk of
+// the contraction (ca_ll_zchunk), the merge of the chunks (ca_ll_merge, ca_ll_logz), the sums over the sweep's slab (ca_ll_colsum, ca_ll_yeta) and the walk
+// itself (ca_ll_walk).  k_clone_ll, k_clone_ll_z and k_clone_ll_finish below are thin kernels over them.
 #define CA_LL_PIECE 128    // bytes of a row staged per piece
 #define CA_LL_PITCH 144    // bytes between rows of a staged piece
 #define CA_LL_LGTAB 256    // entries of the lgamma(k + 1) table
@@ -30,12 +34,100 @@
 // lgamma(y + 1) off the table (rare): kept out of line, so that the unrolled gene loop carries one call and not sixteen copies of the routine
 __device__ __noinline__ double ca_ll_lgamma1p(double y) { return lgamma(y + 1.0); }
 
-template <typename YT, int NC>
-__global__ void __launch_bounds__(CA_TB) __attribute__((amdgpu_waves_per_eu(NC <= 8 ? 4 : NC <= 16 ? 3 : 2, NC <= 8 ? 4 : NC <= 16 ? 3 : 2)))
-k_clone_ll(const YT* __restrict__ Y, const double* __restrict__ tab /*[ngrp][Gp][NC]*/, const unsigned* __restrict__ zmask /*[ngrp][Gp]*/,
-                                                    const double* __restrict__ lgtab /*[CA_LL_LGTAB], or null: no lgamma sum*/, const int64_t* __restrict__ orowptr /* or null */,
-                                                    const int* __restrict__ ocol, const float* __restrict__ oval, double* __restrict__ part /*[nseg][n_cnt][ngrp * NC]*/,
-                                                    double* __restrict__ lgpart /*[nseg][n_cnt]*/, int64_t N, int64_t n_lo, int64_t n_cnt, int G, int Gp, int nseg) {
+// ---- the pieces the scoring kernels share (ca_k_blockll / pairll / dmll / project / evidence.hip.h call into them: one copy of the arithmetic, so the
+// ---- calls return each other's bits by construction)
+
+// eta_ng = sum_d U[n][d] V[g][d] over the CA_LL_DMAX padded factors, d ascending: one chain of fmas from 0
+__device__ __forceinline__ double ca_ll_eta(const double (&u)[CA_LL_DMAX], const double* __restrict__ v /*[CA_LL_DMAX]*/) {
+  double e = 0.0;
+#pragma unroll
+  for (int d = 0; d < CA_LL_DMAX; ++d) e = fma(u[d], v[d], e);
+  return e;
+}
+
+// One chunk [g_lo, g_hi) of the contraction for a lane's cell: the max m of eta over the chunk, then acc[c] = sum_g E[g][c] exp(eta_ng - m), g ascending.
+// A gene's rows of V and E are scalar operands (the bounds are wave-uniform).  Returns m.
+template <int NC>
+__device__ __forceinline__ double ca_ll_zchunk(const double* __restrict__ Un /*[CA_LL_DMAX]: the cell's row of Ut*/, const double* __restrict__ Vt, const double* __restrict__ erow /*[Gp][NC]*/,
+                                               int g_lo, int g_hi, double (&acc)[NC]) {
+  double u[CA_LL_DMAX];
+#pragma unroll
+  for (int d = 0; d < CA_LL_DMAX; ++d) u[d] = Un[d];
+  double m = -__builtin_inf();
+  for (int g = g_lo; g < g_hi; ++g) m = fmax(m, ca_ll_eta(u, Vt + (int64_t)g * CA_LL_DMAX));
+#pragma unroll
+  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+  for (int g = g_lo; g < g_hi; ++g) {
+    const double w = exp(ca_ll_eta(u, Vt + (int64_t)g * CA_LL_DMAX) - m);
+    const double* __restrict__ er = erow + (int64_t)g * NC;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = fma(er[c], w, acc[c]);
+  }
+  return m;
+}
+
+// The chunks' partial sums merged under their overall max, k ascending in [k0, k1): m = max_k m_k, then z[j] = sum_k zpart_kj exp(m_k - m), one fma per term.
+// Addressing by the slab's strides: chunk k's max is mp[ck * ms] and its sum of moment j zp[ck * zs + j * zj], with ck = list ? list[k] : k (k_block_ll_finish
+// goes through its list block -> chunks).  NM = 1 is the scalar case, log Z = m + log z (ca_ll_logz); the Newton rounds merge all their moments at once.
+__device__ __forceinline__ double ca_ll_chunk_max(const double* __restrict__ mp, int64_t ms, const int* __restrict__ list, int k0, int k1) {
+  double m = -__builtin_inf();
+  for (int k = k0; k < k1; ++k) m = fmax(m, mp[(int64_t)(list ? list[k] : k) * ms]);
+  return m;
+}
+template <int NM>
+__device__ __forceinline__ void ca_ll_chunk_sums(double m, const double* __restrict__ mp, int64_t ms, const double* __restrict__ zp, int64_t zs, int64_t zj, const int* __restrict__ list,
+                                                 int k0, int k1, double (&z)[NM]) {
+#pragma unroll
+  for (int j = 0; j < NM; ++j) z[j] = 0.0;
+  for (int k = k0; k < k1; ++k) {
+    const int64_t ck = list ? list[k] : k;
+    const double wk = exp(mp[ck * ms] - m);
+#pragma unroll
+    for (int j = 0; j < NM; ++j) z[j] = fma(zp[ck * zs + j * zj], wk, z[j]);
+  }
+}
+template <int NM>
+__device__ __forceinline__ double ca_ll_merge(const double* __restrict__ mp, int64_t ms, const double* __restrict__ zp, int64_t zs, int64_t zj, const int* __restrict__ list, int k0, int k1,
+                                              double (&z)[NM]) {
+  const double m = ca_ll_chunk_max(mp, ms, list, k0, k1);
+  ca_ll_chunk_sums<NM>(m, mp, ms, zp, zs, zj, list, k0, k1, z);
+  return m;
+}
+__device__ __forceinline__ double ca_ll_logz(const double* __restrict__ mp, int64_t ms, const double* __restrict__ zp, int64_t zs, const int* __restrict__ list, int k0, int k1, double* m_out = nullptr) {
+  double z[1];
+  const double m = ca_ll_merge<1>(mp, ms, zp, zs, 0, list, k0, k1, z);
+  if (m_out) *m_out = m;
+  return m + log(z[0]);
+}
+
+// One column of a cell summed over the sweep's slab entries q in [q0, q1), ascending from 0: p[(list ? list[q] : q) * stride] (the segments of k_clone_ll's slab,
+// or a block's runs of k_block_ll's through the list block -> runs)
+__device__ __forceinline__ double ca_ll_colsum(const double* __restrict__ p, int64_t stride, const int* __restrict__ list, int q0, int q1) {
+  double a = 0.0;
+  for (int q = q0; q < q1; ++q) a += p[(int64_t)(list ? list[q] : q) * stride];
+  return a;
+}
+// sum_g y_ng eta_ng of a cell from the sweep's V columns: sum_d U[n][d] * (column d of V summed as above), d ascending, one fma per factor; pv is the cell's
+// first V column in entry 0, the columns dstride apart
+__device__ __forceinline__ double ca_ll_yeta(const double* __restrict__ Un, int D, const double* __restrict__ pv, int64_t dstride, int64_t stride, const int* __restrict__ list, int q0, int q1) {
+  double yeta = 0.0;
+  for (int d = 0; d < D; ++d) yeta = fma(Un[d], ca_ll_colsum(pv + d * dstride, stride, list, q0, q1), yeta);
+  return yeta;
+}
+
+// ---- the walk in which a lane owns a cell (k_clone_ll, k_block_ll): the staging constants, the loads' addresses, the stage-and-fence piece loop, the overflow
+// ---- lookup and the per-gene update (the fma over NC, the zero mask, s, the lgamma table) are here once.  Where the sums go is the compile-time policy RUNS:
+// ----   false (k_clone_ll): one set of sums per segment, stored after its last gene -- the instantiation carries no run-list register and no gene-by-gene loop;
+// ----   true (k_block_ll): a run list cuts the segment (ca_k_blockll.hip.h has the rules): the sums, s and lg are stored and cleared wherever a run ends.
+// ---- The outputs and the run list are __restrict__ PARAMETERS, not members of a policy object: through an object the compiler no longer proved that the
+// ---- stores at the run ends leave the table alone, loaded the table rows into vector registers (2 NC more of them) and spilled.
+template <typename YT, int NC, bool RUNS>
+__device__ __forceinline__ void ca_ll_walk(const YT* __restrict__ Y, const double* __restrict__ tab /*[ngrp][Gp][NC]*/, const unsigned* __restrict__ zmask /*[ngrp][Gp]*/,
+                                           const double* __restrict__ lgtab /*[CA_LL_LGTAB], or null: no lgamma sum*/, const int64_t* __restrict__ orowptr /* or null */,
+                                           const int* __restrict__ ocol, const float* __restrict__ oval, int64_t n_lo, int64_t n_cnt, int G, int Gp, int nseg,
+                                           double* __restrict__ part /*segments: [nseg][n_cnt][ngrp * NC]; runs: [n_runs][nuse + 2][n_cnt], the sums' columns in use, then s, then lg*/,
+                                           double* __restrict__ lgpart /*segments: [nseg][n_cnt]*/, const int* __restrict__ rcut /*runs: [n_runs + 2]*/,
+                                           const int* __restrict__ rseg /*runs: [nseg + 1]*/, int nuse /*runs: table columns in use*/) {
   constexpr int VEC = YVec<YT>::VEC;
   constexpr int NP = CA_LL_PIECE / 16;                 // 16-byte loads per row of a piece
   constexpr int NLD = 64 * NP / 64;                    // load instructions per piece and wave (64 rows x NP loads over 64 lanes)
@@ -48,7 +140,8 @@ k_clone_ll(const YT* __restrict__ Y, const double* __restrict__ tab /*[ngrp][Gp]
   const int cb = (int)blockIdx.x / nseg;               // wave-uniform from here on
   const int sg = (int)blockIdx.x - cb * nseg;
   const int grp = blockIdx.y, ngrp = gridDim.y;
-  const bool lg = lgtab != nullptr && grp == 0;
+  const bool first = grp == 0;                         // the group that also carries s and lg
+  const bool lg = lgtab != nullptr && first;
   if (lg) {
     for (int i = threadIdx.x; i < CA_LL_LGTAB; i += CA_TB) lgt[i] = lgtab[i];
     __syncthreads();
@@ -81,9 +174,56 @@ k_clone_ll(const YT* __restrict__ Y, const double* __restrict__ tab /*[ngrp][Gp]
   double acc[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-  double lgacc = 0.0;
+  double sacc = 0.0, lgacc = 0.0;
   const double* __restrict__ trow = tab + (int64_t)grp * Gp * NC;
   const unsigned* __restrict__ zrow = zmask + (int64_t)grp * Gp;
+  int run = 0, nend = 0;                               // with a run list: the current run and one past its last gene (scalars)
+  if constexpr (RUNS) { run = rseg[sg]; nend = rcut[run + 1]; }
+  // one gene of this lane's cell
+  auto step = [&](float yf, int g) {
+    double yd = (double)yf;
+    if constexpr (sizeof(YT) == 1) {
+      if (yf == 255.f && noe > 0) yd += ca_mse_excess(ocol, oval, oe0, noe, g);   // per lane, rare: 255 + an entry of the overflow list
+    }
+    const double* __restrict__ tr = trow + (int64_t)g * NC;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = fma(yd, tr[c], acc[c]);
+    const unsigned zm = zrow[g];
+    if (zm != 0u) {   // wave-uniform, rare: columns of this gene with E = 0 (their table entry is 0)
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+        if (((zm >> c) & 1u) && yd > 0.0) acc[c] = -__builtin_inf();
+    }
+    if (RUNS ? first : lg) {   // wave-uniform: the group that carries s (with a run list) and lg
+      if (RUNS) sacc += yd;
+      if (lg) {
+        if (yd < (double)CA_LL_LGTAB && yd == (double)(int)yd) lgacc += lgt[(int)yd];
+        else lgacc += ca_ll_lgamma1p(yd);
+      }
+    }
+  };
+  // the end of a run: its sums to the slab, coalesced over the wave's cells, and the next run begins at 0
+  auto flush = [&]() {
+    if constexpr (RUNS) {
+      const int64_t ncol = nuse + 2;
+      if (valid) {
+        double* out = part + ((int64_t)run * ncol + (int64_t)grp * NC) * n_cnt + li;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (grp * NC + c < nuse) out[(int64_t)c * n_cnt] = acc[c];   // scalar
+        if (first) {
+          double* sl = part + ((int64_t)run * ncol + nuse) * n_cnt + li;
+          sl[0] = sacc;
+          if (lg) sl[n_cnt] = lgacc;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+      sacc = 0.0; lgacc = 0.0;
+      ++run;
+      nend = rcut[run + 1];
+    }
+  };
   fetch(0);
   for (int sub = 0; sub < NSUB; ++sub) {
     const int gb = sg * 64 * VEC + sub * SUBC;
@@ -97,42 +237,45 @@ k_clone_ll(const YT* __restrict__ Y, const double* __restrict__ tab /*[ngrp][Gp]
     for (int p = 0; p < NP; ++p) {
       const int g0 = gb + p * VEC;
       if (g0 >= G) break;
-      const v4u_ t_ = *reinterpret_cast<const v4u_*>(mine + lane * CA_LL_PITCH + p * 16);
-      float y[VEC];
-      YVec<YT>::decode((uint4){t_.x, t_.y, t_.z, t_.w}, y);
+      if (!RUNS || nend > g0 + VEC) {   // scalar: no run ends in this 16-byte group (with a run list: so all its genes are below G)
+        const v4u_ t_ = *reinterpret_cast<const v4u_*>(mine + lane * CA_LL_PITCH + p * 16);
+        float y[VEC];
+        YVec<YT>::decode((uint4){t_.x, t_.y, t_.z, t_.w}, y);
 #pragma unroll
-      for (int j = 0; j < VEC; ++j) {
-        const int g = g0 + j;
-        if (g < G) {   // wave-uniform
-          double yd = (double)y[j];
-          if constexpr (sizeof(YT) == 1) {
-            if (y[j] == 255.f && noe > 0) yd += ca_mse_excess(ocol, oval, oe0, noe, g);   // per lane, rare: 255 + an entry of the overflow list
-          }
-          const double* __restrict__ tr = trow + (int64_t)g * NC;
-#pragma unroll
-          for (int c = 0; c < NC; ++c) acc[c] = fma(yd, tr[c], acc[c]);
-          const unsigned zm = zrow[g];
-          if (zm != 0u) {   // wave-uniform, rare: columns of this gene with E = 0 (their table entry is 0)
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-              if (((zm >> c) & 1u) && yd > 0.0) acc[c] = -__builtin_inf();
-          }
-          if (lg) {   // wave-uniform
-            if (yd < (double)CA_LL_LGTAB && yd == (double)(int)yd) lgacc += lgt[(int)yd];
-            else lgacc += ca_ll_lgamma1p(yd);
-          }
+        for (int j = 0; j < VEC; ++j)
+          if (RUNS || g0 + j < G) step(y[j], g0 + j);   // wave-uniform
+      } else if constexpr (RUNS) {   // a run ends here (the last gene of a segment and gene G - 1 always end one): gene by gene, the counts read back from the staged piece
+#pragma unroll 1
+        for (int j = 0; j < VEC; ++j) {
+          const int g = g0 + j;
+          if (g >= G) break;
+          step((float)*reinterpret_cast<const YT*>(mine + lane * CA_LL_PITCH + p * 16 + j * (int)sizeof(YT)), g);
+          if (g + 1 == nend) flush();   // scalar
         }
       }
     }
   }
-  if (valid) {
-    double* out = part + ((int64_t)sg * n_cnt + li) * ((int64_t)ngrp * NC) + (int64_t)grp * NC;
+  if constexpr (!RUNS) {   // the segment's sums
+    if (valid) {
+      double* out = part + ((int64_t)sg * n_cnt + li) * ((int64_t)ngrp * NC) + (int64_t)grp * NC;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) out[c] = acc[c];
-    if (lg) lgpart[(int64_t)sg * n_cnt + li] = lgacc;
+      for (int c = 0; c < NC; ++c) out[c] = acc[c];
+      if (lg) lgpart[(int64_t)sg * n_cnt + li] = lgacc;
+    }
   }
 }
 
+// the sweep of ca_clone_loglik: the walk, a lane's NC sums (and the lgamma sum) of its segment stored at the end
+template <typename YT, int NC>
+__global__ void __launch_bounds__(CA_TB) __attribute__((amdgpu_waves_per_eu(NC <= 8 ? 4 : NC <= 16 ? 3 : 2, NC <= 8 ? 4 : NC <= 16 ? 3 : 2)))
+k_clone_ll(const YT* __restrict__ Y, const double* __restrict__ tab /*[ngrp][Gp][NC]*/, const unsigned* __restrict__ zmask /*[ngrp][Gp]*/,
+                                                    const double* __restrict__ lgtab /*[CA_LL_LGTAB], or null: no lgamma sum*/, const int64_t* __restrict__ orowptr /* or null */,
+                                                    const int* __restrict__ ocol, const float* __restrict__ oval, double* __restrict__ part /*[nseg][n_cnt][ngrp * NC]*/,
+                                                    double* __restrict__ lgpart /*[nseg][n_cnt]*/, int64_t N, int64_t n_lo, int64_t n_cnt, int G, int Gp, int nseg) {
+  ca_ll_walk<YT, NC, false>(Y, tab, zmask, lgtab, orowptr, ocol, oval, n_lo, n_cnt, G, Gp, nseg, part, lgpart, nullptr, nullptr, 0);
+}
+
+// the contraction of ca_clone_loglik (D > 0): chunk zc = genes [zc CA_LL_ZCHUNK, (zc + 1) CA_LL_ZCHUNK), the sums to zpart[chunk][cell][column], the max to mpart[chunk][cell]
 template <int NC>
 __global__ void __launch_bounds__(CA_TB) k_clone_ll_z(const double* __restrict__ Ut /*[N][CA_LL_DMAX], zero padded*/, const double* __restrict__ Vt /*[Gp][CA_LL_DMAX], zero padded*/,
                                                       const double* __restrict__ Ez /*[ngrp][Gp][NC]*/, double* __restrict__ zpart /*[nzc][n_cnt][ngrp * NC]*/,
@@ -142,28 +285,8 @@ __global__ void __launch_bounds__(CA_TB) k_clone_ll_z(const double* __restrict__
   const int64_t n = n_lo + (valid ? li : n_cnt - 1);
   const int zc = blockIdx.y, grp = blockIdx.z, ngrp = gridDim.z;
   const int g_lo = zc * CA_LL_ZCHUNK, g_hi = (g_lo + CA_LL_ZCHUNK < G) ? g_lo + CA_LL_ZCHUNK : G;   // wave-uniform
-  double u[CA_LL_DMAX];
-#pragma unroll
-  for (int d = 0; d < CA_LL_DMAX; ++d) u[d] = Ut[n * CA_LL_DMAX + d];
-  auto eta_of = [&](int g) {
-    const double* __restrict__ v = Vt + (int64_t)g * CA_LL_DMAX;
-    double e = 0.0;
-#pragma unroll
-    for (int d = 0; d < CA_LL_DMAX; ++d) e = fma(u[d], v[d], e);
-    return e;
-  };
-  double m = -__builtin_inf();
-  for (int g = g_lo; g < g_hi; ++g) m = fmax(m, eta_of(g));
   double acc[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-  const double* __restrict__ erow = Ez + (int64_t)grp * Gp * NC;
-  for (int g = g_lo; g < g_hi; ++g) {
-    const double w = exp(eta_of(g) - m);
-    const double* __restrict__ er = erow + (int64_t)g * NC;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = fma(er[c], w, acc[c]);
-  }
+  const double m = ca_ll_zchunk<NC>(Ut + n * CA_LL_DMAX, Vt, Ez + (int64_t)grp * Gp * NC, g_lo, g_hi, acc);
   if (valid) {
     double* out = zpart + ((int64_t)zc * n_cnt + li) * ((int64_t)ngrp * NC) + (int64_t)grp * NC;
 #pragma unroll
@@ -182,31 +305,17 @@ __global__ void __launch_bounds__(CA_TB) k_clone_ll_finish(const double* __restr
   const int64_t li = i / C;
   const int c = (int)(i - li * C);
   const int64_t n = n_lo + li;
-  double a = 0.0;
-  for (int sg = 0; sg < nseg; ++sg) a += part[((int64_t)sg * n_cnt + li) * nct + c];
+  const int64_t seg = n_cnt * nct;                     // the slabs' strides: a segment of part, a chunk of zpart
+  double a = ca_ll_colsum(part + li * nct + c, seg, nullptr, 0, nseg);
   double logz;
   if (D > 0) {
-    double yeta = 0.0;
-    for (int d = 0; d < D; ++d) {
-      double yv = 0.0;
-      for (int sg = 0; sg < nseg; ++sg) yv += part[((int64_t)sg * n_cnt + li) * nct + C + d];
-      yeta = fma(Ut[n * CA_LL_DMAX + d], yv, yeta);
-    }
-    a += yeta;
-    double m = -__builtin_inf();
-    for (int k = 0; k < nzc; ++k) m = fmax(m, mpart[(int64_t)k * n_cnt + li]);
-    double z = 0.0;
-    for (int k = 0; k < nzc; ++k) z = fma(zpart[((int64_t)k * n_cnt + li) * nzt + c], exp(mpart[(int64_t)k * n_cnt + li] - m), z);
-    logz = m + log(z);
+    a += ca_ll_yeta(Ut + n * CA_LL_DMAX, D, part + li * nct + C, 1, seg, nullptr, 0, nseg);
+    logz = ca_ll_logz(mpart + li, n_cnt, zpart + li * nzt + c, n_cnt * nzt, nullptr, 0, nzc);
   } else {
     logz = logz0[c];
   }
   const double s = s64[n];
   if (s > 0.0) a -= s * logz;   // (a cell without counts: every term is 0)
-  if (lgpart) {
-    double l = 0.0;
-    for (int sg = 0; sg < nseg; ++sg) l += lgpart[(int64_t)sg * n_cnt + li];
-    a += lgamma(s + 1.0) - l;
-  }
+  if (lgpart) a += lgamma(s + 1.0) - ca_ll_colsum(lgpart + li, n_cnt, nullptr, 0, nseg);
   ll[n * C + c] = a;
 }

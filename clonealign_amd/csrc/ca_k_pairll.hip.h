@@ -18,8 +18,8 @@
 // Sums: a lane adds its slot over the cell's non-zero genes in ascending order, alone -- no cross-lane reduction, no atomic, no partial slab.  The value depends
 // on the cell's row and the inputs only: not on its place in the launch, the batch or the cell range of the call; a cell-sharded group returns the single handle's bits.
 //
-// k_pair_cell (before it): per cell log Z_nc, merged from k_clone_ll_z's chunks exactly as k_clone_ll_finish merges them, and base_n = sum_g y eta (+ const),
-// from k_clone_ll's partial sums against [log E | V]: neither is computed again here.  k_pair_ll adds base_n and subtracts s_n lz itself (the lane holds the whole sum).
+// k_pair_cell (before it): per cell log Z_nc, merged from k_clone_ll_z's chunks by the routine k_clone_ll_finish merges them with (ca_ll_logz, ca_k_loglik.hip.h),
+// and base_n = sum_g y eta (+ const) from k_clone_ll's partial sums against [log E | V] (ca_ll_yeta, ca_ll_colsum): neither is computed again here.  k_pair_ll adds base_n and subtracts s_n lz itself (the lane holds the whole sum).
 // k_pair_tab_finish (D = 0): adds the segments of the table sweep's partial sums, base_n and - s_n lz of the slot.
 #define CA_PLL_WMAX 8   // weights per call
 
@@ -33,30 +33,11 @@ __global__ void __launch_bounds__(CA_TB) k_pair_cell(const double* __restrict__ 
   const int c = (int)(i - li * (C + 1));
   const int64_t n = n_lo + li;
   if (c < C) {
-    double logz;
-    if (D > 0) {
-      double m = -__builtin_inf();
-      for (int k = 0; k < nzc; ++k) m = fmax(m, mpart[(int64_t)k * n_cnt + li]);
-      double z = 0.0;
-      for (int k = 0; k < nzc; ++k) z = fma(zpart[((int64_t)k * n_cnt + li) * nzt + c], exp(mpart[(int64_t)k * n_cnt + li] - m), z);
-      logz = m + log(z);
-    } else {
-      logz = logz0[c];
-    }
-    lzc[li * C + c] = logz;
+    lzc[li * C + c] = D > 0 ? ca_ll_logz(mpart + li, n_cnt, zpart + li * nzt + c, n_cnt * nzt, nullptr, 0, nzc) : logz0[c];
     return;
   }
-  double b = 0.0;
-  for (int d = 0; d < D; ++d) {
-    double yv = 0.0;
-    for (int sg = 0; sg < nseg; ++sg) yv += part[((int64_t)sg * n_cnt + li) * nct + C + d];
-    b = fma(Ut[n * CA_LL_DMAX + d], yv, b);
-  }
-  if (lgpart) {
-    double l = 0.0;
-    for (int sg = 0; sg < nseg; ++sg) l += lgpart[(int64_t)sg * n_cnt + li];
-    b += lgamma(s64[n] + 1.0) - l;
-  }
+  double b = D > 0 ? ca_ll_yeta(Ut + n * CA_LL_DMAX, D, part + li * nct + C, 1, n_cnt * nct, nullptr, 0, nseg) : 0.0;
+  if (lgpart) b += lgamma(s64[n] + 1.0) - ca_ll_colsum(lgpart + li, n_cnt, nullptr, 0, nseg);
   base[li] = b;
 }
 

@@ -2,7 +2,8 @@
 // for cells of the resident matrix under a fitted model's gene-level parameters (ca_project_cells; include/clonealign_hip.h has the algorithm):
 //   maximise  F_n(psi) = logsumexp_c( ll_nc(psi) + log_prior_nc ) - |psi|^2 / 2   by generalised EM, one safeguarded Newton step per round.
 // The count matrix is read ONCE, by k_clone_ll against the table [log E | V] (A = Y log E, B = Y V, the lgamma sum; ca_k_loglik.hip.h); k_proj_sums adds its
-// segments.  A round is two launches that never read Y:
+// segments (ca_ll_colsum).  A round is two launches that never read Y; eta and the merge of the chunks are ca_k_loglik.hip.h's (ca_ll_eta, ca_ll_chunk_max,
+// ca_ll_chunk_sums):
 //
 // k_proj_mom<NC, K>: per cell and clone the exponential-family moments of W under the weights E[g][c] exp(eta_ng - m),
 //   Z0 = sum_g E e,  Z1[k] = sum_g E e W[g][k],  Z2[k][l] = sum_g E e W[g][k] W[g][l] (k <= l):  NM = 1 + K + K (K + 1) / 2 sums per clone.
@@ -31,14 +32,9 @@ __global__ void __launch_bounds__(CA_TB) k_proj_sums(const double* __restrict__ 
   const int64_t li = i / ncol;
   const int col = (int)(i - li * ncol);
   const int64_t n = n_lo + li;
-  double a = 0.0;
-  for (int sg = 0; sg < nseg; ++sg) a += part[((int64_t)sg * n_cnt + li) * nct + col];
+  double a = ca_ll_colsum(part + li * nct + col, n_cnt * nct, nullptr, 0, nseg);
   if (col >= C) { B[n * CA_LL_DMAX + (col - C)] = a; return; }
-  if (lgpart) {
-    double l = 0.0;
-    for (int sg = 0; sg < nseg; ++sg) l += lgpart[(int64_t)sg * n_cnt + li];
-    a += lgamma(s64[n] + 1.0) - l;
-  }
+  if (lgpart) a += lgamma(s64[n] + 1.0) - ca_ll_colsum(lgpart + li, n_cnt, nullptr, 0, nseg);
   A[n * C + col] = a;
 }
 
@@ -58,14 +54,8 @@ k_proj_mom(const double* __restrict__ Ut /*[N][CA_LL_DMAX]: psi | x, zero padded
   double u[CA_LL_DMAX];
 #pragma unroll
   for (int d = 0; d < CA_LL_DMAX; ++d) u[d] = Ut[n * CA_LL_DMAX + d];
-  auto eta_of = [&](const double* __restrict__ v) {
-    double e = 0.0;
-#pragma unroll
-    for (int d = 0; d < CA_LL_DMAX; ++d) e = fma(u[d], v[d], e);
-    return e;
-  };
   double m = -__builtin_inf();
-  for (int g = g_lo; g < g_hi; ++g) m = fmax(m, eta_of(Vt + (int64_t)g * CA_LL_DMAX));
+  for (int g = g_lo; g < g_hi; ++g) m = fmax(m, ca_ll_eta(u, Vt + (int64_t)g * CA_LL_DMAX));
   double acc[NC * NM];
 #pragma unroll
   for (int i = 0; i < NC * NM; ++i) acc[i] = 0.0;
@@ -74,7 +64,7 @@ k_proj_mom(const double* __restrict__ Ut /*[N][CA_LL_DMAX]: psi | x, zero padded
     const double* __restrict__ v = Vt + (int64_t)g * CA_LL_DMAX;
     const double* __restrict__ er = erow + (int64_t)g * NC;
     double w[NM];   // e, e W_k, e W_k W_l (k <= l)
-    w[0] = exp(eta_of(v) - m);
+    w[0] = exp(ca_ll_eta(u, v) - m);
     if constexpr (K >= 1) { w[1] = w[0] * v[0]; }
     if constexpr (K == 1) { w[2] = w[1] * v[0]; }
     if constexpr (K == 2) { w[2] = w[0] * v[1]; w[3] = w[1] * v[0]; w[4] = w[1] * v[1]; w[5] = w[2] * v[1]; }
@@ -105,8 +95,7 @@ __global__ void __launch_bounds__(CA_TB) k_proj_step(const double* __restrict__ 
   if (li >= n_cnt) return;
   const int64_t n = n_lo + li;
   if (frozen[n]) return;
-  double m = -__builtin_inf();
-  for (int k = 0; k < nzc; ++k) m = fmax(m, mpart[(int64_t)k * n_cnt + li]);
+  const double m = ca_ll_chunk_max(mpart + li, n_cnt, nullptr, 0, nzc);   // (one max serves every clone of the cell)
   double ub = 0.0;
   for (int d = 0; d < CA_LL_DMAX; ++d) ub = fma(Ut[n * CA_LL_DMAX + d], B[n * CA_LL_DMAX + d], ub);
   const double s = s64[n];
@@ -118,13 +107,7 @@ __global__ void __launch_bounds__(CA_TB) k_proj_step(const double* __restrict__ 
   for (int k = 0; k < NS; ++k) Sc[k] = 0.0;
   for (int c = 0; c < C; ++c) {
     double z[NM];
-#pragma unroll
-    for (int j = 0; j < NM; ++j) z[j] = 0.0;
-    for (int k = 0; k < nzc; ++k) {
-      const double wk = exp(mpart[(int64_t)k * n_cnt + li] - m);
-#pragma unroll
-      for (int j = 0; j < NM; ++j) z[j] = fma(zpart[((int64_t)k * nmt + (int64_t)c * NM + j) * n_cnt + li], wk, z[j]);
-    }
+    ca_ll_chunk_sums<NM>(m, mpart + li, n_cnt, zpart + (int64_t)c * NM * n_cnt + li, (int64_t)nmt * n_cnt, n_cnt, nullptr, 0, nzc, z);
     double a = A[n * C + c] + ub;
     if (s > 0.0) a -= s * (m + log(z[0]));   // (a cell without counts: every term is 0)
     ll[n * C + c] = a;

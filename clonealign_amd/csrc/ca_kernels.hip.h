@@ -947,8 +947,8 @@ __global__ void __launch_bounds__(CA_TB, (DEPTH == 1 && !C16 && !S2F) ? CA_YS_RI
 
 #include "ca_fwdbal.hip.h"   // the balanced forward sweep for small problems (round 5)
 #include "ca_k_mse.hip.h"   // the squared error of a fit on the resident matrix (ca_fit_mse): one float64 sweep, gathered by clone
-#include "ca_k_loglik.hip.h"   // per-cell, per-clone log-likelihood of the resident matrix under a fitted model (ca_clone_loglik): one float64 sweep, a lane per cell
-#include "ca_k_blockll.hip.h"   // the log-likelihood's sufficient statistics by block of genes (ca_clone_loglik_by_block): k_clone_ll's walk with a run list, sums stored at run ends
+#include "ca_k_loglik.hip.h"   // per-cell, per-clone log-likelihood of the resident matrix under a fitted model (ca_clone_loglik): one float64 sweep, a lane per cell; and the pieces every scoring kernel below shares (eta, the contraction's chunk, the chunk merge, the slab sums, the walk)
+#include "ca_k_blockll.hip.h"   // the log-likelihood's sufficient statistics by block of genes (ca_clone_loglik_by_block): the shared walk with a run list, sums stored at run ends
 #include "ca_k_pairll.hip.h"   // log-likelihood under a mixture of two clones (ca_clone_pair_loglik): a wave per cell over its compacted non-zero counts, a lane per (pair, weight)
 #include "ca_k_dmll.hip.h"   // Dirichlet-multinomial log-likelihood per clone on a grid of concentrations (ca_clone_loglik_dm): k_pair_ll's walk, a lane per (clone, concentration), exp(eta) at compaction time
 #include "ca_k_project.hip.h" // per-cell MAP psi and clone posterior for cells outside the fit (ca_project_cells): moments over the genes, a lane per cell; never reads Y
