@@ -3,9 +3,10 @@
 Mirrors ``R/clonealign.R`` (exports in NAMESPACE:3-7) argument for argument; the only
 compute-heavy callee, ``inference_tflow``, runs on the MI355X engine.
 """
+import contextlib
 import string
 import warnings
-from collections import Counter
+from collections import Counter, namedtuple
 
 import numpy as np
 
@@ -137,6 +138,44 @@ def _fit_mse_host(Y, E, clone_idx, per_gene=False, chunk=4096):
     return out
 
 
+def _cells_and_cnv(Y, L):
+    """(Y, L, cn, N, G) of a call on the cells of ``Y`` and the copy numbers ``L``: the count matrix as the engine uploads it, ``L`` [G, C] parsed, the
+    DataFrame's clone names or None; refuses an ``L`` for other genes."""
+    L, cn = _parse_cnv(L)
+    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    N, G = Y.shape
+    if L.shape[0] != G:
+        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    return Y, L, cn, N, G
+
+
+def _clone_names(fit, cn, C):
+    """The clone names of a result: the fit's, else the DataFrame's columns ``cn``, else ``clone_a`` ... ``clone_z``, ``clone_27`` ... (numbered beyond the
+    26 letters, as ``_default_gene_names`` numbers genes)."""
+    if "clone_names" in fit:
+        return list(fit["clone_names"])
+    lt = string.ascii_lowercase
+    return cn if cn is not None else [f"clone_{lt[i]}" if i < 26 else f"clone_{i + 1}" for i in range(C)]
+
+
+@contextlib.contextmanager
+def _engine_lease(engine, method, Y, L, engine_opts):
+    """The engine of a call on the resident matrix ``Y``: the caller's, used as it is and never closed, or a throwaway one built for the upload only
+    (``K = 0``; ``engine_opts`` go to its constructor) and closed on every way out.  An engine that has ``method`` must hold a matrix of ``Y``'s shape."""
+    N, G = Y.shape
+    own = engine is None
+    if own:
+        from .engine import HipEngine
+        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
+    try:
+        if hasattr(engine, method) and (engine.N, engine.G) != (N, G):
+            raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+        yield engine
+    finally:
+        if own:
+            engine.close()
+
+
 def compute_ca_fit_mse(fit, Y, L, model_mu=False, random_clones=False, *, seed=None, drop_unassigned=False, per_gene=False,
                        engine=None, engine_opts=None):
     """Mean squared error of a clonealign fit on expression data under given clones, R/clonealign.R:415-434 (first five arguments as there):
@@ -151,13 +190,8 @@ def compute_ca_fit_mse(fit, Y, L, model_mu=False, random_clones=False, *, seed=N
     Cells labelled "unassigned": the reference fails on ``L[, "unassigned"]`` and so does this (ValueError) unless ``drop_unassigned=True``, which
     skips them and takes the mean over the cells that are left.
     Returns the MSE; with ``per_gene=True`` ``(mse, mse_gene[G])``, the same mean per gene."""
-    L, cn = _parse_cnv(L)
-    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else
-                                                                   [f"clone_{string.ascii_lowercase[i]}" for i in range(L.shape[1])])
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if L.shape[0] != G:
-        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+    Y, L, cn, N, G = _cells_and_cnv(Y, L)
+    names = _clone_names(fit, cn, L.shape[1])
     if len(names) != L.shape[1]:
         raise ValueError(f"fit has {len(names)} clone names but L has {L.shape[1]} columns (clones)")
     clones = np.asarray(fit["clone"], dtype=object).reshape(-1)
@@ -180,20 +214,8 @@ def compute_ca_fit_mse(fit, Y, L, model_mu=False, random_clones=False, *, seed=N
         if mu.shape[0] != G:
             raise ValueError(f"fit$ml_params$mu has length {mu.shape[0]} but L has {G} rows: evaluate on the retained genes")
         E = mu[:, None] * L
-    own = engine is None
-    if own:
-        from .engine import HipEngine
-        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
-    try:
-        if hasattr(engine, "fit_mse"):
-            if (engine.N, engine.G) != (N, G):
-                raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
-            out = engine.fit_mse(idx, E, per_gene=per_gene)
-        else:
-            out = _fit_mse_host(Y, E, idx, per_gene=per_gene)
-    finally:
-        if own:
-            engine.close()
+    with _engine_lease(engine, "fit_mse", Y, L, engine_opts) as eng:
+        out = eng.fit_mse(idx, E, per_gene=per_gene) if hasattr(eng, "fit_mse") else _fit_mse_host(Y, E, idx, per_gene=per_gene)
     if per_gene:
         return out["mse"], (out["sse_gene"] / out["n_cells"] if out["n_cells"] else np.full(G, np.nan))
     return out["mse"]
@@ -229,6 +251,22 @@ def _ll_inputs(Y, E, U, V, what):
     return E, U, V, D, esum
 
 
+def _cell_chunks(Y, chunk, E=None, U=None, V=None, order=None):
+    """The cell walk of the host forms: yields ``(lo, Yc, eta, m, logz)`` per ``chunk`` cells of Y [N, G] dense or scipy.sparse, from cell ``lo`` on.
+    ``Yc``: the chunk densified to float64 (in memory order ``order`` when given).  With ``U`` [N, D], D > 0: the exponent ``eta = U V^T`` [n, G] and,
+    when ``E`` is given too, its largest value per cell ``m`` [n] and the whole-gene ``logz = m + log(exp(eta - m) @ E)`` [n, C]; None otherwise."""
+    for lo in range(0, Y.shape[0], int(chunk)):
+        Yc = Y[lo:lo + int(chunk)]
+        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64, order=order)
+        eta = m = logz = None
+        if U is not None:
+            eta = U[lo:lo + int(chunk)] @ V.T
+            if E is not None:
+                m = eta.max(1)
+                logz = m[:, None] + np.log(np.exp(eta - m[:, None]) @ E)
+        yield lo, Yc, eta, m, logz
+
+
 def _clone_loglik_host(Y, E, U=None, V=None, const=True, chunk=2048):
     """Float64 host form of ``HipEngine.clone_loglik`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time), E
     [G, C], U [N, D] and V [G, D] or both None.  Same return value, same rules (xlogy, the shift by the largest exponent), same refusals (ValueError)."""
@@ -238,17 +276,12 @@ def _clone_loglik_host(Y, E, U=None, V=None, const=True, chunk=2048):
     zero = E == 0
     logE = np.log(np.where(zero, 1.0, E))                            # xlogy: 0 where E = 0, put right below
     ll = np.empty((N, C))
-    for lo in range(0, N, int(chunk)):
-        Yc = Y[lo:lo + int(chunk)]
-        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+    for lo, Yc, eta, _m, logz in _cell_chunks(Y, chunk, E, U if D > 0 else None, V):
         s = Yc.sum(1)
         a = Yc @ logE
         if zero.any():
             a[((Yc > 0).astype(np.float64) @ zero.astype(np.float64)) > 0] = -np.inf
         if D > 0:
-            eta = U[lo:lo + int(chunk)] @ V.T
-            m = eta.max(1)
-            logz = m[:, None] + np.log(np.exp(eta - m[:, None]) @ E)
             a += (Yc * eta).sum(1)[:, None]
         else:
             logz = np.log(esum)[None, :]
@@ -259,10 +292,15 @@ def _clone_loglik_host(Y, E, U=None, V=None, const=True, chunk=2048):
     return ll
 
 
-def _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold, what="Y"):
-    """The model tables of a fit for ``N`` cells, shared by ``clone_loglik`` and ``simulate_counts``: ``L`` [G, C] (parsed) saturated as asked,
-    ``E = mu * L`` [G, C], ``U = [psi | x]`` [N, D] and ``V = [W | beta]`` [G, D] (both None when no exponent term is in play).  ``psi``: None (the
-    ``W`` term drops out), ``"fit"`` or an array [N, K]; ``x`` exactly when the fit has ``beta``.  ``what`` names the cells' owner in the refusals."""
+_FitTables = namedtuple("_FitTables", "L E U V W beta K P x")
+
+
+def _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold, what="Y", free_psi=False):
+    """The model tables of a fit for ``N`` cells, shared by the scoring calls and ``simulate_counts``: ``L`` [G, C] (parsed) saturated as asked,
+    ``E = mu * L`` [G, C], ``U = [psi | x]`` [N, D] and ``V = [W | beta]`` [G, D] (both None when no exponent term is in play), and the pieces: ``W``
+    [G, K], ``beta`` [G, P] and the checked ``x`` [N, P] (None without ``beta``).  ``psi``: None (the ``W`` term drops out), ``"fit"`` or an array
+    [N, K]; ``x`` exactly when the fit has ``beta``.  ``what`` names the cells' owner in the refusals.  ``free_psi``: the call solves for ``psi``
+    itself, so ``W``'s columns count towards the 8 exponent factors although no ``psi`` is given."""
     G = L.shape[0]
     ml = fit["ml_params"]
     mu = np.asarray(ml["mu"], dtype=np.float64).reshape(-1)
@@ -298,9 +336,10 @@ def _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold, what="Y"):
         Vcols.append(beta)
     U = np.concatenate(Ucols, axis=1) if Ucols else None
     V = np.concatenate(Vcols, axis=1) if Vcols else None
-    if U is not None and U.shape[1] > 8:
-        raise ValueError(f"the fit has {U.shape[1]} exponent factors (K + P); at most 8 are supported")
-    return L, E, U, V
+    D = (0 if U is None else U.shape[1]) + (K if free_psi else 0)
+    if D > 8:
+        raise ValueError(f"the fit has {D} exponent factors (K + P); at most 8 are supported")
+    return _FitTables(L, E, U, V, W, beta, K, P, x if P > 0 else None)
 
 
 def clone_loglik(fit, Y, L, *, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
@@ -318,25 +357,12 @@ def clone_loglik(fit, Y, L, *, x=None, psi=None, saturate=True, saturation_thres
     ``engine``: a live engine whose resident matrix is ``Y`` (used as it is); without it a throwaway engine is built for the upload only (``K=0``;
     ``engine_opts`` go to its constructor) and closed afterwards.  An engine without ``clone_loglik`` gets the chunked float64 host form.
     A positive count on a gene where a clone has copy number 0 makes that entry exactly ``-inf``; a zero count there adds nothing."""
-    L, _cn = _parse_cnv(L)
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if L.shape[0] != G:
-        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
-    L, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
-    own = engine is None
-    if own:
-        from .engine import HipEngine
-        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
-    try:
-        if hasattr(engine, "clone_loglik"):
-            if (engine.N, engine.G) != (N, G):
-                raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
-            return engine.clone_loglik(E, U, V, const=const)
-        return _clone_loglik_host(Y, E, U, V, const=const)
-    finally:
-        if own:
-            engine.close()
+    Y, L, _cn, N, _G = _cells_and_cnv(Y, L)
+    t = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
+    with _engine_lease(engine, "clone_loglik", Y, t.L, engine_opts) as eng:
+        if hasattr(eng, "clone_loglik"):
+            return eng.clone_loglik(t.E, t.U, t.V, const=const)
+        return _clone_loglik_host(Y, t.E, t.U, t.V, const=const)
 
 
 def assign_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=None, x=None, psi=None, saturate=True, saturation_threshold=6,
@@ -354,18 +380,42 @@ def assign_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=N
     return _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability)
 
 
-def _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability):
-    """``assign_cells``' result from the log-likelihood ``ll`` [cells, clones]."""
-    N, C = ll.shape
-    _L, cn = _parse_cnv(L)
-    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(C)])
+def _prior_terms(fit, extra_loglik, N, C):
+    """The addends of the clone posterior next to the log-likelihood, for the caller to add in its own order: ``(log alpha [1, C] or None when the fit
+    has no alpha, extra_loglik [N, C] as float64 or None)``; refuses an ``extra_loglik`` of another shape."""
     alpha = fit["ml_params"].get("alpha")
+    with np.errstate(divide="ignore"):
+        la = None if alpha is None else np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C))   # :308
+    ex = None if extra_loglik is None else np.asarray(extra_loglik, dtype=np.float64)
+    if ex is not None and ex.shape != (N, C):
+        raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
+    return la, ex
+
+
+def _log_prior(fit, extra_loglik, N, C):
+    """The [N, C] (or [1, C]) addend ``log alpha + extra_loglik`` of the clone posterior, formed before it meets the log-likelihood."""
+    la, ex = _prior_terms(fit, extra_loglik, N, C)
+    lp = np.zeros((1, C)) if la is None else la
+    with np.errstate(invalid="ignore"):
+        return lp if ex is None else lp + ex
+
+
+def _lse_clones(t):
+    """logsumexp over axis 1 of ``t`` [N, C, ...]; ``-inf`` where every clone is (no NaN)."""
     with np.errstate(divide="ignore", invalid="ignore"):
-        t = ll + (0.0 if alpha is None else np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C)))   # :308
-        if extra_loglik is not None:
-            ex = np.asarray(extra_loglik, dtype=np.float64)
-            if ex.shape != (N, C):
-                raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
+        m = t.max(1)
+        return np.where(np.isneginf(m), -np.inf, m + np.log(np.exp(t - np.where(np.isneginf(m), 0.0, m)[:, None]).sum(1)))
+
+
+def _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability):
+    """``assign_cells``' result from the log-likelihood ``ll`` [cells, clones]: the sum is formed as ``(ll + log alpha) + extra_loglik``, and the
+    logsumexp is its own -- a row of ``-inf`` is to give NaN probabilities."""
+    N, C = ll.shape
+    names = _clone_names(fit, _parse_cnv(L)[1], C)
+    la, ex = _prior_terms(fit, extra_loglik, N, C)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = ll + (0.0 if la is None else la)
+        if ex is not None:
             t = t + ex
         m = t.max(1, keepdims=True)
         lse = m + np.log(np.exp(t - m).sum(1, keepdims=True))        # (a row of -inf: NaN - no clone is possible)
@@ -420,11 +470,8 @@ def _clone_loglik_by_block_host(Y, E, U, V, block_of_gene, n_blocks, const=True,
     logE = np.log(np.where(zero, 1.0, E))                            # xlogy: 0 where E = 0, put right below
     A, logZ = np.zeros((N, B, C)), np.full((N, B, C), -np.inf)
     s, lg = np.zeros((N, B)), (np.zeros((N, B)) if const else None)
-    for lo in range(0, N, int(chunk)):
-        Yc = Y[lo:lo + int(chunk)]
-        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+    for lo, Yc, eta, _m, _logz in _cell_chunks(Y, chunk, None, U if D > 0 else None, V):
         hi = lo + Yc.shape[0]
-        eta = U[lo:hi] @ V.T if D > 0 else None
         for b, idx in enumerate(genes):
             if idx.size == 0:
                 continue
@@ -483,35 +530,16 @@ def _by_block_terms(A, logZ, s, lg):
     return {"within": within, "between": between, "without": without, "clone_loglik": within.sum(1) + between}
 
 
-def _by_block_setup(fit, Y, L, blocks, x, psi, saturate, saturation_threshold, engine, engine_opts):
-    """(Y, L, E, U, V, block names, block_of_gene, clone names, engine, whether it is ours) of a by-block call: ``clone_loglik``'s arguments through
-    ``_fit_tables``."""
-    L, cn = _parse_cnv(L)
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if L.shape[0] != G:
-        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
-    block_names, bg = _block_labels(blocks, G)
-    L, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
-    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(L.shape[1])])
-    own = engine is None
-    if own:
-        from .engine import HipEngine
-        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
-    elif hasattr(engine, "clone_loglik_by_block") and (engine.N, engine.G) != (N, G):
-        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
-    return Y, L, E, U, V, block_names, bg, names, engine, own
-
-
-def _by_block_call(engine, Y, E, U, V, bg, B, const, cells):
-    """The result dict of ``clone_loglik_by_block`` but for the names: through the engine's method, or through the host form when it has none."""
+def _by_block_call(engine, Y, t, bg, B, const, cells):
+    """The result dict of ``clone_loglik_by_block`` under the tables ``t`` but for the names: through the engine's method, or through the host form when it
+    has none."""
     lo, hi = (0, Y.shape[0]) if cells is None else (int(cells[0]), int(cells[1]))
     if hasattr(engine, "clone_loglik_by_block"):
-        st = engine.clone_loglik_by_block(E, U, V, bg, B, const=const, cells=(lo, hi))
+        st = engine.clone_loglik_by_block(t.E, t.U, t.V, bg, B, const=const, cells=(lo, hi))
     else:
         if not 0 <= lo <= hi <= Y.shape[0]:
             raise ValueError(f"clone_loglik_by_block: the cell range [{lo}, {hi}) is outside [0, {Y.shape[0]}]")
-        st = _clone_loglik_by_block_host(Y[lo:hi], E, None if U is None else U[lo:hi], V, bg, B, const=const)
+        st = _clone_loglik_by_block_host(Y[lo:hi], t.E, None if t.U is None else t.U[lo:hi], t.V, bg, B, const=const)
     out = _by_block_terms(st["A"], st["logZ"], st["s"], st["lg"])
     out["counts"] = st["s"]
     return out
@@ -534,12 +562,11 @@ def clone_loglik_by_block(fit, Y, L, blocks, *, x=None, psi=None, saturate=True,
     Returns a dict: ``block_names`` [B], ``counts`` [n, B] (reads per block), ``within`` [n, B, C] (0 where the cell has no reads in b), ``between``
     [n, C], ``without`` [n, B, C], ``clone_loglik`` [n, C] (``sum_b within + between``: ``clone_loglik``'s value up to rounding).  ``-inf`` exactly where a
     positive count meets copy number 0 among the genes that enter; no NaN."""
-    Y, _L, E, U, V, block_names, bg, _names, engine, own = _by_block_setup(fit, Y, L, blocks, x, psi, saturate, saturation_threshold, engine, engine_opts)
-    try:
-        out = _by_block_call(engine, Y, E, U, V, bg, len(block_names), const, cells)
-    finally:
-        if own:
-            engine.close()
+    Y, L, _cn, N, G = _cells_and_cnv(Y, L)
+    block_names, bg = _block_labels(blocks, G)
+    t = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
+    with _engine_lease(engine, "clone_loglik_by_block", Y, t.L, engine_opts) as eng:
+        out = _by_block_call(eng, Y, t, bg, len(block_names), const, cells)
     out["block_names"] = block_names
     return out
 
@@ -567,30 +594,24 @@ def assignment_support(fit, Y, L, blocks, clone_assignment_probability=0.95, *, 
     b left out -- negative means the call flips without b; ``margin_within`` [n, B]: the same difference of block b's ``within`` term alone (the evidence
     of b's genes given their total; no prior enters); ``n_flips`` [B]: cells whose argmax changes without b.  Rivals all ``-inf`` give ``+inf``; a cell
     with every clone ``-inf`` gets NaN margins and is "unassigned".  ``C < 2`` is a ValueError."""
-    Y, L, E, U, V, block_names, bg, _names, engine, own = _by_block_setup(fit, Y, L, blocks, x, psi, saturate, saturation_threshold, engine, engine_opts)
-    try:
-        C = L.shape[1]
-        if C < 2:
-            raise ValueError(f"assignment_support: C = {C} clones: a margin needs at least 2")
-        lo, hi = (0, Y.shape[0]) if cells is None else (int(cells[0]), int(cells[1]))
-        by = _by_block_call(engine, Y, E, U, V, bg, len(block_names), const, (lo, hi))
-        if hasattr(engine, "clone_loglik"):
-            ll = engine.clone_loglik(E, U, V, const=const)[lo:hi]
+    Y, Lm, _cn, N, G = _cells_and_cnv(Y, L)
+    block_names, bg = _block_labels(blocks, G)
+    ft = _fit_tables(fit, Lm, N, x, psi, saturate, saturation_threshold)
+    C = Lm.shape[1]
+    if C < 2:
+        raise ValueError(f"assignment_support: C = {C} clones: a margin needs at least 2")
+    lo, hi = (0, N) if cells is None else (int(cells[0]), int(cells[1]))
+    with _engine_lease(engine, "clone_loglik_by_block", Y, ft.L, engine_opts) as eng:
+        by = _by_block_call(eng, Y, ft, bg, len(block_names), const, (lo, hi))
+        if hasattr(eng, "clone_loglik"):
+            ll = eng.clone_loglik(ft.E, ft.U, ft.V, const=const)[lo:hi]
         else:
-            ll = _clone_loglik_host(Y[lo:hi], E, None if U is None else U[lo:hi], V, const=const)
-    finally:
-        if own:
-            engine.close()
+            ll = _clone_loglik_host(Y[lo:hi], ft.E, None if ft.U is None else ft.U[lo:hi], ft.V, const=const)
     n = ll.shape[0]
-    base = _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability)
+    base = _assign_from_loglik(fit, ll, ft.L, extra_loglik, clone_assignment_probability)   # (the parsed L: a DataFrame's column names do not name the clones here)
     names = base["clone_names"]
-    alpha = fit["ml_params"].get("alpha")
-    prior = np.zeros((n, C))
+    prior = np.zeros((n, C)) + _log_prior(fit, extra_loglik, n, C)
     with np.errstate(divide="ignore", invalid="ignore"):
-        if alpha is not None:
-            prior = prior + np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C))
-        if extra_loglik is not None:
-            prior = prior + np.asarray(extra_loglik, dtype=np.float64)
         t = ll + prior
         cstar = np.argmax(np.where(np.isnan(t), -np.inf, t), axis=1)
         tw = by["without"] + prior[:, None, :]
@@ -604,11 +625,6 @@ def assignment_support(fit, Y, L, blocks, clone_assignment_probability=0.95, *, 
                 probs_without=probs_without, clone_without=clone_without, margin=_margin(t, cstar), margin_without=_margin(tw, cstar),
                 margin_within=_margin(by["within"], cstar), n_flips=flips.sum(0).astype(np.int64))
     return base
-
-
-def _pair_list(C):
-    """The unordered clone pairs ``a < b`` in lexicographic order, [M, 2]."""
-    return np.array([(a, b) for a in range(C) for b in range(a + 1, C)], dtype=np.int64).reshape(-1, 2)
 
 
 def _pair_weights(weights, what="clone_pair_loglik", limit=8):
@@ -646,21 +662,16 @@ def _clone_pair_loglik_host(Y, E, U=None, V=None, weights=(0.5,), const=True, ch
     D = 0 if U is None else np.asarray(U).shape[1]
     if D > 0:
         U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-    pairs = _pair_list(C)
+    pairs = hostprep.pair_list(C)
     M, W = pairs.shape[0], w.shape[0]
     pll = np.empty((N, M, W))
     logz0 = np.log(E.sum(0))
-    for lo in range(0, N, int(chunk)):
-        Yc = Y[lo:lo + int(chunk)]
-        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+    for lo, Yc, eta, _m, logz in _cell_chunks(Y, chunk, E, U if D > 0 else None, V):
         n = Yc.shape[0]
         pos = Yc > 0
         s = Yc.sum(1)
         base = np.zeros(n)
         if D > 0:
-            eta = U[lo:lo + int(chunk)] @ V.T
-            m = eta.max(1)
-            logz = m[:, None] + np.log(np.exp(eta - m[:, None]) @ E)
             base += (Yc * eta).sum(1)
         else:
             logz = np.broadcast_to(logz0[None, :], (n, C))
@@ -678,32 +689,20 @@ def _clone_pair_loglik_host(Y, E, U=None, V=None, weights=(0.5,), const=True, ch
     return {"ll": ll, "pair_ll": pll, "pairs": pairs}
 
 
-def _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, engine, engine_opts, what):
-    """(Y, E, U, V, weight grid, clone names, engine, whether it is ours) of a pair call: ``clone_loglik``'s arguments through ``_fit_tables``."""
-    L, cn = _parse_cnv(L)
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if L.shape[0] != G:
-        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
+def _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, what):
+    """(Y, model tables, weight grid, clone names) of a pair call named ``what``."""
+    Y, L, cn, N, _G = _cells_and_cnv(Y, L)
     if L.shape[1] < 2:
         raise ValueError(f"{what}: C = {L.shape[1]} clones: a pair needs at least 2")
     grid = _pair_weight_grid(weights, what)
-    L, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
-    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(L.shape[1])])
-    own = engine is None
-    if own:
-        from .engine import HipEngine
-        engine = HipEngine(Y, L, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
-    elif hasattr(engine, "clone_pair_loglik") and (engine.N, engine.G) != (N, G):
-        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
-    return Y, E, U, V, grid, names, engine, own
+    return Y, _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold), grid, _clone_names(fit, cn, L.shape[1])
 
 
-def _pair_call(engine, Y, E, U, V, grid, const, lo, hi):
-    """Cells [lo, hi) through the engine's ``clone_pair_loglik``, or through the host form when it has none."""
+def _pair_call(engine, Y, t, grid, const, lo, hi):
+    """Cells [lo, hi) under the tables ``t`` through the engine's ``clone_pair_loglik``, or through the host form when it has none."""
     if hasattr(engine, "clone_pair_loglik"):
-        return engine.clone_pair_loglik(E, U, V, weights=grid, const=const, cells=(lo, hi))
-    return _clone_pair_loglik_host(Y[lo:hi], E, None if U is None else U[lo:hi], V, weights=grid, const=const)
+        return engine.clone_pair_loglik(t.E, t.U, t.V, weights=grid, const=const, cells=(lo, hi))
+    return _clone_pair_loglik_host(Y[lo:hi], t.E, None if t.U is None else t.U[lo:hi], t.V, weights=grid, const=const)
 
 
 def clone_pair_loglik(fit, Y, L, *, weights=(0.3, 0.5, 0.7), x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
@@ -715,12 +714,9 @@ def clone_pair_loglik(fit, Y, L, *, weights=(0.3, 0.5, 0.7), x=None, psi=None, s
 
     Returns ``{"ll" [cells, clones] (clone_loglik's), "pair_ll" [cells, M, W], "pairs" [M, 2] (lexicographic), "weights" [W] (the grid used)}``.  An engine
     without ``clone_pair_loglik`` gets the chunked float64 host form."""
-    Y, E, U, V, grid, _names, engine, own = _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, engine, engine_opts, "clone_pair_loglik")
-    try:
-        out = _pair_call(engine, Y, E, U, V, grid, const, 0, Y.shape[0])
-    finally:
-        if own:
-            engine.close()
+    Y, t, grid, _names = _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, "clone_pair_loglik")
+    with _engine_lease(engine, "clone_pair_loglik", Y, t.L, engine_opts) as eng:
+        out = _pair_call(eng, Y, t, grid, const, 0, Y.shape[0])
     out["weights"] = grid
     return out
 
@@ -743,38 +739,28 @@ def detect_doublets(fit, Y, L, doublet_rate=0.05, doublet_probability=0.5, clone
     rho = float(doublet_rate)
     if not (np.isfinite(rho) and 0.0 <= rho <= 1.0):
         raise ValueError(f"detect_doublets: doublet_rate = {doublet_rate} is outside [0, 1]")
-    Y, E, U, V, grid, names, engine, own = _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, engine, engine_opts, "detect_doublets")
-    N, C = Y.shape[0], E.shape[1]
-    pairs = _pair_list(C)
+    Y, ft, grid, names = _pair_setup(fit, Y, L, weights, x, psi, saturate, saturation_threshold, "detect_doublets")
+    N, C = Y.shape[0], ft.E.shape[1]
+    pairs = hostprep.pair_list(C)
     M, W = pairs.shape[0], grid.shape[0]
     alpha = fit["ml_params"].get("alpha")
-    alpha = np.full(C, 1.0 / C) if alpha is None else np.asarray(alpha, dtype=np.float64).reshape(C)
-    ex = None
-    if extra_loglik is not None:
-        ex = np.asarray(extra_loglik, dtype=np.float64)
-        if ex.shape != (N, C):
-            if own:
-                engine.close()
-            raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
+    alpha = np.full(C, 1.0 / C) if alpha is None else np.asarray(alpha, dtype=np.float64).reshape(C)   # (uniform where the fit has none)
+    _la, ex = _prior_terms(fit, extra_loglik, N, C)
     step = int(chunk_cells) if chunk_cells else max(1, (1 << 28) // (8 * M * W))
     ll = np.empty((N, C))
     pair_log = np.empty((N, M))                                      # log p(y | pair), the weights marginalised (uniform on the grid)
     w_mean = np.empty((N, M))
-    try:
-        with np.errstate(divide="ignore", invalid="ignore"):
-            for lo in range(0, N, step):
-                hi = min(N, lo + step)
-                r = _pair_call(engine, Y, E, U, V, grid, const, lo, hi)
-                ll[lo:hi] = r["ll"]
-                pl = r["pair_ll"]
-                m = pl.max(2, keepdims=True)
-                e = np.exp(pl - np.where(np.isneginf(m), 0.0, m))    # (a pair at -inf for every weight: all zeros, no NaN)
-                tot = e.sum(2)
-                pair_log[lo:hi] = np.where(np.isneginf(m[:, :, 0]), -np.inf, m[:, :, 0] + np.log(tot)) - np.log(W)
-                w_mean[lo:hi] = (e * grid[None, None, :]).sum(2) / tot
-    finally:
-        if own:
-            engine.close()
+    with _engine_lease(engine, "clone_pair_loglik", Y, ft.L, engine_opts) as eng, np.errstate(divide="ignore", invalid="ignore"):
+        for lo in range(0, N, step):
+            hi = min(N, lo + step)
+            r = _pair_call(eng, Y, ft, grid, const, lo, hi)
+            ll[lo:hi] = r["ll"]
+            pl = r["pair_ll"]
+            m = pl.max(2, keepdims=True)
+            e = np.exp(pl - np.where(np.isneginf(m), 0.0, m))        # (a pair at -inf for every weight: all zeros, no NaN)
+            tot = e.sum(2)
+            pair_log[lo:hi] = np.where(np.isneginf(m[:, :, 0]), -np.inf, m[:, :, 0] + np.log(tot)) - np.log(W)
+            w_mean[lo:hi] = (e * grid[None, None, :]).sum(2) / tot
     with np.errstate(divide="ignore", invalid="ignore"):
         het = 1.0 - (alpha ** 2).sum()
         t_s = ll + np.log(alpha)[None, :]                            # singlets, rho left out
@@ -782,11 +768,7 @@ def detect_doublets(fit, Y, L, doublet_rate=0.05, doublet_probability=0.5, clone
         if ex is not None:
             t_s = t_s + ex
             t_p = t_p + np.logaddexp(ex[:, pairs[:, 0]], ex[:, pairs[:, 1]]) - np.log(2.0)
-
-        def lse(t):
-            m = t.max(1)
-            return np.where(np.isneginf(m), -np.inf, m + np.log(np.exp(t - np.where(np.isneginf(m), 0.0, m)[:, None]).sum(1)))
-        ls, lp = lse(t_s), lse(t_p)
+        ls, lp = _lse_clones(t_s), _lse_clones(t_p)
         a_s, a_p = np.log1p(-rho) + ls, np.log(rho) + lp
         loglik = np.where(np.isneginf(a_s) & np.isneginf(a_p), -np.inf, np.logaddexp(a_s, a_p))
         dead = np.isneginf(loglik)
@@ -845,17 +827,12 @@ def _clone_loglik_dm_host(Y, E, U=None, V=None, concentration=(100.,), const=Tru
     dm = np.empty((N, C, K))
     scale = np.empty((N, C, K)) if with_scale else None
     logz0 = np.log(E.sum(0))
-    for lo in range(0, N, int(chunk)):
-        Yc = Y[lo:lo + int(chunk)]
-        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+    for lo, Yc, eta, m, logz in _cell_chunks(Y, chunk, E, U if D > 0 else None, V):
         n = Yc.shape[0]
         s = Yc.sum(1)
         r, g = np.nonzero(Yc > 0)                                    # the non-zero counts, rows ascending and genes ascending within a row
         y = Yc[r, g]
         if D > 0:
-            eta = U[lo:lo + int(chunk)] @ V.T
-            m = eta.max(1)
-            logz = m[:, None] + np.log(np.exp(eta - m[:, None]) @ E)
             t = np.exp(eta[r, g] - m[r])
         else:
             m, logz, t = np.zeros(n), np.broadcast_to(logz0[None, :], (n, C)), np.ones(y.shape[0])
@@ -880,28 +857,11 @@ def _clone_loglik_dm_host(Y, E, U=None, V=None, concentration=(100.,), const=Tru
     return {"ll": ll, "dm_ll": dm} if scale is None else {"ll": ll, "dm_ll": dm, "scale": scale}
 
 
-def _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts):
-    """(Y, L, E, U, V, engine, whether it is ours) of a Dirichlet-multinomial call: ``clone_loglik``'s arguments through ``_fit_tables``."""
-    L, _cn = _parse_cnv(L)
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if L.shape[0] != G:
-        raise ValueError(f"L has {L.shape[0]} rows (genes) but Y has {G} columns (genes)")
-    Ls, E, U, V = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
-    own = engine is None
-    if own:
-        from .engine import HipEngine
-        engine = HipEngine(Y, Ls, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
-    elif hasattr(engine, "clone_loglik_dm") and (engine.N, engine.G) != (N, G):
-        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
-    return Y, E, U, V, engine, own
-
-
-def _dm_call(engine, Y, E, U, V, phi, const):
-    """All cells through the engine's ``clone_loglik_dm``, or through the host form when it has none."""
+def _dm_call(engine, Y, t, phi, const):
+    """All cells under the tables ``t`` through the engine's ``clone_loglik_dm``, or through the host form when it has none."""
     if hasattr(engine, "clone_loglik_dm"):
-        return engine.clone_loglik_dm(E, U, V, concentration=phi, const=const)
-    return _clone_loglik_dm_host(Y, E, U, V, concentration=phi, const=const)
+        return engine.clone_loglik_dm(t.E, t.U, t.V, concentration=phi, const=const)
+    return _clone_loglik_dm_host(Y, t.E, t.U, t.V, concentration=phi, const=const)
 
 
 def clone_loglik_dm(fit, Y, L, *, concentration, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
@@ -914,48 +874,25 @@ def clone_loglik_dm(fit, Y, L, *, concentration, x=None, psi=None, saturate=True
     Returns ``{"ll" [cells, clones] (clone_loglik's), "dm_ll" [cells, clones, n_conc], "concentration" [n_conc]}``.  An engine without
     ``clone_loglik_dm`` gets the chunked float64 host form."""
     phi = _dm_concentrations(concentration)
-    Y, E, U, V, engine, own = _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts)
-    try:
-        out = _dm_call(engine, Y, E, U, V, phi, const)
-    finally:
-        if own:
-            engine.close()
+    Y, Lm, _cn, N, _G = _cells_and_cnv(Y, L)
+    t = _fit_tables(fit, Lm, N, x, psi, saturate, saturation_threshold)
+    with _engine_lease(engine, "clone_loglik_dm", Y, t.L, engine_opts) as eng:
+        out = _dm_call(eng, Y, t, phi, const)
     out["concentration"] = phi
     return out
 
 
-def _dm_prior(fit, extra_loglik, N, C):
-    """The [N, C] (or [1, C]) addend ``log alpha + extra_loglik`` of the clone posterior."""
-    alpha = fit["ml_params"].get("alpha")
-    with np.errstate(divide="ignore"):
-        lp = np.zeros((1, C)) if alpha is None else np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C))
-    if extra_loglik is not None:
-        ex = np.asarray(extra_loglik, dtype=np.float64)
-        if ex.shape != (N, C):
-            raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
-        lp = lp + ex
-    return lp
-
-
-def _lse_clones(t):
-    """logsumexp over axis 1 of ``t`` [N, C, ...]; ``-inf`` where every clone is (no NaN)."""
-    with np.errstate(divide="ignore", invalid="ignore"):
-        m = t.max(1)
-        return np.where(np.isneginf(m), -np.inf, m + np.log(np.exp(t - np.where(np.isneginf(m), 0.0, m)[:, None]).sum(1)))
-
-
-def _estimate_concentration(fit, engine, Y, E, U, V, grid, refine, extra_loglik, const):
+def _estimate_concentration(fit, engine, Y, t, grid, refine, extra_loglik, const):
     """``estimate_concentration`` on a live engine; also returns the log-likelihoods at the chosen concentration (``assign_cells_dm`` reuses them)."""
     grid = np.unique(_dm_concentrations(DM_DEFAULT_GRID if grid is None else grid, "estimate_concentration", limit=1 << 30))
-    N, C = Y.shape[0], E.shape[1]
-    lp = _dm_prior(fit, extra_loglik, N, C)
+    lp = _log_prior(fit, extra_loglik, Y.shape[0], t.E.shape[1])
     seen, ll = {}, None                                              # concentration -> (marginal, dm_ll [N, C])
 
     def visit(values):
         nonlocal ll
         for lo in range(0, len(values), 16):                         # (16 concentrations per device call)
             phi = np.asarray(values[lo:lo + 16], dtype=np.float64)
-            r = _dm_call(engine, Y, E, U, V, phi, const)
+            r = _dm_call(engine, Y, t, phi, const)
             ll = r["ll"]
             cell = _lse_clones(r["dm_ll"] + lp[:, :, None])         # [N, n_conc]
             for k, v in enumerate(phi):
@@ -989,12 +926,10 @@ def estimate_concentration(fit, Y, L, *, grid=None, refine=2, extra_loglik=None,
     ``multinomial_marginal_loglik`` (the same sum under ``clone_loglik``: the limit ``phi -> inf``, from the same call), ``at_edge`` -- True when the
     arg-max of the first grid is its largest value (no detectable overdispersion: the multinomial is adequate) or its smallest; no refinement is made then --
     and ``n_cells_used`` (cells that are ``-inf`` under every clone are left out of every sum)."""
-    Y, E, U, V, engine, own = _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts)
-    try:
-        return _estimate_concentration(fit, engine, Y, E, U, V, grid, refine, extra_loglik, const)[0]
-    finally:
-        if own:
-            engine.close()
+    Y, Lm, _cn, N, _G = _cells_and_cnv(Y, L)
+    t = _fit_tables(fit, Lm, N, x, psi, saturate, saturation_threshold)
+    with _engine_lease(engine, "clone_loglik_dm", Y, t.L, engine_opts) as eng:
+        return _estimate_concentration(fit, eng, Y, t, grid, refine, extra_loglik, const)[0]
 
 
 def assign_cells_dm(fit, Y, L, concentration="auto", clone_assignment_probability=0.95, *, grid=None, refine=2, extra_loglik=None, x=None, psi=None,
@@ -1012,16 +947,14 @@ def assign_cells_dm(fit, Y, L, concentration="auto", clone_assignment_probabilit
     if auto and concentration != "auto":
         raise ValueError(f"assign_cells_dm: concentration must be a value > 0 or \"auto\", got {concentration!r}")
     phi = None if auto else _dm_concentrations([concentration], "assign_cells_dm")
-    Yc, E, U, V, engine, own = _dm_setup(fit, Y, L, x, psi, saturate, saturation_threshold, engine, engine_opts)
-    try:
+    Yc, Lm, _cn, N, _G = _cells_and_cnv(Y, L)
+    t = _fit_tables(fit, Lm, N, x, psi, saturate, saturation_threshold)
+    with _engine_lease(engine, "clone_loglik_dm", Yc, t.L, engine_opts) as eng:
         if auto:
-            est, dm, ll = _estimate_concentration(fit, engine, Yc, E, U, V, grid, refine, extra_loglik, const)
+            est, dm, ll = _estimate_concentration(fit, eng, Yc, t, grid, refine, extra_loglik, const)
         else:
-            r = _dm_call(engine, Yc, E, U, V, phi, const)
+            r = _dm_call(eng, Yc, t, phi, const)
             est, dm, ll = None, r["dm_ll"][:, :, 0], r["ll"]
-    finally:
-        if own:
-            engine.close()
     out = _assign_from_loglik(fit, dm, L, extra_loglik, clone_assignment_probability)
     multi = _assign_from_loglik(fit, ll, L, extra_loglik, clone_assignment_probability)
     out.update(concentration=est["concentration"] if auto else float(phi[0]), multinomial_clone_loglik=ll, multinomial_clone_probs=multi["clone_probs"],
@@ -1087,9 +1020,7 @@ def _project_cells_host(Y, E, V, K, P, X, log_prior, psi_start, const=True, max_
     tri = [(k, l) for k in range(K) for l in range(k, K)]
     out = {"psi": psi, "ll": np.empty((N, C)), "clone_probs": np.empty((N, C)), "objective": np.empty(N), "rounds": np.zeros(N, dtype=np.int32),
            "converged": np.zeros(N, dtype=bool)}
-    for lo in range(0, N, int(chunk)):
-        Yc = Y[lo:lo + int(chunk)]
-        Yc = np.asarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)
+    for lo, Yc, _eta, _m, _logz in _cell_chunks(Y, chunk):
         n = Yc.shape[0]
         s = Yc.sum(1)
         A = Yc @ logE                                                # the sweep: A, B, s and the constant
@@ -1183,74 +1114,32 @@ def project_cells(fit, Y, L, clone_assignment_probability=0.95, *, extra_loglik=
     Returns a :class:`ClonealignFit` with ``psi`` [cells, K], ``clone_probs``, ``clone``, ``loglik`` (``F + |psi|^2 / 2``: the cell's marginal over the
     clones at its psi), ``objective`` (``F``), ``clone_loglik`` [cells, clones], ``rounds``, ``converged`` and ``clone_names``;
     ``recompute_clone_assignment`` works on it.  A fit with ``K = 0`` returns what ``assign_cells`` returns, plus an empty ``psi``."""
-    ml = fit["ml_params"]
-    Lm, cn = _parse_cnv(L)
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if Lm.shape[0] != G:
-        raise ValueError(f"L has {Lm.shape[0]} rows (genes) but Y has {G} columns (genes)")
-    W = np.asarray(ml["W"], dtype=np.float64).reshape(G, -1) if ml.get("W") is not None else np.zeros((G, 0))
-    K = W.shape[1]
+    Y, Lm, cn, N, _G = _cells_and_cnv(Y, L)
+    t = _fit_tables(fit, Lm, N, x, None, saturate, saturation_threshold, free_psi=True)
+    K, C = t.K, Lm.shape[1]
     if K == 0:
         out = assign_cells(fit, Y, L, clone_assignment_probability, extra_loglik=extra_loglik, x=x, saturate=saturate,
                            saturation_threshold=saturation_threshold, const=const, engine=engine, engine_opts=engine_opts)
         out.update(psi=np.zeros((N, 0)), objective=out["loglik"].copy(), rounds=np.zeros(N, dtype=np.int32), converged=np.isfinite(out["loglik"]))
         out["ml_params"] = {"psi": out["psi"], "clone_probs": out["clone_probs"]}
         return out
-    mu = np.asarray(ml["mu"], dtype=np.float64).reshape(-1)
-    if mu.shape[0] != G:
-        raise ValueError(f"fit$ml_params$mu has length {mu.shape[0]} but L has {G} rows: evaluate on the retained genes")
-    C = Lm.shape[1]
-    if "clone_names" in fit and len(fit["clone_names"]) != C:
-        raise ValueError(f"fit has {len(fit['clone_names'])} clone names but L has {C} columns (clones)")
-    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(C)])
-    if saturate:
-        Lm = hostprep.saturate(Lm, saturation_threshold)             # :142-144
-    E = mu[:, None] * Lm
-    beta = np.asarray(ml["beta"], dtype=np.float64).reshape(G, -1) if ml.get("beta") is not None else np.zeros((G, 0))
-    P = beta.shape[1]
-    if (P > 0) != (x is not None):
-        raise ValueError(f"x is required exactly when the fit has beta: the fit has {P} covariates and x is {'missing' if x is None else 'given'}")
-    if K + P > 8:
-        raise ValueError(f"the fit has {K + P} exponent factors (K + P); at most 8 are supported")
-    if P > 0:
-        x = np.asarray(x, dtype=np.float64)
-        x = x.reshape(-1, 1) if x.ndim == 1 else x
-        if x.shape != (N, P):
-            raise ValueError(f"x is {x.shape} but Y has {N} rows (cells) and the fit {P} covariates")
+    names = _clone_names(fit, cn, C)
     if psi_start is not None:
         psi_start = np.asarray(psi_start, dtype=np.float64)
         if psi_start.size != N * K:
             raise ValueError(f"psi_start has {psi_start.size} entries but Y has {N} rows (cells) and the fit K = {K}")
         psi_start = psi_start.reshape(N, K)
-    V = np.concatenate([W, beta], axis=1)
-    alpha = ml.get("alpha")
+    V = np.concatenate([t.W, t.beta], axis=1)
     lp = None
-    if alpha is not None or extra_loglik is not None:
-        with np.errstate(divide="ignore"):
-            lp = np.zeros((N, C)) + (0.0 if alpha is None else np.log(np.asarray(alpha, dtype=np.float64).reshape(1, C)))   # :308
-        if extra_loglik is not None:
-            ex = np.asarray(extra_loglik, dtype=np.float64)
-            if ex.shape != (N, C):
-                raise ValueError(f"extra_loglik is {ex.shape} but the log-likelihood is {N} x {C}")
-            lp = lp + ex
-    own = engine is None
-    if own:
-        from .engine import HipEngine
-        engine = HipEngine(Y, Lm, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
-    try:
-        if hasattr(engine, "project_cells"):
-            if (engine.N, engine.G) != (N, G):
-                raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
+    if fit["ml_params"].get("alpha") is not None or extra_loglik is not None:
+        lp = np.zeros((N, C)) + _log_prior(fit, extra_loglik, N, C)
+    with _engine_lease(engine, "project_cells", Y, t.L, engine_opts) as eng:
+        if hasattr(eng, "project_cells"):
             if K > 2:
                 raise ValueError(f"the fit has K = {K} latent factors; the device form of project_cells takes K <= 2")
-            r = engine.project_cells(E, V, K, X=x if P > 0 else None, log_prior=lp, psi_start=psi_start, const=const, max_iter=max_iter, tol=tol,
-                                     max_step=max_step)
+            r = eng.project_cells(t.E, V, K, X=t.x, log_prior=lp, psi_start=psi_start, const=const, max_iter=max_iter, tol=tol, max_step=max_step)
         else:
-            r = _project_cells_host(Y, E, V, K, P, x if P > 0 else None, lp, psi_start, const, max_iter, tol, max_step)
-    finally:
-        if own:
-            engine.close()
+            r = _project_cells_host(Y, t.E, V, K, t.P, t.x, lp, psi_start, const, max_iter, tol, max_step)
     psi, probs = r["psi"], r["clone_probs"]
     return ClonealignFit(psi=psi, clone_probs=probs, clone=clone_assignment(probs, names, clone_assignment_probability),
                          loglik=r["objective"] + 0.5 * (psi ** 2).sum(1), objective=r["objective"], clone_loglik=r["ll"], rounds=r["rounds"],
@@ -1360,9 +1249,7 @@ def _clone_evidence_host(Y, E, V, K, P, X, psi_start, nodes, weights, const=True
     W, beta = V[:, :K], V[:, K:]
     Et = np.ascontiguousarray(E.T)
     step = int(chunk) if chunk is not None else max(1, 4_000_000 // max(1, C * G))
-    for lo in range(0, N, step):
-        Yc = Y[lo:lo + step]
-        Yc = np.ascontiguousarray(Yc.toarray() if _is_sparse(Yc) else Yc, dtype=np.float64)   # (one memory order: the products below sum the same way)
+    for lo, Yc, _eta, _m, _logz in _cell_chunks(Y, step, order="C"):   # (one memory order: the products below sum the same way)
         n = Yc.shape[0]
         s = Yc.sum(1)
         A = Yc @ logE                                                # the sweep: A, B, s and the constant
@@ -1495,37 +1382,11 @@ def _prec_to_cov(prec, K):
     return np.linalg.inv(H) if K else H
 
 
-def _evidence_setup(fit, Y, L, x, saturate, saturation_threshold, engine, engine_opts):
-    """(Y, L parsed, clone names or None, engine, whether it is ours) shared by the evidence calls: the upload happens once."""
-    Lm, cn = _parse_cnv(L)
-    Y = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Y.shape
-    if Lm.shape[0] != G:
-        raise ValueError(f"L has {Lm.shape[0]} rows (genes) but Y has {G} columns (genes)")
-    own = engine is None
-    if own:
-        from .engine import HipEngine
-        Ls = hostprep.saturate(Lm, saturation_threshold) if saturate else Lm
-        engine = HipEngine(Y, Ls, np.zeros((N, 0)), None, 0, **(engine_opts or {}))
-    elif hasattr(engine, "clone_evidence") and (engine.N, engine.G) != (N, G):
-        raise ValueError(f"the engine holds a {engine.N} x {engine.G} matrix but Y is {N} x {G}")
-    return Y, Lm, cn, engine, own
-
-
 def _clone_evidence_on(engine, fit, Y, Lm, n_nodes, x, psi_start, saturate, saturation_threshold, const, max_iter, tol, max_step):
     """``clone_evidence`` of one fit on a live engine (or the host form for an engine without the method)."""
-    N, G = Y.shape
-    _Ls, E, _U, _V = _fit_tables(fit, Lm, N, x, None, saturate, saturation_threshold)
-    ml = fit["ml_params"]
-    W = np.asarray(ml["W"], dtype=np.float64).reshape(G, -1) if ml.get("W") is not None else np.zeros((G, 0))
-    beta = np.asarray(ml["beta"], dtype=np.float64).reshape(G, -1) if ml.get("beta") is not None else np.zeros((G, 0))
-    K, P = W.shape[1], beta.shape[1]
-    if K + P > 8:
-        raise ValueError(f"the fit has {K + P} exponent factors (K + P); at most 8 are supported")
-    X = None
-    if P > 0:
-        X = np.asarray(x, dtype=np.float64)
-        X = X.reshape(-1, 1) if X.ndim == 1 else X
+    N = Y.shape[0]
+    t = _fit_tables(fit, Lm, N, x, None, saturate, saturation_threshold, free_psi=True)
+    E, K, P, X = t.E, t.K, t.P, t.x
     if psi_start is not None:
         psi_start = np.asarray(psi_start, dtype=np.float64)
         if psi_start.size != N * K:
@@ -1533,7 +1394,7 @@ def _clone_evidence_on(engine, fit, Y, Lm, n_nodes, x, psi_start, saturate, satu
         psi_start = psi_start.reshape(N, K)
     per_axis = int(n_nodes) if n_nodes is not None else (8 if K <= 1 else 5)
     nodes, weights = gauss_hermite_rule(K, per_axis)
-    V = np.concatenate([W, beta], axis=1) if K + P > 0 else None
+    V = np.concatenate([t.W, t.beta], axis=1) if K + P > 0 else None
     if hasattr(engine, "clone_evidence"):
         if K > 2:
             raise ValueError(f"the fit has K = {K} latent factors; the device form of clone_evidence takes K <= 2")
@@ -1562,12 +1423,9 @@ def clone_evidence(fit, Y, L, *, n_nodes=None, x=None, psi_start=None, saturate=
     Returns a dict: ``evidence`` and ``laplace`` [cells, clones], ``psi_mode`` [cells, clones, K], ``psi_cov`` [cells, clones, K, K] (the inverse
     precision at the mode: the Laplace covariance), ``rounds`` and ``converged`` [cells, clones].  A pair with ``converged`` False (``max_iter`` reached)
     holds a value that is deterministic but NOT to be trusted."""
-    Yc, Lm, _cn, engine, own = _evidence_setup(fit, Y, L, x, saturate, saturation_threshold, engine, engine_opts)
-    try:
-        return _clone_evidence_on(engine, fit, Yc, Lm, n_nodes, x, psi_start, saturate, saturation_threshold, const, max_iter, tol, max_step)
-    finally:
-        if own:
-            engine.close()
+    Yc, Lm, _cn, _N, _G = _cells_and_cnv(Y, L)
+    with _engine_lease(engine, "clone_evidence", Yc, hostprep.saturate(Lm, saturation_threshold) if saturate else Lm, engine_opts) as eng:
+        return _clone_evidence_on(eng, fit, Yc, Lm, n_nodes, x, psi_start, saturate, saturation_threshold, const, max_iter, tol, max_step)
 
 
 def _marginal_from_evidence(fit, r, L, extra_loglik, clone_assignment_probability):
@@ -1614,17 +1472,13 @@ def heldout_evidence(fits, Y, L, *, x=None, extra_loglik=None, n_nodes=None, sat
     items = list(fits.items()) if isinstance(fits, dict) else [(i, f) for i, f in enumerate(fits)]
     if not items:
         raise ValueError("heldout_evidence: no fit given")
-    Yc, Lm, _cn, engine, own = _evidence_setup(items[0][1], Y, L, x, saturate, saturation_threshold, engine, engine_opts)
-    N = Yc.shape[0]
+    Yc, Lm, _cn, N, _G = _cells_and_cnv(Y, L)
     res = {}
-    try:
+    with _engine_lease(engine, "clone_evidence", Yc, hostprep.saturate(Lm, saturation_threshold) if saturate else Lm, engine_opts) as eng:
         for name, fit in items:
-            r = _clone_evidence_on(engine, fit, Yc, Lm, n_nodes, x, None, saturate, saturation_threshold, const, max_iter, tol, max_step)
-            cell = _lse_clones(r["evidence"] + _dm_prior(fit, extra_loglik, N, r["evidence"].shape[1]))
+            r = _clone_evidence_on(eng, fit, Yc, Lm, n_nodes, x, None, saturate, saturation_threshold, const, max_iter, tol, max_step)
+            cell = _lse_clones(r["evidence"] + _log_prior(fit, extra_loglik, N, r["evidence"].shape[1]))
             res[name] = {"per_cell": cell, "n_unconverged": int((~r["converged"] & np.isfinite(r["evidence"])).sum())}
-    finally:
-        if own:
-            engine.close()
     live = np.ones(N, dtype=bool)
     for v in res.values():
         live &= np.isfinite(v["per_cell"])
@@ -1751,7 +1605,7 @@ def simulate_counts(fit, L, *, n_cells=None, clones=None, total_counts=None, psi
     G, C = Lm.shape
     if total_counts is None:
         raise ValueError("total_counts is required: a scalar or one library size per cell (the observed row sums give posterior predictive replicates)")
-    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(C)])
+    names = _clone_names(fit, cn, C)
     if len(names) != C:
         raise ValueError(f"fit has {len(names)} clone names but L has {C} columns (clones)")
     ml = fit["ml_params"]
@@ -1796,7 +1650,7 @@ def simulate_counts(fit, L, *, n_cells=None, clones=None, total_counts=None, psi
             idx = np.array([lut[c] for c in cl], dtype=np.int32)
     if K > 0 and psi is None:
         psi = gen.standard_normal((N, K))
-    Ls, E, U, V = _fit_tables(fit, Lm, N, x, psi if K > 0 else None, saturate, saturation_threshold, what="the simulation")
+    _Ls, E, U, V = _fit_tables(fit, Lm, N, x, psi if K > 0 else None, saturate, saturation_threshold, what="the simulation")[:4]
     psi_out = U[:, :K].copy() if K > 0 else np.zeros((N, 0))
     if host:
         counts, _flagged = _simulate_counts_host(E, V, U, idx, total, seed, draw)
@@ -1921,12 +1775,8 @@ def predictive_check(fit, Y, L, n_rep=50, *, seed=0, x=None, saturate=True, satu
     n_rep = int(n_rep)
     if n_rep < 2:
         raise ValueError("n_rep must be at least 2 (the replicates' spread is the scale)")
-    Lm, cn = _parse_cnv(L)
-    Ya = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
-    N, G = Ya.shape
-    if Lm.shape[0] != G:
-        raise ValueError(f"L has {Lm.shape[0]} rows (genes) but Y has {G} columns (genes)")
-    names = list(fit["clone_names"]) if "clone_names" in fit else (cn if cn is not None else [f"clone_{string.ascii_lowercase[i]}" for i in range(Lm.shape[1])])
+    Ya, Lm, cn, N, G = _cells_and_cnv(Y, L)
+    names = _clone_names(fit, cn, Lm.shape[1])
     if len(names) != Lm.shape[1]:
         raise ValueError(f"fit has {len(names)} clone names but L has {Lm.shape[1]} columns (clones)")
     clones = np.asarray(fit["clone"], dtype=object).reshape(-1)
@@ -1942,7 +1792,7 @@ def predictive_check(fit, Y, L, n_rep=50, *, seed=0, x=None, saturate=True, satu
         raise ValueError("every cell is \"unassigned\": there is nothing to evaluate")
     ml = fit["ml_params"]
     has_psi = ml.get("W") is not None and np.asarray(ml["W"]).size > 0
-    Ls, E, U, V = _fit_tables(fit, Lm, N, x, "fit" if has_psi else None, saturate, saturation_threshold)
+    Ls, E, U, V = _fit_tables(fit, Lm, N, x, "fit" if has_psi else None, saturate, saturation_threshold)[:4]
     rows = np.asarray(Ya.sum(axis=1)).reshape(-1)
     if np.any(rows != np.floor(rows)):
         raise ValueError("Y must hold whole numbers: a replicate keeps the observed row sums")

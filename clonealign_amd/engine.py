@@ -9,6 +9,8 @@ import os
 
 import numpy as np
 
+from . import hostprep
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libclonealign_hip.so")
 
@@ -116,6 +118,11 @@ HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_
 POLL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_double)
 
 _lib = None
+
+
+def _ptr(a, empty_null=False):
+    """The C pointer of array ``a``; NULL for None and, when asked, for an array without elements."""
+    return None if a is None or (empty_null and a.size == 0) else a.ctypes.data_as(C.c_void_p)
 
 
 def load_library(path=None):
@@ -446,11 +453,10 @@ class HipEngine:
         if L.shape[0] != self.G or (loc0 is not None and loc0.shape[0] != self.G):
             raise ValueError("L / loc0 do not match the number of genes")
         self._keep += [L, loc0, psi0, Xc, ex, ci, gi]
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
         prob = CaProblem(N=self.N, G=self.G, C=self.C, K=self.K, P=self.P, S=self.S, layout=self.layout,
-                         y_dtype=y_dt, y_on_device=int(y_device_ptr is not None), Y=y_ptr, L=ptr(L),
-                         psi0=ptr(psi0) if self.K > 0 else None, loc0=ptr(loc0), X=ptr(Xc), extra_loglik=ptr(ex),
-                         N_src=int(Ns), G_src=int(Gs), cell_index=ptr(ci), gene_index=ptr(gi))
+                         y_dtype=y_dt, y_on_device=int(y_device_ptr is not None), Y=y_ptr, L=_ptr(L),
+                         psi0=_ptr(psi0) if self.K > 0 else None, loc0=_ptr(loc0), X=_ptr(Xc), extra_loglik=_ptr(ex),
+                         N_src=int(Ns), G_src=int(Gs), cell_index=_ptr(ci), gene_index=_ptr(gi))
         opt = CaOptions()
         self.lib.ca_default_options(C.byref(opt))
         opt.learning_rate = float(learning_rate)
@@ -635,7 +641,7 @@ class HipEngine:
         nz = None if noise is None else np.require(np.asarray(noise, dtype=np.float64).reshape(self.N, self.K),
                                                    requirements=[self._order, "A"])
         if self.K > 0:
-            self._ck(self._fn("init_psi_pca")(self.h, None if nz is None else nz.ctypes.data_as(C.c_void_p), int(n_iter),
+            self._ck(self._fn("init_psi_pca")(self.h, _ptr(nz), int(n_iter),
                                               int(seed) & 0xFFFFFFFFFFFFFFFF, out.ctypes.data_as(C.c_void_p)))
         return out
 
@@ -657,8 +663,7 @@ class HipEngine:
         tot, used = C.c_double(), C.c_int64()
         sg = np.zeros(self.G, dtype=np.float64) if per_gene else None
         sc = np.zeros(self.N, dtype=np.float64) if per_cell else None
-        self._ck(self._fn("fit_mse")(self.h, ci.ctypes.data_as(C.c_void_p), Em.ctypes.data_as(C.c_void_p), C.byref(tot), C.byref(used),
-                                     None if sg is None else sg.ctypes.data_as(C.c_void_p), None if sc is None else sc.ctypes.data_as(C.c_void_p)))
+        self._ck(self._fn("fit_mse")(self.h, ci.ctypes.data_as(C.c_void_p), Em.ctypes.data_as(C.c_void_p), C.byref(tot), C.byref(used), _ptr(sg), _ptr(sc)))
         out = {"sse": tot.value, "n_cells": int(used.value),
                "mse": tot.value / (used.value * self.G) if used.value > 0 and self.G > 0 else float("nan")}
         if per_gene:
@@ -678,9 +683,73 @@ class HipEngine:
         S1 = np.zeros((self.G, max(Q, 0)), dtype=np.float64, order=self._order)
         S2 = np.zeros(self.G, dtype=np.float64)
         ng = np.zeros(max(Q, 0), dtype=np.int64)
-        self._ck(self._fn("logexpr_sums")(self.h, gi.ctypes.data_as(C.c_void_p), Q, None if sf is None else sf.ctypes.data_as(C.c_void_p),
+        self._ck(self._fn("logexpr_sums")(self.h, gi.ctypes.data_as(C.c_void_p), Q, _ptr(sf),
                                           S1.ctypes.data_as(C.c_void_p), S2.ctypes.data_as(C.c_void_p), ng.ctypes.data_as(C.c_void_p)))
         return {"S1": S1, "S2": S2, "n_group": ng}
+
+    def _ll_operands(self, what, E, U, V):
+        """(Em, Um, Vm, D) of a log-likelihood call named ``what``: ``E`` [G, C], ``U`` [N, D] and ``V`` [G, D] in the engine's order; D = 0 passes no U, V."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"{what}: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        if (U is None) != (V is None):
+            raise ValueError(f"{what}: U and V go together (both, or neither)")
+        D = 0
+        Um = Vm = None
+        if U is not None:
+            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
+                raise ValueError(f"{what}: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
+            D = int(U.shape[1])
+            if D > 0:
+                Um, Vm = self._in_order(U), self._in_order(V)
+        return self._in_order(E), Um, Vm, D
+
+    def _latent_operands(self, what, E, V, K, X, psi_start, const, poll_every):
+        """(Em, Vm, K, P, Xm, psm, flags) of a latent-factor call named ``what``: ``E`` [G, C], ``V`` [G, K + P], ``X`` [N, P] and ``psi_start`` [N, K] in
+        the engine's order (None where the library takes NULL); ``flags`` = the constant's bit | ``poll_every`` << 8."""
+        E = np.asarray(E, dtype=np.float64)
+        if E.shape != (self.G, self.C):
+            raise ValueError(f"{what}: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
+        K = int(K)
+        Vm = Xm = psm = None
+        D = 0
+        if V is not None:
+            V = np.asarray(V, dtype=np.float64)
+            if V.ndim != 2 or V.shape[0] != self.G:
+                raise ValueError(f"{what}: V is {V.shape}; expected ({self.G}, K + P)")
+            D = int(V.shape[1])
+        P = D - K
+        if P < 0:
+            raise ValueError(f"{what}: V has {D} columns but K = {K}")
+        if D > 0:
+            Vm = self._in_order(V)
+        if X is not None or P > 0:
+            X = np.zeros((self.N, 0)) if X is None else np.asarray(X, dtype=np.float64)
+            if X.shape != (self.N, P):
+                raise ValueError(f"{what}: X is {X.shape}; V has K + P = {D} columns with K = {K}, so X must be ({self.N}, {P})")
+            Xm = self._in_order(X) if P > 0 else None
+        if psi_start is not None and K > 0:
+            psi_start = np.asarray(psi_start, dtype=np.float64)
+            if psi_start.shape != (self.N, K):
+                raise ValueError(f"{what}: psi_start is {psi_start.shape}; expected ({self.N}, {K})")
+            psm = self._in_order(psi_start)
+        if poll_every is not None and not 1 <= int(poll_every) <= 255:
+            raise ValueError(f"{what}: poll_every must be in [1, 255]")
+        flags = int(bool(const)) | ((int(poll_every) if poll_every is not None else 0) << 8)
+        return self._in_order(E), Vm, K, P, Xm, psm, flags
+
+    def _in_order(self, a):
+        return np.require(a, requirements=[self._order, "A"])
+
+    def _zeros(self, *shape):
+        """A float64 output buffer in the engine's order."""
+        return np.zeros(shape, dtype=np.float64, order=self._order)
+
+    def _cell_range(self, cells):
+        """(lo, hi, n) of ``cells`` = ``(lo, hi)`` or None for all resident cells."""
+        lo, hi = (0, self.N) if cells is None else (int(cells[0]), int(cells[1]))
+        return lo, hi, max(hi - lo, 0)
 
     def clone_loglik(self, E, U=None, V=None, const=True):
         """Log-likelihood ``ll`` [N, C] of every resident cell under every clone at point estimates, in one float64 sweep over the resident matrix
@@ -688,25 +757,9 @@ class HipEngine:
         ``E`` [G, C] non-negative (a fit gives ``mu[:, None] * L``); ``U`` [N, D] and ``V`` [G, D], 0 <= D <= 8, or both None (a fit gives
         ``[psi | x]`` and ``[W | beta]``); ``const=False`` leaves out ``lgamma(s + 1) - sum(lgamma(y + 1))``.  A positive count against ``E = 0`` gives
         exactly ``-inf``, a zero count against it adds nothing; no NaN.  Changes nothing in the engine; two calls agree bit for bit."""
-        E = np.asarray(E, dtype=np.float64)
-        if E.shape != (self.G, self.C):
-            raise ValueError(f"clone_loglik: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
-        if (U is None) != (V is None):
-            raise ValueError("clone_loglik: U and V go together (both, or neither)")
-        D = 0
-        Um = Vm = None
-        if U is not None:
-            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
-                raise ValueError(f"clone_loglik: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
-            D = int(U.shape[1])
-            if D > 0:
-                Um = np.require(U, requirements=[self._order, "A"])
-                Vm = np.require(V, requirements=[self._order, "A"])
-        Em = np.require(E, requirements=[self._order, "A"])
-        ll = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self._fn("clone_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(ll)))
+        Em, Um, Vm, D = self._ll_operands("clone_loglik", E, U, V)
+        ll = self._zeros(self.N, self.C)
+        self._ck(self._fn("clone_loglik")(self.h, _ptr(Em), _ptr(Um), _ptr(Vm), D, int(bool(const)), _ptr(ll)))
         return ll
 
     def clone_pair_loglik(self, E, U=None, V=None, weights=(0.5,), const=True, cells=None, want_ll=True):
@@ -717,32 +770,15 @@ class HipEngine:
         values do not depend on the range.  Returns ``{"ll": [n, C] (clone_loglik's rows, bit for bit; None unless want_ll), "pair_ll": [n, M, W],
         "pairs": [M, 2]}`` with the pairs in lexicographic order.  A positive count where both clones have ``E = 0`` gives exactly ``-inf``; no NaN.
         Changes nothing in the engine; two calls agree bit for bit."""
-        E = np.asarray(E, dtype=np.float64)
-        if E.shape != (self.G, self.C):
-            raise ValueError(f"clone_pair_loglik: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
-        if (U is None) != (V is None):
-            raise ValueError("clone_pair_loglik: U and V go together (both, or neither)")
-        D = 0
-        Um = Vm = None
-        if U is not None:
-            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
-                raise ValueError(f"clone_pair_loglik: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
-            D = int(U.shape[1])
-            if D > 0:
-                Um = np.require(U, requirements=[self._order, "A"])
-                Vm = np.require(V, requirements=[self._order, "A"])
-        lo, hi = (0, self.N) if cells is None else (int(cells[0]), int(cells[1]))
-        n = max(hi - lo, 0)
+        Em, Um, Vm, D = self._ll_operands("clone_pair_loglik", E, U, V)
+        lo, hi, n = self._cell_range(cells)
         w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
         Wn, Cn = int(w.shape[0]), self.C
-        pairs = np.array([(a, b) for a in range(Cn) for b in range(a + 1, Cn)], dtype=np.int64).reshape(-1, 2)
+        pairs = hostprep.pair_list(Cn)
         M = pairs.shape[0]
-        Em = np.require(E, requirements=[self._order, "A"])
-        ll = np.zeros((n, Cn), dtype=np.float64, order=self._order) if want_ll else None
-        pll = np.zeros((n, M * min(Wn, 8)), dtype=np.float64, order=self._order)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self._fn("clone_pair_loglik")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(w), Wn, lo, hi - lo, ptr(ll), ptr(pll)))
+        ll = self._zeros(n, Cn) if want_ll else None
+        pll = self._zeros(n, M * min(Wn, 8))
+        self._ck(self._fn("clone_pair_loglik")(self.h, _ptr(Em), _ptr(Um), _ptr(Vm), D, int(bool(const)), _ptr(w), Wn, lo, hi - lo, _ptr(ll), _ptr(pll)))
         return {"ll": ll, "pair_ll": np.ascontiguousarray(pll).reshape(n, M, Wn), "pairs": pairs}
 
     def clone_loglik_dm(self, E, U=None, V=None, concentration=(100.,), const=True, cells=None, want_ll=True):
@@ -753,30 +789,13 @@ class HipEngine:
         cells); ``cells`` = ``(lo, hi)`` restricts the call to that range of cells (None: all) -- a cell's values do not depend on the range.  Returns
         ``{"ll": [n, C] (clone_loglik's rows, bit for bit; None unless want_ll), "dm_ll": [n, C, n_conc]}``.  A positive count against ``E = 0`` gives
         exactly ``-inf``; no NaN.  Changes nothing in the engine; two calls agree bit for bit."""
-        E = np.asarray(E, dtype=np.float64)
-        if E.shape != (self.G, self.C):
-            raise ValueError(f"clone_loglik_dm: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
-        if (U is None) != (V is None):
-            raise ValueError("clone_loglik_dm: U and V go together (both, or neither)")
-        D = 0
-        Um = Vm = None
-        if U is not None:
-            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
-                raise ValueError(f"clone_loglik_dm: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
-            D = int(U.shape[1])
-            if D > 0:
-                Um = np.require(U, requirements=[self._order, "A"])
-                Vm = np.require(V, requirements=[self._order, "A"])
-        lo, hi = (0, self.N) if cells is None else (int(cells[0]), int(cells[1]))
-        n = max(hi - lo, 0)
+        Em, Um, Vm, D = self._ll_operands("clone_loglik_dm", E, U, V)
+        lo, hi, n = self._cell_range(cells)
         phi = np.ascontiguousarray(np.asarray(concentration, dtype=np.float64).reshape(-1))
         Kn, Cn = int(phi.shape[0]), self.C
-        Em = np.require(E, requirements=[self._order, "A"])
-        ll = np.zeros((n, Cn), dtype=np.float64, order=self._order) if want_ll else None
-        dm = np.zeros((n, Cn * min(Kn, 16)), dtype=np.float64, order=self._order)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self._fn("clone_loglik_dm")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(phi), Kn, lo, hi - lo, ptr(ll), ptr(dm)))
+        ll = self._zeros(n, Cn) if want_ll else None
+        dm = self._zeros(n, Cn * min(Kn, 16))
+        self._ck(self._fn("clone_loglik_dm")(self.h, _ptr(Em), _ptr(Um), _ptr(Vm), D, int(bool(const)), _ptr(phi), Kn, lo, hi - lo, _ptr(ll), _ptr(dm)))
         return {"ll": ll, "dm_ll": np.ascontiguousarray(dm).reshape(n, Cn, Kn)}
 
     def clone_loglik_by_block(self, E, U, V, block_of_gene, n_blocks, const=True, cells=None):
@@ -787,35 +806,17 @@ class HipEngine:
         Returns ``{"A": [n, B, C], "logZ": [n, B, C], "s": [n, B], "lg": [n, B] (None unless const)}``: per block ``sum xlogy(y, E) + sum y eta``,
         ``log sum E exp(eta)``, ``sum y`` and ``sum lgamma(y + 1)``.  A positive count against ``E = 0`` gives ``A = -inf`` exactly; an empty block gives
         ``A = s = lg = 0`` and ``logZ = -inf``; no NaN.  Changes nothing in the engine; two calls agree bit for bit."""
-        E = np.asarray(E, dtype=np.float64)
-        if E.shape != (self.G, self.C):
-            raise ValueError(f"clone_loglik_by_block: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
-        if (U is None) != (V is None):
-            raise ValueError("clone_loglik_by_block: U and V go together (both, or neither)")
-        D = 0
-        Um = Vm = None
-        if U is not None:
-            U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-            if U.ndim != 2 or V.ndim != 2 or U.shape[0] != self.N or V.shape[0] != self.G or U.shape[1] != V.shape[1]:
-                raise ValueError(f"clone_loglik_by_block: U is {U.shape} and V is {V.shape}; expected ({self.N}, D) and ({self.G}, D)")
-            D = int(U.shape[1])
-            if D > 0:
-                Um = np.require(U, requirements=[self._order, "A"])
-                Vm = np.require(V, requirements=[self._order, "A"])
+        Em, Um, Vm, D = self._ll_operands("clone_loglik_by_block", E, U, V)
         bg = np.asarray(block_of_gene)
         if bg.shape != (self.G,) or bg.dtype.kind not in "iu":
             raise ValueError(f"clone_loglik_by_block: block_of_gene must be {self.G} integers, got {bg.dtype} {bg.shape}")
         bg = np.ascontiguousarray(np.clip(bg, -1, 2 ** 31 - 1).astype(np.int32))   # (a label out of range stays out of range: the library names it)
         B = int(n_blocks)
-        lo, hi = (0, self.N) if cells is None else (int(cells[0]), int(cells[1]))
-        n, Bn, Cn = max(hi - lo, 0), max(B, 0), self.C
-        Em = np.require(E, requirements=[self._order, "A"])
-        A = np.zeros((n, Bn * Cn), dtype=np.float64, order=self._order)
-        logZ = np.zeros((n, Bn * Cn), dtype=np.float64, order=self._order)
-        s = np.zeros((n, Bn), dtype=np.float64, order=self._order)
-        lg = np.zeros((n, Bn), dtype=np.float64, order=self._order) if const else None
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        self._ck(self._fn("clone_loglik_by_block")(self.h, ptr(Em), ptr(Um), ptr(Vm), D, int(bool(const)), ptr(bg), B, lo, hi - lo, ptr(A), ptr(logZ), ptr(s), ptr(lg)))
+        lo, hi, n = self._cell_range(cells)
+        Bn, Cn = max(B, 0), self.C
+        A, logZ, s = self._zeros(n, Bn * Cn), self._zeros(n, Bn * Cn), self._zeros(n, Bn)
+        lg = self._zeros(n, Bn) if const else None
+        self._ck(self._fn("clone_loglik_by_block")(self.h, _ptr(Em), _ptr(Um), _ptr(Vm), D, int(bool(const)), _ptr(bg), B, lo, hi - lo, _ptr(A), _ptr(logZ), _ptr(s), _ptr(lg)))
         return {"A": np.ascontiguousarray(A).reshape(n, Bn, Cn), "logZ": np.ascontiguousarray(logZ).reshape(n, Bn, Cn), "s": np.ascontiguousarray(s),
                 "lg": None if lg is None else np.ascontiguousarray(lg)}
 
@@ -827,50 +828,18 @@ class HipEngine:
         matrix, then two launches per round that do not read it.  Returns a dict: ``psi`` [N, K], ``ll`` and ``clone_probs`` [N, C], ``objective`` [N],
         ``rounds`` [N] int32, ``converged`` [N] bool.  ``poll_every``: rounds between two host reads of the frozen flags (None = 4); no result depends
         on it.  Changes nothing in the engine; two calls agree bit for bit."""
-        E = np.asarray(E, dtype=np.float64)
-        if E.shape != (self.G, self.C):
-            raise ValueError(f"project_cells: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
-        K = int(K)
-        Vm = Xm = lpm = psm = None
-        D = 0
-        if V is not None:
-            V = np.asarray(V, dtype=np.float64)
-            if V.ndim != 2 or V.shape[0] != self.G:
-                raise ValueError(f"project_cells: V is {V.shape}; expected ({self.G}, K + P)")
-            D = int(V.shape[1])
-        P = D - K
-        if P < 0:
-            raise ValueError(f"project_cells: V has {D} columns but K = {K}")
-        if D > 0:
-            Vm = np.require(V, requirements=[self._order, "A"])
-        if X is not None or P > 0:
-            X = np.zeros((self.N, 0)) if X is None else np.asarray(X, dtype=np.float64)
-            if X.shape != (self.N, P):
-                raise ValueError(f"project_cells: X is {X.shape}; V has K + P = {D} columns with K = {K}, so X must be ({self.N}, {P})")
-            Xm = np.require(X, requirements=[self._order, "A"]) if P > 0 else None
+        Em, Vm, K, P, Xm, psm, flags = self._latent_operands("project_cells", E, V, K, X, psi_start, const, poll_every)
+        lpm = None
         if log_prior is not None:
             log_prior = np.asarray(log_prior, dtype=np.float64)
             if log_prior.shape != (self.N, self.C):
                 raise ValueError(f"project_cells: log_prior is {log_prior.shape}; expected ({self.N}, {self.C})")
-            lpm = np.require(log_prior, requirements=[self._order, "A"])
-        if psi_start is not None and K > 0:
-            psi_start = np.asarray(psi_start, dtype=np.float64)
-            if psi_start.shape != (self.N, K):
-                raise ValueError(f"project_cells: psi_start is {psi_start.shape}; expected ({self.N}, {K})")
-            psm = np.require(psi_start, requirements=[self._order, "A"])
-        if poll_every is not None and not 1 <= int(poll_every) <= 255:
-            raise ValueError("project_cells: poll_every must be in [1, 255]")
-        Em = np.require(E, requirements=[self._order, "A"])
-        psi = np.zeros((self.N, max(K, 0)), dtype=np.float64, order=self._order)
-        ll = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
-        pr = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
-        obj = np.zeros(self.N, dtype=np.float64)
+            lpm = self._in_order(log_prior)
+        psi, ll, pr, obj = self._zeros(self.N, max(K, 0)), self._zeros(self.N, self.C), self._zeros(self.N, self.C), self._zeros(self.N)
         rounds = np.zeros(self.N, dtype=np.int32)
         conv = np.zeros(self.N, dtype=np.uint8)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        flags = int(bool(const)) | ((int(poll_every) if poll_every is not None else 0) << 8)
-        self._ck(self._fn("project_cells")(self.h, ptr(Em), ptr(Vm), K, P, ptr(Xm), ptr(lpm), ptr(psm), flags, int(max_iter), float(tol), float(max_step),
-                                           ptr(psi) if K > 0 else None, ptr(ll), ptr(pr), ptr(obj), ptr(rounds), ptr(conv)))
+        self._ck(self._fn("project_cells")(self.h, _ptr(Em), _ptr(Vm), K, P, _ptr(Xm), _ptr(lpm), _ptr(psm), flags, int(max_iter), float(tol), float(max_step),
+                                           _ptr(psi) if K > 0 else None, _ptr(ll), _ptr(pr), _ptr(obj), _ptr(rounds), _ptr(conv)))
         return {"psi": psi, "ll": ll, "clone_probs": pr, "objective": obj, "rounds": rounds, "converged": conv.astype(bool)}
 
     def clone_evidence(self, E, V=None, K=0, X=None, psi_start=None, nodes=None, weights=None, const=True, max_iter=50, tol=1e-9, max_step=1.0,
@@ -884,32 +853,7 @@ class HipEngine:
         (the precision's entries k <= l), ``rounds`` [N, C] int32, ``converged`` [N, C] bool -- a pair with ``converged`` False holds a value that is
         deterministic but not to be trusted.  ``poll_every``: rounds between two host reads of the pairs' states (None = 4); no result depends on it.
         Changes nothing in the engine; two calls agree bit for bit."""
-        E = np.asarray(E, dtype=np.float64)
-        if E.shape != (self.G, self.C):
-            raise ValueError(f"clone_evidence: E is {E.shape} but the engine holds {self.G} genes and {self.C} clones")
-        K = int(K)
-        Vm = Xm = psm = None
-        D = 0
-        if V is not None:
-            V = np.asarray(V, dtype=np.float64)
-            if V.ndim != 2 or V.shape[0] != self.G:
-                raise ValueError(f"clone_evidence: V is {V.shape}; expected ({self.G}, K + P)")
-            D = int(V.shape[1])
-        P = D - K
-        if P < 0:
-            raise ValueError(f"clone_evidence: V has {D} columns but K = {K}")
-        if D > 0:
-            Vm = np.require(V, requirements=[self._order, "A"])
-        if X is not None or P > 0:
-            X = np.zeros((self.N, 0)) if X is None else np.asarray(X, dtype=np.float64)
-            if X.shape != (self.N, P):
-                raise ValueError(f"clone_evidence: X is {X.shape}; V has K + P = {D} columns with K = {K}, so X must be ({self.N}, {P})")
-            Xm = np.require(X, requirements=[self._order, "A"]) if P > 0 else None
-        if psi_start is not None and K > 0:
-            psi_start = np.asarray(psi_start, dtype=np.float64)
-            if psi_start.shape != (self.N, K):
-                raise ValueError(f"clone_evidence: psi_start is {psi_start.shape}; expected ({self.N}, {K})")
-            psm = np.require(psi_start, requirements=[self._order, "A"])
+        Em, Vm, K, P, Xm, psm, flags = self._latent_operands("clone_evidence", E, V, K, X, psi_start, const, poll_every)
         if (nodes is None) != (weights is None):
             raise ValueError("clone_evidence: nodes and weights go together (both, or neither)")
         if nodes is None:
@@ -919,21 +863,13 @@ class HipEngine:
         Q = int(wts.shape[0])
         if nd.size != Q * max(K, 0):
             raise ValueError(f"clone_evidence: nodes is {nd.shape}; {Q} weights and K = {K} need ({Q}, {K})")
-        if poll_every is not None and not 1 <= int(poll_every) <= 255:
-            raise ValueError("clone_evidence: poll_every must be in [1, 255]")
         Kp = max(K, 0)
         NH = Kp * (Kp + 1) // 2
-        Em = np.require(E, requirements=[self._order, "A"])
-        ev = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
-        lap = np.zeros((self.N, self.C), dtype=np.float64, order=self._order)
-        mode = np.zeros((self.N, self.C * Kp), dtype=np.float64, order=self._order)
-        prec = np.zeros((self.N, self.C * NH), dtype=np.float64, order=self._order)
+        ev, lap, mode, prec = self._zeros(self.N, self.C), self._zeros(self.N, self.C), self._zeros(self.N, self.C * Kp), self._zeros(self.N, self.C * NH)
         rounds = np.zeros((self.N, self.C), dtype=np.int32, order=self._order)
         conv = np.zeros((self.N, self.C), dtype=np.uint8, order=self._order)
-        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        flags = int(bool(const)) | ((int(poll_every) if poll_every is not None else 0) << 8)
-        self._ck(self._fn("clone_evidence")(self.h, ptr(Em), ptr(Vm), K, P, ptr(Xm), ptr(psm), flags, Q, ptr(nd), ptr(wts), int(max_iter), float(tol),
-                                            float(max_step), ptr(ev), ptr(lap), ptr(mode), ptr(prec), ptr(rounds), ptr(conv)))
+        Em, Vm, Xm, psm, nd_p, wts_p, *outs = (_ptr(a, empty_null=True) for a in (Em, Vm, Xm, psm, nd, wts, ev, lap, mode, prec, rounds, conv))   # (K = 0: no nodes, modes)
+        self._ck(self._fn("clone_evidence")(self.h, Em, Vm, K, P, Xm, psm, flags, Q, nd_p, wts_p, int(max_iter), float(tol), float(max_step), *outs))
         return {"evidence": np.ascontiguousarray(ev), "laplace": np.ascontiguousarray(lap), "psi_mode": np.ascontiguousarray(mode).reshape(self.N, self.C, Kp),
                 "psi_prec": np.ascontiguousarray(prec).reshape(self.N, self.C, NH), "rounds": np.ascontiguousarray(rounds),
                 "converged": np.ascontiguousarray(conv).astype(bool)}
@@ -975,8 +911,7 @@ class HipEngine:
         if self.K > 0:
             p0 = np.require(np.asarray(psi0, dtype=np.float64).reshape(self.N, self.K), requirements=[self._order, "A"])
         l0 = None if loc0 is None else np.ascontiguousarray(np.asarray(loc0, dtype=np.float64).reshape(self.G))
-        self._ck(self._fn("reinit")(self.h, None if p0 is None else p0.ctypes.data_as(C.c_void_p),
-                                    None if l0 is None else l0.ctypes.data_as(C.c_void_p)))
+        self._ck(self._fn("reinit")(self.h, _ptr(p0), _ptr(l0)))
 
     def get_params(self):
         """R/inference-tflow.R:424-434."""
@@ -1154,10 +1089,9 @@ def simulate_counts(E, V, U, clone, total, seed, draw=0, cell_offset=0, device=0
         out = np.zeros((N, G), dtype=np.int32)
     elif out.dtype != np.int32 or out.shape != (N, G) or not out.flags.c_contiguous:
         raise ValueError(f"simulate_counts: out must be a C-contiguous int32 array of shape ({N}, {G})")
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     err = C.create_string_buffer(256)
-    rc = lib.ca_simulate_counts(N, G, Cn, D, ptr(E), ptr(V) if D > 0 else None, ptr(U) if D > 0 else None, ptr(clone), ptr(total),
-                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, int(cell_offset), int(device), ptr(out), err)
+    rc = lib.ca_simulate_counts(N, G, Cn, D, _ptr(E), _ptr(V) if D > 0 else None, _ptr(U) if D > 0 else None, _ptr(clone), _ptr(total),
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, int(cell_offset), int(device), _ptr(out), err)
     if rc != CA_OK:
         raise EngineError(rc, err.value.decode() or "ca_simulate_counts")
     return out
@@ -1205,10 +1139,9 @@ def predictive_stats(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=
             raise ValueError(f"predictive_stats: out[0] must be a C-contiguous float64 array of shape ({N}, {R})")
         if T is not None and (T.dtype != np.int64 or T.shape != (R, G, Cn) or not T.flags.c_contiguous):
             raise ValueError(f"predictive_stats: out[1] must be None or a C-contiguous int64 array of shape ({R}, {G}, {Cn})")
-    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
     err = C.create_string_buffer(256)
-    rc = lib.ca_predictive_stats(N, G, Cn, D, ptr(E), ptr(V) if D > 0 else None, ptr(U) if D > 0 else None, ptr(clone), ptr(total),
-                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0) & 0xFFFFFFFFFFFFFFFF, n_rep, int(cell_offset), int(device), ptr(ll), ptr(T), err)
+    rc = lib.ca_predictive_stats(N, G, Cn, D, _ptr(E), _ptr(V) if D > 0 else None, _ptr(U) if D > 0 else None, _ptr(clone), _ptr(total),
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0) & 0xFFFFFFFFFFFFFFFF, n_rep, int(cell_offset), int(device), _ptr(ll), _ptr(T), err)
     if rc != CA_OK:
         raise EngineError(rc, err.value.decode() or "ca_predictive_stats")
     return ll, T

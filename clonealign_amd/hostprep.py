@@ -32,6 +32,11 @@ def saturate(x, threshold=4):
     return x
 
 
+def pair_list(C):
+    """The unordered clone pairs ``a < b`` in lexicographic order, [M, 2] int64: the order of the pair axis of every pair call."""
+    return np.array([(a, b) for a in range(C) for b in range(a + 1, C)], dtype=np.int64).reshape(-1, 2)
+
+
 def gene_filter(Y, L, gene_filter_threshold=0):
     """R/inference-tflow.R:117-124: drop genes with ``colSums(Y) <= threshold``.
 

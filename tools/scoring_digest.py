@@ -12,7 +12,17 @@ takes that many clones), with_const, layout, cell range (all; lo = 63, 2 cells),
 16 | 17 and at the last gene; g % 3; a labelling with an empty block), W = 1 and 8 pair weights, K = 1 and 16 concentrations with one above 2^100, K = 1 and 2
 free factors, P = 0 and 1 covariates, max_iter = 3, Q = 1 and 5 nodes, the evidence at K = 0, and a two-rank group where two devices are visible.  E has a
 clone with E = 0 at a gene some cell has counts in and one with E = 0 at a gene no cell has counts in; one cell has no counts at all.
-The first line is the library's build id; a line "skipped ..." says what this machine or this engine could not run."""
+The first line is the library's build id; a line "skipped ..." says what this machine or this engine could not run.
+
+Three layers, all by default or the ones named on the command line:
+   engine   the six HipEngine methods (the grid above), then the refusals the methods make themselves;
+   api      the public functions of clonealign_amd.api on throwaway engines (and once on the caller's engine);
+   host     the same functions on an engine object that has only N, G and close: the float64 host forms, no GPU needed.
+The api and host layers run clone_loglik, assign_cells, clone_loglik_by_block, assignment_support, clone_pair_loglik, detect_doublets, clone_loglik_dm,
+estimate_concentration, assign_cells_dm (a value and "auto"), project_cells, clone_evidence, assign_cells_marginal and heldout_evidence (two fits with
+different K) on a base case (257 x 130, C = 7, K = 1, P = 1, alpha, copy numbers above the saturation threshold, L = 0 against a positive count and against
+none) and vary one axis at a time; then a fixed list of inputs with exactly one fault each: the call, the exception type and the message.  Two trees whose
+Python computes the same print the same lines."""
 import hashlib
 import os
 import sys
@@ -20,6 +30,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from clonealign_amd import api  # noqa: E402
 from clonealign_amd import engine as _engine  # noqa: E402
 from clonealign_amd.api import gauss_hermite_rule  # noqa: E402
 from clonealign_amd.engine import HipEngine, HipGroupEngine  # noqa: E402
@@ -126,7 +137,237 @@ def run_case(name, N, G, C, D, storage="u8", const=True, layout="row", cells=Non
         eng.close()
 
 
+def digest(v):
+    """One token for any returned value: arrays by their bytes, label arrays and lists by their joined strings, scalars by their repr."""
+    if isinstance(v, np.ndarray) and v.dtype == object:
+        return f"obj{list(v.shape)} " + hashlib.sha256("\x1f".join(str(e) for e in v.reshape(-1)).encode()).hexdigest()
+    if isinstance(v, np.ndarray):
+        return sha(v) + (" F" if v.ndim > 1 and v.flags.f_contiguous and not v.flags.c_contiguous else "")
+    if isinstance(v, (list, tuple)):
+        return f"list[{len(v)}] " + hashlib.sha256("\x1f".join(str(e) for e in v).encode()).hexdigest()
+    if isinstance(v, (float, np.floating)):
+        return "float " + float(v).hex()
+    return f"{type(v).__name__} {v!r}"
+
+
+def emit_any(case, call, res):
+    if isinstance(res, dict):
+        for k in sorted(res, key=str):
+            emit_any(case, f"{call}.{k}", res[k])
+    else:
+        print(f"{case} | {call} | {digest(res)}")
+
+
+def refusal(case, call, thunk):
+    try:
+        thunk()
+        print(f"{case} | {call} | no refusal")
+    except Exception as e:  # noqa: BLE001
+        print(f"{case} | {call} | {type(e).__name__}: {e}")
+
+
+class HostOnly:
+    """An engine object without a scoring method: every call takes its host form."""
+
+    def __init__(self, N, G):
+        self.N, self.G = N, G
+
+    def close(self):
+        pass
+
+
+def model(N=257, G=130, C=7, K=1, P=1, alpha=True, names=False, seed=1):
+    """(fit, Y, L, x, extra) of an api case: problem()'s counts; L with values above the saturation threshold, 0 against a positive count and against none."""
+    Y, L, _E, U, V, lp = problem(N, G, C, 2, "u8", seed)
+    rng = np.random.default_rng(seed + 100)
+    L.reshape(-1)[rng.choice(G * C, size=max(1, G * C // 10), replace=False)] = 8.0
+    if G >= 17 and C >= 2:
+        L[3, 0] = 0.0                                                # (problem() put a count at gene 3 and none at gene 9)
+        L[9, 1] = 0.0
+    ml = {"mu": rng.lognormal(-1.4, 1.0, G), "clone_probs": np.full((N, C), 1.0 / C)}
+    if K:
+        ml["W"], ml["psi"] = V[:, :K].copy(), U[:, :K].copy()
+    if P:
+        ml["beta"] = V[:, 4:4 + P].copy()
+    if alpha:
+        ml["alpha"] = rng.dirichlet(np.ones(C) * 3.0)
+    fit = {"ml_params": ml}
+    if names:
+        fit["clone_names"] = [f"k{i}" for i in range(C)]
+    return fit, Y, L, (U[:, 4:4 + P].copy() if P else None), lp
+
+
+def other_k(fit):
+    """The same fit with another number of factors: K = 0 for a fit with factors, K = 1 for one without."""
+    ml = dict(fit["ml_params"])
+    if ml.pop("W", None) is None:
+        G, N = ml["mu"].shape[0], ml["clone_probs"].shape[0]
+        rng = np.random.default_rng(9)
+        ml["W"], ml["psi"] = rng.normal(size=(G, 1)) * 0.3, rng.normal(size=(N, 1)) * 0.5
+    else:
+        ml.pop("psi", None)
+    return dict(fit, ml_params=ml)
+
+
+def calls(fit, Y, L, eng, x=None, psi=None, extra=None, const=True, saturate=True, cells=None, chunk_cells=None, fit2=None):
+    """(name, thunk) of every public scoring function on one input."""
+    G = L.shape[0]
+    blocks = np.array([f"chr{g // 50}" for g in range(G)], dtype=object)
+    kw = dict(x=x, saturate=saturate, const=const, engine=eng)
+    kp = dict(kw, psi=psi)
+    exc = extra if cells is None or extra is None else extra[cells[0]:cells[1]]
+    fits = {"a": fit, "b": other_k(fit) if fit2 is None else fit2}
+    return [
+        ("clone_loglik", lambda: api.clone_loglik(fit, Y, L, **kp)),
+        ("assign_cells", lambda: api.assign_cells(fit, Y, L, extra_loglik=extra, **kp)),
+        ("clone_loglik_by_block", lambda: api.clone_loglik_by_block(fit, Y, L, blocks, cells=cells, **kp)),
+        ("assignment_support", lambda: api.assignment_support(fit, Y, L, blocks, extra_loglik=exc, cells=cells, **kp)),
+        ("clone_pair_loglik", lambda: api.clone_pair_loglik(fit, Y, L, weights=(0.3, 0.5), **kp)),
+        ("detect_doublets", lambda: api.detect_doublets(fit, Y, L, weights=(0.3, 0.5), extra_loglik=extra, chunk_cells=chunk_cells, **kp)),
+        ("clone_loglik_dm", lambda: api.clone_loglik_dm(fit, Y, L, concentration=(5.0, 50.0, 500.0), **kp)),
+        ("estimate_concentration", lambda: api.estimate_concentration(fit, Y, L, refine=1, extra_loglik=extra, **kp)),
+        ("assign_cells_dm[40]", lambda: api.assign_cells_dm(fit, Y, L, 40.0, extra_loglik=extra, **kp)),
+        ("assign_cells_dm[auto]", lambda: api.assign_cells_dm(fit, Y, L, "auto", refine=1, extra_loglik=extra, **kp)),
+        ("project_cells", lambda: api.project_cells(fit, Y, L, extra_loglik=extra, max_iter=5, **kw)),
+        ("clone_evidence", lambda: api.clone_evidence(fit, Y, L, max_iter=8, **kw)),
+        ("assign_cells_marginal", lambda: api.assign_cells_marginal(fit, Y, L, extra_loglik=extra, max_iter=8, **kw)),
+        ("heldout_evidence", lambda: api.heldout_evidence(fits, Y, L, extra_loglik=extra, max_iter=8, **kw)),
+    ]
+
+
+def api_case(layer, name, mk, only=None, **kw):
+    fit, Y, L, x, _lp = mk
+    eng = HostOnly(*Y.shape) if layer == "host" else None
+    for call, thunk in calls(fit, Y, L, eng, x=x, **kw):
+        if only is None or call in only:
+            emit_any(f"{layer} {name}", call, thunk())
+
+
+RANGE_CALLS = ("clone_loglik_by_block", "assignment_support")
+PSI_CALLS = ("clone_loglik", "assign_cells", "clone_loglik_by_block", "assignment_support", "clone_pair_loglik", "detect_doublets", "clone_loglik_dm",
+             "estimate_concentration", "assign_cells_dm[40]", "assign_cells_dm[auto]")
+EXTRA_CALLS = ("assign_cells", "assignment_support", "detect_doublets", "estimate_concentration", "assign_cells_dm[40]", "assign_cells_dm[auto]",
+               "project_cells", "assign_cells_marginal", "heldout_evidence")
+
+
+def run_api(layer):
+    """The public functions: a base case, then one axis at a time."""
+    import pandas as pd
+    import scipy.sparse as sps
+    base = model()
+    fit, Y, L, x, lp = base
+    api_case(layer, "base 257x130 C7 K1 P1", base)
+    api_case(layer, "K0", model(K=0))
+    api_case(layer, "65x17 K2 P0", model(N=65, G=17, K=2, P=0))
+    api_case(layer, "no alpha", model(alpha=False))
+    api_case(layer, "extra_loglik", base, only=EXTRA_CALLS, extra=lp)
+    api_case(layer, "no alpha extra_loglik", model(alpha=False), only=EXTRA_CALLS, extra=lp)
+    api_case(layer, "const False", base, const=False)
+    api_case(layer, "saturate False", base, saturate=False)
+    api_case(layer, "psi fit", base, only=PSI_CALLS, psi="fit")
+    api_case(layer, "psi array", base, only=PSI_CALLS, psi=fit["ml_params"]["psi"] * 0.5)
+    api_case(layer, "cells (63, 65)", base, only=RANGE_CALLS, cells=(63, 65), extra=lp)
+    api_case(layer, "chunk_cells 100", base, only=("detect_doublets",), chunk_cells=100, extra=lp)
+    api_case(layer, "Y csr", (fit, sps.csr_matrix(Y), L, x, lp))
+    api_case(layer, "Y int64", (fit, Y.astype(np.int64), L, x, lp))
+    frame = pd.DataFrame(L, columns=[f"col{i}" for i in range(L.shape[1])])
+    api_case(layer, "L DataFrame", (fit, Y, frame, x, lp))
+    api_case(layer, "L DataFrame clone_names", (dict(fit, clone_names=[f"k{i}" for i in range(L.shape[1])]), Y, frame, x, lp))
+    if layer == "api":                                               # the caller's engine: used as it is, for every call
+        from clonealign_amd import hostprep
+        eng = HipEngine(Y, hostprep.saturate(L, 6), np.zeros((Y.shape[0], 0)), None, 0)
+        try:
+            for call, thunk in calls(fit, Y, L, eng, x=x, extra=lp):
+                emit_any("api caller's engine", call, thunk())
+        finally:
+            eng.close()
+    api_refusals(layer, base)
+
+
+def api_refusals(layer, base):
+    """Inputs with exactly one fault each, through every function the fault can reach."""
+    fit, Y, L, x, lp = base
+    N, G = Y.shape
+    eng = HostOnly(N, G) if layer == "host" else None
+    ml = fit["ml_params"]
+
+    def with_ml(**kv):
+        return dict(fit, ml_params={k: v for k, v in dict(ml, **kv).items() if v is not None})
+
+    def sweep(label, f=fit, Yv=Y, Lv=L, only=None, **kw):
+        kw.setdefault("x", x)
+        for call, thunk in calls(f, Yv, Lv, kw.pop("eng", eng), **kw):
+            if only is None or call in only:
+                refusal(f"{layer} refusal {label}", call, thunk)
+
+    sweep("L with one gene less", Lv=L[:-1])
+    sweep("mu of the wrong length", f=with_ml(mu=ml["mu"][:-1]), fit2=fit)
+    sweep("x missing", x=None)
+    sweep("x without beta", f=with_ml(beta=None), fit2=with_ml(beta=None, W=None, psi=None))
+    sweep("psi with the wrong rows", only=PSI_CALLS, psi=ml["psi"][:-1])
+    sweep("psi other", only=PSI_CALLS, psi="other")
+    sweep("extra_loglik of the wrong shape", only=EXTRA_CALLS, extra=lp[:, :-1])
+    refusal(f"{layer} refusal a bad weight", "clone_pair_loglik", lambda: api.clone_pair_loglik(fit, Y, L, weights=(0.3, 1.0), x=x, engine=eng))
+    refusal(f"{layer} refusal a bad weight", "detect_doublets", lambda: api.detect_doublets(fit, Y, L, weights=(0.3, 1.0), x=x, engine=eng))
+    refusal(f"{layer} refusal 17 concentrations", "clone_loglik_dm",
+            lambda: api.clone_loglik_dm(fit, Y, L, concentration=np.geomspace(1.0, 1e4, 17), x=x, engine=eng))
+    one = with_ml(alpha=np.ones(1))
+    sweep("C = 1", f=one, Lv=L[:, :1], only=("assignment_support", "clone_pair_loglik", "detect_doublets"))
+    if layer == "api":
+        rng = np.random.default_rng(3)
+        k3 = with_ml(W=rng.normal(size=(G, 3)) * 0.3, psi=rng.normal(size=(N, 3)))
+        sweep("K = 3 on the device", f=k3, only=("project_cells", "clone_evidence", "assign_cells_marginal"))
+        other = HipEngine(Y[:100], L, np.zeros((100, 0)), None, 0)
+        try:
+            sweep("an engine of another shape", eng=other)
+        finally:
+            other.close()
+
+
+def engine_refusals():
+    """What the six methods refuse before the library is called."""
+    N, G, C = 65, 17, 3
+    Y, L, E, U, V, lp = problem(N, G, C, 2, "u8", 1)
+    eng = HipEngine(Y, L, np.zeros((N, 0)), np.zeros(G), 0)
+    bg = np.zeros(G, dtype=np.int32)
+    nd, wt = gauss_hermite_rule(1, 3)
+    ll_calls = [("clone_loglik", lambda E_, U_, V_: eng.clone_loglik(E_, U_, V_)),
+                ("clone_pair_loglik", lambda E_, U_, V_: eng.clone_pair_loglik(E_, U_, V_)),
+                ("clone_loglik_dm", lambda E_, U_, V_: eng.clone_loglik_dm(E_, U_, V_)),
+                ("clone_loglik_by_block", lambda E_, U_, V_: eng.clone_loglik_by_block(E_, U_, V_, bg, 1))]
+    lat_calls = [("project_cells", lambda E_, V_, K, **kw: eng.project_cells(E_, V_, K, **kw)),
+                 ("clone_evidence", lambda E_, V_, K, **kw: eng.clone_evidence(E_, V_, K, **kw))]
+    try:
+        for name, f in ll_calls:
+            refusal("engine refusal E of the wrong shape", name, lambda: f(E[:, :-1], U[:, :2], V[:, :2]))
+            refusal("engine refusal U without V", name, lambda: f(E, U[:, :2], None))
+            refusal("engine refusal U and V disagree", name, lambda: f(E, U[:, :2], V[:, :3]))
+        for name, f in lat_calls:
+            refusal("engine refusal E of the wrong shape", name, lambda: f(E[:, :-1], V[:, :1], 1))
+            refusal("engine refusal V with fewer than K columns", name, lambda: f(E, V[:, :1], 2))
+            refusal("engine refusal X of the wrong shape", name, lambda: f(E, V[:, :2], 1, X=U[:-1, 4:5]))
+            refusal("engine refusal psi_start of the wrong shape", name, lambda: f(E, V[:, :1], 1, psi_start=U[:-1, :1]))
+            refusal("engine refusal poll_every 0", name, lambda: f(E, V[:, :1], 1, poll_every=0))
+        refusal("engine refusal log_prior of the wrong shape", "project_cells", lambda: eng.project_cells(E, V[:, :1], 1, log_prior=lp[:, :-1]))
+        refusal("engine refusal nodes without weights", "clone_evidence", lambda: eng.clone_evidence(E, V[:, :1], 1, nodes=nd))
+        refusal("engine refusal nodes of the wrong size", "clone_evidence", lambda: eng.clone_evidence(E, V[:, :1], 1, nodes=nd[:-1], weights=wt))
+        refusal("engine refusal block_of_gene not integer", "clone_loglik_by_block", lambda: eng.clone_loglik_by_block(E, None, None, bg.astype(np.float64), 1))
+    finally:
+        eng.close()
+
+
 def main():
+    layers = sys.argv[1:] or ["engine", "api", "host"]
+    if "host" in layers:
+        run_api("host")
+    if "api" in layers:
+        print(f"build id {_engine.build_id()}")
+        run_api("api")
+    if "engine" in layers:
+        run_engine()
+
+
+def run_engine():
     print(f"build id {_engine.build_id()}")
     base = dict(N=257, G=130, C=7, D=2)
     run_case("base u8 257x130 C7 D2", **base, full=True)
@@ -148,6 +389,7 @@ def main():
         run_case("group of two ranks range", **base, devices=[0, 1], cells=(63, 200))
     else:
         print(f"group of two ranks | skipped: {torch.cuda.device_count()} device(s) visible")
+    engine_refusals()
 
 
 if __name__ == "__main__":
