@@ -1494,6 +1494,45 @@ def heldout_evidence(fits, Y, L, *, x=None, extra_loglik=None, n_nodes=None, sat
     return res
 
 
+def _model_inputs_host(E, V, U, clone, total, what="simulate_counts"):
+    """The arguments of the handle-free model calls as float64 / int64 arrays, with ``ca_simulate_counts``'s refusals about them as ValueError (``what``
+    names the call).  Returns ``(E, V, U, clone, total, N, G, C, D)``."""
+    E = np.asarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"{what}: E is {E.shape}; expected (genes, clones)")
+    G, C = E.shape
+    clone = np.asarray(clone, dtype=np.int64).reshape(-1)
+    N = clone.shape[0]
+    total = np.array(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
+    if (U is None) != (V is None):
+        raise ValueError(f"{what}: U and V go together (both, or neither)")
+    D = 0
+    if U is not None:
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"{what}: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = U.shape[1]
+    if D > 8:
+        raise ValueError(f"{what}: D = {D} is outside [0, 8]")
+    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
+    if wrong.size:
+        raise ValueError(f"{what}: E has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
+    for name, M, row in (("V", V, "gene"), ("U", U, "cell")):
+        if D > 0 and not np.isfinite(M).all():
+            r, d = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"{what}: {name} has a non-finite entry ({row} {r}, factor {d})")
+    wrong = np.flatnonzero((clone < 0) | (clone >= C))
+    if wrong.size:
+        raise ValueError(f"{what}: clone[{wrong[0]}] = {clone[wrong[0]]} is outside [0, {C})")
+    wrong = np.flatnonzero((total < 0) | (total > 2 ** 31 - 1))
+    if wrong.size:
+        raise ValueError(f"{what}: total[{wrong[0]}] = {total[wrong[0]]} is outside [0, 2^31 - 1]")
+    wrong = np.flatnonzero((total > 0) & ~(E > 0).any(0)[clone])
+    if wrong.size:
+        raise ValueError(f"{what}: total[{wrong[0]}] = {total[wrong[0]]} but E is zero in every gene of the cell's clone {clone[wrong[0]]}")
+    return E, V, U, clone, total, N, G, C, D
+
+
 def _simulate_counts_host(E, V, U, clone, total, seed, draw=0, cell_offset=0, chunk=1 << 20, _cumsum=None):
     """Numpy float64 restatement of ``ca_simulate_counts`` (include/clonealign_hip.h states the sampler): rows ``y_n ~ Multinomial(total[n], p_n)`` with
     ``p_ng ~ E[g, clone[n]] exp(U[n] . V[g])``.  Per cell: ``eta`` summed factor by factor, the shift by its maximum over the genes with ``E > 0``,
@@ -1504,39 +1543,7 @@ def _simulate_counts_host(E, V, U, clone, total, seed, draw=0, cell_offset=0, ch
     boundary next to it -- the only draws where another grouping of the float64 sums, or the last bit of ``exp``, may pick the neighbouring gene.
     ``chunk``: Philox blocks generated at a time.  Refusals are ``ca_simulate_counts``'s, as ValueError.  ``_cumsum``: another cumulative sum (tests)."""
     from .rng import philox4x32
-    E = np.asarray(E, dtype=np.float64)
-    if E.ndim != 2:
-        raise ValueError(f"simulate_counts: E is {E.shape}; expected (genes, clones)")
-    G, C = E.shape
-    clone = np.asarray(clone, dtype=np.int64).reshape(-1)
-    N = clone.shape[0]
-    total = np.array(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
-    if (U is None) != (V is None):
-        raise ValueError("simulate_counts: U and V go together (both, or neither)")
-    D = 0
-    if U is not None:
-        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
-        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
-            raise ValueError(f"simulate_counts: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
-        D = U.shape[1]
-    if D > 8:
-        raise ValueError(f"simulate_counts: D = {D} is outside [0, 8]")
-    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
-    if wrong.size:
-        raise ValueError(f"simulate_counts: E has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
-    for name, M, row in (("V", V, "gene"), ("U", U, "cell")):
-        if D > 0 and not np.isfinite(M).all():
-            r, d = np.argwhere(~np.isfinite(M))[0]
-            raise ValueError(f"simulate_counts: {name} has a non-finite entry ({row} {r}, factor {d})")
-    wrong = np.flatnonzero((clone < 0) | (clone >= C))
-    if wrong.size:
-        raise ValueError(f"simulate_counts: clone[{wrong[0]}] = {clone[wrong[0]]} is outside [0, {C})")
-    wrong = np.flatnonzero((total < 0) | (total > 2 ** 31 - 1))
-    if wrong.size:
-        raise ValueError(f"simulate_counts: total[{wrong[0]}] = {total[wrong[0]]} is outside [0, 2^31 - 1]")
-    wrong = np.flatnonzero((total > 0) & ~(E > 0).any(0)[clone])
-    if wrong.size:
-        raise ValueError(f"simulate_counts: total[{wrong[0]}] = {total[wrong[0]]} but E is zero in every gene of the cell's clone {clone[wrong[0]]}")
+    E, V, U, clone, total, N, G, C, D = _model_inputs_host(E, V, U, clone, total)
     seed, draw, cell_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw), int(cell_offset)
     if cell_offset < 0 or cell_offset + N > 2 ** 48 or not 0 <= draw < 2 ** 48:
         raise ValueError("simulate_counts: cell_offset + N must lie in [0, 2^48] and draw in [0, 2^48)")
@@ -1748,6 +1755,39 @@ def _predictive_stats_host(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_o
     return ll, T
 
 
+_PredictiveInputs = namedtuple("_PredictiveInputs", "Y L Ls E U V idx used rows Uu N G")
+
+
+def _predictive_inputs(fit, Y, L, x, saturate, saturation_threshold):
+    """What ``predictive_check`` and ``predictive_moments`` make of their arguments, with their refusals: the count matrix and the parsed ``L``, the fit's
+    tables (``Ls``: ``L`` saturated as asked; ``E``, ``U``, ``V`` for all cells), the clone index per cell (-1: "unassigned"), the cells used, their observed
+    row sums and their rows of ``U``."""
+    Ya, Lm, cn, N, G = _cells_and_cnv(Y, L)
+    names = _clone_names(fit, cn, Lm.shape[1])
+    if len(names) != Lm.shape[1]:
+        raise ValueError(f"fit has {len(names)} clone names but L has {Lm.shape[1]} columns (clones)")
+    clones = np.asarray(fit["clone"], dtype=object).reshape(-1)
+    if clones.shape[0] != N:
+        raise ValueError(f"fit has {clones.shape[0]} clone labels but Y has {N} rows (cells)")
+    lut = {c: i for i, c in enumerate(names)}
+    unknown = sorted({str(c) for c in clones if c not in lut and c != "unassigned"})
+    if unknown:
+        raise ValueError("clone labels that are no column of L: " + ", ".join(unknown))
+    idx = np.array([lut.get(c, -1) for c in clones], dtype=np.int32)
+    used = np.flatnonzero(idx >= 0)
+    if used.size == 0:
+        raise ValueError("every cell is \"unassigned\": there is nothing to evaluate")
+    ml = fit["ml_params"]
+    has_psi = ml.get("W") is not None and np.asarray(ml["W"]).size > 0
+    Ls, E, U, V = _fit_tables(fit, Lm, N, x, "fit" if has_psi else None, saturate, saturation_threshold)[:4]
+    rows = np.asarray(Ya.sum(axis=1)).reshape(-1)
+    if np.any(rows != np.floor(rows)):
+        raise ValueError("Y must hold whole numbers: a replicate keeps the observed row sums")
+    rows = rows.astype(np.int64)[used]
+    Uu = None if U is None else U[used]
+    return _PredictiveInputs(Ya, Lm, Ls, E, U, V, idx, used, rows, Uu, N, G)
+
+
 def predictive_check(fit, Y, L, n_rep=50, *, seed=0, x=None, saturate=True, saturation_threshold=6, gene_totals=True, engine_opts=None, host=False):
     """Posterior predictive check of a fit on the model's own scale, per cell and per (gene, clone): the multinomial log-likelihood of every assigned
     cell at its called clone, and the per-clone pseudo-bulk totals, beside the same statistics of ``n_rep`` count matrices drawn from the fitted model.
@@ -1775,29 +1815,7 @@ def predictive_check(fit, Y, L, n_rep=50, *, seed=0, x=None, saturate=True, satu
     n_rep = int(n_rep)
     if n_rep < 2:
         raise ValueError("n_rep must be at least 2 (the replicates' spread is the scale)")
-    Ya, Lm, cn, N, G = _cells_and_cnv(Y, L)
-    names = _clone_names(fit, cn, Lm.shape[1])
-    if len(names) != Lm.shape[1]:
-        raise ValueError(f"fit has {len(names)} clone names but L has {Lm.shape[1]} columns (clones)")
-    clones = np.asarray(fit["clone"], dtype=object).reshape(-1)
-    if clones.shape[0] != N:
-        raise ValueError(f"fit has {clones.shape[0]} clone labels but Y has {N} rows (cells)")
-    lut = {c: i for i, c in enumerate(names)}
-    unknown = sorted({str(c) for c in clones if c not in lut and c != "unassigned"})
-    if unknown:
-        raise ValueError("clone labels that are no column of L: " + ", ".join(unknown))
-    idx = np.array([lut.get(c, -1) for c in clones], dtype=np.int32)
-    used = np.flatnonzero(idx >= 0)
-    if used.size == 0:
-        raise ValueError("every cell is \"unassigned\": there is nothing to evaluate")
-    ml = fit["ml_params"]
-    has_psi = ml.get("W") is not None and np.asarray(ml["W"]).size > 0
-    Ls, E, U, V = _fit_tables(fit, Lm, N, x, "fit" if has_psi else None, saturate, saturation_threshold)[:4]
-    rows = np.asarray(Ya.sum(axis=1)).reshape(-1)
-    if np.any(rows != np.floor(rows)):
-        raise ValueError("Y must hold whole numbers: a replicate keeps the observed row sums")
-    rows = rows.astype(np.int64)[used]
-    Uu = None if U is None else U[used]
+    Ya, Lm, Ls, E, U, V, idx, used, rows, Uu, N, G = _predictive_inputs(fit, Y, L, x, saturate, saturation_threshold)
     if host:
         ll_all = _clone_loglik_host(Ya, E, U, V, const=True)
         T_obs = None
@@ -1835,6 +1853,210 @@ def predictive_check(fit, Y, L, n_rep=50, *, seed=0, x=None, saturate=True, satu
         out.update({"T_observed": T_obs, "T_replicate_mean": T_mean, "T_replicate_sd": T_sd, "z_gene_clone": z_gc,
                     "p_gene_clone": np.minimum(1.0, 2.0 * np.minimum(p_low, p_high))})
     return out
+
+
+def _predictive_moments_host(E, V, U, clone, total, chunk=2048):
+    """Numpy float64 restatement of ``ca_predictive_moments`` (include/clonealign_hip.h states the outputs): per cell ``eta`` summed factor by factor, the
+    shift ``m`` by its maximum over the genes with ``E > 0``, ``w = E exp(eta - m)``, ``Z = sum_g w``, ``p = w / Z``, ``lp = log E + (eta - m) - log Z`` (``log1p(-(the others' w) / Z)`` for a gene with ``p > 1/2``);
+    ``cell_mean = total h`` with ``h = sum_g p lp``, ``cell_var = total sum_g p (lp - h)^2``; ``T_mean``, ``T_var``, ``T_cum3`` [G, C] = the sums over a
+    clone's cells of ``total p``, ``total p (1 - p)`` and ``total p (1 - p)(1 - 2p)``.  A cell without counts gives exactly 0 and joins no sum.  ``chunk``
+    cells at a time: no [cells, genes] array is larger.  Returns ``(cell_mean, cell_var, T_mean, T_var, T_cum3)``; refusals are
+    ``ca_predictive_moments``'s, as ValueError."""
+    E, V, U, clone, total, N, G, C, D = _model_inputs_host(E, V, U, clone, total, "predictive_moments")
+    cell_mean, cell_var = np.zeros(N), np.zeros(N)
+    T = np.zeros((3, G, C))
+    for lo in range(0, N, int(chunk)):
+        rows = lo + np.flatnonzero(total[lo:lo + int(chunk)] > 0)
+        if rows.size == 0:
+            continue
+        e = E[:, clone[rows]].T                                      # [cells, G]
+        pos = e > 0
+        eta = np.zeros(e.shape)
+        for d in range(D):
+            eta = eta + U[rows, d:d + 1] * V[None, :, d]
+        with np.errstate(over="ignore", invalid="ignore"):
+            m = np.where(pos, eta, -np.inf).max(1, keepdims=True)
+            x = np.where(pos, eta - m, 0.0)
+            w = np.where(pos, e * np.exp(x), 0.0)
+        top = w.argmax(1)[:, None]                                   # the largest w (the first such gene) goes last into the sum
+        w_top = np.take_along_axis(w, top, 1)
+        rest = w.copy()
+        np.put_along_axis(rest, top, 0.0, 1)
+        rest = rest.sum(1, keepdims=True)
+        Z = rest + w_top
+        p = w / Z
+        lp = np.where(pos, np.log(np.where(pos, e, 1.0)) + x - np.log(Z), 0.0)
+        big = w_top / Z > 0.5                                        # p > 1/2: the difference above cancels; log1p of the others' share does not
+        np.put_along_axis(lp, top, np.where(big, np.log1p(-rest / Z), np.take_along_axis(lp, top, 1)), 1)
+        h = (p * lp).sum(1, keepdims=True)
+        t = total[rows].astype(np.float64)
+        cell_mean[rows] = t * h[:, 0]
+        cell_var[rows] = t * (p * (lp - h) ** 2).sum(1)
+        tp = t[:, None] * p
+        tpq = tp * (1.0 - p)
+        for c in np.unique(clone[rows]):
+            sel = clone[rows] == c
+            T[0][:, c] += tp[sel].sum(0)
+            T[1][:, c] += tpq[sel].sum(0)
+            T[2][:, c] += (tpq[sel] * (1.0 - 2.0 * p[sel])).sum(0)
+    return cell_mean, cell_var, T[0], T[1], T[2]
+
+
+def refined_normal_cdf(t, mean, var, cum3):
+    """``P(T <= t)`` for an integer-valued sum of independent terms with the given mean, variance and third cumulant, by the normal approximation with
+    the continuity correction and the first Edgeworth (skewness) term: ``F(t) = Phi(x) - gamma (x^2 - 1) phi(x) / 6`` with ``x = (t + 0.5 - mean) / sd``
+    and ``gamma = cum3 / sd^3``, clipped to [0, 1].  A variance of 0 is a point mass at ``mean``.  Arrays broadcast.  Against the exact distribution of
+    a sum of binomials its absolute error is about 0.03 / variance (tests/test_predictive_moments_host.py), so it screens and ranks; it is no tail
+    probability below about 1e-3."""
+    from scipy.special import ndtr
+    t, mean, var, cum3 = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64) for a in (t, mean, var, cum3)))
+    ok = var > 0
+    sd = np.sqrt(np.where(ok, var, 1.0))
+    x = (t + 0.5 - mean) / sd
+    F = ndtr(x) - (cum3 / sd ** 3) * (x * x - 1.0) * np.exp(-0.5 * x * x) / (6.0 * np.sqrt(2.0 * np.pi))
+    return np.where(ok, np.clip(F, 0.0, 1.0), (t >= mean).astype(np.float64))
+
+
+def predictive_moments(fit, Y, L, *, x=None, saturate=True, saturation_threshold=6, engine_opts=None, host=False):
+    """``predictive_check`` without the Monte Carlo where none is needed: given the called clones and the observed row sums -- what its replicates
+    condition on -- a replicate row is one multinomial draw, so the per-clone totals ``T[g, c]`` are sums of independent binomials and the linear part
+    of a row's log-likelihood is a linear statistic; their moments are sums over (cell, gene) of functions of ``p_ng``, taken in one pass on the device
+    that reads no counts (``engine.predictive_moments`` / ``ca_predictive_moments``; include/clonealign_hip.h states them).
+
+    Arguments, label checks and the treatment of "unassigned" cells are ``predictive_check``'s.  Observed side, one engine with ``Y`` resident
+    (``engine_opts`` go to its constructor): ``stat_observed[n] = clone_loglik(const=False)[n, called clone]``, ``T_observed`` from
+    ``clone_gene_sums``.  Expected side: the closed forms on the used cells with their observed row sums.  ``host=True`` runs the numpy restatements
+    on both sides instead; there is no silent fallback otherwise.
+
+    Returns a dict.  ``cells``: the indices used.  Per used cell: ``stat_observed``, ``stat_mean``, ``stat_var`` and ``z_cell`` = (observed - mean) /
+    sd (NaN where the variance is 0: a cell without counts or with one possible gene; ``-inf`` where the observed value is: a count on a gene with
+    copy number 0).  Per (gene, clone): ``T_observed``, ``T_mean``, ``T_var``, ``T_cum3``, ``z_gene_clone`` (NaN where ``T_var`` is 0), ``exposure`` =
+    ``T_mean / E`` (the exact expected count per unit of ``mu L``; NaN where ``E = 0``) and ``p_gene_clone`` = min(1, 2 min(F(T), 1 - F(T - 1))) with
+    ``F = refined_normal_cdf``.  Also ``L`` (as the fit used it, after ``saturate``) and ``clone_cells`` (used cells per clone), which
+    ``dosage_response`` works from.
+
+    What the numbers are: both ``z`` are exact under the model -- mean and sd are computed, nothing is sampled, so they carry no replicate noise and
+    ``p_gene_clone`` has no floor at 1 / (n_rep + 1).  What they are not: the per-cell statistic is the likelihood's LINEAR part, ``sum_g y log p``,
+    not ``predictive_check``'s full ``log_prob`` (the ``lgamma`` constant has no closed-form moments), so the two ``z_cell`` differ.  ``F``'s absolute
+    error against the exact distribution is about 0.03 / variance (tests/test_predictive_moments_host.py), so ``p_gene_clone`` ranks and screens and
+    is no tail probability below about 1e-3.  And, as for ``predictive_check``: the clones (and ``psi``) were chosen to fit the observed cells, so the
+    observed side is favoured; and real counts are overdispersed against a multinomial, so on real data these are rankings on a depth-aware scale,
+    not calibrated tests."""
+    Ya, _Lm, Ls, E, U, V, idx, used, rows, Uu, N, G = _predictive_inputs(fit, Y, L, x, saturate, saturation_threshold)
+    C = E.shape[1]
+    if host:
+        ll_all = _clone_loglik_host(Ya, E, U, V, const=False)
+        T_obs = np.zeros((G, C))
+        dense = Ya[used].toarray() if _is_sparse(Ya) else np.asarray(Ya)[used]
+        np.add.at(T_obs.T, idx[used], dense.astype(np.float64))
+        mean, var, T_mean, T_var, T_cum3 = _predictive_moments_host(E, V, Uu, idx[used], rows)
+    else:
+        from . import engine as _engine
+        opts = dict(engine_opts or {})
+        eng = _engine.HipEngine(Ya, Ls, np.zeros((N, 0)), None, 0, **opts)
+        try:
+            ll_all = eng.clone_loglik(E, U, V, const=False)
+            T_obs = np.ascontiguousarray(eng.clone_gene_sums(idx)[0])
+        finally:
+            eng.close()
+        mean, var, T_mean, T_var, T_cum3 = _engine.predictive_moments(E, V, Uu, idx[used], rows, device=int(opts.get("device", 0)))
+    obs = ll_all[used, idx[used]]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z_cell = np.where(var > 0, (obs - mean) / np.sqrt(np.where(var > 0, var, 1.0)), np.nan)
+        z_gc = np.where(T_var > 0, (T_obs - T_mean) / np.sqrt(np.where(T_var > 0, T_var, 1.0)), np.nan)
+        exposure = np.where(E > 0, T_mean / np.where(E > 0, E, 1.0), np.nan)
+    p_low, p_high = refined_normal_cdf(T_obs, T_mean, T_var, T_cum3), 1.0 - refined_normal_cdf(T_obs - 1.0, T_mean, T_var, T_cum3)
+    return {"cells": used, "stat_observed": obs, "stat_mean": mean, "stat_var": var, "z_cell": z_cell,
+            "T_observed": T_obs, "T_mean": T_mean, "T_var": T_var, "T_cum3": T_cum3, "z_gene_clone": z_gc, "exposure": exposure,
+            "p_gene_clone": np.minimum(1.0, 2.0 * np.minimum(p_low, p_high)), "L": Ls, "clone_cells": np.bincount(idx[used], minlength=C).astype(np.int64)}
+
+
+def _dosage_fit(T, X, L, use, kappa_max=8.0, max_iter=50, tol=1e-10, max_step=2.0):
+    """The per-gene fits of ``dosage_response`` from arrays [G, C]: observed totals ``T``, exposures ``X``, copy numbers ``L`` and the mask ``use`` of
+    the (gene, clone) entries that take part.  Every gene runs the same safeguarded Newton iteration on its concave profile log-likelihood."""
+    G, C = T.shape
+    use = use & (L > 0) & np.isfinite(X) & (X > 0)
+    l = np.where(use, np.log(np.where(use, L, 1.0)), 0.0)
+    logX = np.where(use, np.log(np.where(use, X, 1.0)), -np.inf)
+    Tm = np.where(use, T, 0.0)
+    Tt, Tl = Tm.sum(1), (Tm * l).sum(1)
+    n_used = use.sum(1)
+    ls = np.sort(np.where(use, l, np.inf), axis=1)
+    distinct = np.isfinite(ls[:, :1]).sum(1) + (np.isfinite(ls[:, 1:]) & (ls[:, 1:] != ls[:, :-1])).sum(1)
+    ok = (distinct >= 2) & (Tt > 0)
+
+    def state(k):                                                    # lp(kappa), E_pi[l], Var_pi[l], pi
+        a = k[:, None] * l + logX
+        top = np.where(ok, a.max(1, initial=-np.inf), 0.0)
+        ex = np.where(use & ok[:, None], np.exp(a - top[:, None]), 0.0)
+        s = np.where(ok, ex.sum(1), 1.0)
+        pi = ex / s[:, None]
+        El = (pi * l).sum(1)
+        return k * Tl - Tt * (top + np.log(s)), El, (pi * (l - El[:, None]) ** 2).sum(1), pi
+
+    k = np.ones(G)
+    f, El, Vl, pi = state(k)
+    f1 = f.copy()
+    conv = np.zeros(G, dtype=bool)
+    for _it in range(int(max_iter)):
+        todo = ok & ~conv
+        if not todo.any():
+            break
+        grad, curv = Tl - Tt * El, Tt * Vl
+        with np.errstate(divide="ignore", invalid="ignore"):
+            step = np.where(curv > 0, grad / np.where(curv > 0, curv, 1.0), np.sign(grad) * max_step)
+        kn = np.clip(k + np.clip(step, -max_step, max_step), -kappa_max, kappa_max)
+        moved = np.abs(kn - k)                                       # the Newton step inside the bounds: what convergence is judged by
+        fn, Eln, Vln, pin = state(kn)
+        for _h in range(40):                                         # concave in kappa: halve the step while the value falls by more than its rounding noise
+            worse = todo & (fn < f - 64.0 * np.finfo(np.float64).eps * (np.abs(f) + np.abs(fn) + Tt)) & (kn != k)
+            if not worse.any():
+                break
+            kn = np.where(worse, 0.5 * (k + kn), kn)
+            fn, Eln, Vln, pin = state(kn)
+        upd = todo[:, None]
+        k, f, El, Vl, pi = np.where(todo, kn, k), np.where(todo, fn, f), np.where(todo, Eln, El), np.where(todo, Vln, Vl), np.where(upd, pin, pi)
+        conv |= todo & (moved <= tol * np.maximum(1.0, np.abs(k)))
+    f0 = state(np.zeros(G))[0]
+    nan = np.full(G, np.nan)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        se = np.where(ok & (Tt * Vl > 0), 1.0 / np.sqrt(np.where(Tt * Vl > 0, Tt * Vl, 1.0)), np.where(ok, np.inf, np.nan))
+        fitted = Tt[:, None] * pi
+        pearson = np.where(use & (fitted > 0), (Tm - fitted) ** 2 / np.where(fitted > 0, fitted, 1.0), 0.0).sum(1)
+    lrt1, lrt0 = np.maximum(0.0, 2.0 * (f - f1)), np.maximum(0.0, 2.0 * (f - f0))
+    from scipy.special import erfc
+    return {"kappa": np.where(ok, k, nan), "se": se, "lrt_proportional": np.where(ok, lrt1, nan), "lrt_insensitive": np.where(ok, lrt0, nan),
+            "p_proportional": np.where(ok, erfc(np.sqrt(lrt1 / 2.0)), nan), "p_insensitive": np.where(ok, erfc(np.sqrt(lrt0 / 2.0)), nan),
+            "n_clones_used": n_used.astype(np.int64), "total_count": Tt, "converged": ok & conv, "at_bound": ok & (np.abs(k) == kappa_max),
+            "pearson": np.where(ok, pearson, nan), "df": n_used.astype(np.int64) - 2}
+
+
+def dosage_response(fit, Y, L, *, moments=None, kappa_max=8.0, max_iter=50, tol=1e-10, x=None, saturate=True, saturation_threshold=6, engine_opts=None,
+                    host=False):
+    """Per-gene test of the model's central assumption, that expression is proportional to copy number: fits ``expression ~ mu_g L[g, c]^kappa_g`` per
+    gene, where ``kappa = 1`` is the clonealign assumption and ``kappa = 0`` dosage compensation.  Works from ``predictive_moments``'s ``T_observed``
+    and ``exposure`` alone, on the host, in O(genes x clones); ``moments=`` reuses a result of ``predictive_moments``, otherwise the other arguments
+    go to it.
+
+    Per gene, over the clones with used cells, ``L[g, c] > 0`` (the ``L`` the fit used, after ``saturate``) and a finite exposure ``X_c``: the Poisson
+    working model, conditional on the cells' normalisers, ``T_c ~ Poisson(mu L_c^kappa X_c)``, with ``mu`` profiled out: ``lp(kappa) = kappa sum_c
+    T_c l_c - T. log sum_c X_c exp(kappa l_c)``, ``l = log L``, concave; a safeguarded Newton iteration from ``kappa = 1`` (steps clipped, halved
+    where the value would fall, ``|kappa| <= kappa_max``; stops at a step below ``tol``).
+
+    Returns a dict of arrays [genes]: ``kappa``, ``se`` = 1 / sqrt(T. Var_pi[l]) (``pi_c ~ X_c L_c^kappa``), ``lrt_proportional`` = 2 (lp(kappa_hat)
+    - lp(1)) and ``lrt_insensitive`` (against 0) with their chi-square(1) tail probabilities ``p_proportional`` and ``p_insensitive``,
+    ``n_clones_used``, ``total_count``, ``converged``, ``at_bound`` (``|kappa| = kappa_max``: every count sits in the clones of extreme copy number),
+    ``pearson`` = sum_c (T_c - fitted_c)^2 / fitted_c and ``df`` = ``n_clones_used - 2``.  A gene with fewer than two distinct copy numbers among its
+    used clones, or without counts, is not identifiable: NaN, with ``n_clones_used`` as found.
+
+    Real counts are overdispersed against the Poisson working model, which makes both likelihood-ratio tests anti-conservative: ``pearson / df`` well
+    above 1 says by how much, and is what to look at before a ``p`` value.  Genes with ``kappa`` near 0 carry no information about the clone of a
+    cell; they are the ones to leave out of a fit."""
+    if moments is None:
+        moments = predictive_moments(fit, Y, L, x=x, saturate=saturate, saturation_threshold=saturation_threshold, engine_opts=engine_opts, host=host)
+    T, X, Ls = (np.asarray(moments[k], dtype=np.float64) for k in ("T_observed", "exposure", "L"))
+    use = np.broadcast_to(np.asarray(moments["clone_cells"])[None, :] > 0, T.shape)
+    return _dosage_fit(T, X, Ls, use, float(kappa_max), int(max_iter), float(tol))
 
 
 def _logexpr_sums_host(Y, group_idx, n_groups, size_factors=None, chunk=4096):

@@ -474,3 +474,42 @@ inline hipError_t launch_predictive(hipStream_t stream, const ca_pred_ops& o) {
                      o.lw_blk, o.row_blk, o.ll, o.T, o.n_cnt, o.G, o.C, o.D, o.plan.S, o.plan.nco, o.plan.hist_lds, (uint32_t)o.seed, (uint32_t)(o.seed >> 32), o.draw0, o.n_rep, o.q0);
   return hipGetLastError();
 }
+
+// ---- k_predmom_loge / k_predmom_cell / k_predmom_gene<D> / k_predmom_finish: the launches of ca_predictive_moments on one batch of cells (no engine: the call owns its stream) ----
+// the call's tables (E, log E and V transposed, the running sums acc [3][C][G]) and the batch's arrays: the cells' inputs, what the cell phase leaves for the
+// gene phase (m, Z), the list of cells with counts by clone, its strips, the first strip of every clone, the strip sums
+struct ca_predmom_ops { const double *Et, *Vt, *U; double* lEt; const int32_t* clone; const int64_t* total; double *w_blk, *m, *z, *mean, *var; const int32_t *list, *first;
+                        const ca_pm_strip* strips; double *genepart, *acc; int64_t n_cnt; int blocks, nstrips, G, C, D; bool w_lds; };
+inline hipError_t launch_predmom_loge(hipStream_t stream, const ca_predmom_ops& o) {
+  const int64_t n = (int64_t)o.C * o.G;
+  hipLaunchKernelGGL(k_predmom_loge, dim3((unsigned)cdiv(n, CA_PM_TB)), dim3(CA_PM_TB), 0, stream, o.Et, o.lEt, n);
+  return hipGetLastError();
+}
+inline hipError_t launch_predmom_cell(hipStream_t stream, const ca_predmom_ops& o) {
+  hipLaunchKernelGGL(k_predmom_cell, dim3((unsigned)o.blocks), dim3(CA_PM_TB), o.w_lds ? (size_t)o.G * sizeof(double) : 0, stream, o.Et, o.lEt, o.Vt, o.U, o.clone, o.total,
+                     o.w_lds ? nullptr : o.w_blk, o.m, o.z, o.mean, o.var, o.n_cnt, o.G, o.D);
+  return hipGetLastError();
+}
+template <int D>
+hipError_t predmom_gene_t(hipStream_t stream, const ca_predmom_ops& o) {
+  const int gtiles = cdiv(o.G, CA_PM_TB);
+  hipLaunchKernelGGL((k_predmom_gene<D>), dim3((unsigned)((int64_t)gtiles * o.nstrips)), dim3(CA_PM_TB), 0, stream, o.Et, o.Vt, o.U, o.total, o.m, o.z, o.list, o.strips, o.genepart,
+                     o.G, gtiles);
+  return hipGetLastError();
+}
+inline hipError_t launch_predmom_gene(hipStream_t stream, const ca_predmom_ops& o) {   // (V's row of a gene lives in registers: one instantiation per D = 1 .. CA_LL_DMAX)
+  switch (o.D) {
+    case 1: return predmom_gene_t<1>(stream, o);
+    case 2: return predmom_gene_t<2>(stream, o);
+    case 3: return predmom_gene_t<3>(stream, o);
+    case 4: return predmom_gene_t<4>(stream, o);
+    case 5: return predmom_gene_t<5>(stream, o);
+    case 6: return predmom_gene_t<6>(stream, o);
+    case 7: return predmom_gene_t<7>(stream, o);
+    default: return predmom_gene_t<8>(stream, o);
+  }
+}
+inline hipError_t launch_predmom_finish(hipStream_t stream, const ca_predmom_ops& o) {
+  hipLaunchKernelGGL(k_predmom_finish, dim3((unsigned)cdiv((int64_t)o.C * o.G, CA_PM_TB)), dim3(CA_PM_TB), 0, stream, o.genepart, o.first, o.acc, o.G, o.C);
+  return hipGetLastError();
+}

@@ -61,6 +61,9 @@ EXPORTS = (
     "ca_simulate_counts", "ca_simulate_kernel_ms",
     # log-likelihoods and per-clone gene totals of replicate rows that never leave the device (predictive_stats), no handle, additions to ABI 6
     "ca_predictive_stats", "ca_predictive_kernel_ms",
+    # the replicates' moments in closed form: per cell the mean and variance of the log-likelihood's linear part, per (gene, clone) three cumulants of the totals
+    # (predictive_moments), no handle, additions to ABI 6
+    "ca_predictive_moments", "ca_predictive_moments_kernel_ms",
     # clone evidence with psi integrated out: Newton mode, Laplace value and quadrature per (cell, clone) (clone_evidence / heldout_evidence), additions to ABI 6
     "ca_clone_evidence", "ca_group_clone_evidence",
 )
@@ -192,6 +195,9 @@ def load_library(path=None):
     lib.ca_predictive_stats.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                         C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_char_p]
     lib.ca_predictive_kernel_ms.argtypes = [C.POINTER(C.c_double)]
+    lib.ca_predictive_moments.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
+    lib.ca_predictive_moments_kernel_ms.argtypes = [C.POINTER(C.c_double)]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -1151,6 +1157,45 @@ def predictive_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``predictive_stats`` call took (HIP events around each launch)."""
     ms = C.c_double(0.0)
     load_library().ca_predictive_kernel_ms(C.byref(ms))
+    return ms.value
+
+
+def predictive_moments(E, V, U, clone, total, device=0):
+    """The moments of ``predictive_stats``'s replicates in closed form, nothing drawn (ca_predictive_moments; include/clonealign_hip.h states them).  Arguments
+    as for ``simulate_counts``.  Returns ``(cell_mean, cell_var, T_mean, T_var, T_cum3)``: per cell the mean and variance over the replicates of the linear
+    part of the row's log-likelihood, ``sum_g y_g log p_g`` (float64 [N]); per (gene, clone) the mean, variance and third cumulant of the rows summed per
+    clone (float64 [G, C]).  The cell values depend on the cell's own arguments alone; the tables of cells split over calls add up to within rounding.
+    Refusals raise EngineError."""
+    lib = load_library()
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"predictive_moments: E is {E.shape}; expected (genes, clones)")
+    G, Cn = E.shape
+    clone = np.ascontiguousarray(clone, dtype=np.int32).reshape(-1)
+    N = clone.shape[0]
+    total = np.ascontiguousarray(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
+    D = 0
+    if (U is None) != (V is None):
+        raise ValueError("predictive_moments: U and V go together (both, or neither)")
+    if U is not None:
+        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"predictive_moments: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = int(U.shape[1])
+    cell = np.zeros((2, max(N, 1)), dtype=np.float64)                # (never an empty buffer: the call wants five pointers also without cells)
+    T = np.zeros((3, G, Cn), dtype=np.float64)
+    err = C.create_string_buffer(256)
+    rc = lib.ca_predictive_moments(N, G, Cn, D, _ptr(E), _ptr(V) if D > 0 else None, _ptr(U) if D > 0 else None, _ptr(clone), _ptr(total), int(device),
+                                   _ptr(cell[0]), _ptr(cell[1]), _ptr(T[0]), _ptr(T[1]), _ptr(T[2]), err)
+    if rc != CA_OK:
+        raise EngineError(rc, err.value.decode() or "ca_predictive_moments")
+    return cell[0, :N], cell[1, :N], T[0], T[1], T[2]
+
+
+def predictive_moments_kernel_ms():
+    """Milliseconds the kernel launches of this thread's last ``predictive_moments`` call took (HIP events around each launch; 0 without factors)."""
+    ms = C.c_double(0.0)
+    load_library().ca_predictive_moments_kernel_ms(C.byref(ms))
     return ms.value
 
 

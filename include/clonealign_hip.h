@@ -744,6 +744,39 @@ int ca_predictive_stats(int64_t N, int32_t G, int32_t C, int32_t D, const double
 /* milliseconds the k_predictive launches of the calling thread's last ca_predictive_stats took (HIP events around each launch, summed; 0 after a refusal) */
 int ca_predictive_kernel_ms(double* ms);
 
+/* The moments of ca_predictive_stats's replicates in closed form, needs no handle: nothing is drawn.  Notation, layouts (row-major host arrays) and refusals are
+ * ca_predictive_stats's.  Given the clones and the row sums -- what the replicates condition on -- a replicate row of cell n is ONE draw of
+ * Multinomial(total_n, p_n), so the per-clone total T[g][c] is a sum of independent binomials over the clone's cells and the linear part of the row's
+ * log-likelihood, sum_g y_ng log p_ng (ca_clone_loglik without the lgamma constant, at the cell's clone), is a linear statistic of one multinomial.
+ * Per cell n, with c = clone[n], float64 throughout: eta_g and the shift m exactly as in step 1 of the ca_simulate_counts sampler (m = max of eta_g over
+ * the genes with E[g][c] > 0); w_g = E[g][c] exp(eta_g - m), 0 where E = 0; Z = sum_g w_g in a fixed order (the largest w last); p_g = w_g / Z;
+ * lp_g = log p_g taken as log E[g][c] + (eta_g - m) - log Z (not log(exp(...)); 0 and unused where E = 0) -- except for a gene with p_g > 1/2, the one
+ * of largest w, where that difference cancels (|lp| may be 1e-20 under rounding noise of 1e-16): there lp_g = log1p(-(sum of the other w) / Z), which
+ * keeps its relative accuracy and is 0 exactly for a lone gene; h = sum_g p_g lp_g.  Outputs (host, row-major):
+ *   cell_mean[n] = total_n h                              the mean of the linear part over the replicates                                    (N float64)
+ *   cell_var[n]  = total_n sum_g p_g (lp_g - h)^2         its variance, in the centred form                                                  (N float64)
+ *   T_mean[g][c] = sum over the call's cells with clone[n] == c of total_n p_ng                                                           (G x C float64)
+ *   T_var[g][c]  = the same sum of total_n p (1 - p)
+ *   T_cum3[g][c] = the same sum of total_n p (1 - p)(1 - 2p), the third cumulant; every term is formed per (cell, gene), never as a difference of sums.
+ * Exactly 0: both cell values at total_n = 0; the three columns of a clone without cells (or whose cells all have total 0); every entry with E[g][c] = 0;
+ * cell_var, and the cell's share of T_var and T_cum3, where the cell's clone has one positive gene (p = 1 and lp = 0 exactly).  No NaN or inf for accepted
+ * input, |eta| of several hundred included.  The caller's buffers are overwritten, not added to.
+ * Sums run in a fixed order without float atomics: two calls agree bit for bit.  cell_mean and cell_var of a cell depend on its own inputs alone -- not on
+ * N, the internal batching or how a caller splits the cells over calls.  The gene-side sums are grouped by the call (cells sorted by clone, in strips whose
+ * length depends on N, G, C and D): across a split of the cells they add up to within rounding, not bit for bit.  D = 0: p depends on the clone alone and
+ * the tables follow from the clones' sums of totals, on the host; its last bits may differ from a call with a zero factor.
+ * Device buffers stay below 256 MB (the cells go in batches that fit) as long as the five tables of C x G float64 do, up to 1.6 million (gene, clone)
+ * pairs; there is no ca_group_* form (the cell values need none; the tables of a split add up).
+ * CA_ERR_INVALID (message in err, naming the argument; nothing is written to any output): everything ca_predictive_stats refuses about E, V, U, clone,
+ * total, D, N, G and C (a cell with total > 0 whose clone has E = 0 in every gene among it); any of the five outputs NULL.  err (optional, >= 256 bytes)
+ * receives the message on failure. */
+int ca_predictive_moments(int64_t N, int32_t G, int32_t C, int32_t D, const double* E /* G x C */, const double* V /* G x D, or NULL */,
+                          const double* U /* N x D, or NULL */, const int32_t* clone /* N */, const int64_t* total /* N */, int32_t device,
+                          double* cell_mean /* N */, double* cell_var /* N */,
+                          double* T_mean /* G x C */, double* T_var /* G x C */, double* T_cum3 /* G x C */, char* err);
+/* milliseconds the kernel launches of the calling thread's last ca_predictive_moments took (HIP events around each launch, summed; 0 after a refusal and at D = 0) */
+int ca_predictive_moments_kernel_ms(double* ms);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ONE fit, cell-sharded over several devices of ONE process (ABI 6; SURVEY.md section 8b "multi-GPU via one process / 8 devices,
  * communicator created per fit", section 8e).  The reference's caller is a single R session: inference_tflow() is called once
