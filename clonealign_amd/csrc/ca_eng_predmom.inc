@@ -1,11 +1,7 @@
-// ca_eng_predmom.inc -- part of clonealign_hip.hip (textually included there, after ca_eng_predictive.inc; one translation unit): C ABI without a handle: the mean and variance of the log-likelihood's linear part per cell and the mean, variance and third cumulant of the per-clone gene totals of ca_predictive_stats's replicates, in closed form (ca_predictive_moments; include/clonealign_hip.h states the outputs), the kernel time of the calling thread's last call.
+// ca_eng_predmom.inc -- part of clonealign_hip.hip (textually included there, after ca_eng_predictive.inc; one translation unit; ca_gen_call, the call's scaffold, is defined in ca_eng_simulate.inc): C ABI without a handle: the mean and variance of the log-likelihood's linear part per cell and the mean, variance and third cumulant of the per-clone gene totals of ca_predictive_stats's replicates, in closed form (ca_predictive_moments; include/clonealign_hip.h states the outputs), the kernel time of the calling thread's last call.
 namespace { thread_local double predmom_kernel_ms = 0.0; }
 
-int ca_predictive_moments_kernel_ms(double* ms) {
-  if (!ms) return CA_ERR_INVALID;
-  *ms = predmom_kernel_ms;
-  return CA_OK;
-}
+int ca_predictive_moments_kernel_ms(double* ms) { return gen_kernel_ms(ms, predmom_kernel_ms); }
 
 // How a call with factors is cut under a budget of `budget` bytes per kind of device buffer (64 MB): NB cells per batch (a cell's U row, clone, total, m, Z,
 // mean, variance and list entry: 8 D + 56 bytes), SL list entries per strip of the gene phase.  SL: at least 64; about 2048 blocks per launch (strips x tiles of
@@ -32,17 +28,15 @@ inline ca_pm_cut predmom_cut(int64_t N, int32_t G, int32_t C, int32_t D, int64_t
 // k_predmom_gene and k_predmom_finish, which adds the batch's strips onto the running tables; the batches go in order, so the sums have one fixed order.
 int ca_predictive_moments(int64_t N, int32_t G, int32_t C, int32_t D, const double* E, const double* V, const double* U, const int32_t* clone, const int64_t* total,
                           int32_t device, double* cell_mean, double* cell_var, double* T_mean, double* T_var, double* T_cum3, char* err) {
-  auto fail = [&](int code, const std::string& m) { if (err) { strncpy(err, m.c_str(), 255); err[255] = 0; } return code; };
-  auto refuse = [&](const std::string& m) { return fail(CA_ERR_INVALID, "ca_predictive_moments: " + m); };
-  predmom_kernel_ms = 0.0;
+  ca_gen_call call("ca_predictive_moments", err, predmom_kernel_ms);
   std::string bad = sim_check_shape(N, G, C, D, E, V, U, clone, total, false, "E, clone and total must not be NULL", 0);
-  if (!bad.empty()) return refuse(bad);
+  if (!bad.empty()) return call.refuse(bad);
   const std::pair<const char*, const double*> outs[5] = {{"cell_mean", cell_mean}, {"cell_var", cell_var}, {"T_mean", T_mean}, {"T_var", T_var}, {"T_cum3", T_cum3}};
   for (const auto& o : outs)
-    if (!o.second) return refuse(std::string(o.first) + " must not be NULL");
+    if (!o.second) return call.refuse(std::string(o.first) + " must not be NULL");
   std::vector<double> Et, Vt;
   bad = sim_check_values(N, G, C, D, E, V, U, clone, total, Et, Vt);
-  if (!bad.empty()) return refuse(bad);
+  if (!bad.empty()) return call.refuse(bad);
   const size_t CG = (size_t)C * G;
   if (N == 0) {
     for (double* T : {T_mean, T_var, T_cum3}) std::fill(T, T + CG, 0.0);
@@ -94,56 +88,23 @@ int ca_predictive_moments(int64_t N, int32_t G, int32_t C, int32_t D, const doub
   const ca_pm_cut cut = predmom_cut(N, G, C, D, budget);
   const int64_t NB = cut.NB;
   const bool w_lds = (size_t)G * 8 <= CA_PM_LDS;
-  double *Et_d = nullptr, *lEt_d = nullptr, *Vt_d = nullptr, *U_d = nullptr, *w_d = nullptr, *m_d = nullptr, *z_d = nullptr, *mean_d = nullptr, *var_d = nullptr, *gp_d = nullptr,
-         *acc_d = nullptr;
-  int32_t *cl_d = nullptr, *list_d = nullptr, *first_d = nullptr; int64_t* tot_d = nullptr; ca_pm_strip* st_d = nullptr;
-  hipStream_t stream = nullptr; hipEvent_t ev[2] = {nullptr, nullptr};
-  auto cleanup = [&]() { hipFree(Et_d); hipFree(lEt_d); hipFree(Vt_d); hipFree(U_d); hipFree(w_d); hipFree(m_d); hipFree(z_d); hipFree(mean_d); hipFree(var_d); hipFree(gp_d);
-                         hipFree(acc_d); hipFree(cl_d); hipFree(list_d); hipFree(first_d); hipFree(tot_d); hipFree(st_d);
-                         for (int i = 0; i < 2; ++i) if (ev[i]) hipEventDestroy(ev[i]);
-                         if (stream) hipStreamDestroy(stream); };
-#define MCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); return fail(e_ == hipErrorOutOfMemory ? CA_ERR_NOMEM : CA_ERR_HIP, std::string("ca_predictive_moments: " #call ": ") + hipGetErrorString(e_)); } } while (0)
-  MCK(hipSetDevice(device));
   int n_cu = 0;
-  MCK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
+  if (!call.open(device) || !call.note(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device), "hipDeviceGetAttribute")) return call.failed();
   int64_t blocks = std::min<int64_t>(NB, 8 * (int64_t)std::max(n_cu, 1));
   if (!w_lds) blocks = std::min<int64_t>(blocks, std::max<int64_t>(1, budget / ((int64_t)G * 8)));
-  MCK(hipStreamCreate(&stream));
-  for (int i = 0; i < 2; ++i) MCK(hipEventCreate(&ev[i]));
-  MCK(hipMalloc((void**)&Et_d, CG * sizeof(double)));
-  MCK(hipMemcpyAsync(Et_d, Et.data(), CG * sizeof(double), hipMemcpyHostToDevice, stream));
-  MCK(hipMalloc((void**)&lEt_d, CG * sizeof(double)));
-  MCK(hipMalloc((void**)&Vt_d, Vt.size() * sizeof(double)));
-  MCK(hipMemcpyAsync(Vt_d, Vt.data(), Vt.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-  MCK(hipMalloc((void**)&acc_d, 3 * CG * sizeof(double)));
-  MCK(hipMemsetAsync(acc_d, 0, 3 * CG * sizeof(double), stream));
-  MCK(hipMalloc((void**)&U_d, (size_t)NB * D * sizeof(double)));
-  MCK(hipMalloc((void**)&cl_d, (size_t)NB * sizeof(int32_t)));
-  MCK(hipMalloc((void**)&tot_d, (size_t)NB * sizeof(int64_t)));
-  MCK(hipMalloc((void**)&m_d, (size_t)NB * sizeof(double)));
-  MCK(hipMalloc((void**)&z_d, (size_t)NB * sizeof(double)));
-  MCK(hipMalloc((void**)&mean_d, (size_t)NB * sizeof(double)));
-  MCK(hipMalloc((void**)&var_d, (size_t)NB * sizeof(double)));
-  MCK(hipMalloc((void**)&list_d, (size_t)NB * sizeof(int32_t)));
-  MCK(hipMalloc((void**)&st_d, (size_t)cut.strips * sizeof(ca_pm_strip)));
-  MCK(hipMalloc((void**)&first_d, ((size_t)C + 1) * sizeof(int32_t)));
-  MCK(hipMalloc((void**)&gp_d, (size_t)cut.strips * 3 * G * sizeof(double)));
-  if (!w_lds) MCK(hipMalloc((void**)&w_d, (size_t)blocks * G * sizeof(double)));
+  call.model(Et, Vt, D, NB);
   ca_predmom_ops o;
-  o.Et = Et_d; o.lEt = lEt_d; o.Vt = Vt_d; o.U = U_d; o.clone = cl_d; o.total = tot_d; o.w_blk = w_d; o.m = m_d; o.z = z_d; o.mean = mean_d; o.var = var_d; o.list = list_d;
-  o.strips = st_d; o.first = first_d; o.genepart = gp_d; o.acc = acc_d; o.G = G; o.C = C; o.D = D;
-  double kernel_ms = 0.0;
-  auto timed = [&](auto&& launch) -> hipError_t {   // one launch between the two events; its time joins the call's
-    hipError_t e_ = hipEventRecord(ev[0], stream);
-    if (e_ == hipSuccess) e_ = launch();
-    if (e_ == hipSuccess) e_ = hipEventRecord(ev[1], stream);
-    if (e_ == hipSuccess) e_ = hipEventSynchronize(ev[1]);
-    float ms = 0.f;
-    if (e_ == hipSuccess) e_ = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    kernel_ms += ms;
-    return e_;
-  };
-  MCK(timed([&]() { return launch_predmom_loge(stream, o); }));
+  o.Et = call.Et; o.Vt = call.Vt; o.U = call.U; o.clone = call.clone; o.total = call.total; o.G = G; o.C = C; o.D = D; o.w_lds = w_lds;
+  o.lEt = call.alloc<double>((int64_t)CG);
+  o.acc = call.alloc<double>(3 * (int64_t)CG);
+  o.m = call.alloc<double>(NB); o.z = call.alloc<double>(NB); o.mean = call.alloc<double>(NB); o.var = call.alloc<double>(NB);
+  int32_t *list_d = call.alloc<int32_t>(NB), *first_d = call.alloc<int32_t>((int64_t)C + 1);
+  ca_pm_strip* st_d = call.alloc<ca_pm_strip>(cut.strips);
+  o.list = list_d; o.first = first_d; o.strips = st_d;
+  o.genepart = call.alloc<double>(cut.strips * 3 * G);
+  o.w_blk = w_lds ? nullptr : call.alloc<double>(blocks * G);
+  if (o.acc) call.note(hipMemsetAsync(o.acc, 0, 3 * CG * sizeof(double), call.stream), "hipMemsetAsync of the tables");
+  if (!call.timed([&]() { return launch_predmom_loge(call.stream, o); })) return call.failed();
   std::vector<int32_t> list, first((size_t)C + 1), fill((size_t)C);
   std::vector<ca_pm_strip> strips;
   for (int64_t n_lo = 0; n_lo < N; n_lo += NB) {
@@ -165,37 +126,21 @@ int ca_predictive_moments(int64_t N, int32_t G, int32_t C, int32_t D, const doub
     list.resize((size_t)at);
     for (int64_t i = 0; i < n_cnt; ++i)
       if (total[n_lo + i] > 0) list[(size_t)fill[(size_t)clone[n_lo + i]]++] = (int32_t)i;
-    if ((int64_t)strips.size() > cut.strips) { cleanup(); return fail(CA_ERR_HIP, "ca_predictive_moments: internal: more strips than planned"); }
-    MCK(hipMemcpyAsync(U_d, U + (size_t)n_lo * D, (size_t)n_cnt * D * sizeof(double), hipMemcpyHostToDevice, stream));
-    MCK(hipMemcpyAsync(cl_d, clone + n_lo, (size_t)n_cnt * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    MCK(hipMemcpyAsync(tot_d, total + n_lo, (size_t)n_cnt * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    if ((int64_t)strips.size() > cut.strips) return call.fail(CA_ERR_HIP, "internal: more strips than planned");
     if (at > 0) {
-      MCK(hipMemcpyAsync(list_d, list.data(), (size_t)at * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-      MCK(hipMemcpyAsync(st_d, strips.data(), strips.size() * sizeof(ca_pm_strip), hipMemcpyHostToDevice, stream));
-      MCK(hipMemcpyAsync(first_d, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+      call.note(hipMemcpyAsync(list_d, list.data(), (size_t)at * sizeof(int32_t), hipMemcpyHostToDevice, call.stream), "hipMemcpyAsync of the list");
+      call.note(hipMemcpyAsync(st_d, strips.data(), strips.size() * sizeof(ca_pm_strip), hipMemcpyHostToDevice, call.stream), "hipMemcpyAsync of the strips");
+      call.note(hipMemcpyAsync(first_d, first.data(), first.size() * sizeof(int32_t), hipMemcpyHostToDevice, call.stream), "hipMemcpyAsync of the strips' index");
     }
-    MCK(hipStreamSynchronize(stream));   // (the copies have read the caller's pageable arrays and the lists)
-    o.n_cnt = n_cnt; o.blocks = (int)std::min<int64_t>(blocks, n_cnt); o.w_lds = w_lds; o.nstrips = (int)strips.size();
-    MCK(timed([&]() { return launch_predmom_cell(stream, o); }));
-    if (at > 0) {
-      MCK(timed([&]() { return launch_predmom_gene(stream, o); }));
-      MCK(timed([&]() { return launch_predmom_finish(stream, o); }));
-    }
-    MCK(hipMemcpy(cell_mean + n_lo, mean_d, (size_t)n_cnt * sizeof(double), hipMemcpyDeviceToHost));
-    MCK(hipMemcpy(cell_var + n_lo, var_d, (size_t)n_cnt * sizeof(double), hipMemcpyDeviceToHost));
+    o.n_cnt = n_cnt; o.blocks = (int)std::min<int64_t>(blocks, n_cnt); o.nstrips = (int)strips.size();
+    if (!call.feed(U, clone, total, n_lo, n_cnt) || !call.timed([&]() { return launch_predmom_cell(call.stream, o); })) return call.failed();   // (feed's wait covers the lists)
+    if (at > 0 && (!call.timed([&]() { return launch_predmom_gene(call.stream, o); }) || !call.timed([&]() { return launch_predmom_finish(call.stream, o); }))) return call.failed();
+    if (!call.ok(hipMemcpy(cell_mean + n_lo, o.mean, (size_t)n_cnt * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy", (size_t)n_cnt * sizeof(double)) ||
+        !call.ok(hipMemcpy(cell_var + n_lo, o.var, (size_t)n_cnt * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy", (size_t)n_cnt * sizeof(double)))
+      return call.failed();
   }
-  {   // [3][c][g] on the device -> the caller's three [g][c]
-    std::vector<double> acc(3 * CG);
-    MCK(hipMemcpy(acc.data(), acc_d, 3 * CG * sizeof(double), hipMemcpyDeviceToHost));
-    double* outT[3] = {T_mean, T_var, T_cum3};
-    for (int k = 0; k < 3; ++k)
-      for (int c = 0; c < C; ++c) {
-        const double* src = acc.data() + ((size_t)k * C + c) * G;
-        for (int g = 0; g < G; ++g) outT[k][(size_t)g * C + c] = src[g];
-      }
-  }
-#undef MCK
-  cleanup();
-  predmom_kernel_ms = kernel_ms;
-  return CA_OK;
+  // [3][c][g] on the device -> the caller's three [g][c]
+  double* const outT[3] = {T_mean, T_var, T_cum3};
+  if (!call.gene_major(o.acc, 3, C, G, [&](int64_t k) { return outT[k]; })) return call.failed();
+  return call.done();
 }

@@ -306,26 +306,34 @@ int dalloc(ca_engine* h, T** p, int64_t n) {
   return CA_OK;
 }
 
-// The device memory of ONE CALL on the resident matrix (ca_eng_init.inc, ca_eng_score.inc; the engine's own buffers are dalloc's): what the call allocated,
-// freed when it returns -- on every path, after waiting for the stream (queued copies read the call's host vectors until then: declare the owner AFTER them).
-// A failed allocation or copy is kept in rc with the engine's message; later requests do nothing, so a block of requests is checked once.
+// The device memory of ONE CALL (ca_eng_init.inc, ca_eng_score.inc on an engine's stream; ca_gen_call of ca_eng_simulate.inc on its own; the engine's own buffers
+// are dalloc's): what the call allocated, freed when it returns -- on every path, after waiting for the stream (queued copies read the call's host vectors until
+// then: declare the owner AFTER them).  The first failed allocation or copy is kept in rc with its message in *err; later requests do nothing, so a block of
+// requests is checked once.  oom: the code for hipErrorOutOfMemory -- CA_ERR_HIP on an engine, as these calls have always reported it.
 struct ca_call_mem {
-  ca_engine* h;
+  hipStream_t stream;
+  std::string* err;
+  int oom;
   std::vector<void*> owned;
   int rc = CA_OK;
-  explicit ca_call_mem(ca_engine* h_) : h(h_) {}
+  ca_call_mem(hipStream_t stream_, std::string* err_, int oom_ = CA_ERR_HIP) : stream(stream_), err(err_), oom(oom_) {}
+  explicit ca_call_mem(ca_engine* h) : ca_call_mem(h->stream, &h->err) {}
   ca_call_mem(const ca_call_mem&) = delete;
   ca_call_mem& operator=(const ca_call_mem&) = delete;
-  ~ca_call_mem() {
-    if (!owned.empty()) hipStreamSynchronize(h->stream);
+  ~ca_call_mem() { release(); }
+  void release() {
+    if (!owned.empty()) hipStreamSynchronize(stream);
     for (void* p : owned) hipFree(p);
+    owned.clear();
   }
-  bool ok(hipError_t e, const char* what, size_t bytes) {
-    if (e == hipSuccess) return true;
-    h->err = std::string(what) + " of " + std::to_string(bytes) + " bytes: " + hipGetErrorString(e);
-    rc = CA_ERR_HIP;
-    return false;
+  bool note(hipError_t e, const std::string& what) {   // true while nothing has failed
+    if (e != hipSuccess && rc == CA_OK) {
+      *err = what + ": " + hipGetErrorString(e);
+      rc = e == hipErrorOutOfMemory ? oom : CA_ERR_HIP;
+    }
+    return rc == CA_OK;
   }
+  bool ok(hipError_t e, const char* what, size_t bytes) { return note(e, std::string(what) + " of " + std::to_string(bytes) + " bytes"); }
   template <typename T>
   T* alloc(int64_t count) {
     void* p = nullptr;
@@ -334,9 +342,9 @@ struct ca_call_mem {
     return static_cast<T*>(p);
   }
   template <typename T>
-  T* upload(const std::vector<T>& v) {   // (the copy is queued on h->stream)
+  T* upload(const std::vector<T>& v) {   // (the copy is queued on the stream)
     T* p = alloc<T>((int64_t)v.size());
-    if (p) ok(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, h->stream), "hipMemcpyAsync", v.size() * sizeof(T));
+    if (p) ok(hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream), "hipMemcpyAsync", v.size() * sizeof(T));
     return rc == CA_OK ? p : nullptr;
   }
 };

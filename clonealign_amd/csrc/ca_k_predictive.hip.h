@@ -4,8 +4,8 @@
 //   ll[n][r]      = lgamma(total_n + 1) - sum_g lgamma(y_g + 1) + sum over y_g > 0 of y_g (log E[g][c_n] + eta_g - m - log Z_n)      one float64 per (cell, replicate)
 //   T[r][c_n][g] += y_g                                                                                                              int64, integer atomics
 // One launch, k_predictive: A BLOCK OWNS A CELL and walks the batch's cells with the grid's stride.  Per cell:
-//   1. / 2. the shift m and the cumulative table, statement by statement k_simulate's steps 1 and 2 (sim_table below repeats them; k_simulate itself is left
-//      as it is), ONCE for all n_rep replicates -- the table costs G exp, as much as one replicate's draws at about 5000 counts per cell.  On the way
+//   1. / 2. the shift m and the cumulative table: k_simulate's own steps 1 and 2 (the routine both kernels call, in ca_k_simulate.hip.h), ONCE for all n_rep
+//      replicates -- the table costs G exp, as much as one replicate's draws at about 5000 counts per cell.  On the way
 //      log w_g = log E + eta_g - m (not log(exp(...))) goes to the block's slab in global memory: a thread reads back exactly the genes it wrote.
 //   per replicate:
 //   3. the draws of k_simulate over ALL the cell's Philox blocks b = j >> 1 (k_simulate's work items cut the same sequence at multiples of CA_SIM_SEG), the
@@ -19,84 +19,6 @@
 // Global scratch per block: G float64 of log w; with S > 1 G float64 of table; without an LDS histogram G int32 of counters (zeroed by the host once, kept
 // zero by step 4).  The counters in global memory are touched by atomics alone (add in step 3, exchange with 0 in step 4): they are served by L2, never by
 // a line of L1 that an atomic went past.
-
-// k_simulate's steps 1 and 2 for one cell: the table in co (LDS) and cg (S > 1), log w in lw; returns cum[G - 1].  Every thread of the block calls it.
-__device__ __forceinline__ double sim_table(const double* __restrict__ e, const double* __restrict__ u, const double* __restrict__ Vt, double* co, double* cg,
-                                            double* lw, double* x_sum, double* x_max, int G, int D, int S) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double m = -HUGE_VAL;
-  if (D > 0) {
-    for (int g = tid; g < G; g += CA_SIM_TB)
-      if (e[g] > 0.0) m = fmax(m, sim_eta(u, Vt, D, G, g));
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_xor(m, off));
-    if (lane == 0) x_max[wave] = m;
-    __syncthreads();
-    m = x_max[0];
-    for (int k = 1; k < CA_SIM_WAVES; ++k) m = fmax(m, x_max[k]);
-    __syncthreads();
-  } else {
-    m = 0.0;
-  }
-  double carry = 0.0, top = 0.0;
-  for (int base = 0; base < G; base += CA_SIM_TB) {
-    const int g = base + tid;
-    double w = 0.0;
-    if (g < G) {
-      const double eg = e[g];
-      double l = 0.0;
-      if (eg > 0.0) {
-        if (D > 0) {
-          const double x = sim_eta(u, Vt, D, G, g) - m;
-          w = eg * exp(x);
-          l = log(eg) + x;
-        } else {
-          w = eg;
-          l = log(eg);
-        }
-      }
-      lw[g] = l;
-    }
-    double s = w;
-    for (int off = 1; off < 64; off <<= 1) {
-      const double v = __shfl_up(s, off);
-      if (lane >= off) s += v;
-    }
-    if (lane == 63) x_sum[wave] = s;
-    __syncthreads();
-    double before = 0.0, all = 0.0;
-#pragma unroll 1
-    for (int k = 0; k < CA_SIM_WAVES; ++k) {
-      if (k == wave) before = all;
-      all += x_sum[k];
-    }
-    const double r = carry + (before + s);
-    carry += all;
-    double c = w > 0.0 ? r : 0.0;
-    for (int off = 1; off < 64; off <<= 1) {
-      const double v = __shfl_up(c, off);
-      if (lane >= off) c = fmax(c, v);
-    }
-    if (lane == 63) x_max[wave] = c;
-    __syncthreads();
-    double tile = top;
-#pragma unroll 1
-    for (int k = 0; k < CA_SIM_WAVES; ++k) {
-      if (k == wave) c = fmax(c, tile);
-      tile = fmax(tile, x_max[k]);
-    }
-    top = tile;
-    if (g < G) {
-      if (S == 1) {
-        co[g] = c;
-      } else {
-        cg[g] = c;
-        if (g % S == S - 1 || g == G - 1) co[g / S] = c;
-      }
-    }
-  }
-  __syncthreads();
-  return top;
-}
 
 // Waves per SIMD the register budget is set for: 8 = two blocks of 1024 threads per CU, k_simulate's residency (the draws wait on dependent LDS reads, which a
 // second block hides), at 64 registers and some scratch; 4 = one block per CU at up to 128 registers.  DESIGN section 7 has both forms' resource usage and times.
@@ -130,31 +52,22 @@ k_predictive(const double* __restrict__ Et /*[C][G]*/, const double* __restrict_
     }
     __syncthreads();   // the previous cell's table is no longer searched; the first cell: lgt and the zeroed histogram are complete
     const int cl = clone[cell];
-    const double cum_all = sim_table(Et + (size_t)cl * G, U + cell * D, Vt, co, cg, lw, x_sum, x_max, G, D, S);
+    const double cum_all = sim_table<true>(Et + (size_t)cl * G, U + cell * D, Vt, co, cg, lw, x_sum, x_max, G, D, S);
     const double t_max = __longlong_as_double(__double_as_longlong(cum_all) - 1);   // the largest double below cum[G - 1] (> 0: the host refused an all-zero clone)
     const double log_z = log(cum_all);
     const double lg_tot = ca_ll_lgamma1p((double)tot);
     const uint64_t q = q0 + (uint64_t)cell;
-    const uint32_t c1 = (uint32_t)q;
     const int64_t nblk = (tot + 1) >> 1;
     for (int r = 0; r < n_rep; ++r) {
-      const uint64_t draw = draw0 + (uint64_t)r;
-      const uint32_t c2 = (uint32_t)draw, c3 = (uint32_t)((draw >> 32) & 0xFFFFu) | ((uint32_t)(q >> 32) << 16);
+      const sim_ctr ctr = sim_counter(q, draw0 + (uint64_t)r);
       // 3. the draws (k_simulate's step 3 / 4 over every Philox block of the cell)
       for (int64_t i = tid; i < nblk; i += CA_SIM_TB) {
         uint32_t r4[4];
-        sim_philox((uint32_t)i, c1, c2, c3, k0, k1, r4);
+        sim_philox((uint32_t)i, ctr.c1, ctr.c2, ctr.c3, k0, k1, r4);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           if (2 * i + h >= tot) break;
-          const uint64_t x = ((uint64_t)r4[2 * h + 1] << 21) | (uint64_t)(r4[2 * h] >> 11);
-          const double uu = ((double)x + 0.5) * 0x1p-53;
-          const double t = fmin(uu * cum_all, t_max);
-          int g = sim_search(co, nco, t);
-          if (S > 1) {
-            const int gb = g * S;
-            g = gb + sim_search(cg + gb, (G - gb < S) ? G - gb : S, t);
-          }
+          const int g = sim_gene(r4[2 * h], r4[2 * h + 1], cum_all, t_max, co, nco, cg, G, S);
           if (hist_lds) atomicAdd(&hist[g], 1);
           else atomicAdd(&row[g], 1);
         }

@@ -17,6 +17,7 @@
 //      else in this library (fixed order, no atomics), the order of arrival is not observable here.  The histogram is then stored (the cell's only item) or
 //      added to the zeroed row (one of several items).
 // LDS per block: 8 * ceil(G / S) + 4 * G (histogram, when it fits) <= CA_SIM_LDS bytes; S and the histogram's place are the host's pick (sim_plan).
+// Steps 1 and 2 (sim_table) and one draw of step 3 (sim_counter, sim_gene) are routines of this file that k_predictive (ca_k_predictive.hip.h) calls too.
 
 #define CA_SIM_TB 1024        // threads per block: two blocks fill a CU's 32 waves at the LDS budget below
 #define CA_SIM_SEG 16384      // draws per work item (even: an item starts on a Philox block)
@@ -60,25 +61,33 @@ __device__ __forceinline__ int sim_search(const double* tab, int len, double t) 
   return lo;
 }
 
-__global__ void __launch_bounds__(CA_SIM_TB)
-k_simulate(const double* __restrict__ Et /*[C][G]*/, const double* __restrict__ Vt /*[D][G]*/, const double* __restrict__ U /*[cells][D]*/,
-           const int32_t* __restrict__ clone /*[cells]*/, const int64_t* __restrict__ total /*[cells]*/, const ca_sim_item* __restrict__ items,
-           double* cumg /*[cells][G] when S > 1*/, int32_t* Y /*[cells][G], zeroed*/, int G, int D, int S, int nco, int hist_lds,
-           uint32_t k0, uint32_t k1, uint64_t draw, uint64_t q0 /* global index of the batch's first cell */) {
-  extern __shared__ double sim_sm[];
-  __shared__ double x_sum[CA_SIM_WAVES], x_max[CA_SIM_WAVES];
-  double* co = sim_sm;                                        // [nco]: cum[min((k + 1) S, G) - 1]
-  int* hist = reinterpret_cast<int*>(sim_sm + nco);           // [G] when hist_lds
-  const ca_sim_item it = items[blockIdx.x];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t cell = it.cell;
-  const double* __restrict__ e = Et + (size_t)clone[cell] * G;
-  double* cg = cumg ? cumg + (size_t)cell * G : nullptr;
-  int32_t* yrow = Y + (size_t)cell * G;
-  const double* __restrict__ u = U + cell * D;
+// The Philox counter words of cell q's draws at stream `draw`; word 0 is the block index b = j >> 1, filled in by the caller's loop.
+struct sim_ctr { uint32_t c1, c2, c3; };
+__device__ __forceinline__ sim_ctr sim_counter(uint64_t q, uint64_t draw) {
+  return sim_ctr{(uint32_t)q, (uint32_t)draw, (uint32_t)((draw >> 32) & 0xFFFFu) | ((uint32_t)(q >> 32) << 16)};
+}
 
-  // (Steps 1 and 2 are repeated statement by statement in sim_table of ca_k_predictive.hip.h, whose replicate rows must be these rows bit for bit: a change
-  // here is made there too; tests/test_gpu_predictive.py compares the two.)
+// Step 3 for one draw: the gene of the 64-bit half (lo, hi) of a Philox block -- u on 53 bits, t = min(u cum[G - 1], t_max), the search in co (LDS) and,
+// with S > 1, in the gene's S-gene group of cg.
+__device__ __forceinline__ int sim_gene(uint32_t lo, uint32_t hi, double cum_all, double t_max, const double* co, int nco, const double* cg, int G, int S) {
+  const uint64_t x = ((uint64_t)hi << 21) | (uint64_t)(lo >> 11);
+  const double uu = ((double)x + 0.5) * 0x1p-53;
+  const double t = fmin(uu * cum_all, t_max);
+  int g = sim_search(co, nco, t);
+  if (S > 1) {
+    const int gb = g * S;
+    g = gb + sim_search(cg + gb, (G - gb < S) ? G - gb : S, t);
+  }
+  return g;
+}
+
+// Steps 1 and 2 for one cell, called by every thread of a CA_SIM_TB block: the table in co (LDS) and cg (S > 1); returns cum[G - 1].  k_simulate and k_predictive
+// both draw from THIS table, which is what makes the latter's replicate rows the former's rows bit for bit.  LW: log w_g = log E + eta_g - m also goes to lw
+// (k_predictive's statistic; w itself has the same bits either way).
+template <bool LW>
+__device__ __forceinline__ double sim_table(const double* __restrict__ e, const double* __restrict__ u, const double* __restrict__ Vt, double* co, double* cg,
+                                            double* lw, double* x_sum, double* x_max, int G, int D, int S) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // 1. the shift: the largest exponent over the genes that can be drawn
   double m = -HUGE_VAL;
   if (D > 0) {
@@ -93,9 +102,6 @@ k_simulate(const double* __restrict__ Et /*[C][G]*/, const double* __restrict__ 
   } else {
     m = 0.0;
   }
-  if (hist_lds)
-    for (int g = tid; g < G; g += CA_SIM_TB) hist[g] = 0;
-
   // 2. weights, their inclusive scan and the running maximum that makes it a table
   double carry = 0.0, top = 0.0;   // block-uniform: the sum and the table value before this tile
   for (int base = 0; base < G; base += CA_SIM_TB) {
@@ -103,7 +109,22 @@ k_simulate(const double* __restrict__ Et /*[C][G]*/, const double* __restrict__ 
     double w = 0.0;
     if (g < G) {
       const double eg = e[g];
-      if (eg > 0.0) w = D > 0 ? eg * exp(sim_eta(u, Vt, D, G, g) - m) : eg;
+      if (LW) {
+        double l = 0.0;
+        if (eg > 0.0) {
+          if (D > 0) {
+            const double x = sim_eta(u, Vt, D, G, g) - m;
+            w = eg * exp(x);
+            l = log(eg) + x;
+          } else {
+            w = eg;
+            l = log(eg);
+          }
+        }
+        lw[g] = l;
+      } else if (eg > 0.0) {
+        w = D > 0 ? eg * exp(sim_eta(u, Vt, D, G, g) - m) : eg;
+      }
     }
     double s = w;
     for (int off = 1; off < 64; off <<= 1) {
@@ -143,32 +164,45 @@ k_simulate(const double* __restrict__ Et /*[C][G]*/, const double* __restrict__ 
       }
     }
   }
-  __syncthreads();   // the table (LDS, and this block's own stores to its cell's slab) and the zeroed histogram are complete
+  __syncthreads();   // the table (LDS, and this block's own stores to its cell's slab) is complete
+  return top;
+}
+
+__global__ void __launch_bounds__(CA_SIM_TB)
+k_simulate(const double* __restrict__ Et /*[C][G]*/, const double* __restrict__ Vt /*[D][G]*/, const double* __restrict__ U /*[cells][D]*/,
+           const int32_t* __restrict__ clone /*[cells]*/, const int64_t* __restrict__ total /*[cells]*/, const ca_sim_item* __restrict__ items,
+           double* cumg /*[cells][G] when S > 1*/, int32_t* Y /*[cells][G], zeroed*/, int G, int D, int S, int nco, int hist_lds,
+           uint32_t k0, uint32_t k1, uint64_t draw, uint64_t q0 /* global index of the batch's first cell */) {
+  extern __shared__ double sim_sm[];
+  __shared__ double x_sum[CA_SIM_WAVES], x_max[CA_SIM_WAVES];
+  double* co = sim_sm;                                        // [nco]: cum[min((k + 1) S, G) - 1]
+  int* hist = reinterpret_cast<int*>(sim_sm + nco);           // [G] when hist_lds
+  const ca_sim_item it = items[blockIdx.x];
+  const int tid = threadIdx.x;
+  const int64_t cell = it.cell;
+  double* cg = cumg ? cumg + (size_t)cell * G : nullptr;
+  int32_t* yrow = Y + (size_t)cell * G;
+
+  if (hist_lds)
+    for (int g = tid; g < G; g += CA_SIM_TB) hist[g] = 0;
+  // 1. / 2. the shift and the table (its closing barrier also completes the zeroed histogram)
+  const double cum_all = sim_table<false>(Et + (size_t)clone[cell] * G, U + cell * D, Vt, co, cg, nullptr, x_sum, x_max, G, D, S);
 
   // 3. / 4. the draws
   const int64_t tot = total[cell];
   const int64_t left = tot - (int64_t)it.j_lo;
   const int cnt = (int)(left < CA_SIM_SEG ? left : CA_SIM_SEG);
   const bool only = tot <= CA_SIM_SEG;
-  const double cum_all = top;
   const double t_max = __longlong_as_double(__double_as_longlong(cum_all) - 1);   // the largest double below cum[G - 1] (> 0: the host refused an all-zero clone)
-  const uint64_t q = q0 + (uint64_t)cell;
-  const uint32_t c1 = (uint32_t)q, c2 = (uint32_t)draw, c3 = (uint32_t)((draw >> 32) & 0xFFFFu) | ((uint32_t)(q >> 32) << 16);
+  const sim_ctr ctr = sim_counter(q0 + (uint64_t)cell, draw);
   const int nblk = (cnt + 1) >> 1;
   for (int i = tid; i < nblk; i += CA_SIM_TB) {
     uint32_t r4[4];
-    sim_philox((it.j_lo >> 1) + (uint32_t)i, c1, c2, c3, k0, k1, r4);
+    sim_philox((it.j_lo >> 1) + (uint32_t)i, ctr.c1, ctr.c2, ctr.c3, k0, k1, r4);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       if (2 * i + h >= cnt) break;
-      const uint64_t x = ((uint64_t)r4[2 * h + 1] << 21) | (uint64_t)(r4[2 * h] >> 11);
-      const double uu = ((double)x + 0.5) * 0x1p-53;
-      const double t = fmin(uu * cum_all, t_max);
-      int g = sim_search(co, nco, t);
-      if (S > 1) {
-        const int gb = g * S;
-        g = gb + sim_search(cg + gb, (G - gb < S) ? G - gb : S, t);
-      }
+      const int g = sim_gene(r4[2 * h], r4[2 * h + 1], cum_all, t_max, co, nco, cg, G, S);
       if (hist_lds) atomicAdd(&hist[g], 1);
       else atomicAdd(&yrow[g], 1);
     }

@@ -1070,33 +1070,48 @@ def allele_loglik(clone_allele, cov, ref, device=0, layout="row"):
     return out
 
 
+def _model_operands(what, E, V, U, clone, total):
+    """The model arguments the handle-free generative calls share, as the library reads them: ``(E, V, U, clone, total, N, G, Cn, D)`` with C-contiguous float64
+    ``E`` [G, Cn], int32 ``clone`` [N] and int64 ``total`` [N] (a scalar is every cell's); ``V`` [G, D] and ``U`` [N, D] float64, or both None where D = 0."""
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"{what}: E is {E.shape}; expected (genes, clones)")
+    G, Cn = E.shape
+    clone = np.ascontiguousarray(clone, dtype=np.int32).reshape(-1)
+    N = clone.shape[0]
+    total = np.ascontiguousarray(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
+    if (U is None) != (V is None):
+        raise ValueError(f"{what}: U and V go together (both, or neither)")
+    D = 0
+    if U is not None:
+        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"{what}: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
+        D = int(U.shape[1])
+    if D == 0:
+        U = V = None
+    return E, V, U, clone, total, N, G, Cn, D
+
+
+def _last_kernel_ms(symbol):
+    ms = C.c_double(0.0)
+    getattr(load_library(), symbol)(C.byref(ms))
+    return ms.value
+
+
 def simulate_counts(E, V, U, clone, total, seed, draw=0, cell_offset=0, device=0, out=None):
     """Count rows drawn from a fitted model on the device (ca_simulate_counts; include/clonealign_hip.h has the sampler): ``y_n ~ Multinomial(total[n],
     p_n)``, ``p_ng ~ E[g, clone[n]] exp(U[n] . V[g])``.  ``E`` [G, C]; ``V`` [G, D] and ``U`` [N, D], or both None; ``clone`` [N] in [0, C); ``total`` [N].
     Returns int32 [N, G] (``out``: a C-contiguous int32 [N, G] array to fill instead).  Row n depends on (seed, draw, cell_offset + n) and its own
     arguments alone, so splitting the cells over calls (or devices) with ``cell_offset`` gives the same bits.  Refusals raise EngineError."""
     lib = load_library()
-    E = np.ascontiguousarray(E, dtype=np.float64)
-    if E.ndim != 2:
-        raise ValueError(f"simulate_counts: E is {E.shape}; expected (genes, clones)")
-    G, Cn = E.shape
-    clone = np.ascontiguousarray(clone, dtype=np.int32).reshape(-1)
-    N = clone.shape[0]
-    total = np.ascontiguousarray(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
-    D = 0
-    if (U is None) != (V is None):
-        raise ValueError("simulate_counts: U and V go together (both, or neither)")
-    if U is not None:
-        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
-        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
-            raise ValueError(f"simulate_counts: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
-        D = int(U.shape[1])
+    E, V, U, clone, total, N, G, Cn, D = _model_operands("simulate_counts", E, V, U, clone, total)
     if out is None:
         out = np.zeros((N, G), dtype=np.int32)
     elif out.dtype != np.int32 or out.shape != (N, G) or not out.flags.c_contiguous:
         raise ValueError(f"simulate_counts: out must be a C-contiguous int32 array of shape ({N}, {G})")
     err = C.create_string_buffer(256)
-    rc = lib.ca_simulate_counts(N, G, Cn, D, _ptr(E), _ptr(V) if D > 0 else None, _ptr(U) if D > 0 else None, _ptr(clone), _ptr(total),
+    rc = lib.ca_simulate_counts(N, G, Cn, D, _ptr(E), _ptr(V), _ptr(U), _ptr(clone), _ptr(total),
                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw) & 0xFFFFFFFFFFFFFFFF, int(cell_offset), int(device), _ptr(out), err)
     if rc != CA_OK:
         raise EngineError(rc, err.value.decode() or "ca_simulate_counts")
@@ -1105,9 +1120,7 @@ def simulate_counts(E, V, U, clone, total, seed, draw=0, cell_offset=0, device=0
 
 def simulate_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``simulate_counts`` call took (HIP events around each launch)."""
-    ms = C.c_double(0.0)
-    load_library().ca_simulate_kernel_ms(C.byref(ms))
-    return ms.value
+    return _last_kernel_ms("ca_simulate_kernel_ms")
 
 
 def predictive_stats(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=0, device=0, gene_totals=True, out=None):
@@ -1118,21 +1131,7 @@ def predictive_stats(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=
     of these shapes and dtypes to fill instead (the second None without totals).  ``ll_rep[n, r]`` depends on (seed, draw0 + r, cell_offset + n) and the
     cell's own arguments alone; ``T_rep`` of cells split over calls adds up.  Refusals raise EngineError."""
     lib = load_library()
-    E = np.ascontiguousarray(E, dtype=np.float64)
-    if E.ndim != 2:
-        raise ValueError(f"predictive_stats: E is {E.shape}; expected (genes, clones)")
-    G, Cn = E.shape
-    clone = np.ascontiguousarray(clone, dtype=np.int32).reshape(-1)
-    N = clone.shape[0]
-    total = np.ascontiguousarray(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
-    D = 0
-    if (U is None) != (V is None):
-        raise ValueError("predictive_stats: U and V go together (both, or neither)")
-    if U is not None:
-        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
-        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
-            raise ValueError(f"predictive_stats: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
-        D = int(U.shape[1])
+    E, V, U, clone, total, N, G, Cn, D = _model_operands("predictive_stats", E, V, U, clone, total)
     n_rep = int(n_rep)
     if not -2 ** 31 <= n_rep < 2 ** 31:
         raise ValueError(f"predictive_stats: n_rep = {n_rep} does not fit 32 bits")
@@ -1146,7 +1145,7 @@ def predictive_stats(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=
         if T is not None and (T.dtype != np.int64 or T.shape != (R, G, Cn) or not T.flags.c_contiguous):
             raise ValueError(f"predictive_stats: out[1] must be None or a C-contiguous int64 array of shape ({R}, {G}, {Cn})")
     err = C.create_string_buffer(256)
-    rc = lib.ca_predictive_stats(N, G, Cn, D, _ptr(E), _ptr(V) if D > 0 else None, _ptr(U) if D > 0 else None, _ptr(clone), _ptr(total),
+    rc = lib.ca_predictive_stats(N, G, Cn, D, _ptr(E), _ptr(V), _ptr(U), _ptr(clone), _ptr(total),
                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0) & 0xFFFFFFFFFFFFFFFF, n_rep, int(cell_offset), int(device), _ptr(ll), _ptr(T), err)
     if rc != CA_OK:
         raise EngineError(rc, err.value.decode() or "ca_predictive_stats")
@@ -1155,9 +1154,7 @@ def predictive_stats(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=
 
 def predictive_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``predictive_stats`` call took (HIP events around each launch)."""
-    ms = C.c_double(0.0)
-    load_library().ca_predictive_kernel_ms(C.byref(ms))
-    return ms.value
+    return _last_kernel_ms("ca_predictive_kernel_ms")
 
 
 def predictive_moments(E, V, U, clone, total, device=0):
@@ -1167,25 +1164,11 @@ def predictive_moments(E, V, U, clone, total, device=0):
     clone (float64 [G, C]).  The cell values depend on the cell's own arguments alone; the tables of cells split over calls add up to within rounding.
     Refusals raise EngineError."""
     lib = load_library()
-    E = np.ascontiguousarray(E, dtype=np.float64)
-    if E.ndim != 2:
-        raise ValueError(f"predictive_moments: E is {E.shape}; expected (genes, clones)")
-    G, Cn = E.shape
-    clone = np.ascontiguousarray(clone, dtype=np.int32).reshape(-1)
-    N = clone.shape[0]
-    total = np.ascontiguousarray(np.broadcast_to(np.asarray(total, dtype=np.int64), (N,)))
-    D = 0
-    if (U is None) != (V is None):
-        raise ValueError("predictive_moments: U and V go together (both, or neither)")
-    if U is not None:
-        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
-        if U.ndim != 2 or V.ndim != 2 or U.shape[0] != N or V.shape[0] != G or U.shape[1] != V.shape[1]:
-            raise ValueError(f"predictive_moments: U is {U.shape} and V is {V.shape}; expected ({N}, D) and ({G}, D)")
-        D = int(U.shape[1])
+    E, V, U, clone, total, N, G, Cn, D = _model_operands("predictive_moments", E, V, U, clone, total)
     cell = np.zeros((2, max(N, 1)), dtype=np.float64)                # (never an empty buffer: the call wants five pointers also without cells)
     T = np.zeros((3, G, Cn), dtype=np.float64)
     err = C.create_string_buffer(256)
-    rc = lib.ca_predictive_moments(N, G, Cn, D, _ptr(E), _ptr(V) if D > 0 else None, _ptr(U) if D > 0 else None, _ptr(clone), _ptr(total), int(device),
+    rc = lib.ca_predictive_moments(N, G, Cn, D, _ptr(E), _ptr(V), _ptr(U), _ptr(clone), _ptr(total), int(device),
                                    _ptr(cell[0]), _ptr(cell[1]), _ptr(T[0]), _ptr(T[1]), _ptr(T[2]), err)
     if rc != CA_OK:
         raise EngineError(rc, err.value.decode() or "ca_predictive_moments")
@@ -1194,9 +1177,7 @@ def predictive_moments(E, V, U, clone, total, device=0):
 
 def predictive_moments_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``predictive_moments`` call took (HIP events around each launch; 0 without factors)."""
-    ms = C.c_double(0.0)
-    load_library().ca_predictive_moments_kernel_ms(C.byref(ms))
-    return ms.value
+    return _last_kernel_ms("ca_predictive_moments_kernel_ms")
 
 
 _NP_DTYPE = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2, np.dtype(np.uint16): 3, np.dtype(np.uint8): 4}
