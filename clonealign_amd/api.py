@@ -627,6 +627,173 @@ def assignment_support(fit, Y, L, blocks, clone_assignment_probability=0.95, *, 
     return base
 
 
+def bootstrap_gene_weights(G, n_rep, *, seed=0, blocks=None):
+    """Gene weights of ``n_rep`` bootstrap replicates, [n_rep, G] float64: how often each gene was drawn when G genes are resampled with replacement
+    (a row is ``Multinomial(G, 1/G)`` and sums to G).  With ``blocks`` (a length-G labelling as for ``clone_loglik_by_block``: chromosome arms, copy-number
+    segments) WHOLE BLOCKS are drawn with replacement, as many draws as there are blocks, and a gene carries its block's count: the genes of a copy-number
+    segment move together and are not independent evidence.  The draws come from the counter-based generator of ``rng`` (``rng.index_draw``), stream =
+    replicate, so a replicate's weights depend on ``(seed, replicate)`` alone -- the same bits on every run, and the first rows of a larger ``n_rep``."""
+    from . import rng
+    G, n_rep = int(G), int(n_rep)
+    if G < 1 or n_rep < 0:
+        raise ValueError(f"bootstrap_gene_weights: G = {G} and n_rep = {n_rep}; expected G >= 1 and n_rep >= 0")
+    if blocks is None:
+        B, bg = G, np.arange(G)
+    else:
+        names, bg = _block_labels(blocks, G)
+        B = len(names)
+    w = np.empty((n_rep, G), dtype=np.float64)
+    for r in range(n_rep):
+        w[r] = np.bincount(rng.index_draw(seed, r, B, B), minlength=B).astype(np.float64)[bg]
+    return w
+
+
+def _reweighted_weights(weights, G, what="clone_loglik_reweighted"):
+    """The replicate weights of a reweighted call as [R, G] float64 after the library's refusals (ValueError names the offender)."""
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+    if w.ndim != 2 or w.shape[1] != G:
+        raise ValueError(f"{what}: weights is {w.shape}; expected (R, {G})")
+    if w.shape[0] < 1:
+        raise ValueError(f"{what}: R = {w.shape[0]} replicates is below 1")
+    wrong = np.argwhere(~np.isfinite(w) | (w < 0))
+    if wrong.size:
+        raise ValueError(f"{what}: the weights have a negative or non-finite entry (replicate {wrong[0][0]}, gene {wrong[0][1]})")
+    wrong = np.flatnonzero(~(w > 0).any(1))
+    if wrong.size:
+        raise ValueError(f"{what}: the weights of replicate {wrong[0]} are all zero (genes 0 .. {G - 1})")
+    return w
+
+
+def _clone_loglik_reweighted_host(Y, E, U, V, weights, log_prior=None, cells=None, want_ll=True, chunk=256, with_scale=False):
+    """Float64 host form of ``HipEngine.clone_loglik_reweighted`` for engines without it, and its yardstick: Y [N, G] dense or scipy.sparse (densified
+    ``chunk`` cells at a time), E [G, C], U [N, D] and V [G, D] or both None, ``weights`` [R, G], ``log_prior`` [N, C] / [1, C] or None.  Same return value
+    and rules: ``ll_r = sum_g w_rg xlogy(y, E) - s_r log sum_g w_rg E exp(eta)`` (no ``sum w y eta``, no lgamma constant: the same for every clone),
+    ``-inf`` exactly where a positive count with a positive weight meets ``E = 0``, 0 where ``s_r = 0``, no NaN; ``votes`` by ``np.argmax`` of
+    ``ll_r + log_prior``; a replicate with every clone at ``-inf`` adds nothing to ``prob_sum`` / ``prob_sq``.  ``with_scale``: also ``"scale"``
+    [n, R, C], the sum of the terms' magnitudes (the tests' bar)."""
+    E, U, V, D, _esum = _ll_inputs(Y, E, U, V, "clone_loglik_reweighted")
+    N, G = Y.shape
+    C = E.shape[1]
+    W = _reweighted_weights(weights, G)
+    R = W.shape[0]
+    lo0, hi0 = (0, N) if cells is None else (int(cells[0]), int(cells[1]))
+    if lo0 < 0 or hi0 < lo0 or hi0 > N:
+        raise ValueError(f"clone_loglik_reweighted: the cell range [{lo0}, {lo0} + {hi0 - lo0}) is outside [0, {N}]")
+    n = hi0 - lo0
+    lp = None if log_prior is None else np.broadcast_to(np.asarray(log_prior, dtype=np.float64), (N, C))
+    if lp is not None and (np.isnan(lp) | (lp == np.inf)).any():
+        r, c = np.argwhere(np.isnan(lp) | (lp == np.inf))[0]
+        raise ValueError(f"clone_loglik_reweighted: log_prior has a NaN or +inf entry (cell {r}, clone {c}); -inf excludes a clone")
+    zero = E == 0
+    logE = np.log(np.where(zero, 1.0, E))
+    B1 = (W.T[:, :, None] * logE[:, None, :]).reshape(G, R * C)
+    Bz = ((W.T > 0)[:, :, None] & zero[:, None, :]).astype(np.float64).reshape(G, R * C)
+    B2 = (W.T[:, :, None] * E[:, None, :]).reshape(G, R * C)
+    with np.errstate(divide="ignore"):
+        logz0 = np.log(W @ E)[None]                                    # D = 0: [1, R, C]
+    out = {"votes": np.zeros((n, C), dtype=np.int32), "prob_sum": np.zeros((n, C)), "prob_sq": np.zeros((n, C)), "reads": np.empty((n, R)),
+           "ll": np.empty((n, R, C)) if want_ll else None}
+    if with_scale:
+        out["scale"] = np.empty((n, R, C))
+    Ys = Y[lo0:hi0]
+    Us = None if D == 0 else U[lo0:hi0]
+    for lo, Yc, eta, _m, _lz in _cell_chunks(Ys, chunk, None, Us, V):
+        k = Yc.shape[0]
+        s = Yc @ W.T                                                   # [k, R]
+        a = (Yc @ B1).reshape(k, R, C)
+        ninf = ((Yc > 0).astype(np.float64) @ Bz).reshape(k, R, C) > 0
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            if D > 0:
+                m = eta.max(1)
+                logz = m[:, None, None] + np.log((np.exp(eta - m[:, None]) @ B2).reshape(k, R, C))
+            else:
+                logz = np.broadcast_to(logz0, (k, R, C))
+            pos = (s > 0)[:, :, None]
+            ll = np.where(ninf, -np.inf, np.where(pos, a - s[:, :, None] * np.where(pos, logz, 0.0), 0.0))
+            t = ll if lp is None else ll + lp[lo0 + lo:lo0 + lo + k, None, :]
+            mx = t.max(2, keepdims=True)
+            alive = ~np.isneginf(mx)
+            e = np.where(t == mx, 1.0, np.exp(t - np.where(alive, mx, 0.0)))
+            p = np.where(alive, e / e.sum(2, keepdims=True), 0.0)
+        best = np.argmax(t, axis=2)                                    # [k, R]
+        out["votes"][lo:lo + k] = (best[:, :, None] == np.arange(C)).sum(1)
+        out["prob_sum"][lo:lo + k] = p.sum(1)
+        out["prob_sq"][lo:lo + k] = (p * p).sum(1)
+        out["reads"][lo:lo + k] = s
+        if want_ll:
+            out["ll"][lo:lo + k] = ll
+        if with_scale:
+            with np.errstate(invalid="ignore"):
+                out["scale"][lo:lo + k] = (Yc @ np.abs(B1)).reshape(k, R, C) + s[:, :, None] * np.where(np.isfinite(logz), np.abs(logz), 0.0)
+    return out
+
+
+def _reweighted_call(engine, Y, t, weights, log_prior, cells, want_ll):
+    """The cells ``cells`` under the tables ``t`` through the engine's ``clone_loglik_reweighted``, or through the host form when it has none."""
+    if hasattr(engine, "clone_loglik_reweighted"):
+        return engine.clone_loglik_reweighted(t.E, t.U, t.V, weights, log_prior=log_prior, cells=cells, want_ll=want_ll)
+    return _clone_loglik_reweighted_host(Y, t.E, t.U, t.V, weights, log_prior=log_prior, cells=cells, want_ll=want_ll)
+
+
+def clone_loglik_reweighted(fit, Y, L, weights, *, x=None, psi=None, saturate=True, saturation_threshold=6, extra_loglik=None, cells=None, want_ll=True,
+                            engine=None, engine_opts=None):
+    """``clone_loglik`` with the genes REWEIGHTED, for every row of ``weights`` [R, genes] at once (``bootstrap_gene_weights`` makes them): the replicates of
+    a bootstrap over genes, all in two float64 matrix products against the resident matrix (``HipEngine.clone_loglik_reweighted``).
+    ``ll_r[n, c] = sum_g w_rg xlogy(y_ng, E_gc) - s_r[n] log sum_g w_rg E_gc exp(eta_ng)`` with ``s_r[n] = sum_g w_rg y_ng``: for integer weights
+    ``clone_loglik(const=False)`` of the matrix with gene g repeated ``w_rg`` times, minus ``sum_g w_rg y_ng eta_ng`` -- that term and the lgamma constant are
+    the same for every clone of a cell and are left out.  ``fit``, ``Y``, ``L``, ``x``, ``psi``, ``saturate``, ``engine`` as for ``clone_loglik``;
+    ``extra_loglik`` [cells, clones] (all cells of ``Y``) joins ``log alpha`` in the prior; ``cells`` = ``(lo, hi)`` restricts the call to that range.
+    Returns a dict: ``votes`` [n, C] int32 (replicates whose argmax of ``ll_r + log alpha + extra_loglik`` is c), ``prob_sum`` and ``prob_sq`` [n, C]
+    (sums over the replicates of the posterior and of its square), ``reads`` [n, R] (``s_r``), ``ll`` [n, R, C] (None unless ``want_ll``).  A positive
+    count with a positive weight against copy number 0 gives exactly ``-inf``; ``s_r = 0`` gives ``ll_r = 0``; no NaN.  An engine without
+    ``clone_loglik_reweighted`` gets the chunked float64 host form."""
+    Y, L, _cn, N, G = _cells_and_cnv(Y, L)
+    t = _fit_tables(fit, L, N, x, psi, saturate, saturation_threshold)
+    C = t.L.shape[1]
+    w = _reweighted_weights(weights, G)
+    prior = np.ascontiguousarray(np.broadcast_to(_log_prior(fit, extra_loglik, N, C), (N, C)))
+    with _engine_lease(engine, "clone_loglik_reweighted", Y, t.L, engine_opts) as eng:
+        return _reweighted_call(eng, Y, t, w, prior, cells, want_ll)
+
+
+def bootstrap_assignments(fit, Y, L, n_rep=100, clone_assignment_probability=0.95, support_threshold=0.95, *, seed=0, blocks=None, weights=None,
+                          extra_loglik=None, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, engine=None, engine_opts=None):
+    """``assign_cells`` with BOOTSTRAP SUPPORT for every call: the genes are resampled with replacement ``n_rep`` times (``bootstrap_gene_weights``; whole
+    ``blocks`` when given; or the caller's ``weights`` [R, genes]), every replicate is called again, and a cell's support is the share of replicates that
+    repeat its call -- what phylogenetics does with sites.  A multinomial over thousands of genes pushes almost every posterior to 0.999...; when the
+    counts are overdispersed many of those calls are wrong, and their support is visibly lower.  One upload: a throwaway engine serves both calls, and all
+    replicates are one ``clone_loglik_reweighted`` on the device.  Every other argument as for ``assign_cells``.
+
+    Returns a :class:`ClonealignFit` that holds everything ``assign_cells`` returns, identically, plus: ``support`` [N] (the share of replicates whose
+    argmax is the cell's own -- the argmax of ``ll + log alpha + extra_loglik`` on the full data), ``clone_support`` [N, C] (the share per clone),
+    ``mean_probs`` and ``sd_probs`` [N, C] (mean and standard deviation of the replicates' posteriors), ``clone_bootstrap`` (``clone``, or
+    ``"unassigned"`` where ``support < support_threshold``), ``n_newly_unassigned`` (calls that ``clone`` makes and ``clone_bootstrap`` withholds),
+    ``weights_seed`` (``seed``; None with the caller's ``weights``) and ``n_rep``."""
+    Y, Lm, _cn, N, G = _cells_and_cnv(Y, L)
+    ft = _fit_tables(fit, Lm, N, x, psi, saturate, saturation_threshold)
+    C = ft.L.shape[1]
+    own = weights is None
+    w = _reweighted_weights(bootstrap_gene_weights(G, n_rep, seed=seed, blocks=blocks) if own else weights, G, "bootstrap_assignments")
+    R = w.shape[0]
+    prior = np.ascontiguousarray(np.broadcast_to(_log_prior(fit, extra_loglik, N, C), (N, C)))
+    with _engine_lease(engine, "clone_loglik_reweighted", Y, ft.L, engine_opts) as eng:
+        ll = eng.clone_loglik(ft.E, ft.U, ft.V, const=const) if hasattr(eng, "clone_loglik") else _clone_loglik_host(Y, ft.E, ft.U, ft.V, const=const)
+        rw = _reweighted_call(eng, Y, ft, w, prior, None, False)
+    base = _assign_from_loglik(fit, ll, ft.L, extra_loglik, clone_assignment_probability)   # (the parsed L: a DataFrame's column names do not name the clones here)
+    with np.errstate(invalid="ignore"):
+        t = ll + prior
+    cstar = np.argmax(np.where(np.isnan(t), -np.inf, t), axis=1)
+    clone_support = rw["votes"] / float(R)
+    support = clone_support[np.arange(N), cstar]
+    mean = rw["prob_sum"] / R
+    sd = np.sqrt(np.maximum(rw["prob_sq"] / R - mean * mean, 0.0))
+    clone = np.asarray(base["clone"], dtype=object)
+    boot = np.where(support >= support_threshold, clone, "unassigned").astype(object)
+    base.update(support=support, clone_support=clone_support, mean_probs=mean, sd_probs=sd, clone_bootstrap=boot,
+                n_newly_unassigned=int(((clone != "unassigned") & (boot == "unassigned")).sum()), weights_seed=int(seed) if own else None, n_rep=int(R))
+    return base
+
+
 def _pair_weights(weights, what="clone_pair_loglik", limit=8):
     """The mixture weights of a pair call: 1 to 8 finite values in the open interval (0, 1) (ValueError names the offender otherwise)."""
     w = np.asarray(weights, dtype=np.float64).reshape(-1)

@@ -380,6 +380,59 @@ int launch_dm_ll(ca_engine* h, const ca_dml_ops& o) {
   if (h->ystore == CA_YSTORE_U16) return dm_ll_t<uint16_t>(h, o);
   return dm_ll_t<float>(h, o);
 }
+// ---- k_boot_build / k_boot_prod<YT, EXPSRC, NT> / k_boot_zero<YT> / k_boot_finish / k_boot_reduce: one chunk of replicates of ca_clone_loglik_reweighted on one batch of cells (never the 4-bit loop image) ----
+// the call's weights [R][G], E compact and the padded factors; the chunk's right-hand sides (B1: nc1 columns, B2: nc2, Z0 at D = 0) for the replicates
+// [r0, r0 + rc); the batch's slabs and outputs; the list of genes with a zero of E and its masks (nz entries of nw words; flags holds rcp replicates a cell)
+struct ca_boot_ops { const double *W, *Ec, *Ut, *Vt; double *B1, *B2, *Z0, *part, *zpart, *mpart, *llb, *sb; const int* zg; const unsigned* zm; unsigned* flags;
+                     int64_t n_lo, n_cnt; int r0, rc, rcp, nw, nz, D, nzc, nc1, nc2; };
+int launch_boot_build(ca_engine* h, const ca_boot_ops& o) {
+  const int nb_tab = cdiv((int64_t)h->Gp * (o.nc1 + (o.D > 0 ? o.nc2 : 0)), CA_TB), nb_z0 = o.D > 0 ? 0 : cdiv((int64_t)o.rc * h->C, CA_TB);
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_boot_build, dim3((unsigned)(nb_tab + nb_z0)), dim3(CA_TB), 0, h->stream, o.Ec, o.W, o.B1, o.D > 0 ? o.B2 : nullptr, o.Z0, o.r0, o.rc,
+                                                h->G, h->Gp, h->C, o.nc1, o.nc2, nb_tab));
+  return CA_OK;
+}
+// the product: exps = false, the resident rows against B1 into part; exps = true (D > 0), exp(eta - m) against B2 into zpart / mpart
+template <typename YT, bool EXPSRC, int NT>
+int boot_prod_t(ca_engine* h, const ca_boot_ops& o, int ngroups) {
+  const int ncol = EXPSRC ? o.nc2 : o.nc1;
+  LAUNCH(h, EXPSRC ? CA_KERNEL_OTHER : CA_KERNEL_YPASS,
+         hipLaunchKernelGGL((k_boot_prod<YT, EXPSRC, NT>), dim3((unsigned)cdiv(o.n_cnt, 16 * (CA_TB / 64)), (unsigned)o.nzc, (unsigned)ngroups), dim3(CA_TB), 0, h->stream,
+                            (const YT*)h->Y, h->n_ovf > 0 ? h->ovf_rowptr : nullptr, h->ovf_col, h->ovf_val, o.Ut, o.Vt, EXPSRC ? o.B2 : o.B1, EXPSRC ? o.zpart : o.part,
+                            EXPSRC ? o.mpart : nullptr, o.n_lo, o.n_cnt, h->G, h->Gp, ncol));
+  return CA_OK;
+}
+// groups of CA_BOOT_NT column tiles (group z takes the tiles from z NT on); a product of at most four tiles -- a short last chunk of replicates -- takes the
+// four-tile instantiation
+template <typename YT, bool EXPSRC>
+int boot_prod_nt(ca_engine* h, const ca_boot_ops& o) {
+  const int tiles = (EXPSRC ? o.nc2 : o.nc1) / 16;
+  if (tiles <= 4) return boot_prod_t<YT, EXPSRC, 4>(h, o, 1);
+  return boot_prod_t<YT, EXPSRC, CA_BOOT_NT>(h, o, cdiv(tiles, CA_BOOT_NT));
+}
+int launch_boot_prod(ca_engine* h, const ca_boot_ops& o, bool exps) {
+  if (exps) return boot_prod_nt<float, true>(h, o);   // (never reads Y)
+  if (h->ystore == CA_YSTORE_U8) return boot_prod_nt<uint8_t, false>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return boot_prod_nt<uint16_t, false>(h, o);
+  return boot_prod_nt<float, false>(h, o);
+}
+template <typename YT>
+int boot_zero_t(ca_engine* h, const ca_boot_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_boot_zero<YT>), dim3((unsigned)cdiv(o.n_cnt * o.rc * o.nw, CA_TB)), dim3(CA_TB), 0, h->stream, (const YT*)h->Y, o.W, o.zg, o.zm, o.flags,
+                                                o.n_lo, o.n_cnt, o.r0, o.rc, o.rcp, o.nw, o.nz, h->G, h->Gp));
+  return CA_OK;
+}
+int launch_boot_zero(ca_engine* h, const ca_boot_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) return boot_zero_t<uint8_t>(h, o);
+  if (h->ystore == CA_YSTORE_U16) return boot_zero_t<uint16_t>(h, o);
+  return boot_zero_t<float>(h, o);
+}
+// ll_r and s_r of the chunk, then the chunk's replicates added into the call's votes and shares (the pointers at the batch's first row)
+int launch_boot_finish(ca_engine* h, const ca_boot_ops& o, const double* lp, int* votes, double* psum, double* psq) {
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_boot_finish, dim3((unsigned)cdiv(o.n_cnt * o.rc, CA_TB)), dim3(CA_TB), 0, h->stream, o.part, o.zpart, o.mpart, o.Z0,
+                                                o.nz > 0 ? o.flags : nullptr, o.llb, o.sb, o.n_cnt, o.rc, o.rcp, o.nw, h->C, o.D, o.nzc, o.nc1, o.nc2));
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_boot_reduce, dim3((unsigned)cdiv(o.n_cnt, CA_TB)), dim3(CA_TB), 0, h->stream, o.llb, lp, votes, psum, psq, o.n_lo, o.n_cnt, o.rc, h->C));
+  return CA_OK;
+}
 
 // ---- k_proj_mom<NC, K> / k_proj_step<K>: one round of ca_project_cells on one batch of cells (neither reads the count matrix) ----
 // the moments' operands: U = [psi | x] and V = [W | beta] padded to CA_LL_DMAX factors, E in groups of NC clone columns, the frozen flags, the chunk slabs

@@ -1,4 +1,4 @@
-// ca_eng_score.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, the scoring family -- the calls that score the resident count matrix under a fitted model: the per-cell, per-clone log-likelihood (ca_clone_loglik), under a mixture of two clones (ca_clone_pair_loglik), Dirichlet-multinomial (ca_clone_loglik_dm), by block of genes (ca_clone_loglik_by_block), the per-cell MAP psi of cells outside a fit (ca_project_cells), the clone evidence with psi integrated out (ca_clone_evidence).
+// ca_eng_score.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, the scoring family -- the calls that score the resident count matrix under a fitted model: the per-cell, per-clone log-likelihood (ca_clone_loglik), under a mixture of two clones (ca_clone_pair_loglik), Dirichlet-multinomial (ca_clone_loglik_dm), by block of genes (ca_clone_loglik_by_block), the per-cell MAP psi of cells outside a fit (ca_project_cells), the clone evidence with psi integrated out (ca_clone_evidence), with the genes reweighted for every replicate of a bootstrap (ca_clone_loglik_reweighted).
 // All of them read the matrix, the row sums and the overflow list only: no wait for the loop's side stream, no variable, Adam slot or draw index changes.  Their
 // inputs and outputs cover the local cells, so a sharded handle needs no sums from its peers; it still takes part in ONE small collective, the verdict on the
 // input (a non-finite U is local), so that every rank returns the same code instead of one of them leaving the others waiting.
@@ -659,5 +659,165 @@ int ca_clone_evidence(ca_handle h, const double* E, const double* V, int32_t K, 
       }
     }
   }
+  return CA_OK;
+}
+
+extern "C++" {
+namespace {
+thread_local double boot_kernel_ms = 0.0;
+// the event pairs around the launch groups of one call; their times are added after the call's last synchronise
+struct ca_event_pairs {
+  std::vector<hipEvent_t> ev;
+  ~ca_event_pairs() { for (hipEvent_t e : ev) hipEventDestroy(e); }
+  hipError_t mark(hipStream_t s) {
+    hipEvent_t e = nullptr;
+    hipError_t rc = hipEventCreate(&e);
+    if (rc != hipSuccess) return rc;
+    ev.push_back(e);
+    return hipEventRecord(e, s);
+  }
+  hipError_t total(double* ms) const {
+    *ms = 0.0;
+    for (size_t i = 0; i + 1 < ev.size(); i += 2) {
+      float t = 0.f;
+      hipError_t rc = hipEventElapsedTime(&t, ev[i], ev[i + 1]);
+      if (rc != hipSuccess) return rc;
+      *ms += t;
+    }
+    return hipSuccess;
+  }
+};
+}  // namespace
+}  // extern "C++"
+
+// the kernel time of the calling thread's last successful ca_clone_loglik_reweighted (its launches between event pairs; no copy)
+int ca_reweighted_kernel_ms(double* ms) {
+  if (!ms) return CA_ERR_INVALID;
+  *ms = boot_kernel_ms;
+  return CA_OK;
+}
+
+// The gene-reweighted log-likelihood of the resident cells [cell_lo, cell_lo + cell_cnt) for R sets of gene weights, reduced to votes and shares on the device
+// (bootstrap support for clone calls; include/clonealign_hip.h has the formulas and the rules, ca_k_bootll.hip.h the kernels).  The operands, the verdict, the
+// batch size and the outputs' layout are the scoring family's; the replicates go in chunks of CA_BOOT_RCHUNK: per chunk one k_boot_build, then per batch of
+// cells the product against the resident rows, the product against exp(eta - m) (D > 0), the side pass over the genes with a zero of E, k_boot_finish and
+// k_boot_reduce.  votes / prob_sum / prob_sq stay on the device from the first chunk to the last.
+int ca_clone_loglik_reweighted(ca_handle h, const double* E, const double* U, const double* V, int32_t D, const double* w, int32_t R, const double* log_prior, int64_t c_lo,
+                               int64_t c_cnt, double* ll, int32_t* votes, double* prob_sum, double* prob_sq, double* reads) {
+  if (!h) return CA_ERR_INVALID;
+  const std::string pre = "ca_clone_loglik_reweighted: ";
+  {
+    const char* null_arg = !E ? "E" : !w ? "w" : !votes ? "votes" : !prob_sum ? "prob_sum" : !prob_sq ? "prob_sq" : nullptr;
+    if (null_arg) { h->err = pre + null_arg + " is NULL"; return CA_ERR_INVALID; }
+  }
+  CA_NOT_IN_RUN(h);
+  boot_kernel_ms = 0.0;
+  if (D < 0 || D > CA_LL_DMAX) { h->err = pre + "D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
+  if (D > 0 && (!U || !V)) { h->err = pre + "D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
+  if (R < 1) { h->err = pre + "R = " + std::to_string(R) + " replicates is below 1"; return CA_ERR_INVALID; }
+  const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C;
+  HIPCK(h, hipSetDevice(h->device));
+  ca_ll_operands op;
+  ll_operands(h, ca_ll_req{E, V, D, {{U, D, "U", "factor"}, {nullptr, 0, "", ""}}, c_lo, c_cnt, false, false, 0, true}, op);
+  std::string& bad = op.bad;
+  for (int r = 0; r < R && bad.empty(); ++r) {   // (the weights are the same on every rank)
+    bool any = false;
+    for (int g = 0; g < G; ++g) {
+      const double v = w[(size_t)r * G + g];
+      if (!std::isfinite(v) || v < 0.0) { bad = "the weights have a negative or non-finite entry (replicate " + std::to_string(r) + ", gene " + std::to_string(g) + ")"; break; }
+      any = any || v > 0.0;
+    }
+    if (bad.empty() && !any) bad = "the weights of replicate " + std::to_string(r) + " are all zero (genes 0 .. " + std::to_string(G - 1) + ")";
+  }
+  std::vector<double> lp;
+  if (log_prior && bad.empty()) {
+    lp.resize((size_t)N * C);
+    for (int64_t n = 0; n < N && bad.empty(); ++n)
+      for (int c = 0; c < C; ++c) {
+        const double v = log_prior[hidx(h->layout, n, c, N, C)];
+        if (std::isnan(v) || v == HUGE_VAL) { bad = "log_prior has a NaN or +inf entry (cell " + std::to_string(n) + ", clone " + std::to_string(c) + "); -inf excludes a clone"; break; }
+        lp[(size_t)n * C + c] = v;
+      }
+  }
+  CACK(agree_on_verdict(h, bad));
+  if (!bad.empty()) { h->err = pre + bad; return CA_ERR_INVALID; }
+  if (c_cnt == 0) return CA_OK;
+  // the genes where some clone has E = 0, with the mask of those clones in words of 32
+  const int nw = cdiv(C, 32);
+  std::vector<int> zg;
+  std::vector<unsigned> zm;
+  for (int g = 0; g < G; ++g) {
+    bool any = false;
+    for (int c = 0; c < C && !any; ++c) any = op.Ec[(size_t)g * C + c] == 0.0;
+    if (!any) continue;
+    zg.push_back(g);
+    zm.resize(zm.size() + (size_t)nw, 0u);
+    for (int c = 0; c < C; ++c)
+      if (op.Ec[(size_t)g * C + c] == 0.0) zm[zm.size() - (size_t)nw + (size_t)(c >> 5)] |= 1u << (c & 31);
+  }
+  const int nz = (int)zg.size();
+  // columns of a full chunk, padded to whole tiles of 16; the slabs of a batch under the byte budget
+  const int RC = std::min<int>(R, CA_BOOT_RCHUNK), nzc = cdiv(G, CA_LL_ZCHUNK);
+  auto cols16 = [](int n) { return (n + 15) / 16 * 16; };
+  const int nc1max = cols16(RC * (C + 1)), nc2max = cols16(RC * C);
+  const int64_t per_cell = ((int64_t)nzc * (nc1max + (D > 0 ? nc2max + 1 : 0)) + (int64_t)RC * (C + 1) + 2 * (int64_t)C) * (int64_t)sizeof(double) +
+                           ((int64_t)RC * nw + C) * (int64_t)sizeof(int);
+  const int64_t NB = cells_per_batch(c_cnt, per_cell, CA_LL_BUDGET);
+  ca_rows_out o_ll(h, ll, c_cnt, (int64_t)R * C), o_ps(h, prob_sum, c_cnt, C), o_pq(h, prob_sq, c_cnt, C), o_rd(h, reads, c_cnt, R);
+  std::vector<int> o_vt((size_t)c_cnt * C);
+  std::vector<double> wv(w, w + (size_t)R * G);
+  ca_event_pairs evs;
+  ca_call_mem mem(h);
+  const ca_ll_dev dev = upload_operands(mem, op);
+  ca_boot_ops o;
+  o.W = mem.upload(wv); o.Ec = dev.Ec; o.Ut = dev.Ut; o.Vt = dev.Vt;
+  o.zg = nz > 0 ? mem.upload(zg) : nullptr; o.zm = nz > 0 ? mem.upload(zm) : nullptr;
+  const double* lp_d = log_prior ? mem.upload(lp) : nullptr;
+  o.B1 = mem.alloc<double>((int64_t)Gp * nc1max);
+  o.B2 = D > 0 ? mem.alloc<double>((int64_t)Gp * nc2max) : nullptr;
+  o.Z0 = D > 0 ? nullptr : mem.alloc<double>((int64_t)RC * C);
+  o.part = mem.alloc<double>((int64_t)nzc * NB * nc1max);
+  o.zpart = D > 0 ? mem.alloc<double>((int64_t)nzc * NB * nc2max) : nullptr;
+  o.mpart = D > 0 ? mem.alloc<double>((int64_t)nzc * NB) : nullptr;
+  o.llb = mem.alloc<double>(NB * RC * C);
+  o.sb = mem.alloc<double>(NB * RC);
+  o.flags = nz > 0 ? mem.alloc<unsigned>(NB * RC * nw) : nullptr;
+  int* vt_d = mem.alloc<int>(c_cnt * C);
+  double *ps_d = mem.alloc<double>(c_cnt * C), *pq_d = mem.alloc<double>(c_cnt * C);
+  if (mem.rc != CA_OK) return mem.rc;
+  o.rcp = RC; o.nw = nw; o.nz = nz; o.D = D; o.nzc = nzc;
+  HIPCK(h, hipMemsetAsync(vt_d, 0, (size_t)c_cnt * C * sizeof(int), h->stream));
+  HIPCK(h, hipMemsetAsync(ps_d, 0, (size_t)c_cnt * C * sizeof(double), h->stream));
+  HIPCK(h, hipMemsetAsync(pq_d, 0, (size_t)c_cnt * C * sizeof(double), h->stream));
+  for (int r0 = 0; r0 < R; r0 += CA_BOOT_RCHUNK) {
+    o.r0 = r0; o.rc = std::min<int>(CA_BOOT_RCHUNK, R - r0);
+    o.nc1 = cols16(o.rc * (C + 1)); o.nc2 = cols16(o.rc * C);
+    HIPCK(h, evs.mark(h->stream));
+    CACK(launch_boot_build(h, o));
+    HIPCK(h, evs.mark(h->stream));
+    for (int64_t n_lo = c_lo; n_lo < c_lo + c_cnt; n_lo += NB) {
+      o.n_lo = n_lo; o.n_cnt = std::min<int64_t>(NB, c_lo + c_cnt - n_lo);
+      const int64_t row = n_lo - c_lo;
+      HIPCK(h, evs.mark(h->stream));
+      CACK(launch_boot_prod(h, o, false));
+      if (D > 0) CACK(launch_boot_prod(h, o, true));
+      if (nz > 0) CACK(launch_boot_zero(h, o));
+      CACK(launch_boot_finish(h, o, lp_d, vt_d + row * C, ps_d + row * C, pq_d + row * C));
+      HIPCK(h, evs.mark(h->stream));
+      // (the copies run in stream order: before the next launches overwrite the batch's buffers)
+      if (ll) HIPCK(h, hipMemcpy2DAsync(o_ll.p + ((size_t)row * R + (size_t)r0) * C, (size_t)R * C * sizeof(double), o.llb, (size_t)o.rc * C * sizeof(double),
+                                        (size_t)o.rc * C * sizeof(double), (size_t)o.n_cnt, hipMemcpyDeviceToHost, h->stream));
+      if (reads) HIPCK(h, hipMemcpy2DAsync(o_rd.p + (size_t)row * R + (size_t)r0, (size_t)R * sizeof(double), o.sb, (size_t)o.rc * sizeof(double), (size_t)o.rc * sizeof(double),
+                                           (size_t)o.n_cnt, hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  HIPCK(h, hipMemcpyAsync(o_vt.data(), vt_d, o_vt.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCK(h, hipMemcpyAsync(o_ps.p, ps_d, (size_t)c_cnt * C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCK(h, hipMemcpyAsync(o_pq.p, pq_d, (size_t)c_cnt * C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCK(h, hipStreamSynchronize(h->stream));
+  HIPCK(h, evs.total(&boot_kernel_ms));
+  o_ll.finish(); o_ps.finish(); o_pq.finish(); o_rd.finish();
+  for (int64_t n = 0; n < c_cnt; ++n)
+    for (int c = 0; c < C; ++c) votes[hidx(h->layout, n, c, c_cnt, C)] = o_vt[(size_t)(n * C + c)];
   return CA_OK;
 }

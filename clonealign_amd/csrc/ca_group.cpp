@@ -795,6 +795,42 @@ int ca_group_clone_loglik_dm(ca_group_handle g, const double* E, const double* U
   return CA_OK;
 }
 
+int ca_group_clone_loglik_reweighted(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, const double* w, int32_t R, const double* log_prior,
+                                     int64_t cell_lo, int64_t cell_cnt, double* ll, int32_t* votes, double* prob_sum, double* prob_sq, double* reads) {
+  GROUP_ALIVE(g);
+  {
+    const char* null_arg = !E ? "E" : !w ? "w" : !votes ? "votes" : !prob_sum ? "prob_sum" : !prob_sq ? "prob_sq" : nullptr;
+    if (null_arg) { g->err = std::string("ca_clone_loglik_reweighted: ") + null_arg + " is NULL"; return CA_ERR_INVALID; }
+  }
+  if (!duv_ok(g, "ca_clone_loglik_reweighted", D, U, V)) return CA_ERR_INVALID;
+  if (R < 1) { g->err = "ca_clone_loglik_reweighted: R = " + std::to_string(R) + " replicates is below 1"; return CA_ERR_INVALID; }   // (it sizes the ranks' outputs)
+  RangePlan p;
+  if (!plan_range(g, "ca_clone_loglik_reweighted", cell_lo, cell_cnt, U, D, p)) return CA_ERR_INVALID;
+  const int64_t C = g->C, RCn = (int64_t)R * C;
+  const size_t W = (size_t)g->W;
+  std::vector<std::vector<double>> lps(W);
+  if (log_prior) for (size_t r = 0; r < W; ++r) slice_rows(log_prior, g->layout, g->N, C, g->shard[r].lo, g->shard[r].hi, lps[r]);
+  auto o_ll = p.outputs(ll ? RCn : 0), o_ps = p.outputs(C), o_pq = p.outputs(C), o_rd = p.outputs(reads ? R : 0);
+  std::vector<std::vector<int32_t>> o_vt(W);
+  for (size_t r = 0; r < W; ++r) o_vt[r].resize((size_t)(p.rows(r) * C) + 1);
+  const int st = settle_verdict(g, dispatch(g, [&](int ri) {
+    const size_t r = (size_t)ri;
+    return ca_clone_loglik_reweighted(g->h[r], E, p.u(r), V, D, w, R, log_prior ? lps[r].data() : nullptr, p.local_lo(r), p.rows(r), ll ? o_ll[r].data() : nullptr,
+                                      o_vt[r].data(), o_ps[r].data(), o_pq[r].data(), reads ? o_rd[r].data() : nullptr);
+  }), "ca_clone_loglik_reweighted");
+  if (st != CA_OK) return st;
+  if (ll) p.scatter(o_ll, RCn, ll);
+  p.scatter(o_ps, C, prob_sum);
+  p.scatter(o_pq, C, prob_sq);
+  if (reads) p.scatter(o_rd, R, reads);
+  for (size_t r = 0; r < W; ++r) {
+    const int64_t n = p.rows(r), at = p.lo[r] - cell_lo;
+    for (int64_t c = 0; c < C; ++c)
+      for (int64_t i = 0; i < n; ++i) votes[hidx(g->layout, at + i, c, cell_cnt, C)] = o_vt[r][(size_t)hidx(g->layout, i, c, n, C)];
+  }
+  return CA_OK;
+}
+
 int ca_group_clone_loglik_by_block(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const int32_t* block_of_gene,
                                    int32_t n_blocks, int64_t cell_lo, int64_t cell_cnt, double* A, double* logZ, double* s, double* lg) {
   GROUP_ALIVE(g);

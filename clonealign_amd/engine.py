@@ -66,7 +66,22 @@ EXPORTS = (
     "ca_predictive_moments", "ca_predictive_moments_kernel_ms",
     # clone evidence with psi integrated out: Newton mode, Laplace value and quadrature per (cell, clone) (clone_evidence / heldout_evidence), additions to ABI 6
     "ca_clone_evidence", "ca_group_clone_evidence",
+    # gene-reweighted log-likelihood for every replicate of a bootstrap, votes and shares reduced on the device (clone_loglik_reweighted / bootstrap_assignments),
+    # additions to ABI 6
+    "ca_clone_loglik_reweighted", "ca_group_clone_loglik_reweighted", "ca_reweighted_kernel_ms",
 )
+CA_BOOT_RCHUNK = 32   # replicates per chunk of ca_clone_loglik_reweighted (include/clonealign_hip.h)
+
+
+def reweighted_cells_per_batch(n, G, C, D, R):
+    """Cells per internal batch of ``clone_loglik_reweighted`` on ``n`` cells: the library's arithmetic (ca_clone_loglik_reweighted in
+    csrc/ca_eng_score.inc: the slabs of a batch stay below a quarter of a gigabyte, whole blocks of 256 cells), restated so that a test can tell whether a
+    call spans two batches.  No result depends on it."""
+    rc = min(int(R), CA_BOOT_RCHUNK)
+    nzc, nw = -(-int(G) // 512), -(-int(C) // 32)
+    nc1, nc2 = -(-rc * (C + 1) // 16) * 16, -(-rc * C // 16) * 16
+    per_cell = (nzc * (nc1 + (nc2 + 1 if D > 0 else 0)) + rc * (C + 1) + 2 * C) * 8 + (rc * nw + C) * 4
+    return min(int(n), max(256, ((1 << 28) // per_cell) // 256 * 256))
 CA_SPARSE_CSR, CA_SPARSE_CSC = 0, 1
 
 
@@ -234,6 +249,10 @@ def load_library(path=None):
     lib.ca_group_clone_pair_loglik.argtypes = lib.ca_clone_pair_loglik.argtypes
     lib.ca_group_clone_loglik_by_block.argtypes = lib.ca_clone_loglik_by_block.argtypes
     lib.ca_group_clone_loglik_dm.argtypes = lib.ca_clone_loglik_dm.argtypes
+    lib.ca_clone_loglik_reweighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.ca_group_clone_loglik_reweighted.argtypes = lib.ca_clone_loglik_reweighted.argtypes
+    lib.ca_reweighted_kernel_ms.argtypes = [C.POINTER(C.c_double)]
     # initialise this library's HIP runtime NOW: torch bundles its own, and whichever runtime is loaded first must also be
     # initialised first (loaded first but initialised second it reports "no ROCm-capable device is detected")
     lib.ca_device_count(None)
@@ -826,6 +845,37 @@ class HipEngine:
         return {"A": np.ascontiguousarray(A).reshape(n, Bn, Cn), "logZ": np.ascontiguousarray(logZ).reshape(n, Bn, Cn), "s": np.ascontiguousarray(s),
                 "lg": None if lg is None else np.ascontiguousarray(lg)}
 
+    def clone_loglik_reweighted(self, E, U, V, weights, log_prior=None, cells=None, want_ll=False):
+        """``clone_loglik``'s score with the genes REWEIGHTED, for every row of ``weights`` [R, G] (finite, >= 0, no row all zero) at once -- the
+        replicates of a bootstrap over genes -- on the device in float64 on the matrix cores (ca_clone_loglik_reweighted; include/clonealign_hip.h has the
+        formulas and the rules): ``ll_r[n, c] = sum_g w_rg xlogy(y_ng, E_gc) - s_r[n] log sum_g w_rg E_gc exp(eta_ng)``, ``s_r[n] = sum_g w_rg y_ng``.  For
+        integer weights that is ``clone_loglik(const=False)`` of the matrix with column g repeated ``w_rg`` times minus ``sum_g w_rg y_ng eta_ng``; that term
+        and the lgamma constant are the same for every clone and are left out.  ``E``, ``U``, ``V`` as for ``clone_loglik`` (both None for D = 0; ``U``
+        covers all resident cells); ``log_prior`` [N, C] over all resident cells or None (``-inf`` excludes a clone); ``cells`` = ``(lo, hi)`` restricts
+        the call to that range (None: all).  Returns ``{"votes": [n, C] int32 (replicates whose argmax of ll_r + log_prior is c, ties to the lowest),
+        "prob_sum", "prob_sq": [n, C] (sums over r of the softmax and of its square), "reads": [n, R] (s_r), "ll": [n, R, C] (None unless want_ll)}``.
+        ``ll_r = -inf`` exactly where a positive count with a positive weight meets ``E = 0``; ``s_r = 0`` gives ``ll_r = 0``; no NaN.  No value depends
+        on the cell range, the batching or on which other replicates share the call.  Changes nothing in the engine; two calls agree bit for bit."""
+        Em, Um, Vm, D = self._ll_operands("clone_loglik_reweighted", E, U, V)
+        lo, hi, n = self._cell_range(cells)
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+        if w.ndim != 2 or w.shape[1] != self.G:
+            raise ValueError(f"clone_loglik_reweighted: weights is {w.shape}; expected (R, {self.G})")
+        R, Cn = int(w.shape[0]), self.C
+        lpm = None
+        if log_prior is not None:
+            log_prior = np.asarray(log_prior, dtype=np.float64)
+            if log_prior.shape != (self.N, Cn):
+                raise ValueError(f"clone_loglik_reweighted: log_prior is {log_prior.shape}; expected ({self.N}, {Cn})")
+            lpm = self._in_order(log_prior)
+        ll = self._zeros(n, R * Cn) if want_ll else None
+        ps, pq, rd = self._zeros(n, Cn), self._zeros(n, Cn), self._zeros(n, R)
+        votes = np.zeros((n, Cn), dtype=np.int32, order=self._order)
+        self._ck(self._fn("clone_loglik_reweighted")(self.h, _ptr(Em), _ptr(Um), _ptr(Vm), D, _ptr(w), R, _ptr(lpm), lo, hi - lo, _ptr(ll), _ptr(votes), _ptr(ps),
+                                                     _ptr(pq), _ptr(rd)))
+        return {"votes": np.ascontiguousarray(votes), "prob_sum": np.ascontiguousarray(ps), "prob_sq": np.ascontiguousarray(pq), "reads": np.ascontiguousarray(rd),
+                "ll": None if ll is None else np.ascontiguousarray(ll).reshape(n, R, Cn)}
+
     def project_cells(self, E, V=None, K=0, X=None, log_prior=None, psi_start=None, const=True, max_iter=25, tol=1e-9, max_step=1.0, poll_every=None):
         """Per-cell MAP ``psi`` of the resident cells under a fit's gene-level parameters and the exact clone posterior at it (ca_project_cells;
         include/clonealign_hip.h has the algorithm): maximises ``logsumexp_c(ll_nc(psi) + log_prior_nc) - |psi|^2 / 2`` per cell by generalised EM with one
@@ -1121,6 +1171,11 @@ def simulate_counts(E, V, U, clone, total, seed, draw=0, cell_offset=0, device=0
 def simulate_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``simulate_counts`` call took (HIP events around each launch)."""
     return _last_kernel_ms("ca_simulate_kernel_ms")
+
+
+def reweighted_kernel_ms():
+    """Milliseconds the kernel launches of this thread's last ``HipEngine.clone_loglik_reweighted`` call took (HIP events around the launches, no copy)."""
+    return _last_kernel_ms("ca_reweighted_kernel_ms")
 
 
 def predictive_stats(E, V, U, clone, total, seed, draw0=0, n_rep=1, cell_offset=0, device=0, gene_totals=True, out=None):

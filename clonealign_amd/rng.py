@@ -59,6 +59,21 @@ def normal_draw(seed, draw, n):
     return z.reshape(-1)[:n].astype(np.float32)
 
 
+def index_draw(seed, stream, n, bound):
+    """``n`` integers in ``[0, bound)`` (int64, ``bound`` <= 2^31) for stream index ``stream`` of ``seed``: Philox4x32-10 under the key ``seed ^ "boot"``,
+    counter = (block index, stream index), four 32-bit words a block, word ``u`` mapped to ``(u * bound) >> 32``.  Draw i depends on (seed, stream, i)
+    alone, so a stream's draws do not depend on how many streams are taken."""
+    seed = (int(seed) ^ 0x626F6F74626F6F74) & 0xFFFFFFFFFFFFFFFF
+    nblk = (int(n) + 3) // 4
+    ctr = np.zeros((nblk, 4), dtype=np.uint32)
+    ctr[:, 0] = np.arange(nblk, dtype=np.uint64) & 0xFFFFFFFF
+    ctr[:, 1] = np.arange(nblk, dtype=np.uint64) >> 32
+    ctr[:, 2] = np.uint32(int(stream) & 0xFFFFFFFF)
+    ctr[:, 3] = np.uint32((int(stream) >> 32) & 0xFFFFFFFF)
+    r = philox4x32(ctr, (seed & 0xFFFFFFFF, seed >> 32)).astype(np.uint64).reshape(-1)[:int(n)]
+    return ((r * np.uint64(int(bound))) >> np.uint64(32)).astype(np.int64)
+
+
 class EpsStream:
     """Sequential eps[S,G] draws; mirrors the per-``sess$run`` sampling of the reference."""
 

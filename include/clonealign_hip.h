@@ -521,6 +521,43 @@ int ca_clone_loglik_by_block(ca_handle h, const double* E /* G x C */, const dou
                              double* A /* cell_cnt x (n_blocks C) */, double* logZ /* cell_cnt x (n_blocks C) */, double* s /* cell_cnt x n_blocks */,
                              double* lg /* cell_cnt x n_blocks, or NULL when with_const == 0 */);
 
+/* BOOTSTRAP SUPPORT FOR CLONE CALLS: ca_clone_loglik's score with the genes REWEIGHTED, for R sets of weights at once, for the cells
+ * [cell_lo, cell_lo + cell_cnt).  Resampling the genes with replacement gives integer weights (how often a gene was drawn); the share of replicates that repeat
+ * a cell's call says how sure the call is.  Notation and input rules of ca_clone_loglik (E is G x C, eta_ng = U_n . V_g, U is N x D over ALL resident cells);
+ * w is R x G, row-major whatever the problem's layout, every entry finite and >= 0, no row all zero:
+ *   A_r[n][c]    = sum_g w_rg xlogy(y_ng, E[g][c])
+ *   s_r[n]       = sum_g w_rg y_ng
+ *   logZ_r[n][c] = log sum_g w_rg E[g][c] exp(eta_ng)
+ *   ll_r[n][c]   = A_r[n][c] - s_r[n] logZ_r[n][c]
+ * For integer weights this is ca_clone_loglik (with_const = 0) of the matrix with column g repeated w_rg times, MINUS sum_g w_rg y_ng eta_ng: that term and the
+ * lgamma constant are the same for every clone of a cell, change no posterior and no argmax, and are left out.
+ * The reduced form is the normal output (R x N x C doubles are 640 MB at 100k cells, 8 clones, R = 100).  With t_r = ll_r + log_prior (log_prior: N x C over ALL
+ * resident cells in the problem's layout, NULL = 0, -inf excludes a clone; NaN and +inf are refused):
+ *   votes[n][c]    (int32) the number of replicates whose argmax_c t_r is c, ties to the lowest clone
+ *   prob_sum[n][c], prob_sq[n][c]   sum_r softmax_c(t_r) and sum_r softmax_c(t_r)^2, r ascending (a replicate whose t_r is -inf in every clone votes for clone 0
+ *                  and adds nothing to either)
+ * all cell_cnt x C in the problem's layout, row = cell - cell_lo.  ll (or NULL: not written) is cell_cnt x (R C), column = r * C + clone; reads (or NULL) is
+ * cell_cnt x R, s_r.  Rules:
+ *   ll_r = -inf exactly where a positive count with a positive weight meets E = 0; a zero weight or a zero count adds nothing.  No NaN anywhere: the -inf is set
+ *     from a mask before anything is subtracted (never -inf - s (-inf)), and s_r[n] = 0 gives ll_r[n][:] = 0 whatever logZ_r is.
+ *   the exponent's shift is ca_clone_loglik's: per cell and chunk of CA_LL_ZCHUNK genes the max of eta over EVERY gene of the chunk, the chunks merged in
+ *     ascending order under their overall max; a zero weight behaves there as E = 0 does.
+ *   Everything is float64 on v_mfma_f64_16x16x4_f64 (cells x (replicate, clone) over the genes), no atomics, every sum in a fixed order: two calls agree bit for
+ *     bit.  The call cuts R into chunks of CA_BOOT_RCHUNK replicates and the cells into batches; no value depends on either cut, on the cell range or on R --
+ *     one call with R replicates returns what R calls with one each return -- so a cell-sharded group returns the single handle's bits.
+ *   any storage (u8 with its overflow list -- escaped counts enter with their true values --, u16, f32), dense or sparse uploads, both layouts.
+ * CA_ERR_INVALID (with a message naming the offender): everything ca_clone_loglik refuses; R < 1; a weight that is negative or non-finite (replicate and gene
+ * are named); a replicate whose weights are all zero; log_prior NaN or +inf; a cell range outside [0, N]; E, w, votes, prob_sum or prob_sq NULL.
+ * Sharded handle: U, log_prior, the cell range and the outputs are the local cells'; the only collective is the verdict on the input.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+#define CA_BOOT_RCHUNK 32   /* replicates per chunk of ca_clone_loglik_reweighted (mirrored in clonealign_amd/engine.py) */
+int ca_clone_loglik_reweighted(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */, int32_t D,
+                               const double* w /* R x G, row-major */, int32_t R, const double* log_prior /* N x C, or NULL */, int64_t cell_lo, int64_t cell_cnt,
+                               double* ll /* cell_cnt x (R C), or NULL */, int32_t* votes /* cell_cnt x C */, double* prob_sum /* cell_cnt x C */,
+                               double* prob_sq /* cell_cnt x C */, double* reads /* cell_cnt x R: s_r, or NULL */);
+/* the kernel time (ms, HIP events around the launches, no copy) of the calling thread's last successful ca_clone_loglik_reweighted; 0 before the first */
+int ca_reweighted_kernel_ms(double* ms);
+
 /* Project cells onto a fitted model: for every resident cell the MAP value of its latent factor psi_n under the fit's GENE-LEVEL parameters, and the
  * exact clone posterior at it -- the per-cell part of the model for cells the fit never saw (no refit; every cell is independent).  Notation of
  * ca_clone_loglik: E (G x C) = mu L, V = [W | beta] (G x D, D = K + P), U_n = [psi_n | x_n] (the first K columns free, the last P given by X),
@@ -852,6 +889,12 @@ int ca_group_clone_loglik_dm(ca_group_handle g, const double* E, const double* U
 int ca_group_clone_loglik_by_block(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
                                    const int32_t* block_of_gene, int32_t n_blocks, int64_t cell_lo, int64_t cell_cnt, double* A, double* logZ, double* s,
                                    double* lg /* or NULL when with_const == 0 */);
+/* ca_clone_loglik_reweighted over the group: U and log_prior hold ALL cells, the cell range counts the group's cells, the outputs hold the range's rows; each
+ * cell's values are the single handle's, bit for bit (every rank is called with its part of the range, an empty one included, for the verdict on the input) */
+int ca_group_clone_loglik_reweighted(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D,
+                                     const double* w /* R x G, row-major */, int32_t R, const double* log_prior /* N x C, all cells, or NULL */, int64_t cell_lo,
+                                     int64_t cell_cnt, double* ll /* cell_cnt x (R C), or NULL */, int32_t* votes, double* prob_sum, double* prob_sq,
+                                     double* reads /* cell_cnt x R, or NULL */);
 /* ca_project_cells over the group: X, log_prior, psi_start and every output hold ALL cells (sliced by the shards); each cell's results are the single handle's, bit for bit */
 int ca_group_project_cells(ca_group_handle g, const double* E, const double* V, int32_t K, int32_t P, const double* X /* N x P, all cells, or NULL */,
                            const double* log_prior /* N x C, all cells, or NULL */, const double* psi_start /* N x K, all cells, or NULL */,
