@@ -137,7 +137,8 @@ int yfin_flush(ca_engine* h) {
 int ys_finish(ca_engine* h, bool defer = false) {
   h->yfin_pending = true;
   if (!defer) CACK(yfin_flush(h));
-  h->ys_slot = (h->ys_slot + 1) % 3;
+  h->ys_slot = (h->ys_slot + 1) % 3;   // (the only place the ring advances: ca_ystream_parts finds the launch's exponents one slot back)
+  h->ys_launched = true;
   h->ys_steps = 0;
   h->ys_quant_ready = false;
   h->ycache_valid = true;

@@ -222,6 +222,7 @@ struct ca_engine {
   unsigned* ys_amax = nullptr;   // [2]: exact maxima of a fresh state (k_ym_absmax), float bit patterns
   float* ys_amaxp = nullptr; int ys_nq = 0;   // [3][ys_ncap][2]: per-block maxima each quantiser run leaves for the next one
   int ys_ncap = 0, ys_namax[3] = {0, 0, 0};   // pairs a slot can hold / holds (a merged update leaves one pair per gene block and per psi block)
+  bool ys_launched = false;      // a stream launch has filled the partial slabs at least once (ca_ystream_parts)
   bool ys_quant_ready = false;   // the images of the CURRENT parameter state were made by the quantiser riding on k_adam_cell
   int ys_slot = 0, ys_steps = -1, ys_RS = 256, ys_nrg = 0, ys_nseg = 0; int64_t ys_N64 = 0; float ys_step_bound = -1.f;
   double adam_bound = -1.0;      // ca_adam_step_bound of this fit's Adam settings (create_impl); < 0: none holds.  Both look-aheads rest on it: ys_step_bound, poly_step_bound

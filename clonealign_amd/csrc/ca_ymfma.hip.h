@@ -272,6 +272,13 @@ __device__ __forceinline__ ca_i32x4 ca_mfma_i8(uint4 a, uint4 b, ca_i32x4 c) {
 constexpr int CA_YS_GW = 512;      // genes per segment (block = one segment x four strips); the switch in k_ys_mfma assumes 8 x 64
 static_assert(CA_YS_GW == 512, "k_ys_mfma's accumulator switch has eight cases");
 constexpr int CA_YS_PITCH = 80;    // LDS row pitch of the 64-byte rows: 16 lanes of a ds_read_b128 group fall on 16 different bank quads
+// Round 19: a cell tile (16 rows) of a staging region starts 128 B past the end of the one before.  A transposed read is served in lane groups {0-31} and
+// {32-63}, i.e. two cell tiles at a time, and one tile's sixteen lanes cover 32 of the 64 banks (8 rows, 20 banks apart, two halves); at the plain pitch the
+// tiles lie 16 x 80 B = 320 banks = 0 (mod 64) apart and the pair met on the same 32 banks: every transposed read a two-way conflict.  352 banks = 32 (mod 64)
+// puts odd tiles on the other half.  Addresses only: the bytes a lane writes and reads back are the same.
+constexpr int CA_YS_TILE = 16 * CA_YS_PITCH + 128;   // bytes from one cell tile of a staging region to the next
+constexpr int CA_YS_STAGE = 4 * CA_YS_TILE;          // a wave's staging region (64 rows)
+static_assert((CA_YS_TILE / 4) % 64 == 32 && CA_YS_TILE % 16 == 0, "odd cell tiles sit 32 banks off the even ones, 16-byte aligned");
 
 // The eight transposed reads of a 64-gene block (four gene tiles x two halves of the 16 cells) and their wait in ONE asm
 // statement: the compiler treats an asm output as valid as soon as the statement ends, and would otherwise be free to copy a
@@ -297,7 +304,7 @@ __device__ __forceinline__ void ca_ds_read_tr_b8_x4(unsigned addr, uint2 (&lo)[2
       : "v"(addr)
       : "memory");
 }
-static_assert(8 * CA_YS_PITCH == 640, "offsets in ca_ds_read_tr_b8_x8 / _x4 assume the 80-byte pitch");
+static_assert(8 * CA_YS_PITCH == 640, "offsets in ca_ds_read_tr_b8_x8 / _x4 assume the 80-byte pitch inside a cell tile (rows 8 .. 15 of the tile the lane's address names)");
 __device__ __forceinline__ uint4 ca_and4(uint4 a, unsigned m) { return (uint4){a.x & m, a.y & m, a.z & m, a.w & m}; }
 
 // The bias (stored byte = y - 128) is undone by the finisher: 128 x the digit sums of the parameter images, which the
@@ -328,13 +335,14 @@ struct ca_ys_io {
 #endif
 // LDS of the 4-bit image's own launch (OWN): the staging regions, then the segment's W image (read by the row products and the escapes
 // instead of a buffer load per piece), the row-escape sums, each wave's copy of psi's digits for the step, and -- past the 32-KB combine
-// buffer, since it is read in the combine -- the block's column-escape sums [512 genes] int64.  36 KB: four blocks per CU (160 KB).
-constexpr int CA_YS4_OFF_W = 4 * 64 * CA_YS_PITCH;
+// buffer and the tables, since it is read in the combine -- the block's column-escape sums [512 genes] int64.  37 KB: four blocks per CU (160 KB).
+constexpr int CA_YS4_OFF_W = 4 * CA_YS_STAGE;
 constexpr int CA_YS4_OFF_ROW = CA_YS4_OFF_W + (CA_YS_GW / 64) * 1024;
 constexpr int CA_YS4_OFF_PSI = CA_YS4_OFF_ROW + 4 * 64 * 8;
-constexpr int CA_YS4_OFF_COL = 4 * (CA_YS_GW / 64) * 64 * 4 * 4;
+constexpr int CA_YS4_COMB = 4 * (CA_YS_GW / 64) * 64 * 4 * 4;   // the combine buffer
+constexpr int CA_YS4_OFF_COL = CA_YS4_OFF_PSI + 4 * 256 > CA_YS4_COMB ? CA_YS4_OFF_PSI + 4 * 256 : CA_YS4_COMB;
 constexpr int CA_YS4_LDS_BYTES = CA_YS4_OFF_COL + CA_YS_GW * 8;
-static_assert(CA_YS4_OFF_PSI + 4 * 256 <= CA_YS4_OFF_COL, "the 4-bit launch's tables fit below its column-escape sums");
+static_assert(CA_YS4_OFF_PSI + 4 * 256 <= CA_YS4_OFF_COL && CA_YS4_COMB <= CA_YS4_OFF_COL, "the 4-bit launch's tables and the combine buffer lie below its column-escape sums");
 static_assert(4 * CA_YS4_LDS_BYTES <= 160 * 1024, "four blocks of the 4-bit launch per CU");
 // Y4: the loop image is the 4-bit one (k_pack_y4) and its escape list is added exactly -- row side into the cell's 64-bit sum before it
 // becomes a float, column side into the block's integer combine -- so YWpart / YTpart are the 1-byte image's to the last bit.
@@ -349,7 +357,7 @@ static_assert(4 * CA_YS4_LDS_BYTES <= 160 * 1024, "four blocks of the 4-bit laun
 template <int DEPTH = CA_YS_DEPTH, bool Y4 = false, bool OWN = false, int N2 = 0>
 __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restrict__ Ys, const ca_ys_io& io, int64_t N, int Gp,
                                                 int RS /* cells per strip, multiple of 64 */,
-                                                unsigned char* ca_ys_lds /* 16-byte aligned, CA_YS_LDS_BYTES: [4 waves][64][CA_YS_PITCH], reused for the combine */) {
+                                                unsigned char* ca_ys_lds /* 16-byte aligned, CA_YS_LDS_BYTES: [4 waves][4 cell tiles][CA_YS_TILE], reused for the combine */) {
   const uint4* __restrict__ Wr = io.Wr;
   const uint4* __restrict__ Pr = io.Pr;
   constexpr bool Y4L = Y4 && OWN;
@@ -366,22 +374,25 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6) & 3);
   const int nseg = Gp / CA_YS_GW;
   const int rg = blk / nseg, seg = blk - rg * nseg;
-  unsigned char* my = ca_ys_lds + (size_t)wv * 64 * CA_YS_PITCH;
+  unsigned char* my = ca_ys_lds + (size_t)wv * CA_YS_STAGE;
   const int64_t c0 = ((int64_t)rg * 4 + wv) * RS;             // first cell of this wave's strip
   const int64_t c1 = (c0 + RS < N) ? c0 + RS : N;             // (rows up to the next multiple of 64 exist and hold zeros)
   const int g0 = seg * CA_YS_GW;
   const unsigned grp = (unsigned)(j >> 2);
+  // psi's row-group masks, two forms of the same thing: msk[] is read only where !Y4L (prm[], once per cell step), gsel only where Y4L (per MFMA); each
+  // instantiation uses one, the other is dead code the compiler drops
   unsigned msk[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) msk[t] = grp == (unsigned)t ? 0xFFFFFFFFu : 0u;
+  const unsigned gsel = 0xFFu << (8u * grp);   // (Y4L) the same masks in one register: msk[t] = the sign-extended byte t
   ca_i32x4 acc_yt[NP];
 #pragma unroll
   for (int a = 0; a < NP; ++a) acc_yt[a] = (ca_i32x4){0, 0, 0, 0};
-  // staging: load instruction i of a piece covers rows 16 i .. 16 i + 15, 64 bytes each
+  // staging: load instruction i of a piece covers rows 16 i .. 16 i + 15 (cell tile i), 64 bytes each; row 16 t + r of the region is at t * CA_YS_TILE + r * CA_YS_PITCH
   const int lrow = lane >> 2, lch = lane & 3;
   unsigned char* wr_dst = my + lrow * CA_YS_PITCH + 16 * lch;
   const unsigned char* rd_row = my + j * CA_YS_PITCH + 16 * q;
-  const unsigned rd_tr = (unsigned)(size_t)my + (unsigned)((16 * q + (j >> 1)) * CA_YS_PITCH + 8 * (j & 1));
+  const unsigned rd_tr = (unsigned)(size_t)my + (unsigned)(q * CA_YS_TILE + (j >> 1) * CA_YS_PITCH + 8 * (j & 1));   // (lane group q reads cell tile q)
   constexpr int PB = Y4 ? 2048 : 4096, NL = PB / 1024;                              // bytes of a piece, 1-KiB loads per piece
   const uint8_t* src = N2 > 0 ? Ys + ((c0 >> 6) * (int64_t)nseg + seg) * SB2        // (scalar) the strip's first (cell step, segment) of the 2-bit / 4-bit image
                               : Ys + ((c0 >> 6) * (int64_t)(Gp / 64) + (g0 >> 6)) * PB;     // (scalar) piece (cell step, gene block), 1 KiB per load
@@ -397,12 +408,16 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), 0, 0x7FFFFFFF, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(wsrc), 0, NP * 1024, 0x00020000);
   const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(Pr + (c0 >> 6) * 64), 0, 0x7FFFFFFF, 0x00020000);
+  // Cache policy of the piece loads: the non-temporal hint, except in the 4-bit image's own launch (round 19).  That launch reads the same image once per
+  // iteration and nothing as large in between.  Measured by alternation only (profiles/r19_stream_ab.txt: 97.4 - 98.3 us per iteration against 98.9 - 99.9 with the
+  // hint, no region overlapping).  Supposed, not measured: that part of the image (160 MB at the headline shape) is still in the memory-side cache on the next
+  // pass -- the launch's HBM read bytes were not counted.  The riding forms share the sweep's lines: hint kept.
   auto issue = [&](int slot, int st, int a, unsigned vo) {
     const int so = N2 > 0 ? st * nseg * SB2 + (a < N2 ? a * 1024 : N2 * 1024 + (a - N2) * 2048) : (st * (Gp / 64) + a) * PB;   // (scalar)
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       if (N2 > 0 && i > 0 && a < N2) continue;   // (a narrow piece is one load; `a` is a constant wherever this is called)
-      const ca_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(vo + 1024u * (unsigned)i), so, 2 /* nt: streamed once */);
+      const ca_v4u v = __builtin_amdgcn_raw_buffer_load_b128(ry, (int)(vo + 1024u * (unsigned)i), so, Y4L ? 0 : 2 /* nt: streamed once */);
       R[slot][i] = (uint4){v.x, v.y, v.z, v.w};
     }
     if (!Y4L) {
@@ -440,7 +455,7 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   if (Y4L) {
     static_assert(2 * CA_YM_TB == CA_YS_GW, "the block's threads hold the segment's W image and column sums in two halves");
     if (N2 > 0) {
-      // gather the W image into the private order: the image as the quantiser left it goes through the staging regions (8 KiB of their 20, no piece is parked yet),
+      // gather the W image into the private order: the image as the quantiser left it goes through the staging regions (8 KiB of their 22, no piece is parked yet),
       // and row x = (block a, lane 16 q + j) takes byte (digit j & 3, gene) of each of its sixteen genes -- the address the escapes use
       uint4* tmp = reinterpret_cast<uint4*>(ca_ys_lds);
       tmp[threadIdx.x] = wimg[0];
@@ -490,7 +505,7 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   // Y4: the bucket of this wave (its strip of the block's segment) in the escape list, and 64 int64 slots of LDS past the four staging
   // regions where a cell step's row-side escapes are summed (slot = cell in the step)
   const int64_t kb = ((int64_t)blk * 4 + wv) * RS;
-  unsigned long long* rowesc = reinterpret_cast<unsigned long long*>(ca_ys_lds + (Y4L ? CA_YS4_OFF_ROW : 4 * 64 * CA_YS_PITCH)) + wv * 64;
+  unsigned long long* rowesc = reinterpret_cast<unsigned long long*>(ca_ys_lds + (Y4L ? CA_YS4_OFF_ROW : 4 * CA_YS_STAGE)) + wv * 64;
   unsigned char* psl = ca_ys_lds + CA_YS4_OFF_PSI + wv * 256;   // (Y4L) psi's digits of the step: [cell quarter][digit][16 cells]
   if (Y4) rowesc[lane] = 0ull;
   for (int st = 0; st < nsteps; ++st) {
@@ -536,7 +551,7 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
           const uint4 v = R[slot][nar ? 0 : t >> 1];
           const int sh = nar ? 2 * t : 4 * (t & 1);
           const uint4 av = ca_and4((uint4){v.x >> sh, v.y >> sh, v.z >> sh, v.w >> sh}, nar ? 0x03030303u : 0x0F0F0F0Fu);
-          *reinterpret_cast<uint4*>(const_cast<unsigned char*>(rd_row) + 16 * t * CA_YS_PITCH) = av;
+          *reinterpret_cast<uint4*>(const_cast<unsigned char*>(rd_row) + t * CA_YS_TILE) = av;
           acc_yw[t] = ca_mfma_i8(av, wr, acc_yw[t]);
         }
         if (a + DEPTH < NP) issue(slot, st, a + DEPTH, voff);
@@ -554,13 +569,13 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
         } else if (more) issue(slot, st + 1, a + DEPTH - NP, voff);
       } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(wr_dst + 16 * i * CA_YS_PITCH) = R[slot][i];
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<uint4*>(wr_dst + i * CA_YS_TILE) = R[slot][i];
         if (a + DEPTH < NP) issue(slot, st, a + DEPTH, voff);
         else if (more) issue(slot, st + 1, a + DEPTH - NP, voff);
         // row products: the four cell tiles against this 64-gene block
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          const uint4 av = *reinterpret_cast<const uint4*>(rd_row + 16 * t * CA_YS_PITCH);
+          const uint4 av = *reinterpret_cast<const uint4*>(rd_row + t * CA_YS_TILE);
           acc_yw[t] = ca_mfma_i8(av, wr, acc_yw[t]);
         }
       }
@@ -572,10 +587,13 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           uint4 pa;
-          if (Y4L) {   // psi masked to row group 2 h2 + t here, not held four times over the step (the opaque copy keeps it from being shared)
-            unsigned g_ = grp;
-            asm volatile("" : "+v"(g_));
-            pa = ca_and4(pr, g_ == (unsigned)(2 * h2 + t) ? 0xFFFFFFFFu : 0u);
+          if (Y4L) {   // psi masked to row group 2 h2 + t here, not held four times over the step: four ANDs against the lane's mask (round 19; before, a compare and selects per MFMA)
+            // The lane's mask for group 2 h2 + t is one signed byte field of gsel (0xFF in byte `grp`): a single vector instruction, no lane-mask SGPR and none
+            // of its wait states.  asm volatile: the four masked images are not shared between the pieces -- sixteen registers the budget has not.
+            // (the "n" offset is a constant because the h2 and t loops are fully unrolled: this builds with optimisation on only, like the rest of the file's asm)
+            unsigned m_;
+            asm volatile("v_bfe_i32 %0, %1, %2, 8" : "=v"(m_) : "v"(gsel), "n"(8 * (2 * h2 + t)));
+            pa = ca_and4(pr, m_);
           } else {
             pa = prm[2 * h2 + t];
           }
@@ -636,7 +654,7 @@ __device__ __forceinline__ void ca_ys_mfma_body(int blk, const uint8_t* __restri
   // column products of the strip: lane (gene n = j, q), accumulator a: gene tile 4 a + q, digits r = 0..3; combine the four
   // strips of the block in LDS (integer sums: any order), one row of YTi per block
   __syncthreads();
-  int* comb = reinterpret_cast<int*>(ca_ys_lds);   // [4 waves][8 acc][64 lanes][4]: 32 KB > the 20 KB of tiles: the launch asks for 32 KB
+  int* comb = reinterpret_cast<int*>(ca_ys_lds);   // [4 waves][8 acc][64 lanes][4]: 32 KB > the 22 KB of tiles: the launch asks for 32 KB
 #pragma unroll
   for (int a = 0; a < NP; ++a)
 #pragma unroll
@@ -687,8 +705,8 @@ __global__ void __launch_bounds__(CA_YM_TB, Y4 ? CA_YS4_WAVES : CA_YS_WAVES) k_y
 }
 // (the riding forms -- k_fwd_cell_mix_ys, k_fwd_bal_ys -- are instantiated per format: the 1-byte ones are round 6's code; the 4-bit ones exist
 //  only for the series form's rank-one shapes (D = 1, no c16 / s2), whose sweeps run only in the passes the series form hands over)
-constexpr int CA_YS_LDS_BYTES = 4 * (CA_YS_GW / 64) * 64 * 4 * 4;   // the combine buffer (32 KB) >= 4 x 64 x CA_YS_PITCH (+ 4 x 64 x 8 B of the 4-bit image's row escapes)
-static_assert(4 * 64 * CA_YS_PITCH + 4 * 64 * 8 <= CA_YS_LDS_BYTES, "staging + row escapes fit the combine buffer");
+constexpr int CA_YS_LDS_BYTES = 4 * (CA_YS_GW / 64) * 64 * 4 * 4;   // the combine buffer (32 KB) >= 4 x CA_YS_STAGE (+ 4 x 64 x 8 B of the 4-bit image's row escapes)
+static_assert(4 * CA_YS_STAGE + 4 * 64 * 8 <= CA_YS_LDS_BYTES, "staging + row escapes fit the combine buffer");
 
 // Parameter images of the one-copy stream for one parameter state.  The fixed-point exponents need the largest magnitudes of W
 // and psi: lag = 0 takes them from amax_in as exact maxima (k_ym_absmax ran before: ONE pair); in the loop amax_in holds the PREVIOUS

@@ -703,6 +703,37 @@ static int get_generic(ca_handle h, const char* name, double* out, bool grad) {
 int ca_get_param(ca_handle h, const char* name, double* out) { return get_generic(h, name, out, false); }
 int ca_get_gradient(ca_handle h, const char* name, double* out) { return get_generic(h, name, out, true); }
 
+// What the one-copy count-matrix stream's last launch left, before the finisher sums it: the float partial slabs, the exponents that launch read (the slot
+// behind ys_slot: ys_finish advanced the ring) and the fixed-point values in the parameter images, reassembled from their digits as the stream's escapes do.
+int ca_ystream_parts(ca_handle h, int64_t dims[6], float* yw_part, float* yt_part, int32_t exps[2], int32_t* w_fix, int32_t* p_fix) {
+  if (!h || !dims) return CA_ERR_INVALID;
+  if (!h->y_ys || h->K != 1) { h->err = "ca_ystream_parts: this engine does not run the one-copy count-matrix stream"; return CA_ERR_INVALID; }
+  if (!h->ys_launched) { h->err = "ca_ystream_parts: no launch of the count-matrix stream yet (ca_elbo / ca_gradients / a loop call makes one)"; return CA_ERR_STATE; }
+  HIPCK(h, hipSetDevice(h->device));
+  CACK(gate_close(h));
+  CACK(wait_y(h, true));   // (a launch still running on the side stream: the copies below are ordered behind it; the results it is awaited for stay as they are)
+  const int64_t N = h->N, Gp = h->Gp, N64 = h->ys_N64;
+  dims[0] = h->ys_nseg; dims[1] = N; dims[2] = h->ys_nrg; dims[3] = Gp; dims[4] = h->ys_RS;
+  dims[5] = (h->ycache_valid && !h->ys_quant_ready) ? 1 : 0;   // the images are still the ones that launch read
+  if (yw_part) HIPCK(h, hipMemcpyAsync(yw_part, h->YWpart, (size_t)(h->ys_nseg * N) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (yt_part) HIPCK(h, hipMemcpyAsync(yt_part, h->YTpart, (size_t)(h->ys_nrg * Gp) * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+  if (exps) HIPCK(h, hipMemcpyAsync(exps, h->ys_exps + 2 * ((h->ys_slot + 2) % 3), 2 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  std::vector<signed char> wi(w_fix ? (size_t)Gp * 16 : 0), pi(p_fix ? (size_t)N64 * 16 : 0);
+  if (w_fix) HIPCK(h, hipMemcpyAsync(wi.data(), h->Wr, wi.size(), hipMemcpyDeviceToHost, h->stream));
+  if (p_fix) HIPCK(h, hipMemcpyAsync(pi.data(), h->Pr, pi.size(), hipMemcpyDeviceToHost, h->stream));
+  SYNC(h);
+  // entry i of an image: step i >> 6, lanes 16 ((i >> 4) & 3) + p hold digit p of it in byte i & 15; x = sum_p d_p 256^p, d_p signed
+  auto fix = [](const std::vector<signed char>& img, int64_t n, int32_t* out) {
+    for (int64_t i = 0; i < n; ++i) {
+      const signed char* d = img.data() + ((i >> 6) * 64 + 16 * ((i >> 4) & 3)) * 16 + (i & 15);
+      out[i] = (int32_t)((int64_t)d[0] + (int64_t)d[16] * 256 + (int64_t)d[32] * 65536 + (int64_t)d[48] * 16777216);
+    }
+  };
+  if (w_fix) fix(wi, Gp, w_fix);
+  if (p_fix) fix(pi, N64, p_fix);
+  return CA_OK;
+}
+
 int ca_set_param(ca_handle h, const char* name, const double* in) {
   if (!h || !name || !in) return CA_ERR_INVALID;
   CA_NOT_IN_RUN(h);

@@ -69,6 +69,8 @@ EXPORTS = (
     # gene-reweighted log-likelihood for every replicate of a bootstrap, votes and shares reduced on the device (clone_loglik_reweighted / bootstrap_assignments),
     # additions to ABI 6
     "ca_clone_loglik_reweighted", "ca_group_clone_loglik_reweighted", "ca_reweighted_kernel_ms",
+    # the count-matrix stream's partial slabs, exponents and fixed-point images, read-only (ystream_parts), addition to ABI 6
+    "ca_ystream_parts",
 )
 CA_BOOT_RCHUNK = 32   # replicates per chunk of ca_clone_loglik_reweighted (include/clonealign_hip.h)
 
@@ -170,6 +172,7 @@ def load_library(path=None):
     lib.ca_get_info.argtypes = [C.c_void_p, C.POINTER(CaInfo)]
     lib.ca_synchronize.argtypes = [C.c_void_p]
     lib.ca_stream_busy.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.ca_ystream_parts.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_comm_unique_id.argtypes = [C.c_char_p]
     lib.ca_comm_init.argtypes = [C.c_void_p, C.c_char_p]
     lib.ca_p2p_export.argtypes = [C.c_void_p, C.c_char_p]
@@ -938,6 +941,19 @@ class HipEngine:
         b = C.c_int32()
         self._ck(self.lib.ca_stream_busy(self.h, C.byref(b)))
         return bool(b.value)
+
+    def ystream_parts(self):
+        """What the count-matrix stream's last launch left, before its finisher (ca_ystream_parts; read-only): ``yw_part`` [nseg, N] and ``yt_part`` [nrg, Gp]
+        float32, ``exps`` (W, psi), ``strip_cells`` (a row group of yt_part is four strips), the fixed-point values in the parameter images now (``w_fix`` [Gp], ``p_fix`` [N64], int32) and ``images_current`` -- whether
+        those are the images that launch read.  include/clonealign_hip.h states each."""
+        dims = (C.c_int64 * 6)()
+        self._ck(self.lib.ca_ystream_parts(self.h, dims, None, None, None, None, None))
+        nseg, N, nrg, Gp, RS, _cur = (int(d) for d in dims)
+        N64 = -(-N // 64) * 64
+        yw, yt = np.empty((nseg, N), np.float32), np.empty((nrg, Gp), np.float32)
+        exps, wf, pf = np.empty(2, np.int32), np.empty(Gp, np.int32), np.empty(N64, np.int32)
+        self._ck(self.lib.ca_ystream_parts(self.h, dims, *(a.ctypes.data_as(C.c_void_p) for a in (yw, yt, exps, wf, pf))))
+        return {"yw_part": yw, "yt_part": yt, "exps": exps, "w_fix": wf, "p_fix": pf, "strip_cells": RS, "images_current": bool(dims[5])}
 
     # -------------------------------------------------------------- fetch / poke
     def _shape(self, name):

@@ -306,6 +306,17 @@ int ca_synchronize(ca_handle h);
 /* *busy = 1 while work queued on the engine's stream has not completed, else 0; never blocks, never changes anything (a poll hook can
  * watch the device drain while it holds the loop up). */
 int ca_stream_busy(ca_handle h, int32_t* busy);
+/* Read-only, for tests and diagnostics: what the last launch of the one-copy count-matrix stream (K = 1; ca_info.y_mfma = 2) left, before its finisher sums it.
+ * CA_ERR_INVALID on an engine without that stream, CA_ERR_STATE before its first launch (ca_elbo / ca_gradients / a loop call makes one).  Changes no result; a
+ * launch still running on the engine's side stream is waited for.  dims = {nseg, N, nrg, Gp, RS, images_current}, N64 = N rounded up to 64; every other pointer may be NULL (call once for dims).
+ *   yw_part [nseg][N]  float: the segment's (512 genes) share of (Y W)_n, = (float)(v 2^-exps[0]), v = sum_g min(y_ng, 255) fix(W_g) as an exact integer
+ *   yt_part [nrg][Gp]  float: the row group's (4 strips of RS cells) share of (Y^T psi)_g, = (float)(v 2^-exps[1]), v = sum_n min(y_ng, 255) fix(psi_n)
+ *                      (counts above 255 keep 255 in the resident matrix; their excess goes through the overflow list, outside these slabs)
+ *   exps    [2]        the fixed-point exponents that launch read (W, psi)
+ *   w_fix [Gp], p_fix [N64]  the fixed-point values in the parameter images NOW, fix(x) = rint(x 2^exp), zero past G and N.  images_current = 1: they are
+ *                      the ones that launch read (after ca_gradients / ca_elbo); 0: the parameters have moved since (after ca_step / ca_iterate / ca_run: the
+ *                      loop's update quantises the new state), and fix() of the state before the step reproduces them from exps. */
+int ca_ystream_parts(ca_handle h, int64_t dims[6], float* yw_part, float* yt_part, int32_t exps[2], int32_t* w_fix, int32_t* p_fix);
 
 /* cell-sharded multi-GPU (one process per GPU): RCCL communicator over xGMI.
  * Rank 0 calls ca_comm_unique_id() and distributes the 128 bytes out of band. */
