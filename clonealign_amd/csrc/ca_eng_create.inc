@@ -594,6 +594,15 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   h->cell_lean = h->poly && variant_on(h, CA_VAR_CELL_LEAN, "CA_CELL_LEAN");
   // ... and with its backward moments gathered by fp64 MFMA per wave instead of the thread-owned chain between two block barriers (CA_VAR_CELL_MFMA): likewise
   h->cell_mfma = h->poly && variant_on(h, CA_VAR_CELL_MFMA, "CA_CELL_MFMA");
+  // ... and the way back from it: the stream's column jobs off the cell launch, reduction + per-gene pass + column jobs as one launch (CA_VAR_GENE_RIDE,
+  // ca_polygene.hip.h); which order a pass takes is decided where it is queued (gene_ride_merges: a cell-sharded fit keeps the two launches)
+  h->gene_ride = h->poly && variant_on(h, CA_VAR_GENE_RIDE, "CA_GENE_RIDE");
+  // ... and whether the stream's column jobs leave the cell launch with it.  Measured (profiles/r22_tail_ab.txt (B), merged launch alone against merged launch + moved
+  // columns, alternating): 25k / 50k x 5k x 8 and 50k x 3k x 6 gain 2.0 - 2.4 us per iteration from the move (cell launch 16.7 -> 14.1 and 20.1 -> 18.2 us), 12.5k is
+  // level, and at 100 000 cells (x 8 and x 4 clones) the move LOSES 0.3 - 0.7: there the cell launch is no shorter without them (28.3 us either way) and they sit at
+  // the end of the way back, in front of the update that reads their sums.  The rule is the cell count between the measured shapes; what decides it inside the cell
+  // launch -- which block ends it -- has not been stamped (DESIGN section 10).  ca_options.reserved[1] = 7 / 8 (lab) keeps / moves them whatever the rule says.
+  h->gene_cols = h->gene_ride && (h->opt.reserved[1] == 8 || (h->opt.reserved[1] != 7 && Nn <= CA_GENE_COLS_MAXN));
   // the Y stream rides on the forward sweep's launch: 1-byte storage, K = 1, the fused sweep with its default block shapes
   h->ride_ok = h->ystore == CA_YSTORE_U8 && K == 1 && D <= 2 && h->fused_ok && !h->c16 && h->fwd_cell && (h->fc_tl == 6 || h->fc_tl == 8 || (h->fc_tl == 2 && h->fc_nbig == 0)) &&
                !h->y_ys && variant_on(h, CA_VAR_Y_RIDE, "CA_Y_RIDE");

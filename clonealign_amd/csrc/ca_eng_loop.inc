@@ -38,7 +38,7 @@ int refresh_derived(ca_engine* h) {
   CACK(make_etamax(h));
   h->gaux_slot = -1;
   h->ycache_valid = false;
-  h->yfin_pending = false;
+  h->yfin_pending = false; h->ycol_pending = false;
   h->look_valid = false;
   h->poly_fresh = false;
   h->poly_seq_base = h->poly_seq + 1;   // (an arbitrary parameter change: ranges seen before it say nothing)
@@ -72,8 +72,10 @@ ca_yfin_args yfin_args(ca_engine* h, int rows, int nseg) {
   a.YWpart = h->YWpart; a.nseg = nseg + (h->n_ovf > 0 ? 1 : 0); a.F = h->F; a.D = h->D; a.N = h->N; a.YW = h->YW; a.yw_part = h->yw_part;
   return a;
 }
-int launch_yfinish(ca_engine* h, int rows, int nseg) {
-  const ca_yfin_args a = yfin_args(h, rows, nseg);
+// (cols_only: the column sums alone -- the row jobs of this stream launch are done, CA_VAR_GENE_RIDE)
+int launch_yfinish(ca_engine* h, int rows, int nseg, bool cols_only = false) {
+  ca_yfin_args a = yfin_args(h, rows, nseg);
+  if (cols_only) a.nrow = 0;
   LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_yfinish, dim3(a.ncol + a.nrow), dim3(1024), 0, h->stream, a.part, a.out, a.rows, a.ld, a.cols, a.col_chunk_ptr,
                                                 a.csum, h->K, a.G, a.ncol, a.YWpart, a.nseg, a.F, a.D, a.N, a.YW, a.yw_part));
   return CA_OK;
@@ -127,7 +129,14 @@ ca_ys_io ys_io(ca_engine* h) {
 }
 ca_ovf_args ys_ovf(ca_engine* h) { return ovf_args(h, h->YWpart + (int64_t)h->ys_nseg * h->N); }
 // finisher of the one-copy stream: the vector stream's own (k_yfinish) over the float partial slabs the stream left
+// (ycol_pending: the series form's cell launch has run the row jobs, the column jobs were to ride on its merged way back, which has not been queued -- the consumer
+//  that comes first gets them as a launch: k_yfinish's column blocks, bitwise the riding waves' sums)
 int yfin_flush(ca_engine* h) {
+  if (h->ycol_pending && !h->yfin_pending) {
+    h->ycol_pending = false;
+    return launch_yfinish(h, h->ys_nrg, h->ys_nseg, true);
+  }
+  h->ycol_pending = false;
   if (!h->yfin_pending) return CA_OK;
   h->yfin_pending = false;
   return launch_yfinish(h, h->ys_nrg, h->ys_nseg);
@@ -135,7 +144,7 @@ int yfin_flush(ca_engine* h) {
 // the stream's slabs are complete (launch issued): finisher now, or left pending for the backward sweep that follows in the loop;
 // advances the quantiser's slot ring
 int ys_finish(ca_engine* h, bool defer = false) {
-  h->yfin_pending = true;
+  h->yfin_pending = true; h->ycol_pending = false;
   if (!defer) CACK(yfin_flush(h));
   h->ys_slot = (h->ys_slot + 1) % 3;   // (the only place the ring advances: ca_ystream_parts finds the launch's exponents one slot back)
   h->ys_launched = true;
@@ -200,7 +209,7 @@ int ensure_ycache(ca_engine* h) {
     return CA_OK;
   }
   if (h->ycache_valid || h->K == 0) { h->ycache_valid = true; return yfin_flush(h); }
-  h->yfin_pending = false;
+  h->yfin_pending = false; h->ycol_pending = false;
   if (h->y_ys) return ycache_ys(h);
   dim3 grid((unsigned)((int64_t)h->nrg * h->nseg));
   // entries above 255: one extra "segment" of YW and one extra term of Y^T psi; their per-entry work rides on the
@@ -300,6 +309,14 @@ int train_bwd(ca_engine* h, const float* mu32, bool cell_sums_global) {
   if (h->poly_fresh) {   // the backward moments of this look-ahead half are in the workspace: per-gene sums straight into red (no slabs, no column sums)
     h->poly_fresh = false;
     h->fold_now = false;
+    // CA_VAR_GENE_RIDE: the reduction of those moments is not queued yet where this pass takes the merged way back (fused_pass decided); it comes with the per-gene
+    // pass below, and so do the stream's column jobs if they are still pending.  (Sharded since the forward half, which cannot happen inside a fit: the launch now.)
+    const bool merged_back = h->red_pending && gene_ride_merges(h);
+    if (h->red_pending && !merged_back) HIPCK(h, ca_poly_reduce(h->stream, &h->pws, h->N, h->C, nullptr, nullptr, nullptr, 0, h->F, nullptr, 0, 1));
+    h->red_pending = false;
+    ca_yfin_args back_cols;
+    memset(&back_cols, 0, sizeof(back_cols));
+    if (merged_back && h->ycol_pending && !h->yfin_pending) { back_cols = yfin_args(h, h->ys_nrg, h->ys_nseg); back_cols.nrow = 0; h->ycol_pending = false; }
     CACK(yfin_flush(h));
     // a pending monitor pass's tail (reduction of the cell partials into red -- which this pass's alpha step reads --, psi.(YW) sum, ELBO assembly) rides as
     // an extra block of the per-gene launch, as it does on the matrix-core way back; sharded it is a collective of its own
@@ -339,7 +356,13 @@ int train_bwd(ca_engine* h, const float* mu32, bool cell_sums_global) {
     }
     else if (h->mon_tail.enabled) { CACK(wait_y(h, false)); bwd_tail = h->mon_tail; h->mon_tail.enabled = 0; }   // (reserved[1] = 6: whole, lab)
     CACK(prof_begin(h, CA_KERNEL_BWD));
-    const hipError_t e = ca_poly_backward(h->stream, &h->pws, h->V, mu32, h->Lb, h->G, h->C, h->red + h->off_g, &bwd_tail);
+    hipError_t e;
+    if (merged_back) {
+      if (++h->gene_tag == 0u) h->gene_tag = 1u;
+      // (0.5 s: every reducer a gene block waits for has a lower block index and depends on nobody in the launch, ca_polygene.hip.h)
+      e = ca_poly_backward_merged(h->stream, &h->pws, h->V, mu32, h->Lb, h->G, h->C, h->red + h->off_g, &bwd_tail, back_cols.ncol > 0 ? &back_cols : nullptr,
+                                  h->poly_nb_ub, h->gene_tag, 50000000ull, reinterpret_cast<unsigned int*>(h->host_dev + 44));
+    } else e = ca_poly_backward(h->stream, &h->pws, h->V, mu32, h->Lb, h->G, h->C, h->red + h->off_g, &bwd_tail);
     HIPCK(h, e);
     CACK(prof_end(h));
     h->poly_df = true;
@@ -360,6 +383,7 @@ int train_bwd(ca_engine* h, const float* mu32, bool cell_sums_global) {
     // pending monitor pass needs is added to its cell sum INSIDE the all-reduce's launch, and so are the column sums of this sweep's
     // slabs -- fwd, bwd, all-reduce, update: four launches where there were six.  Other transports keep the launches.
     ride_ar = is_sharded(h) && p2p_ride_ok(h, h->red_n);
+    if (h->ycol_pending) CACK(yfin_flush(h));   // (column sums a series pass left for a merged way back that never came: this sweep's update reads them)
     if (is_sharded(h) && !ride_ar) CACK(yfin_flush(h));   // (the tail's local sums go into this pass's all-reduce, so they stay here)
     if (h->yfin_pending) { yfin = yfin_args(h, h->ys_nrg, h->ys_nseg); h->yfin_pending = false; }
     ca_small_args bwd_tail = no_small_args();
@@ -510,7 +534,7 @@ void adam_stepped(ca_engine* h, bool xmax_ready) {
   h->poly_xmax_ready = xmax_ready;
   if (h->poly_xglob_steps >= 0) h->poly_xglob_steps += 1;
   h->ycache_valid = false;
-  h->yfin_pending = false;
+  h->yfin_pending = false; h->ycol_pending = false;
   h->look_valid = false;
   if (h->poly && h->y_ys && h->K > 0) h->poly_y_defer = true;   // series form: the next series pass sends the count-matrix products of the stepped state to the side stream
 }
@@ -770,6 +794,7 @@ int poly_guard(ca_engine* h, bool* use_series, double** mirror, double* seq, boo
     steps = (int)(h->adam_steps - h->poly_steps_at[(s - CA_POLY_LAG) % 16]);
   }
   *use_series = ca_poly_covers(r[0], r[1], r[2], steps, poly_step_bound(h));
+  h->poly_nb_ub = *use_series ? ca_poly_nb_ahead(r[0], r[1], r[2], steps, poly_step_bound(h)) : 0;   // (sizes the merged way back's grid, enters no result)
   h->poly_seq = s;
   h->poly_steps_at[s % 16] = h->adam_steps;
   return CA_OK;
@@ -892,7 +917,9 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     }
     // (the stream's finisher stays in line behind it: on the side stream beside the cell launch its 1024-thread blocks got through late -- 198 against 187 us
     //  per iteration at cfg-3, 110 against 102 at 50k x 3k x 6)
-    // ... nor as its own launch in line (5.4 us and a gap): its jobs ride as extra blocks of the cell launch, as they do on the backward sweep's
+    // ... nor as its own launch in line (5.4 us and a gap): its jobs ride as extra blocks -- the row jobs behind the cell launch's cell blocks, in the slots the
+    // blocks with one pass fewer leave (a finisher block is that kernel with its 207 - 241 VGPRs: it cannot run beside two cell blocks on a CU); the column jobs,
+    // whose sums nobody reads before the update, on the launch that follows (CA_VAR_GENE_RIDE; off: behind the cell blocks too, as they were)
     h->ys_defer_next = h->y_ys && !h->ycache_valid && h->opt.reserved[1] != 3;   // (reserved[1] = 3: the finisher as a launch of its own, lab)
     const int yrc = ensure_ycache(h);
     const bool mom_left = h->mom_args != nullptr;
@@ -901,6 +928,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     if (mom_left) { h->err = "internal: the series form's moments were to ride on a count-matrix stream launch that was not made"; return CA_ERR_STATE; }
     h->ys_defer_next = false;
     ca_yfin_args yfin_ride;
+    memset(&yfin_ride, 0, sizeof(yfin_ride));
     const bool yfin_rides = h->yfin_pending;
     if (yfin_rides) { yfin_ride = yfin_args(h, h->ys_nrg, h->ys_nseg); h->yfin_pending = false; }
     if (moments_aside) HIPCK(h, hipStreamWaitEvent(h->stream, h->ev_poly1, 0));
@@ -915,9 +943,18 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
       if (h->K > 0) { ltail.yw_part = h->yw_part; ltail.n_yw = h->n_yw; }
       ltail.reduce_only = 1; ltail.host_out = nullptr;
     }
-    e = ca_poly_cells(h->stream, &h->pws, h->N, h->C, h->K, &cp, h->alpha_u, h->cell_part, h->dFpart, yfin_rides ? &yfin_ride : nullptr,
-                      sh ? &ltail : nullptr, h->poly_xmax_ready ? h->poly_xpart : nullptr, (int)cdiv(h->N, CA_TB), h->F, sh ? h->red + h->off_x : nullptr,
-                      h->opt.rank, std::max(h->opt.world, 1), h->cell_lean, h->cell_mfma);
+    // CA_VAR_GENE_RIDE: the column jobs go with the reduction -- with the merged way back that train_bwd queues (unsharded), else as extra blocks of k_poly_red here
+    const bool cols_move = yfin_rides && h->gene_cols;   // (the measured rule of create_impl: not at 100 000 cells, where the cell launch hides them)
+    const bool merges = gene_ride_merges(h);
+    ca_yfin_args yfin_cols = yfin_ride;
+    if (cols_move) yfin_ride.ncol = 0;
+    e = ca_poly_cells(h->stream, &h->pws, h->N, h->C, h->K, &cp, h->alpha_u, h->cell_part, h->dFpart, yfin_rides ? &yfin_ride : nullptr, h->cell_lean, h->cell_mfma);
+    // the ONE place that decides where the reduction of the backward moments runs: here, as a launch (with the sharded fit's riders), or inside train_bwd's launch
+    h->red_pending = merges;
+    if (merges) h->ycol_pending = cols_move;
+    else if (e == hipSuccess)
+      e = ca_poly_reduce(h->stream, &h->pws, h->N, h->C, cols_move ? &yfin_cols : nullptr, sh ? &ltail : nullptr, h->poly_xmax_ready ? h->poly_xpart : nullptr,
+                         (int)cdiv(h->N, CA_TB), h->F, sh ? h->red + h->off_x : nullptr, h->opt.rank, std::max(h->opt.world, 1));
     h->mon_tail_local = sh;   // (the tail set up below starts with its local sums made)
     if (sh) { h->poly_xslot_pending = true; h->poly_xglob_steps = -1; }   // (the slots hold THIS rank's number until the collective has summed them)
     HIPCK(h, e);

@@ -1,6 +1,9 @@
 // ca_eng_reduce.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): the transports' all-reduce of a device vector (peer-to-peer launch with its riders, host callback, RCCL).
 // does a transport reduce this engine's sums over the ranks?
 inline bool is_sharded(const ca_engine* h) { return h->opt.world > 1 || h->comm || h->host_ar || (h->p2p && h->p2p->connected); }
+// CA_VAR_GENE_RIDE: does a series pass take the merged way back (reduction + per-gene pass + column jobs in one launch, ca_polygene.hip.h)?  Not a cell-sharded
+// fit: its collective sits between the reduction and the per-gene pass.  Not without the mapped host word the bounded wait reports to.
+inline bool gene_ride_merges(const ca_engine* h) { return h->gene_ride && !is_sharded(h) && h->host_dev != nullptr; }
 // work that rides in the peer-to-peer all-reduce's launch instead of getting launches of its own in front of it (ca_p2p_args)
 struct ca_ar_ride {
   const float* gpart = nullptr; int nslice = 0; int64_t fold_lo = 0, fold_n = 0;

@@ -69,6 +69,9 @@ inline double ca_adam_step_bound(double lr, double b1, double b2) {
   for (int t = 1; t <= 200000; ++t) { p1 *= b1; p2 *= b2; sup = std::max(sup, std::sqrt(1.0 - p2) / (1.0 - p1)); }
   return lr * sup * (1.0 - b1) / std::sqrt((1.0 - b2) * (1.0 - b1 * b1 / b2));
 }
+#ifndef CA_GENE_COLS_MAXN
+#define CA_GENE_COLS_MAXN 65536   // cells up to which the stream's column jobs leave the series form's cell launch (CA_VAR_GENE_RIDE, see create_impl)
+#endif
 struct ca_engine {
   // ---- problem
   int64_t N = 0;
@@ -174,6 +177,13 @@ struct ca_engine {
   bool mom_last = false, mom_ovf_first = false; int mom_free_slots = 0, mom_per = CA_MOM_PER, mom_nred = CA_MOM_NRED;
   bool cell_mfma = false;   // ... with the backward moments of its register bins gathered by fp64 MFMA per wave (CA_VAR_CELL_MFMA, k_poly_cell<CP, LEAN, true>)
   bool cell_lean = false;   // the series form's cell launch in its lean form (CA_VAR_CELL_LEAN, ca_poly.hip k_poly_cell<CP, true>)
+  // CA_VAR_GENE_RIDE (ca_polygene.hip.h): the stream's column jobs leave the cell launch, and an unsharded pass runs reduction + per-gene pass + column jobs as one
+  // launch from train_bwd.  red_pending: the cell launch of the look-ahead half poly_fresh refers to is queued, its reduction is not (it comes with the per-gene pass);
+  // ycol_pending: the column sums of the current stream launch are still to be made (the row jobs are done) -- yfin_flush gives any earlier consumer the launch;
+  // poly_nb_ub: the bin count can be no more than this (poly_guard's look ahead): sizes the reducers' share of the merged grid, enters no result
+  // gene_cols: the column jobs go with the reduction (the rule in create_impl: up to CA_GENE_COLS_MAXN cells); else they stay behind the cell launch's blocks
+  bool gene_cols = false;
+  bool gene_ride = false, red_pending = false, ycol_pending = false; unsigned gene_tag = 0; int poly_nb_ub = 0;
   bool poly = false, poly_side = false, poly_y_defer = false, poly_fresh = false, poly_df = false /* the last backward half was the series form's: d/dF is ONE slab */; ca_poly_ws pws; float* poly_zero = nullptr; unsigned char* poly_mem = nullptr;
   float *Mb2 = nullptr, *mu32B = nullptr, *Zpart2 = nullptr; double* gene_partB = nullptr;
   bool y_defer = false;
@@ -264,6 +274,10 @@ int comm_check(ca_engine* h) {
   }
   if (h->host_pinned && *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 43) != 0u) {
     h->err = "a reducer block of the series form's moment role gave up waiting for the moment blocks of its launch (k_ys_mfma_mom); the engine's state is undefined";
+    return CA_ERR_STATE;
+  }
+  if (h->host_pinned && *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 44) != 0u) {
+    h->err = "a gene block of the series form's merged way back gave up waiting for the reducer blocks of its launch (k_poly_tail); the engine's state is undefined";
     return CA_ERR_STATE;
   }
   if (h->host_pinned && *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 42) != 0u) {

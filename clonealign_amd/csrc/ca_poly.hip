@@ -131,9 +131,12 @@ template <int CP, bool LEAN, bool MFMA>
 __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restrict__ hdr, const double* __restrict__ tabB, ca_cell_ptrs p,
                                                      const float* __restrict__ alpha_u, double* __restrict__ cell_part, int64_t N, int C, int K,
                                                      float* __restrict__ dF /*[N]*/, double* __restrict__ Qpart /*[grid][nb][R+2][C]*/, int ncb, ca_yfin_args yfin) {
-  // Blocks behind the ncb cell blocks finish the count-matrix stream's two products (column sums, row sums and psi.(YW) partials: what k_yfinish does as a
-  // launch of its own, 5.4 us and a launch gap on the iteration's critical path): nothing in this launch reads them, the per-gene launch that follows does.
-  // The cell blocks are two to a CU and live as long as the launch; these few hundred short blocks take the free slots beside them.
+  // Blocks behind the ncb cell blocks finish the count-matrix stream's products (what k_yfinish does as a launch of its own, 5.4 us and a launch gap on the
+  // iteration's critical path): nothing in this launch reads them.  They are this kernel with this kernel's registers (207 - 241 VGPRs: two blocks per CU, and the
+  // cell blocks are two to a CU), so none of them runs BESIDE a cell block: each starts in a slot a cell block has left.  The row jobs (YW and the psi.(YW)
+  // partials, which the launch that follows reads) are one round of loads and a block sum, short enough for the slots the blocks with one pass fewer leave.  The
+  // column jobs are four dependent rounds of loads per wave and nobody reads their sums before the update: with CA_VAR_GENE_RIDE they ride on the launch that
+  // follows (k_poly_tail, or k_poly_red where the reduction keeps its launch) and yfin.ncol is 0 here; off, they stay as they were.
   if ((int)blockIdx.x >= ncb) {
     const int e = (int)blockIdx.x - ncb;
     const int ncolblk = (yfin.ncol + CA_TB / 64 - 1) / (CA_TB / 64);
@@ -359,14 +362,24 @@ __device__ __forceinline__ void ca_poly_xslot_body(const ca_xslot_args& a) {
   __syncthreads();
   if ((int)threadIdx.x < a.world) a.slots[threadIdx.x] = (int)threadIdx.x == a.rank ? (double)fmaxf(fmaxf(sx[0], sx[1]), fmaxf(sx[2], sx[3])) : 0.0;
 }
-// (nred: the blocks that reduce; a cell-sharded fit adds up to two more behind them -- the pending monitor pass's local block sums (a ca_small_args with
-//  reduce_only) and this rank's max |x| slot -- what would otherwise be two small launches in front of the iteration's collective)
+// (nred: the blocks that reduce; a cell-sharded fit adds two more behind them -- the pending monitor pass's local block sums (a ca_small_args with
+//  reduce_only) and this rank's max |x| slot -- what would otherwise be two small launches in front of the iteration's collective.  Behind those `nfix` blocks:
+//  the count-matrix stream's column jobs, four to a block, where the reduction keeps a launch of its own and CA_VAR_GENE_RIDE moves them off the cell launch --
+//  a cell-sharded fit, whose collective carries their sums.  COLS = false: no such jobs -- the forward moments' reduction, and every reduction with the switch
+//  off: the launch as it was, registers and all; the column waves' 32 loads in flight per lane are compiled into the form that runs them only)
+template <bool COLS>
 __global__ void __launch_bounds__(CA_TB) k_poly_red(const double* __restrict__ part, int nblk, int64_t stride, const ca_poly_hdr* __restrict__ hdr, int per_bin,
                                                     int mode, int C, double* __restrict__ out, unsigned int* __restrict__ xbits, int nred, ca_small_args tail,
-                                                    ca_xslot_args xs) {
+                                                    ca_xslot_args xs, int nfix, ca_yfin_args yfin) {
   if ((int)blockIdx.x >= nred) {
     const int e = (int)blockIdx.x - nred;
-    if (e == 0 && tail.enabled) ca_final_small_body(tail);
+    if (COLS && e >= nfix) {
+      if constexpr (COLS) {
+        const int job = (e - nfix) * (CA_TB / 64) + (int)(threadIdx.x >> 6);
+        if (job < yfin.ncol) ca_yfin_col_wave(yfin, job);
+      }
+    }
+    else if (e == 0 && tail.enabled) ca_final_small_body(tail);
     else if (xs.slots) ca_poly_xslot_body(xs);
     return;
   }
@@ -374,57 +387,18 @@ __global__ void __launch_bounds__(CA_TB) k_poly_red(const double* __restrict__ p
   ca_pm_red_body<false>(part, nblk, stride, hdr->nb * per_bin, mode, C, out, blockIdx.x * (CA_TB / 64) + (threadIdx.x >> 6), nred * (CA_TB / 64));
 }
 
-// ---- K3: per gene: the two gradient sums from its bin's polynomial ---------------------------------------------------------------------------------
+#include "ca_polygene.hip.h"    // the per-gene body, and the launch that runs reduction, per-gene pass, monitor tail and column jobs as one grid (CA_VAR_GENE_RIDE)
+
+// ---- K3: per gene: the two gradient sums from its bin's polynomial (ca_pg_gene_block), as a launch of its own behind k_poly_red ---------------------------------
 __global__ void __launch_bounds__(CA_TB) k_poly_gene(const ca_poly_hdr* __restrict__ hdr, const double* __restrict__ tabQ, const float* __restrict__ V,
                                                      const float* __restrict__ mu, const float* __restrict__ Lb, int G, int C,
                                                      double* __restrict__ red_g /*[G][2]: d/dmu, d/dV*/, ca_small_args tail, int ngblk) {
-  constexpr int RQ = R + 2;
   if ((int)blockIdx.x >= ngblk) {   // a pending monitor pass's tail (cell partials -> red, psi.(YW) sum, ELBO assembly): the extra block, as on the matrix-core way back
     if (tail.enabled) ca_final_small_body(tail);
     return;
   }
-  // The moment tables of the first NBL bins (the usual case has one to three) in LDS: a gene reads 176 doubles of its bin's table, and from global memory that
-  // was a chain of 320 dependent-latency loads per thread -- the 11.9 us this launch took.  One load per step: T_{k+1} of a step is T_k of the one before.
-  constexpr int NBL = CA_PL_NBL;
-  __shared__ double s_tq[NBL][RQ * 8];
-  const int nb = hdr->nb;
-  const double vlo = hdr->vlo, delta = hdr->delta;
-  for (int i = threadIdx.x; i < (nb < NBL ? nb : NBL) * RQ * C; i += CA_TB) s_tq[i / (RQ * C)][i % (RQ * C)] = tabQ[i];
-  __syncthreads();
-  const int g = blockIdx.x * CA_TB + threadIdx.x;
-  if (g >= G) return;
-  const double v = (double)V[g];
-  int b = (int)floor((v - vlo) / delta);
-  b = b < 0 ? 0 : (b >= nb ? nb - 1 : b);
-  const double dv = v - (vlo + ((double)b + 0.5) * delta);
-  float lrow[8];
-  {
-    const float4 l0 = *reinterpret_cast<const float4*>(Lb + (int64_t)g * CA_CW), l1 = *reinterpret_cast<const float4*>(Lb + (int64_t)g * CA_CW + 4);
-    lrow[0] = l0.x; lrow[1] = l0.y; lrow[2] = l0.z; lrow[3] = l0.w; lrow[4] = l1.x; lrow[5] = l1.y; lrow[6] = l1.z; lrow[7] = l1.w;
-  }
-  double s0 = 0.0, s1 = 0.0;
-  // q = sum_{k <= R} dv^k T_k;  q' = sum_{k <= R} dv^k (k + 1) T_{k+1}   (T_k = Q_k / k!)
-#define CA_PL_GENE(TQ)                                                            \
-  _Pragma("unroll")                                                               \
-  for (int c = 0; c < 8; ++c) {                                                   \
-    if (c < C) {                                                                  \
-      double tn = (TQ)[(R + 1) * C + c], tk = (TQ)[R * C + c];                    \
-      double q = tk, dq = (double)(R + 1) * tn;                                   \
-      _Pragma("unroll 10")                                                        \
-      for (int k = R - 1; k >= 0; --k) {                                          \
-        tn = tk; tk = (TQ)[k * C + c];                                            \
-        q = q * dv + tk;                                                          \
-        dq = dq * dv + (double)(k + 1) * tn;                                      \
-      }                                                                           \
-      const double l = (double)lrow[c];                                           \
-      s0 += l * q; s1 += l * dq;                                                  \
-    }                                                                             \
-  }
-  if (nb <= NBL) { CA_PL_GENE(s_tq[b]) }   // (uniform)
-  else { const double* tq = tabQ + (int64_t)b * RQ * C; CA_PL_GENE(tq) }
-#undef CA_PL_GENE
-  red_g[(int64_t)g * 2 + 0] = s0;
-  red_g[(int64_t)g * 2 + 1] = (double)mu[g] * s1;
+  __shared__ double s_tq[CA_PL_NBL][(R + 2) * 8];
+  ca_pg_gene_block<false>(hdr, tabQ, V, mu, Lb, G, C, red_g, (int)blockIdx.x, s_tq, nullptr, nullptr);
 }
 
 inline int cdiv_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
@@ -434,7 +408,7 @@ using namespace ca_series;
 
 size_t ca_poly_workspace_bytes(int G, int n_cell_blocks) {
   const size_t nbg = (size_t)cdiv_i(G, GPB);
-  return sizeof(ca_poly_hdr) + 64 + ((nbg * sizeof(unsigned int) + 63) / 64) * 64 + sizeof(double) * ((size_t)NB * (R + 1) * 16 * (nbg + 1) + (size_t)NB * (R + 2) * 8 * ((size_t)n_cell_blocks + 1));
+  return sizeof(ca_poly_hdr) + 64 + ((nbg * sizeof(unsigned int) + 63) / 64) * 64 + CA_PL_NGFLAG * sizeof(unsigned int) + sizeof(double) * ((size_t)NB * (R + 1) * 16 * (nbg + 1) + (size_t)NB * (R + 2) * 8 * ((size_t)n_cell_blocks + 1));
 }
 
 void ca_poly_bind(ca_poly_ws* w, void* base, int G, int n_cell_blocks) {
@@ -443,6 +417,7 @@ void ca_poly_bind(ca_poly_ws* w, void* base, int G, int n_cell_blocks) {
   w->xbits = reinterpret_cast<unsigned int*>(q); q += 64;
   const size_t nbg = (size_t)cdiv_i(G, GPB);
   w->mflags = reinterpret_cast<unsigned int*>(q); q += ((nbg * sizeof(unsigned int) + 63) / 64) * 64;   // (the moment role's tags, ca_polymom.hip.h: zeroed with the workspace)
+  w->gflags = reinterpret_cast<unsigned int*>(q); q += CA_PL_NGFLAG * sizeof(unsigned int);   // (the merged way back's tags, ca_polygene.hip.h: likewise)
   w->tabB = reinterpret_cast<double*>(q); q += sizeof(double) * (size_t)NB * (R + 1) * 16;
   w->partB = reinterpret_cast<double*>(q); q += sizeof(double) * (size_t)NB * (R + 1) * 16 * nbg;
   w->tabQ = reinterpret_cast<double*>(q); q += sizeof(double) * (size_t)NB * (R + 2) * 8;
@@ -484,14 +459,15 @@ hipError_t ca_poly_moments(hipStream_t st, const ca_poly_ws* w, const float* V, 
   {
     ca_small_args no_tail; memset(&no_tail, 0, sizeof(no_tail));
     ca_xslot_args no_xs; memset(&no_xs, 0, sizeof(no_xs));
-    hipLaunchKernelGGL(k_poly_red, dim3(256), dim3(CA_TB), 0, st, w->partB, w->n_gene_blocks, (int64_t)NB * (R + 1) * 16, w->hdr,
-                       (R + 1) * 16, 0, C, w->tabB, w->xbits, 256, no_tail, no_xs);
+    ca_yfin_args no_yfin; memset(&no_yfin, 0, sizeof(no_yfin));
+    hipLaunchKernelGGL(k_poly_red<false>, dim3(256), dim3(CA_TB), 0, st, w->partB, w->n_gene_blocks, (int64_t)NB * (R + 1) * 16, w->hdr,
+                       (R + 1) * 16, 0, C, w->tabB, w->xbits, 256, no_tail, no_xs, 0, no_yfin);
   }
   return hipGetLastError();
 }
 
 hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, int K, const void* cell_ptrs, const float* alpha_u, double* cell_part, float* dF,
-                         const void* yfin_args, const void* local_tail, const float* xs_part, int xs_n, const float* xs_F, double* xs_slots, int rank, int world, bool lean, bool mfma) {
+                         const void* yfin_args, bool lean, bool mfma) {
   const ca_cell_ptrs& p = *static_cast<const ca_cell_ptrs*>(cell_ptrs);
   ca_yfin_args yfin;
   if (yfin_args) memcpy(&yfin, yfin_args, sizeof(yfin)); else memset(&yfin, 0, sizeof(yfin));
@@ -510,14 +486,26 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
   }
 #undef CA_PCELL
 #undef CA_PCELL_
-  {
-    ca_small_args tail;
-    if (local_tail) memcpy(&tail, local_tail, sizeof(tail)); else memset(&tail, 0, sizeof(tail));
-    const ca_xslot_args xs = {xs_part, xs_part ? xs_n : 0, xs_F, N, xs_slots, rank, world};
-    const int nextra = (tail.enabled || xs_slots) ? 2 : 0;
-    hipLaunchKernelGGL(k_poly_red, dim3(256 + nextra), dim3(CA_TB), 0, st, w->Qpart, w->n_cell_blocks, (int64_t)NB * (R + 2) * 8, w->hdr,
-                       (R + 2) * C, 1, C, w->tabQ, nullptr, 256, tail, xs);
-  }
+  return hipGetLastError();
+}
+
+constexpr int NRED_Q = 256;   // reducer blocks of the backward moments: a wave per output, up to NB (R + 2) 8 = 5632 of them
+
+hipError_t ca_poly_reduce(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, const void* yfin_cols, const void* local_tail, const float* xs_part, int xs_n,
+                          const float* xs_F, double* xs_slots, int rank, int world) {
+  ca_small_args tail;
+  if (local_tail) memcpy(&tail, local_tail, sizeof(tail)); else memset(&tail, 0, sizeof(tail));
+  ca_yfin_args yfin;
+  if (yfin_cols) memcpy(&yfin, yfin_cols, sizeof(yfin)); else memset(&yfin, 0, sizeof(yfin));
+  yfin.nrow = 0;
+  const ca_xslot_args xs = {xs_part, xs_part ? xs_n : 0, xs_F, N, xs_slots, rank, world};
+  const int nfix = (tail.enabled || xs_slots) ? 2 : 0;
+  if (yfin.ncol > 0)
+    hipLaunchKernelGGL(k_poly_red<true>, dim3(NRED_Q + nfix + cdiv_i(yfin.ncol, CA_TB / 64)), dim3(CA_TB), 0, st, w->Qpart, w->n_cell_blocks, (int64_t)NB * (R + 2) * 8,
+                       w->hdr, (R + 2) * C, 1, C, w->tabQ, nullptr, NRED_Q, tail, xs, nfix, yfin);
+  else   // (no column jobs: the launch as it was)
+    hipLaunchKernelGGL(k_poly_red<false>, dim3(NRED_Q + nfix), dim3(CA_TB), 0, st, w->Qpart, w->n_cell_blocks, (int64_t)NB * (R + 2) * 8, w->hdr,
+                       (R + 2) * C, 1, C, w->tabQ, nullptr, NRED_Q, tail, xs, nfix, yfin);
   return hipGetLastError();
 }
 
@@ -527,6 +515,27 @@ hipError_t ca_poly_backward(hipStream_t st, const ca_poly_ws* w, const float* V,
   if (small_tail) memcpy(&tail, small_tail, sizeof(tail)); else memset(&tail, 0, sizeof(tail));
   const int ngblk = cdiv_i(G, CA_TB);
   hipLaunchKernelGGL(k_poly_gene, dim3(ngblk + (tail.enabled ? 1 : 0)), dim3(CA_TB), 0, st, w->hdr, w->tabQ, V, mu, Lb, G, C, red_g, tail, ngblk);
+  return hipGetLastError();
+}
+
+hipError_t ca_poly_backward_merged(hipStream_t st, const ca_poly_ws* w, const float* V, const float* mu, const float* Lb, int G, int C, double* red_g,
+                                   const void* small_tail, const void* yfin_cols, int nb_hint, unsigned int tag, unsigned long long timeout_ticks, unsigned int* err) {
+  if (tag == 0u || !err) return hipErrorInvalidValue;
+  ca_small_args tail;
+  if (small_tail) memcpy(&tail, small_tail, sizeof(tail)); else memset(&tail, 0, sizeof(tail));
+  ca_yfin_args yfin;
+  if (yfin_cols) memcpy(&yfin, yfin_cols, sizeof(yfin)); else memset(&yfin, 0, sizeof(yfin));
+  yfin.nrow = 0;
+  ca_gr_args a;
+  memset(&a, 0, sizeof(a));
+  a.part = w->Qpart; a.nblk = w->n_cell_blocks; a.stride = (int64_t)NB * (R + 2) * 8; a.tabQ = w->tabQ;
+  // (as many reducer blocks as nb_hint bins' outputs fill, a wave each; the waves stride over the outputs, so a bin count above the hint costs time, not outputs)
+  a.nred = nb_hint > 0 ? std::min(NRED_Q, std::max(1, cdiv_i((int64_t)nb_hint * (R + 2) * C, CA_TB / 64))) : NRED_Q;
+  a.hdr = w->hdr; a.V = V; a.mu = mu; a.Lb = Lb; a.G = G; a.C = C; a.red_g = red_g; a.ngblk = cdiv_i(G, CA_TB);
+  a.flags = w->gflags; a.tag = tag; a.timeout_ticks = timeout_ticks; a.err = err;
+  static_assert(NRED_Q <= CA_PL_NGFLAG, "a flag word per reducer block");
+  // block order = dispatch order: reducers, gene blocks, the monitor pass's tail, the column jobs
+  hipLaunchKernelGGL(k_poly_tail, dim3(a.nred + a.ngblk + (tail.enabled ? 1 : 0) + cdiv_i(yfin.ncol, CA_TB / 64)), dim3(CA_TB), 0, st, a, tail, yfin);
   return hipGetLastError();
 }
 

@@ -212,8 +212,9 @@ __device__ __forceinline__ void ca_pm_B_body(const ca_pm_args& a, int grp0, int 
 
 // ---- fixed-order sums of the partials: one wave per output, lanes stride over the partials, then the wave's tree (same order every time) ----------------------
 // mode 0: plain sum (tabB); mode 1: sum / k! with k = (j / C) % (R + 2) (tabQ = Q_k / k!).  Waves wave0, wave0 + nwave, ... of the outputs: WHICH wave sums an
-// output does not enter its value.  DEV: the partials are read with device-scope loads (the riding form, see above).
-template <bool DEV>
+// output does not enter its value.  DEV: the partials are read with device-scope loads (the riding form, see above).  PUB: the outputs are stored with
+// device-scope stores -- blocks of the SAME launch read them behind a hand-over (ca_polygene.hip.h).
+template <bool DEV, bool PUB = false>
 __device__ __forceinline__ void ca_pm_red_body(const double* __restrict__ part, int nblk, int64_t stride, int nout, int mode, int C, double* __restrict__ out,
                                                int wave0, int nwave) {
   const int lane = threadIdx.x & 63;
@@ -239,7 +240,7 @@ __device__ __forceinline__ void ca_pm_red_body(const double* __restrict__ part, 
         for (int i = 2; i <= k; ++i) f *= (double)i;
         a /= f;
       }
-      out[j] = a;
+      ca_pm_st<PUB>(out + j, a);
     }
   }
 }

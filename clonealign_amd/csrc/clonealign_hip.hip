@@ -109,7 +109,7 @@ static int preprocess_t(const ST* src, int64_t N, int G, int C, int layout, cons
 // ca_run's gated update: what the host's bookkeeping of a step changes (train_from_lookahead + the merged branch of train_update) -- taken before
 // the launch is queued, put back when the host's answer is "stop" (the launch then stores nothing)
 struct gate_snapshot {
-  bool look_valid, bwd_ready, pre_valid, em_stale, y_defer, ys_quant_ready, ycache_valid, yfin_pending, fold_now;
+  bool look_valid, bwd_ready, pre_valid, em_stale, y_defer, ys_quant_ready, ycache_valid, yfin_pending, ycol_pending, fold_now;
   int64_t pre_A, pre_B, hint_A, hint_B, gaux_slot;
   int vmm_at_idx, gaux_idx, ys_steps, ys_namax[3];
   float b1p, b2p; uint64_t adam_steps;
@@ -117,7 +117,7 @@ struct gate_snapshot {
   float *vchi, *vchi_alt, *alpha_u, *alpha_u_alt;
   void take(const ca_engine* h) {
     look_valid = h->look_valid; bwd_ready = h->bwd_ready; pre_valid = h->pre_valid; em_stale = h->em_stale; y_defer = h->y_defer;
-    ys_quant_ready = h->ys_quant_ready; ycache_valid = h->ycache_valid; yfin_pending = h->yfin_pending; fold_now = h->fold_now;
+    ys_quant_ready = h->ys_quant_ready; ycache_valid = h->ycache_valid; yfin_pending = h->yfin_pending; ycol_pending = h->ycol_pending; fold_now = h->fold_now;
     pre_A = h->pre_A; pre_B = h->pre_B; hint_A = h->hint_A; hint_B = h->hint_B; gaux_slot = h->gaux_slot;
     vmm_at_idx = h->vmm_at_idx; gaux_idx = h->gaux_idx; ys_steps = h->ys_steps;
     for (int i = 0; i < 3; ++i) ys_namax[i] = h->ys_namax[i];
@@ -127,7 +127,7 @@ struct gate_snapshot {
   }
   void restore(ca_engine* h) const {
     h->look_valid = look_valid; h->bwd_ready = bwd_ready; h->pre_valid = pre_valid; h->em_stale = em_stale; h->y_defer = y_defer;
-    h->ys_quant_ready = ys_quant_ready; h->ycache_valid = ycache_valid; h->yfin_pending = yfin_pending; h->fold_now = fold_now;
+    h->ys_quant_ready = ys_quant_ready; h->ycache_valid = ycache_valid; h->yfin_pending = yfin_pending; h->ycol_pending = ycol_pending; h->fold_now = fold_now;
     h->pre_A = pre_A; h->pre_B = pre_B; h->hint_A = -1; h->hint_B = -1; h->gaux_slot = gaux_slot;
     h->vmm_at_idx = vmm_at_idx; h->gaux_idx = gaux_idx; h->ys_steps = ys_steps;
     for (int i = 0; i < 3; ++i) h->ys_namax[i] = ys_namax[i];
@@ -144,20 +144,20 @@ struct gate_snapshot {
 // first when the answer is "stop" (every block of the sweep then returns at its first instruction)
 struct fwd_snapshot {
   double *gene_part, *gene_part_alt, *gene_partB, *gene_partB_alt;
-  bool pre_valid, em_stale, yfin_pending, ys_quant_ready, ycache_valid, look_valid, bwd_ready;
+  bool pre_valid, em_stale, yfin_pending, ycol_pending, ys_quant_ready, ycache_valid, look_valid, bwd_ready;
   int ys_slot, ys_steps;
   int64_t look_slot;
   unsigned long long host_seq, host_seq_next;
   ca_small_args mon_tail;
   void take(const ca_engine* h) {
     gene_part = h->gene_part; gene_part_alt = h->gene_part_alt; gene_partB = h->gene_partB; gene_partB_alt = h->gene_partB_alt;
-    pre_valid = h->pre_valid; em_stale = h->em_stale; yfin_pending = h->yfin_pending; ys_quant_ready = h->ys_quant_ready; ycache_valid = h->ycache_valid;
+    pre_valid = h->pre_valid; em_stale = h->em_stale; yfin_pending = h->yfin_pending; ycol_pending = h->ycol_pending; ys_quant_ready = h->ys_quant_ready; ycache_valid = h->ycache_valid;
     look_valid = h->look_valid; bwd_ready = h->bwd_ready; ys_slot = h->ys_slot; ys_steps = h->ys_steps; look_slot = h->look_slot;
     host_seq = h->host_seq; host_seq_next = h->host_seq_next; mon_tail = h->mon_tail;
   }
   void restore(ca_engine* h) const {
     h->gene_part = gene_part; h->gene_part_alt = gene_part_alt; h->gene_partB = gene_partB; h->gene_partB_alt = gene_partB_alt;
-    h->pre_valid = pre_valid; h->em_stale = em_stale; h->yfin_pending = yfin_pending; h->ys_quant_ready = ys_quant_ready; h->ycache_valid = ycache_valid;
+    h->pre_valid = pre_valid; h->em_stale = em_stale; h->yfin_pending = yfin_pending; h->ycol_pending = ycol_pending; h->ys_quant_ready = ys_quant_ready; h->ycache_valid = ycache_valid;
     h->look_valid = look_valid; h->bwd_ready = bwd_ready; h->ys_slot = ys_slot; h->ys_steps = ys_steps; h->look_slot = look_slot;
     h->host_seq = host_seq; h->host_seq_next = host_seq_next; h->mon_tail = mon_tail;
   }
@@ -382,6 +382,7 @@ int ca_get_info(ca_handle h, ca_info* i) {
   i->mom_ride = h->mom_ride ? 1 : 0;
   i->cell_lean = h->cell_lean ? 1 : 0; i->cell_mfma = h->cell_mfma ? 1 : 0;
   i->mom_last = h->mom_last ? 1 : 0; i->mom_free_slots = h->mom_free_slots;
+  i->gene_ride = gene_ride_merges(h) ? 1 : 0;
   i->fold_gsum = (h->fold_gsum && !is_sharded(h)) ? 1 : 0; i->yfin_split = (h->yfin_split && !is_sharded(h)) ? 1 : 0;
   i->update_merge = (h->upd_merge && h->fused_ok && h->fwd_cell && h->K > 0) ? 1 : 0;
   return CA_OK;
@@ -764,7 +765,7 @@ int ca_reinit(ca_handle h, const double* psi0, const double* loc0) {
   // A forward-sweep block that gave up on a left-over tile leaves a sticky word (comm_check: "the engine's state is undefined").  A restart defines every
   // variable and every Adam slot again, so THIS call -- and only this one -- clears it; a dead peer-to-peer transport stays dead.
   HIPCK(h, hipStreamSynchronize(h->stream));
-  if (h->host_pinned) { *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 41) = 0u; *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 42) = 0u; *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 43) = 0u; }
+  if (h->host_pinned) { *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 41) = 0u; *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 42) = 0u; *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 43) = 0u; *reinterpret_cast<volatile unsigned int*>(h->host_pinned + 44) = 0u; }
   SYNC(h);
   const int64_t N = h->N; const int G = h->G, C = h->C, K = h->K, D = h->D;
   auto zero = [&](float* p, int64_t n) { return p && n > 0 ? hipMemsetAsync(p, 0, (size_t)n * sizeof(float), h->stream) : hipSuccess; };

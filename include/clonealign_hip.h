@@ -145,7 +145,13 @@ enum ca_variant {
                                  list), the others 4 bits as before: fewer bytes per pass, the same integer sums.  Picked where the 4-bit image is, the matrix is
                                  large enough for the launch to follow its bytes, and N2 = 6 or 5 keeps the escapes at 1 in 256 counts (CA_VARX_Y2 forces N2 = 6).
                                  Off: the 4-bit image's launch as it was */
-  CA_VAR_RIDE_SEQ = 1 << 13  /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
+  CA_VAR_GENE_RIDE = 1 << 28, /* the series form's way back from its cell launch: the count-matrix stream's column sums, which nobody reads before the update, leave the
+                                 cell launch (whose extra blocks can only start in slots its cell blocks have left), and an unsharded pass runs the reduction of the
+                                 backward moments, the per-gene pass, the pending monitor pass's tail and those column sums as ONE launch, the moment table handed over
+                                 inside it through tagged words (ca_polygene.hip.h) -- a launch and a kernel boundary less per iteration; a cell-sharded fit keeps
+                                 reduction and per-gene pass apart (its collective sits between them) and carries the column sums on the reduction launch.  The same
+                                 additions in the same order: the same bits.  Off: cell launch, k_poly_red and k_poly_gene as they were */
+  CA_VAR_RIDE_SEQ = 1 << 13 /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
 /* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
  * code has been deleted; the constants keep their values and ca_create returns CA_ERR_INVALID for them, in every build. */
@@ -205,7 +211,7 @@ typedef struct ca_options {
   int32_t gate_timeout_us;          /* ca_run with the gated update (CA_VAR_RUN_GATE): how long the queued update's relay block polls for the host's
                                      * go / stop word before the launch gives up -- it then stores nothing, the device goes idle, and the host queues
                                      * the update again after its decision (0 = 1000 us).  Not an error and not a result: only who waits for whom */
-  int32_t reserved[2];              /* lab knobs of the series form: [0] cell blocks per CU (0 = 2), [1] = 1: its count-matrix stream on the side stream (measured slower) */
+  int32_t reserved[2];              /* lab knobs of the series form: [0] cell blocks per CU (0 = 2), [1] = 1: its count-matrix stream on the side stream (measured slower), 7 / 8: with CA_VAR_GENE_RIDE the stream's column sums stay behind the cell launch's blocks / go with the reduction, whatever the size rule says (A/B runs; the same bits) */
 } ca_options;
 /* (The library reads no tuning from the process environment.  Only the timing-lab build, -DCA_LAB -- never the product's .so, its
  *  ca_build_id() starts with "lab-" -- accepts the same switches as CA_* variables, and only when CLONEALIGN_DEBUG_ENV is set.) */
@@ -248,6 +254,8 @@ typedef struct ca_info {
                                 count, the others y_stream_bits (which stays the width of the wide blocks); 0: no 2-bit blocks */
   int64_t y_stream_esc;      /* entries of the escape list the series form's own stream launch reads (the 2-bit / 4-bit image's where y_stream_n2 > 0, else the 4-bit image's; 0 at 8 bits) */
   int64_t y_stream_bytes;    /* bytes that launch reads per pass: its image plus its escape list */
+  int32_t gene_ride;         /* 1: a series pass of this engine runs reduction, per-gene pass and the stream's column sums as one launch (CA_VAR_GENE_RIDE); 0: as launches
+                                of their own (the switch off, no series form, or a cell-sharded fit) */
 } ca_info;
 enum ca_transport { CA_TRANSPORT_NONE = 0, CA_TRANSPORT_RCCL = 1, CA_TRANSPORT_HOST = 2, CA_TRANSPORT_P2P = 3 };
 
