@@ -2138,6 +2138,292 @@ def predictive_moments(fit, Y, L, *, x=None, saturate=True, saturation_threshold
             "p_gene_clone": np.minimum(1.0, 2.0 * np.minimum(p_low, p_high)), "L": Ls, "clone_cells": np.bincount(idx[used], minlength=C).astype(np.int64)}
 
 
+def _separability_inputs_host(E, V, U, what="clone_separability"):
+    """The arguments of ``ca_clone_separability`` as float64 arrays with its refusals as ValueError.  Returns ``(E, V, U, N, G, C, D)``; without factors ``N = 1``."""
+    E = np.asarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"{what}: E is {E.shape}; expected (genes, clones)")
+    G, C = E.shape
+    if C < 2 or G < 1:
+        raise ValueError(f"{what}: G = {G}, C = {C}: G must be >= 1 and C >= 2")
+    if (U is None) != (V is None):
+        raise ValueError(f"{what}: U and V go together (both, or neither)")
+    N, D = 1, 0
+    if U is not None:
+        U, V = np.asarray(U, dtype=np.float64), np.asarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"{what}: U is {U.shape} and V is {V.shape}; expected (cells, D) and ({G}, D)")
+        N, D = U.shape
+    if D > 8:
+        raise ValueError(f"{what}: D = {D} is outside [0, 8]")
+    wrong = np.argwhere(~np.isfinite(E) | (E < 0))
+    if wrong.size:
+        raise ValueError(f"{what}: E has a negative or non-finite entry (gene {wrong[0][0]}, clone {wrong[0][1]})")
+    with np.errstate(over="ignore"):
+        s = E.sum(0)
+    if (s == 0).any():
+        raise ValueError(f"{what}: E is zero in every gene of clone {np.flatnonzero(s == 0)[0]}: its column sums to 0")
+    if not np.isfinite(s).all():
+        raise ValueError(f"{what}: E sums to a non-finite value in clone {np.flatnonzero(~np.isfinite(s))[0]}")
+    for name, M, row in (("V", V, "gene"), ("U", U, "cell")):
+        if D > 0 and not np.isfinite(M).all():
+            r, d = np.argwhere(~np.isfinite(M))[0]
+            raise ValueError(f"{what}: {name} has a non-finite entry ({row} {r}, factor {d})")
+    if D == 0:
+        U = V = None
+    return E, V, U, N, G, C, D
+
+
+def _clone_separability_host(E, V, U, chunk=256, with_scale=False):
+    """Numpy float64 restatement of ``ca_clone_separability`` (include/clonealign_hip.h states the outputs) from the PER-GENE sums, no expanded form:
+    ``e = E / E.sum(0)``; per cell ``eta`` summed factor by factor, the shift ``m`` its maximum over every gene, ``w = exp(eta - m)``, ``Z_c = sum_g e_gc w_g``,
+    ``logZ = m + log Z``; per ordered pair ``p = e_a w / Z_a``, ``excl = sum_X p``, ``d = (log e_a - log e_b) - (log Z_a - log Z_b)`` on ``S`` and
+    ``m_k = sum_S p d^k``.  ``Z_a = 0`` (underflow) gives ``logZ = -inf`` and zeros in every pair entry that involves ``a``.  ``chunk`` cells at a time.
+    Without factors one row (N = 1).  Returns ``(logZ [N, C], excl, m1, m2, m3 [N, C, C])``; ``with_scale=True`` appends the three scales
+    ``sum_S p (|delta| + |Delta|)^k`` [N, C, C] the device's parity bars are stated in.  Refusals are the library's, as ValueError."""
+    E, V, U, N, G, C, D = _separability_inputs_host(E, V, U)
+    e = E / E.sum(0)
+    pos = e > 0
+    with np.errstate(divide="ignore"):
+        le = np.where(pos, np.log(np.where(pos, e, 1.0)), 0.0)
+    logZ = np.zeros((N, C))
+    out = np.zeros((4, N, C, C))
+    scale = np.zeros((3, N, C, C))
+    for lo in range(0, N, int(chunk)):
+        hi = min(N, lo + int(chunk))
+        eta = np.zeros((hi - lo, G))
+        for d in range(D):
+            eta = eta + U[lo:hi, d:d + 1] * V[None, :, d]
+        m = eta.max(1, keepdims=True)
+        w = np.exp(eta - m)
+        Z = np.stack([(w * e[None, :, c]).sum(1) for c in range(C)], axis=1)   # [cells, C]; a column at a time, so equal columns of e give equal bits
+        with np.errstate(divide="ignore"):
+            lz = np.log(Z)
+        logZ[lo:hi] = m + lz
+        live = Z > 0
+        for a in range(C):
+            pa = np.where(live[:, a:a + 1], e[None, :, a] * w / np.where(live[:, a:a + 1], Z[:, a:a + 1], 1.0), 0.0)
+            for b in range(C):
+                if a == b:
+                    continue
+                both = live[:, a] & live[:, b]
+                S, X = pos[:, a] & pos[:, b], pos[:, a] & ~pos[:, b]
+                delta = le[S, a] - le[S, b]
+                Delta = np.where(both, lz[:, a] - np.where(both, lz[:, b], 0.0), 0.0) if both.any() else np.zeros(hi - lo)
+                Delta = np.where(both, Delta, 0.0)
+                dd = delta[None, :] - Delta[:, None]
+                pS = pa[:, S]
+                out[0, lo:hi, a, b] = np.where(both, pa[:, X].sum(1), 0.0)
+                sc = np.abs(delta)[None, :] + np.abs(Delta)[:, None]
+                for k in (1, 2, 3):
+                    out[k, lo:hi, a, b] = np.where(both, (pS * dd ** k).sum(1), 0.0)
+                    scale[k - 1, lo:hi, a, b] = np.where(both, (pS * sc ** k).sum(1), 0.0)
+    res = (logZ, out[0], out[1], out[2], out[3])
+    return res + (scale[0], scale[1], scale[2]) if with_scale else res
+
+
+def edgeworth_normal_cdf(t, mean, var, cum3=0.0):
+    """``P(T <= t)`` for a CONTINUOUS-valued sum of independent terms with the given mean, variance and third cumulant: the normal approximation with the
+    first Edgeworth (skewness) term and NO continuity correction (``refined_normal_cdf`` is the form for integer-valued sums): ``F(t) = Phi(x) - gamma
+    (x^2 - 1) phi(x) / 6`` with ``x = (t - mean) / sd`` and ``gamma = cum3 / sd^3``, clipped to [0, 1].  A variance of 0 is a step at ``mean``.  Arrays broadcast."""
+    from scipy.special import ndtr
+    t, mean, var, cum3 = np.broadcast_arrays(*(np.asarray(a, dtype=np.float64) for a in (t, mean, var, cum3)))
+    ok = var > 0
+    sd = np.sqrt(np.where(ok, var, 1.0))
+    x = (t - mean) / sd
+    F = ndtr(x) - (cum3 / sd ** 3) * (x * x - 1.0) * np.exp(-0.5 * x * x) / (6.0 * np.sqrt(2.0 * np.pi))
+    return np.where(ok, np.clip(F, 0.0, 1.0), (t >= mean).astype(np.float64))
+
+
+def _per_read_cumulants(excl, m1, m2, m3):
+    """``(q, kappa, v, c3)`` of the log-likelihood ratio per read GIVEN that the read excludes nobody: ``q = 1 - excl``, ``kappa = m1 / q``, ``v = max(m2 / q -
+    kappa^2, 0)``, ``c3 = m3 / q - 3 kappa m2 / q + 2 kappa^3``; all 0 where ``q = 0`` (every read excludes the rival)."""
+    q = 1.0 - excl
+    ok = q > 0
+    qs = np.where(ok, q, 1.0)
+    kappa, s2, s3 = np.where(ok, m1 / qs, 0.0), np.where(ok, m2 / qs, 0.0), np.where(ok, m3 / qs, 0.0)
+    return q, kappa, np.maximum(s2 - kappa * kappa, 0.0), s3 - 3.0 * kappa * s2 + 2.0 * kappa ** 3
+
+
+def _p_confuse(t, q, kappa, v, c3, lp_diff=0.0, concentration=None):
+    """The closed form behind ``clone_separability``: the probability that ``t`` reads of a row of clone ``a`` leave ``Lambda + lp_a - lp_b <= 0``: no read
+    excludes ``b`` (``q^t``) and, given that, ``Lambda`` -- mean ``t kappa``, variance ``t v``, third cumulant ``t c3`` -- falls at or below ``-(lp_a - lp_b)``
+    (``edgeworth_normal_cdf``).  ``concentration`` inflates the variance by ``(t + phi) / (1 + phi)`` and drops the skewness term.  Arrays broadcast."""
+    t = np.asarray(t, dtype=np.float64)
+    var, cum3 = t * v, t * c3
+    if concentration is not None:
+        var, cum3 = var * (t + concentration) / (1.0 + concentration), 0.0
+    with np.errstate(invalid="ignore"):
+        return np.power(q, t) * edgeworth_normal_cdf(0.0, t * kappa + lp_diff, var, cum3)
+
+
+def clone_separability(fit, L, total_counts, *, psi=None, x=None, clones=None, log_prior=None, concentration=None, per_cell=False, saturate=True,
+                       saturation_threshold=6, engine_opts=None, host=False):
+    """Can expression tell the clones of a fitted model apart at a given read depth -- answered BEFORE any counts are scored, in closed form, by one pass on
+    the device that reads no count matrix (``engine.clone_separability`` / ``ca_clone_separability``; include/clonealign_hip.h states its five outputs).
+
+    For a row of ``t`` reads drawn from clone ``a``, the log-likelihood ratio against clone ``b``, ``Lambda = ll_a - ll_b``, is a linear statistic of one
+    multinomial.  A read on a gene where ``b`` has copy number 0 rules ``b`` out; its per-read probability is ``excl``.  Given no such read, all ``t`` reads
+    fall where both clones express, and ``Lambda`` has mean ``t kappa``, variance ``t v`` and third cumulant ``t c3`` with ``q = 1 - excl``, ``kappa = m1 / q``,
+    ``v = max(m2 / q - kappa^2, 0)``, ``c3 = m3 / q - 3 kappa m2 / q + 2 kappa^3``.  The probability that the cell is NOT called ``a`` over ``b`` is then
+    ``p_confuse[n, a, b] = q^t clip(Phi(z) - gamma (z^2 - 1) phi(z) / 6, 0, 1)`` with ``z = -(t kappa + lp_a - lp_b) / sqrt(t v)`` and ``gamma = c3 /
+    (sqrt(t) v^1.5)`` (``edgeworth_normal_cdf``: no continuity correction, ``Lambda`` is not integer-valued; ``v = 0`` gives a step at the mean).
+
+    ``L`` [genes, clones] for the fit's retained genes, saturated as ``clone_loglik`` does.  ``total_counts``: a scalar or one read depth per cell.
+    ``psi``: None means the fit's own cells (``fit["ml_params"]["psi"]``), or an array [cells, K]; ``x`` [cells, P] exactly when the fit has ``beta``.  A fit
+    without factors or covariates has one row for every cell.  ``clones`` [cells]: the cells' called clones (names or indices; "unassigned" joins no row
+    mean).  ``log_prior`` [clones] or [cells, clones]: default equal priors.  ``concentration=phi``: a Dirichlet-multinomial overdispersion; the variance is
+    inflated by ``(t + phi) / (1 + phi)``, the Dirichlet-multinomial covariance factor, and the skewness term is dropped -- an APPROXIMATION that leaves
+    ``q^t`` multinomial.  The cells go through the engine in slices, so host memory stays bounded; ``host=True`` runs the numpy restatement
+    (``_clone_separability_host``) instead; there is no silent fallback otherwise.
+
+    Returns a dict.  [C, C], row = true clone, column = rival, diagonal 0: ``kl_per_read`` (mean over the cells of ``m1``: the drift of ``Lambda`` per read),
+    ``excl_per_read``, ``var_per_read`` (mean of ``v``), ``drift_per_read`` (mean of ``kappa``), ``cum3_per_read``; ``confusion``: row ``a`` is the mean of
+    ``p_confuse[:, a, :]`` over the cells of clone ``a`` when ``clones`` is given (NaN for a clone without cells), over all cells otherwise.  Per cell:
+    ``p_error_cell`` = min(1, sum_b p_confuse[n, clone_n, b]) and ``worst_rival`` (NaN / -1 without a called clone, so also without ``clones``), ``logZ``
+    [cells, C], ``total_counts``.  Also ``clone_names`` and ``concentration``.  ``per_cell=True`` adds ``excl``, ``m1``, ``m2``, ``m3`` and ``p_confuse``
+    [cells, C, C].
+
+    What the numbers are NOT: they hold under the model.  Real counts are overdispersed against a multinomial, so without ``concentration`` the confusion
+    probabilities are LOWER bounds and ``reads_needed`` an optimistic depth; the pairwise events are combined by a union bound in ``p_error_cell``; and the
+    Edgeworth form is no tail probability below about 1e-3."""
+    Lm, cn = _parse_cnv(L)
+    G, C = Lm.shape
+    names = _clone_names(fit, cn, C)
+    ml = fit["ml_params"]
+    K = 0 if ml.get("W") is None else int(np.asarray(ml["W"]).size // max(G, 1))
+    if K > 0 and psi is None:
+        psi = "fit"
+    total = np.asarray(total_counts, dtype=np.float64)
+    if not np.all(np.isfinite(total)) or np.any(total < 0):
+        raise ValueError("total_counts must be finite and non-negative")
+    sizes = {"total_counts": int(total.reshape(-1).shape[0]) if total.ndim > 0 else None,
+             "psi": None if K == 0 or psi is None else int(np.asarray(ml["psi"] if isinstance(psi, str) else psi).size // K),
+             "x": None if x is None else int(np.asarray(x).shape[0]),
+             "clones": None if clones is None else int(np.asarray(clones, dtype=object).reshape(-1).shape[0]),
+             "log_prior": None if log_prior is None or np.ndim(log_prior) < 2 else int(np.shape(log_prior)[0])}
+    given = {k: v for k, v in sizes.items() if v is not None}
+    if len(set(given.values())) > 1:
+        raise ValueError("the arguments disagree on the number of cells: " + ", ".join(f"{k} {v}" for k, v in given.items()))
+    N = next(iter(given.values())) if given else 1
+    t = _fit_tables(fit, Lm, N, x, psi if K > 0 else None, saturate, saturation_threshold, what="the separability call")
+    total = np.array(np.broadcast_to(total.reshape(-1) if total.ndim > 0 else total, (N,)))
+    lp = np.zeros((1, C)) if log_prior is None else np.asarray(log_prior, dtype=np.float64).reshape(-1, C)
+    if lp.shape[0] not in (1, N):
+        raise ValueError(f"log_prior is {np.shape(log_prior)}; expected ({C},) or ({N}, {C})")
+    if concentration is not None and not (np.isfinite(concentration) and concentration > 0):
+        raise ValueError("concentration must be a positive number")
+    idx = None
+    if clones is not None:
+        cl = np.asarray(clones).reshape(-1)
+        if cl.dtype.kind in "iu":
+            idx = cl.astype(np.int64)
+        else:
+            lut = {c: i for i, c in enumerate(names)}
+            unknown = sorted({str(c) for c in cl if c not in lut and c != "unassigned"})
+            if unknown:
+                raise ValueError("clone labels that are no column of L: " + ", ".join(unknown))
+            idx = np.array([lut.get(c, -1) for c in cl], dtype=np.int64)
+        if idx.size and (idx.min() < -1 or idx.max() >= C):
+            raise ValueError(f"clone index outside [0, {C})")
+    device = int(dict(engine_opts or {}).get("device", 0))
+    if not host:
+        from . import engine as _engine
+    step = max(1, (1 << 21) // (C * C))                              # four [cells, C, C] float64 arrays of 16 MB a slice
+    sums = np.zeros((6, C, C))                                       # m1, excl, v, kappa, c3, p_confuse over the cells that count for a row
+    cnt = np.zeros(C)
+    logZ = np.zeros((N, C))
+    p_err, rival = np.full(N, np.nan), np.full(N, -1, dtype=np.int64)
+    keep = [[] for _ in range(5)] if per_cell else None
+    off = ~np.eye(C, dtype=bool)
+    for lo in range(0, N, step):
+        hi = min(N, lo + step)
+        if t.U is None:
+            raw = _clone_separability_host(t.E, None, None) if host else _engine.clone_separability(t.E, None, None, device=device)
+            raw = tuple(np.broadcast_to(a, (hi - lo,) + a.shape[1:]) for a in raw)
+        else:
+            raw = _clone_separability_host(t.E, t.V, t.U[lo:hi]) if host else _engine.clone_separability(t.E, t.V, t.U[lo:hi], device=device)
+        lz, ex, a1, a2, a3 = raw
+        logZ[lo:hi] = lz
+        q, kappa, v, c3 = _per_read_cumulants(ex, a1, a2, a3)
+        lps = lp if lp.shape[0] == 1 else lp[lo:hi]
+        with np.errstate(invalid="ignore"):
+            lpd = np.where(off[None], lps[:, :, None] - lps[:, None, :], 0.0)
+        pc = np.where(off[None], _p_confuse(total[lo:hi, None, None], q, kappa, v, c3, lpd, concentration), 0.0)
+        if idx is None:
+            w = np.ones((hi - lo, C))
+        else:
+            w = np.zeros((hi - lo, C))
+            called = np.flatnonzero(idx[lo:hi] >= 0)
+            w[called, idx[lo:hi][called]] = 1.0
+            row = pc[called, idx[lo:hi][called]]                     # [called, C]
+            p_err[lo + called] = np.minimum(1.0, row.sum(1))
+            rival[lo + called] = row.argmax(1)
+        for k, a in enumerate((a1, ex, v, kappa, c3, pc)):
+            sums[k] += np.einsum("na,nab->ab", w, a)
+        cnt += w.sum(0)
+        if per_cell:
+            for k, a in enumerate((ex, a1, a2, a3, pc)):
+                keep[k].append(np.array(a))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(cnt[None, :, None] > 0, sums / np.where(cnt > 0, cnt, 1.0)[None, :, None], np.nan)
+    res = {"kl_per_read": mean[0], "excl_per_read": mean[1], "var_per_read": mean[2], "drift_per_read": mean[3], "cum3_per_read": mean[4], "confusion": mean[5],
+           "p_error_cell": p_err, "worst_rival": rival, "logZ": logZ, "total_counts": total, "clone_names": list(names), "concentration": concentration}
+    if per_cell:
+        for k, name in enumerate(("excl", "m1", "m2", "m3", "p_confuse")):
+            res[name] = np.concatenate(keep[k], axis=0)
+    return res
+
+
+def reads_needed(sep, error=0.05):
+    """Reads per cell at which clone ``a`` is told from clone ``b`` with confusion at most ``error``: per ordered pair the smallest integer ``t`` with
+    ``p_confuse(t) <= error``, where ``p_confuse`` is ``clone_separability``'s closed form at the cell-AVERAGED per-read quantities of ``sep`` (a result of
+    ``clone_separability``: ``drift_per_read``, ``var_per_read``, ``cum3_per_read``, ``excl_per_read``, ``concentration``) and equal priors, found by doubling
+    and bisection.  ``p_confuse`` need not fall monotonically -- with equal priors a cell with hardly any reads is called ``a`` by default when the rare reads
+    are the ones that favour ``b`` -- so the crossing reported is the LAST one among the doubling probes 1, 2, 4, ..: from there on every probe stays at or
+    below ``error``, and ``p_confuse(t) <= error < p_confuse(t - 1)``.  [C, C] float64: ``inf`` where the pair cannot be told apart at any depth (``kappa = 0`` and ``q = 1``: identical clones), 0 on the diagonal,
+    NaN for a clone without cells.  As for ``clone_separability``: under the model, so without ``concentration`` an optimistic depth."""
+    if not 0.0 < error < 1.0:
+        raise ValueError("error must lie in (0, 1)")
+    kappa, v, c3, q = sep["drift_per_read"], sep["var_per_read"], sep["cum3_per_read"], 1.0 - sep["excl_per_read"]
+    C = kappa.shape[0]
+    out = np.zeros((C, C))
+    for a in range(C):
+        for b in range(C):
+            if a == b:
+                continue
+            if not np.isfinite(kappa[a, b]):
+                out[a, b] = np.nan
+                continue
+            f = lambda t: float(_p_confuse(float(t), q[a, b], kappa[a, b], v[a, b], c3[a, b], 0.0, sep.get("concentration")))  # noqa: E731
+            if q[a, b] >= 1.0 and kappa[a, b] <= 0.0:
+                out[a, b] = np.inf
+                continue
+            probes = [2 ** k for k in range(41)]
+            over = [k for k, tt in enumerate(probes) if f(tt) > error]
+            if over and over[-1] == len(probes) - 1:
+                out[a, b] = np.inf
+                continue
+            lo = probes[over[-1]] if over else 0                     # (f(0) = 1 > error: nothing is known without reads)
+            hi = max(2 * lo, 1)
+            while hi - lo > 1:                                       # f(lo) > error >= f(hi)
+                mid = (lo + hi) // 2
+                lo, hi = (lo, mid) if f(mid) <= error else (mid, hi)
+            out[a, b] = hi
+    return out
+
+
+def merge_candidates(sep, threshold=0.2):
+    """The unordered pairs of clones that expression cannot tell apart at the depth ``sep`` (a result of ``clone_separability``) was made for: those whose
+    ``confusion`` exceeds ``threshold`` in BOTH directions.  A list of ``(name_a, name_b, confusion[a, b], confusion[b, a])``, ``a < b``, sorted by
+    decreasing ``min`` of the two (ties in clone order): candidates to merge before a fit."""
+    conf, names = sep["confusion"], sep["clone_names"]
+    C = conf.shape[0]
+    found = [(a, b) for a in range(C) for b in range(a + 1, C) if conf[a, b] > threshold and conf[b, a] > threshold]
+    found.sort(key=lambda ab: (-min(conf[ab], conf[ab[::-1]]), ab))
+    return [(names[a], names[b], float(conf[a, b]), float(conf[b, a])) for a, b in found]
+
+
 def _dosage_fit(T, X, L, use, kappa_max=8.0, max_iter=50, tol=1e-10, max_step=2.0):
     """The per-gene fits of ``dosage_response`` from arrays [G, C]: observed totals ``T``, exposures ``X``, copy numbers ``L`` and the mask ``use`` of
     the (gene, clone) entries that take part.  Every gene runs the same safeguarded Newton iteration on its concave profile log-likelihood."""

@@ -566,3 +566,41 @@ inline hipError_t launch_predmom_finish(hipStream_t stream, const ca_predmom_ops
   hipLaunchKernelGGL(k_predmom_finish, dim3((unsigned)cdiv((int64_t)o.C * o.G, CA_PM_TB)), dim3(CA_PM_TB), 0, stream, o.genepart, o.first, o.acc, o.G, o.C);
   return hipGetLastError();
 }
+
+// ---- k_sep_loge / k_sep_build / k_boot_prod<float, true, NT> / k_sep_scale / k_sep_merge / k_sep_finish: the launches of ca_clone_separability on one batch of cells (no engine: the call owns its stream) ----
+// the call's tables (e and log e [Gp][C], the padded factors Vt [Gp][CA_LL_DMAX]); the right-hand side B [Gp][W] of the columns [c_lo, c_lo + W); the batch's padded
+// factors Ut, its slabs (part, mpart, the chunks' scales wk, the shift m), the merged rows R [n_cnt][ncolp] and the five outputs
+struct ca_sep_ops { const double *Ec, *Vt, *Ut; double *lE, *B, *part, *mpart, *wk, *m, *R, *logZ, *excl, *m1, *m2, *m3; int64_t n_cnt; int G, Gp, C, nzc, ncol, ncolp, c_lo, W; };
+inline hipError_t launch_sep_loge(hipStream_t stream, const ca_sep_ops& o) {
+  const int64_t n = (int64_t)o.Gp * o.C;
+  hipLaunchKernelGGL(k_sep_loge, dim3((unsigned)cdiv(n, CA_TB)), dim3(CA_TB), 0, stream, o.Ec, o.lE, n);
+  return hipGetLastError();
+}
+inline hipError_t launch_sep_build(hipStream_t stream, const ca_sep_ops& o) {
+  hipLaunchKernelGGL(k_sep_build, dim3((unsigned)cdiv((int64_t)o.Gp * o.W, CA_TB)), dim3(CA_TB), 0, stream, o.Ec, o.lE, o.B, o.c_lo, o.W, o.ncol, o.G, o.Gp, o.C);
+  return hipGetLastError();
+}
+// the bootstrap's exponent product on the call's own stream: groups of CA_BOOT_NT column tiles, the four-tile instantiation for at most four (boot_prod_nt's rule)
+template <int NT>
+hipError_t sep_prod_t(hipStream_t stream, const ca_sep_ops& o, int ngroups) {
+  hipLaunchKernelGGL((k_boot_prod<float, true, NT>), dim3((unsigned)cdiv(o.n_cnt, 16 * (CA_TB / 64)), (unsigned)o.nzc, (unsigned)ngroups), dim3(CA_TB), 0, stream, (const float*)nullptr,
+                     (const int64_t*)nullptr, (const int*)nullptr, (const float*)nullptr, o.Ut, o.Vt, (const double*)o.B, o.part, o.mpart, (int64_t)0, o.n_cnt, o.G, o.Gp, o.W);
+  return hipGetLastError();
+}
+inline hipError_t launch_sep_prod(hipStream_t stream, const ca_sep_ops& o) {
+  const int tiles = o.W / 16;
+  return tiles <= 4 ? sep_prod_t<4>(stream, o, 1) : sep_prod_t<CA_BOOT_NT>(stream, o, cdiv(tiles, CA_BOOT_NT));
+}
+inline hipError_t launch_sep_scale(hipStream_t stream, const ca_sep_ops& o) {
+  hipLaunchKernelGGL(k_sep_scale, dim3((unsigned)cdiv(o.n_cnt, CA_TB)), dim3(CA_TB), 0, stream, (const double*)o.mpart, o.wk, o.m, o.n_cnt, o.nzc);
+  return hipGetLastError();
+}
+inline hipError_t launch_sep_merge(hipStream_t stream, const ca_sep_ops& o) {
+  hipLaunchKernelGGL(k_sep_merge, dim3((unsigned)cdiv(o.n_cnt * o.W, CA_TB)), dim3(CA_TB), 0, stream, (const double*)o.part, (const double*)o.wk, o.R, o.n_cnt, o.nzc, o.c_lo, o.W, o.ncolp);
+  return hipGetLastError();
+}
+inline hipError_t launch_sep_finish(hipStream_t stream, const ca_sep_ops& o) {
+  hipLaunchKernelGGL(k_sep_finish, dim3((unsigned)cdiv(o.n_cnt * o.C * o.C, CA_TB)), dim3(CA_TB), 0, stream, (const double*)o.R, (const double*)o.m, o.logZ, o.excl, o.m1, o.m2, o.m3, o.n_cnt,
+                     o.C, o.ncolp);
+  return hipGetLastError();
+}

@@ -64,6 +64,9 @@ EXPORTS = (
     # the replicates' moments in closed form: per cell the mean and variance of the log-likelihood's linear part, per (gene, clone) three cumulants of the totals
     # (predictive_moments), no handle, additions to ABI 6
     "ca_predictive_moments", "ca_predictive_moments_kernel_ms",
+    # clone separability in closed form: per cell and ordered pair of clones the per-read moments of the log-likelihood ratio and the probability of an
+    # excluding read (clone_separability / reads_needed / merge_candidates), no handle, additions to ABI 6
+    "ca_clone_separability", "ca_clone_separability_kernel_ms",
     # clone evidence with psi integrated out: Newton mode, Laplace value and quadrature per (cell, clone) (clone_evidence / heldout_evidence), additions to ABI 6
     "ca_clone_evidence", "ca_group_clone_evidence",
     # gene-reweighted log-likelihood for every replicate of a bootstrap, votes and shares reduced on the device (clone_loglik_reweighted / bootstrap_assignments),
@@ -216,6 +219,9 @@ def load_library(path=None):
     lib.ca_predictive_moments.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
     lib.ca_predictive_moments_kernel_ms.argtypes = [C.POINTER(C.c_double)]
+    lib.ca_clone_separability.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
+    lib.ca_clone_separability_kernel_ms.argtypes = [C.POINTER(C.c_double)]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -1249,6 +1255,41 @@ def predictive_moments(E, V, U, clone, total, device=0):
 def predictive_moments_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``predictive_moments`` call took (HIP events around each launch; 0 without factors)."""
     return _last_kernel_ms("ca_predictive_moments_kernel_ms")
+
+
+def clone_separability(E, V, U, device=0):
+    """How well expression separates every ordered pair of clones, per cell, in closed form; no counts are read (ca_clone_separability;
+    include/clonealign_hip.h states the outputs).  ``E`` [G, C]; ``V`` [G, D] and ``U`` [N, D]: one row per cell.  Without factors (both None) the values do not
+    depend on the cell and one row is returned.  Returns ``(logZ [N, C], excl, m1, m2, m3 [N, C, C])``, float64: for a row of clone ``a`` against clone ``b``
+    the per-read probability of a read that excludes ``b`` and the first three per-read moments of the log-likelihood ratio over the genes both clones
+    express.  A cell's values depend on its own row of ``U`` alone, so cells may be split over calls or devices.  Refusals raise EngineError."""
+    lib = load_library()
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError(f"clone_separability: E is {E.shape}; expected (genes, clones)")
+    G, Cn = E.shape
+    if (U is None) != (V is None):
+        raise ValueError("clone_separability: U and V go together (both, or neither)")
+    N, D = 1, 0
+    if U is not None:
+        U, V = np.ascontiguousarray(U, dtype=np.float64), np.ascontiguousarray(V, dtype=np.float64)
+        if U.ndim != 2 or V.ndim != 2 or V.shape[0] != G or U.shape[1] != V.shape[1]:
+            raise ValueError(f"clone_separability: U is {U.shape} and V is {V.shape}; expected (cells, D) and ({G}, D)")
+        N, D = int(U.shape[0]), int(U.shape[1])
+        if D == 0:
+            U = V = None
+    logZ = np.zeros((max(N, 1), Cn), dtype=np.float64)               # (never an empty buffer: the call wants five pointers also without cells)
+    pair = np.zeros((4, max(N, 1), Cn, Cn), dtype=np.float64)
+    err = C.create_string_buffer(256)
+    rc = lib.ca_clone_separability(N, G, Cn, D, _ptr(E), _ptr(V), _ptr(U), int(device), _ptr(logZ), _ptr(pair[0]), _ptr(pair[1]), _ptr(pair[2]), _ptr(pair[3]), err)
+    if rc != CA_OK:
+        raise EngineError(rc, err.value.decode() or "ca_clone_separability")
+    return logZ[:N], pair[0, :N], pair[1, :N], pair[2, :N], pair[3, :N]
+
+
+def clone_separability_kernel_ms():
+    """Milliseconds the kernel launches of this thread's last ``clone_separability`` call took (HIP events around each launch; 0 without factors)."""
+    return _last_kernel_ms("ca_clone_separability_kernel_ms")
 
 
 _NP_DTYPE = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2, np.dtype(np.uint16): 3, np.dtype(np.uint8): 4}

@@ -833,6 +833,40 @@ int ca_predictive_moments(int64_t N, int32_t G, int32_t C, int32_t D, const doub
 /* milliseconds the kernel launches of the calling thread's last ca_predictive_moments took (HIP events around each launch, summed; 0 after a refusal and at D = 0) */
 int ca_predictive_moments_kernel_ms(double* ms);
 
+/* Clone separability in closed form, needs no handle and reads no counts: per cell and ORDERED pair of clones (a, b), a != b, the per-read moments of the
+ * log-likelihood ratio Lambda = ll_a - ll_b of a row drawn from clone a -- a linear statistic of one multinomial -- and the per-read probability of a read
+ * that rules b out.  Layouts are row-major host arrays, as for ca_predictive_moments; float64 throughout.
+ *   e_gc = E[g][c] / sum_g E[g][c] (genes ascending): every output but logZ is invariant to a column's scale, and the normalisation keeps Delta small.
+ *   eta_ng = U_n . V_g, d ascending, and its shift m_n exactly as in ca_clone_loglik: one chain of fused multiply-adds from 0; m_n is the max of eta over
+ *   EVERY gene, taken per chunk of 512 genes, the chunks merged in ascending order under their overall max (linearly, each scaled by exp(m_chunk - m_n)).
+ *   Z_nc = sum_g e_gc exp(eta_ng - m_n);  p_ncg = e_gc exp(eta_ng - m_n) / Z_nc.
+ *   For a != b: S = {g: e_ga > 0 and e_gb > 0}, X = {g: e_ga > 0 and e_gb = 0}, delta_g = log e_ga - log e_gb on S (log e taken once per (gene, clone)),
+ *   Delta = log Z_na - log Z_nb, d_g = delta_g - Delta (= log p_nag - log p_nbg).
+ * Outputs:
+ *   logZ[n][c]    = m_n + log Z_nc                                                                                                  (N x C)
+ *   excl[n][a][b] = sum_{g in X} p_nag       the probability that one read of a row of clone a falls where b has copy number 0        (N x C x C)
+ *   m1, m2, m3 [n][a][b] = sum_{g in S} p_nag d_g^k, k = 1, 2, 3: m1 + (what excl leaves out) is KL(p_a || p_b) per read            (N x C x C each)
+ *     With factors they come from ONE float64 matrix product, cells x (C + 4 C (C - 1)) columns over the genes with exp(eta - m) on the left (the sums
+ *     Z, X = sum_X e exp, M_k = sum_S e delta^k exp), by the expanded forms with q = 1 - excl:  m1 = M1/Z_a - Delta q,  m2 = M2/Z_a - 2 Delta M1/Z_a +
+ *     Delta^2 q,  m3 = M3/Z_a - 3 Delta M2/Z_a + 3 Delta^2 M1/Z_a - Delta^3 q; within 1e-10 sum_S p (|delta| + |Delta|)^k of the per-gene sums.
+ * Exactly 0: the diagonal a = b of the four pair outputs; excl where X is empty; m1 = m2 = m3 where the columns a and b of e are equal bit for bit
+ * (E[:, b] = 2 E[:, a] included).  No NaN or inf for accepted input, |eta| = 700 included, with one exception by rule: where Z_na underflows to 0 under the
+ * shift (every positive gene of a lies about 745 or more below the cell's largest exponent) logZ[n][a] = -inf and every pair entry of that cell that
+ * involves a -- (a, b) and (b, a) -- is 0; the mask is applied before anything is divided.
+ * Sums run in a fixed order without float atomics: two calls agree bit for bit.  A cell's values depend on its own row of U alone -- not on N, the internal
+ * batching (at most 65 536 cells a batch) or the chunking of the columns -- so a caller may split the cells over calls or devices; there is no ca_group_*
+ * form.  Device buffers stay below 256 MB (the cells go in batches and, for many clones, the columns in chunks) as long as sixteen cells' rows do, about
+ * 300 clones.  The caller's buffers are overwritten.  D = 0: the values do not depend on the cell; the host computes one row from the per-gene sums and
+ * fills all N (kernel_ms 0; last bits may differ from a call with a zero factor).
+ * CA_ERR_INVALID (the message starts "ca_clone_separability: " and names the argument; nothing is written to any output): C < 2, G < 1, N < 0, D outside
+ * [0, 8]; D > 0 with U or V NULL; E NULL or any output NULL; N C C >= 2^60; a negative or non-finite entry of E; a column of E that sums to 0 or to a
+ * non-finite value; a non-finite entry of U or V.  N = 0 is no error.  err (optional, >= 256 bytes) receives the message on failure. */
+int ca_clone_separability(int64_t N, int32_t G, int32_t C, int32_t D, const double* E /* G x C */, const double* V /* G x D, or NULL */,
+                          const double* U /* N x D, or NULL */, int32_t device, double* logZ /* N x C */, double* excl /* N x C x C */,
+                          double* m1 /* N x C x C */, double* m2 /* N x C x C */, double* m3 /* N x C x C */, char* err);
+/* milliseconds the kernel launches of the calling thread's last ca_clone_separability took (HIP events around each launch, summed; 0 after a refusal and at D = 0) */
+int ca_clone_separability_kernel_ms(double* ms);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ONE fit, cell-sharded over several devices of ONE process (ABI 6; SURVEY.md section 8b "multi-GPU via one process / 8 devices,
  * communicator created per fit", section 8e).  The reference's caller is a single R session: inference_tflow() is called once
