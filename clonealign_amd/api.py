@@ -2512,6 +2512,231 @@ def dosage_response(fit, Y, L, *, moments=None, kappa_max=8.0, max_iter=50, tol=
     return _dosage_fit(T, X, Ls, use, float(kappa_max), int(max_iter), float(tol))
 
 
+def _profile_operands_host(mu, kappa, blocks, G, what="copy_number_profile"):
+    """``mu`` [G], ``kappa`` [J] and the int labels ``blocks`` [G] (or None) of ``ca_copy_number_profile`` with its refusals as ValueError.  Returns
+    ``(mu, kappa, blocks, B)``; ``B = G`` without labels."""
+    mu, kappa = np.asarray(mu, dtype=np.float64).reshape(-1), np.asarray(kappa, dtype=np.float64).reshape(-1)
+    if mu.shape[0] != G:
+        raise ValueError(f"{what}: mu has {mu.shape[0]} entries but E has {G} rows (genes)")
+    for name, v, row in (("mu", mu, "gene"), ("kappa", kappa, "candidate")):
+        wrong = np.flatnonzero(~np.isfinite(v) | (v < 0))
+        if wrong.size:
+            raise ValueError(f"{what}: {name} has a negative or non-finite entry ({row} {wrong[0]})")
+    if not 1 <= kappa.shape[0] <= 16:
+        raise ValueError(f"{what}: J = {kappa.shape[0]} is outside [1, 16]")
+    if blocks is None:
+        return mu, kappa, None, G
+    blocks = np.asarray(blocks, dtype=np.int64).reshape(-1)
+    if blocks.shape[0] != G:
+        raise ValueError(f"{what}: blocks has {blocks.shape[0]} labels but E has {G} rows (genes)")
+    B = int(blocks.max()) + 1
+    wrong = np.flatnonzero(blocks < 0)
+    if wrong.size:
+        raise ValueError(f"{what}: block_of_gene[{wrong[0]}] = {blocks[wrong[0]]} is outside [0, {B})")
+    return mu, kappa, blocks, B
+
+
+def _copy_number_profile_host(E, V, U, clone, total, mu, kappa, blocks=None, work=1 << 22):
+    """Numpy float64 restatement of ``ca_copy_number_profile`` (include/clonealign_hip.h states the output): per cell ``eta``, the shift ``m``, ``w = E
+    exp(eta - m)`` and ``Z`` as in ``_predictive_moments_host``; ``x = exp(eta - m) / Z`` for every gene and ``p = w / Z``.  Per-gene mode: ``a = ((mu
+    kappa_j - E) / E) p`` where ``E > 0``, ``(mu kappa_j) x`` where ``E = 0``.  Block mode (``blocks``: int labels [G] in [0, B)): the shares ``A = sum_{g in
+    b} mu_g x`` and ``S = sum_{g in b} p`` (1 exactly where the block holds every expressed gene of the cell's clone, at most ``1 - 2^-53`` where it does not), ``a = max(kappa_j A - S, -1)``, and 0
+    by rule where every gene of the block has ``mu_g kappa_j == E[g, c]``.  ``cost[b, c, j]`` = the sum over the clone's cells with counts of ``total
+    log1p(a)``.  At most ``work`` (cell, gene-or-block, candidate) terms at a time.  Refusals are the library's, as ValueError."""
+    E, V, U, clone, total, N, G, C, D = _model_inputs_host(E, V, U, clone, total, "copy_number_profile")
+    mu, kappa, blocks, B = _profile_operands_host(mu, kappa, blocks, G)
+    J = kappa.shape[0]
+    cost = np.zeros((B, C, J))
+    delta = (mu[:, None] * kappa[None, :])[:, None, :] - E[:, :, None]                      # [G, C, J]: the product rounded, then the difference
+    if blocks is None:
+        cf = np.where(E[:, :, None] > 0, delta / np.where(E > 0, E, 1.0)[:, :, None], delta)
+    else:
+        onehot = np.zeros((G, B))
+        onehot[np.arange(G), blocks] = 1.0
+        npos = onehot.T @ (E > 0).astype(np.float64)                                         # [B, C]
+        full = (npos == npos.sum(0, keepdims=True)) & (npos.sum(0, keepdims=True) > 0)
+        same = (onehot.T @ (delta != 0).reshape(G, C * J).astype(np.float64)).reshape(B, C, J) == 0
+    chunk = max(1, int(work) // (B * J if blocks is not None else G * J))
+    live = np.flatnonzero(total > 0)
+    for lo in range(0, live.size, chunk):
+        rows = live[lo:lo + chunk]
+        e = E[:, clone[rows]].T                                      # [cells, G]
+        pos = e > 0
+        eta = np.zeros(e.shape)
+        for d in range(D):
+            eta = eta + U[rows, d:d + 1] * V[None, :, d]
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            m = np.where(pos, eta, -np.inf).max(1, keepdims=True)
+            ex = np.exp(eta - m)
+            w = np.where(pos, e * ex, 0.0)
+            top = w.argmax(1)[:, None]                               # the largest w (the first such gene) goes last into the sum
+            rest = w.copy()
+            np.put_along_axis(rest, top, 0.0, 1)
+            Z = rest.sum(1, keepdims=True) + np.take_along_axis(w, top, 1)
+            p, xg = w / Z, ex / Z
+            t = total[rows].astype(np.float64)
+            for c in np.unique(clone[rows]):
+                sel = clone[rows] == c
+                if blocks is None:
+                    q = np.where(pos[sel], p[sel], xg[sel])[:, :, None]
+                    a = np.where(cf[None, :, c, :] == 0, 0.0, cf[None, :, c, :] * q)
+                else:
+                    A, S = (mu[None, :] * xg[sel]) @ onehot, p[sel] @ onehot
+                    S = np.where(full[None, :, c], 1.0, np.minimum(S, 1.0 - 2.0 ** -53))
+                    a = np.maximum(kappa[None, None, :] * A[:, :, None] - S[:, :, None], -1.0)
+                    a = np.where(same[None, :, c, :], 0.0, a)
+                cost[:, c, :] += (t[sel, None, None] * np.log1p(a)).sum(0)
+    return cost
+
+
+def _profile_gain(T, E, mu, kappa, blocks, B):
+    """The observed side of the profile: ``gain[b, c, j] = sum_{g in b} xlogy(T, mu_g kappa_j) - xlogy(T, E)`` with ``0 log 0 = 0``.  A gene whose reads are
+    impossible under both weights (``T > 0``, ``E = 0`` and ``mu_g kappa_j = 0``) adds 0; otherwise an impossible candidate makes the entry ``-inf``, and
+    reads on a gene with ``E = 0`` make every possible candidate ``+inf``: never NaN."""
+    from scipy.special import xlogy
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tk = xlogy(T[:, :, None], (mu[:, None] * kappa[None, :])[:, None, :])                # [G, C, J]
+        te = xlogy(T, E)[:, :, None]
+        term = np.where(np.isneginf(tk) & np.isneginf(te), 0.0, tk - te)
+    if blocks is None:
+        return term
+    fin = np.isfinite(term)
+    gain, neg, posi = np.zeros((B,) + term.shape[1:]), np.zeros((B,) + term.shape[1:], dtype=bool), np.zeros((B,) + term.shape[1:], dtype=bool)
+    np.add.at(gain, blocks, np.where(fin, term, 0.0))
+    np.logical_or.at(neg, blocks, np.isneginf(term))
+    np.logical_or.at(posi, blocks, np.isposinf(term))
+    return np.where(neg, -np.inf, np.where(posi, np.inf, gain))
+
+
+def copy_number_profile(fit, Y, L, *, candidates=None, blocks=None, prior=None, x=None, saturate=True, saturation_threshold=6, engine_opts=None,
+                        host=False):
+    """Which copy number do the expression data support for this gene -- or this segment -- in this clone, and by how many nats?  The likelihood profile
+    over one entry ``L[g, c]`` (or over all genes of a block at once, ``blocks``: a label per gene, chromosome arms or copy-number segments) with ``mu``,
+    ``W``, ``psi``, ``beta`` and the called clones held at the fit's values: replacing the weight ``mu_g L[g, c]`` by ``mu_g kappa_j`` in clone ``c`` only
+    changes the total multinomial log-likelihood by exactly ``delta_ll = gain - cost``, where ``gain`` needs the observed per-clone totals alone and
+    ``cost``, the change of the cells' normalisers, is one pass on the device that reads no counts (``engine.copy_number_profile`` /
+    ``ca_copy_number_profile``; include/clonealign_hip.h states it).
+
+    Arguments, label checks and the treatment of "unassigned" cells are ``predictive_moments``'s.  ``candidates``: up to 16 copy numbers, by default the
+    integers ``0 .. saturation_threshold``; ``kappa`` is ``candidates`` after ``saturate`` (candidates that coincide there, negatives and non-finite values:
+    ValueError).  ``prior``: weights over the candidates (uniform by default).  Observed side, one engine with ``Y`` resident (``engine_opts`` go to its
+    constructor): ``T_observed`` from ``clone_gene_sums``.  ``host=True`` runs the numpy restatement (``_copy_number_profile_host``) on both sides instead;
+    there is no silent fallback otherwise.
+
+    Returns a dict; the first axis is the genes, or with ``blocks`` the blocks in order of first appearance (``block_names``, ``block_of_gene``).
+    ``candidates``, ``kappa`` [J]; ``T_observed`` [genes, clones]; ``gain``, ``cost``, ``delta_ll`` [., clones, J]; ``input_cn`` [., clones]: ``L`` as the fit
+    used it (after ``saturate``), NaN for a block whose genes disagree in that clone; ``map_cn`` = ``kappa`` at the largest ``delta_ll`` (the first such);
+    ``log_bf`` = ``max_j delta_ll``, the log Bayes factor of the best candidate against the matrix as given, whose ``delta_ll`` is 0 by definition;
+    ``posterior`` [., clones, J] = softmax over the candidates of ``delta_ll + log prior``; ``posterior_input`` = its value at ``input_cn`` (NaN where
+    ``input_cn`` is NaN or no candidate); ``clone_cells``.  Never NaN in ``delta_ll``: ``-inf`` where the candidate is 0 and the clone has reads on the gene
+    (on a gene of the block), ``+inf`` for every positive candidate where the matrix as given is impossible (``E = 0`` with reads), ``-inf`` also where the candidate leaves a cell with reads no expressed gene at all (``cost = -inf``) even if none of the clone's
+    reads sit on the genes in question, ``0 log 0 = 0``; a clone
+    without cells has ``delta_ll = 0`` and ``posterior`` = the prior.
+
+    What the numbers are not.  The profile is CONDITIONAL on the fitted ``mu``, ``W``, ``psi`` and clone calls: a gene whose copy number is wrong by one
+    factor in ALL clones is absorbed by ``mu`` and invisible here, and the fit's ``mu`` was itself estimated under the wrong ``L`` -- so correct
+    (``apply_copy_number_calls``) and refit rather than read the profile as final.  And it is MULTINOMIAL: real counts are overdispersed, so ``log_bf`` is
+    anti-conservative -- a ranking on a depth-aware scale, not a calibrated Bayes factor."""
+    Ya, _Lm, Ls, E, U, V, idx, used, rows, Uu, N, G = _predictive_inputs(fit, Y, L, x, saturate, saturation_threshold)
+    C = E.shape[1]
+    mu = np.asarray(fit["ml_params"]["mu"], dtype=np.float64).reshape(-1)
+    cand = np.arange(int(saturation_threshold) + 1, dtype=np.float64) if candidates is None else np.asarray(candidates, dtype=np.float64).reshape(-1)
+    if not 1 <= cand.shape[0] <= 16:
+        raise ValueError(f"candidates has {cand.shape[0]} entries; between 1 and 16 are supported")
+    if not np.isfinite(cand).all() or (cand < 0).any():
+        raise ValueError("candidates must be finite and >= 0")
+    kappa = hostprep.saturate(cand, saturation_threshold) if saturate else cand.copy()
+    if np.unique(kappa).shape[0] != kappa.shape[0]:
+        raise ValueError(f"candidates coincide{' after saturation at ' + str(saturation_threshold) if saturate else ''}: {kappa.tolist()}")
+    J = kappa.shape[0]
+    names, bg = _block_labels(blocks, G) if blocks is not None else (None, None)
+    B = G if bg is None else len(names)
+    pr = np.full(J, 1.0 / J) if prior is None else np.asarray(prior, dtype=np.float64).reshape(-1)
+    if pr.shape[0] != J or not np.isfinite(pr).all() or (pr <= 0).any():
+        raise ValueError(f"prior must hold {J} positive weights, one per candidate")
+    pr = pr / pr.sum()
+    if host:
+        T_obs = np.zeros((G, C))
+        dense = Ya[used].toarray() if _is_sparse(Ya) else np.asarray(Ya)[used]
+        np.add.at(T_obs.T, idx[used], dense.astype(np.float64))
+        cost = _copy_number_profile_host(E, V, Uu, idx[used], rows, mu, kappa, bg)
+    else:
+        from . import engine as _engine
+        opts = dict(engine_opts or {})
+        eng = _engine.HipEngine(Ya, Ls, np.zeros((N, 0)), None, 0, **opts)
+        try:
+            T_obs = np.ascontiguousarray(eng.clone_gene_sums(idx)[0])
+        finally:
+            eng.close()
+        cost = _engine.copy_number_profile(E, V, Uu, idx[used], rows, mu, kappa, blocks=bg, device=int(opts.get("device", 0)))
+    gain = _profile_gain(T_obs, E, mu, kappa, bg, B)
+    with np.errstate(invalid="ignore"):
+        delta = np.where(np.isinf(gain), gain, np.where(np.isneginf(cost), -np.inf, gain - cost))
+    if bg is None:
+        input_cn = np.array(Ls, dtype=np.float64)
+    else:
+        lo, hi = np.full((B, C), np.inf), np.full((B, C), -np.inf)
+        np.minimum.at(lo, bg, Ls)
+        np.maximum.at(hi, bg, Ls)
+        input_cn = np.where(lo == hi, lo, np.nan)
+    jmap = delta.argmax(2)
+    best = np.take_along_axis(delta, jmap[:, :, None], 2)[:, :, 0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        wgt = np.where(np.isposinf(best)[:, :, None], np.isposinf(delta).astype(np.float64),
+                       np.exp(np.where(np.isneginf(best)[:, :, None], 0.0, delta - np.where(np.isfinite(best), best, 0.0)[:, :, None]))) * pr[None, None, :]
+    post = wgt / wgt.sum(2, keepdims=True)
+    hit = kappa[None, None, :] == input_cn[:, :, None]                                      # (NaN equals nothing)
+    post_in = np.where(hit.any(2), (post * hit).sum(2), np.nan)
+    out = {"candidates": cand, "kappa": kappa, "T_observed": T_obs, "gain": gain, "cost": cost, "delta_ll": delta, "input_cn": input_cn,
+           "map_cn": kappa[jmap], "log_bf": best, "posterior": post, "posterior_input": post_in,
+           "clone_cells": np.bincount(idx[used], minlength=C).astype(np.int64)}
+    if bg is not None:
+        out.update({"block_names": names, "block_of_gene": bg})
+    return out
+
+
+def suspect_copy_numbers(profile, log_bf=10.0):
+    """The entries of the copy-number matrix the expression data contradict: the (gene-or-block, clone) pairs of a ``copy_number_profile`` whose best
+    candidate differs from the matrix as given (``map_cn != input_cn``; a block whose genes disagree counts as different) with ``log_bf`` above the bar,
+    sorted by ``log_bf``, largest first.  Returns a list of dicts: ``index`` (the row of the profile), ``block`` (its label; None in per-gene mode),
+    ``clone`` (column), ``input_cn``, ``map_cn``, ``log_bf``, and the runner-up: ``runner_up_cn`` and ``runner_up_delta_ll``, the second-best candidate
+    and its ``delta_ll`` (NaN with a single candidate).  ``log_bf`` is ``copy_number_profile``'s: conditional on the fit and multinomial, so a ranking on
+    a depth-aware scale and anti-conservative on overdispersed counts."""
+    delta, lb, mp, ic, kappa = (np.asarray(profile[k]) for k in ("delta_ll", "log_bf", "map_cn", "input_cn", "kappa"))
+    rows, cols = np.nonzero((lb > float(log_bf)) & ~(mp == ic))
+    order = np.argsort(-lb[rows, cols], kind="stable")
+    names = profile.get("block_names")
+    out = []
+    for r, c in zip(rows[order].tolist(), cols[order].tolist()):
+        d = delta[r, c].copy()
+        d[int(d.argmax())] = -np.inf
+        j2 = int(d.argmax())
+        second = kappa.shape[0] > 1
+        out.append({"index": r, "block": None if names is None else names[r], "clone": c, "input_cn": float(ic[r, c]), "map_cn": float(mp[r, c]),
+                    "log_bf": float(lb[r, c]), "runner_up_cn": float(kappa[j2]) if second else float("nan"),
+                    "runner_up_delta_ll": float(d[j2]) if second else float("nan")})
+    return out
+
+
+def apply_copy_number_calls(profile, L, log_bf=10.0, blocks=None):
+    """A copy of ``L`` [genes, clones] (float64 array) with the entries ``suspect_copy_numbers(profile, log_bf)`` lists replaced by their ``map_cn`` --
+    whole blocks in block mode (``blocks``: the labels the profile was made with; by default the profile's own).  This is the matrix to refit with: the
+    profile is conditional on a ``mu`` that was estimated under the uncorrected matrix."""
+    Lm = np.array(_parse_cnv(L)[0], dtype=np.float64)
+    G = Lm.shape[0]
+    rows = np.asarray(profile["delta_ll"]).shape[0]
+    bg = profile.get("block_of_gene")
+    if blocks is not None:
+        if bg is None:
+            raise ValueError("the profile was made per gene: blocks does not apply")
+        bg = _block_labels(blocks, G)[1]
+    if (G if bg is None else int(np.max(bg)) + 1) != rows or (bg is not None and len(bg) != G) or Lm.shape[1] != np.asarray(profile["log_bf"]).shape[1]:
+        raise ValueError(f"L is {Lm.shape} but the profile has {rows} rows and {np.asarray(profile['log_bf']).shape[1]} clones")
+    for s in suspect_copy_numbers(profile, log_bf):
+        Lm[(s["index"] if bg is None else np.asarray(bg) == s["index"]), s["clone"]] = s["map_cn"]
+    return Lm
+
+
 def _logexpr_sums_host(Y, group_idx, n_groups, size_factors=None, chunk=4096):
     """Float64 host form of ``HipEngine.logexpr_sums`` for engines without it: Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time),
     ``group_idx`` in [-1, n_groups) with -1 = leave the cell out.  Same return value, same refusals (ValueError)."""

@@ -567,6 +567,37 @@ inline hipError_t launch_predmom_finish(hipStream_t stream, const ca_predmom_ops
   return hipGetLastError();
 }
 
+// ---- k_cnp_cell / k_cnp_gene<JB> / k_cnp_block / k_cnp_finish: the launches of ca_copy_number_profile on one batch of cells (no engine: the call owns its stream) ----
+// the call's tables (E and V transposed, mu, kappa, in per-gene mode their products mk [J][G], the running sums acc [C][J][W], W = G or B; in block mode the run list, `full` [C][B] and `same` [C][J][B]) and
+// the batch's arrays: the cells' inputs, m and Z, the shares [cells][2][B], the list of cells with counts by clone, its strips, the first strip of every clone, the strip sums
+struct ca_cnp_ops { const double *Et, *Vt, *U, *mu, *kappa, *mk; const int32_t* clone; const int64_t* total; double *w_blk, *m, *z, *share; const int32_t *list, *first, *run_gene, *run_first;
+                    const unsigned char *full, *same; const ca_pm_strip* strips; double *part, *acc; int64_t n_cnt; int blocks, nstrips, G, C, D, J, B; bool w_lds, by_block; };
+inline hipError_t launch_cnp_cell(hipStream_t stream, const ca_cnp_ops& o) {
+  hipLaunchKernelGGL(k_cnp_cell, dim3((unsigned)o.blocks), dim3(CA_PM_TB), o.w_lds ? (size_t)o.G * sizeof(double) : 0, stream, o.Et, o.Vt, o.U, o.clone, o.total,
+                     o.w_lds ? nullptr : o.w_blk, o.m, o.z, o.mu, o.by_block ? o.run_gene : nullptr, o.run_first, o.full, o.share, o.n_cnt, o.G, o.D, o.B);
+  return hipGetLastError();
+}
+template <int JB>
+hipError_t cnp_gene_t(hipStream_t stream, const ca_cnp_ops& o) {
+  const int gtiles = cdiv(o.G, CA_PM_TB);
+  hipLaunchKernelGGL((k_cnp_gene<JB>), dim3((unsigned)((int64_t)gtiles * o.nstrips)), dim3(CA_PM_TB), 0, stream, o.Et, o.Vt, o.U, o.total, o.m, o.z, o.list, o.strips, o.mk, o.part,
+                     o.G, o.D, o.J, gtiles);
+  return hipGetLastError();
+}
+inline hipError_t launch_cnp_sum(hipStream_t stream, const ca_cnp_ops& o) {   // (the accumulators live in registers: one instantiation per bucket of J)
+  if (o.by_block) {
+    const int tiles = cdiv(o.J * o.B, CA_PM_TB);
+    hipLaunchKernelGGL(k_cnp_block, dim3((unsigned)((int64_t)tiles * o.nstrips)), dim3(CA_PM_TB), 0, stream, o.share, o.total, o.list, o.strips, o.kappa, o.same, o.part, o.B, o.J, tiles);
+    return hipGetLastError();
+  }
+  return o.J <= 4 ? cnp_gene_t<4>(stream, o) : o.J <= 8 ? cnp_gene_t<8>(stream, o) : cnp_gene_t<16>(stream, o);
+}
+inline hipError_t launch_cnp_finish(hipStream_t stream, const ca_cnp_ops& o) {
+  const int64_t JW = (int64_t)o.J * (o.by_block ? o.B : o.G);
+  hipLaunchKernelGGL(k_cnp_finish, dim3((unsigned)cdiv(JW * o.C, CA_PM_TB)), dim3(CA_PM_TB), 0, stream, o.part, o.first, o.acc, JW, o.C);
+  return hipGetLastError();
+}
+
 // ---- k_sep_loge / k_sep_build / k_boot_prod<float, true, NT> / k_sep_scale / k_sep_merge / k_sep_finish: the launches of ca_clone_separability on one batch of cells (no engine: the call owns its stream) ----
 // the call's tables (e and log e [Gp][C], the padded factors Vt [Gp][CA_LL_DMAX]); the right-hand side B [Gp][W] of the columns [c_lo, c_lo + W); the batch's padded
 // factors Ut, its slabs (part, mpart, the chunks' scales wk, the shift m), the merged rows R [n_cnt][ncolp] and the five outputs

@@ -958,4 +958,5 @@ __global__ void __launch_bounds__(CA_TB, (DEPTH == 1 && !C16 && !S2F) ? CA_YS_RI
 #include "ca_k_predictive.hip.h"   // replicate rows of ca_simulate_counts reduced where they are drawn (ca_predictive_stats): the table once per cell, per replicate one float64 and int64 per-gene totals; the rows are never stored
 #include "ca_k_predmom.hip.h"   // the replicates' moments in closed form (ca_predictive_moments): per cell the mean and variance of the log-likelihood's linear part, per (gene, clone) three cumulants of the totals; a block per cell, then a lane per gene over strips of cells sorted by clone; never reads Y
 #include "ca_k_separability.hip.h"   // clone separability in closed form (ca_clone_separability): the right-hand side of one float64 product of exp(eta - m) against C + 4 C (C - 1) columns (run by k_boot_prod), the linear merge of its gene chunks and the per-pair epilogue; never reads Y
+#include "ca_k_cnprofile.hip.h"   // the copy-number likelihood profile (ca_copy_number_profile): per (gene or block of genes, clone, candidate copy number) the sum over the clone's cells of total log1p(the change of the cell's normaliser); a lane per gene with the candidates' accumulators in registers, or a lane per (candidate, block) over per-cell shares; never reads Y
 #include "ca_k_logexpr.hip.h"   // log-expression sums per gene and cell group on the resident matrix (ca_logexpr_sums): one float64 sweep, pieces cut at group boundaries

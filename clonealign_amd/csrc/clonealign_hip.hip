@@ -907,5 +907,6 @@ int ca_preprocess(int64_t N, int32_t G, int32_t C, int32_t layout, int32_t y_dty
 #include "ca_eng_predictive.inc"   // C ABI without a handle: the replicates' log-likelihoods and per-clone gene totals without the rows (ca_predictive_stats)
 #include "ca_eng_predmom.inc"   // C ABI without a handle: the replicates' moments in closed form, per cell and per (gene, clone) (ca_predictive_moments)
 #include "ca_eng_separability.inc"   // C ABI without a handle: per cell and ordered pair of clones the per-read moments of the log-likelihood ratio, in closed form (ca_clone_separability)
+#include "ca_eng_cnprofile.inc"   // C ABI without a handle: the expression side of the likelihood profile over one entry or one block of the copy-number matrix, per clone and candidate copy number (ca_copy_number_profile)
 
 }  // extern "C"

@@ -67,6 +67,9 @@ EXPORTS = (
     # clone separability in closed form: per cell and ordered pair of clones the per-read moments of the log-likelihood ratio and the probability of an
     # excluding read (clone_separability / reads_needed / merge_candidates), no handle, additions to ABI 6
     "ca_clone_separability", "ca_clone_separability_kernel_ms",
+    # the expression side of the likelihood profile over the copy-number matrix: per (gene or block of genes, clone, candidate copy number) the change of the
+    # cells' normalisers (copy_number_profile / suspect_copy_numbers / apply_copy_number_calls), no handle, additions to ABI 6
+    "ca_copy_number_profile", "ca_copy_number_profile_kernel_ms",
     # clone evidence with psi integrated out: Newton mode, Laplace value and quadrature per (cell, clone) (clone_evidence / heldout_evidence), additions to ABI 6
     "ca_clone_evidence", "ca_group_clone_evidence",
     # gene-reweighted log-likelihood for every replicate of a bootstrap, votes and shares reduced on the device (clone_loglik_reweighted / bootstrap_assignments),
@@ -222,6 +225,9 @@ def load_library(path=None):
     lib.ca_clone_separability.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p]
     lib.ca_clone_separability_kernel_ms.argtypes = [C.POINTER(C.c_double)]
+    lib.ca_copy_number_profile.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p]
+    lib.ca_copy_number_profile_kernel_ms.argtypes = [C.POINTER(C.c_double)]
     lib.ca_get_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_set_param.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
     lib.ca_get_gradient.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
@@ -1290,6 +1296,38 @@ def clone_separability(E, V, U, device=0):
 def clone_separability_kernel_ms():
     """Milliseconds the kernel launches of this thread's last ``clone_separability`` call took (HIP events around each launch; 0 without factors)."""
     return _last_kernel_ms("ca_clone_separability_kernel_ms")
+
+
+def copy_number_profile(E, V, U, clone, total, mu, kappa, blocks=None, device=0):
+    """The expression side of the likelihood profile over the copy-number matrix (ca_copy_number_profile; include/clonealign_hip.h states it): ``cost[b, c, j]``
+    = the sum over the cells of clone ``c`` of ``total log1p(sum_{g in b} (mu_g kappa_j - E[g, c]) x_ng)``, what replacing ``E[g, c]`` by ``mu_g kappa_j`` for the
+    genes of block ``b`` adds to the cells' ``total log Z``.  Arguments as for ``predictive_moments``; ``mu`` [G] and ``kappa`` [J], 1 <= J <= 16, finite and
+    >= 0; ``blocks``: None (per-gene mode, every gene its own block) or int labels [G] in [0, B) with B = the largest label + 1, at most 2048.  Returns float64
+    [G or B, C, J].  No counts are read; the tables of cells split over calls add up to within rounding.  Refusals raise EngineError."""
+    lib = load_library()
+    E, V, U, clone, total, N, G, Cn, D = _model_operands("copy_number_profile", E, V, U, clone, total)
+    mu = np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)
+    kappa = np.ascontiguousarray(kappa, dtype=np.float64).reshape(-1)
+    if mu.shape[0] != G:
+        raise ValueError(f"copy_number_profile: mu has {mu.shape[0]} entries but E has {G} rows (genes)")
+    B = G
+    if blocks is not None:
+        blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1)
+        if blocks.shape[0] != G:
+            raise ValueError(f"copy_number_profile: blocks has {blocks.shape[0]} labels but E has {G} rows (genes)")
+        B = int(blocks.max()) + 1 if G else 0
+    cost = np.zeros((max(B, 1), Cn, max(kappa.shape[0], 1)), dtype=np.float64)      # (never an empty buffer; a refused B or J leaves it unread)
+    err = C.create_string_buffer(256)
+    rc = lib.ca_copy_number_profile(N, G, Cn, D, _ptr(E), _ptr(V), _ptr(U), _ptr(clone), _ptr(total), _ptr(mu), int(kappa.shape[0]), _ptr(kappa),
+                                    B, _ptr(blocks), int(device), _ptr(cost), err)
+    if rc != CA_OK:
+        raise EngineError(rc, err.value.decode() or "ca_copy_number_profile")
+    return cost
+
+
+def copy_number_profile_kernel_ms():
+    """Milliseconds the kernel launches of this thread's last ``copy_number_profile`` call took (HIP events around each launch; 0 without factors)."""
+    return _last_kernel_ms("ca_copy_number_profile_kernel_ms")
 
 
 _NP_DTYPE = {np.dtype(np.float64): 0, np.dtype(np.float32): 1, np.dtype(np.int32): 2, np.dtype(np.uint16): 3, np.dtype(np.uint8): 4}

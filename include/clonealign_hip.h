@@ -867,6 +867,40 @@ int ca_clone_separability(int64_t N, int32_t G, int32_t C, int32_t D, const doub
 /* milliseconds the kernel launches of the calling thread's last ca_clone_separability took (HIP events around each launch, summed; 0 after a refusal and at D = 0) */
 int ca_clone_separability_kernel_ms(double* ms);
 
+/* The expression side of a likelihood profile over the copy-number matrix, needs no handle and reads no counts.  Notation, layouts (row-major host arrays) and
+ * refusals about E, V, U, clone, total are ca_predictive_moments's, and so are eta, the shift m_n, w_g = E[g][c_n] exp(eta_g - m_n) and Z_n (the same statements,
+ * the same bits).  Replacing the weight E[g][c] by mu_g kappa_j for the genes g of one block b, in clone c only, with everything else held fixed, changes the
+ * total multinomial log-likelihood by gain - cost, where gain = sum_{g in b} T[g][c] (log(mu_g kappa_j) - log E[g][c]) needs the observed per-clone totals T
+ * alone (ca_clone_gene_sums; the caller's part) and
+ *   cost[b][c][j] = sum over the call's cells with clone[n] == c and total_n > 0 of total_n log1p(a_nbj),   a_nbj = sum_{g in b} (mu_g kappa_j - E[g][c]) x_ng,
+ *   x_ng = exp(eta_ng - m_n) / Z_n                                                                                                  (B x C x J float64)
+ * is this call's output.  Float64 throughout.
+ * Per-gene mode (block_of_gene NULL, B == G; every gene its own block): delta = mu_g kappa_j - E (the product rounded, then the difference);
+ *   a = (delta / E) p_ng with p_ng = w_g / Z_n where E > 0 (p = 1 exactly where w = Z), a = delta x_ng where E = 0; a >= -1 always.
+ * Block mode (block_of_gene[g] in [0, B), any labelling, B <= 2048): per (cell, block) the two shares A = sum_{g in b} mu_g x_ng and S = sum_{g in b} p_ng, each
+ *   summed in an order fixed by the labelling alone; a = max(kappa_j A - S, -1).  Two rules keep what a sum of rounded shares cannot: S = 1 exactly where the
+ *   block holds every gene with E[g][c] > 0 of the cell's clone and S = min(sum, 1 - 2^-53) where it does not (so a > -1 there, however the shares round), and
+ *   the entry is 0 where every gene of the block has mu_g kappa_j == E[g][c] bit for bit.
+ * Exactly 0: a clone without cells in the call, cells with total_n = 0 (they join no sum), an entry whose delta is 0 (an empty block included).
+ * -inf, and only there: where a = -1 for a cell with reads -- per gene, mu_g kappa_j = 0 on a gene with p_ng = 1 (the clone's only expressed gene, or one
+ * beside which every other weight of the cell vanishes in float64: w = Z); in block mode, kappa_j A = 0 on a block that holds every expressed gene of the
+ * clone.  The caller's gain is -inf there as well whenever the counts are possible under E.  No NaN for accepted input as long as exp(eta_g - m_n) stays finite
+ * for the genes with E[g][c] = 0 too (m_n is the largest eta over the genes with E > 0; about 709 above it the term overflows to +inf).
+ * Sums run in a fixed order without float atomics: two calls agree bit for bit.  The sums over cells are grouped by the call (cells listed by clone, in strips
+ * whose length depends on N, G, C, D, J and B alone), so across a split of the cells the tables add up to within rounding, not bit for bit.  D = 0: x depends
+ * on the clone alone and the host does the whole call in O(G C J + N); its last bits may differ from a call with a zero factor.  Device buffers stay below
+ * 64 MB per kind (the cells go in batches that fit) as long as C x J x B float64 do; there is no ca_group_* form (the tables of a split add up).
+ * CA_ERR_INVALID (the message starts "ca_copy_number_profile: " and names the argument; nothing is written to cost): everything ca_predictive_moments refuses
+ * about E, V, U, clone, total, D, N, G and C; mu, kappa or cost NULL; a negative or non-finite entry of mu or kappa; J outside [1, 16]; block_of_gene NULL with
+ * B != G; a label outside [0, B); B > 2048 in block mode (use per-gene mode for a block per gene).  N = 0 is no error: zeros.  The caller's buffer is
+ * overwritten.  err (optional, >= 256 bytes) receives the message on failure. */
+int ca_copy_number_profile(int64_t N, int32_t G, int32_t C, int32_t D, const double* E /* G x C */, const double* V /* G x D, or NULL */,
+                           const double* U /* N x D, or NULL */, const int32_t* clone /* N */, const int64_t* total /* N */,
+                           const double* mu /* G, finite, >= 0 */, int32_t J, const double* kappa /* J, finite, >= 0 */,
+                           int32_t B, const int32_t* block_of_gene /* G, or NULL: per-gene mode */, int32_t device, double* cost /* B x C x J */, char* err);
+/* milliseconds the kernel launches of the calling thread's last ca_copy_number_profile took (HIP events around each launch, summed; 0 after a refusal and at D = 0) */
+int ca_copy_number_profile_kernel_ms(double* ms);
+
 /* ------------------------------------------------------------------------------------------------------------------------------
  * ONE fit, cell-sharded over several devices of ONE process (ABI 6; SURVEY.md section 8b "multi-GPU via one process / 8 devices,
  * communicator created per fit", section 8e).  The reference's caller is a single R session: inference_tflow() is called once
