@@ -958,6 +958,273 @@ def detect_doublets(fit, Y, L, doublet_rate=0.05, doublet_probability=0.5, clone
                          weights=grid, ml_params={"clone_probs": clone_probs})
 
 
+MIX_CMAX = 32                                                       # components of a mixture call, extra profiles included (include/clonealign_hip.h)
+
+
+def _mixture_start(start, n, C, lo=0, what="clone_mixture"):
+    """The start of a mixture call as [n, C] float64 after the library's refusals (ValueError names the offender), or None."""
+    if start is None:
+        return None
+    st = np.asarray(start, dtype=np.float64)
+    if st.ndim == 1 and st.shape[0] == C:
+        st = np.broadcast_to(st, (n, C))
+    if st.shape != (n, C):
+        raise ValueError(f"{what}: start is {st.shape}; expected ({n}, {C})")
+    wrong = np.argwhere(~np.isfinite(st) | (st < 0))
+    if wrong.size:
+        raise ValueError(f"{what}: start has a negative or non-finite entry (cell {lo + wrong[0][0]}, clone {wrong[0][1]})")
+    off = np.flatnonzero(~(np.abs(st.sum(1) - 1.0) <= 1e-9))
+    if off.size:
+        raise ValueError(f"{what}: the start of cell {lo + off[0]} sums to {st[off[0]].sum()}: off 1 by more than 1e-9")
+    return np.ascontiguousarray(st)
+
+
+def _mixture_settings(C, max_iter, tol, what="clone_mixture"):
+    """(max_iter, tol) of a mixture call after the library's refusals."""
+    if C > MIX_CMAX:
+        raise ValueError(f"{what}: C = {C} clones: a mixture takes at most {MIX_CMAX}")
+    if int(max_iter) < 0:
+        raise ValueError(f"{what}: max_iter = {max_iter} is negative")
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError(f"{what}: tol_nats = {tol} is negative or not finite")
+    return int(max_iter), float(tol)
+
+
+def _mix_chol_solve(A, b):
+    """``x`` with ``A x = b`` for a batch of symmetric matrices [n, C, C] by Cholesky (the lower triangle is read), and ``ok`` [n]: every pivot positive and
+    finite.  Rows that break down return garbage that the caller ignores."""
+    n, C, _ = A.shape
+    Lw = A.copy()
+    ok = np.ones(n, dtype=bool)
+    with np.errstate(all="ignore"):
+        for k in range(C):
+            p = Lw[:, k, k]
+            good = (p > 0) & np.isfinite(p)
+            ok &= good
+            l = np.sqrt(np.where(good, p, 1.0))
+            Lw[:, k, k] = l
+            Lw[:, k + 1:, k] /= l[:, None]
+            Lw[:, k + 1:, k + 1:] -= Lw[:, k + 1:, k, None] * Lw[:, None, k + 1:, k]
+        x = b.copy()
+        for k in range(C):
+            x[:, k] /= Lw[:, k, k]
+            x[:, k + 1:] -= Lw[:, k + 1:, k] * x[:, k, None]
+        for k in range(C - 1, -1, -1):
+            x[:, k] /= Lw[:, k, k]
+            x[:, :k] -= Lw[:, k, :k] * x[:, k, None]
+    return x, ok
+
+
+def _clone_mixture_host(Y, E, U=None, V=None, start=None, max_iter=50, tol=1e-3, const=True, cells=None, want_ll=True, want_grad=True, chunk=128):
+    """Float64 host form of ``HipEngine.clone_mixture`` for engines without it, the same algorithm in numpy (include/clonealign_hip.h has the formulas, the
+    round and the rules): Y [N, G] dense or scipy.sparse (densified ``chunk`` cells at a time), E [G, C], U [N, D] and V [G, D] or both None, ``start``
+    [n, C] for the cells of the range or None (uniform).  Same return value, same rules (unsupported entries left out and ``mix_ll = -inf``, the uniform
+    restart of a start that excludes the data, ``max_iter = 0`` evaluates), same refusals (ValueError).  Every cell of a chunk is evaluated in every round
+    and a stopped cell's weights are frozen, so a cell's values do not depend on when the others stop: T rounds are T calls of one round, bit for bit."""
+    from scipy.special import gammaln
+    E, U, V, D, esum = _ll_inputs(Y, E, U, V, "clone_mixture")
+    N, G = Y.shape
+    C = E.shape[1]
+    max_iter, tol = _mixture_settings(C, max_iter, tol)
+    lo0, hi0 = (0, N) if cells is None else (int(cells[0]), int(cells[1]))
+    if lo0 < 0 or hi0 < lo0 or hi0 > N:
+        raise ValueError(f"clone_mixture: the cell range [{lo0}, {lo0} + {hi0 - lo0}) is outside [0, {N}]")
+    n = hi0 - lo0
+    st = _mixture_start(start, n, C, lo0)
+    Ys = Y[lo0:hi0]
+    Us = None if D == 0 else U[lo0:hi0]
+    out = {"ll": _clone_loglik_host(Ys, E, Us, V if D > 0 else None, const=const) if want_ll else None, "weights": np.empty((n, C)),
+           "grad": np.empty((n, C)) if want_grad else None, "mix_ll": np.empty(n), "bound": np.empty(n), "rounds": np.zeros(n, dtype=np.int32)}
+    steps = (1.0, 0.5, 0.25, 0.125)
+    for lo, Yc, eta, _m, logz in _cell_chunks(Ys, chunk, E, Us, V):
+        k = Yc.shape[0]
+        s = Yc.sum(1)
+        base = (Yc * eta).sum(1) if D > 0 else np.zeros(k)
+        if D == 0:
+            logz = np.broadcast_to(np.log(esum)[None, :], (k, C))
+        if const:
+            base = base + gammaln(s + 1.0) - gammaln(Yc + 1.0).sum(1)
+        lz = logz.min(1)
+        q = E[None, :, :] * np.exp(lz[:, None] - logz)[:, None, :]   # [k, G, C], every factor <= 1
+        pos = Yc > 0
+        usable = pos & (q.sum(2) > 0)
+        ninf = (pos & ~usable).any(1)
+        seff = np.where(usable, Yc, 0.0).sum(1)
+        ssafe = np.where(seff > 0, seff, 1.0)
+        ysafe = np.where(pos, Yc, 1.0)
+
+        def evaluate(pi, hess):
+            m = np.einsum("ngc,nc->ng", q, pi)
+            good = usable & (m > 0)
+            bad = (usable & ~good).any(1)
+            msafe = np.where(good, m, 1.0)
+            f = (Yc * np.log(msafe)).sum(1)                          # (log 1 = 0 where an entry is left out)
+            r = np.where(good, Yc / msafe, 0.0)
+            g = np.einsum("ng,ngc->nc", r, q)
+            H = np.matmul(q.transpose(0, 2, 1), q * (r * r / ysafe)[:, :, None]) if hess else None
+            gap = np.maximum(g.max(1) - (pi * g).sum(1), 0.0)
+            bound = np.where(seff > 0, np.where(bad, np.inf, gap), 0.0)
+            return good, bad, f, g, H, bound
+
+        pi = np.full((k, C), 1.0 / C) if st is None else st[lo:lo + k].copy()
+        good, bad, f, g, H, bound = evaluate(pi, max_iter > 0)
+        if max_iter > 0 and bad.any():                               # a start whose zeros exclude the data: the uniform start
+            pi[bad] = 1.0 / C
+            good, bad, f, g, H, bound = evaluate(pi, True)
+        rounds = np.zeros(k, dtype=np.int32)
+        done = np.zeros(k, dtype=bool)
+        while True:
+            done |= ~(seff > 0) | (bound <= tol) | (rounds >= max_iter)
+            if done.all():
+                break
+            with np.errstate(all="ignore"):
+                gam = g - seff[:, None]
+                hcc = np.einsum("ncc->nc", H).copy()
+                hsafe = np.where(hcc > 0, hcc, 1.0)
+                term = np.where(hcc > 0, np.abs(pi - np.maximum(pi + gam / hsafe, 0.0)), pi)
+                eps = np.minimum(1e-3, term.max(1))
+                active = (pi <= eps[:, None]) & (gam < 0)
+                nF = C - active.sum(1)
+                ridge = np.where(nF > 0, 1e-12 * np.where(active, 0.0, hcc).sum(1) / np.maximum(nF, 1), 0.0)
+                A = np.where(active[:, :, None] | active[:, None, :], 0.0, H)
+                ii = np.arange(C)
+                A[:, ii, ii] = np.where(active, 1.0, hcc + ridge[:, None])
+                dF, ok = _mix_chol_solve(A, np.where(active, 0.0, gam))
+                d = np.where(active, np.where(hcc > 0, gam / hsafe, -1.0), dF)
+                ok &= np.isfinite(d).all(1)
+                d = np.where(ok[:, None], d, 0.0)
+                phi0 = f - seff * pi.sum(1)
+                pn = pi * g / ssafe[:, None]                         # the EM step, unless a trial point passes
+                taken = np.zeros(k, dtype=bool)
+                for t in steps:                                      # descending: the largest step that passes
+                    tr = np.maximum(pi + t * d, 0.0)
+                    mt = np.einsum("ngc,nc->ng", q, tr)
+                    ft = np.where(good, Yc * np.log(np.where(good, mt, 1.0)), 0.0).sum(1)
+                    ph = ft - seff * tr.sum(1)
+                    passes = ok & ~taken & np.isfinite(ph) & (ph >= phi0 + 1e-4 * (gam * (tr - pi)).sum(1))
+                    pn = np.where(passes[:, None], tr, pn)
+                    taken |= passes
+                tot = pn.sum(1)
+                pn = np.where(((tot > 0) & np.isfinite(tot))[:, None], pn / np.where(tot > 0, tot, 1.0)[:, None], pn)
+            pi = np.where(done[:, None], pi, pn)
+            rounds += ~done
+            good, bad, f, g, H, bound = evaluate(pi, True)
+        out["weights"][lo:lo + k] = pi
+        if want_grad:
+            out["grad"][lo:lo + k] = np.where(seff[:, None] > 0, g / ssafe[:, None], 0.0)
+        out["mix_ll"][lo:lo + k] = np.where(ninf | bad, -np.inf, f + base - np.where(s > 0, s * lz, 0.0))
+        out["bound"][lo:lo + k] = bound
+        out["rounds"][lo:lo + k] = rounds
+    out["converged"] = out["bound"] <= tol
+    return out
+
+
+def _extra_profiles(extra_profiles, G, what):
+    """(profiles [G, M] float64, names) of ``extra_profiles``: a [G, M] matrix (or a length-G vector) of non-negative expected expression, or a dict of name to
+    vector; None gives M = 0."""
+    if extra_profiles is None:
+        return np.zeros((G, 0)), []
+    if isinstance(extra_profiles, dict):
+        names = [str(k) for k in extra_profiles]
+        X = np.stack([np.asarray(v, dtype=np.float64).reshape(-1) for v in extra_profiles.values()], axis=1) if names else np.zeros((G, 0))
+    else:
+        X = np.asarray(extra_profiles, dtype=np.float64)
+        X = X.reshape(-1, 1) if X.ndim == 1 else X
+        names = [f"extra_{i + 1}" for i in range(X.shape[1] if X.ndim == 2 else 0)]
+    if X.ndim != 2 or X.shape[0] != G:
+        raise ValueError(f"{what}: extra_profiles is {X.shape}; expected ({G}, M): one column of expected expression per profile")
+    wrong = np.argwhere(~np.isfinite(X) | (X < 0))
+    if wrong.size:
+        raise ValueError(f"{what}: extra_profiles has a negative or non-finite entry (gene {wrong[0][0]}, profile {names[wrong[0][1]]})")
+    return X, names
+
+
+def clone_mixture(fit, Y, L, *, start=None, max_iter=50, tol=1e-3, extra_profiles=None, x=None, psi=None, saturate=True, saturation_threshold=6, const=True,
+                  cells=None, engine=None, engine_opts=None):
+    """The maximum-likelihood MIXTURE of the clones of a fitted model for every row of ``Y``: a spatial spot or a bulk sample (clone prevalences), a droplet
+    with ambient RNA or a tumour clone with a normal cell (``extra_profiles``), a doublet at any weights, a triplet.  The sum of multinomial rows of several
+    clones is multinomial in ``sum_c pi_c p_n.c``; the weights ``pi`` on the simplex are found per row by projected Newton on the device
+    (``HipEngine.clone_mixture``; include/clonealign_hip.h has the formulas, the round and the rules) and come with a CERTIFIED bound: no other weights
+    gain more than ``bound`` nats (concavity), and a row stops when ``bound <= tol`` or after ``max_iter`` rounds.  ``Y``, ``L``, ``x``, ``psi``,
+    ``saturate``, ``const``, ``engine`` and ``engine_opts`` as for ``clone_loglik``; ``cells`` = ``(lo, hi)`` restricts the call to that range.
+
+    ``extra_profiles``: a [genes, M] matrix of non-negative expected expression, or a dict of name to vector -- an ambient profile, a diploid ``2 mu`` --
+    that become further columns of the table (scale does not matter: every column is normalised by its own ``Z``; the cell's exponent term applies to them
+    too); ``C + M <= 32``.  A throwaway engine is built with ``C + M`` columns; an engine passed in must hold that many.  ``start`` [rows, C + M] on the
+    simplex (None: uniform); a start whose zeros exclude the data is replaced by the uniform one; ``max_iter=0`` evaluates at the start.
+
+    Returns a dict: ``weights`` [n, C + M], ``mix_ll`` [n], ``ll`` [n, C + M] (``clone_loglik``'s, one column per component), ``grad`` [n, C + M]
+    (``g_c / s_eff``: 1 on the support of an optimum), ``bound`` [n], ``rounds`` [n], ``converged`` [n] (``bound <= tol``), ``component_names`` and
+    ``log_lr_single`` [n] = ``mix_ll - max_c ll``: by how many nats the mixture beats the best single component.  An engine without ``clone_mixture`` gets
+    the float64 host form."""
+    return _mixture_api(fit, Y, L, start, max_iter, tol, extra_profiles, x, psi, saturate, saturation_threshold, const, cells, engine, engine_opts, "clone_mixture")
+
+
+def _mixture_api(fit, Y, L, start, max_iter, tol, extra_profiles, x, psi, saturate, saturation_threshold, const, cells, engine, engine_opts, what):
+    Y, Lm, cn, N, G = _cells_and_cnv(Y, L)
+    t = _fit_tables(fit, Lm, N, x, psi, saturate, saturation_threshold)
+    C = t.L.shape[1]
+    X, xnames = _extra_profiles(extra_profiles, G, what)
+    M = X.shape[1]
+    if C + M > MIX_CMAX:
+        raise ValueError(f"{what}: C + M = {C} + {M} components: a mixture takes at most {MIX_CMAX}")
+    max_iter, tol = _mixture_settings(C + M, max_iter, tol, what)
+    names = list(_clone_names(fit, cn, C)) + xnames
+    E = np.ascontiguousarray(np.concatenate([t.E, X], axis=1))
+    Lall = np.ascontiguousarray(np.concatenate([t.L, np.ones((G, M))], axis=1))   # (the engine's own L is not read by a scoring call: it sets the column count)
+    lo, hi = (0, N) if cells is None else (int(cells[0]), int(cells[1]))
+    if lo < 0 or hi < lo or hi > N:
+        raise ValueError(f"{what}: the cell range [{lo}, {lo} + {hi - lo}) is outside [0, {N}]")
+    st = _mixture_start(start, hi - lo, C + M, lo, what)
+    if engine is not None and hasattr(engine, "clone_mixture") and getattr(engine, "C", C + M) != C + M:
+        raise ValueError(f"{what}: the engine holds {engine.C} columns but the call has {C} clones + {M} extra profiles = {C + M} components; "
+                         "build the engine with that many columns")
+    with _engine_lease(engine, "clone_mixture", Y, Lall, engine_opts) as eng:
+        if hasattr(eng, "clone_mixture"):
+            out = eng.clone_mixture(E, t.U, t.V, start=st, max_iter=max_iter, tol=tol, const=const, cells=(lo, hi))
+        else:
+            out = _clone_mixture_host(Y, E, t.U, t.V, start=st, max_iter=max_iter, tol=tol, const=const, cells=(lo, hi))
+    with np.errstate(invalid="ignore"):
+        best = out["ll"].max(1) if C + M else np.zeros(hi - lo)
+        out["log_lr_single"] = np.where(np.isneginf(out["mix_ll"]) & np.isneginf(best), np.nan, out["mix_ll"] - best)
+    out["component_names"] = names
+    out["n_clones"] = C
+    return out
+
+
+def mixture_loglik(fit, Y, L, weights, *, extra_profiles=None, x=None, psi=None, saturate=True, saturation_threshold=6, const=True, cells=None, engine=None,
+                   engine_opts=None):
+    """``clone_mixture`` in EVALUATION mode: the mixture log-likelihood of every row of ``Y`` at the given ``weights`` [rows, C + M] (or one row for all), zeros
+    included, with the gradient and the bound at those weights and no round taken.  A one-hot row reproduces ``clone_loglik``'s value, ``(w, 1 - w)`` on a
+    pair ``clone_pair_loglik``'s.  Same return value as ``clone_mixture`` (``rounds`` is 0)."""
+    return _mixture_api(fit, Y, L, weights, 0, 0.0, extra_profiles, x, psi, saturate, saturation_threshold, const, cells, engine, engine_opts, "mixture_loglik")
+
+
+def deconvolve_clones(fit, Y, L, *, extra_profiles=None, min_weight=0.05, start=None, max_iter=50, tol=1e-3, x=None, psi=None, saturate=True,
+                      saturation_threshold=6, const=True, cells=None, engine=None, engine_opts=None):
+    """Clone composition of every row of ``Y`` under a fitted model, from ``clone_mixture`` (same keywords): what a spot, a bulk sample or a contaminated
+    droplet is made of.  Returns everything ``clone_mixture`` returns, except that ``weights`` [n, C] holds the clones' columns and ``weights_extra``
+    [n, M] those of ``extra_profiles`` (``weights_all`` [n, C + M] is the solver's row), plus: ``dominant`` [n] (the name of the largest component),
+    ``n_components`` [n] (weights at or above ``min_weight``), ``is_mixed`` [n] (more than one such component) and ``prevalence`` [C + M]: the
+    read-weighted mean weight per component over the rows -- the bulk deconvolution when ``Y`` has one row (rows without reads, or that no component can
+    explain, carry no weight)."""
+    if not (np.isfinite(min_weight) and 0.0 <= min_weight <= 1.0):
+        raise ValueError(f"deconvolve_clones: min_weight = {min_weight} is outside [0, 1]")
+    out = _mixture_api(fit, Y, L, start, max_iter, tol, extra_profiles, x, psi, saturate, saturation_threshold, const, cells, engine, engine_opts, "deconvolve_clones")
+    w = out["weights"]
+    C = out["n_clones"]
+    Yc = _counts_array(Y.values if hasattr(Y, "columns") and hasattr(Y, "values") else Y)
+    lo, hi = (0, Yc.shape[0]) if cells is None else (int(cells[0]), int(cells[1]))
+    reads = np.asarray(Yc[lo:hi].sum(1), dtype=np.float64).reshape(-1)
+    reads = np.where(np.isfinite(out["mix_ll"]), reads, 0.0)
+    names = np.asarray(out["component_names"], dtype=object)
+    n_comp = (w >= min_weight).sum(1)
+    out.update(weights_all=w, weights=w[:, :C], weights_extra=w[:, C:], dominant=names[np.argmax(w, axis=1)] if w.shape[1] else np.empty(w.shape[0], dtype=object),
+               n_components=n_comp, is_mixed=n_comp > 1, min_weight=float(min_weight),
+               prevalence=(reads[:, None] * w).sum(0) / reads.sum() if reads.sum() > 0 else np.full(w.shape[1], np.nan))
+    return out
+
+
 DM_DEFAULT_GRID = tuple(10.0 ** np.arange(1.0, 4.75, 0.5))         # 8 concentrations, 10 .. 10^4.5
 
 

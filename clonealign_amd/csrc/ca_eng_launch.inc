@@ -364,6 +364,24 @@ int launch_pair_ll(ca_engine* h, const ca_pll_ops& o) {
   if (h->ystore == CA_YSTORE_U16) return pair_ll_t<uint16_t>(h, o);
   return pair_ll_t<float>(h, o);
 }
+// ---- k_mix_list<YT> / k_mix_rounds: the compacted list of a batch's rows and the projected-Newton rounds over it (ca_clone_mixture, every D; never the 4-bit loop image) ----
+// one batch of cells [n_lo, n_lo + n_cnt): E compact [G][C], the cells' log Z and base sums (k_pair_cell), the list slabs [n_cnt][Gp] (gene, y, r, r^2 / y) and
+// counts, the batch's rows of the start (null: uniform), the batch's rows of the outputs
+struct ca_mix_ops { const double *Ec, *lzc, *base, *start; int* lg; double *ly, *lr, *lq; int* ln; double *w, *g, *mll, *bnd; int* rnd; int64_t n_lo, n_cnt; int max_iter; double tol; };
+template <typename YT>
+int mix_list_t(ca_engine* h, const ca_mix_ops& o) {
+  LAUNCH(h, CA_KERNEL_YPASS, hipLaunchKernelGGL((k_mix_list<YT>), dim3((unsigned)cdiv(o.n_cnt, CA_TB / 64)), dim3(CA_TB), 0, h->stream, (const YT*)h->Y,
+                                                h->n_ovf > 0 ? h->ovf_rowptr : nullptr, h->ovf_col, h->ovf_val, o.lg, o.ly, o.ln, o.n_lo, o.n_cnt, h->G, h->Gp, h->nseg));
+  return CA_OK;
+}
+int launch_mix(ca_engine* h, const ca_mix_ops& o) {
+  if (h->ystore == CA_YSTORE_U8) CACK(mix_list_t<uint8_t>(h, o));
+  else if (h->ystore == CA_YSTORE_U16) CACK(mix_list_t<uint16_t>(h, o));
+  else CACK(mix_list_t<float>(h, o));
+  LAUNCH(h, CA_KERNEL_OTHER, hipLaunchKernelGGL(k_mix_rounds, dim3((unsigned)cdiv(o.n_cnt, CA_TB / 64)), dim3(CA_TB), 0, h->stream, o.Ec, o.lzc, o.base, h->s64, o.lg, o.ly, o.lr,
+                                                o.lq, o.ln, o.start, o.w, o.g, o.mll, o.bnd, o.rnd, o.n_lo, o.n_cnt, h->Gp, h->C, o.max_iter, o.tol));
+  return CA_OK;
+}
 // ---- k_dm_ll<YT>: the Dirichlet-multinomial sweep over the resident matrix in its storage (ca_clone_loglik_dm, every D; never the 4-bit loop image) ----
 // one batch of cells [n_lo, n_lo + n_cnt): E compact [G][C], the cells' log Z, max of eta and heads (k_dm_cell), the concentrations, the padded factors (null: D = 0),
 // the batch's rows of the output [n_cnt][CK]; ysmall: the largest integer count on the product route (0: none)

@@ -1,4 +1,4 @@
-// ca_eng_score.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, the scoring family -- the calls that score the resident count matrix under a fitted model: the per-cell, per-clone log-likelihood (ca_clone_loglik), under a mixture of two clones (ca_clone_pair_loglik), Dirichlet-multinomial (ca_clone_loglik_dm), by block of genes (ca_clone_loglik_by_block), the per-cell MAP psi of cells outside a fit (ca_project_cells), the clone evidence with psi integrated out (ca_clone_evidence), with the genes reweighted for every replicate of a bootstrap (ca_clone_loglik_reweighted).
+// ca_eng_score.inc -- part of clonealign_hip.hip (textually included there, in this order; one translation unit): C ABI, the scoring family -- the calls that score the resident count matrix under a fitted model: the per-cell, per-clone log-likelihood (ca_clone_loglik), under a mixture of two clones (ca_clone_pair_loglik), the maximum-likelihood mixture of all clones (ca_clone_mixture), Dirichlet-multinomial (ca_clone_loglik_dm), by block of genes (ca_clone_loglik_by_block), the per-cell MAP psi of cells outside a fit (ca_project_cells), the clone evidence with psi integrated out (ca_clone_evidence), with the genes reweighted for every replicate of a bootstrap (ca_clone_loglik_reweighted).
 // All of them read the matrix, the row sums and the overflow list only: no wait for the loop's side stream, no variable, Adam slot or draw index changes.  Their
 // inputs and outputs cover the local cells, so a sharded handle needs no sums from its peers; it still takes part in ONE small collective, the verdict on the
 // input (a non-finite U is local), so that every rank returns the same code instead of one of them leaving the others waiting.
@@ -146,10 +146,13 @@ int sweep_batch(ca_engine* h, const ca_ll_operands& op, const ca_ll_dev& dev, do
 // ONE body serves ca_clone_loglik and ca_clone_pair_loglik: the pair call runs the same launches over its cell range -- its ll is ca_clone_loglik's bit for bit,
 // and the pair-independent pieces (sum y eta, the lgamma sum, log Z) are those launches' -- and then, per batch, k_pair_cell and k_pair_ll (D > 0) or the
 // table sweep of k_clone_ll with k_pair_tab_finish (D = 0).  ca_clone_loglik_dm is a third caller: after the same launches, per batch, k_dm_cell and k_dm_ll (every D).
+// ca_clone_mixture is a fourth: after the same launches, per batch, k_pair_cell (log Z and base, every D), k_mix_list and k_mix_rounds (ca_k_mixture.hip.h).
 struct ca_pair_req { const double* weights; int W; double* pair_ll; };   // the pair part of a call: W weights in (0, 1), the output cell_cnt x (M W)
 struct ca_dm_req { const double* conc; int K; double* dm_ll; };          // the Dirichlet-multinomial part of a call: K concentrations > 0, the output cell_cnt x (C K)
+// the mixture part of a call (ca_clone_mixture): the start (cell_cnt x C on the simplex, or null: uniform), the rounds' settings, the outputs (grad may be null)
+struct ca_mix_req { const double* start; int max_iter; double tol; double *weights, *grad, *mix_ll, *bound; int32_t* rounds; };
 int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, int64_t c_lo, int64_t c_cnt, double* ll,
-                  const ca_pair_req* pq, const ca_dm_req* dq = nullptr) {
+                  const ca_pair_req* pq, const ca_dm_req* dq = nullptr, const ca_mix_req* mq = nullptr) {
   const std::string pre = std::string(who) + ": ";
   if (D < 0 || D > CA_LL_DMAX) { h->err = pre + "D = " + std::to_string(D) + " is outside [0, " + std::to_string(CA_LL_DMAX) + "]"; return CA_ERR_INVALID; }   // (the same on every rank: no collective)
   if (D > 0 && (!U || !V)) { h->err = pre + "D = " + std::to_string(D) + " needs both U (cells x D) and V (genes x D)"; return CA_ERR_INVALID; }
@@ -177,12 +180,17 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
       phi_max = std::max(phi_max, v);
     }
   }
+  if (mq) {   // (the same on every rank as well; the start's rows are the rank's own and join the verdict below)
+    if (C > CA_MIX_CMAX) { h->err = pre + "C = " + std::to_string(C) + " clones: a mixture takes at most " + std::to_string(CA_MIX_CMAX); return CA_ERR_INVALID; }
+    if (mq->max_iter < 0) { h->err = pre + "max_iter = " + std::to_string(mq->max_iter) + " is negative"; return CA_ERR_INVALID; }
+    if (!std::isfinite(mq->tol) || mq->tol < 0.0) { h->err = pre + "tol_nats = " + std::to_string(mq->tol) + " is negative or not finite"; return CA_ERR_INVALID; }
+  }
   HIPCK(h, hipSetDevice(h->device));
   const int MP = C * (C - 1) / 2, MW = MP * W;
   // the contraction's operands (D > 0): E in groups of NZ clone columns; the pair and Dirichlet-multinomial parts read E compact
   const int NZ = C <= 8 ? 8 : C <= 16 ? 16 : 32, ngz = cdiv(C, NZ), nzt = ngz * NZ, nzc = cdiv(G, CA_LL_ZCHUNK);
   ca_ll_operands op;
-  ll_operands(h, ca_ll_req{E, V, D, {{U, D, "U", "factor"}, {nullptr, 0, "", ""}}, c_lo, c_cnt, with_const != 0, false, NZ, pq != nullptr || dq != nullptr}, op);
+  ll_operands(h, ca_ll_req{E, V, D, {{U, D, "U", "factor"}, {nullptr, 0, "", ""}}, c_lo, c_cnt, with_const != 0, false, NZ, pq != nullptr || dq != nullptr || mq != nullptr}, op);
   std::string& bad = op.bad;
   const int nct = op.nct;
   // the pair part's operands; for D = 0 the table log(A P_ga + B P_gb) of M W columns in groups of NP, its both-zero masks and the slots' shifts
@@ -212,13 +220,29 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
           }
     }
   }
+  std::vector<double> st;   // (the start of a mixture call, row-major)
+  if (mq && mq->start && bad.empty()) {
+    st.resize((size_t)(c_cnt * C));
+    for (int64_t i = 0; i < c_cnt && bad.empty(); ++i) {
+      double sum = 0.0;
+      for (int c = 0; c < C; ++c) {
+        const double v = mq->start[hidx(h->layout, i, c, c_cnt, C)];
+        if (!std::isfinite(v) || v < 0.0) { bad = "start has a negative or non-finite entry (cell " + std::to_string(c_lo + i) + ", clone " + std::to_string(c) + ")"; break; }
+        st[(size_t)(i * C + c)] = v;
+        sum += v;
+      }
+      if (bad.empty() && !(std::fabs(sum - 1.0) <= 1e-9)) bad = "the start of cell " + std::to_string(c_lo + i) + " sums to " + std::to_string(sum) + ": off 1 by more than 1e-9";
+    }
+  }
   CACK(agree_on_verdict(h, bad));
   if (!bad.empty()) { h->err = pre + bad; return CA_ERR_INVALID; }
   if (c_cnt == 0) return CA_OK;
-  // cells in batches, so that the partial slabs stay below a quarter of a gigabyte
-  const int64_t per_cell = ((int64_t)nseg * (nct + 1) + (D > 0 ? (int64_t)nzc * (nzt + 1) : 0) + (pq ? (int64_t)C + 1 + MW + (D == 0 ? (int64_t)nseg * nctp : 0) : 0) + (dq ? (int64_t)C + 1 + K + CK : 0)) * (int64_t)sizeof(double);
+  // cells in batches, so that the partial slabs stay below a quarter of a gigabyte; a mixture call adds its list slab, up to Gp entries of (gene, y, r, r^2 / y) a cell
+  const int64_t mix_cell = mq ? ((int64_t)3 * C + 3) * (int64_t)sizeof(double) + (int64_t)Gp * (3 * (int64_t)sizeof(double) + (int64_t)sizeof(int)) + 2 * (int64_t)sizeof(int) : 0;
+  const int64_t per_cell = mix_cell + ((int64_t)nseg * (nct + 1) + (D > 0 ? (int64_t)nzc * (nzt + 1) : 0) + (pq ? (int64_t)C + 1 + MW + (D == 0 ? (int64_t)nseg * nctp : 0) : 0) + (dq ? (int64_t)C + 1 + K + CK : 0)) * (int64_t)sizeof(double);
   const int64_t NB = cells_per_batch(c_cnt, per_cell, CA_LL_BUDGET);
   ca_rows_out o_ll(h, ll, c_cnt, C), o_pair(h, pq ? pq->pair_ll : nullptr, c_cnt, MW), o_dm(h, dq ? dq->dm_ll : nullptr, c_cnt, CK);
+  ca_rows_out o_mw(h, mq ? mq->weights : nullptr, c_cnt, C), o_mg(h, mq ? mq->grad : nullptr, c_cnt, C);
   ca_call_mem mem(h);
   const ca_ll_dev dev = upload_operands(mem, op);
   double* part = mem.alloc<double>((int64_t)nseg * NB * nct);
@@ -226,7 +250,7 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
   double* zpart = D > 0 ? mem.alloc<double>((int64_t)nzc * NB * nzt) : nullptr;
   double* mpart = D > 0 ? mem.alloc<double>((int64_t)nzc * NB) : nullptr;
   double* ll_d = mem.alloc<double>(h->N * C);
-  double* lzc_d = pq || dq ? mem.alloc<double>(NB * C) : nullptr;
+  double* lzc_d = pq || dq || mq ? mem.alloc<double>(NB * C) : nullptr;
   double *wts_d = nullptr, *slz_d = nullptr, *base_d = nullptr, *ppart = nullptr, *pll_d = nullptr;
   ca_ll_dev ptd{};
   if (pq) {
@@ -241,6 +265,15 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
     mrow_d = mem.alloc<double>(NB);
     head_d = mem.alloc<double>(NB * K);
     dll_d = mem.alloc<double>(NB * CK);
+  }
+  ca_mix_ops mx{};
+  const double* st_d = nullptr;
+  if (mq) {
+    if (!st.empty()) st_d = mem.upload(st);
+    base_d = mem.alloc<double>(NB);
+    mx.lg = mem.alloc<int>(NB * Gp); mx.ly = mem.alloc<double>(NB * Gp); mx.lr = mem.alloc<double>(NB * Gp); mx.lq = mem.alloc<double>(NB * Gp); mx.ln = mem.alloc<int>(NB);
+    mx.w = mem.alloc<double>(NB * C); mx.g = mem.alloc<double>(NB * C); mx.mll = mem.alloc<double>(NB); mx.bnd = mem.alloc<double>(NB); mx.rnd = mem.alloc<int>(NB);
+    mx.Ec = dev.Ec; mx.lzc = lzc_d; mx.base = base_d; mx.max_iter = mq->max_iter; mx.tol = mq->tol;
   }
   if (mem.rc != CA_OK) return mem.rc;
   for (int64_t n_lo = c_lo; n_lo < c_lo + c_cnt; n_lo += NB) {
@@ -271,6 +304,19 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
       }
       HIPCK(h, hipMemcpyAsync(o_pair.p + (size_t)(n_lo - c_lo) * MW, pll_d, (size_t)n_cnt * MW * sizeof(double), hipMemcpyDeviceToHost, h->stream));   // (in stream order: before the next batch overwrites it)
     }
+    if (mq) {   // log Z and base are the pair part's (k_pair_cell, every D: logz0 at D = 0), then the list and the rounds
+      hipLaunchKernelGGL(k_pair_cell, dim3((unsigned)cdiv(n_cnt * (C + 1), CA_TB)), dim3(CA_TB), 0, h->stream, part, lgpart, zpart, mpart, dev.logz0, dev.Ut, h->s64, lzc_d, base_d, n_lo, n_cnt,
+                         C, (int)D, (int)nseg, nct, nzc, nzt);
+      HIPCK(h, hipGetLastError());
+      mx.start = st_d ? st_d + (size_t)(n_lo - c_lo) * C : nullptr; mx.n_lo = n_lo; mx.n_cnt = n_cnt;
+      CACK(launch_mix(h, mx));
+      const size_t row = (size_t)(n_lo - c_lo);   // (the copies run in stream order: before the next batch overwrites the buffers)
+      HIPCK(h, hipMemcpyAsync(o_mw.p + row * C, mx.w, (size_t)n_cnt * C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      if (mq->grad) HIPCK(h, hipMemcpyAsync(o_mg.p + row * C, mx.g, (size_t)n_cnt * C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCK(h, hipMemcpyAsync(mq->mix_ll + row, mx.mll, (size_t)n_cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCK(h, hipMemcpyAsync(mq->bound + row, mx.bnd, (size_t)n_cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCK(h, hipMemcpyAsync(mq->rounds + row, mx.rnd, (size_t)n_cnt * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    }
     if (dq) {
       hipLaunchKernelGGL(k_dm_cell, dim3((unsigned)cdiv(n_cnt * (C + K), CA_TB)), dim3(CA_TB), 0, h->stream, lgpart, zpart, mpart, dev.logz0, h->s64, conc_d, lzc_d, mrow_d, head_d, n_lo,
                          n_cnt, C, K, (int)D, (int)nseg, nzc, nzt);
@@ -284,7 +330,7 @@ int clone_ll_impl(ca_engine* h, const char* who, const double* E, const double* 
   }
   if (ll) HIPCK(h, hipMemcpyAsync(o_ll.p, ll_d + (size_t)c_lo * C, (size_t)c_cnt * C * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCK(h, hipStreamSynchronize(h->stream));
-  o_ll.finish(); o_pair.finish(); o_dm.finish();
+  o_ll.finish(); o_pair.finish(); o_dm.finish(); o_mw.finish(); o_mg.finish();
   return CA_OK;
 }
 }  // namespace
@@ -305,6 +351,21 @@ int ca_clone_pair_loglik(ca_handle h, const double* E, const double* U, const do
   CA_NOT_IN_RUN(h);
   ca_pair_req pq{weights, (int)n_weights, pair_ll};
   return clone_ll_impl(h, "ca_clone_pair_loglik", E, U, V, D, with_const, cell_lo, cell_cnt, ll, &pq);
+}
+
+// The maximum-likelihood mixture of all clones for each of the resident cells [cell_lo, cell_lo + cell_cnt): simplex weights by projected Newton, with a certified
+// bound in nats (include/clonealign_hip.h has the formulas, the round and the rules; ca_k_mixture.hip.h the kernels).  ca_clone_loglik's launches, k_pair_cell's
+// log Z and base, then the list and the rounds.
+int ca_clone_mixture(ca_handle h, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const double* start, int32_t max_iter, double tol_nats,
+                     int64_t cell_lo, int64_t cell_cnt, double* ll, double* weights, double* grad, double* mix_ll, double* bound_nats, int32_t* rounds) {
+  if (!h) return CA_ERR_INVALID;
+  {
+    const char* null_arg = !E ? "E" : !weights ? "weights" : !mix_ll ? "mix_ll" : !bound_nats ? "bound_nats" : !rounds ? "rounds" : nullptr;
+    if (null_arg) { h->err = std::string("ca_clone_mixture: ") + null_arg + " is NULL"; return CA_ERR_INVALID; }
+  }
+  CA_NOT_IN_RUN(h);
+  ca_mix_req mq{start, (int)max_iter, tol_nats, weights, grad, mix_ll, bound_nats, rounds};
+  return clone_ll_impl(h, "ca_clone_mixture", E, U, V, D, with_const, cell_lo, cell_cnt, ll, nullptr, nullptr, &mq);
 }
 
 // The Dirichlet-multinomial log-likelihood of the resident cells [cell_lo, cell_lo + cell_cnt) under every clone at every concentration of the grid (overdispersed

@@ -777,6 +777,37 @@ int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double*
   return CA_OK;
 }
 
+int ca_group_clone_mixture(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const double* start, int32_t max_iter,
+                           double tol_nats, int64_t cell_lo, int64_t cell_cnt, double* ll, double* weights, double* grad, double* mix_ll, double* bound_nats, int32_t* rounds) {
+  GROUP_ALIVE(g);
+  {
+    const char* null_arg = !E ? "E" : !weights ? "weights" : !mix_ll ? "mix_ll" : !bound_nats ? "bound_nats" : !rounds ? "rounds" : nullptr;
+    if (null_arg) { g->err = std::string("ca_clone_mixture: ") + null_arg + " is NULL"; return CA_ERR_INVALID; }
+  }
+  RangePlan p;
+  if (!duv_ok(g, "ca_clone_mixture", D, U, V) || !plan_range(g, "ca_clone_mixture", cell_lo, cell_cnt, U, D, p)) return CA_ERR_INVALID;
+  const int64_t C = g->C;
+  const size_t W = (size_t)g->W;
+  std::vector<std::vector<double>> st(W);   // each rank's rows of the start: those of its part of the range
+  if (start) for (size_t r = 0; r < W; ++r) slice_rows(start, g->layout, g->N, C, p.lo[r], p.hi[r], st[r]);
+  auto o_ll = p.outputs(ll ? C : 0), o_w = p.outputs(C), o_g = p.outputs(grad ? C : 0), o_m = p.outputs(1), o_b = p.outputs(1);
+  std::vector<std::vector<int32_t>> o_r(W);
+  for (size_t r = 0; r < W; ++r) o_r[r].resize((size_t)p.rows(r) + 1);
+  const int s = settle_verdict(g, dispatch(g, [&](int ri) {
+    const size_t r = (size_t)ri;
+    return ca_clone_mixture(g->h[r], E, p.u(r), V, D, with_const, start && p.rows(r) > 0 ? st[r].data() : nullptr, max_iter, tol_nats, p.local_lo(r), p.rows(r),
+                            ll ? o_ll[r].data() : nullptr, o_w[r].data(), grad ? o_g[r].data() : nullptr, o_m[r].data(), o_b[r].data(), o_r[r].data());
+  }), "ca_clone_mixture");
+  if (s != CA_OK) return s;
+  if (ll) p.scatter(o_ll, C, ll);
+  p.scatter(o_w, C, weights);
+  if (grad) p.scatter(o_g, C, grad);
+  p.scatter(o_m, 1, mix_ll);
+  p.scatter(o_b, 1, bound_nats);
+  for (size_t r = 0; r < W; ++r) std::copy(o_r[r].begin(), o_r[r].begin() + p.rows(r), rounds + (p.lo[r] - cell_lo));
+  return CA_OK;
+}
+
 int ca_group_clone_loglik_dm(ca_group_handle g, const double* E, const double* U, const double* V, int32_t D, int32_t with_const, const double* conc, int32_t n_conc,
                              int64_t cell_lo, int64_t cell_cnt, double* ll, double* dm_ll) {
   GROUP_ALIVE(g);

@@ -950,6 +950,7 @@ __global__ void __launch_bounds__(CA_TB, (DEPTH == 1 && !C16 && !S2F) ? CA_YS_RI
 #include "ca_k_loglik.hip.h"   // per-cell, per-clone log-likelihood of the resident matrix under a fitted model (ca_clone_loglik): one float64 sweep, a lane per cell; and the pieces every scoring kernel below shares (eta, the contraction's chunk, the chunk merge, the slab sums, the walk)
 #include "ca_k_blockll.hip.h"   // the log-likelihood's sufficient statistics by block of genes (ca_clone_loglik_by_block): the shared walk with a run list, sums stored at run ends
 #include "ca_k_pairll.hip.h"   // log-likelihood under a mixture of two clones (ca_clone_pair_loglik): a wave per cell over its compacted non-zero counts, a lane per (pair, weight)
+#include "ca_k_mixture.hip.h"   // maximum-likelihood mixture of all clones per cell (ca_clone_mixture): the compacted list in a global slab, projected-Newton rounds in one launch, a wave per cell
 #include "ca_k_dmll.hip.h"   // Dirichlet-multinomial log-likelihood per clone on a grid of concentrations (ca_clone_loglik_dm): k_pair_ll's walk, a lane per (clone, concentration), exp(eta) at compaction time
 #include "ca_k_bootll.hip.h"   // gene-reweighted log-likelihood for every replicate of a bootstrap (ca_clone_loglik_reweighted): two float64 products on v_mfma_f64_16x16x4_f64, cells x (replicate, clone) over the genes; votes and shares reduced on the device
 #include "ca_k_project.hip.h" // per-cell MAP psi and clone posterior for cells outside the fit (ca_project_cells): moments over the genes, a lane per cell; never reads Y

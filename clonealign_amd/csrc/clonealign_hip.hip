@@ -662,7 +662,7 @@ int ca_final_elbo(ca_handle h, int32_t n_rep, const float* eps_stream, int64_t n
 }
 
 #include "ca_eng_init.inc"   // C ABI, once per fit on the resident matrix: PCA initialisation of psi (transformed count-matrix pass, Gram-Schmidt and Jacobi on the host, blocked subspace iteration), per-clone gene sums, the squared error of a fit, log-expression sums per gene and cell group
-#include "ca_eng_score.inc"   // C ABI, the scoring family on the resident matrix under a fitted model: log-likelihood per cell and clone, pair mixture, Dirichlet-multinomial, by block of genes, per-cell MAP psi, clone evidence, gene-reweighted for a bootstrap's replicates; their shared operands, verdict, batches and output layout
+#include "ca_eng_score.inc"   // C ABI, the scoring family on the resident matrix under a fitted model: log-likelihood per cell and clone, pair mixture, mixture of all clones, Dirichlet-multinomial, by block of genes, per-cell MAP psi, clone evidence, gene-reweighted for a bootstrap's replicates; their shared operands, verdict, batches and output layout
 static int get_generic(ca_handle h, const char* name, double* out, bool grad) {
   if (!h || !name || !out) return CA_ERR_INVALID;
   HIPCK(h, hipSetDevice(h->device));

@@ -53,6 +53,9 @@ EXPORTS = (
     "ca_project_cells", "ca_group_project_cells",
     # log-likelihood under every mixture of two clones on a weight grid (clone_pair_loglik / detect_doublets), additions to ABI 6
     "ca_clone_pair_loglik", "ca_group_clone_pair_loglik",
+    # maximum-likelihood mixture of all clones per cell: simplex weights by projected Newton with a certified bound (clone_mixture / mixture_loglik /
+    # deconvolve_clones), additions to ABI 6
+    "ca_clone_mixture", "ca_group_clone_mixture",
     # Dirichlet-multinomial log-likelihood per clone on a grid of concentrations (clone_loglik_dm / estimate_concentration / assign_cells_dm), additions to ABI 6
     "ca_clone_loglik_dm", "ca_group_clone_loglik_dm",
     # the log-likelihood's sufficient statistics by block of genes (clone_loglik_by_block / assignment_support), additions to ABI 6
@@ -207,6 +210,8 @@ def load_library(path=None):
     lib.ca_clone_pair_loglik.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                          C.c_void_p, C.c_void_p]
     lib.ca_clone_loglik_dm.argtypes = lib.ca_clone_pair_loglik.argtypes
+    lib.ca_clone_mixture.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_int64, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_clone_loglik_by_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ca_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
@@ -262,6 +267,7 @@ def load_library(path=None):
     lib.ca_group_project_cells.argtypes = lib.ca_project_cells.argtypes
     lib.ca_group_clone_evidence.argtypes = lib.ca_clone_evidence.argtypes
     lib.ca_group_clone_pair_loglik.argtypes = lib.ca_clone_pair_loglik.argtypes
+    lib.ca_group_clone_mixture.argtypes = lib.ca_clone_mixture.argtypes
     lib.ca_group_clone_loglik_by_block.argtypes = lib.ca_clone_loglik_by_block.argtypes
     lib.ca_group_clone_loglik_dm.argtypes = lib.ca_clone_loglik_dm.argtypes
     lib.ca_clone_loglik_reweighted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
@@ -821,6 +827,38 @@ class HipEngine:
         self._ck(self._fn("clone_pair_loglik")(self.h, _ptr(Em), _ptr(Um), _ptr(Vm), D, int(bool(const)), _ptr(w), Wn, lo, hi - lo, _ptr(ll), _ptr(pll)))
         return {"ll": ll, "pair_ll": np.ascontiguousarray(pll).reshape(n, M, Wn), "pairs": pairs}
 
+    def _mixture_start(self, start, lo, hi):
+        """The start of a mixture call as the library takes it: the range's rows [hi - lo, C] in the engine's order."""
+        return self._in_order(start)
+
+    def clone_mixture(self, E, U=None, V=None, start=None, max_iter=50, tol=1e-3, const=True, cells=None, want_ll=True, want_grad=True):
+        """The maximum-likelihood MIXTURE of all clones for each resident cell -- a spot, a bulk sample, a contaminated droplet, an off-grid doublet: counts
+        multinomial in ``sum_c pi_c p_n.c`` -- on the device in float64 (ca_clone_mixture; include/clonealign_hip.h has the formulas, the round and the
+        rules): simplex weights by projected Newton, stopped when the certified bound ``max_c g_c - sum_c pi_c g_c`` on what any other weights could gain
+        is at most ``tol`` nats, or after ``max_iter`` rounds.  ``E``, ``U``, ``V`` and ``const`` as for ``clone_loglik`` (``U`` covers all resident
+        cells; columns of ``E`` may be profiles that are no clone); ``start`` [n, C] rows on the simplex for the cells of the range, or None for uniform
+        weights; ``max_iter=0`` evaluates at the start; ``cells`` = ``(lo, hi)`` restricts the call to that range (None: all) -- a cell's values do not
+        depend on the range.  Returns ``{"ll": [n, C] (clone_loglik's rows, bit for bit; None unless want_ll), "weights": [n, C], "grad": [n, C]
+        (``g_c / s_eff``; None unless want_grad), "mix_ll": [n], "bound": [n], "rounds": [n] int32, "converged": [n] bool (``bound <= tol``)}``.  A
+        positive count that no column supports gives ``mix_ll = -inf`` exactly and is left out of the weights; no NaN.  Changes nothing in the engine;
+        two calls agree bit for bit."""
+        Em, Um, Vm, D = self._ll_operands("clone_mixture", E, U, V)
+        lo, hi, n = self._cell_range(cells)
+        Cn = self.C
+        sm = None
+        if start is not None:
+            start = np.asarray(start, dtype=np.float64)
+            if start.shape != (n, Cn):
+                raise ValueError(f"clone_mixture: start is {start.shape}; expected ({n}, {Cn})")
+            sm = self._mixture_start(start, lo, hi) if n > 0 else None
+        ll = self._zeros(n, Cn) if want_ll else None
+        w, g = self._zeros(n, Cn), (self._zeros(n, Cn) if want_grad else None)
+        mll, bnd, rd = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        self._ck(self._fn("clone_mixture")(self.h, _ptr(Em), _ptr(Um), _ptr(Vm), D, int(bool(const)), _ptr(sm), int(max_iter), float(tol), lo, hi - lo, _ptr(ll),
+                                           _ptr(w), _ptr(g), _ptr(mll), _ptr(bnd), _ptr(rd)))
+        return {"ll": ll, "weights": np.ascontiguousarray(w), "grad": None if g is None else np.ascontiguousarray(g), "mix_ll": mll, "bound": bnd, "rounds": rd,
+                "converged": bnd <= float(tol)}
+
     def clone_loglik_dm(self, E, U=None, V=None, concentration=(100.,), const=True, cells=None, want_ll=True):
         """DIRICHLET-MULTINOMIAL log-likelihood of the resident cells under every clone at every concentration ``phi`` of ``concentration`` (1 to 16 finite
         values > 0), on the device in float64 (ca_clone_loglik_dm; include/clonealign_hip.h has the formula and the rules):
@@ -1101,6 +1139,18 @@ class HipGroupEngine(HipEngine):
 
     def info(self):
         return self.rank_info(0) | {"N": self.N, "group": self.group_info()}
+
+    def _mixture_start(self, start, lo, hi):
+        """ca_group_clone_mixture takes the start over ALL cells, as it takes U: the range's rows in place, the others unread."""
+        full = self._zeros(self.N, self.C)
+        if 0 <= lo <= hi <= self.N:                                  # (any other range is the library's to refuse)
+            full[lo:hi] = start
+        return full
+
+    def clone_mixture(self, E, U=None, V=None, start=None, max_iter=50, tol=1e-3, const=True, cells=None, want_ll=True, want_grad=True):
+        """``HipEngine.clone_mixture`` over the group (ca_group_clone_mixture): every rank solves the cells of the range that lie in its shard; each cell's
+        values are the single handle's, bit for bit."""
+        return super().clone_mixture(E, U, V, start=start, max_iter=max_iter, tol=tol, const=const, cells=cells, want_ll=want_ll, want_grad=want_grad)
 
     def _no(self, *a, **k):
         raise NotImplementedError("not available on a device group (use the rank engines through rank_info / a single HipEngine)")

@@ -488,6 +488,47 @@ int ca_clone_pair_loglik(ca_handle h, const double* E /* G x C */, const double*
                          int32_t with_const, const double* weights /* n_weights, each in (0, 1) */, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt,
                          double* ll /* cell_cnt x C, or NULL */, double* pair_ll /* cell_cnt x (M n_weights) */);
 
+/* The maximum-likelihood MIXTURE OF ALL CLONES per cell -- a spatial spot, a bulk sample, a contaminated droplet, an off-grid doublet or a triplet: the sum of
+ * multinomial rows of several clones is multinomial in sum_c pi_c p_n.c -- for the cells [cell_lo, cell_lo + cell_cnt): the weights pi on the simplex that
+ * maximise it, by projected Newton, with a certified bound.  Notation and arguments of ca_clone_loglik: E (G x C; further columns may be profiles that are no
+ * clone, e.g. ambient RNA), eta_ng = U_n . V_g, Z_nc = sum_g E[g][c] exp(eta_ng), s_n = sum_g y_ng; U is N x D over ALL resident cells.  Per cell, with
+ * lz = min_c log Z_nc and q_gc = E[g][c] exp(lz - log Z_nc) (every factor is at most 1, so nothing overflows):
+ *   mix_ll(pi) = sum_{g: y>0} y_g log m_g - s lz + sum_g y_g eta_g + const_n,    m_g = sum_c pi_c q_gc
+ *   g_c   = sum_{g: y>0} y_g q_gc / m_g          (so sum_c pi_c g_c = s_eff, the counts on usable entries)
+ *   H_cd  = sum_{g: y>0} y_g q_gc q_gd / m_g^2   (minus the Hessian; positive semidefinite)
+ *   bound = max_c g_c - sum_c pi_c g_c           [nats; rounded up to 0 where rounding leaves it below]
+ * mix_ll is concave in pi, so for any pi on the simplex max_pi' mix_ll(pi') - mix_ll(pi) <= bound (concavity and sum_c pi'_c = 1): a theorem, and the stop
+ * rule.  The constraint is dropped the mixSQP way: maximise phi(pi) = f(pi) - s_eff sum_c pi_c over pi >= 0 (f(t pi) = f(pi) + s_eff log t, so the maximiser
+ * has sum 1).  One round, at the current pi (sum 1):
+ *   1. evaluate g, H, mix_ll and bound; stop if bound <= tol_nats or rounds == max_iter.  The returned mix_ll, grad and bound are those of the returned
+ *      weights, from the same evaluation.
+ *   2. gamma = g - s_eff; active set {c : pi_c <= eps and gamma_c < 0}, eps = min(1e-3, max_c |pi_c - max(pi_c + gamma_c / H_cc, 0)|) (Bertsekas).
+ *   3. on the free set solve (H_FF + ridge I) d_F = gamma_F by Cholesky, ridge = 1e-12 trace(H_FF) / |F|; active components take d_c = gamma_c / H_cc.
+ *   4. trial points max(pi + t d, 0) for t = 1, 1/2, 1/4, 1/8: the largest t whose phi is finite and phi(trial) >= phi(pi) + 1e-4 gamma . (trial - pi);
+ *      if none passes (or the solve breaks down) the round takes one EM step pi_c g_c / s_eff, which never lowers f.
+ *   5. renormalise to sum 1 (phi does not decrease under it).
+ * A round keeps no state but pi -- T rounds in one call are T calls of one round, bit for bit -- and a weight that reached 0 comes back as soon as its
+ * gamma_c > 0.  start: cell_cnt x C in the problem's layout, rows on the simplex, or NULL for uniform weights.  Outputs, row = cell - cell_lo: weights
+ * (cell_cnt x C), grad (cell_cnt x C or NULL: g_c / s_eff, which is 1 on the support of an optimum and <= 1 + bound / s_eff elsewhere), mix_ll, bound_nats
+ * and rounds (cell_cnt each); ll (cell_cnt x C, or NULL): ca_clone_loglik's rows of those cells, bit for bit.  Rules:
+ *   a positive count on a gene whose every q_gc is 0 makes mix_ll exactly -inf; such entries are left out of m, g and H, and the weights and the bound are
+ *     those of the remaining entries.  Zero counts are never visited.  A cell with s_n = 0 (or no usable entry) returns the start, mix_ll = const_n, bound 0,
+ *     rounds 0.  No NaN anywhere.
+ *   with max_iter > 0 a start at which mix_ll is -inf on an otherwise usable entry (the start's zeros exclude the data) is replaced by the uniform start.
+ *   max_iter = 0 evaluates at the start, zeros included: a one-hot start reproduces ca_clone_loglik's value and (w, 1 - w) on a pair ca_clone_pair_loglik's,
+ *     to rounding.  Where the start's zeros exclude a usable entry, mix_ll is -inf, bound_nats +inf, and grad leaves those entries out.
+ *   Everything is float64; a wave per cell over its compacted non-zero counts, all rounds in one launch; every sum runs in a fixed order (no atomics): two calls
+ *     agree bit for bit, and a cell's values depend neither on the cell range it was asked in, nor on the batching, nor on its place in the launch, so a
+ *     cell-sharded group returns the single handle's bits.
+ * CA_ERR_INVALID (with a message naming the offender): everything ca_clone_loglik refuses; C > 32; max_iter < 0; tol_nats negative or non-finite; a start row
+ * with a negative or non-finite entry or whose sum is off 1 by more than 1e-9; a cell range outside [0, N]; E, weights, mix_ll, bound_nats or rounds NULL.
+ * Sharded handle: U, the cell range, start and the outputs are the local cells'; the only collective is the verdict on the input.
+ * Read-only: no variable, Adam slot or draw index changes; not from a poll hook (CA_ERR_STATE), like the other sums. */
+int ca_clone_mixture(ca_handle h, const double* E /* G x C */, const double* U /* N x D, or NULL */, const double* V /* G x D, or NULL */, int32_t D, int32_t with_const,
+                     const double* start /* cell_cnt x C on the simplex, or NULL: uniform */, int32_t max_iter, double tol_nats, int64_t cell_lo, int64_t cell_cnt,
+                     double* ll /* cell_cnt x C, or NULL */, double* weights /* cell_cnt x C */, double* grad /* cell_cnt x C, or NULL */, double* mix_ll,
+                     double* bound_nats, int32_t* rounds /* each cell_cnt */);
+
 /* DIRICHLET-MULTINOMIAL log-likelihood of the resident counts under every clone at a grid of concentrations, for the cells [cell_lo, cell_lo + cell_cnt):
  * scoring that allows for the overdispersion of the counts relative to ca_clone_loglik's multinomial.  Notation and arguments of ca_clone_loglik: E (G x C),
  * eta_ng = U_n . V_g, Z_nc = sum_g E[g][c] exp(eta_ng), s_n = sum_g y_ng, p_ngc = E[g][c] exp(eta_ng) / Z_nc; U is N x D over ALL resident cells.  For a
@@ -966,6 +1007,12 @@ int ca_group_clone_loglik(ca_group_handle g, const double* E, const double* U /*
 int ca_group_clone_pair_loglik(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
                                const double* weights, int32_t n_weights, int64_t cell_lo, int64_t cell_cnt, double* ll /* cell_cnt x C, or NULL */,
                                double* pair_ll /* cell_cnt x (M n_weights) */);
+/* ca_clone_mixture over the group: U and start (N x C, or NULL) hold ALL cells, the cell range counts the group's cells, the outputs hold the range's rows; each
+ * cell's values are the single handle's, bit for bit (every rank is called with its part of the range, an empty one included, for the verdict on the input) */
+int ca_group_clone_mixture(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
+                           const double* start /* N x C, all cells, or NULL: uniform */, int32_t max_iter, double tol_nats, int64_t cell_lo, int64_t cell_cnt,
+                           double* ll /* cell_cnt x C, or NULL */, double* weights /* cell_cnt x C */, double* grad /* cell_cnt x C, or NULL */, double* mix_ll,
+                           double* bound_nats, int32_t* rounds /* each cell_cnt */);
 /* ca_clone_loglik_dm over the group: U holds ALL cells, the cell range counts the group's cells, ll and dm_ll hold the range's rows; each cell's values are the
  * single handle's, bit for bit (every rank is called with its part of the range, an empty one included, for the verdict on the input) */
 int ca_group_clone_loglik_dm(ca_group_handle g, const double* E, const double* U /* N x D, all cells, or NULL */, const double* V, int32_t D, int32_t with_const,
