@@ -650,8 +650,9 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   CACK(dalloc(h, &h->terms_dev, 4));
   CACK(ensure_elbo_cap(h, 64));
   CACK(ensure_eps_cap(h, 1));
-  // ---- column sums and Y^T X via the streaming kernel with all-ones factors (exact for integer counts:
-  //      every per-strip partial is an integer < 2^24, the cross-strip sum is fp64)
+  // ---- column sums and Y^T X via the streaming kernel with all-ones factors (a block's four strips are summed in float32, the cross-strip
+  //      sum is fp64: exact for integer counts while a block's partial stays below 2^24 -- u8 bytes always do, and their overflow excess is added in double
+  //      below; u16 counts over 512 cells and f32 counts above 65535 need not, and colsum is then good to float32 rounding, 6e-8 relative)
   {
     // colsum: run ypass with K' = 1, psi == 1, W == 0 on temporary factor buffers
     const int cols = 1 + ((K > 0) ? P : 0);

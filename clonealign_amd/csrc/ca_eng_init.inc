@@ -251,43 +251,65 @@ int ca_clone_gene_sums(ca_handle h, const int32_t* clone_of_cell, double* Tout, 
   HIPCK(h, hipSetDevice(h->device));
   CACK(wait_y(h, true));
   const int64_t N = h->N; const int G = h->G, Gp = h->Gp, C = h->C;
-  std::vector<float> ind((size_t)N * C, 0.f), asg((size_t)N, 0.f);
-  std::vector<double> out;
-  ca_call_mem mem(h);
-  float *Fp = mem.alloc<float>(N * C), *Vp = mem.alloc<float>((int64_t)Gp * C), *YWp = mem.alloc<float>((int64_t)(h->nseg + 1) * N * C);
-  float *YTp = mem.alloc<float>((int64_t)(h->nrb + 1) * Gp * C), *csum = mem.alloc<float>((int64_t)std::max(h->n_ovf_chunk, 1) * C);
-  double* ytd = mem.alloc<double>((int64_t)Gp * C);
-  if (mem.rc != CA_OK) return mem.rc;
-  HIPCK(h, hipMemsetAsync(Vp, 0, (size_t)Gp * C * sizeof(float), h->stream));
-  const int nrb_tot = h->nrg + (h->n_ovf > 0 ? 1 : 0);
+  // the assigned cells, sorted by clone (stable: cells ascending within a clone)
+  std::vector<int64_t> start((size_t)C + 1, 0);
   for (int64_t n = 0; n < N; ++n) {
     const int c = clone_of_cell[n];
     if (c >= C) { h->err = "clone index out of range"; return CA_ERR_INVALID; }
-    if (c >= 0) { ind[(size_t)n * C + c] = 1.f; asg[n] = 1.f; }
+    if (c >= 0) start[(size_t)c + 1]++;
   }
-  // T = Y^T I  (strip partials are exact integers below 2^24 for integer counts; the cross-strip sum is fp64)
-  HIPCK(h, hipMemcpyAsync(Fp, ind.data(), ind.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  CACK(ypass_tf<0>(h, Fp, Vp, C, YWp, YTp, csum));
-  hipLaunchKernelGGL(k_colsum, dim3(cdiv((int64_t)Gp * C, 64)), dim3(1024), 0, h->stream, YTp, ytd, nrb_tot, (int64_t)Gp * C, Gp * C);
-  out.resize((size_t)G * C);
-  HIPCK(h, hipMemcpyAsync(out.data(), ytd, out.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCK(h, hipStreamSynchronize(h->stream));
-  for (int g = 0; g < G; ++g)
-    for (int c = 0; c < C; ++c) Tout[hidx(h->layout, g, c, G, C)] = out[(size_t)g * C + c];
-  // Syy = (Y^2)^T 1_assigned
-  HIPCK(h, hipMemcpyAsync(Fp, asg.data(), asg.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-  CACK(ypass_tf<3>(h, Fp, Vp, 1, YWp, YTp, csum));
-  hipLaunchKernelGGL(k_colsum, dim3(cdiv((int64_t)Gp, 64)), dim3(1024), 0, h->stream, YTp, ytd, nrb_tot, (int64_t)Gp, Gp);
-  HIPCK(h, hipMemcpyAsync(Syy, ytd, (size_t)G * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCK(h, hipStreamSynchronize(h->stream));
+  for (int c = 0; c < C; ++c) start[(size_t)c + 1] += start[(size_t)c];
+  const int64_t M = start[(size_t)C];
+  // pack = [T G x C | Syy G], summed in FLOAT64 from the resident counts: a float32 partial is exact only below 2^24, which 512 cells of a strip
+  // block pass with u16 counts, one f32 count can, and a gene's overflow entries do -- and n Syy - Sy^2 of the correlation cancels the digits
+  // a float32-accurate Syy has left.  Integer counts: every partial here is an integer, exact below 2^53.
+  std::vector<double> pack((size_t)G * C + G, 0.0);
+  ca_call_mem mem(h);
+  if (M > 0) {
+    std::vector<int64_t> rows((size_t)M), piece;
+    std::vector<int> piece_clone;
+    {
+      std::vector<int64_t> fill(start.begin(), start.end() - 1);
+      for (int64_t n = 0; n < N; ++n) { const int c = clone_of_cell[n]; if (c >= 0) rows[(size_t)fill[(size_t)c]++] = n; }
+    }
+    // pieces of the list for the blocks: at most 128 over all cells and at least 256 cells each (as the column statistics of the PCA are cut), cut at the clones
+    const int64_t per = std::max<int64_t>(256, cdiv(M, (int64_t)128));
+    for (int c = 0; c < C; ++c)
+      for (int64_t r = start[(size_t)c]; r < start[(size_t)c + 1]; r += per) { piece.push_back(r); piece_clone.push_back(c); }
+    const int np = (int)piece.size();
+    piece.push_back(M);
+    const int64_t* rows_d = mem.upload(rows);
+    const int64_t* piece_d = mem.upload(piece);
+    double* part = mem.alloc<double>((int64_t)np * 2 * G);
+    if (mem.rc != CA_OK) return mem.rc;
+    const dim3 grid(cdiv(G, CA_TB), np);
+    if (h->ystore == CA_YSTORE_U8) hipLaunchKernelGGL((k_col_listsums<uint8_t>), grid, dim3(CA_TB), 0, h->stream, (const uint8_t*)h->Y, rows_d, piece_d, G, Gp, part);
+    else if (h->ystore == CA_YSTORE_U16) hipLaunchKernelGGL((k_col_listsums<uint16_t>), grid, dim3(CA_TB), 0, h->stream, (const uint16_t*)h->Y, rows_d, piece_d, G, Gp, part);
+    else hipLaunchKernelGGL((k_col_listsums<float>), grid, dim3(CA_TB), 0, h->stream, (const float*)h->Y, rows_d, piece_d, G, Gp, part);
+    HIPCK(h, hipGetLastError());
+    std::vector<double> hp((size_t)np * 2 * G);
+    HIPCK(h, hipMemcpyAsync(hp.data(), part, hp.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));   // (the host vectors above are read by the copies until here)
+    for (int p = 0; p < np; ++p)   // pieces in list order
+      for (int g = 0; g < G; ++g) {
+        pack[(size_t)g * C + piece_clone[(size_t)p]] += hp[((size_t)p * 2 + 0) * G + g];
+        pack[(size_t)G * C + g] += hp[((size_t)p * 2 + 1) * G + g];
+      }
+    // entries held as 255 + overflow excess: put right in double from the host copy of the list, fixed (cell, gene) order
+    for (int64_t e = 0; e < h->n_ovf; ++e) {
+      const int c = clone_of_cell[h->h_orow[(size_t)e]];
+      if (c < 0) continue;
+      const double x = (double)h->h_oval[(size_t)e];
+      pack[(size_t)h->h_ocol[(size_t)e] * C + c] += x;
+      pack[(size_t)G * C + h->h_ocol[(size_t)e]] += (255.0 + x) * (255.0 + x) - 255.0 * 255.0;
+    }
+  }
   if (is_sharded(h)) {   // sharded: totals over all cells
-    std::vector<double> pack((size_t)G * C + G);
-    for (int g = 0; g < G; ++g) { for (int c = 0; c < C; ++c) pack[(size_t)g * C + c] = out[(size_t)g * C + c]; pack[(size_t)G * C + g] = Syy[g]; }
     double* scratch = mem.alloc<double>((int64_t)pack.size());
     if (mem.rc != CA_OK) return mem.rc;
     CACK(allreduce_host_vec(h, pack, scratch));
-    for (int g = 0; g < G; ++g) { for (int c = 0; c < C; ++c) Tout[hidx(h->layout, g, c, G, C)] = pack[(size_t)g * C + c]; Syy[g] = pack[(size_t)G * C + g]; }
   }
+  for (int g = 0; g < G; ++g) { for (int c = 0; c < C; ++c) Tout[hidx(h->layout, g, c, G, C)] = pack[(size_t)g * C + c]; Syy[g] = pack[(size_t)G * C + g]; }
   return CA_OK;
 }
 

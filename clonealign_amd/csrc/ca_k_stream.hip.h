@@ -225,6 +225,26 @@ __global__ void __launch_bounds__(CA_TB) k_col_logstats(const YT* __restrict__ Y
   out[((int64_t)blockIdx.y * 2 + 1) * G + g] = ss;
 }
 
+// Column sums of y and of y^2 in FLOAT64 over pieces of a cell list (ca_clone_gene_sums: the assigned cells sorted by clone, every piece
+// inside one clone's range): thread = gene as above, block column = piece [piece_start[p], piece_start[p + 1]) of the list; out
+// [pieces][2][G].  A count is below 2^24 in every storage, so y, y^2 and every partial sum of integer counts below 2^53 is exact here --
+// which the float32 strip partials of k_ypass are not, once a count passes 255 (4 x 128 rows of u16 counts, or one f32 count, reach 2^24).
+// Counts stored as 255 + overflow-list excess are corrected by the caller.
+template <typename YT>
+__global__ void __launch_bounds__(CA_TB) k_col_listsums(const YT* __restrict__ Y, const int64_t* __restrict__ rows,
+                                                        const int64_t* __restrict__ piece_start, int G, int Gp, double* __restrict__ out) {
+  const int g = (int)blockIdx.x * CA_TB + (int)threadIdx.x;
+  if (g >= G) return;
+  const int64_t i0 = piece_start[blockIdx.y], i1 = piece_start[blockIdx.y + 1];
+  double s = 0.0, ss = 0.0;
+  for (int64_t i = i0; i < i1; ++i) {
+    const double y = (double)Y[rows[i] * (int64_t)Gp + g];
+    s += y; ss += y * y;
+  }
+  out[((int64_t)blockIdx.y * 2 + 0) * G + g] = s;
+  out[((int64_t)blockIdx.y * 2 + 1) * G + g] = ss;
+}
+
 // ------------------------------------------------------------------ fit constants (once per fit)
 // One block per cell: s_n, c_n = lgamma(s_n+1) - sum_g lgamma(y+1), A_nc = sum_g xlogy(y, L_gc).
 // (the terms TF recomputes in every run of tfd$Multinomial$log_prob, R/inference-tflow.R:294-296)

@@ -427,6 +427,8 @@ int ca_init_psi_pca(ca_handle h, const double* noise, int32_t n_iter, uint64_t s
  * shipping Y back: clone_of_cell[n] in [0, C) or -1 ("unassigned", dropped at :319-320).
  *   T[g][c] = sum over cells assigned to clone c of y_ng      (G x C, problem layout)
  *   Syy[g]  = sum over assigned cells of y_ng^2
+ * Both are float64 sums in a fixed order (u8 overflow entries with their true values): T is exact for integer counts in every storage
+ * while a total stays below 2^53, Syy good to float64 rounding -- n Syy - (sum_c T)^2 of the correlation cancels most of its digits.
  * Pearson's r of (copy number of the assigned clone, counts) follows from T, Syy and the clone sizes on the host. */
 int ca_clone_gene_sums(ca_handle h, const int32_t* clone_of_cell, double* T, double* Syy);
 
