@@ -594,6 +594,8 @@ int create_impl(ca_engine* h, const ca_problem* p) {
   h->cell_lean = h->poly && variant_on(h, CA_VAR_CELL_LEAN, "CA_CELL_LEAN");
   // ... and with its backward moments gathered by fp64 MFMA per wave instead of the thread-owned chain between two block barriers (CA_VAR_CELL_MFMA): likewise
   h->cell_mfma = h->poly && variant_on(h, CA_VAR_CELL_MFMA, "CA_CELL_MFMA");
+  // ... and, for that form alone, with its head's loads issued at once and its block end as one parking step (CA_VAR_CELL_EDGE): the same bits
+  h->cell_edge = h->poly && h->cell_lean && h->cell_mfma && variant_on(h, CA_VAR_CELL_EDGE, "CA_CELL_EDGE");
   // ... and the way back from it: the stream's column jobs off the cell launch, reduction + per-gene pass + column jobs as one launch (CA_VAR_GENE_RIDE,
   // ca_polygene.hip.h); which order a pass takes is decided where it is queued (gene_ride_merges: a cell-sharded fit keeps the two launches)
   h->gene_ride = h->poly && variant_on(h, CA_VAR_GENE_RIDE, "CA_GENE_RIDE");

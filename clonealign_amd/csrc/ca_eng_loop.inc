@@ -948,7 +948,7 @@ int fused_pass(ca_engine* h, int64_t slotA, int64_t slotB, double* elbo_dst, dou
     const bool merges = gene_ride_merges(h);
     ca_yfin_args yfin_cols = yfin_ride;
     if (cols_move) yfin_ride.ncol = 0;
-    e = ca_poly_cells(h->stream, &h->pws, h->N, h->C, h->K, &cp, h->alpha_u, h->cell_part, h->dFpart, yfin_rides ? &yfin_ride : nullptr, h->cell_lean, h->cell_mfma);
+    e = ca_poly_cells(h->stream, &h->pws, h->N, h->C, h->K, &cp, h->alpha_u, h->cell_part, h->dFpart, yfin_rides ? &yfin_ride : nullptr, h->cell_lean, h->cell_mfma, h->cell_edge);
     // the ONE place that decides where the reduction of the backward moments runs: here, as a launch (with the sharded fit's riders), or inside train_bwd's launch
     h->red_pending = merges;
     if (merges) h->ycol_pending = cols_move;

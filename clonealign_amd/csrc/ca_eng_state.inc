@@ -176,6 +176,7 @@ struct ca_engine {
   // stream's blocks leave free in one round of the launch (what the pick saw), and the role's shape (groups per moment block, reducer blocks)
   bool mom_last = false, mom_ovf_first = false; int mom_free_slots = 0, mom_per = CA_MOM_PER, mom_nred = CA_MOM_NRED;
   bool cell_mfma = false;   // ... with the backward moments of its register bins gathered by fp64 MFMA per wave (CA_VAR_CELL_MFMA, k_poly_cell<CP, LEAN, true>)
+  bool cell_edge = false;   // ... lean and MFMA both: the head's loads in one round trip, the block end in one parking step (CA_VAR_CELL_EDGE, k_poly_cell<CP, true, true, true>)
   bool cell_lean = false;   // the series form's cell launch in its lean form (CA_VAR_CELL_LEAN, ca_poly.hip k_poly_cell<CP, true>)
   // CA_VAR_GENE_RIDE (ca_polygene.hip.h): the stream's column jobs leave the cell launch, and an unsharded pass runs reduction + per-gene pass + column jobs as one
   // launch from train_bwd.  red_pending: the cell launch of the look-ahead half poly_fresh refers to is queued, its reduction is not (it comes with the per-gene pass);

@@ -314,11 +314,59 @@ __device__ __forceinline__ double ca_dpp_gmax(double v) {
   v = fmax(v, ca_dpp_xor<1>(v));
   return v;
 }
+// The q(z) half of the lean epilogue on its own (CA_VAR_CELL_EDGE): log gamma and gamma of this lane's (cell, clone) from its logit alone -- the statements of
+// ca_cell_fused_group below, the same operands in the same order -- for a caller that has the logit a pass ahead and places this chain (an fp64 exp, a log, a
+// division, two lane-group reductions) beside arithmetic that does not depend on it instead of behind it.
+struct ca_cell_qz { double lg, gam; };
+template <int CP>
+__device__ __forceinline__ ca_cell_qz ca_cell_qz_half(float glf, bool ok) {
+  const double gl = ok ? (double)glf : -INFINITY;
+  const double mx = ca_dpp_gmax<CP>(gl);
+  const double ex = ok ? exp(gl - mx) : 0.0;
+  const double se = ca_dpp_gsum<CP>(ex);
+  const double lse = mx + log(se);
+  ca_cell_qz r;
+  r.lg = gl - lse;
+  r.gam = ok ? ex / se : 0.0;
+  return r;
+}
+// v + v[lane ^ 1] + ... over the wave's 64 lanes, every lane with the result, paired as ca_block_sum's butterfly pairs them (xor 1, 2, 4, 8, 16, 32: the same
+// additions, so the same bits) without its six trips through the LDS crossbar: xor 1, 2, 4 as above, xor 8 as a rotation by eight inside the row of 16, xor 16 and
+// 32 by the row and half swaps (ca_sum_xor16_32's, on the two halves of a double: both halves come back in the same order, so each pair is own and partner).
+__device__ __forceinline__ double ca_dpp_wave_sum(double v) {
+  typedef unsigned v2u __attribute__((ext_vector_type(2)));
+  v += ca_dpp_xor<1>(v);
+  v += ca_dpp_xor<2>(v);
+  v += ca_dpp_xor<4>(v);
+  {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const int lo = (int)(uint32_t)u, hi = (int)(uint32_t)(u >> 32);
+    const int rl = __builtin_amdgcn_update_dpp(lo, lo, 0x128, 0xF, 0xF, false);   // row_ror:8
+    const int rh = __builtin_amdgcn_update_dpp(hi, hi, 0x128, 0xF, 0xF, false);
+    v += __builtin_bit_cast(double, ((uint64_t)(uint32_t)rh << 32) | (uint64_t)(uint32_t)rl);
+  }
+  {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const unsigned lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
+    const v2u l = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+    v = __builtin_bit_cast(double, ((uint64_t)h.x << 32) | (uint64_t)l.x) + __builtin_bit_cast(double, ((uint64_t)h.y << 32) | (uint64_t)l.y);
+  }
+  {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const unsigned lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
+    const v2u l = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), h = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    v = __builtin_bit_cast(double, ((uint64_t)h.x << 32) | (uint64_t)l.x) + __builtin_bit_cast(double, ((uint64_t)h.y << 32) | (uint64_t)l.y);
+  }
+  return v;
+}
 template <int CP, bool WR = true,   // WR = false (mc_samples = 2, four draws in one sweep): the monitor pass's pair of samples -- sums only, no coef / d logits
-          bool LEAN = false>        // LEAN: `pre` is a ca_cell_pre_lean, D = 1 and K <= 1 (the series form's cell launch); every other caller gets the code it had
+          bool LEAN = false,        // LEAN: `pre` is a ca_cell_pre_lean, D = 1 and K <= 1 (the series form's cell launch); every other caller gets the code it had
+          bool QZ = false>          // QZ (LEAN only): log gamma and gamma come with `qz` (ca_cell_qz_half of this lane's logit), made where the caller had room for them
 __device__ __forceinline__ void ca_cell_fused_group(const ca_cell_ptrs& p, const double* la, int64_t n, int64_t N, int C, int D, int K,
                                                     double ZA, double ZB, ca_cell_acc& acc, const ca_cell_pre* pre = nullptr,
-                                                    float* cf_out = nullptr /* this lane's coef as stored (0 where none), for a caller that goes on with it */) {
+                                                    float* cf_out = nullptr /* this lane's coef as stored (0 where none), for a caller that goes on with it */,
+                                                    const ca_cell_qz* qz = nullptr) {
+  static_assert(!QZ || LEAN, "the q(z) half on its own exists for the lean form");
   const int c = threadIdx.x % CP;
   auto gmax = [](double v) {
     if constexpr (LEAN) return ca_dpp_gmax<CP>(v);
@@ -339,13 +387,18 @@ __device__ __forceinline__ void ca_cell_fused_group(const ca_cell_ptrs& p, const
   const bool okn = n < N, ok = okn && c < C;
   const int64_t nn = okn ? n : N - 1;
   const int cc = c < C ? c : C - 1;
+  ca_cell_qz z;
+  if constexpr (QZ) z = *qz;
+  else {
   const double gl = ok ? (double)(pre ? pre->gl : p.glogit[nn * C + cc]) : -INFINITY;
   const double mx = gmax(gl);
   const double ex = ok ? exp(gl - mx) : 0.0;
   const double se = gsum(ex);
   const double lse = mx + log(se);
-  const double lg = gl - lse;
-  const double gam = ok ? ex / se : 0.0;
+  z.lg = gl - lse;
+  z.gam = ok ? ex / se : 0.0;
+  }
+  const double lg = z.lg, gam = z.gam;
   const double sn = pre ? pre->sn : p.s64[nn];
   double em = 0.0;   // (LEAN: the zero it would read, times ln 2)
   if constexpr (!LEAN) em = (D > 0) ? (double)p.etamax2[nn] * CA_LN2 : 0.0;

@@ -113,6 +113,8 @@ __device__ __forceinline__ double ca_sigmoid_d(double x) { return 1.0 / (1.0 + e
 #define CA_LAB_PH_AFTER(value, blk, i) do { } while (0)
 #define CA_LAB_CELL_PH(blk, pass, i) do { } while (0)
 #define CA_LAB_CELL_PH_AFTER(value, blk, pass, i) do { } while (0)
+#define CA_LAB_CELL_EDGE(blk, i, kind) do { } while (0)
+#define CA_LAB_CELL_EDGE_END(blk) do { } while (0)
 #define CA_LAB_BLOCK_T0() do { } while (0)
 #define CA_LAB_BLOCK_END(kind, idx) do { } while (0)
 #define CA_LAB_LEAVE(label) return

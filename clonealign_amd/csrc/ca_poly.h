@@ -59,7 +59,8 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
                          const void* yfin_args /* a ca_yfin_args: the count-matrix stream's finishing sums as extra blocks of the cell launch (its row jobs alone
                                                   where CA_VAR_GENE_RIDE sends the column jobs to the launch that follows: ncol = 0), or NULL */,
                          bool lean /* CA_VAR_CELL_LEAN: the passes without their memory and LDS-crossbar round trips (k_poly_cell<CP, true>); the same bits either way */,
-                         bool mfma /* CA_VAR_CELL_MFMA: the backward moments of the register bins by fp64 MFMA per wave; the chain's sums in another fixed association */);
+                         bool mfma /* CA_VAR_CELL_MFMA: the backward moments of the register bins by fp64 MFMA per wave; the chain's sums in another fixed association */,
+                         bool edge /* CA_VAR_CELL_EDGE (lean and mfma both): the head's loads at once, the block end in one parking step; the same bits either way */);
 // The way back from the cell launch's slabs, in one of two orders (the engine picks, fused_pass / train_bwd):
 //   two launches: ca_poly_reduce (tabQ = fixed-order sums of the slabs) and, later, ca_poly_backward (per gene) -- a cell-sharded fit, whose collective sits between
 //     the two, and CA_VAR_GENE_RIDE off;

@@ -127,7 +127,18 @@ __global__ void __launch_bounds__(TB_B) k_poly_B(ca_pm_args a) {
 // 0, 1, 2, 3 through LDS (the passes' own arrays, idle by then) into the block's slab: layout and meaning as before; the order inside an MFMA is the hardware's
 // and every other order is the code's, so the sums are the same from run to run, but not the thread-owned chain's association: fp64 rounding apart.  Bins past NBR
 // (a wide exponent range) keep that chain through the slab, and with it the pass's two barriers, under a uniform test.  MFMA = false is the launch as it was.
-template <int CP, bool LEAN, bool MFMA>
+//
+// EDGE (CA_VAR_CELL_EDGE, the default; with LEAN and MFMA only) is what stands around the passes.  The head made three dependent trips to memory -- the bin count,
+// then the tables it bounds, then, behind the barrier, the first prefetch -- with the last wave's log softmax(alpha) (twelve crossbar trips, an exp and a log in
+// fp64) in front of that barrier.  None needs another's result: the workspace always holds NB tables and those past nb are never read, so alpha, the header, the
+// first prefetch and the tables of all NBL bins are issued before the first wait; every wave makes its own copy of log alpha in its own words of la[] through the
+// DPP network (xor 1, 2, 4 as the 64-lane butterfly starts; its later steps add an exact 0.0 or compare with -inf).  The block's end took five barrier-separated
+// stages; here every wave leaves its three sums (ca_dpp_wave_sum: the butterfly's pairs) and its gamma sums in words the passes never use, one barrier says that
+// the passes' arrays are idle, waves 1 - 3 park their tiles, and behind a second barrier wave 0 adds the tiles while wave 1 makes the block sums, each chain's
+// loads issued before its adds.  In a pass, the q(z) half of the epilogue (ca_cell_qz_half: it needs the prefetched logit alone) stands with bin 0, peeled out of
+// the bins' loop (nb >= 1), where it runs beside that bin's exp and Horner chains instead of behind the loop.  The same operands in the same order: EDGE = false
+// is the launch as it was, and the two agree to the bit (tests/test_gpu_cell_edge.py).
+template <int CP, bool LEAN, bool MFMA, bool EDGE = false>
 __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restrict__ hdr, const double* __restrict__ tabB, ca_cell_ptrs p,
                                                      const float* __restrict__ alpha_u, double* __restrict__ cell_part, int64_t N, int C, int K,
                                                      float* __restrict__ dF /*[N]*/, double* __restrict__ Qpart /*[grid][nb][R+2][C]*/, int ncb, ca_yfin_args yfin) {
@@ -140,6 +151,7 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
   if ((int)blockIdx.x >= ncb) {
     const int e = (int)blockIdx.x - ncb;
     const int ncolblk = (yfin.ncol + CA_TB / 64 - 1) / (CA_TB / 64);
+    CA_LAB_CELL_EDGE(blockIdx.x, 0, e < ncolblk ? 3 : 2);
     if (e < ncolblk) {
       const int job = e * (CA_TB / 64) + (int)(threadIdx.x >> 6);
       if (job < yfin.ncol) ca_yfin_col_wave(yfin, job);
@@ -147,8 +159,10 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
       __shared__ double ca_yfin_sm[CA_TB / 64];
       ca_yfin_row_block(yfin, e - ncolblk, ca_yfin_sm);
     }
+    CA_LAB_CELL_EDGE_END(blockIdx.x);
     return;
   }
+  CA_LAB_CELL_EDGE(blockIdx.x, 0, 1);
   constexpr int CPB = CA_TB / CP;             // cells per pass of the block
   constexpr int RQ = R + 2;                   // moments 0 .. R + 1 (the derivative of q needs one more)
   constexpr int NBR = 4;                      // bins whose moments a thread keeps in registers (the usual case: one to three bins); the rest go through its slab
@@ -163,13 +177,50 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
   // and from global memory those loads -- not the arithmetic -- were what a pass took
   constexpr int NBL = CA_PL_NBL;
   __shared__ double s_tb[NBL][(R + 1) * 16];
-  const int nb = hdr->nb;
+  static_assert(!EDGE || (LEAN && MFMA), "the head and block end of CA_VAR_CELL_EDGE exist for the lean MFMA form");
+  using pre_t = typename std::conditional<LEAN, ca_cell_pre_lean, ca_cell_pre>::type;
+  using x_t = typename std::conditional<LEAN, float, double>::type;
+  [[maybe_unused]] x_t x_head = 0; [[maybe_unused]] pre_t pre_head = {};
+  int nb_; [[maybe_unused]] double vlo_ = 0.0, delta_ = 0.0;
+  if constexpr (EDGE) {
+    // every load of the head before the first wait: alpha (wanted first), the header, the first pass's operands, the tables of all NBL bins (in bounds whatever nb:
+    // the workspace holds NB of them; those past nb are staged and never read)
+    const int t_ = threadIdx.x, c8 = t_ & 7;
+    const float auf = alpha_u[c8 < C ? c8 : C - 1];
+    nb_ = hdr->nb; vlo_ = hdr->vlo; delta_ = hdr->delta;
+    if ((int64_t)blockIdx.x * CPB < N) {   // (blockIdx.x < ngroups: a block without a pass loads no cell)
+      const int64_t n_ = (int64_t)blockIdx.x * CPB + t_ / CP, nn_ = n_ < N ? n_ : N - 1;
+      const int cc_ = t_ % CP < C ? t_ % CP : C - 1;
+      x_head = (x_t)p.F[nn_];
+      pre_head.gl = p.glogit[nn_ * C + cc_]; pre_head.sn = p.s64[nn_]; pre_head.Anc = p.A[nn_ * C + cc_];
+      pre_head.cn = p.cn[nn_];
+    }
+    constexpr int NST = (NBL < NB ? NBL : NB) * (R + 1) * 16, NSL = (NST + CA_TB - 1) / CA_TB;
+    double stg[NSL];
+#pragma unroll
+    for (int j = 0; j < NSL; ++j) { const int i = j * CA_TB + t_; stg[j] = tabB[i < NST ? i : NST - 1]; }
+    for (int i = t_; i < CPB * NB; i += CA_TB) (&s_eb[0][0])[i] = 0.0;   // (bins past nb: zeros, so that the gather needs no bounds)
+    // log softmax(alpha), a copy per wave in la[8 wave ..]: lane groups of eight, one lane per clone; ca_log_softmax_alpha's additions (its butterfly pairs xor 1, 2, 4
+    // first; lanes past C hold -inf / 0.0, so every later step compares with -inf or adds an exact 0.0)
+    const double au = c8 < C ? (double)auf : -INFINITY;
+    double mx = au;
+    mx = fmax(mx, ca_dpp_xor<1>(mx)); mx = fmax(mx, ca_dpp_xor<2>(mx)); mx = fmax(mx, ca_dpp_xor<4>(mx));
+    double se = c8 < C ? exp(au - mx) : 0.0;
+    se += ca_dpp_xor<1>(se); se += ca_dpp_xor<2>(se); se += ca_dpp_xor<4>(se);
+    if ((t_ & 63) < 8 && c8 < C) la[(t_ >> 6) * 8 + c8] = au - (mx + log(se));
+#pragma unroll
+    for (int j = 0; j < NSL; ++j) { const int i = j * CA_TB + t_; if (i < NST) (&s_tb[0][0])[i] = stg[j]; }
+  } else {
+  nb_ = hdr->nb;
   ca_log_softmax_alpha(alpha_u, C, la);
   for (int i = threadIdx.x; i < CPB * NB; i += CA_TB) (&s_eb[0][0])[i] = 0.0;   // (bins past nb: zeros, so that the gather needs no bounds)
-  for (int i = threadIdx.x; i < (nb < NBL ? nb : NBL) * (R + 1) * 16; i += CA_TB) (&s_tb[0][0])[i] = tabB[i];
+  for (int i = threadIdx.x; i < (nb_ < NBL ? nb_ : NBL) * (R + 1) * 16; i += CA_TB) (&s_tb[0][0])[i] = tabB[i];
+  }
+  const int nb = nb_;
   __syncthreads();
   const int t = threadIdx.x, c = t % CP, slot = t / CP;
-  const double vlo = hdr->vlo, delta = hdr->delta;
+  double vlo, delta;
+  if constexpr (EDGE) { vlo = vlo_; delta = delta_; } else { vlo = hdr->vlo; delta = hdr->delta; }
   // backward moments: thread t < (R + 2) C owns (k, clone) = (t / C, t % C) of EVERY bin -- nobody else adds to its outputs, cells are added in cell order
   const bool qown = t < RQ * C;
   const int qk = qown ? t / C : 0, qc = qown ? t % C : 0;
@@ -191,9 +242,7 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
   const int64_t ngroups = (N + CPB - 1) / CPB;
   const int cc = c < C ? c : C - 1;
   // what the epilogue reads for this lane's (cell, clone) that nothing here produces: loaded a pass AHEAD, beside the arithmetic of the current one
-  using pre_t = typename std::conditional<LEAN, ca_cell_pre_lean, ca_cell_pre>::type;
-  // (LEAN: x travels as the float it is and widens at the top of its own pass -- widened beside its load, the prefetch was waited for where it was issued)
-  using x_t = typename std::conditional<LEAN, float, double>::type;
+  // (pre_t.  LEAN: x travels as the float it is, x_t, and widens at the top of its own pass -- widened beside its load, the prefetch was waited for where it was issued)
   auto load_pass = [&](int64_t grp, x_t& x_, pre_t& pre_) {
     const int64_t n_ = grp * CPB + slot, nn_ = n_ < N ? n_ : N - 1;
     x_ = (x_t)p.F[nn_];
@@ -201,8 +250,10 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
     if constexpr (LEAN) pre_.cn = p.cn[nn_];
   };
   x_t x_next = 0; pre_t pre_next = {};
-  if ((int64_t)blockIdx.x < ngroups) load_pass(blockIdx.x, x_next, pre_next);
+  if constexpr (EDGE) { x_next = x_head; pre_next = pre_head; }   // (issued with the head's other loads)
+  else if ((int64_t)blockIdx.x < ngroups) load_pass(blockIdx.x, x_next, pre_next);
   [[maybe_unused]] int pass = 0;   // (the timing lab's stamps)
+  CA_LAB_CELL_EDGE(blockIdx.x, 1, 0);
   for (int64_t grp = blockIdx.x; grp < ngroups; grp += ncb, ++pass) {
     CA_LAB_CELL_PH(blockIdx.x, pass, 0);
     const int64_t n = grp * CPB + slot;
@@ -210,10 +261,6 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
     if constexpr (LEAN) pre.x = x;
     if (grp + ncb < ngroups) load_pass(grp + ncb, x_next, pre_next);
     double ZA = 0.0, ZB = 0.0, dZB = 0.0;
-    for (int b = 0; b < nb; ++b) {
-      const double vb = vlo + ((double)b + 0.5) * delta;
-      const double e = exp(x * vb);
-      double pa, pb, dpb = 0.0;
 #define CA_PL_HORNER(TB)                                                  \
       pa = (TB)[R * 16 + cc]; pb = (TB)[R * 16 + 8 + cc];                 \
       _Pragma("unroll 10")                                                \
@@ -222,12 +269,26 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
         pa = pa * x + (TB)[k * 16 + cc];                                  \
         pb = pb * x + (TB)[k * 16 + 8 + cc];                              \
       }
-      if (b < NBL) { CA_PL_HORNER(s_tb[b]) }                              // (LDS)
-      else { const double* tb = tabB + ((int64_t)b * (R + 1)) * 16; CA_PL_HORNER(tb) }
-#undef CA_PL_HORNER
-      ZA += e * pa; ZB += e * pb; dZB += e * (vb * pb + dpb);
-      if (c == 0) s_eb[slot][b] = e;
+#define CA_PL_BIN(b)                                                      \
+    {                                                                     \
+      const double vb = vlo + ((double)(b) + 0.5) * delta;                \
+      const double e = exp(x * vb);                                       \
+      double pa, pb, dpb = 0.0;                                           \
+      if ((b) < NBL) { CA_PL_HORNER(s_tb[b]) }              /* (LDS) */   \
+      else { const double* tb = tabB + ((int64_t)(b) * (R + 1)) * 16; CA_PL_HORNER(tb) } \
+      ZA += e * pa; ZB += e * pb; dZB += e * (vb * pb + dpb);             \
+      if (c == 0) s_eb[slot][b] = e;                                      \
     }
+    [[maybe_unused]] ca_cell_qz qz;
+    if constexpr (EDGE) {   // bin 0 (nb >= 1) as straight-line code, and beside it the q(z) half of the epilogue: it needs the prefetched logit alone
+      qz = ca_cell_qz_half<CP>(pre.gl, n < N && c < C);
+      CA_PL_BIN(0)
+      for (int b = 1; b < nb; ++b) CA_PL_BIN(b)
+    } else {
+    for (int b = 0; b < nb; ++b) CA_PL_BIN(b)
+    }
+#undef CA_PL_BIN
+#undef CA_PL_HORNER
     CA_LAB_CELL_PH_AFTER(dZB, blockIdx.x, pass, 1);
     if constexpr (LEAN) {   // x^k: every lane runs the chain, keeps its own k = c, c + CP, ... by selects and stores them without a condition
       double xk = 1.0, keep[NXK];
@@ -243,6 +304,8 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
     }
     CA_LAB_CELL_PH(blockIdx.x, pass, 2);
     float cff = 0.f;
+    if constexpr (EDGE) ca_cell_fused_group<CP, true, true, true>(p, la + (t >> 6) * 8 /* the wave's own copy */, n, N, C, 1, K, ZA, ZB, acc, &pre, &cff, &qz);
+    else
     ca_cell_fused_group<CP, true, LEAN>(p, la, n, N, C, 1, K, ZA, ZB, acc, &pre, &cff);
     // this lane's coef as the epilogue stored it (float: what the matrix-core way back reads as well); d/dF = sum_c coef dZ/dx
     const double cf = (double)cff;
@@ -313,6 +376,63 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
     __syncthreads();
     CA_LAB_CELL_PH(blockIdx.x, pass, 6);
   }
+  CA_LAB_CELL_EDGE(blockIdx.x, 2, 0);
+  if constexpr (EDGE) {
+    // The block end in one parking step.  Before any barrier every wave leaves what it owes where the passes never write: its three sums (the butterfly's
+    // additions, ca_dpp_wave_sum) in la[32 ..], behind the four copies of log alpha, and its lanes' gamma sums in sm.  The first barrier says that every wave is
+    // past its last pass, so the passes' arrays are idle: waves 1, 2, 3 park their tiles there.  Behind the second, wave 0 adds the tiles to its own (lane for lane
+    // in the tile map, wave order) and stores the slab, and wave 1 makes the block sums of ca_cell_fused_finish -- waves 0, 1, 2, 3; cells 0 .. CPB - 1 from 0.0 --
+    // its loads sixteen at a time in front of their adds.
+    constexpr int QW = RQ * NBR * CP;   // one wave's tiles: [k][bin CP + clone]
+    static_assert(CPB * NB >= QW && CPB * XS >= QW && NBL * (R + 1) * 16 >= QW, "a wave's tiles fit each of the three arrays");
+    static_assert(32 + 3 * (CA_TB / 64) <= 64, "the waves' sums behind the copies of log alpha");
+    const double r0 = ca_dpp_wave_sum(acc.ee), r1 = ca_dpp_wave_sum(acc.pr), r2 = ca_dpp_wave_sum(acc.q);
+    if ((t & 63) == 0) { la[32 + 3 * wv + 0] = r0; la[32 + 3 * wv + 1] = r1; la[32 + 3 * wv + 2] = r2; }
+    sm[t] = acc.gsumc;
+    __syncthreads();
+    double* const p1 = &s_eb[0][0], * const p2 = &s_xp[0][0], * const p3 = &s_tb[0][0];
+    double* const pw = wv == 1 ? p1 : (wv == 2 ? p2 : p3);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < NCT; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int k = 16 * i + 4 * r + mk;
+          if (wv > 0 && k < RQ) pw[k * (NBR * CP) + j * 16 + mrow] = qm[i][j][r];   // (column j 16 + mrow = bin CP + clone)
+        }
+    __syncthreads();
+    if (wv == 0) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NCT; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int k = 16 * i + 4 * r + mk, col = j * 16 + mrow, b = j * BPT + mbl;
+            if (k < RQ && b < nb && mcl < C) mine[(b * RQ + k) * C + mcl] = ((qm[i][j][r] + p1[k * (NBR * CP) + col]) + p2[k * (NBR * CP) + col]) + p3[k * (NBR * CP) + col];
+          }
+    } else if (wv == 1) {
+      const int l = t & 63, W_ = 3 + C;
+      if (l < C) {
+        double a = 0.0;
+#pragma unroll
+        for (int i0 = 0; i0 < CPB; i0 += 16) {   // (sixteen loads, then their adds: cells 0 .. CPB - 1 in order)
+          double g[16];
+#pragma unroll
+          for (int i = 0; i < 16; ++i) g[i] = sm[(i0 + i) * CP + l];
+#pragma unroll
+          for (int i = 0; i < 16; ++i) a += g[i];
+        }
+        cell_part[(int64_t)blockIdx.x * W_ + 3 + l] = a;
+      } else if (l >= 8 && l < 11) {
+        const double w0 = la[32 + l - 8], w1 = la[35 + l - 8], w2 = la[38 + l - 8], w3 = la[41 + l - 8];
+        cell_part[(int64_t)blockIdx.x * W_ + l - 8] = ((w0 + w1) + w2) + w3;
+      }
+    }
+    CA_LAB_CELL_EDGE_END(blockIdx.x);
+    return;
+  }
   ca_cell_fused_finish<CP>(acc, sm, cell_part, blockIdx.x, C);
   if constexpr (MFMA) {   // the four waves' tiles, added in wave order, into the block's slab
     // Waves 1, 2, 3 park theirs in LDS arrays of the passes, which nobody reads any more (every wave is past the barriers of ca_cell_fused_finish, so past its
@@ -346,6 +466,7 @@ __global__ void __launch_bounds__(CA_TB) k_poly_cell(const ca_poly_hdr* __restri
 #pragma unroll
     for (int b = 0; b < NBR; ++b) if (b < nb) mine[(b * RQ + qk) * C + qc] = qa[b];
   }
+  CA_LAB_CELL_EDGE_END(blockIdx.x);
 }
 
 // ---- fixed-order sums of the block partials: one wave per output, lanes stride over the blocks, then the wave's tree (same order every time) --------
@@ -467,7 +588,7 @@ hipError_t ca_poly_moments(hipStream_t st, const ca_poly_ws* w, const float* V, 
 }
 
 hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, int K, const void* cell_ptrs, const float* alpha_u, double* cell_part, float* dF,
-                         const void* yfin_args, bool lean, bool mfma) {
+                         const void* yfin_args, bool lean, bool mfma, bool edge) {
   const ca_cell_ptrs& p = *static_cast<const ca_cell_ptrs*>(cell_ptrs);
   ca_yfin_args yfin;
   if (yfin_args) memcpy(&yfin, yfin_args, sizeof(yfin)); else memset(&yfin, 0, sizeof(yfin));
@@ -476,16 +597,21 @@ hipError_t ca_poly_cells(hipStream_t st, const ca_poly_ws* w, int64_t N, int C, 
   const int nextra = yfin_args ? cdiv_i(yfin.ncol, CA_TB / 64) + yfin.nrow : 0;
   const dim3 grid(w->n_cell_blocks + nextra);
 #define CA_PCELL(CPV, LV) do { if (mfma) CA_PCELL_(CPV, LV, true); else CA_PCELL_(CPV, LV, false); } while (0)
-#define CA_PCELL_(CPV, LV, MV) hipLaunchKernelGGL((k_poly_cell<CPV, LV, MV>), grid, dim3(CA_TB), 0, st, w->hdr, w->tabB, p, alpha_u, cell_part, N, C, K, dF, w->Qpart, \
+#define CA_PCELL_(CPV, LV, MV) CA_PCELL__(CPV, LV, MV, false)
+#define CA_PCELL__(CPV, LV, MV, EV) hipLaunchKernelGGL((k_poly_cell<CPV, LV, MV, EV>), grid, dim3(CA_TB), 0, st, w->hdr, w->tabB, p, alpha_u, cell_part, N, C, K, dF, w->Qpart, \
                                          w->n_cell_blocks, yfin)
+  if (edge && !(lean && mfma)) return hipErrorInvalidValue;   // (the form exists for the lean MFMA launch: the engine asks for it nowhere else)
   if (lean) {   // (3 .. 8 clones: ca_poly_ok)
     if (K > 1) return hipErrorInvalidValue;   // (the lean epilogue takes psi of the prior term from x: one latent dimension, which is all ca_poly_ok admits)
+    if (edge) { if (CP == 4) CA_PCELL__(4, true, true, true); else CA_PCELL__(8, true, true, true); }
+    else
     if (CP == 4) CA_PCELL(4, true); else CA_PCELL(8, true);
   } else {
     if (CP == 4) CA_PCELL(4, false); else CA_PCELL(8, false);
   }
 #undef CA_PCELL
 #undef CA_PCELL_
+#undef CA_PCELL__
   return hipGetLastError();
 }
 
@@ -542,5 +668,9 @@ hipError_t ca_poly_backward_merged(hipStream_t st, const ca_poly_ws* w, const fl
 #ifdef CA_LAB   // timing-lab builds only: reader of the cell passes' phase stamps (tools/lab/ca_lab_hooks.inc, tools/cell_stamps.py)
 extern "C" int ca_lab_read_cell_stamps(unsigned long long* out, int n_words) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(ca_series::ca_lab_stamps4), (size_t)n_words * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
+}
+// ... and of the block-level stamps of every block of the cell launch (tools/cell_edges.py)
+extern "C" int ca_lab_read_cell_edges(unsigned long long* out, int n_words) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(ca_series::ca_lab_stamps5), (size_t)n_words * sizeof(unsigned long long)) == hipSuccess ? 0 : 2;
 }
 #endif

@@ -380,7 +380,7 @@ int ca_get_info(ca_handle h, ca_info* i) {
   i->fwd_balanced = h->fwd_bal ? h->bal_q : 0;
   i->fwd_series = h->poly ? 1 : 0; i->series_passes = h->n_series; i->series_fallbacks = h->n_series_fallback;
   i->mom_ride = h->mom_ride ? 1 : 0;
-  i->cell_lean = h->cell_lean ? 1 : 0; i->cell_mfma = h->cell_mfma ? 1 : 0;
+  i->cell_lean = h->cell_lean ? 1 : 0; i->cell_mfma = h->cell_mfma ? 1 : 0; i->cell_edge = h->cell_edge ? 1 : 0;
   i->mom_last = h->mom_last ? 1 : 0; i->mom_free_slots = h->mom_free_slots;
   i->gene_ride = gene_ride_merges(h) ? 1 : 0;
   i->fold_gsum = (h->fold_gsum && !is_sharded(h)) ? 1 : 0; i->yfin_split = (h->yfin_split && !is_sharded(h)) ? 1 : 0;

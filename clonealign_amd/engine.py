@@ -26,7 +26,7 @@ YSTORE_NAME = {v: k for k, v in YSTORE.items()}
 KERNEL_NAMES = ("fwd", "bwd", "ypass", "cell", "other")
 # ca_variant bits (ca_options.variant_off: a set bit switches the variant OFF) and ca_tune_id slots
 VARIANTS = {"fused": 1 << 0, "fwd_mfma": 1 << 1, "fwd_cell": 1 << 2, "bwd_mfma": 1 << 3, "tail_fuse": 1 << 4, "async_y": 1 << 5,
-            "pre": 1 << 6, "pair_elbo": 1 << 7, "prep_fast": 1 << 8, "update_merge": 1 << 9, "p2p": 1 << 10, "fold_gsum": 1 << 11, "y_ride": 1 << 12, "ride_seq": 1 << 13, "y_mfma1": 1 << 14, "yfin_ride": 1 << 15, "p2p_ride": 1 << 16, "run_gate": 1 << 17, "s2_fuse": 1 << 18, "fwd_bal": 1 << 19, "bwd_tl3": 1 << 20, "series": 1 << 21, "y4": 1 << 22, "mom_ride": 1 << 23, "cell_lean": 1 << 24, "mom_last": 1 << 25, "cell_mfma": 1 << 26, "y2": 1 << 27, "gene_ride": 1 << 28}
+            "pre": 1 << 6, "pair_elbo": 1 << 7, "prep_fast": 1 << 8, "update_merge": 1 << 9, "p2p": 1 << 10, "fold_gsum": 1 << 11, "y_ride": 1 << 12, "ride_seq": 1 << 13, "y_mfma1": 1 << 14, "yfin_ride": 1 << 15, "p2p_ride": 1 << 16, "run_gate": 1 << 17, "s2_fuse": 1 << 18, "fwd_bal": 1 << 19, "bwd_tl3": 1 << 20, "series": 1 << 21, "y4": 1 << 22, "mom_ride": 1 << 23, "cell_lean": 1 << 24, "mom_last": 1 << 25, "cell_mfma": 1 << 26, "y2": 1 << 27, "gene_ride": 1 << 28, "cell_edge": 1 << 29}
 VARIANTS_ON = {"y_mfma2": 1 << 0, "async_small": 1 << 1, "y_mfma1": 1 << 2, "fold_always": 1 << 3, "ride_seq": 1 << 4, "p2p_same_device": 1 << 5, "run_fwd": 1 << 6, "bal_tiles": 1 << 7, "series": 1 << 8, "y4": 1 << 9, "mom_last": 1 << 10, "y2": 1 << 11}      # ca_variant_on: opt-in variants
 OPT_VERBOSE = 0x80000000
 TUNE = {"gsplit": 0, "fsplit": 1, "fc_tl": 2, "fc_nbig": 3, "csplit": 4, "csplit_m": 5, "tr": 6, "rg": 7}
@@ -129,7 +129,8 @@ class CaInfo(C.Structure):
                 ("update_merge", C.c_int32), ("fwd_balanced", C.c_int32), ("fwd_series", C.c_int32), ("y_stream_bits", C.c_int32),
                 ("series_passes", C.c_int64), ("series_fallbacks", C.c_int64), ("mom_ride", C.c_int32), ("cell_lean", C.c_int32),
                 ("mom_last", C.c_int32), ("mom_free_slots", C.c_int32), ("cell_mfma", C.c_int32),
-                ("y_stream_n2", C.c_int32), ("y_stream_esc", C.c_int64), ("y_stream_bytes", C.c_int64), ("gene_ride", C.c_int32)]
+                ("y_stream_n2", C.c_int32), ("y_stream_esc", C.c_int64), ("y_stream_bytes", C.c_int64), ("gene_ride", C.c_int32),
+                ("cell_edge", C.c_int32)]
 
 
 class CaGroupInfo(C.Structure):

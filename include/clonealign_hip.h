@@ -151,6 +151,11 @@ enum ca_variant {
                                  inside it through tagged words (ca_polygene.hip.h) -- a launch and a kernel boundary less per iteration; a cell-sharded fit keeps
                                  reduction and per-gene pass apart (its collective sits between them) and carries the column sums on the reduction launch.  The same
                                  additions in the same order: the same bits.  Off: cell launch, k_poly_red and k_poly_gene as they were */
+  CA_VAR_CELL_EDGE = 1 << 29, /* the series form's cell launch (lean passes, MFMA gather) with what stands around its passes off their critical path: every load of a
+                                 block's head (first prefetch, bin geometry, the bins' tables, alpha) issued before the first wait, and the block's end as one parking
+                                 step -- every wave leaves its sums and tiles in the passes' idle LDS arrays at once, and after one barrier the finishing adds are
+                                 shared between the waves.  Every sum keeps its operands and its order: the same bits.  Off: the launch as it was
+                                 (k_poly_cell<CP, true, true, false>) */
   CA_VAR_RIDE_SEQ = 1 << 13 /* (no effect: it was the off-switch of CA_VARX_RIDE_SEQ, whose code is deleted; the bit keeps its value, accepted and ignored) */
 };
 /* Opt-in variants (bits of ca_options.variant_on).  Those marked RETIRED were measured slower than what ships (rounds 2-5: DESIGN_HISTORY.md, profiles/) and their
@@ -256,6 +261,7 @@ typedef struct ca_info {
   int64_t y_stream_bytes;    /* bytes that launch reads per pass: its image plus its escape list */
   int32_t gene_ride;         /* 1: a series pass of this engine runs reduction, per-gene pass and the stream's column sums as one launch (CA_VAR_GENE_RIDE); 0: as launches
                                 of their own (the switch off, no series form, or a cell-sharded fit) */
+  int32_t cell_edge;         /* 1: the series form's cell launch issues its head's loads at once and ends its blocks in one parking step (CA_VAR_CELL_EDGE) */
 } ca_info;
 enum ca_transport { CA_TRANSPORT_NONE = 0, CA_TRANSPORT_RCCL = 1, CA_TRANSPORT_HOST = 2, CA_TRANSPORT_P2P = 3 };
 

@@ -27,6 +27,13 @@ __device__ unsigned long long ca_lab_stamps3[2048 * 4];
 __device__ unsigned long long ca_lab_stamps4[64 * 8 * 8];
 #define CA_LAB_CELL_PH(blk, pass, i) do { if (threadIdx.x == 0 && (blk) < 64 && (pass) < 8) ca_lab_stamps4[((blk) * 8 + (pass)) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 #define CA_LAB_CELL_PH_AFTER(value, blk, pass, i) do { asm volatile("" ::"v"(value)); CA_LAB_CELL_PH(blk, pass, i); } while (0)
+// block-level stamps of EVERY block of the series form's cell launch (tools/cell_edges.py), the 100 MHz clock all compute units share: word i of block blk --
+// cell blocks (kind 1): 0 block start, 1 first pass begins (head done), 2 last pass ends, 3 block returns; finisher blocks (kind 2 row jobs, 3 column jobs): 0 start,
+// 3 return -- and the kind in word 4.  One clock read and one store by thread 0 each.
+__device__ unsigned long long ca_lab_stamps5[4096 * 8];
+#define CA_LAB_CELL_EDGE(blk, i, kind) do { if (threadIdx.x == 0 && (blk) < 4096) { ca_lab_stamps5[(blk) * 8 + (i)] = __builtin_amdgcn_s_memrealtime(); if ((i) == 0) ca_lab_stamps5[(blk) * 8 + 4] = (kind); } } while (0)
+// (the return stamp behind a block barrier: the block's last wave, not thread 0's)
+#define CA_LAB_CELL_EDGE_END(blk) do { __syncthreads(); CA_LAB_CELL_EDGE(blk, 3, 0); } while (0)
 // every block of the merged forward launch leaves {start, end, kind << 32 | index, HW_ID | XCC_ID << 32}
 __device__ unsigned long long ca_lab_stamps[8192 * 4];
 #define CA_LAB_BLOCK_T0() const unsigned long long st0_ = __builtin_amdgcn_s_memrealtime()
